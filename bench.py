@@ -13,18 +13,25 @@ Worlds are independent: each rank owns its own 4096 worlds (weak scaling, no col
 path); the only collectives are the timing barrier and the MAX over ranks.
 
 Timing -- STATIONARY: after the W warm-up steps the worlds (state rows, goal lists, robot rows) are snapshotted; the K
-steps are captured once into a HIP graph (untimed); the timed region -- [untimed: restore the snapshot] barrier +
-synchronize | ONE graph launch = exactly K steps | synchronize + barrier -- is repeated R times (`timing_repeats`,
-default 50), so every repeat times the SAME trajectory segment (Gym steps W .. W+K of the episode that starts at the
-reset: with W = 20, K = 200 that is the span of a whole reference episode, time_limit 50 s = 200 Gym steps).
-`ms_per_step` is the MEDIAN over the repeats of (MAX over ranks of the elapsed wall time) / K; HIP events on the launch
-stream around every replay give the kernel duration of the same samples (mean and median reported; kernel <= wall).
+steps are captured once (untimed) into HIP graphs of at most GRAPH_STEPS steps and replayed untimed for GRAPH_WARM_S (working
+clocks; the restore undoes them); the timed region -- [untimed: restore the snapshot] barrier + synchronize | graph replays
+= exactly K steps | synchronize + barrier -- runs R times (`--repeats`,
+default 1: a plain run times exactly the K steps `--steps` asks for), every repeat over the SAME trajectory segment (Gym
+steps W .. W+K of the episode that starts at the reset: with W = 20, K = 200 that is the span of a whole reference episode,
+time_limit 50 s = 200 Gym steps).  `ms_per_step` is the MEDIAN over the repeats of (MAX over ranks of the elapsed wall
+time) / K; HIP events on the launch stream around every timed region give the kernel duration of the same samples.
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` if asked (what the timed path computed in its
+last step: the worlds' state rows, goal lists and robot rows as a caller of CrowdWorlds.step reads them, float32, rank 0's
+shard, a fixed seeded sample of worlds when they exceed DUMP_LIMIT_BYTES) and prints ONE JSON line.  Everything else --
+the copy bandwidth, roofline and PMC figures, other_configs, cpu_baseline, gym_step, the finite-state check and the full
+file -- runs only with `--full`.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): bench.py starts its own N ranks -- N fresh child processes, one
 per GPU, before this process imports torch or touches HIP -- relays rank 0's line and exits with the children's worst exit code
 (launch_ranks).  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks the launcher made are used as they are.
 
-Prints ONE COMPACT JSON line (< 4 KB: compact_line) on rank 0; the full blocks (every other_configs roofline, the PMC figures and
+With `--full`, prints ONE COMPACT JSON line (< 4 KB: compact_line) on rank 0; the full blocks (every other_configs roofline, the PMC figures and
 their sources) go to gpurun_out/bench_full.json and to stderr.  The line carries
   roofline      algorithmic bytes per launch / average kernel duration against the 8 TB/s HBM3E peak (the contract's
                 figure: a NORMALISED ALGORITHMIC THROUGHPUT -- the 20 fused substeps keep the state in registers / LDS,
@@ -71,6 +78,11 @@ SIMDS, CLOCK_HZ = 256 * 4, 2.4e9
 VALU_CLASS_CYCLES = {"fma": 2.2, "other": 4.1, "trans": 8.2}
 CPU_ROWS = ("cfg2", "cfg4_first20", "cfg4_dense", "cfg5_shard", "moussaid", "cfg3_new_guo", "robot26", "n30", "peragent", "n15", "n40")   # other_configs rows that get their own CPU figure (cfg5 = 8 x its shard)
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "pmc_summary.json")
+# steps per captured graph: K steps are replayed as K // GRAPH_STEPS copies of one graph and a remainder graph, so capture time and
+# the untimed upload replay stay bounded whatever K is (one graph launch per 1000 steps: ~30 ms of kernels at the headline)
+GRAPH_STEPS = 1000
+GRAPH_WARM_S = 0.25             # untimed graph replays before the timed region (restored away), so that it starts at working clocks
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: above this, a fixed seeded sample of the worlds is written
 
 
 def parse(argv=None):
@@ -78,7 +90,10 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=50, help="timed replays of the K-step graph (median reported)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of K steps each, every one from the post-warm-up worlds (median reported)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: roofline / PMC figures, other_configs, "
+                                                        "cpu_baseline, gym_step, finite-state check, the full result file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what they computed as DIR/<name>.npy (float32)")
     ap.add_argument("--worlds", type=int, default=4096, help="worlds per GPU (weak scaling)")
     ap.add_argument("--total-worlds", type=int, default=None, help="worlds of the whole job, split evenly over the ranks (strong scaling)")
     ap.add_argument("--agents", type=int, default=25)
@@ -94,10 +109,10 @@ def parse(argv=None):
     ap.add_argument("--per-agent-params", action="store_true", help="every human its own (jittered) parameter row: all_params_equal = False")
     ap.add_argument("--orca-math", default="default", choices=["default", "exact", "fast", "fma"], help="cs_worlds.orca_math of ORCA worlds (default: CROWDSTEP_ORCA_MATH, else exact -- the build that equals the restatement bit for bit)")
     ap.add_argument("--no-restore", action="store_true", help="let the worlds evolve from replay to replay (the round-2 protocol) instead of restoring the snapshot")
-    ap.add_argument("--eager", action="store_true", help="launch every step from Python (default: one HIP graph of K steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-gym-step", action="store_true", help="skip the device-resident Gym step figures (gym_step)")
+    ap.add_argument("--eager", action="store_true", help="launch every step from Python (default: HIP graph replays, K steps in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle figures")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the other configurations")
+    ap.add_argument("--no-gym-step", action="store_true", help="(--full) skip the device-resident Gym step figures (gym_step)")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"), help="where the full (uncompacted) result goes")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank: exercises the N > 1 code path on a one-GPU box")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -396,21 +411,36 @@ class Runner:
                 wall.append(time.perf_counter() - t0)
                 kern.append(float(np.mean([starts[k].elapsed_ms(stops[k]) for k in range(steps)])))
         else:
-            # the K steps are captured once into a HIP graph (untimed) and replayed with ONE launch per timed region:
-            # no per-launch host gap; HIP events on the launch stream bracket the K kernels of every replay
-            with _lib.Graph.capture(self.stream) as graph:
-                for k in range(steps):
-                    cw.step(dt, n_sub, action)
-            graph.launch()                      # one untimed replay (first launch of an instantiated graph uploads it)
+            # the K steps are captured once into HIP graphs of at most GRAPH_STEPS steps (untimed) and replayed back to back on
+            # one stream: no per-launch host gap; HIP events on the launch stream bracket the K kernels of every timed region
+            def capture(k):
+                with _lib.Graph.capture(self.stream) as g:
+                    for _ in range(k):
+                        cw.step(dt, n_sub, action)
+                return g
+
+            per = min(steps, GRAPH_STEPS)
+            plan = [capture(per)] * (steps // per)
+            if steps % per:
+                plan.append(capture(steps % per))
+            t_warm = time.perf_counter()
+            for graph in dict.fromkeys(plan):
+                graph.launch()                  # one untimed replay each (first launch of an instantiated graph uploads it)
             _lib.stream_sync(self.stream)
+            # then untimed replays for GRAPH_WARM_S, undone by the restore below: the timed region starts on a warm GPU (a lone cold
+            # window of 20 steps reads ~12 % slower than the median of the same window repeated)
+            while snap and time.perf_counter() - t_warm < GRAPH_WARM_S:
+                plan[0].launch()
+                _lib.stream_sync(self.stream)
             e0, e1 = _lib.Event(), _lib.Event()
             for _ in range(repeats):
                 if snap:
-                    snap.restore()              # untimed: the replay below starts from the post-warm-up worlds every time
+                    snap.restore()              # untimed: the replays below start from the post-warm-up worlds every time
                 self.barrier()
                 t0 = time.perf_counter()
                 e0.record(self.stream)
-                graph.launch()
+                for graph in plan:
+                    graph.launch()
                 e1.record(self.stream)
                 _lib.stream_sync(self.stream)
                 self.barrier()
@@ -466,6 +496,25 @@ class Runner:
             best = ms if best is None else min(best, ms)
         a.free(); b.free()
         return 2.0 * nbytes / (best * 1e-3) / 1e9
+
+
+def dump_outputs(cw, out_dir) -> dict:
+    """What the timed path computed in its last step, as a caller of CrowdWorlds.step reads it back: states [W, rows, 13], goals and,
+    with a visible robot, robot rows [W, 13], float32.  Above DUMP_LIMIT_BYTES the same fixed seeded sample of worlds (ascending ids)
+    is taken from every array.  Returns {name: shape}."""
+    arrays = {"states": cw.get_states(), "goals": cw.get_goals()}
+    if cw.d_robot is not None:
+        arrays["robot"] = cw.get_robot()
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    W = arrays["states"].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(W, W * DUMP_LIMIT_BYTES // total, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def family_of(model):
@@ -888,19 +937,19 @@ def main(argv=None):
     spec = workload_spec(args)
     cw, host, W = build_worlds(spec, rank, world_size)
     wall, kern = run.measure(cw, spec, args.steps, args.warmup, args.repeats, eager=args.eager, restore=not args.no_restore)
+    dumped = dump_outputs(cw, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     per_rank_kernel_us = run.gather(float(np.mean(kern)) * 1e3)
     total_worlds = args.total_worlds if args.total_worlds is not None else world_size * args.worlds
     # which card every rank sat on
     me = {"rank": rank, "device": dev_index, "pci": _lib.device_pci_bus_id(dev_index), "worlds": W, "kernel_us": float(np.mean(kern)) * 1e3}
     ranks = run.gather_objects(me)
 
-    # sanity: the state is finite and moved
-    S_end = cw.get_states()
-    finite = float(np.mean(np.isfinite(S_end[..., :8])))
-
-    copy_gbs = run.copy_bandwidth() if rank == 0 else None
-    others = []
-    if not args.no_other_configs:
+    finite, copy_gbs, others = None, None, []
+    if args.full:
+        # sanity: the state is finite and moved
+        finite = float(np.mean(np.isfinite(cw.get_states()[..., :8])))
+        copy_gbs = run.copy_bandwidth() if rank == 0 else None
+    if args.full and not args.no_other_configs:
         for ospec in other_config_specs(args):
             ocw, _, oW = build_worlds(ospec, rank, world_size)
             k_o = ospec["steps"]   # every row over its OWN window, whatever --steps says: the driver's line and profiles/ show the same figures
@@ -926,7 +975,6 @@ def main(argv=None):
         agent_substeps = total_worlds * args.agents * n_sub * args.steps
         value = agent_substeps / med
         g, b, wpb = cw.launch_geometry()
-        rl = roofline_block(spec, W, kern, copy_gbs, cw, window=(args.warmup, args.steps))
         out = {
             "metric": "env-steps/sec (worlds x agents) for HSFM 25-agent crowd",
             "value": value,
@@ -954,23 +1002,25 @@ def main(argv=None):
                 # (blocks of one wavefront go to the dispatcher several to a workgroup -- wg= in the variant string: grid / wg workgroups of block x wg threads)
                 "launch": {"grid": g, "block": b, "worlds_per_block": wpb, "blocks_per_workgroup": _wg_of(cw.step_variant())},
                 "timed_region": "eager launches, one HIP event pair per launch" if args.eager else
-                                "[untimed: worlds restored to the post-warm-up snapshot] barrier + sync | ONE replay of a HIP graph holding exactly K "
-                                "cs_step launches | sync + barrier; repeated R times on the SAME trajectory segment (Gym steps W .. W+K), median reported",
+                                f"[untimed: {GRAPH_WARM_S} s of graph replays, worlds restored to the post-warm-up snapshot] barrier + sync | back-to-back replays of HIP graphs of at most "
+                                f"{GRAPH_STEPS} cs_step launches, exactly K in all | sync + barrier; repeated R times on the SAME trajectory segment "
+                                f"(Gym steps W .. W+K), median reported",
                 "stationary": not args.no_restore,
             },
             "world_substeps_per_s": value / args.agents,
             "gym_steps_per_s": value / args.agents / n_sub,
-            "finite_fraction": finite,
-            "kernel_us": rl["kernel_avg_ms"] * 1e3,
-            "kernel_us_median": rl["kernel_median_ms"] * 1e3,
-            "kernel_le_wall": bool(rl["kernel_median_ms"] <= med / args.steps * 1e3),
+            "kernel_us": float(np.mean(kern)) * 1e3,
+            "kernel_us_median": float(np.median(kern)) * 1e3,
+            "kernel_le_wall": bool(np.median(kern) <= med / args.steps * 1e3),
             "per_rank_kernel_us": per_rank_kernel_us,
             "dist": dist_info,
             "ranks": ranks,
-            "roofline": rl,
-            "other_configs": others,
         }
-        if not args.no_cpu_baseline and world_size == 1 and not args.robot and not args.per_agent_params:
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if args.full:
+            out.update(finite_fraction=finite, roofline=roofline_block(spec, W, kern, copy_gbs, cw, window=(args.warmup, args.steps)), other_configs=others)
+        if args.full and not args.no_cpu_baseline and world_size == 1 and not args.robot and not args.per_agent_params:
             out["cpu_baseline"] = cpu_baseline(dict(spec, warmup=args.warmup, steps=args.steps), args.cpu_seconds)   # rank 0, N = 1 only
             out["gpu_over_cpu"] = value / world_size / out["cpu_baseline"]["value"]
             # the other configurations the oracle covers, each beside its own row (3 s of CPU work per row)
@@ -998,12 +1048,16 @@ def main(argv=None):
                 out["full_json"] = None
                 print(f"bench.py: full result not written ({e})", file=sys.stderr)
 
-        write_full()   # the measurement is on disk before the side figure below runs
-        if not args.no_gym_step and not args.no_other_configs and world_size == 1 and args.model != "orca" and not args.robot and not args.per_agent_params and not args.walls:
+        if args.full:
+            write_full()   # the measurement is on disk before the side figure below runs
+        if args.full and not args.no_gym_step and not args.no_other_configs and world_size == 1 and args.model != "orca" and not args.robot and not args.per_agent_params and not args.walls:
             out["gym_step"] = gym_step_child(args.worlds, args.agents)
             write_full()
-        print(json.dumps(out), file=sys.stderr, flush=True)      # the full blocks: stderr + the side file
-        line = compact_line(out)
+        if args.full:
+            print(json.dumps(out), file=sys.stderr, flush=True)      # the full blocks: stderr + the side file
+            line = compact_line(out)
+        else:
+            line = json.dumps(_r(out), allow_nan=False, separators=(",", ":"))
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(line, flush=True)

@@ -214,3 +214,33 @@ def test_cpu_baseline_runner_covers_the_robot_and_per_agent_rows():
                                  robot_visible=rob is not None, robot=rob, action=act, threads=1)
         np.testing.assert_array_equal(r.S, S)
         assert not np.array_equal(r.S, host["S"][sel])
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_limit_from_one_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array float32; above DUMP_LIMIT_BYTES the SAME seeded sample of worlds from every array, the same on every call."""
+    import types
+
+    import numpy as np
+
+    W = 50
+    S = np.arange(W * 3 * 13, dtype=np.float64).reshape(W, 3, 13)
+    goals = np.arange(W * 3 * 2 * 2, dtype=np.float32).reshape(W, 3, 2, 2)
+    robot = np.arange(W * 13, dtype=np.float32).reshape(W, 13)
+    cw = types.SimpleNamespace(get_states=lambda: S, get_goals=lambda: goals, get_robot=lambda: robot, d_robot=object())
+    shapes = bench.dump_outputs(cw, str(tmp_path / "all"))
+    assert shapes == {"states": [W, 3, 13], "goals": [W, 3, 2, 2], "robot": [W, 13]}
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in shapes}
+    assert all(a.dtype == np.float32 for a in got.values()) and np.array_equal(got["states"], S.astype(np.float32))
+
+    full_bytes = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", full_bytes // 3)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(cw, str(tmp_path / run))
+    s = {k: np.load(tmp_path / "s1" / f"{k}.npy") for k in shapes}
+    assert sum(a.nbytes for a in s.values()) <= full_bytes // 3 and 0 < s["states"].shape[0] < W
+    ids = s["robot"][:, 0] / 13                      # robot row w starts at 13 w: the sampled world ids, ascending
+    assert np.array_equal(ids, np.sort(ids)) and np.array_equal(s["states"], S[ids.astype(int)].astype(np.float32))
+    assert np.array_equal(s["goals"], goals[ids.astype(int)])
+    assert all(np.array_equal(s[k], np.load(tmp_path / "s2" / f"{k}.npy")) for k in shapes)
+    cw.d_robot = None
+    assert set(bench.dump_outputs(cw, str(tmp_path / "norobot"))) == {"states", "goals"}

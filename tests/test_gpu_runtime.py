@@ -42,7 +42,7 @@ def test_crowdstep_first_then_torch_share_one_hip_runtime():
     assert r.stdout.strip().splitlines()[-1].startswith("OK")
 
 
-def test_bench_launches_its_own_ranks_and_prints_one_parsable_line():
+def test_bench_launches_its_own_ranks_and_prints_one_parsable_line(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the rehearsal form for a one-GPU box: both ranks on GPU 0, gloo for the
     barrier): the parent starts two fresh rank processes before touching HIP, relays rank 0's line -- ONE line on stdout, strict JSON
     under 4 KB, n_gpus = 2, one record per rank with its device and PCI address, value = the worlds of BOTH ranks over the slowest
@@ -53,7 +53,7 @@ def test_bench_launches_its_own_ranks_and_prints_one_parsable_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend", "gloo", "--steps", "4", "--warmup", "2",
-           "--repeats", "3", "--worlds", "512", "--no-other-configs", "--no-cpu-baseline", "--full-json", os.path.join(ROOT, "gpurun_out", "bench_full_test.json")]
+           "--repeats", "3", "--worlds", "512", "--full", "--no-other-configs", "--no-cpu-baseline", "--full-json", str(tmp_path / "bench_full_test.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -102,3 +102,52 @@ def test_one_wavefront_blocks_step_the_same_bits_however_many_share_a_workgroup(
         assert line, r.stdout[-500:]
         hashes[wg] = line[-1]
     assert hashes["1"] == hashes["2"] == hashes["4"], hashes
+
+
+EAGER_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+import bench
+args = bench.parse(%(argv)r)
+spec = bench.workload_spec(args)
+cw, _, _ = bench.build_worlds(spec, 0, 1)
+for _ in range(args.warmup + args.steps):
+    cw.step(spec["dt"], spec["substeps"], cw.bench_action)
+np.save(%(out)r + "/states.npy", cw.get_states())
+np.save(%(out)r + "/goals.npy", cw.get_goals())
+"""
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times exactly K steps (K > GRAPH_STEPS: full graphs and a remainder graph), prints the headline
+    without the --full blocks, and --dump-outputs writes the worlds as W + K eager steps of the same inputs leave them, bit for bit, on every run."""
+    import json
+
+    import numpy as np
+
+    argv = ["--gpus", "1", "--steps", "1203", "--warmup", "3", "--worlds", "96"]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 1203 and d["warmup"] == 3 and d["timing_repeats"] == 1 and d["n_gpus"] == 1
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 96 * 25 * 20 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+        assert {"metric", "unit", "higher_is_better", "dtype"} <= set(d) and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert not {"roofline", "other_configs", "cpu_baseline", "gym_step", "finite_fraction"} & set(d)
+        assert d["outputs"]["arrays"]["states"] == [96, 25, 13]
+    r = subprocess.run([sys.executable, "-c", EAGER_CHILD % {"root": ROOT, "argv": argv, "out": str(tmp_path)}], capture_output=True, text=True,
+                       timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    for name in ("states", "goals"):
+        want = np.load(tmp_path / f"{name}.npy")
+        for run in ("a", "b"):
+            got = np.load(tmp_path / run / f"{name}.npy")
+            assert got.dtype == np.float32 and got.shape == want.shape
+            assert np.array_equal(got, want, equal_nan=True), (name, run, float(np.nanmax(np.abs(got - want))))

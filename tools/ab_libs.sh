@@ -6,6 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/ab_libs.txt
 : > $OUT
 B="python3 $R/bench.py --no-cpu-baseline --no-other-configs --no-gym-step --full-json $R/gpurun_out/ab_full.json"
+B="$B --full"   # the roofline block read below is written by a full run only
 run() {   # label, bench flags...: the figures of THIS run or "FAILED" (never a stale ab_full.json)
   local label=$1; shift
   rm -f $R/gpurun_out/ab_full.json

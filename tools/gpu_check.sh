@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/gpu_check.sh TAG [bench args...]   -- gpu tests, one bench line, section stamps
 TAG=${1:-x}; shift
+set -- --full "$@"   # the roofline block and finite_fraction read below come from a full run only
 mkdir -p gpurun_out
 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}_tests.log 2>&1; tail -4 gpurun_out/${TAG}_tests.log
 python bench.py --no-cpu-baseline "$@" > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err

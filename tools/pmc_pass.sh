@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
+rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
 python3 - <<PY
 import csv, glob, collections
 f = glob.glob("$OUT/**/*counter_collection.csv", recursive=True)

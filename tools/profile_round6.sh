@@ -26,13 +26,13 @@ CFG[peragent]="--per-agent-params"
 CFG[cfg5_nowalls]="--worlds 8192 --agents 50 --model hsfm_farina --scenario circle --static 3 --device-generator"
 NAMES=${@:-cfg3 cfg2 cfg4_first20 cfg4_dense cfg4_first20_fma cfg4_dense_fma cfg5 moussaid cfg3_new_guo robot26 n30 peragent n15 n40}
 # the DRIVER's command (BENCH_rNN.json): python3 bench.py --gpus 1 --steps 20 --warmup 5 -- its line is the one quoted first in README / DESIGN
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_protocol_bench.json 2> $O/driver_protocol_bench.log || { echo "driver-protocol bench failed"; tail -5 $O/driver_protocol_bench.log; exit 1; }
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_protocol_bench.json 2> $O/driver_protocol_bench.log || { echo "driver-protocol bench failed"; tail -5 $O/driver_protocol_bench.log; exit 1; }
 cp gpurun_out/bench_full.json $O/driver_protocol_bench_full.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/driver_stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gym-step > /dev/null 2> $O/driver_stats.log || { echo "driver stats run failed"; tail -5 $O/driver_stats.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/driver_stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-gym-step > /dev/null 2> $O/driver_stats.log || { echo "driver stats run failed"; tail -5 $O/driver_stats.log; exit 1; }
 cp $(find $O/driver_stats -name "*kernel_stats.csv" | head -1) $O/driver_protocol_kernel_stats.csv && head -4 $O/driver_protocol_kernel_stats.csv | cut -c1-160
 rm -rf $O/driver_stats
 # the default bench command itself under the kernel trace: its k_sfm_step<..., 25, 1> row is the kernel behind `value`
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/main_stats -- python3 bench.py --no-gym-step > $O/main_bench.json 2> $O/main_stats.log || { echo "main stats run failed"; tail -5 $O/main_stats.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/main_stats -- python3 bench.py --full --no-gym-step > $O/main_bench.json 2> $O/main_stats.log || { echo "main stats run failed"; tail -5 $O/main_stats.log; exit 1; }
 cp $(find $O/main_stats -name "*kernel_stats.csv" | head -1) $O/main_kernel_stats.csv && head -4 $O/main_kernel_stats.csv | cut -c1-160
 rm -rf $O/main_stats
 for name in $NAMES; do
@@ -40,7 +40,7 @@ for name in $NAMES; do
   S="--steps 50 --warmup 20"
   case "$A" in *--steps*) S="";; esac
   echo "== $name: $A"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_stats -- python3 bench.py $A $S --repeats 4 > $O/${name}_bench.json 2> $O/${name}_stats.log || { echo "stats run failed"; tail -5 $O/${name}_stats.log; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_stats -- python3 bench.py $A $S --full --repeats 4 > $O/${name}_bench.json 2> $O/${name}_stats.log || { echo "stats run failed"; tail -5 $O/${name}_stats.log; exit 1; }
   cp $(find $O/${name}_stats -name "*kernel_stats.csv" | head -1) $O/${name}_kernel_stats.csv && head -3 $O/${name}_kernel_stats.csv | cut -c1-160
   # (the counters are taken over the SAME window as the kernel time above: round 3 paired the instruction count of Gym steps 20-30 with
   #  the time of steps 20-70, which made cfg5's wall pass look stall-bound -- profiles/r4k_cfg5_wall_pass_counters_*.txt)

@@ -9,7 +9,7 @@ for ph in "0 20" "25 20"; do set -- $ph
 done
 python3 tools/facade_latency.py 300 $O/facade_latency.json > $O/facade_latency.txt 2>&1; tail -4 $O/facade_latency.txt
 for W in 512 1024 2048 4096 8192 16384 32768; do
-  python3 bench.py --worlds $W --steps 50 --warmup 20 --no-other-configs --no-cpu-baseline --no-gym-step 2>/dev/null | python3 -c "
+  python3 bench.py --worlds $W --steps 50 --warmup 20 --full --no-other-configs --no-cpu-baseline --no-gym-step 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('worlds %6d | kernel_us %8.2f frac %.3f' % ($W, d['kernel_us'], d['roofline']['frac']))" | tee -a $O/worlds_per_gpu_curve.txt
 done
 for W in 1024 2048 4096 8192 16384 32768; do

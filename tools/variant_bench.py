@@ -19,7 +19,7 @@ for spec in [a for a in sys.argv[1:] if not a.startswith("--")]:
            "-I", os.path.join(ROOT, "include"), "-o", so] + [f for f in flags.split(",") if f] + \
           [os.path.join(hb.CSRC, x) for x in hb.SOURCES]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    code = ("import sys; sys.argv=['bench.py','--no-cpu-baseline']+%r; sys.path.insert(0,%r);"
+    code = ("import sys; sys.argv=['bench.py','--full','--no-cpu-baseline']+%r; sys.path.insert(0,%r);"
             "from social_navigation_pyenvs_amd import _lib; _lib.LIB_PATH=%r; import bench; bench.main()" % (extra, ROOT, so))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT)
     try:
