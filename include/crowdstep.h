@@ -518,6 +518,22 @@ int cs_gym_step_staged(const cs_worlds* w, float dt, int n_substeps, const float
                        float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, const cs_generator* gen,
                        const cs_worlds* staging, const cs_stage_book* stage_book, void* stream);
 
+/*
+ * cs_policy_no_train  the CrowdNav baseline robot policies that need no training (crowd_nav/policy_no_train/: blind_planner.py,
+ *   simple_social_planner.py, sfm_helbing.py, sfm_guo.py, sfm_moussaid.py with forces.py) -- Policy.predict(JointState) for the robots
+ *   of W worlds in one launch.  d_robot13 [W][13] robot safe-state rows (cs_worlds.d_robot: x, y, yaw, Vx, Vy, BVx, BVy, Omega, radius,
+ *   mass, gx, gy, v_pref); d_obs [W][n][obs_cols] observation rows (cs_gym_observe: px, py, vx, vy, radius[, theta, omega]; obs_cols 5 or
+ *   7); d_action [W][2] out: ActionXY (vx, vy).  time_step: the policy's (ROBOT_SAMPLING_TIME in the simulator); only the social-force
+ *   policies read it.  params (host, CS_PNT_N_PARAMS floats, read before the call returns): the policy's own dict packed into the 20
+ *   agent.py slots [relax_t, Ai, Aw, Bi, Bw, Ci, Cw, Di, Dw, Ei, k1, k2, a_lambda, gamma, ns, ns1, ko, kd, alpha, k_lambda] and its
+ *   mass in slot CS_PNT_MASS; required by the social-force policies, ignored (may be NULL) by bp / ssp.
+ *   Errors (CS_ERR_ARG, before any device call): unknown policy id, W < 1, n < 0, obs_cols not 5 or 7, null pointers.
+ */
+enum { CS_PNT_BP = 0, CS_PNT_SSP = 1, CS_PNT_SFM_HELBING = 2, CS_PNT_SFM_GUO = 3, CS_PNT_SFM_MOUSSAID = 4 };
+enum { CS_PNT_MASS = 20, CS_PNT_N_PARAMS = 21 };
+int cs_policy_no_train(int policy, int W, int n, const float* d_robot13, const float* d_obs, int obs_cols, float time_step,
+                       const float* params /* host, CS_PNT_N_PARAMS floats */, float* d_action, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

@@ -612,6 +612,7 @@ class BatchedSocialNavGym:
                 self._maybe_refill(dl)
         if not same:
             cur.wait_stream(side)                  # ... and with whoever reads the results
+        dl["obs_fresh"] = True                     # the step wrote the observation buffer act_device reads
         reward, terminated, truncated, info = dl["results"][parity]
         return dl["obs"], reward, terminated, truncated, info
 
@@ -638,6 +639,58 @@ class BatchedSocialNavGym:
     def action_buffer(self):
         """The persistent [W, 2] action tensor the step kernel reads: write actions into it and pass it to ``step_device``."""
         return self._device_loop_state()["act"]
+
+    def act_device(self, policy):
+        """Every world's robot decides with a no-train CrowdNav policy (``policy``: a name of crowd_nav.policy_no_train.policy_factory or
+        an instance of its classes) -- ``predict`` for W robots in ONE launch of cs_policy_no_train on ``device_stream()``, reading the
+        resident robot rows and the current observation, writing ActionXY rows into ``action_buffer()``.  Returns that buffer, ready
+        for ``step_device(env.action_buffer())``; nothing crosses to the host.  The policy's ``time_step`` (None: the robot time step)
+        is the social-force policies' integration step.  Needs worlds generated on the device (``reset(..., device=True)``) and a
+        holonomic robot (the policies act in ActionXY, robot_agent.py:112-114)."""
+        import ctypes as C
+
+        import torch
+
+        dl = self._device_loop_state()
+        if isinstance(policy, str):
+            from ..crowd_nav.policy_no_train.policy_factory import policy_factory
+
+            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
+        else:
+            pol = policy
+        from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
+
+        if not isinstance(pol, NoTrainPolicy):
+            raise TypeError(f"act_device takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}")
+        if pol.kinematics != "holonomic" or self.cw.unicycle:
+            raise ValueError("act_device: the no-train policies act in ActionXY and need a holonomic robot")
+        if self.cw.d_robot is None:
+            raise ValueError("act_device needs the robot rows")
+        side, cur = dl["stream"], torch.cuda.current_stream()
+        same = cur.cuda_stream == side.cuda_stream
+        if not same:
+            side.wait_stream(cur)
+        lib = _lib.load()
+        if not dl.get("obs_fresh"):                # no step since the batch was generated: take the observation of the resident rows
+            d = self.cw.descriptor(respawn=False)
+            _lib.check(lib.cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()),
+                                          C.c_void_p(side.cuda_stream)))
+            dl["obs_fresh"] = True
+        # the ctypes arguments bound once per (policy, time step, parameters): a decision is one library call
+        ts = self.robot_time_step if pol.time_step is None else pol.time_step
+        prm = pol.packed_params()
+        key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
+        bound = dl.setdefault("pnt_args", {})
+        args = bound.get(key)
+        if args is None:
+            args = (C.c_int(pol.pnt_id), C.c_int(self.W), C.c_int(self.n), C.c_void_p(self.cw.d_robot.ptr), C.c_void_p(dl["obs"].data_ptr()),
+                    C.c_int(dl["obs"].shape[2]), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p),
+                    C.c_void_p(dl["act"].data_ptr()), C.c_void_p(side.cuda_stream), prm)
+            bound[key] = args
+        _lib.check(lib.cs_policy_no_train(*args[:-1]))
+        if not same:
+            cur.wait_stream(side)
+        return dl["act"]
 
     def lookahead_device(self, action_space):
         """The per-decision array work of CADRL / SARL for every world, on the device: one-step look-ahead of the humans

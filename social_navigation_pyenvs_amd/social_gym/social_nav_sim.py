@@ -4,7 +4,8 @@ Kept from the reference (same names and semantics): the three scenario generator
 ``np.random`` draw order (:200-431), ``reset_sim`` (:97-198), ``set_time_step`` / ``set_robot_time_step``
 (:82-95), ``collision_detection_and_reaching_goal`` (:949-984), ``compute_reward_and_infos`` (:986-1029),
 ``onestep_lookahead`` (:1031-1049), ``transform_human_states`` / constant-velocity propagation
-(:935-947, 1051-1066) and a headless ``run_k_steps`` (:670-714).  Everything PyGame (window, sprites,
+(:935-947, 1051-1066), a headless ``run_k_steps`` (:670-714) and ``set_robot_policy`` (:877-928) with the no-train CrowdNav
+robot policies driving the robot in ``update`` / ``run_k_steps``.  Everything PyGame (window, sprites,
 rewind, plots, manual driving) is out of scope: rendering is bypassed on this path.
 
 Rejection loops are bounded (``MAX_PLACEMENT_TRIES``): the reference's ``while True`` loops never end
@@ -299,7 +300,10 @@ class SocialNavSim:
 
     # ------------------------------------------------------------------ headless stepping
     def update(self):
-        """One simulator update of sampling_time (humans only; the robot is moved by the caller)."""
+        """One simulator update of sampling_time (humans only; the robot is moved by the caller) -- unless a CrowdNav robot policy
+        was set with ``set_robot_policy(..., crowdnav_policy=True)``: then the reference's update() / control_robot() (:476-530)."""
+        if self._policy_drives_robot():
+            return self._update_with_policy()
         self.motion_model_manager.update_humans(self.sim_t, self.sampling_time)
         self.sim_t += self.sampling_time
         self.n_updates += 1
@@ -307,13 +311,109 @@ class SocialNavSim:
 
     def run_k_steps(self, steps, quit=True, additional_info=False, stop_when_collision_or_goal=False, save_states_time_step=None):
         """Headless rollout of the humans (:670-714, without the robot controller): returns the human states
-        [steps, N, 8] (x, y, yaw, Vx|BVx, Vy|BVy, Omega, Gx, Gy)."""
+        [steps, N, 8] (x, y, yaw, Vx|BVx, Vy|BVy, Omega, Gx, Gy).  With a CrowdNav robot policy set (``set_robot_policy``): the
+        reference's whole contract instead (_run_k_steps_with_policy)."""
+        if self._policy_drives_robot():
+            return self._run_k_steps_with_policy(steps, additional_info, stop_when_collision_or_goal, save_states_time_step)
         mm = self.motion_model_manager
         out = np.empty((steps, len(self.humans), N_GENERAL_STATES), dtype=PRECISION)
         for k in range(steps):
             out[k] = mm.get_human_states(include_goal=True, headed=mm.headed)
             self.update()
         return out
+
+    # ------------------------------------------------------------------ CrowdNav robot policies (:877-928, :476-530, :670-714)
+    def set_robot_policy(self, policy_name: str, runge_kutta=False, crowdnav_policy=False, model_dir=None, il=False):
+        """The robot follows ``policy_name``.  ``crowdnav_policy=True``: one of the no-train CrowdNav policies (bp, ssp, sfm_helbing,
+        sfm_guo, sfm_moussaid; crowd_nav.policy_no_train.policy_factory -- the other keys raise NotImplementedError with their reason),
+        decided through its ``predict`` (csrc/policy_no_train.hip) every robot time step, with v_pref 1 as in the reference.  Trained
+        policies (``model_dir``) are user code: NotImplementedError.  ``crowdnav_policy=False``: a human motion model
+        (set_human_motion_model_as_robot_policy)."""
+        if not crowdnav_policy:
+            self.set_human_motion_model_as_robot_policy(policy_name, runge_kutta)
+            return
+        if model_dir is not None:
+            raise NotImplementedError("trained CrowdNav policies (model_dir) are user code: configure and load them, then robot.set_policy()")
+        from ..crowd_nav.policy_no_train.policy_factory import policy_factory
+
+        policy = policy_factory[policy_name]()
+        policy.set_phase("test")
+        policy.set_device("cpu")
+        policy.set_env(self)
+        self.robot.desired_speed = 1
+        self.robot.set_policy(policy)
+        self.robot.policy.time_step = self.robot_sampling_time
+        self.robot_controlled = True
+        self.robot_crowdnav_policy = True
+        if self.parallelize_robot:
+            self.robot.policy.parallelize = True
+            self.robot.parallelize = True
+
+    def _policy_drives_robot(self) -> bool:
+        return (self.insert_robot and getattr(self, "robot_crowdnav_policy", False) and self.robot_controlled
+                and getattr(self.robot, "policy", None) is not None)
+
+    def _control_robot(self):
+        """control_robot's CrowdNav branch (:495-507): a decision every robot time step, the pose moved between decisions."""
+        robot = self.robot
+        if is_multiple(self.sim_t, self.robot_sampling_time):
+            action = robot.act([h.get_observable_state() for h in self.humans])
+            robot.step(action, self.sampling_time)
+            if np.linalg.norm(robot.position - robot.get_goal_position()) < robot.radius and len(robot.goals) > 1:
+                robot.goals.append(robot.goals.pop(0))
+            self.updated = True
+            if robot.laser is not None:
+                robot.get_laser_readings(self.humans, self.walls)
+        else:
+            self.motion_model_manager.update_robot_pose(self.sampling_time)
+
+    def _update_with_policy(self):
+        """update() (:476-491): the robot decides / moves, the humans are stepped against its PRE-update row, then it takes its new one."""
+        self.n_updates += 1
+        robot = self.robot
+        before = robot.get_safe_state()
+        self._control_robot()
+        after = robot.get_safe_state()
+        robot.set_state(before)
+        self.motion_model_manager.update_humans(self.sim_t, self.sampling_time)
+        robot.set_state(after)
+        self.sim_t = self.n_updates * self.sampling_time
+
+    def _run_k_steps_with_policy(self, steps, additional_info, stop_when_collision_or_goal, save_states_time_step):
+        """run_k_steps (:670-714) with the robot driven by its policy: the initial state is included, states are saved every
+        ``save_states_time_step``; returns (human_states, robot_states[, collision, time_to_goal, success, truncated])."""
+        if save_states_time_step is None:
+            save_states_time_step = self.sampling_time
+        if not is_multiple(save_states_time_step, self.sampling_time):
+            raise ValueError(f"Time step to save states must be a multiple of environment sampling time: {self.sampling_time}")
+        mm = self.motion_model_manager
+        human_states = [mm.get_human_states()]
+        robot_states = [mm.get_robot_state()]
+        if stop_when_collision_or_goal and not additional_info:
+            raise ValueError("Cannot stop the episode if you don't compute additional info")
+        collision = success = truncated = False
+        time_to_goal = None
+        for step in range(steps):
+            if stop_when_collision_or_goal and (collision or success):
+                break
+            self.update()
+            if is_multiple(self.sim_t, save_states_time_step):
+                human_states.append(mm.get_human_states())
+                robot_states.append(mm.get_robot_state())
+            if additional_info:
+                for h in self.humans:
+                    if np.linalg.norm(h.position - self.robot.position) < (h.radius + self.robot.radius):
+                        collision = True
+                if len(robot_states) > 1 and not np.array_equal(robot_states[-1][6:8], robot_states[-2][6:8]):   # the goal changed
+                    time_to_goal = self.n_updates * self.sampling_time
+                    success = True
+                if step == steps - 1 and not collision and not success:
+                    truncated = True
+        human_states = np.array(human_states, dtype=PRECISION)
+        robot_states = np.array(robot_states, dtype=PRECISION)
+        if additional_info:
+            return human_states, robot_states, collision, time_to_goal, success, truncated
+        return human_states, robot_states
 
     # ------------------------------------------------------------------ CrowdNav hooks (:935-1066)
     def transform_human_states(self, state, theta_and_omega_visible=False):

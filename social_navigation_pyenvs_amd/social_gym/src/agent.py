@@ -232,8 +232,8 @@ class RobotAgent(Agent):
         return self.policy.predict(JointState(self.get_full_state(), ob))
 
     def configure(self, config, section, policy_factory=None):
-        """Reads [robot] visible / v_pref / radius / policy / sensor (robot_agent.py:144-150).  The policy
-        classes are consumers of this env, not part of it: pass the caller's `policy_factory` mapping."""
+        """Reads [robot] visible / v_pref / radius / policy / sensor (robot_agent.py:144-150).  Pass a `policy_factory` mapping:
+        the caller's own, or crowd_nav.policy_no_train.policy_factory for the no-train baselines (bp, ssp, sfm_*)."""
         self.visible = config.getboolean(section, "visible")
         self.desired_speed = config.getfloat(section, "v_pref")
         self.radius = config.getfloat(section, "radius")

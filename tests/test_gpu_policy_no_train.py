@@ -1,0 +1,213 @@
+"""GPU suite of the no-train CrowdNav robot policies: csrc/policy_no_train.hip against golden G18 (recorded from the reference),
+the batched launch against the W = 1 ``predict``, the device-resident act -> step loop, and the policy-driven simulator."""
+import math
+
+import numpy as np
+import pytest
+
+import parity_util
+from golden_io import load_cases
+from test_policy_no_train_cpu import _decisions, policy_f64
+
+pytestmark = pytest.mark.gpu
+
+SUPPORTED = ["bp", "ssp", "sfm_helbing", "sfm_guo", "sfm_moussaid"]
+
+
+def _states(robot, obs):
+    from social_navigation_pyenvs_amd.crowd_nav.utils.state import FullState, JointState, ObservableState
+
+    return JointState(FullState(*[float(x) for x in robot[:9]]), [ObservableState(*[float(x) for x in h[:5]]) for h in obs])
+
+
+def _undetermined(policy, robot, obs):
+    """Decisions float32 cannot settle: a Moussaid pair whose theta_ij is within 1e-6 of 0 (its sign picks the side of the
+    lateral term), an ssp surface distance within 1e-6 of the 0.2 threshold."""
+    px, py, vx, vy, rr = (float(x) for x in robot[:5])
+    for h in np.asarray(obs, np.float64).reshape(-1, 5):
+        dx, dy = px - h[0], py - h[1]
+        d = math.hypot(dx, dy)
+        if policy == "ssp" and abs(d - h[4] - rr - 0.2) < 1e-6:
+            return "ssp_threshold"
+        if policy == "sfm_moussaid":
+            nx, ny = dx / d, dy / d
+            ix, iy = 2.0 * (vx - h[2]) - nx, 2.0 * (vy - h[3]) - ny
+            th = math.atan2(ny, nx) - math.atan2(iy, ix) + math.pi
+            th = th - 2 * math.pi if th > math.pi else (th + 2 * math.pi if th < -math.pi else th)
+            if abs(th) < 1e-6:
+                return "moussaid_theta"
+    return None
+
+
+def test_g18_decisions_and_edge_cases_match_the_reference():
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy_no_train.policy_factory import policy_factory
+
+    _lib.require_gpu()
+    cases = _decisions()
+    policies = {name: policy_factory[name]() for name in SUPPORTED}
+    worst, explained, unexplained = 0.0, {}, []
+    for c in cases:
+        p = policies[c["policy"]]
+        p.time_step = c["time_step"]
+        st = _states(c["robot"], c["obs"])
+        a = p.predict(st)
+        assert p.last_state is st
+        got = np.array([a.vx, a.vy])
+        assert np.all(np.isfinite(got))
+        err = float(np.max(np.abs(got - c["action"])))
+        if err <= 1e-5:
+            worst = max(worst, err)
+            continue
+        why = _undetermined(c["policy"], c["robot"], c["obs"])
+        if why is None:
+            unexplained.append((c["policy"], c["kind"], c.get("tag"), c["n"], err))
+        else:
+            explained[why] = explained.get(why, 0) + 1
+    parity_util.record("g18_policy_no_train_actions", worst)
+    print(f"G18 actions: {len(cases)} compared, worst within-bar error {worst:.2e}, float32-undetermined {explained}")
+    assert not unexplained, unexplained[:10]
+    # the at-goal convention and the ssp threshold held where float32 decides them
+    on_goal = [c for c in cases if c.get("tag") == "on_goal" and c["policy"] == "bp"][0]
+    a = policies["bp"].predict(_states(on_goal["robot"], on_goal["obs"]))
+    assert (a.vx, a.vy) == (1.0, 0.0)
+
+
+def _batched(n, W=4096, visible=False):
+    from test_gpu_generators import _config
+
+    from social_navigation_pyenvs_amd.social_gym.social_nav_gym import BatchedSocialNavGym
+
+    env = BatchedSocialNavGym(_config("hybrid_scenario", human_num=n, policy="sfm_guo"), W, robot_visible=visible)
+    env.reset(phase="test", first_case=11, device=True)
+    return env
+
+
+@pytest.mark.parametrize("n", [5, 25])
+def test_act_device_equals_w1_predict_bit_for_bit(n):
+    torch = pytest.importorskip("torch")
+    from social_navigation_pyenvs_amd.crowd_nav.policy_no_train.policy_factory import policy_factory
+
+    env = _batched(n)
+    W = env.W
+    for _ in range(3):          # robots and humans in motion
+        env.step_device(env.act_device("sfm_helbing"))
+    rows = np.unique(np.r_[0, W - 1, np.random.default_rng(n).choice(W, 382, replace=False)])
+    for name in SUPPORTED:
+        act = env.act_device(name).cpu().numpy().copy()
+        assert np.all(np.isfinite(act))
+        robot = env.cw.d_robot.download()
+        obs = env._dl["obs"].cpu().numpy()
+        pol = policy_factory[name]()
+        pol.time_step = env.robot_time_step
+        for w in rows:
+            r = robot[w]
+            a = pol.predict(_states([r[0], r[1], r[3], r[4], r[8], r[10], r[11], r[12], r[2]], obs[w]))
+            assert np.float32(a.vx) == act[w, 0] and np.float32(a.vy) == act[w, 1], (name, w, a, act[w])
+        # and the batch against the float64 restatement (inputs as the device holds them)
+        for w in rows[:64]:
+            r = robot[w].astype(np.float64)
+            ref = policy_f64(name, [r[0], r[1], r[3], r[4], r[8], r[10], r[11], r[12], r[2]], obs[w].astype(np.float64), env.robot_time_step)
+            if _undetermined(name, [r[0], r[1], r[3], r[4], r[8]], obs[w]) is None:
+                assert np.max(np.abs(act[w] - ref)) < 1e-5, (name, w, act[w], ref)
+    del torch
+
+
+@pytest.mark.parametrize("policy,visible", [("sfm_moussaid", False), ("ssp", True)])
+def test_act_step_loop_reads_the_current_observation(policy, visible):
+    """64 worlds, 200 Gym steps of act_device -> step_device with auto-reset: at every step the actions are the kernel's answer on
+    that step's observation and robot rows, and a robot that was not reset carries the previous action as its velocity."""
+    torch = pytest.importorskip("torch")
+    from social_navigation_pyenvs_amd.crowd_nav.policy_no_train import policy as pnt
+    from social_navigation_pyenvs_amd.crowd_nav.policy_no_train.policy_factory import policy_factory
+
+    env = _batched(5, W=64, visible=visible)
+    pol = policy_factory[policy]()
+    ended = 0
+    act_prev = None
+    for k in range(200):
+        act = env.act_device(pol)
+        assert act is env.action_buffer()
+        obs = env._dl["obs"].clone()
+        rob = env.cw.d_robot.torch().view(env.W, 13).clone()
+        np.testing.assert_array_equal(obs.cpu().numpy(), env.observe_device().cpu().numpy())     # the observation of the resident rows
+        check = torch.empty_like(act)
+        pnt.launch(pol.pnt_id, env.W, env.n, rob.data_ptr(), obs.data_ptr(), obs.shape[2], env.robot_time_step, pol.packed_params(),
+                   check.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        np.testing.assert_array_equal(act.cpu().numpy(), check.cpu().numpy())
+        if act_prev is not None:
+            kept = (env._dl["counter"] != 0).cpu().numpy()       # worlds that were not reset by the previous step
+            np.testing.assert_array_equal(rob.cpu().numpy()[kept][:, 3:5], act_prev[kept])
+        act_prev = act.cpu().numpy().copy()
+        _, _, term, trunc, _ = env.step_device(env.action_buffer())
+        ended += int((term | trunc).sum().item())
+    assert ended > 0         # episodes ended and were reset on the way
+    print(f"{policy}: {ended} episodes ended in 200 steps of 64 worlds")
+
+
+def test_act_device_refuses_what_it_cannot_drive():
+    pytest.importorskip("torch")
+    env = _batched(5, W=8)
+    with pytest.raises(TypeError):
+        env.act_device(object())
+    with pytest.raises(NotImplementedError):
+        env.act_device("orca")
+    env.cw.unicycle = True
+    with pytest.raises(ValueError, match="holonomic"):
+        env.act_device("bp")
+    env.cw.unicycle = False
+
+
+def _ref_margin(c):
+    """How close the reference came to the other outcome: the smallest |surface distance| robot-human over the saved rows, and the
+    smallest |distance to goal - radius|."""
+    hs, rs, r = c["human_states"], c["robot_states"], c["init_robot"][8]
+    hr = c["init_humans"][:, 8]
+    col = np.min(np.abs(np.linalg.norm(hs[:, :, 0:2] - rs[:, None, 0:2], axis=2) - hr[None] - r))
+    goal = np.min(np.abs(np.linalg.norm(rs[:, 0:2] - rs[:, 6:8], axis=1) - r))
+    return float(col), float(goal)
+
+
+def test_g18_episodes_policy_driven_simulator():
+    from social_navigation_pyenvs_amd.social_gym.social_nav_sim import SocialNavSim
+
+    eps = [c for c in load_cases("g18_policy_no_train") if c["kind"] == "episode"]
+    assert len(eps) >= 12
+    worst, disagreements, undetermined = 0.0, [], []
+    for c in eps:
+        np.random.seed(c["seed"])
+        sim = SocialNavSim(c["config"], c["scenario"])
+        sim.set_time_step(c["dt"])
+        rows0 = np.array([[*h.position, h.yaw, *h.linear_velocity, *h.body_velocity, h.angular_velocity, h.radius, h.mass, *h.goals[0],
+                           h.desired_speed] for h in sim.humans])
+        np.testing.assert_allclose(rows0, c["init_humans"], atol=1e-12)     # the same world as the reference's
+        sim.set_robot_policy(c["policy"], crowdnav_policy=True)
+        hs, rs, col, ttg, succ, trunc = sim.run_k_steps(c["steps"], additional_info=True, stop_when_collision_or_goal=c["stop"],
+                                                        save_states_time_step=c["save_states_time_step"])
+        stride = int(round(c["save_states_time_step"] / c["dt"]))
+        m = 40 // stride + 1                                         # the rows of the first 40 updates (two robot decisions)
+        assert len(hs) >= min(m, len(c["human_states"])) and hs.shape[1:] == c["human_states"].shape[1:]
+        m = min(m, len(c["human_states"]))
+        e_h = float(np.max(np.abs(hs[:m][:, :, [0, 1, 3, 4]] - c["human_states"][:m][:, :, [0, 1, 3, 4]])))
+        e_r = float(np.max(np.abs(rs[:m][:, [0, 1, 3, 4, 6, 7]] - c["robot_states"][:m][:, [0, 1, 3, 4, 6, 7]])))
+        if e_h >= 1e-4 or e_r >= 1e-4:
+            # only a decision float32 cannot settle may move the robot off the reference's path: the inputs of the two decisions
+            # (t = 0, 0.25) as the REFERENCE's rows hold them, classified as in the action test
+            why = []
+            for t in (0, 20 // stride):
+                if t < len(c["robot_states"]):
+                    r = c["robot_states"][t]
+                    obs = np.concatenate([c["human_states"][t][:, [0, 1, 3, 4]], c["init_humans"][:, 8:9]], axis=1)
+                    why.append(_undetermined(c["policy"], [r[0], r[1], r[3], r[4], c["init_robot"][8]], obs))
+            assert any(why), (c["policy"], c["seed"], e_h, e_r)
+            undetermined.append((c["policy"], c["seed"], e_r, why))
+        else:
+            worst = max(worst, e_h, e_r)
+        if (col, succ, trunc) != (c["collision"], c["success"], c["truncated"]):
+            disagreements.append((c["policy"], c["seed"], (col, succ, trunc), (c["collision"], c["success"], c["truncated"]), _ref_margin(c)))
+    parity_util.record("g18_policy_no_train_episodes", worst, bar=1e-4)
+    print(f"G18 episodes: {len(eps)}, worst first-40-update error {worst:.2e} ({len(undetermined)} episodes off the path after a "
+          f"float32-undetermined decision: {undetermined}), outcome disagreements {disagreements}")
+    assert len(undetermined) <= 3
+    for d in disagreements:        # only a near-tie of the reference, or an episode a float32-undetermined decision moved, may end otherwise
+        assert min(d[4]) < 5e-3 or (d[0], d[1]) in {(u[0], u[1]) for u in undetermined}, d
