@@ -551,7 +551,7 @@ int big_world_buckets(int rows)
 
 size_t sfm_big_scratch_bytes(const cs_worlds* w)
 {
-    const int W = w->W, rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int W = w->W, rows = rows_of(w);
     const size_t state_bytes = ((size_t)W * rows * 13 * sizeof(float) + 255) & ~(size_t)255;
     const size_t misc = (((size_t)W * sizeof(float) + 255) & ~(size_t)255) + 2 * ((((size_t)W * rows * sizeof(float2)) + 255) & ~(size_t)255) + 256;
     return 2 * state_bytes + misc + grid_bytes(W, rows, big_world_buckets(rows));
@@ -562,7 +562,7 @@ size_t sfm_big_scratch_bytes(const cs_worlds* w)
 int sfm_big_launch(const cs_worlds* w, float dt, int n_substeps, float* d_out, int mutate_input, bool robot_from_array, const float* d_action,
                    float* d_peek, hipStream_t stream, float* d_trace)
 {
-    const int W = w->W, n = w->n, rows = n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int W = w->W, n = w->n, rows = rows_of(w);
     if (robot_from_array && !(w->flags & CS_ROBOT_ROW)) robot_from_array = false;
     const bool robot_moves = d_action != nullptr && w->d_robot != nullptr;
     const int NB = big_world_buckets(rows);
@@ -576,7 +576,7 @@ int sfm_big_launch(const cs_worlds* w, float dt, int n_substeps, float* d_out, i
     GArgs a;
     std::memset(&a, 0, sizeof(a));
     a.W = W; a.n = n; a.rows = rows; a.G = w->G; a.O = w->O; a.Smax = w->Smax; a.NB = NB; a.type = w->type; a.flags = w->flags; a.dt = dt;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)W * rows; }
+    state_strides(w, a.as, a.fs);
     a.goals = w->d_goals; a.params = w->d_params; a.safety = w->d_safety; a.obstacles = w->d_obstacles;
     a.bx = w->respawn_bound_x; a.by = w->respawn_bound_y; a.world_flags = w->d_world_flags; a.robot = w->d_robot; a.action = d_action;
     float* SA = (float*)base;

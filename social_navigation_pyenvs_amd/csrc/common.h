@@ -18,6 +18,64 @@ inline int fail(int code, const std::string& msg)
     return code;
 }
 
+// ---- what every entry point works out about a cs_worlds ----
+// rows per world: the humans, and the robot as the last row with CS_ROBOT_ROW
+inline int rows_of(const cs_worlds* w) { return w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0); }
+// agent / field strides of d_state (crowdstep.h CS_LAYOUT_*); the layout has been checked
+inline void state_strides(const cs_worlds* w, long& as, long& fs)
+{
+    if (w->layout == CS_LAYOUT_AOS) { as = 13; fs = 1; }
+    else { as = 1; fs = (long)w->W * rows_of(w); }
+}
+
+// Argument checks the entry points combine, each CS_OK or the fail() status and message; an entry runs the ones it needs in its own order
+inline int check_shape(const cs_worlds* w) { return w->W > 0 && w->n > 0 && w->G > 0 ? CS_OK : fail(CS_ERR_ARG, "W, n, G must be positive"); }
+// d_state, d_goals, d_safety and (with_params: the force models) d_params
+inline int check_buffers(const cs_worlds* w, bool with_params)
+{
+    return w->d_state && w->d_goals && (w->d_params || !with_params) && w->d_safety ? CS_OK : fail(CS_ERR_ARG, "null device buffer in cs_worlds");
+}
+// the entries that only read rows (rewards, observations, the robot's models: with_robot asks for d_robot as well)
+inline int check_rows(const cs_worlds* w, bool with_robot)
+{
+    if (w->W > 0 && w->n > 0 && w->d_state && (w->d_robot || !with_robot)) return CS_OK;
+    return fail(CS_ERR_ARG, with_robot ? "bad cs_worlds (a robot needs d_robot)" : "bad cs_worlds");
+}
+inline int check_layout(const cs_worlds* w) { return w->layout == CS_LAYOUT_AOS || w->layout == CS_LAYOUT_SOA ? CS_OK : fail(CS_ERR_ARG, "bad layout"); }
+inline int check_obstacles(const cs_worlds* w)
+{
+    return w->O == 0 || (w->O > 0 && w->d_obstacles && w->Smax > 0) ? CS_OK : fail(CS_ERR_ARG, "bad obstacle description");
+}
+// the nine SFM / HSFM models (forces_parallel.py:211 raises ValueError for any other type)
+inline int check_sfm_type(const cs_worlds* w)
+{
+    return w->type >= 0 && w->type <= 8 ? CS_OK : fail(CS_ERR_TYPE, "Type " + std::to_string(w->type) + " does not exist for this implementation");
+}
+// RVO2's parameters, for the crowd's ORCA steps and the robot's own ORCA model (up to 16 neighbours: ORCA_DEFAULTS uses 10)
+inline int check_orca(const cs_worlds* w)
+{
+    if (w->orca_max_neighbors < 0 || w->orca_max_neighbors > 16) return fail(CS_ERR_ARG, "orca_max_neighbors must be in 0..16");
+    if (!(w->orca_time_horizon > 0.0f) || !(w->orca_neighbor_dist >= 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
+    if (w->orca_n_vertices < 0 || (w->orca_n_vertices > 0 && !w->d_orca_vertices)) return fail(CS_ERR_ARG, "bad ORCA obstacle vertices");
+    if (w->orca_n_vertices > 0 && !(w->orca_time_horizon_obst > 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
+    return CS_OK;
+}
+// the arithmetic of the crowd's register-resident ORCA build (CS_ORCA_MATH_*)
+inline int check_orca_math(const cs_worlds* w)
+{
+    if (w->orca_math >= CS_ORCA_MATH_DEFAULT && w->orca_math <= CS_ORCA_MATH_FMA) return CS_OK;
+    return fail(CS_ERR_ARG, "cs_worlds.orca_math: CS_ORCA_MATH_DEFAULT / EXACT / FAST / FMA");
+}
+inline int check_gym_book(const cs_gym_book* b)
+{
+    if (b->clock_len > 0 && b->d_counter && b->d_seeds && b->d_mask && b->d_clock && b->d_reward && b->d_terminated && b->d_truncated && b->d_info) return CS_OK;
+    return fail(CS_ERR_ARG, "null buffer in cs_gym_book");
+}
+inline int check_stage_book(const cs_stage_book* b)
+{
+    return b->d_staged_seed && b->d_epoch && b->d_base_seed && b->d_staged_status ? CS_OK : fail(CS_ERR_ARG, "null buffer in cs_stage_book");
+}
+
 #ifdef CS_STAMPS
 extern unsigned long long* g_stamp_buf; // diagnostic build only (tools/stamp_probe.py)
 #endif

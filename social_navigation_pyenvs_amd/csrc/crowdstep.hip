@@ -118,6 +118,7 @@ namespace {
 
 using csimpl::fail;
 using csimpl::g_err;
+using namespace csimpl;
 
 using namespace cstep;
 
@@ -209,7 +210,7 @@ struct Geometry { int grid, block, wpb, ws; };
 
 int geometry(const cs_worlds* w, Geometry& g)
 {
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     if (rows <= 0) return fail(CS_ERR_ARG, "rows per world must be positive");
     if (rows > csimpl::big_world_min_rows(1024)) { g.block = 256; g.wpb = 1; g.ws = 0; g.grid = ((rows + 255) / 256) * w->W; return CS_OK; }   // grid path (bigworld.hip)
     if (rows <= 64) { g.block = 64; g.wpb = 64 / rows; }
@@ -228,19 +229,14 @@ int geometry(const cs_worlds* w, Geometry& g)
 int check_worlds(const cs_worlds* w)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->type < 0 || w->type > 8) return fail(CS_ERR_TYPE, "Type " + std::to_string(w->type) + " does not exist for this implementation");
-    if (w->W <= 0 || w->n <= 0 || w->G <= 0) return fail(CS_ERR_ARG, "W, n, G must be positive");
-    if (!w->d_state || !w->d_goals || !w->d_params || !w->d_safety) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_sfm_type(w)) || (rc = check_shape(w)) || (rc = check_buffers(w, true)) || (rc = check_obstacles(w)) || (rc = check_layout(w)))
+        return rc;
     return CS_OK;
 }
 
-void strides(const cs_worlds* w, int rows, long& as, long& fs)
-{
-    if (w->layout == CS_LAYOUT_AOS) { as = 13; fs = 1; }
-    else { as = 1; fs = (long)w->W * rows; }
-}
+// the mode of the entries that commit their substeps: the robot row comes from d_robot where there is one
+int commit_mode(const cs_worlds* w) { return M_COMMIT_GOALS | (((w->flags & CS_ROBOT_ROW) && w->d_robot) ? (int)M_ROBOT_FROM_ARRAY : 0); }
 
 // Which instantiation of k_sfm_step a launch runs.  One function decides it for launch_step and for cs_step_variant (the
 // diagnostic entry the parity tests use to assert that every benched build is the one they compared with the oracle).
@@ -249,7 +245,7 @@ struct RobotModel { int type; const float* params; float margin; const float* d_
 Variant select_variant(const cs_worlds* w, int mode, const Geometry& g, bool need_snap = false, bool robot_model = false)
 {
     const bool robot = (w->flags & CS_ROBOT_ROW) != 0;
-    const int rows = w->n + (robot ? 1 : 0);
+    const int rows = rows_of(w);
     const bool peq = (w->flags & CS_ALL_PARAMS_EQUAL) != 0;
     if (g.block != 64) return Variant{1024, 1, 0, 0, peq};
     // more than two one-wave blocks per SIMD -> the 4-waves-per-SIMD register budget pays (SIMD count asked from the device: a
@@ -379,7 +375,7 @@ int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, 
     Geometry g;
     rc = geometry(w, g);
     if (rc) return rc;
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     if (rows > csimpl::big_world_min_rows(1024))   // worlds beyond one block: partners through a uniform grid in HBM (bigworld.hip)
         return csimpl::sfm_big_launch(w, dt, nsub, d_out ? d_out : w->d_state, (mode & M_MUTATE_INPUT) ? 1 : 0,
                                       (mode & M_ROBOT_FROM_ARRAY) != 0, d_action, (mode & M_PEEK) ? d_peek : nullptr, stream, d_trace);
@@ -388,7 +384,7 @@ int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, 
     a.W = w->W; a.n = w->n; a.rows = rows; a.G = w->G; a.O = w->O; a.Smax = w->Smax;
     a.type = w->type; a.flags = w->flags; a.mode = mode; a.nsub = nsub; a.wpb = g.wpb; a.ws = g.ws; a.dt = dt;
     a.Sin = w->d_state; a.Sout = d_out ? d_out : w->d_state;
-    strides(w, rows, a.in_as, a.in_fs);
+    state_strides(w, a.in_as, a.in_fs);
     a.out_as = a.in_as; a.out_fs = a.in_fs;
     a.goals = w->d_goals; a.params = w->d_params; a.safety = w->d_safety; a.obstacles = w->d_obstacles;
     a.robot = w->d_robot; a.action = d_action; a.peek_out = d_peek;
@@ -537,8 +533,7 @@ int cs_step(const cs_worlds* w, float dt, int n_substeps, const float* d_action,
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
     if (w->type == CS_ORCA) return csimpl::orca_launch(w, dt, n_substeps, d_action, nullptr, (hipStream_t)stream);
     if (w->type == CS_SOCIAL_MOMENTUM) return csimpl::social_momentum_launch(w, dt, n_substeps, d_action, nullptr, (hipStream_t)stream);
-    int mode = M_COMMIT_GOALS;
-    if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
+    const int mode = commit_mode(w);
     return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream);
 }
 
@@ -547,15 +542,14 @@ int cs_step_observe(const cs_worlds* w, float dt, int n_substeps, const float* d
 {
     if (!w || !d_obs) return fail(CS_ERR_ARG, "null argument");
     if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     // the SFM / HSFM kernels of one block write the observation from their registers; everything else steps, then reads it back
     if (w->type < 0 || w->type > 8 || rows > csimpl::big_world_min_rows(1024)) {
         const int rc = cs_step(w, dt, n_substeps, d_action, stream);
         return rc ? rc : cs_gym_observe(w, theta_and_omega_visible, d_obs, stream);
     }
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
-    int mode = M_COMMIT_GOALS;
-    if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
+    const int mode = commit_mode(w);
     return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
                        theta_and_omega_visible ? 7 : 5);
 }
@@ -565,7 +559,7 @@ int cs_gym_step_is_one_launch(const cs_worlds* w)
     // ONE launch where the step kernel is the LDS kernel of one wavefront per block (SFM / HSFM worlds of up to 64 rows); the two
     // launches everywhere else (ORCA, social momentum, the DPP-row kernel's small worlds keep their own launch: same results)
     if (!w) return 0;
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     bool fused = w->type >= 0 && w->type <= 8 && rows <= 64 && w->W > 0 && w->n > 0;
     if (fused) {
         if (check_worlds(w)) fused = false;
@@ -573,9 +567,7 @@ int cs_gym_step_is_one_launch(const cs_worlds* w)
             Geometry g;
             if (geometry(w, g)) fused = false;
             else {
-                int mode = M_COMMIT_GOALS;
-                if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
-                fused = select_variant(w, mode, g).maxt == 64;   // (small plain worlds keep the DPP-row kernel and its own reward launch)
+                fused = select_variant(w, commit_mode(w), g).maxt == 64;   // (small plain worlds keep the DPP-row kernel and its own reward launch)
             }
         }
     }
@@ -595,11 +587,8 @@ int cs_gym_step(const cs_worlds* w, float dt, int n_substeps, const float* d_act
         return rc ? rc : cs_step_observe(w, dt, n_substeps, d_action, theta_and_omega_visible, d_obs, stream);
     }
     if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    if (book->clock_len <= 0 || !book->d_counter || !book->d_seeds || !book->d_mask || !book->d_clock || !book->d_reward ||
-        !book->d_terminated || !book->d_truncated || !book->d_info)
-        return fail(CS_ERR_ARG, "null buffer in cs_gym_book");
-    int mode = M_COMMIT_GOALS;
-    if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
+    if (const int rc = check_gym_book(book)) return rc;
+    const int mode = commit_mode(w);
     const GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
     return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
                        theta_and_omega_visible ? 7 : 5, &gh);
@@ -615,12 +604,9 @@ int cs_gym_step_staged(const cs_worlds* w, float dt, int n_substeps, const float
     if (!book->auto_reset && !book->d_prev_mask) return fail(CS_ERR_ARG, "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)");
     if (cs_gym_step_is_one_launch(w) != 2) return fail(CS_ERR_ARG, "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)");
     if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    if (book->clock_len <= 0 || !book->d_counter || !book->d_seeds || !book->d_mask || !book->d_clock || !book->d_reward ||
-        !book->d_terminated || !book->d_truncated || !book->d_info)
-        return fail(CS_ERR_ARG, "null buffer in cs_gym_book");
+    if (const int rc = check_gym_book(book)) return rc;
     if (book->d_seeds != stage_book->d_seeds) return fail(CS_ERR_ARG, "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer");
-    int mode = M_COMMIT_GOALS;
-    if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
+    const int mode = commit_mode(w);
     GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
     const int rc = csimpl::stage_fold(gen, staging, w, stage_book, theta_and_omega_visible ? 7 : 5, d_obs, gh.fold);
     if (rc) return rc;
@@ -634,8 +620,7 @@ int cs_step_trace(const cs_worlds* w, float dt, int n_substeps, const float* d_a
     if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
     if (w->type < 0 || w->type > 8) return fail(CS_ERR_ARG, "cs_step_trace covers the SFM / HSFM models (types 0..8)");
-    int mode = M_COMMIT_GOALS;
-    if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
+    const int mode = commit_mode(w);
     return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, d_trace);
 }
 
@@ -656,12 +641,12 @@ int cs_collision_reward(const cs_worlds* w, const float* d_action, float T, cons
 {
     // the swept test only reads positions, velocities and radii: every crowd model (0..8, ORCA, social momentum) qualifies
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || !w->d_state) return fail(CS_ERR_ARG, "bad cs_worlds");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_rows(w, false)) || (rc = check_layout(w))) return rc;
     if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     long as, fs;
-    strides(w, rows, as, fs);
+    state_strides(w, as, fs);
     if (w->n <= 64) {
         const int wpb = 64 / w->n, grid = (w->W + wpb - 1) / wpb;
         hipLaunchKernelGGL(k_collision_reward_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w->W, w->n, rows, wpb,
@@ -681,15 +666,12 @@ int cs_collision_reward_gym(const cs_worlds* w, const float* d_action, float T, 
                             float* d_out, const cs_gym_book* book, void* stream)
 {
     if (!w || !book) return fail(CS_ERR_ARG, "null argument");
-    if (w->W <= 0 || w->n <= 0 || !w->d_state) return fail(CS_ERR_ARG, "bad cs_worlds");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_rows(w, false)) || (rc = check_layout(w))) return rc;
     if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    if (book->clock_len <= 0 || !book->d_counter || !book->d_seeds || !book->d_mask || !book->d_clock || !book->d_reward ||
-        !book->d_terminated || !book->d_truncated || !book->d_info)
-        return fail(CS_ERR_ARG, "null buffer in cs_gym_book");
+    if ((rc = check_gym_book(book))) return rc;
     if (w->n > 64) {   // the lane-per-world reward kernel: the two launches
-        const int rc = cs_collision_reward(w, d_action, T, d_global_time, reward_cfg, d_out, stream);
-        if (rc) return rc;
+        if ((rc = cs_collision_reward(w, d_action, T, d_global_time, reward_cfg, d_out, stream))) return rc;
         if (book->d_prev_mask)
             return cs_gym_bookkeeping_next_step(w->W, d_out, book->d_counter, book->d_seeds, book->d_mask, book->d_prev_mask, d_global_time,
                                                 book->d_clock, book->clock_len, book->d_reward, book->d_terminated, book->d_truncated,
@@ -697,9 +679,9 @@ int cs_collision_reward_gym(const cs_worlds* w, const float* d_action, float T, 
         return cs_gym_bookkeeping(w->W, d_out, book->d_counter, book->d_seeds, book->d_mask, d_global_time, book->d_clock, book->clock_len,
                                   book->auto_reset, book->d_reward, book->d_terminated, book->d_truncated, book->d_info, book->seed_stride, stream);
     }
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     long as, fs;
-    strides(w, rows, as, fs);
+    state_strides(w, as, fs);
     const int wpb = 64 / w->n, grid = (w->W + wpb - 1) / wpb;
     hipLaunchKernelGGL(k_collision_reward_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w->W, w->n, rows, wpb,
                        (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action,
@@ -739,7 +721,7 @@ int cs_imitation_block(const cs_worlds* w, int32_t robot_type, const float* robo
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
     if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     // An invisible robot does not act on the crowd: the crowd's n substeps fuse into ONE launch that leaves what the robot's integrator
     // sees of it at every substep in a snapshot, and the robot's n substeps are ONE launch behind it -- 2 launches instead of 2 n.
     const bool fusable = !(w->flags & CS_ROBOT_ROW) && w->type >= 0 && w->type <= 8 && robot_type >= 0 && robot_type <= 8 &&
@@ -776,7 +758,7 @@ int cs_reserve_scratch(const cs_worlds* w, int n_substeps, void* stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
     if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     void* p = nullptr;
     int rc = CS_OK;
     if (w->type == CS_ORCA) {
@@ -810,7 +792,7 @@ int cs_step_variant(const cs_worlds* w, int entry, char* buf, size_t buflen)
     int mode = entry == 2 ? (int)M_PEEK : (int)M_COMMIT_GOALS;
     if (entry == 1) mode |= M_MUTATE_INPUT;
     if (entry != 1 && (w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
-    if (w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0) > csimpl::big_world_min_rows(1024)) {
+    if (rows_of(w) > csimpl::big_world_min_rows(1024)) {
         std::snprintf(buf, buflen, "k_bw_sfm_step<SOC=%d,HEADED=%d,PEQ=%d> grid=%d block=256 (uniform grid in HBM)", w->type % 3, w->type / 3,
                       (w->flags & CS_ALL_PARAMS_EQUAL) ? 1 : 0, g.grid);
         return CS_OK;
@@ -820,10 +802,11 @@ int cs_step_variant(const cs_worlds* w, int entry, char* buf, size_t buflen)
         std::snprintf(buf, buflen, "k_sfm_step_row16<SOC=%d,HEADED=%d,ROWS=%d> grid=%d block=64 wpb=4", w->type % 3, w->type / 3, v.rows_ct, (w->W + 3) / 4);
         return CS_OK;
     }
+    const size_t lds = step_lds_bytes(w, g, v.peq, nullptr, nullptr);
+    char wg[16] = "";
+    if (g.block == 64) std::snprintf(wg, sizeof(wg), " wg=%d", step_wg_waves_for(lds));
     std::snprintf(buf, buflen, "k_sfm_step<SOC=%d,HEADED=%d,PEQ=%d,MAXT=%d,OCC=%d,ROWS_CT=%d,LEAN=%d> grid=%d block=%d wpb=%d lds=%d%s",
-                  w->type % 3, w->type / 3, v.peq ? 1 : 0, v.maxt, v.occ, v.rows_ct, v.lean, g.grid, g.block, g.wpb,
-                  (int)step_lds_bytes(w, g, v.peq, nullptr, nullptr),
-                  g.block == 64 ? (step_wg_waves_for(step_lds_bytes(w, g, v.peq, nullptr, nullptr)) == 4 ? " wg=4" : (step_wg_waves_for(step_lds_bytes(w, g, v.peq, nullptr, nullptr)) == 2 ? " wg=2" : " wg=1")) : "");
+                  w->type % 3, w->type / 3, v.peq ? 1 : 0, v.maxt, v.occ, v.rows_ct, v.lean, g.grid, g.block, g.wpb, (int)lds, wg);
     return CS_OK;
 }
 

@@ -34,6 +34,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 constexpr int GEN_MAXN = 128; // humans per world the per-lane placement arrays hold
 
@@ -754,14 +755,13 @@ __global__ __launch_bounds__(64) void k_consume_staged(const StageArgs a)
 
 int fill_gen_out(const cs_worlds* w, GenOut& o)
 {
-    o.robot_row = (w->flags & CS_ROBOT_ROW) ? 1 : 0;
+    o.rows = rows_of(w);
+    o.robot_row = o.rows - w->n;
     o.orca = w->type == CS_ORCA ? 1 : 0;
-    o.rows = w->n + o.robot_row;
     o.G = w->G;
     o.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { o.as = 13; o.fs = 1; }
-    else if (w->layout == CS_LAYOUT_SOA) { o.as = 1; o.fs = (long)w->W * o.rows; }
-    else return fail(CS_ERR_ARG, "bad layout");
+    if (const int rc = check_layout(w)) return rc;
+    state_strides(w, o.as, o.fs);
     o.goals = w->d_goals;
     o.robot = w->d_robot;
     o.world_flags = const_cast<int*>(w->d_world_flags);
@@ -770,8 +770,8 @@ int fill_gen_out(const cs_worlds* w, GenOut& o)
 
 int check_generator(const cs_generator* gen, const cs_worlds* w)
 {
-    if (!w->d_state || !w->d_goals) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || w->G <= 0) return fail(CS_ERR_ARG, "W, n, G must be positive");
+    if (!w->d_state || !w->d_goals) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");   // (the generators write rows and goals only)
+    if (const int rc = check_shape(w)) return rc;
     if (gen->n != w->n) return fail(CS_ERR_ARG, "cs_generator.n differs from cs_worlds.n");
     if (gen->n > GEN_MAXN) return fail(CS_ERR_ARG, "the device generators place at most 128 humans per world");
     if (gen->scenario < CS_SCN_CIRCULAR_CROSSING || gen->scenario > CS_SCN_HYBRID) return fail(CS_ERR_ARG, "unknown scenario");
@@ -787,7 +787,7 @@ int check_generator(const cs_generator* gen, const cs_worlds* w)
 int stage_args(const cs_generator* gen, const cs_worlds* staging, const cs_worlds* live, const cs_stage_book* book, StageArgs& a)
 {
     if (!gen || !staging || !book) return fail(CS_ERR_ARG, "null argument");
-    if (!book->d_staged_seed || !book->d_epoch || !book->d_base_seed || !book->d_staged_status) return fail(CS_ERR_ARG, "null buffer in cs_stage_book");
+    if (const int rc = check_stage_book(book)) return rc;
     const int K = book->depth;
     if (K <= 0 || (K & (K - 1)) != 0) return fail(CS_ERR_ARG, "cs_stage_book.depth must be a power of two");
     if (staging->W % K != 0) return fail(CS_ERR_ARG, "the staging batch must hold depth * W worlds");
@@ -847,14 +847,13 @@ int cs_generate_worlds(const cs_generator* gen, const cs_worlds* w, const uint32
     GArgs a;
     a.g = *gen;
     a.W = w->W;
-    a.robot_row = (w->flags & CS_ROBOT_ROW) ? 1 : 0;
+    a.rows = rows_of(w);
+    a.robot_row = a.rows - w->n;
     a.orca = w->type == CS_ORCA ? 1 : 0;
-    a.rows = w->n + a.robot_row;
     a.G = w->G;
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; }
-    else if (w->layout == CS_LAYOUT_SOA) { a.as = 1; a.fs = (long)w->W * a.rows; }
-    else return fail(CS_ERR_ARG, "bad layout");
+    if (const int rc = check_layout(w)) return rc;
+    state_strides(w, a.as, a.fs);
     a.goals = w->d_goals;
     a.robot = w->d_robot;
     a.world_flags = const_cast<int*>(w->d_world_flags);

@@ -13,6 +13,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 __global__ void k_gym_observe(int W, int n, int rows, int C, const float* S, long as, long fs, float* obs)
 {
@@ -42,10 +43,11 @@ extern "C" {
 int cs_gym_observe(const cs_worlds* w, int theta_and_omega_visible, float* d_obs, void* stream)
 {
     if (!w || !d_obs || !w->d_state) return fail(CS_ERR_ARG, "null argument");
-    if (w->W <= 0 || w->n <= 0) return fail(CS_ERR_ARG, "bad cs_worlds");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0), C = theta_and_omega_visible ? 7 : 5;
-    const long as = w->layout == CS_LAYOUT_AOS ? 13 : 1, fs = w->layout == CS_LAYOUT_AOS ? 1 : (long)w->W * rows;
+    int rc;
+    if ((rc = check_rows(w, false)) || (rc = check_layout(w))) return rc;   // (d_state was checked above)
+    const int rows = rows_of(w), C = theta_and_omega_visible ? 7 : 5;
+    long as, fs;
+    state_strides(w, as, fs);
     const long total = (long)w->W * w->n * C;
     hipLaunchKernelGGL(k_gym_observe, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w->W, w->n, rows, C,
                        (const float*)w->d_state, as, fs, d_obs);
@@ -71,9 +73,9 @@ int cs_copy_worlds_masked_observe(const cs_worlds* src, const cs_worlds* dst, co
         return fail(CS_ERR_ARG, "source and destination worlds differ in shape");
     if (!src->d_state || !dst->d_state || !src->d_goals || !dst->d_goals) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");
     CopyArgs a;
-    a.W = src->W; a.n = src->n; a.rows = src->n + ((src->flags & CS_ROBOT_ROW) ? 1 : 0); a.G = src->G;
+    a.W = src->W; a.n = src->n; a.rows = rows_of(src); a.G = src->G;
     a.Ss = src->d_state; a.Sd = dst->d_state;
-    a.as = src->layout == CS_LAYOUT_AOS ? 13 : 1; a.fs = src->layout == CS_LAYOUT_AOS ? 1 : (long)src->W * a.rows;
+    state_strides(src, a.as, a.fs);
     a.sas = a.as; a.sfs = a.fs;
     a.gs = src->d_goals; a.gd = dst->d_goals; a.rs = src->d_robot; a.rd = dst->d_robot;
     a.fsrc = src->d_world_flags; a.fdst = const_cast<int*>(dst->d_world_flags); a.mask = d_mask; a.status = d_status;

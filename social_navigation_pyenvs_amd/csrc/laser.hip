@@ -18,6 +18,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 struct LArgs {
     int W, n, rows, O, Smax, samples, obstacles_shared;
@@ -80,18 +81,18 @@ extern "C" int cs_laser_scan(const cs_worlds* w, const float* d_pose, int pose_s
                              float max_distance, float* d_out, void* stream)
 {
     if (!w || !d_out) return fail(CS_ERR_ARG, "null argument");
-    if (w->W <= 0 || w->n < 0 || !w->d_state) return fail(CS_ERR_ARG, "bad cs_worlds");
+    if (w->W <= 0 || w->n < 0 || !w->d_state) return fail(CS_ERR_ARG, "bad cs_worlds");   // n = 0: a scan of the walls alone
     if (samples <= 0) return fail(CS_ERR_ARG, "samples must be positive");
     if (max_distance > 10.0f) return fail(CS_ERR_ARG, "Maxium distance for laser is 10 meters"); // sensors.py:13
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
+    int rc;
+    if ((rc = check_obstacles(w))) return rc;
     LArgs a;
-    a.W = w->W; a.n = w->n; a.rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    a.W = w->W; a.n = w->n; a.rows = rows_of(w);
     a.O = w->O; a.Smax = w->Smax; a.samples = samples;
     a.obstacles_shared = (w->flags & CS_OBSTACLES_SHARED) ? 1 : 0;
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; }
-    else if (w->layout == CS_LAYOUT_SOA) { a.as = 1; a.fs = (long)w->W * a.rows; }
-    else return fail(CS_ERR_ARG, "bad layout");
+    if ((rc = check_layout(w))) return rc;
+    state_strides(w, a.as, a.fs);
     if (d_pose) { a.pose = d_pose; a.pose_stride = pose_stride > 0 ? pose_stride : 3; }
     else if (w->d_robot) { a.pose = w->d_robot; a.pose_stride = 13; } // robot safe-state rows: px, py, theta first
     else return fail(CS_ERR_ARG, "no sensor pose: d_pose and cs_worlds.d_robot are both null");

@@ -45,9 +45,9 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 constexpr float RVO_EPSILON = 0.00001f;
-constexpr int KMAX = 16; // max_neighbors supported (ORCA_DEFAULTS uses 10)
 constexpr int KOBST = 16; // obstacle edges kept per agent (the nearest ones), static-obstacle worlds only
 
 struct OArgs {
@@ -1561,41 +1561,76 @@ static int orca_math_of(const cs_worlds* w)
     return m - CS_ORCA_MATH_EXACT;
 }
 
-// dynamic LDS of the one-block kernel (k_orca_step) for these worlds: [2][T] rows + radii / respawn scratch, and either the
-// register-resident build's line copies (maxNeighbors = 10, no obstacles) or the generic build's per-agent columns
-static size_t orca_block_shmem(const cs_worlds* w, bool lp3_static)
+// How orca_launch runs these worlds: one plan for the launch, cs_reserve_scratch (orca_uses_grid) and the name cs_step_variant reports, as
+// select_variant serves the SFM path
+struct OrcaPlan {
+    bool grid;          // the grid path (orca_big_launch): more than 512 rows, or generic-build columns beyond a block's 160 KB of LDS
+    int rows, T, wpb;   // one-block path: block size (worlds of more than 64 rows: one world per block) and worlds per block
+    bool fast10;        // the register-resident solve: maxNeighbors = 10, no obstacle lines, one parameter set
+    int KO;             // obstacle lines kept per agent
+    int lp3_static;     // linearProgram3 as the statically unrolled walk (lp3_fast10) instead of lp3_rows
+    int fm;             // template parameter FM of the register-resident build: 0 exact, 1 fast, 2 fma (the generic builds are always exact)
+    size_t shmem;       // dynamic LDS of a block
+};
+
+OrcaPlan orca_plan(const cs_worlds* w)
 {
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
-    const int T = rows <= 64 ? 64 : (rows <= 256 ? 256 : 512);
-    const int wpb = rows <= 64 ? 64 / rows : 1;
-    const int TL = wpb * rows;
+    OrcaPlan p;
+    p.rows = rows_of(w);
+    p.T = p.rows <= 64 ? 64 : (p.rows <= 256 ? 256 : 512);
+    p.wpb = p.rows <= 64 ? 64 / p.rows : 1;
     const int K = w->orca_max_neighbors, nv = w->orca_n_vertices;
-    const int KO = nv > 0 ? (nv < KOBST ? nv : KOBST) : 0;
-    const bool fast10 = K == 10 && nv == 0 && w->d_orca_agent_params == nullptr;
-    return (size_t)T * (2 * sizeof(float4) + 4 * sizeof(float)) +
-           (fast10 ? (size_t)10 * TL * sizeof(float4) + (lp3_static ? 0 : 72 * (sizeof(float4) + sizeof(float2))) + (size_t)T * (sizeof(float4) + sizeof(int))
-                   : (size_t)(K + KO) * TL * (2 * sizeof(float4) + 2 * sizeof(float)));
+    p.KO = nv > 0 ? (nv < KOBST ? nv : KOBST) : 0;
+    p.fast10 = K == 10 && nv == 0 && w->d_orca_agent_params == nullptr;
+    p.fm = p.fast10 ? orca_math_of(w) : 0;
+    const char* lp3_env = std::getenv("CROWDSTEP_ORCA_LP3");   // A/B switch: =static keeps every build on the unrolled walk
+    const bool lp3_env_static = lp3_env && std::strcmp(lp3_env, "static") == 0;
+    // dynamic LDS of the one-block kernel (k_orca_step): [2][T] rows + radii / respawn scratch, and either the register-resident build's line
+    // copies or the generic build's per-agent columns (TL = lanes that hold an agent: the width of the per-lane LDS columns)
+    const int TL = p.wpb * p.rows;
+    auto block_shmem = [&](bool lp3_static) {
+        return (size_t)p.T * (2 * sizeof(float4) + 4 * sizeof(float)) +
+               (p.fast10 ? (size_t)10 * TL * sizeof(float4) + (lp3_static ? 0 : 72 * (sizeof(float4) + sizeof(float2))) + (size_t)p.T * (sizeof(float4) + sizeof(int))
+                         : (size_t)(K + p.KO) * TL * (2 * sizeof(float4) + 2 * sizeof(float)));
+    };
+    p.grid = p.rows > big_world_min_rows(512) || block_shmem(true) > 160 * 1024;
+    if (p.grid) {
+        p.lp3_static = lp3_env_static ? 1 : 0;
+        p.shmem = p.fast10 ? (size_t)(10 * 64 + 72 + 64) * sizeof(float4) + 72 * sizeof(float2) + 64 * sizeof(int)
+                           : (size_t)(K + p.KO) * 64 * (2 * sizeof(float4)) + (size_t)(K + p.KO) * 64 * (sizeof(float) + sizeof(int));
+    } else {
+        // linearProgram3 of the register-resident build: one 16-lane row per (agent, violated line) (lp3_rows) in one-wavefront blocks;
+        // worlds of more than 64 rows keep the statically unrolled walk (their blocks have no LDS left for the projected lines)
+        p.lp3_static = (p.T > 64 || lp3_env_static) ? 1 : 0;
+        p.shmem = block_shmem(p.lp3_static != 0);
+    }
+    return p;
 }
 
-// worlds of more than 512 rows, and worlds whose generic-build columns outgrow a block's 160 KB of LDS, take the grid path
-bool orca_uses_grid(const cs_worlds* w)
+// what orca_launch checks before it plans (cs_step_variant runs the same checks)
+int check_orca_worlds(const cs_worlds* w)
 {
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
-    return rows > big_world_min_rows(512) || orca_block_shmem(w, true) > 160 * 1024;
+    if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
+    int rc;
+    if ((rc = check_shape(w)) || (rc = check_buffers(w, false))) return rc;
+    if (w->O != 0) return fail(CS_ERR_ARG, "ORCA worlds take their static obstacles as RVO2 vertex records "
+                                              "(cs_worlds.d_orca_vertices), not as the SFM segment array");
+    if ((rc = check_orca(w)) || (rc = check_orca_math(w))) return rc;
+    return CS_OK;
 }
+
+bool orca_uses_grid(const cs_worlds* w) { return orca_plan(w).grid; }
 
 size_t orca_big_scratch_bytes(const cs_worlds* w)
 {
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     const size_t state_bytes = (size_t)w->W * rows * 13 * sizeof(float);
     return ((state_bytes + 255) & ~(size_t)255) + grid_bytes(w->W, rows, big_world_buckets(rows));
 }
 
-static int orca_big_launch(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float* d_peek, hipStream_t stream)
+static int orca_big_launch(const cs_worlds* w, const OrcaPlan& p, float dt, int n_substeps, const float* d_action, float* d_peek, hipStream_t stream)
 {
-    const int n = w->n, W = w->W;
-    const bool robot_row = (w->flags & CS_ROBOT_ROW) != 0;
-    const int rows = n + (robot_row ? 1 : 0);
+    const int n = w->n, W = w->W, rows = p.rows;
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "a robot action needs cs_worlds.d_robot");
     const int NB = big_world_buckets(rows);
     const size_t state_bytes = (size_t)W * rows * 13 * sizeof(float);
@@ -1607,23 +1642,20 @@ static int orca_big_launch(const cs_worlds* w, float dt, int n_substeps, const f
     }
     BigArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.W = W; a.n = n; a.rows = rows; a.robot_row = robot_row ? 1 : 0; a.flags = w->flags; a.G = w->G; a.NB = NB; a.dt = dt;
+    a.W = W; a.n = n; a.rows = rows; a.robot_row = rows - n; a.flags = w->flags; a.G = w->G; a.NB = NB; a.dt = dt;
     a.neighbor_dist = w->orca_neighbor_dist; a.time_horizon = w->orca_time_horizon;
     // cell edge = neighborDist (a floor keeps a degenerate neighborDist = 0 from dividing by zero: nobody is a neighbour then)
     a.inv_cell = 1.0f / (w->orca_neighbor_dist > 1e-3f ? w->orca_neighbor_dist : 1e-3f);
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)W * rows; }
+    state_strides(w, a.as, a.fs);
     a.goals = w->d_goals; a.margin = w->d_safety;
     a.robot = w->d_robot; a.action = d_action;
     a.K = w->orca_max_neighbors; a.nv = w->orca_n_vertices; a.verts = w->d_orca_vertices; a.time_horizon_obst = w->orca_time_horizon_obst;
-    a.KO = a.nv > 0 ? (a.nv < KOBST ? a.nv : KOBST) : 0;
+    a.KO = p.KO;
     a.agent_params = w->d_orca_agent_params;
-    const bool fast10 = a.K == 10 && a.nv == 0 && a.agent_params == nullptr;   // the register-resident solve: no obstacle lines, one parameter set
+    a.lp3_static = p.lp3_static;
     float* S2 = (float*)base;
     void* grid_mem = base + state_pad;
-    const char* lp3_env = std::getenv("CROWDSTEP_ORCA_LP3");
-    a.lp3_static = (lp3_env && std::strcmp(lp3_env, "static") == 0) ? 1 : 0;
-    const size_t shmem = fast10 ? (size_t)(10 * 64 + 72 + 64) * sizeof(float4) + 72 * sizeof(float2) + 64 * sizeof(int)
-                                : (size_t)(a.K + a.KO) * 64 * (2 * sizeof(float4)) + (size_t)(a.K + a.KO) * 64 * (sizeof(float) + sizeof(int));
+    const size_t shmem = p.shmem;
     if (shmem > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void*)k_bw_orca_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     HIP_TRY(hipMemcpyAsync(S2, w->d_state, state_bytes, hipMemcpyDeviceToDevice, stream));   // the columns a step does not write
@@ -1636,7 +1668,7 @@ static int orca_big_launch(const cs_worlds* w, float dt, int n_substeps, const f
         const int rcg = grid_build(cur, a.as, a.fs, W, rows, NB, nullptr, a.inv_cell, grid_mem, g, stream);
         if (rcg) return rcg;
         a.cellxy = g.cellxy; a.start = g.start; a.sorted = g.sorted;
-        if (fast10) hipLaunchKernelGGL(k_bw_orca_step<true>, dim3((rows + 63) / 64, W), dim3(64), shmem, stream, a);
+        if (p.fast10) hipLaunchKernelGGL(k_bw_orca_step<true>, dim3((rows + 63) / 64, W), dim3(64), shmem, stream, a);
         else hipLaunchKernelGGL(k_bw_orca_step<false>, dim3((rows + 63) / 64, W), dim3(64), shmem, stream, a);
         if (d_peek) { HIP_TRY(hipGetLastError()); return CS_OK; }
         if (w->flags & CS_RESPAWN)
@@ -1650,53 +1682,38 @@ static int orca_big_launch(const cs_worlds* w, float dt, int n_substeps, const f
 
 int orca_launch(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float* d_peek, hipStream_t stream)
 {
-    if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || w->G <= 0) return fail(CS_ERR_ARG, "W, n, G must be positive");
-    if (!w->d_state || !w->d_goals || !w->d_safety) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");
-    if (w->O != 0) return fail(CS_ERR_ARG, "ORCA worlds take their static obstacles as RVO2 vertex records "
-                                              "(cs_worlds.d_orca_vertices), not as the SFM segment array");
-    if (w->orca_n_vertices < 0 || (w->orca_n_vertices > 0 && !w->d_orca_vertices)) return fail(CS_ERR_ARG, "bad ORCA obstacle vertices");
-    if (w->orca_n_vertices > 0 && !(w->orca_time_horizon_obst > 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
-    if (w->orca_max_neighbors < 0 || w->orca_max_neighbors > KMAX) return fail(CS_ERR_ARG, "orca_max_neighbors must be in 0..16");
-    if (!(w->orca_time_horizon > 0.0f) || !(w->orca_neighbor_dist >= 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
-    if (w->orca_math < CS_ORCA_MATH_DEFAULT || w->orca_math > CS_ORCA_MATH_FMA) return fail(CS_ERR_ARG, "cs_worlds.orca_math: CS_ORCA_MATH_DEFAULT / EXACT / FAST / FMA");
-    if (orca_uses_grid(w)) return orca_big_launch(w, dt, n_substeps, d_action, d_peek, stream);
+    if (const int rc = check_orca_worlds(w)) return rc;
+    const OrcaPlan p = orca_plan(w);
+    if (p.grid) return orca_big_launch(w, p, dt, n_substeps, d_action, d_peek, stream);
     OArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.W = w->W; a.n = w->n; a.rows = rows; a.G = w->G; a.flags = w->flags; a.nsub = n_substeps;
-    a.wpb = rows <= 64 ? 64 / rows : 1; a.K = w->orca_max_neighbors;
+    a.W = w->W; a.n = w->n; a.rows = p.rows; a.G = w->G; a.flags = w->flags; a.nsub = n_substeps;
+    a.wpb = p.wpb; a.K = w->orca_max_neighbors;
     a.dt = dt; a.neighbor_dist = w->orca_neighbor_dist; a.time_horizon = w->orca_time_horizon;
     a.bx = w->respawn_bound_x; a.by = w->respawn_bound_y;
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * rows; }
+    state_strides(w, a.as, a.fs);
     a.goals = w->d_goals; a.margin = w->d_safety; a.robot = w->d_robot; a.action = d_action;
     a.peek_out = d_peek; a.world_flags = w->d_world_flags;
     a.verts = w->d_orca_vertices; a.nv = w->orca_n_vertices; a.time_horizon_obst = w->orca_time_horizon_obst;
-    a.KO = a.nv > 0 ? (a.nv < KOBST ? a.nv : KOBST) : 0;
+    a.KO = p.KO;
 #ifdef CS_STAMPS
     a.stamps = g_stamp_buf;
 #endif
     if (d_peek) a.flags &= ~CS_RESPAWN;
-    const int T = rows <= 64 ? 64 : (rows <= 256 ? 256 : 512);   // worlds of more than 64 rows: one world per block
+    const int T = p.T, fm = p.fm;
+    const bool fast10 = p.fast10;
     const int grid = (w->W + a.wpb - 1) / a.wpb;
     a.agent_params = w->d_orca_agent_params;
-    const bool fast10 = a.K == 10 && a.nv == 0 && a.agent_params == nullptr; // the register-resident solve: no obstacle lines, one parameter set
-    const int TL = a.wpb * rows;                // lanes that hold an agent: the width of the per-lane LDS columns
-    // linearProgram3 of the register-resident build: one 16-lane row per (agent, violated line) (lp3_rows) in one-wavefront blocks;
-    // worlds of more than 64 rows keep the statically unrolled walk (their blocks have no LDS left for the projected lines)
-    const char* lp3_env = std::getenv("CROWDSTEP_ORCA_LP3");
-    a.lp3_static = (T > 64 || (lp3_env && std::strcmp(lp3_env, "static") == 0)) ? 1 : 0;
-    const size_t shmem = orca_block_shmem(w, a.lp3_static != 0);
+    a.lp3_static = p.lp3_static;
     a.young_from = (T == 64 && grid == 2 * csimpl::device_simds()) ? grid / 2 : 0x7fffffff;
     auto launch = [&](auto kernel) -> int {
-        if (shmem > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(T), shmem, stream, a);
+        if (p.shmem > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.shmem));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(T), p.shmem, stream, a);
         return CS_OK;
     };
     int rc;
-    const int fm = fast10 ? orca_math_of(w) : 0;   // the generic build (other maxNeighbors, static obstacles, per-agent parameters) is always exact
     if (T == 64) {
         if (!fast10) rc = launch(k_orca_step<false, 64>);
         else rc = fm == 0 ? launch(k_orca_step<true, 64, 0>) : (fm == 1 ? launch(k_orca_step<true, 64, 1>) : launch(k_orca_step<true, 64, 2>));
@@ -1714,34 +1731,29 @@ int orca_launch(const cs_worlds* w, float dt, int n_substeps, const float* d_act
 
 int orca_variant(const cs_worlds* w, char* buf, size_t buflen)
 {
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
-    const int T = rows <= 64 ? 64 : (rows <= 256 ? 256 : 512);
-    const bool fast10 = w->orca_max_neighbors == 10 && w->orca_n_vertices == 0 && w->d_orca_agent_params == nullptr;
-    const int wpb = rows <= 64 ? 64 / rows : 1;
-    if (orca_uses_grid(w)) {
-        std::snprintf(buf, buflen, "k_bw_orca_step<FAST10=%d> grid=(%d,%d) block=64 (one launch per substep)", fast10 ? 1 : 0, (rows + 63) / 64, w->W);
+    if (const int rc = check_orca_worlds(w)) return rc;
+    const OrcaPlan p = orca_plan(w);
+    if (p.grid) {
+        std::snprintf(buf, buflen, "k_bw_orca_step<FAST10=%d> grid=(%d,%d) block=64 (one launch per substep)", p.fast10 ? 1 : 0, (p.rows + 63) / 64, w->W);
         return CS_OK;
     }
-    std::snprintf(buf, buflen, "k_orca_step<FAST10=%d,MAXT=%d> grid=%d block=%d wpb=%d math=%s", fast10 ? 1 : 0, T, (w->W + wpb - 1) / wpb, T, wpb,
-                  !fast10 ? "exact" : (orca_math_of(w) == 0 ? "exact" : (orca_math_of(w) == 1 ? "fast" : "fma")));
+    std::snprintf(buf, buflen, "k_orca_step<FAST10=%d,MAXT=%d> grid=%d block=%d wpb=%d math=%s", p.fast10 ? 1 : 0, p.T, (w->W + p.wpb - 1) / p.wpb, p.T,
+                  p.wpb, p.fm == 0 ? "exact" : (p.fm == 1 ? "fast" : "fma"));
     return CS_OK;
 }
 
 int orca_robot_launch(const cs_worlds* w, float robot_margin, const float* d_human_margin, float dt, hipStream_t stream, int just_velocities)
 {
-    if (w->orca_max_neighbors < 0 || w->orca_max_neighbors > KMAX) return fail(CS_ERR_ARG, "orca_max_neighbors must be in 0..16");
-    if (!(w->orca_time_horizon > 0.0f) || !(w->orca_neighbor_dist >= 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
-    if (w->orca_n_vertices < 0 || (w->orca_n_vertices > 0 && !w->d_orca_vertices)) return fail(CS_ERR_ARG, "bad ORCA obstacle vertices");
-    if (w->orca_n_vertices > 0 && !(w->orca_time_horizon_obst > 0.0f)) return fail(CS_ERR_ARG, "bad ORCA parameters");
+    if (const int rc = check_orca(w)) return rc;
     ORArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.W = w->W; a.n = w->n; a.robot_row = (w->flags & CS_ROBOT_ROW) ? 1 : 0; a.rows = w->n + a.robot_row;
+    a.W = w->W; a.n = w->n; a.rows = rows_of(w); a.robot_row = a.rows - a.n;
     a.write_row = a.robot_row && w->type != CS_ORCA;   // an ORCA crowd takes the moved robot after its own doStep (:389)
     a.K = w->orca_max_neighbors; a.nv = w->orca_n_vertices; a.KO = a.nv > 0 ? (a.nv < KOBST ? a.nv : KOBST) : 0;
     a.dt = dt; a.neighbor_dist = w->orca_neighbor_dist; a.time_horizon = w->orca_time_horizon;
     a.time_horizon_obst = w->orca_time_horizon_obst; a.robot_margin = robot_margin;
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * a.rows; }
+    state_strides(w, a.as, a.fs);
     a.hmargin = d_human_margin; a.robot = w->d_robot; a.verts = w->d_orca_vertices; a.just_velocities = just_velocities ? 1 : 0;
     const size_t shmem = (size_t)(a.K + a.KO) * 64 * (2 * sizeof(float4) + 2 * sizeof(float));
     if (shmem > 64 * 1024)

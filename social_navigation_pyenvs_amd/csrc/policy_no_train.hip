@@ -25,12 +25,7 @@ constexpr int WAVES_PER_BLOCK = 4;
 
 struct PntParams { float p[CS_PNT_N_PARAMS]; };
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-}
+using rmodel::wave_sum;
 
 __device__ __forceinline__ void toward_goal(float px, float py, float gx, float gy, float vd, float* out)
 {

@@ -27,6 +27,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 struct KArgsRk {
     int W, n, rows, G, O, Smax, type, flags;
@@ -45,24 +46,9 @@ struct KArgsRk {
     float* dense;
 };
 
-constexpr float PI_F = 3.14159265358979323846f;
-constexpr float TWO_PI_F = 6.28318530717958647692f;
-
-__device__ __forceinline__ float bound_angle(float a)   // utils.py:7-13
-{
-    if (a >= TWO_PI_F) a = fmodf(a, TWO_PI_F);
-    if (a <= -TWO_PI_F) a = fmodf(a, TWO_PI_F);
-    if (a > PI_F) a -= TWO_PI_F;
-    if (a < -PI_F) a += TWO_PI_F;
-    return a;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using rmodel::PI_F;
+using rmodel::bound_angle;
+using rmodel::wave_sum;
 
 // compute_pairwise_social_force(kind, agent1, agent2) (forces.py:63-128): force on agent 1; r1 / r2 = radius + safety_space
 __device__ __forceinline__ void pair_force(int kind, const float* P, float p1x, float p1y, float v1x, float v1y, float r1, float p2x,
@@ -462,7 +448,7 @@ __global__ __launch_bounds__(64) void k_robot_rk45(const KArgsRobotRk a)
     auto set_state = [&](const float (&yt)[NS]) {   // set_new_*_state_from_rk45_solution(robot, y), :88-103
         r.px = yt[0]; r.py = yt[1];
         if (HEADED) {
-            r.yaw = rmodel::bound_angle(yt[2]);
+            r.yaw = bound_angle(yt[2]);
             r.bvx = yt[3]; r.bvy = yt[4];
             const float sp = sqrtf(r.bvx * r.bvx + r.bvy * r.bvy);
             if (sp > r.vd) { r.bvx = r.bvx / sp * r.vd; r.bvy = r.bvy / sp * r.vd; }
@@ -516,19 +502,18 @@ __global__ __launch_bounds__(64) void k_robot_rk45(const KArgsRobotRk a)
 int rk45_launch(const cs_worlds* w, float dt, float t_final, float eval_dt, int n_eval, float* d_memory, float* d_dense, int32_t* d_nfev, void* stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->type < 0 || w->type > 8) return fail(CS_ERR_TYPE, "Type " + std::to_string(w->type) + " does not exist for this implementation");
-    if (w->W <= 0 || w->n <= 0 || w->G <= 0) return fail(CS_ERR_ARG, "W, n, G must be positive");
-    if (!w->d_state || !w->d_goals || !w->d_params || !w->d_safety || !d_memory) return fail(CS_ERR_ARG, "null device buffer");
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_sfm_type(w)) || (rc = check_shape(w)) || (rc = check_buffers(w, true))) return rc;
+    if (!d_memory) return fail(CS_ERR_ARG, "null device buffer");
+    if ((rc = check_obstacles(w)) || (rc = check_layout(w))) return rc;
     if (!(dt > 0.0f)) return fail(CS_ERR_ARG, "dt must be positive");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     if (rows > 64) return fail(CS_ERR_ARG, "the RK45 step supports up to 64 rows per world");
     KArgsRk a;
     std::memset(&a, 0, sizeof(a));
     a.W = w->W; a.n = w->n; a.rows = rows; a.G = w->G; a.O = w->O; a.Smax = w->Smax; a.type = w->type; a.flags = w->flags;
     a.dt = dt; a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * rows; }
+    state_strides(w, a.as, a.fs);
     a.goals = w->d_goals; a.params = w->d_params; a.safety = w->d_safety; a.obstacles = w->d_obstacles;
     a.memory = d_memory; a.nfev = d_nfev;
     a.t_final = t_final; a.eval_dt = eval_dt; a.n_eval = n_eval; a.dense = d_dense;
@@ -563,24 +548,24 @@ int cs_robot_model_rk45(const cs_worlds* w, int32_t robot_type, const float* rob
                         float* d_robot_memory, float dt, int32_t* d_nfev, void* stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || !w->d_state || !w->d_robot) return fail(CS_ERR_ARG, "bad cs_worlds (a robot needs d_robot)");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_rows(w, true)) || (rc = check_layout(w))) return rc;
     const float* hm = d_human_margin ? d_human_margin : w->d_safety;
     if (!hm || !robot_params || !d_robot_memory) return fail(CS_ERR_ARG, "null argument");
     if (robot_type < 0 || robot_type > 8) return fail(CS_ERR_TYPE, "Runge-Kutta integration of the robot takes one of the nine SFM / HSFM models");
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
+    if ((rc = check_obstacles(w))) return rc;
     if (!(dt > 0.0f)) return fail(CS_ERR_ARG, "dt must be positive");
     if (w->n > 64) return fail(CS_ERR_ARG, "the robot's RK45 step supports up to 64 humans per world");
     KArgsRobotRk a;
     std::memset(&a, 0, sizeof(a));
-    a.W = w->W; a.n = w->n; a.rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    a.W = w->W; a.n = w->n; a.rows = rows_of(w);
     // as robot_step_impl (robot_model.hip): an ORCA crowd's simulator sees the moved robot only after its own doStep (motion_model_manager.py:389)
     a.write_row = ((w->flags & CS_ROBOT_ROW) && w->type != CS_ORCA) ? 1 : 0;
     a.O = w->O; a.Smax = w->Smax; a.type = robot_type; a.obstacles_shared = (w->flags & CS_OBSTACLES_SHARED) ? 1 : 0;
     a.dt = dt; a.robot_margin = robot_margin;
     std::memcpy(a.P, robot_params, sizeof(a.P));
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * a.rows; }
+    state_strides(w, a.as, a.fs);
     a.hmargin = hm; a.robot = w->d_robot; a.memory = d_robot_memory; a.obstacles = w->d_obstacles; a.nfev = d_nfev;
     if (robot_type >= CS_HSFM_FARINA) hipLaunchKernelGGL(k_robot_rk45<true>, dim3(w->W), dim3(64), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_robot_rk45<false>, dim3(w->W), dim3(64), 0, (hipStream_t)stream, a);

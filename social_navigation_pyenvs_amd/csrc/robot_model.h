@@ -28,6 +28,14 @@ __device__ __forceinline__ float bound_angle(float a)
     return a;
 }
 
+// sum over the 64 lanes of a wavefront, xor butterfly (every lane gets the total; robot_model.hip's DPP / readlane sum adds in another order)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // the robot's dynamic state and what its model remembers between substeps (agent.desired_force)
 struct RState {
     float px, py, yaw, vx, vy, bvx, bvy, om;

@@ -32,6 +32,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 struct RArgs {
     int W, n, rows, O, Smax, type, robot_row, write_row, obstacles_shared;
@@ -293,24 +294,24 @@ static int robot_step_impl(const cs_worlds* w, int32_t robot_type, const float* 
                            const float* d_human_margin, float* d_robot_memory, float dt, int just_velocities, void* stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || !w->d_state || !w->d_robot) return fail(CS_ERR_ARG, "bad cs_worlds (a robot needs d_robot)");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_rows(w, true)) || (rc = check_layout(w))) return rc;
     const float* hm = d_human_margin ? d_human_margin : w->d_safety;
     if (!hm) return fail(CS_ERR_ARG, "no human margins");
     if (robot_type == CS_ORCA) return csimpl::orca_robot_launch(w, robot_margin, hm, dt, (hipStream_t)stream, just_velocities);
     if (robot_type < 0 || robot_type > 8)
         return fail(CS_ERR_TYPE, "The robot motion model '" + std::to_string(robot_type) + "' does not exist");
     if (!robot_params || !d_robot_memory) return fail(CS_ERR_ARG, "null argument");
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
+    if ((rc = check_obstacles(w))) return rc;
     RArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.W = w->W; a.n = w->n; a.robot_row = (w->flags & CS_ROBOT_ROW) ? 1 : 0; a.rows = w->n + a.robot_row;
+    a.W = w->W; a.n = w->n; a.rows = rows_of(w); a.robot_row = a.rows - a.n;
     a.write_row = a.robot_row && w->type != CS_ORCA;   // an ORCA crowd's simulator sees the moved robot only after its doStep (:389)
     a.O = w->O; a.Smax = w->Smax; a.type = robot_type; a.obstacles_shared = (w->flags & CS_OBSTACLES_SHARED) ? 1 : 0;
     a.dt = dt; a.robot_margin = robot_margin;
     std::memcpy(a.P, robot_params, sizeof(a.P));
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * a.rows; }
+    state_strides(w, a.as, a.fs);
     a.hmargin = hm; a.robot = w->d_robot; a.memory = d_robot_memory; a.obstacles = w->d_obstacles;
     a.snap = nullptr; a.nsub = 1; a.just_velocities = just_velocities;
     const int wpb = 4;
@@ -323,12 +324,12 @@ int cs_actual_collision_reward(const cs_worlds* w, float T, const float* d_globa
                                void* stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || !w->d_state) return fail(CS_ERR_ARG, "bad cs_worlds");
-    if (w->layout != CS_LAYOUT_AOS && w->layout != CS_LAYOUT_SOA) return fail(CS_ERR_ARG, "bad layout");
+    int rc;
+    if ((rc = check_rows(w, false)) || (rc = check_layout(w))) return rc;
     if (!d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    const int rows = rows_of(w);
     long as, fs;
-    if (w->layout == CS_LAYOUT_AOS) { as = 13; fs = 1; } else { as = 1; fs = (long)w->W * rows; }
+    state_strides(w, as, fs);
     const int block = 64;
     hipLaunchKernelGGL(k_actual_collision_reward, dim3((w->W + block - 1) / block), dim3(block), 0, (hipStream_t)stream, w->W, w->n,
                        rows, w->d_state, as, fs, w->d_robot, T, d_global_time, reward_cfg[0], reward_cfg[1], reward_cfg[2],
@@ -360,7 +361,7 @@ int csimpl::robot_block_launch(const cs_worlds* w, int robot_type, const float* 
 {
     const float* hm = d_human_margin ? d_human_margin : w->d_safety;
     if (!hm || !robot_params || !d_robot_memory || !d_snap) return fail(CS_ERR_ARG, "null argument");
-    if (w->O < 0 || (w->O > 0 && (!w->d_obstacles || w->Smax <= 0))) return fail(CS_ERR_ARG, "bad obstacle description");
+    if (const int rc = check_obstacles(w)) return rc;
     RArgs a;
     std::memset(&a, 0, sizeof(a));
     a.W = w->W; a.n = w->n; a.robot_row = 0; a.rows = w->n; a.write_row = 0;
@@ -368,7 +369,7 @@ int csimpl::robot_block_launch(const cs_worlds* w, int robot_type, const float* 
     a.dt = dt; a.robot_margin = robot_margin;
     std::memcpy(a.P, robot_params, sizeof(a.P));
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * a.rows; }
+    state_strides(w, a.as, a.fs);   // (no robot row: the fused imitation block's worlds)
     a.hmargin = hm; a.robot = w->d_robot; a.memory = d_robot_memory; a.obstacles = w->d_obstacles;
     a.snap = d_snap; a.nsub = n_substeps;
     const int wpb = 4;

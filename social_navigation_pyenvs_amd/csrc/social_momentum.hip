@@ -28,6 +28,7 @@
 namespace {
 
 using csimpl::fail;
+using namespace csimpl;
 
 constexpr int SM_MAX_ACTIONS = 64;
 constexpr float SM_LAMBDA = 0.11f; // social_momentum.py:8
@@ -218,9 +219,9 @@ namespace csimpl {
 int social_momentum_launch(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float* d_peek, hipStream_t stream)
 {
     if (!w) return fail(CS_ERR_ARG, "null cs_worlds");
-    if (w->W <= 0 || w->n <= 0 || w->G <= 0) return fail(CS_ERR_ARG, "W, n, G must be positive");
-    if (!w->d_state || !w->d_goals || !w->d_safety) return fail(CS_ERR_ARG, "null device buffer in cs_worlds");
-    const int rows = w->n + ((w->flags & CS_ROBOT_ROW) ? 1 : 0);
+    int rc;
+    if ((rc = check_shape(w)) || (rc = check_buffers(w, false))) return rc;
+    const int rows = rows_of(w);
     if (rows > 64) return fail(CS_ERR_ARG, "the social-momentum step supports up to 64 rows per world");
     const int A = w->sm_n_actions > 0 ? w->sm_n_actions : 20; // motion_model_manager.py:249
     if (A > SM_MAX_ACTIONS) return fail(CS_ERR_ARG, "sm_n_actions must be <= 64");
@@ -230,7 +231,7 @@ int social_momentum_launch(const cs_worlds* w, float dt, int n_substeps, const f
     a.wpb = 64 / rows; a.A = A;
     a.dt = dt; a.bx = w->respawn_bound_x; a.by = w->respawn_bound_y;
     a.S = w->d_state;
-    if (w->layout == CS_LAYOUT_AOS) { a.as = 13; a.fs = 1; } else { a.as = 1; a.fs = (long)w->W * rows; }
+    state_strides(w, a.as, a.fs);   // (any layout other than AoS reads as SoA here)
     a.goals = w->d_goals; a.safety = w->d_safety; a.robot = w->d_robot; a.action = d_action;
     a.peek_out = d_peek; a.world_flags = w->d_world_flags;
     if (d_peek) a.flags &= ~CS_RESPAWN;

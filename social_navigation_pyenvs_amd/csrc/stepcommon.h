@@ -136,18 +136,6 @@ __device__ __forceinline__ float mod_two_pi(float x)
     return t;
 }
 
-// social_gym/src/utils.py:7-13 (Python % == fmod for the operand signs reaching each branch)
-__device__ __forceinline__ float bound_angle(float a)
-{
-    const float two_pi = 6.283185307179586f;
-    const float pi = 3.141592653589793f;
-    if (a >= two_pi) a = fmodf(a, two_pi);
-    if (a <= -two_pi) a = fmodf(a, two_pi);
-    if (a > pi) a -= two_pi;
-    if (a < -pi) a += two_pi;
-    return a;
-}
-
 // bound_angle for the heading update, branch-free: a - 2 pi rint(a / 2 pi) with a two-term (Cody-Waite) 2 pi, which
 // is what the reference's branches give for any |a| (fmod by 2 pi, then one fold into [-pi, pi]); ties at exactly
 // +-pi stay, as in the reference.  A data-dependent branch costs ~55 cycles of wave latency on this SIMD

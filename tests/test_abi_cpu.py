@@ -180,3 +180,209 @@ def test_new_entry_points_reject_bad_arguments_before_touching_a_device():
     st.W = 32
     assert lib.cs_refill_staged_worlds(C.byref(g), C.byref(st), C.byref(book), null) == _lib.CS_ERR_ARG
     assert "cs_generator.n differs" in lib.cs_last_error().decode()
+
+
+# One bad input per row, for every entry point that takes a cs_worlds: (entry, descriptor fields on top of a 4 x 5 SFM batch whose device
+# pointers are all NULL, the status the library returns, a fragment of its message).  "dev" in the fields sets the four buffers d_state,
+# d_goals, d_params, d_safety (and "robot" d_robot) to a dummy non-NULL address that the checks only compare with NULL; "book" = "null"
+# hands over a cs_gym_book without buffers.  A row whose descriptor carries a dummy pointer into an entry that launches kernels is only run
+# where no GPU is visible: nothing may ever hand such a pointer to a launch on a real device.
+_ORCA = dict(type=9, orca_neighbor_dist=10.0, orca_time_horizon=5.0, orca_time_horizon_obst=5.0, orca_max_neighbors=10)
+_BAD_CS_WORLDS = [
+    ("cs_step", None, -1, "null cs_worlds"),
+    ("cs_step", dict(W=0), -1, "W, n, G must be positive"),
+    ("cs_step", dict(n=0), -1, "W, n, G must be positive"),
+    ("cs_step", dict(), -1, "null device buffer"),
+    ("cs_step", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_step", dict(type=42), -2, "does not exist"),
+    ("cs_step", dict(dev=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_step", dict(_ORCA), -1, "null device buffer"),
+    ("cs_step", dict(_ORCA, W=0), -1, "W, n, G must be positive"),
+    ("cs_step", dict(_ORCA, dev=1, orca_max_neighbors=17), -1, "orca_max_neighbors must be in 0..16"),
+    ("cs_step", dict(type=10), -1, "null device buffer"),
+    ("cs_step", dict(type=10, n=0), -1, "W, n, G must be positive"),
+    ("cs_peek", None, -1, "null argument"),
+    ("cs_peek", dict(W=0), -1, "W, n, G must be positive"),
+    ("cs_peek", dict(), -1, "null device buffer"),
+    ("cs_peek", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_peek", dict(type=42), -2, "does not exist"),
+    ("cs_peek", dict(_ORCA, dev=1, orca_max_neighbors=17), -1, "orca_max_neighbors must be in 0..16"),
+    ("cs_update_humans_parallel", None, -1, "null argument"),
+    ("cs_update_humans_parallel", dict(n=0), -1, "W, n, G must be positive"),
+    ("cs_update_humans_parallel", dict(), -1, "null device buffer"),
+    ("cs_update_humans_parallel", dict(type=42), -2, "does not exist"),
+    ("cs_update_humans_parallel", dict(dev=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_step_trace", None, -1, "null argument"),
+    ("cs_step_trace", dict(W=0), -1, "W, n, G must be positive"),
+    ("cs_step_trace", dict(), -1, "null device buffer"),
+    ("cs_step_trace", dict(type=42), -1, "covers the SFM / HSFM models"),
+    ("cs_step_trace", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_step_observe", None, -1, "null argument"),
+    ("cs_step_observe", dict(n=0), -1, "W, n, G must be positive"),
+    ("cs_step_observe", dict(), -1, "null device buffer"),
+    ("cs_step_observe", dict(type=42), -2, "does not exist"),
+    ("cs_step_observe", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_step_observe", dict(_ORCA, dev=1, orca_max_neighbors=17), -1, "orca_max_neighbors must be in 0..16"),
+    ("cs_collision_reward", None, -1, "null cs_worlds"),
+    ("cs_collision_reward", dict(W=0), -1, "bad cs_worlds"),
+    ("cs_collision_reward", dict(n=0), -1, "bad cs_worlds"),
+    ("cs_collision_reward", dict(), -1, "bad cs_worlds"),
+    ("cs_collision_reward", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_collision_reward", dict(dev=1), -1, "null argument"),
+    ("cs_collision_reward_gym", None, -1, "null argument"),
+    ("cs_collision_reward_gym", dict(W=0), -1, "bad cs_worlds"),
+    ("cs_collision_reward_gym", dict(), -1, "bad cs_worlds"),
+    ("cs_collision_reward_gym", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_collision_reward_gym", dict(dev=1, robot=1, book="null"), -1, "null buffer in cs_gym_book"),
+    ("cs_gym_step", None, -1, "null argument"),
+    ("cs_gym_step", dict(W=0), -1, "bad cs_worlds"),
+    ("cs_gym_step", dict(dev=1, robot=1, book="null"), -1, "null buffer in cs_gym_book"),
+    ("cs_gym_step", dict(dev=1, robot=1, n=80, book="null"), -1, "null buffer in cs_gym_book"),
+    ("cs_gym_step_staged", None, -1, "null argument"),
+    ("cs_gym_step_staged", dict(W=0), -1, "these worlds take the two launches"),
+    ("cs_gym_step_staged", dict(dev=1, robot=1, book="null"), -1, "null buffer in cs_gym_book"),
+    ("cs_actual_collision_reward", None, -1, "null cs_worlds"),
+    ("cs_actual_collision_reward", dict(n=0), -1, "bad cs_worlds"),
+    ("cs_actual_collision_reward", dict(), -1, "bad cs_worlds"),
+    ("cs_actual_collision_reward", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_robot_model_step", None, -1, "null cs_worlds"),
+    ("cs_robot_model_step", dict(W=0), -1, "bad cs_worlds (a robot needs d_robot)"),
+    ("cs_robot_model_step", dict(dev=1), -1, "bad cs_worlds (a robot needs d_robot)"),
+    ("cs_robot_model_step", dict(dev=1, robot=1, layout=5), -1, "bad layout"),
+    ("cs_robot_model_step", dict(dev=1, robot=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_robot_model_velocities", None, -1, "null cs_worlds"),
+    ("cs_robot_model_velocities", dict(n=0), -1, "bad cs_worlds (a robot needs d_robot)"),
+    ("cs_imitation_block", None, -1, "null cs_worlds"),
+    ("cs_imitation_block", dict(W=0), -1, "bad cs_worlds (a robot needs d_robot)"),
+    ("cs_robot_model_rk45", None, -1, "null cs_worlds"),
+    ("cs_robot_model_rk45", dict(W=0), -1, "bad cs_worlds (a robot needs d_robot)"),
+    ("cs_robot_model_rk45", dict(dev=1, robot=1, layout=5), -1, "bad layout"),
+    ("cs_robot_model_rk45", dict(dev=1, robot=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_update_humans_rk45", None, -1, "null cs_worlds"),
+    ("cs_update_humans_rk45", dict(type=42), -2, "does not exist"),
+    ("cs_update_humans_rk45", dict(W=0), -1, "W, n, G must be positive"),
+    ("cs_update_humans_rk45", dict(), -1, "null device buffer"),
+    ("cs_update_humans_rk45", dict(dev=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_update_humans_rk45", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_complete_rk45_simulation", None, -1, "null cs_worlds"),
+    ("cs_complete_rk45_simulation", dict(n=0), -1, "W, n, G must be positive"),
+    ("cs_gym_observe", None, -1, "null argument"),
+    ("cs_gym_observe", dict(), -1, "null argument"),
+    ("cs_gym_observe", dict(dev=1, W=0), -1, "bad cs_worlds"),
+    ("cs_gym_observe", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_copy_worlds_masked", None, -1, "null argument"),
+    ("cs_copy_worlds_masked", dict(), -1, "null device buffer"),
+    ("cs_copy_worlds_masked_status", None, -1, "null argument"),
+    ("cs_copy_worlds_masked_observe", None, -1, "null argument"),
+    ("cs_laser_scan", None, -1, "null argument"),
+    ("cs_laser_scan", dict(W=0), -1, "bad cs_worlds"),
+    ("cs_laser_scan", dict(), -1, "bad cs_worlds"),
+    ("cs_laser_scan", dict(dev=1, O=1, Smax=2), -1, "bad obstacle description"),
+    ("cs_laser_scan", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_laser_scan", dict(dev=1, n=0), -1, "no sensor pose"),          # n = 0 passes the laser's checks (the scan sees walls only)
+    ("cs_generate_worlds", None, -1, "null argument"),
+    ("cs_generate_worlds", dict(), -1, "null device buffer"),
+    ("cs_generate_worlds", dict(dev=1, W=0), -1, "W, n, G must be positive"),
+    ("cs_generate_worlds", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_refill_staged_worlds", None, -1, "null argument"),
+    ("cs_refill_staged_worlds", dict(), -1, "null device buffer"),
+    ("cs_consume_staged_worlds", None, -1, "null argument"),
+    ("cs_consume_staged_worlds", dict(), -1, "null device buffer"),
+    ("cs_reserve_scratch", None, -1, "null cs_worlds"),
+    ("cs_launch_geometry", None, -1, "null cs_worlds"),
+    ("cs_launch_geometry", dict(n=0), -1, "rows per world must be positive"),
+    ("cs_step_variant", None, -1, "null argument"),
+    ("cs_step_variant", dict(W=0), -1, "W, n, G must be positive"),
+    ("cs_step_variant", dict(n=0), -1, "W, n, G must be positive"),
+    ("cs_step_variant", dict(), -1, "null device buffer"),
+    ("cs_step_variant", dict(dev=1, layout=5), -1, "bad layout"),
+    ("cs_step_variant", dict(type=42), -2, "does not exist"),
+    ("cs_step_variant", dict(dev=1, O=1, Smax=2), -1, "bad obstacle description"),
+    # the register-resident ORCA build (maxNeighbors 10, no vertices) is the one whose name reports its arithmetic; cs_step_variant runs
+    # orca_launch's checks, so an orca_math outside CS_ORCA_MATH_* is refused as the launch refuses it
+    ("cs_step_variant", dict(_ORCA, dev=1, orca_math=3), 0, "math=fma"),
+    ("cs_step_variant", dict(_ORCA, dev=1, orca_math=7), -1, "cs_worlds.orca_math"),
+    ("cs_step_variant", dict(_ORCA, dev=1, orca_max_neighbors=17), -1, "orca_max_neighbors must be in 0..16"),
+]
+_QUERY_ENTRIES = {"cs_step_variant", "cs_launch_geometry", "cs_gym_step_is_one_launch"}
+
+
+def _bad_cs_worlds_call(entry, w, book):
+    """Calls `entry` with descriptor `w` (a ctypes pointer or None) and otherwise well-formed arguments: dummy device pointers for every
+    buffer an entry checks for NULL before it reads the descriptor, host arrays for host arguments."""
+    import ctypes as C
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.generators import cs_generator
+
+    lib = _lib.load()
+    null, dev = C.c_void_p(None), C.c_void_p(0x1000)
+    f, i = C.c_float, C.c_int
+    cfg = (C.c_float * 5)(25.0, 1.0, -0.25, 0.2, 0.5)
+    rp = (C.c_float * 20)()
+    gen = cs_generator(scenario=0, n=5, insert_robot=0, randomize_attributes=0, randomize_positions=1, max_tries=100, circle_radius=7.0,
+                       traffic_length=14.0, traffic_height=3.0, robot_radius=0.3, human_mass=75.0, robot_mass=80.0, robot_desired_speed=1.0)
+    sb = _lib.cs_stage_book(d_seeds=0x1000, d_base_seed=0x1000, d_epoch=0x1000, d_staged_seed=0x1000, d_staged_status=0x1000, d_failed=0x1000,
+                            seed_stride=0, depth=1, d_pending=0x1000)
+    gb = C.byref(book)
+    buf = C.create_string_buffer(256)
+    calls = {
+        "cs_step": lambda: lib.cs_step(w, f(0.01), i(1), null, null),
+        "cs_peek": lambda: lib.cs_peek(w, f(0.01), dev, null),
+        "cs_update_humans_parallel": lambda: lib.cs_update_humans_parallel(w, f(0.01), dev, null),
+        "cs_step_trace": lambda: lib.cs_step_trace(w, f(0.01), i(1), null, dev, null),
+        "cs_step_observe": lambda: lib.cs_step_observe(w, f(0.01), i(1), null, i(0), dev, null),
+        "cs_collision_reward": lambda: lib.cs_collision_reward(w, dev, f(0.25), dev, cfg, dev, null),
+        "cs_collision_reward_gym": lambda: lib.cs_collision_reward_gym(w, dev, f(0.25), dev, cfg, dev, gb, null),
+        "cs_gym_step": lambda: lib.cs_gym_step(w, f(0.01), i(1), dev, f(0.25), dev, cfg, dev, gb, i(0), dev, null),
+        "cs_gym_step_staged": lambda: lib.cs_gym_step_staged(w, f(0.01), i(1), dev, f(0.25), dev, cfg, dev, gb, i(0), dev, C.byref(gen), w,
+                                                             C.byref(sb), null),
+        "cs_actual_collision_reward": lambda: lib.cs_actual_collision_reward(w, f(0.25), dev, cfg, dev, null),
+        "cs_robot_model_step": lambda: lib.cs_robot_model_step(w, i(0), rp, f(0.0), dev, dev, f(0.01), null),
+        "cs_robot_model_velocities": lambda: lib.cs_robot_model_velocities(w, i(0), rp, f(0.0), dev, dev, f(0.01), null),
+        "cs_imitation_block": lambda: lib.cs_imitation_block(w, i(0), rp, f(0.0), dev, dev, f(0.01), i(1), null),
+        "cs_robot_model_rk45": lambda: lib.cs_robot_model_rk45(w, i(0), rp, f(0.0), dev, dev, f(0.01), null, null),
+        "cs_update_humans_rk45": lambda: lib.cs_update_humans_rk45(w, f(0.01), dev, null, null),
+        "cs_complete_rk45_simulation": lambda: lib.cs_complete_rk45_simulation(w, f(0.01), f(1.0), dev, dev, i(4), null, null),
+        "cs_gym_observe": lambda: lib.cs_gym_observe(w, i(0), dev, null),
+        "cs_copy_worlds_masked": lambda: lib.cs_copy_worlds_masked(w, w, dev, null),
+        "cs_copy_worlds_masked_status": lambda: lib.cs_copy_worlds_masked_status(w, w, dev, null, null),
+        "cs_copy_worlds_masked_observe": lambda: lib.cs_copy_worlds_masked_observe(w, w, dev, null, i(0), null, null),
+        "cs_laser_scan": lambda: lib.cs_laser_scan(w, null, i(0), f(6.28), i(16), f(10.0), dev, null),
+        "cs_generate_worlds": lambda: lib.cs_generate_worlds(C.byref(gen), w, dev, null, null, null, dev, null),
+        "cs_refill_staged_worlds": lambda: lib.cs_refill_staged_worlds(C.byref(gen), w, C.byref(sb), null),
+        "cs_consume_staged_worlds": lambda: lib.cs_consume_staged_worlds(C.byref(gen), w, w, dev, C.byref(sb), i(0), null, null),
+        "cs_reserve_scratch": lambda: lib.cs_reserve_scratch(w, i(1), null),
+        "cs_launch_geometry": lambda: lib.cs_launch_geometry(w, null, null, null),
+        "cs_step_variant": lambda: lib.cs_step_variant(w, i(0), buf, C.c_size_t(len(buf))),
+    }
+    rc = calls[entry]()
+    return rc, (buf.value if entry == "cs_step_variant" and rc == 0 else lib.cs_last_error()).decode()
+
+
+@pytest.mark.parametrize("entry,fields,rc,fragment", _BAD_CS_WORLDS,
+                         ids=[f"{r[0]}-{i}" for i, r in enumerate(_BAD_CS_WORLDS)])
+def test_cs_worlds_entry_points_check_their_arguments(entry, fields, rc, fragment):
+    """What every entry point that takes a cs_worlds answers to one bad input -- the status and the message -- with no GPU involved."""
+    import ctypes as C
+
+    from social_navigation_pyenvs_amd import _lib
+
+    w, book = None, _lib.cs_gym_book(**{k: 0x1000 for k in ("d_counter", "d_seeds", "d_mask", "d_clock", "d_reward", "d_terminated",
+                                                            "d_truncated", "d_info")}, clock_len=4, auto_reset=1)
+    if fields is not None:
+        fields = dict(fields)
+        dummy = fields.pop("dev", 0)
+        robot = fields.pop("robot", 0)
+        if fields.pop("book", None) == "null":
+            book = _lib.cs_gym_book(clock_len=4, auto_reset=1)
+        desc = _lib.cs_worlds(**{"W": 4, "n": 5, "G": 2, "type": 0, "layout": _lib.CS_LAYOUT_AOS, **fields})
+        if dummy:
+            desc.d_state = desc.d_goals = desc.d_params = desc.d_safety = 0x1000
+        if robot:
+            desc.d_robot = 0x1000
+        if (dummy or robot) and entry not in _QUERY_ENTRIES and _lib.device_count() > 0:
+            pytest.skip("a GPU is visible: a dummy device pointer is never handed to an entry point that launches kernels there")
+        w = C.byref(desc)
+    got_rc, msg = _bad_cs_worlds_call(entry, w, book)
+    assert (got_rc, fragment in msg) == (rc, True), msg

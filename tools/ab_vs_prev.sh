@@ -3,7 +3,7 @@
 # earlier commit under _ab_r5/ (git worktree add -f _ab_r5 <commit>; build there): headline and cfg2, interleaved twice.
 #   bash tools/ab_vs_prev.sh > gpurun_out/ab_vs_prev.txt
 run() {  # tree, label, lib, bench flags
-  ( cd $1 && CROWDSTEP_LIB=$3 python bench.py --gpus 1 --steps 50 --warmup 20 --full --no-other-configs --no-cpu-baseline --no-gym-step $4 2>/dev/null | python -c "
+  ( cd $1 && CROWDSTEP_LIB=$3 python3 bench.py --gpus 1 --steps 50 --warmup 20 --full --no-other-configs --no-cpu-baseline --no-gym-step $4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$2', '${4:-cfg3}', 'kernel_us', d['kernel_us'], 'ms_per_step', d['ms_per_step'], d['roofline']['variant'], d['build_id'][:8])" )

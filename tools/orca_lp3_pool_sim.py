@@ -2,10 +2,11 @@
 per round) would change, counted on the restatement's own lines like tools/orca_lp3_stats.py: passes and vote-loop trips per wavefront, today (each wavefront deals
 its own agents) against the pooled deal (a round's passes dealt round-robin over the four wavefronts; the round ends with the slowest of them).  A statistics
 tool, not a parity oracle.  Result (HISTORY.md 0.6): the mean trips per wavefront drop by 22 - 26 %, the trips of the slowest wavefront of every round do not."""
-import sys, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tools')
+import os, sys, numpy as np
+TOOLS = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(TOOLS)); sys.path.insert(0, TOOLS)
 import importlib.util
-spec=importlib.util.spec_from_file_location('st','/root/repo/tools/orca_lp3_stats.py'); st=importlib.util.module_from_spec(spec); spec.loader.exec_module(st)
+spec=importlib.util.spec_from_file_location('st', os.path.join(TOOLS, 'orca_lp3_stats.py')); st=importlib.util.module_from_spec(spec); spec.loader.exec_module(st)
 from oracle import crowd_oracle as orc
 from social_navigation_pyenvs_amd import scenarios as sc
 f32=np.float32
