@@ -534,6 +534,35 @@ enum { CS_PNT_MASS = 20, CS_PNT_N_PARAMS = 21 };
 int cs_policy_no_train(int policy, int W, int n, const float* d_robot13, const float* d_obs, int obs_cols, float time_step,
                        const float* params /* host, CS_PNT_N_PARAMS floats */, float* d_action, void* stream);
 
+/*
+ * cs_value_net_decide  the decision of the trained value-based robots for W worlds: the per-action model() loop, compute_action_value
+ *   and the arg-max of CADRL.predict (crowd_nav/policy/cadrl.py:264-273, :85-90: value_network on every (action, human) row, minimum over
+ *   the humans) and of MultiHumanRL.predict with SARL's network (crowd_nav/policy/multi_human_rl.py:52-63, crowd_nav/policy/sarl.py:28-65:
+ *   mlp1 -> mlp2, attention on (mlp1, mean of mlp1) or on mlp1 alone, the masked softmax exp(s) * (s != 0) normalised, mlp3 on (the first
+ *   six columns of the first human's row, the weighted feature)), with reach_destination (cadrl.py:244).  Reads cs_lookahead's output:
+ *   d_rotated [W][A][n][cols] (cols 13 or 15), d_rewards [W][A]; d_actions [A][2]; d_robot [W][robot_stride] as cs_lookahead takes it
+ *   (px, py, vx, vy, radius, gx, gy, v_pref, ...).  Writes d_values [W][A] = reward + gamma^(dt * v_pref) * V, d_choice [W] (may be
+ *   NULL) = the first maximum of a world's values (np.argmax), or d_override[w] where that is in 0..A-1 (d_override may be NULL; -1 =
+ *   greedy: the caller's epsilon-greedy draw), and d_action_out [W][2] = the chosen action, (0, 0) for a robot within its radius of its
+ *   goal.  float32 on the f32-input matrix instructions; the activations of a row tile stay in LDS from the input columns to the value;
+ *   a (world, action) gives the same bits for W = 1 as inside any batch.  Two kernels on `stream`: the network, then the per-world pick.
+ *
+ *   The network is described by `dims` (host):  CS_VN_CADRL: [L, w_1 .. w_L] (the output widths of value_network's Linear layers,
+ *   w_L = 1);  CS_VN_SARL: [with_global_state, L1, mlp1 widths.., L2, mlp2 widths.., La, attention widths.., L3, mlp3 widths..]
+ *   (attention and mlp3 end in 1).  ReLU follows every layer but a chain's last, and mlp1's last too.  Widths 1..256, at most 16 layers.
+ *   d_weights is the blob cs_value_net_pack writes, n_weight_floats its length.
+ * cs_value_net_pack  (host only, no device) lays the Linear layers out for the kernel: params[2 l] = weight of layer l ([out][in], row
+ *   major, as torch.nn.Linear holds it), params[2 l + 1] = its bias, layers in the order of `dims`.  blob == NULL: only *n_floats is set.
+ *   Errors of both (CS_ERR_ARG, before any device call): unknown kind, cols not 13 or 15, a width outside 1..256, a malformed `dims`,
+ *   n < 1, W or A < 1, null pointers, a blob of another size, a network whose tile does not fit the LDS.
+ */
+enum { CS_VN_CADRL = 0, CS_VN_SARL = 1 };
+int cs_value_net_pack(int kind, const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats);
+int cs_value_net_decide(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                        int cols, const float* d_rotated, const float* d_rewards, const float* d_actions, const float* d_robot,
+                        int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values, int32_t* d_choice,
+                        float* d_action_out, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

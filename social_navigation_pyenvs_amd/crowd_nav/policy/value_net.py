@@ -1,0 +1,81 @@
+"""The seam between the value-based policies (CADRL, SARL) and the fused decision kernel (cs_value_net_decide, csrc/value_net.hip).
+
+``describe(policy)`` turns a policy's torch module into the kernel's layer description, ``DeviceNet`` keeps the packed weight blob on the
+GPU and repacks it only when a parameter changed (the tensors' version counters), ``decide`` is the one library call of a decision.
+There is no host implementation of the decision: without the library or a GPU these raise."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+CS_VN_CADRL, CS_VN_SARL = 0, 1     # include/crowdstep.h
+
+
+def _linears(seq):
+    import torch.nn as nn
+
+    return [m for m in seq if isinstance(m, nn.Linear)]
+
+
+def describe(model):
+    """(kind, dims int32 array, [Linear ...] in the order of dims) of a cadrl.ValueNetwork / sarl.ValueNetwork."""
+    if hasattr(model, "value_network"):
+        ls = _linears(model.value_network)
+        return CS_VN_CADRL, np.array([len(ls)] + [l.out_features for l in ls], np.int32), ls
+    dims, layers = [int(bool(model.with_global_state))], []
+    for chain in (model.mlp1, model.mlp2, model.attention, model.mlp3):
+        ls = _linears(chain)
+        dims += [len(ls)] + [l.out_features for l in ls]
+        layers += ls
+    return CS_VN_SARL, np.array(dims, np.int32), layers
+
+
+def pack(kind, dims, cols, arrays):
+    """The kernel's weight blob (float32 numpy) from [weight_0, bias_0, weight_1, ...] float32 arrays.  Host only: no GPU needed."""
+    from ... import _lib
+
+    lib = _lib.load()
+    dims = np.ascontiguousarray(dims, np.int32)
+    arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
+    ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+    nf = C.c_size_t(0)
+    d = dims.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.cs_value_net_pack(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), None, None, C.byref(nf)))
+    blob = np.zeros(nf.value, np.float32)
+    _lib.check(lib.cs_value_net_pack(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
+    return blob
+
+
+class DeviceNet:
+    """A policy's network as the kernel reads it: description + packed blob in HBM, rebuilt when the module's parameters changed."""
+
+    def __init__(self, model, cols):
+        self.model, self.cols = model, int(cols)
+        self.kind, self.dims, self.layers = describe(model)
+        self._key = None
+        self.blob = None
+
+    def _versions(self):
+        return tuple((p.data_ptr(), p._version) for l in self.layers for p in (l.weight, l.bias))
+
+    def refresh(self):
+        import torch
+
+        key = self._versions()
+        if key != self._key:
+            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in (l.weight, l.bias)]
+            self.blob = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays)).to("cuda")
+            self._key = key
+        return self.blob
+
+
+def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None):
+    """cs_value_net_decide on device pointers (ints); `net` a DeviceNet whose blob is current (refresh())."""
+    from ... import _lib
+
+    P = C.c_void_p
+    _lib.check(_lib.load().cs_value_net_decide(
+        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(net.blob.data_ptr()), C.c_size_t(net.blob.numel()),
+        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), P(rotated), P(rewards), P(actions), P(robot), C.c_int(robot_stride),
+        C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))

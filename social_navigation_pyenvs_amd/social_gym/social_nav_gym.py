@@ -640,18 +640,30 @@ class BatchedSocialNavGym:
         """The persistent [W, 2] action tensor the step kernel reads: write actions into it and pass it to ``step_device``."""
         return self._device_loop_state()["act"]
 
-    def act_device(self, policy):
+    def act_device(self, policy, explore=None):
         """Every world's robot decides with a no-train CrowdNav policy (``policy``: a name of crowd_nav.policy_no_train.policy_factory or
         an instance of its classes) -- ``predict`` for W robots in ONE launch of cs_policy_no_train on ``device_stream()``, reading the
         resident robot rows and the current observation, writing ActionXY rows into ``action_buffer()``.  Returns that buffer, ready
         for ``step_device(env.action_buffer())``; nothing crosses to the host.  The policy's ``time_step`` (None: the robot time step)
         is the social-force policies' integration step.  Needs worlds generated on the device (``reset(..., device=True)``) and a
-        holonomic robot (the policies act in ActionXY, robot_agent.py:112-114)."""
+        holonomic robot (the policies act in ActionXY, robot_agent.py:112-114).
+
+        A ``crowd_nav.policy`` CADRL / SARL instance decides with its value network instead: cs_peek (or the constant-velocity model
+        when the policy's ``query_env`` is false) -> cs_lookahead -> cs_value_net_decide, all on ``device_stream()``.  ``explore``: an
+        int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
+        values and choices of that decision stay readable through ``last_values_device()``."""
         import ctypes as C
 
         import torch
 
         dl = self._device_loop_state()
+        if not isinstance(policy, str):
+            from ..crowd_nav.policy.cadrl import CADRL
+
+            if isinstance(policy, CADRL):
+                return self._act_device_value(dl, policy, explore)
+        if explore is not None:
+            raise ValueError("act_device: explore= belongs to the value-based policies (CADRL, SARL)")
         if isinstance(policy, str):
             from ..crowd_nav.policy_no_train.policy_factory import policy_factory
 
@@ -692,6 +704,61 @@ class BatchedSocialNavGym:
             cur.wait_stream(side)
         return dl["act"]
 
+    def _act_device_value(self, dl, pol, explore):
+        """act_device for a CADRL / SARL instance: W decisions of its value network, nothing crosses to the host."""
+        import torch
+
+        from ..crowd_nav.policy import value_net
+
+        if pol.kinematics != "holonomic" or self.cw.unicycle:
+            raise ValueError("act_device: the value-based policies act in ActionXY and need a holonomic robot")
+        if pol.model is None:
+            raise AttributeError(f"{pol.name}: configure() the policy before it decides")
+        if bool(pol.with_theta_and_omega_visible) != self.headed_obs:
+            raise ValueError("act_device: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
+        if self.cw.d_robot is None:
+            raise ValueError("act_device needs the robot rows")
+        if pol.action_space_ndarray is None:
+            pol.build_action_space(float(self._gen_kw["robot_desired_speed"]))
+        W = self.W
+        acts = pol.device_action_space()            # (kept on the policy beside action_space_ndarray, uploaded again when its values change)
+        A = acts.shape[0]
+        if explore is not None:
+            if not (torch.is_tensor(explore) and explore.is_cuda and explore.dtype == torch.int32 and tuple(explore.shape) == (W,)):
+                raise ValueError("act_device: explore is an int32 CUDA tensor [W] of action indices (-1 = greedy)")
+            explore = explore.contiguous()
+        net = pol.device_net()                       # (repacked here, on the caller's stream, only when a parameter changed)
+        if dl.get("vn_values") is None or dl["vn_values"].shape[1] != A:
+            dl["vn_values"] = torch.zeros((W, A), dtype=torch.float32, device="cuda")
+            dl["vn_choice"] = torch.zeros(W, dtype=torch.int32, device="cuda")
+        side, cur = dl["stream"], torch.cuda.current_stream()
+        same = cur.cuda_stream == side.cuda_stream
+        if not same:
+            side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            nxt = None
+            if not pol.query_env:                    # cadrl.py:92-105: the humans keep their velocity over the robot's step
+                o, T = self.observe_device(), self.robot_time_step
+                nxt = (torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 5] + o[..., 6] * T, o[..., 2], o[..., 3], o[..., 6]], -1)
+                       if self.headed_obs else torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 2], o[..., 3]], -1)).contiguous()
+            rot, rew, rob = self._lookahead_on_side_stream(dl, acts, next_humans=nxt, with_robot=True)
+            value_net.decide(net, W, A, self.n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], pol.gamma,
+                             self.robot_time_step, None if explore is None else explore.data_ptr(), dl["vn_values"].data_ptr(),
+                             dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream)
+            for t in (rot, rew, rob) + (() if explore is None else (explore,)) + (() if nxt is None else (nxt,)):
+                t.record_stream(side)
+        if not same:
+            cur.wait_stream(side)
+        return dl["act"]
+
+    def last_values_device(self):
+        """(action values [W, A] float32, chosen action index [W] int32) of the last value-based ``act_device`` decision, as CUDA tensors
+        rewritten by the next one; None before the first."""
+        dl = self._device_loop_state()
+        if dl.get("vn_values") is None:
+            return None
+        return dl["vn_values"], dl["vn_choice"]
+
     def lookahead_device(self, action_space):
         """The per-decision array work of CADRL / SARL for every world, on the device: one-step look-ahead of the humans
         (``get_next_human_observable_states``, cadrl.py:258-259 -> cs_peek) and ``compute_rotated_states_and_reward``
@@ -711,7 +778,7 @@ class BatchedSocialNavGym:
         cur_stream.wait_stream(side)
         return out
 
-    def _lookahead_on_side_stream(self, dl, action_space):
+    def _lookahead_on_side_stream(self, dl, action_space, next_humans=None, with_robot=False):
         import ctypes as C
 
         import torch
@@ -725,13 +792,14 @@ class BatchedSocialNavGym:
         lib = _lib.load()
         d = cw.descriptor(respawn=False)
         peek = cw._buffer("peek", (W, n, 8))
-        _lib.check(lib.cs_peek(C.byref(d), C.c_float(self.robot_time_step), C.c_void_p(peek.ptr), C.c_void_p(cw.stream)))
+        if next_humans is None:
+            _lib.check(lib.cs_peek(C.byref(d), C.c_float(self.robot_time_step), C.c_void_p(peek.ptr), C.c_void_p(cw.stream)))
         if "la_cols" not in dl:
             # next humans: (px, py, vx, vy), or (x, y, yaw, Vx, Vy, Omega) with theta / omega visible (cadrl.py:42-83) = cs_peek's first six
             dl["la_cols"] = torch.as_tensor([0, 1, 2, 3, 4, 5] if self.headed_obs else [0, 1, 3, 4], device="cuda")
             dl["la_robot_cols"] = torch.as_tensor([0, 1, 3, 4, 8, 10, 11, 12, 2], device="cuda")   # FullState order
             dl["la_robot"] = cw.d_robot.torch().view(W, 13)
-        nxt = peek.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous()
+        nxt = peek.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous() if next_humans is None else next_humans
         cur = dl["state"][:, :n].index_select(2, dl["cols"]).contiguous()
         rob = dl["la_robot"].index_select(1, dl["la_robot_cols"]).contiguous()
         rot = torch.empty((W, A, n, 15 if self.headed_obs else 13), dtype=torch.float32, device="cuda")
@@ -740,7 +808,7 @@ class BatchedSocialNavGym:
                                     C.c_void_p(nxt.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(rob.data_ptr()), C.c_int(9),
                                     C.c_float(self.robot_time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()),
                                     C.c_void_p(cw.stream)))
-        return rot, rew
+        return (rot, rew, rob) if with_robot else (rot, rew)
 
     # ------------------------------------------------------------------ imitation learning, W worlds at once
     def set_human_motion_model_as_robot_policy(self, policy_name, runge_kutta=False, safety_space=0.0):

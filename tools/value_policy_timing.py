@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""Device time of the value-based robot decision (CADRL, SARL; csrc/value_net.hip) at 4096 worlds x 81 actions x {5, 25} humans, measured
+in one process on the same worlds and weights:
+
+    kernel    cs_value_net_decide alone on the look-ahead rows (the network kernel + the per-world pick)
+    decide    BatchedSocialNavGym.act_device(policy): cs_peek + cs_lookahead + the kernel
+    torch     the baseline: the same policy.model run by torch in float32 under no_grad on the same rows, then min / argmax in torch
+
+Warm device, HIP events around every single run, `kernel` and `torch` alternated, median of --repeats each, and the spread (min, max,
+interquartile range) of the baseline.  FLOP are the useful ones (2 x in x out per Linear layer and row; the padding of widths to the
+tile is not counted), the fraction is against the 157 TFLOP/s float32 matrix peak.  Writes profiles/value_policy_timing.json and prints it.
+
+    python tools/value_policy_timing.py [--worlds 4096] [--humans 5 25] [--policies cadrl sarl] [--repeats 20] [--out FILE]
+    python tools/value_policy_timing.py --trace-only        # a few act_device decisions, for a kernel trace of `decide`
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+for _d in ("tools", "tests", os.path.join("tests", "golden")):
+    sys.path.insert(0, os.path.join(ROOT, _d))
+
+PEAK_F32_MATRIX = 157e12
+
+
+def _env(n, W):
+    from policy_no_train_bench import _config
+
+    from social_navigation_pyenvs_amd.social_gym.social_nav_gym import BatchedSocialNavGym
+
+    env = BatchedSocialNavGym(_config(n), W)
+    env.reset(phase="test", first_case=11, device=True)
+    for _ in range(3):
+        env.step_device(env.act_device("sfm_helbing"))
+    return env
+
+
+def _policy(name, env):
+    import torch
+    from test_value_policy_cpu import make_policy, seeded_weights      # the default policy.config and G16's weight scale: one copy, the tests'
+
+    pol = make_policy(name)
+    seeded_weights(pol.model, 1700)
+    pol.set_phase("test")
+    pol.set_device(torch.device("cuda"))
+    pol.time_step = env.robot_time_step
+    return pol
+
+
+def useful_flop(pol, rows, groups):
+    """2 x in x out per Linear layer: per (action, human) row for the pairwise chains, per (world, action) for SARL's mlp3."""
+    import torch.nn as nn
+
+    lin = lambda seq: sum(2 * m.in_features * m.out_features for m in seq if isinstance(m, nn.Linear))
+    m = pol.model
+    if hasattr(m, "value_network"):
+        return rows * lin(m.value_network)
+    return rows * (lin(m.mlp1) + lin(m.mlp2) + lin(m.attention)) + groups * lin(m.mlp3)
+
+
+def torch_decide(pol, rot, rew, disc, chunk):
+    import torch
+
+    W, A, n, cols = rot.shape
+    out = torch.empty((W, A), dtype=torch.float32, device=rot.device)
+    with torch.no_grad():
+        for w0 in range(0, W, chunk):
+            x = rot[w0:w0 + chunk].reshape(-1, n, cols)
+            v = pol.model(x)[..., 0].min(dim=-1).values if pol.name == "CADRL" else pol.model(x)[:, 0]
+            out[w0:w0 + chunk] = v.view(-1, A)
+        values = rew + disc * out
+        return values, torch.argmax(values, dim=1)
+
+
+def main():
+    import numpy as np
+    import torch
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--worlds", type=int, default=4096)
+    ap.add_argument("--humans", type=int, nargs="+", default=[5, 25])
+    ap.add_argument("--policies", nargs="+", default=["cadrl", "sarl"])
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--torch-chunk", type=int, default=1024, help="worlds per torch forward (the whole batch's intermediates at once need tens of GB)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "value_policy_timing.json"))
+    ap.add_argument("--trace-only", action="store_true")
+    a = ap.parse_args()
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    _lib.require_gpu()
+    results = []
+    for n in a.humans:
+        env = _env(n, a.worlds)
+        W = env.W
+        for name in a.policies:
+            pol = _policy(name, env)
+            with torch.cuda.stream(env.device_stream()):
+                for _ in range(3):
+                    env.act_device(pol)
+                if a.trace_only:
+                    torch.cuda.synchronize()
+                    continue
+                acts = pol.device_action_space()
+                rot, rew = env.lookahead_device(acts)
+                rob = env.cw.d_robot.torch().view(W, 13)[:, [0, 1, 3, 4, 8, 10, 11, 12, 2]].contiguous()
+                disc = torch.pow(torch.tensor(pol.gamma, dtype=torch.float64, device="cuda"), env.robot_time_step * rob[:, 7].double()).float()[:, None]
+                net = pol.device_net()
+                vals = torch.zeros((W, 81), device="cuda")
+                pick = torch.zeros(W, dtype=torch.int32, device="cuda")
+                act = torch.zeros((W, 2), device="cuda")
+                stream = env.device_stream().cuda_stream
+
+                def kernel():
+                    value_net.decide(net, W, 81, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), 9, pol.gamma, env.robot_time_step,
+                                     None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+
+                def timed(fn):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    return e0.elapsed_time(e1)
+
+                for _ in range(3):
+                    kernel()
+                    torch_decide(pol, rot, rew, disc, a.torch_chunk)
+                tv, tp = torch_decide(pol, rot, rew, disc, a.torch_chunk)
+                scale = torch.clamp(tv.abs().max(dim=1).values, min=1.0)
+                rel = float(((vals - tv).abs().max(dim=1).values / scale).max())
+                tk, tt, td = [], [], []
+                for _ in range(a.repeats):
+                    tk.append(timed(kernel))
+                    tt.append(timed(lambda: torch_decide(pol, rot, rew, disc, a.torch_chunk)))
+                    td.append(timed(lambda: env.act_device(pol)))
+                flop = useful_flop(pol, W * 81 * n, W * 81)
+                q = lambda xs, p: float(np.percentile(xs, p))
+                r = dict(policy=name, worlds=W, actions=81, humans=n, repeats=a.repeats, useful_gflop=flop / 1e9,
+                         kernel_ms=q(tk, 50), kernel_min_ms=min(tk), kernel_max_ms=max(tk),
+                         decide_ms=q(td, 50), decide_min_ms=min(td), decide_max_ms=max(td),
+                         torch_ms=q(tt, 50), torch_min_ms=min(tt), torch_max_ms=max(tt), torch_iqr_ms=q(tt, 75) - q(tt, 25),
+                         torch_chunk_worlds=a.torch_chunk, kernel_tflops=flop / (q(tk, 50) * 1e-3) / 1e12,
+                         kernel_fraction_of_f32_matrix_peak=flop / (q(tk, 50) * 1e-3) / PEAK_F32_MATRIX,
+                         torch_tflops=flop / (q(tt, 50) * 1e-3) / 1e12, speedup_vs_torch=q(tt, 50) / q(tk, 50),
+                         kernel_not_slower_than_torch=bool(q(tk, 50) <= q(tt, 50) + (max(tt) - min(tt))),
+                         worst_rel_value_diff_vs_torch=rel, same_pick_fraction=float((pick.long() == tp).float().mean()),
+                         tile_rows=os.environ.get("CROWDSTEP_VN_TILE", "default"), device=_lib.device_name(0))
+                print(json.dumps(r), flush=True)
+                results.append(r)
+        env.close()
+    if results and a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
