@@ -535,6 +535,35 @@ int cs_policy_no_train(int policy, int W, int n, const float* d_robot13, const f
                        const float* params /* host, CS_PNT_N_PARAMS floats */, float* d_action, void* stream);
 
 /*
+ * cs_gym_step_policy  cs_policy_no_train followed by cs_gym_step -- `action = robot.act(ob); ob, reward, done, info = env.step(action)`, the
+ *   seam of Explorer.run_k_episodes (crowd_nav/utils/explorer.py:57-58) with a robot of crowd_nav/policy_no_train/ (*.py) -- in ONE launch: the
+ *   step kernel's prologue decides every world's ActionXY from the rows it has loaded (the robot row of cs_worlds.d_robot and the humans'
+ *   state rows: the values cs_policy_no_train reads from d_robot13 and from the observation rows), BEFORE the Gym head, the swept collision
+ *   test and the robot's advance consume it; the decided action is also stored to d_action [W][2] (out: no action row is read).  Bit for
+ *   bit what the two calls leave, in every buffer.  Arguments as cs_gym_step's, then policy / policy_time_step / policy_params as
+ *   cs_policy_no_train's policy / time_step / params.  One launch for the worlds cs_gym_step runs as one launch on the plain crowd
+ *   batch's builds without walls (all_params_equal, <= 2 goal slots; 25 humans, 25 or 5 humans + a visible robot, and every row count of
+ *   the run-time partner loop); everywhere else (ORCA, social momentum, walls, the DPP-row kernel's small worlds, the grid path) the
+ *   decision kernel and the Gym step's launches follow each other on `stream` inside this call: one entry, the same results.
+ *   d_obs must hold the current observation (cs_gym_observe / the previous step's) -- the worlds of the second kind decide from it.
+ *   Errors (CS_ERR_ARG, before any device call): unknown policy id, policy_time_step <= 0, a unicycle batch (CS_ROBOT_UNICYCLE: the
+ *   policies act in ActionXY), cs_worlds.d_robot null, d_action null, a social-force policy without parameters, null cs_gym_book buffers.
+ * cs_gym_step_staged_policy  the same in front of cs_gym_step_staged (its arguments, its conditions and its errors; then the three policy
+ *   arguments): decision, reward, bookkeeping, substeps, observation and the take-over of the staged episodes in ONE launch.
+ * cs_gym_step_policy_variant  which kernels cs_gym_step_policy runs for these worlds: "k_sfm_step<...,LEAN=8+k> ... (policy decided in the
+ *   head)" for the one launch, "k_policy_no_train + " and cs_step_variant's answer otherwise (the tests assert which build they compared).
+ */
+int cs_gym_step_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time,
+                       const float* reward_cfg /* host, 5 floats */, float* d_out, const cs_gym_book* book, int theta_and_omega_visible,
+                       float* d_obs, int policy, float policy_time_step, const float* policy_params /* host, CS_PNT_N_PARAMS floats */,
+                       void* stream);
+int cs_gym_step_staged_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time,
+                              const float* reward_cfg, float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs,
+                              const cs_generator* gen, const cs_worlds* staging, const cs_stage_book* stage_book, int policy,
+                              float policy_time_step, const float* policy_params, void* stream);
+int cs_gym_step_policy_variant(const cs_worlds* w, char* buf, size_t buflen);
+
+/*
  * cs_value_net_decide  the decision of the trained value-based robots for W worlds: the per-action model() loop, compute_action_value
  *   and the arg-max of CADRL.predict (crowd_nav/policy/cadrl.py:264-273, :85-90: value_network on every (action, human) row, minimum over
  *   the humans) and of MultiHumanRL.predict with SARL's network (crowd_nav/policy/multi_human_rl.py:52-63, crowd_nav/policy/sarl.py:28-65:

@@ -290,9 +290,23 @@ Variant select_variant(const cs_worlds* w, int mode, const Geometry& g, bool nee
 
 kfn variant_kernel(const Variant& v, int type)
 {
-    for (auto lookup : {sfm_builds_generic, sfm_builds_leanrt, sfm_builds_lean25, sfm_builds_lean30, sfm_builds_small, sfm_builds_lean50, sfm_builds_robot26, sfm_builds_robotx, sfm_builds_imit, sfm_builds_peragent})
+    for (auto lookup : {sfm_builds_generic, sfm_builds_leanrt, sfm_builds_lean25, sfm_builds_lean30, sfm_builds_small, sfm_builds_lean50, sfm_builds_robot26, sfm_builds_robotx, sfm_builds_imit, sfm_builds_peragent,
+                        sfm_builds_policy, sfm_builds_policy_robot})
         if (kfn fn = lookup(v, type)) return fn;
     return nullptr;
+}
+
+// The robot's no-train policy decided in the step launch's head (cs_gym_step_policy; sfmstep_kernel.h POLICY).  A build that decides is
+// the TWIN of the build the plain Gym step runs for the same worlds -- same budget, same row count, LEAN + 8 -- so that everything behind
+// the decision is the same instruction stream on the same operands; worlds whose build has no twin (walls, the DPP-row kernel's small
+// worlds, the compile-time row counts nobody asked a twin for) decide in a launch of their own.
+struct PolicyArgs { int id; float time_step; const float* params; float* d_action; };
+constexpr int LEAN_POLICY = 8;
+
+Variant policy_twin(Variant v)
+{
+    if (v.maxt == 64 && v.peq && (v.lean == 1 || v.lean == 3)) { v.lean += LEAN_POLICY; return v; }
+    return Variant{0, 0, 0, 0, v.peq};
 }
 
 // the Gym head's arguments from the C ABI's (book == nullptr: reward row only)
@@ -368,7 +382,7 @@ size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, bool peq, int* seg_
 
 int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, const float* d_action,
                 float* d_peek, hipStream_t stream, float4* d_snap = nullptr, float* d_trace = nullptr, const RobotModel* rm = nullptr,
-                float* d_obs = nullptr, int obs_cols = 0, const GymHead* gym = nullptr)
+                float* d_obs = nullptr, int obs_cols = 0, const GymHead* gym = nullptr, const PolicyArgs* pol = nullptr)
 {
     int rc = check_worlds(w);
     if (rc) return rc;
@@ -404,7 +418,13 @@ int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, 
     a.snap = d_snap;
     a.trace = d_trace;
     a.obs = d_obs; a.obs_cols = obs_cols;
-    const Variant v = select_variant(w, mode, g, d_snap != nullptr, rm != nullptr);
+    Variant v = select_variant(w, mode, g, d_snap != nullptr, rm != nullptr);
+    if (pol) {   // (callers ask policy_step_is_one_launch first)
+        v = policy_twin(v);
+        if (!gym || rm || !variant_kernel(v, w->type)) return fail(CS_ERR_ARG, "no step build decides the robot's policy for these worlds");
+        a.pnt_policy = pol->id; a.pnt_time_step = pol->time_step; a.pnt_action = pol->d_action;
+        if (pol->params) { std::memcpy(a.pnt_P, pol->params, sizeof(a.pnt_P)); a.pnt_mass = pol->params[CS_PNT_MASS]; }
+    }
     if (gym) {
         if (v.maxt != 64) return fail(CS_ERR_ARG, "the Gym head runs inside the step launch of blocks of one wavefront only");
         a.gym = *gym;
@@ -612,6 +632,94 @@ int cs_gym_step_staged(const cs_worlds* w, float dt, int n_substeps, const float
     if (rc) return rc;
     return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
                        theta_and_omega_visible ? 7 : 5, &gh);
+}
+
+// cs_gym_step_policy / cs_gym_step_staged_policy: the argument checks of the two (no device call before they pass)
+static int check_policy_step(const cs_worlds* w, int n_substeps, const float* d_action, const cs_gym_book* book, const float* d_obs,
+                             int policy, float time_step, const float* params)
+{
+    if (!w || !book || !d_obs) return fail(CS_ERR_ARG, "null argument");
+    if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
+    if (policy < CS_PNT_BP || policy > CS_PNT_SFM_MOUSSAID) return fail(CS_ERR_ARG, "unknown no-train policy id (CS_PNT_*)");
+    if (!(time_step > 0.0f)) return fail(CS_ERR_ARG, "the policy's time_step must be positive");
+    if (w->flags & CS_ROBOT_UNICYCLE) return fail(CS_ERR_ARG, "the no-train policies act in ActionXY: a unicycle batch (CS_ROBOT_UNICYCLE) cannot take them");
+    if (!w->d_robot) return fail(CS_ERR_ARG, "the robot's policy needs the robot rows (cs_worlds.d_robot is null)");
+    if (!d_action) return fail(CS_ERR_ARG, "null action buffer: the decided actions are stored there");
+    if (policy >= CS_PNT_SFM_HELBING) {
+        if (!params) return fail(CS_ERR_ARG, "the social-force policies need their parameters");
+        if (!(params[CS_PNT_MASS] != 0.0f) || !(params[0] != 0.0f)) return fail(CS_ERR_ARG, "mass and relaxation_time must be non-zero");
+    }
+    return check_gym_book(book);
+}
+
+// 0: the decision is a launch of its own in front of the Gym step's; 1: cs_gym_step_policy is ONE launch; 2: cs_gym_step_staged_policy too
+static int policy_step_is_one_launch(const cs_worlds* w)
+{
+    const int one = cs_gym_step_is_one_launch(w);
+    if (!one) return 0;
+    Geometry g;
+    if (geometry(w, g)) return 0;
+    return variant_kernel(policy_twin(select_variant(w, commit_mode(w), g)), w->type) ? one : 0;
+}
+
+int cs_gym_step_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time, const float* reward_cfg,
+                       float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, int policy, float policy_time_step,
+                       const float* policy_params, void* stream)
+{
+    if (const int rc = check_policy_step(w, n_substeps, d_action, book, d_obs, policy, policy_time_step, policy_params)) return rc;
+    if (!policy_step_is_one_launch(w)) {   // decide from the observation rows, then the Gym step as it is: the same results
+        const int rc = cs_policy_no_train(policy, w->W, w->n, w->d_robot, d_obs, theta_and_omega_visible ? 7 : 5, policy_time_step, policy_params,
+                                          d_action, stream);
+        return rc ? rc : cs_gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream);
+    }
+    if (!d_global_time || !reward_cfg || !d_out) return fail(CS_ERR_ARG, "null argument");
+    const GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
+    const PolicyArgs pol{policy, policy_time_step, policy_params, d_action};
+    return launch_step(w, dt, n_substeps, commit_mode(w), nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
+                       theta_and_omega_visible ? 7 : 5, &gh, &pol);
+}
+
+int cs_gym_step_staged_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time, const float* reward_cfg,
+                              float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, const cs_generator* gen,
+                              const cs_worlds* staging, const cs_stage_book* stage_book, int policy, float policy_time_step,
+                              const float* policy_params, void* stream)
+{
+    if (const int rc = check_policy_step(w, n_substeps, d_action, book, d_obs, policy, policy_time_step, policy_params)) return rc;
+    if (!gen || !staging || !stage_book) return fail(CS_ERR_ARG, "null argument");
+    if (const int rc = check_stage_book(stage_book)) return rc;
+    if (!stage_book->d_pending || !stage_book->d_failed) return fail(CS_ERR_ARG, "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed");
+    if (!book->auto_reset && !book->d_prev_mask) return fail(CS_ERR_ARG, "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)");
+    if (book->d_seeds != stage_book->d_seeds) return fail(CS_ERR_ARG, "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer");
+    if (cs_gym_step_is_one_launch(w) != 2) return fail(CS_ERR_ARG, "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)");
+    if (policy_step_is_one_launch(w) != 2) {
+        const int rc = cs_policy_no_train(policy, w->W, w->n, w->d_robot, d_obs, theta_and_omega_visible ? 7 : 5, policy_time_step, policy_params,
+                                          d_action, stream);
+        return rc ? rc : cs_gym_step_staged(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, gen,
+                                            staging, stage_book, stream);
+    }
+    if (!d_global_time || !reward_cfg || !d_out) return fail(CS_ERR_ARG, "null argument");
+    GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
+    const int rc = csimpl::stage_fold(gen, staging, w, stage_book, theta_and_omega_visible ? 7 : 5, d_obs, gh.fold);
+    if (rc) return rc;
+    const PolicyArgs pol{policy, policy_time_step, policy_params, d_action};
+    return launch_step(w, dt, n_substeps, commit_mode(w), nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
+                       theta_and_omega_visible ? 7 : 5, &gh, &pol);
+}
+
+int cs_gym_step_policy_variant(const cs_worlds* w, char* buf, size_t buflen)
+{
+    if (!w || !buf || buflen == 0) return fail(CS_ERR_ARG, "null argument");
+    if (policy_step_is_one_launch(w)) {
+        Geometry g;
+        if (const int rc = geometry(w, g)) return rc;
+        const Variant v = policy_twin(select_variant(w, commit_mode(w), g));
+        std::snprintf(buf, buflen, "k_sfm_step<SOC=%d,HEADED=%d,PEQ=1,MAXT=%d,OCC=%d,ROWS_CT=%d,LEAN=%d+%d> grid=%d block=%d wpb=%d (policy decided in the head)",
+                      w->type % 3, w->type / 3, v.maxt, v.occ, v.rows_ct, LEAN_POLICY, v.lean - LEAN_POLICY, g.grid, g.block, g.wpb);
+        return CS_OK;
+    }
+    const int n0 = std::snprintf(buf, buflen, "k_policy_no_train + ");
+    if (n0 < 0 || (size_t)n0 >= buflen) return CS_OK;
+    return cs_step_variant(w, 0, buf + n0, buflen - (size_t)n0);
 }
 
 int cs_step_trace(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float* d_trace, void* stream)

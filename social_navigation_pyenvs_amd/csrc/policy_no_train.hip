@@ -8,12 +8,14 @@
 // One wavefront per world, lanes over humans (a loop of stride 64 beyond 64 humans), then a butterfly reduction: the per-human
 // terms are summed in the same tree for every world, so a world gives the same bits in a batch of 4096 as alone (predict(), W = 1).
 // The pair law is rmodel::pair_term (robot_model.h), the single-agent term of forces.py with r_ij = robot radius + human radius.
+// The policies themselves are stated once, in policy_no_train.h, which the Gym step's kernel includes too (cs_gym_step_policy).
 // Floating-point contraction is off, as in robot_model.h.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "common.h"
+#include "policy_no_train.h"
 #include "robot_model.h"
 
 namespace {
@@ -26,16 +28,6 @@ constexpr int WAVES_PER_BLOCK = 4;
 struct PntParams { float p[CS_PNT_N_PARAMS]; };
 
 using rmodel::wave_sum;
-
-__device__ __forceinline__ void toward_goal(float px, float py, float gx, float gy, float vd, float* out)
-{
-    // theta = atan2(gy - py, gx - px); (cos, sin) * v_pref: at the goal atan2(0, 0) = 0 gives (v_pref, 0), never NaN
-    const float th = atan2f(gy - py, gx - px);
-    float s, c;
-    sincosf(th, &s, &c);
-    out[0] = c * vd;
-    out[1] = s * vd;
-}
 
 __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_policy_no_train(int policy, int W, int n, const float* __restrict__ robot,
                                                                             const float* __restrict__ obs, int oc, float time_step,
@@ -51,7 +43,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_policy_no_train(int 
     float* out = action + (long)w * 2;
 
     if (policy == CS_PNT_BP) {
-        if (lane == 0) toward_goal(px, py, gx, gy, vd, out);
+        if (lane == 0) pnt::toward_goal(px, py, gx, gy, vd, out[0], out[1]);
         return;
     }
     if (policy == CS_PNT_SSP) {
@@ -59,14 +51,12 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_policy_no_train(int 
         bool near = false;
         for (int j = lane; j < n; j += WAVE) {
             const float* h = ow + (long)j * oc;
-            const float dx = h[0] - px, dy = h[1] - py;
-            const float d = sqrtf(dx * dx + dy * dy) - h[4] - rr;
-            near = near || (d <= 0.2f);
+            near = near || pnt::ssp_near(h[0], h[1], h[4], px, py, rr);
         }
         const bool any = __any(near);
         if (lane == 0) {
             if (any) { out[0] = 0.0f; out[1] = 0.0f; }
-            else toward_goal(px, py, gx, gy, vd, out);
+            else pnt::toward_goal(px, py, gx, gy, vd, out[0], out[1]);
         }
         return;
     }
@@ -78,26 +68,13 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_policy_no_train(int 
         const float* h = ow + (long)j * oc;
         float tx, ty;
         rmodel::pair_term(soc, P, px, py, vx, vy, h[0], h[1], h[2], h[3], rr + h[4], tx, ty);
-        fx += tx;
-        fy += ty;
+        pnt::add_term(fx, fy, tx, ty);
     }
     fx = wave_sum(fx);
     fy = wave_sum(fy);
     if (lane != 0) return;
-    // forces.py:11-25: desired force, 0 within one radius of the goal
-    const float mass = P[CS_PNT_MASS];
-    const float ddx = gx - px, ddy = gy - py;
-    const float dist = sqrtf(ddx * ddx + ddy * ddy);
-    if (dist > rr) {
-        fx = mass * (ddx / dist * vd - vx) / P[0] + fx;
-        fy = mass * (ddy / dist * vd - vy) / P[0] + fy;
-    }
-    // sfm_helbing.py:46-48: Euler over the policy's time step, speed clamped to v_pref
-    float nvx = vx + fx / mass * time_step, nvy = vy + fy / mass * time_step;
-    const float sp = sqrtf(nvx * nvx + nvy * nvy);
-    if (sp > vd) { nvx = nvx / sp * vd; nvy = nvy / sp * vd; }
-    out[0] = nvx;
-    out[1] = nvy;
+    // desired force, Euler over the policy's time step, the v_pref clamp (policy_no_train.h)
+    pnt::sfm_decide(P[0], P[CS_PNT_MASS], time_step, px, py, vx, vy, rr, gx, gy, vd, fx, fy, out[0], out[1]);
 }
 
 } // namespace

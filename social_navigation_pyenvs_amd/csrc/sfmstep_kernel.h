@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "crowdstep.h"
+#include "policy_no_train.h"
 #include "robot_model.h"
 #include "stepcommon.h"
 
@@ -56,9 +57,12 @@ constexpr int ACC_PITCH = 128; // float2 slots per accumulator row (block = one 
 //            does not need them and the goal switch is predicated; 4 = 3 + the robot follows a HUMAN motion model of its own
 //            (imitation learning, social_nav_gym.py:252-274): update_robot runs inside the substep loop (robot_model.h);
 //            5 = 3 with the walls kept (a Gym with a visible robot in a walled scene)
+//            + 8 (9 = 8 + 1, 11 = 8 + 3; the template argument is LEAN_ARG, the kernel's LEAN its low three bits) = POLICY: the robot's
+//            no-train policy (policy_no_train.h) is decided in the prologue from the rows the launch has loaded, before the Gym head
+//            consumes the action: cs_gym_step_policy.  New instantiations beside the old ones (sfmstep_policy*.hip), which do not change.
 constexpr int WG_WAVES_MAX = 4;   // (launch bound of the one-wavefront builds: four independent wavefronts per workgroup; a bound of eight -- which measures the same as
                                   //  four -- makes the compiler allocate the Moussaid builds ten registers fewer and their launches 2 us longer)
-template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEAN>
+template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEAN_ARG>
 // One-wavefront builds (MAXT = 64) are launched as workgroups of a.wg_waves INDEPENDENT wavefronts (four by default), each the "block" the
 // rest of this file talks about -- its own worlds, its own slice of the dynamic LDS, no barrier with the others.  Measured (tools/ab_wg_waves.sh):
 // cfg3 29.3 -> 28.2 us per launch, a launch of one substep 7.3 -> 6.1 us, with 512 workgroups of four instead of 2048 of one; inside an XCD the
@@ -67,6 +71,9 @@ template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEA
 // the eight XCDs, whatever the workgroup size: HISTORY.md.)
 __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_sfm_step(const KArgs a)
 {
+    constexpr int LEAN = LEAN_ARG & 7;
+    constexpr bool POLICY = LEAN_ARG >= 8;
+    static_assert(!POLICY || (MAXT == 64 && (LEAN == 1 || LEAN == 3)), "the policy is decided in the head of the plain crowd batch's builds without walls");
     extern __shared__ __align__(16) unsigned char smem_raw0[];
     const int wave_in_wg = MAXT == 64 ? (int)(threadIdx.x >> 6) : 0;
     unsigned char* smem_raw = smem_raw0 + (MAXT == 64 ? (size_t)wave_in_wg * a.lds_per_wave : 0);
@@ -200,5 +207,7 @@ kfn sfm_builds_robot26(const Variant& v, int type);   // sfmstep_robot26.hip: 25
 kfn sfm_builds_robotx(const Variant& v, int type);   // sfmstep_robotx.hip: 5 / 10 / 50 humans + a visible robot
 kfn sfm_builds_imit(const Variant& v, int type);     // sfmstep_imit.hip: a visible robot under its own human motion model (imitation learning)
 kfn sfm_builds_peragent(const Variant& v, int type); // sfmstep_peragent.hip: 25 rows per world, per-agent parameters (Helbing / Guo laws)
+kfn sfm_builds_policy(const Variant& v, int type);        // sfmstep_policy.hip: the robot's no-train policy decided in the head, invisible robot (LEAN = 8 + 1)
+kfn sfm_builds_policy_robot(const Variant& v, int type);  // sfmstep_policy_robot.hip: ... visible robot as the last row (LEAN = 8 + 3)
 
 } // namespace cstep

@@ -31,7 +31,7 @@
     const bool robot_moves = a.action != nullptr; // (lean build: only the invisible robot of the epilogue)
     float ax, ay;                                 // robot action (held for the whole block, social_nav_gym.py:240-243)
     {
-        const float* ap = robot_moves ? a.action + (long)wc * 2 : dummy;
+        const float* ap = (robot_moves && !POLICY) ? a.action + (long)wc * 2 : dummy;   // (POLICY: the action is decided in the prologue)
         ax = ap[0]; ay = ap[1];
     }
     // parameters: my own row of P for the single-agent forces; P[0] of my world for the pair loop
@@ -64,6 +64,7 @@
     }
     // (cs_gym_step: the robot as the head sees it and the action, see below)
     float hrb[6] = {0, 0, 0, 0, 0, 0}, hact[2] = {0, 0};
+    float prb[3] = {0, 0, 0};   // (POLICY) what the robot's policy reads beside them: its velocity and v_pref
     // cs_gym_step_staged's take-over in the epilogue (gymhead.h GymFold): compiled into the builds without walls only -- the 50-row wall build
     // has no register to spare (its shard went 191 -> 200 us with the fold compiled in), and a Gym with polygon walls keeps the two launches
 #ifdef CS_NO_FOLD   // (diagnostic variant build: what the fold's code costs the launches that do not use it)
@@ -77,7 +78,8 @@
         if (a.gym.out != nullptr && valid) {
             const float* rb = a.robot + (long)w * 13;      // the robot BEFORE its move of substep 1
             hrb[0] = rb[0]; hrb[1] = rb[1]; hrb[2] = rb[8]; hrb[3] = rb[10]; hrb[4] = rb[11]; hrb[5] = rb[2];
-            hact[0] = a.action[(long)w * 2]; hact[1] = a.action[(long)w * 2 + 1];
+            if constexpr (POLICY) { prb[0] = rb[3]; prb[1] = rb[4]; prb[2] = rb[12]; }
+            else { hact[0] = a.action[(long)w * 2]; hact[1] = a.action[(long)w * 2 + 1]; }
             if (row == 0) hpre = gym_head_preload<MAXT == 64 && !(LEAN == 2 || LEAN == 5)>(a.gym, w);   // (last: the compiler waits for these right here)
         }
     }

@@ -62,6 +62,34 @@
     float4* lds_rob = reinterpret_cast<float4*>(lds_vr);
     float2* lds_rf = reinterpret_cast<float2*>(lds_g0x);
 
+    // ---- cs_gym_step_policy (POLICY builds): the robot's no-train policy, decided HERE from the rows as they came in -- the robot columns of
+    //      the load phase (d_robot: what cs_policy_no_train reads) and the humans' rows in their lanes (px, py, vx, vy, r: the columns the
+    //      observation rows cs_policy_no_train reads were written from; DESIGN.md 4.3) -- so that the head below, the swept test and the
+    //      robot's advance consume it as they consume an action row.  Every lane of a world ends up with its world's action; the lane of
+    //      row 0 leaves it in the action buffer (one 8-byte store).  policy_no_train.h states the policies; the sum over humans is its
+    //      world_sum: k_policy_no_train's butterfly, world by world.  The policy id is a kernel argument: wave-uniform branches.
+    if constexpr (POLICY) {
+        const float qx = hrb[0], qy = hrb[1], qr = hrb[2], qgx = hrb[3], qgy = hrb[4], qvx = prb[0], qvy = prb[1], qvd = prb[2];
+        float dax = 0.0f, day = 0.0f;
+        if (a.pnt_policy == CS_PNT_BP) pnt::toward_goal(qx, qy, qgx, qgy, qvd, dax, day);
+        else if (a.pnt_policy == CS_PNT_SSP) {
+            const bool near = human && pnt::ssp_near(px, py, r, qx, qy, qr);
+            const unsigned long long mine = (rows >= 64 ? ~0ull : ((1ull << rows) - 1ull)) << base;   // the lanes of my world
+            if ((__builtin_amdgcn_ballot_w64(near) & mine) == 0ull) pnt::toward_goal(qx, qy, qgx, qgy, qvd, dax, day);
+        } else {
+            float tx = 0.0f, ty = 0.0f;
+            if (human) {
+                float ux, uy;
+                rmodel::pair_term(a.pnt_policy - CS_PNT_SFM_HELBING, a.pnt_P, qx, qy, qvx, qvy, px, py, vx, vy, qr + r, ux, uy);
+                pnt::add_term(tx, ty, ux, uy);
+            }
+            const float fx = pnt::world_sum(tx, tid, lw, rows, n, a.wpb), fy = pnt::world_sum(ty, tid, lw, rows, n, a.wpb);
+            pnt::sfm_decide(a.pnt_P[0], a.pnt_mass, a.pnt_time_step, qx, qy, qvx, qvy, qr, qgx, qgy, qvd, fx, fy, dax, day);
+        }
+        ax = valid ? dax : 0.0f; ay = valid ? day : 0.0f;
+        hact[0] = ax; hact[1] = ay;
+        if (valid && row == 0) *reinterpret_cast<float2*>(a.pnt_action + (long)w * 2) = make_float2(ax, ay);
+    }
     // ---- cs_gym_step: the head of the Gym step, on the rows as they came in (social_nav_gym.py:229-233) -- the swept robot-human
     //      distances by the humans' lanes, then the lane of row 0 walks its world's in index order and does the episode bookkeeping
     //      (gymhead.h: the very code of k_collision_reward_wave).  One scalar branch in a plain cs_step.

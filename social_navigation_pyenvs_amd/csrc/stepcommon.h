@@ -46,12 +46,27 @@ struct KArgs {
     float4* snap;          // optional [nsub][W][n] (x, y, vx, vy) of every human at the START of every substep (imitation block)
     float* trace;          // optional [nsub][W][rows][12] px, py, theta, vx, vy, bvx, bvy, omega, gx, gy, goals[0].x, goals[0].y of every
                            // row AFTER every substep (respawn included; the robot row as the NEXT substep will see it): cs_step_trace
-    // the robot under a human motion model inside the crowd's launch (k_sfm_step<..., LEAN = 4>, cs_imitation_block with a visible robot)
-    int rm_type;           // the robot's model 0..8
-    float rm_margin;       // robot.safety_space as its model adds it to the radius
-    const float* rm_hmargin; // [W][rows] the humans' safety space as the robot's model sees it
-    float* rm_memory;      // [W][2] robot.desired_force between substeps
-    float rm_P[20];        // the robot's parameters
+    // One block of 104 bytes with two readings, never both in one launch (an anonymous union of two structs of the same layout: no kernel
+    // argument of the builds that existed before the second reading moved).
+    union {
+        // the robot under a human motion model inside the crowd's launch (k_sfm_step<..., LEAN = 4>, cs_imitation_block with a visible robot)
+        struct {
+            int rm_type;           // the robot's model 0..8
+            float rm_margin;       // robot.safety_space as its model adds it to the radius
+            const float* rm_hmargin; // [W][rows] the humans' safety space as the robot's model sees it
+            float* rm_memory;      // [W][2] robot.desired_force between substeps
+            float rm_P[20];        // the robot's parameters
+        };
+        // the robot's no-train policy decided in the prologue (k_sfm_step<..., LEAN = 8 + 1 | 3>, cs_gym_step_policy; policy_no_train.h)
+        struct {
+            int pnt_policy;        // CS_PNT_*
+            float pnt_time_step;   // the policy's integration step
+            float* pnt_action;     // [W][2] where the head's lane leaves the decided ActionXY (== action: the launch reads no action row)
+            float pnt_mass;        // the policy's mass (slot CS_PNT_MASS of the packed parameters)
+            float pnt_pad;
+            float pnt_P[20];       // ... and their agent.py slots 0..19
+        };
+    };
     int wg_waves;          // one-wavefront builds (MAXT = 64): independent wavefronts per workgroup (each a virtual block of its own); 1 elsewhere
     int lds_per_wave;      // ... and the bytes of dynamic LDS each of them owns
     int young_from;        // blocks from this index on are the YOUNGER wavefront of their SIMD (a grid of exactly two wavefronts per SIMD), INT_MAX: no such split

@@ -704,6 +704,86 @@ class BatchedSocialNavGym:
             cur.wait_stream(side)
         return dl["act"]
 
+    def act_step_device(self, policy, auto_reset=True):
+        """``act_device(policy)`` and ``step_device(action_buffer(), auto_reset)`` as ONE library call -- and, for the SFM / HSFM crowds of
+        the one-wavefront step kernels, ONE launch (cs_gym_step_policy / cs_gym_step_staged_policy): the step kernel's head decides every
+        world's ActionXY from the rows it has loaded before it consumes it.  ``policy``: a no-train CrowdNav policy as ``act_device``
+        takes it (a name of policy_factory or an instance of its classes).  Returns what ``step_device`` returns and leaves the decided
+        actions in ``action_buffer()``; runs on ``device_stream()``, nothing crosses to the host.  Bit for bit the results of the two
+        calls.  The other crowds (ORCA, social momentum, walls, the smallest worlds) run the decision kernel and the step's launches
+        inside the same call.  A CADRL / SARL instance decides in milliseconds and gains nothing here: ``act_device``, then ``step_device``."""
+        import ctypes as C
+
+        import torch
+
+        from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
+
+        if not isinstance(policy, (str, NoTrainPolicy)):   # (refused before anything touches the device)
+            raise TypeError(f"act_step_device takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}: "
+                            "a value-based policy (CADRL, SARL) decides with act_device, then step_device")
+        dl = self._device_loop_state()
+        if isinstance(policy, str):
+            from ..crowd_nav.policy_no_train.policy_factory import policy_factory
+
+            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
+        else:
+            pol = policy
+        if pol.kinematics != "holonomic" or self.cw.unicycle:
+            raise ValueError("act_step_device: the no-train policies act in ActionXY and need a holonomic robot")
+        if self.cw.d_robot is None:
+            raise ValueError("act_step_device needs the robot rows")
+        mode = "next_step" if auto_reset == "next_step" else ("same_step" if auto_reset else "none")
+        if mode == "next_step":
+            if "ns_masks" not in dl:
+                dl["ns_masks"] = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
+                torch.cuda.synchronize()
+        elif dl.get("mode") == "next_step" and "ns_masks" in dl and any(bool(m.any().item()) for m in dl["ns_masks"]):
+            raise RuntimeError("a NEXT_STEP auto-reset is pending for some world: keep auto_reset=\"next_step\" (or reset()) before changing the mode")
+        dl["mode"] = mode
+        parity = dl["parity"]
+        dl["parity"] ^= 1
+        c = self._step_pieces(dl, parity, mode)
+        # the policy's three ctypes arguments bound once per (policy, time step, parameters), as act_device binds its own
+        ts = self.robot_time_step if pol.time_step is None else pol.time_step
+        prm = pol.packed_params()
+        key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
+        bound = dl.setdefault("pnt_step_args", {})
+        pargs = bound.get(key)
+        if pargs is None:
+            pargs = (C.c_int(pol.pnt_id), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p), prm)
+            bound[key] = pargs
+        lib, chk = _lib.load(), _lib.check
+        side, cur = dl["stream"], torch.cuda.current_stream()
+        same = cur.cuda_stream == side.cuda_stream
+        if not same:
+            side.wait_stream(cur)
+        if not dl.get("obs_fresh"):                # no step since the batch was generated: the observation of the resident rows (what
+            d = self.cw.descriptor(respawn=False)  # the worlds that decide in a launch of their own read; act_device does the same)
+            chk(lib.cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()), C.c_void_p(side.cuda_stream)))
+            dl["obs_fresh"] = True
+        if c["fold"] is not None:
+            chk(lib.cs_gym_step_staged_policy(*c["fold"][:-1], *pargs[:3], c["fold"][-1]))
+            self._maybe_refill(dl)
+        else:
+            chk(lib.cs_gym_step_policy(*c["step"][:-1], *pargs[:3], c["step"][-1]))
+            if c["tail"] is not None:
+                chk(lib.cs_consume_staged_worlds(*c["tail"]))
+                self._maybe_refill(dl)
+        if not same:
+            cur.wait_stream(side)
+        reward, terminated, truncated, info = dl["results"][parity]
+        return dl["obs"], reward, terminated, truncated, info
+
+    def act_step_variant(self) -> str:
+        """Which kernels ``act_step_device`` runs for this batch (cs_gym_step_policy_variant): the step build that decides in its head, or
+        ``k_policy_no_train + `` the plain step's build."""
+        import ctypes as C
+
+        d = self.cw.descriptor()
+        buf = C.create_string_buffer(320)
+        _lib.check(_lib.load().cs_gym_step_policy_variant(C.byref(d), buf, C.c_size_t(320)))
+        return buf.value.decode()
+
     def _act_device_value(self, dl, pol, explore):
         """act_device for a CADRL / SARL instance: W decisions of its value network, nothing crosses to the host."""
         import torch
