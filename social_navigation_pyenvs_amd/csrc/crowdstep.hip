@@ -252,33 +252,33 @@ Variant select_variant(const cs_worlds* w, int mode, const Geometry& g, bool nee
     // partitioned (CPX) device has fewer)
     const bool crowded = g.grid > 2 * csimpl::device_simds();
     // The plain crowd batch (what Gym scenarios and the bench step): all_params_equal -> every pair once, <= 2 goal slots, committed
-    // in place -> a LEAN build: 1 = no walls, no robot row; 2 = walls; 3 = no walls + the robot as the last row (a Gym with a
-    // visible robot: cs_step hands the robot rows over through d_robot, M_ROBOT_FROM_ARRAY); 5 = walls + robot row.  Everything else (
+    // in place -> a LEAN build (sfmstep_kernel.h LEAN_*): no walls, no robot row; walls; no walls + the robot as the last row (a Gym with a
+    // visible robot: cs_step hands the robot rows over through d_robot, M_ROBOT_FROM_ARRAY); walls + robot row.  Everything else (
     // per-agent parameters, longer goal lists, peek / out-of-place modes) runs the generic build.
     const bool lean_mode = robot ? (mode & ~(int)M_ROBOT_FROM_ARRAY) == M_COMMIT_GOALS : mode == M_COMMIT_GOALS;
-    int kind = 0;
-    if (peq && w->G <= 2 && lean_mode) kind = robot ? (w->O == 0 ? 3 : 5) : (w->O == 0 ? 1 : 2);
-    if (robot_model) {   // the robot's own motion model inside the launch: the LEAN = 4 builds only (callers check fusable_imitation)
-        if (kind != 3) return Variant{0, 0, 0, 0, peq};
-        return Variant{64, rows == 26 ? 1 : 3, rows == 26 ? 26 : 0, 4, true};
+    int kind = LEAN_GENERIC;
+    if (peq && w->G <= 2 && lean_mode) kind = robot ? (w->O == 0 ? LEAN_ROBOT_ROW : LEAN_ROBOT_ROW_WALLS) : (w->O == 0 ? LEAN_PLAIN : LEAN_WALLS);
+    if (robot_model) {   // the robot's own motion model inside the launch: the LEAN_IMITATION builds only (callers check fusable_imitation)
+        if (kind != LEAN_ROBOT_ROW) return Variant{0, 0, 0, 0, peq};
+        return Variant{64, rows == 26 ? 1 : 3, rows == 26 ? 26 : 0, LEAN_IMITATION, true};
     }
     // per-agent parameters, 25 rows, Helbing / Guo: the compile-time pair-once build with the partners' parameter rows in registers
     // (sfmstep_peragent.hip; one spill-free register budget for every grid)
-    if (kind == 0 && !peq && rows == 25 && w->type % 3 != 2 && !need_snap) return Variant{64, 1, 25, 0, false};
-    if (kind == 0) return Variant{64, 3, 0, 0, peq};
+    if (kind == LEAN_GENERIC && !peq && rows == 25 && w->type % 3 != 2 && !need_snap) return Variant{64, 1, 25, LEAN_GENERIC, false};
+    if (kind == LEAN_GENERIC) return Variant{64, 3, 0, LEAN_GENERIC, peq};
     // small plain worlds (10 humans: BASELINE.json configs[1]; 5: the reference's default environment): one world per 16-lane
     // DPP row, partners exchanged with row shifts instead of LDS (rowstep.hip).  CROWDSTEP_ROW16=0 keeps them on the LDS kernel.
     const char* row16_env = std::getenv("CROWDSTEP_ROW16");
     const bool row16_on = !(row16_env && row16_env[0] == '0');
-    if (kind == 1 && row16_on && !need_snap && csimpl::row16_supports(rows)) return Variant{16, 2, rows, 1, true};
+    if (kind == LEAN_PLAIN && row16_on && !need_snap && csimpl::row16_supports(rows)) return Variant{16, 2, rows, LEAN_PLAIN, true};
     // Compile-time row counts (partner groups laid out at compile time: no loop, no scalar branches): the BASELINE.json
     // configurations (10, 25, 50 humans) and the shapes around them -- 20 and 30 humans, and each with the visible robot's extra
     // row (6, 11, 26, 51).  Register budgets: 25 / 26 / 30 / 20 rows = OCC 1 (spill-free, ~136 VGPRs) while the grid holds at most
     // two waves per SIMD, OCC 4 (128 VGPRs, a few spills) beyond; 10 / 11 / 6 rows fit 128 VGPRs without spills; 50 / 51 rows
     // unrolled spill 30-47 VGPRs at the 4-wave budget and take the three-wave one (168 VGPRs).
     struct Row { int kind, rows, occ_sparse, occ_crowded; };
-    static const Row table[] = {{1, 25, 1, 4}, {1, 30, 1, 4}, {1, 20, 1, 4}, {1, 10, 4, 4}, {1, 50, 3, 3}, {2, 50, 3, 3},
-                                {3, 26, 1, 4}, {3, 6, 4, 4}, {3, 11, 4, 4}, {3, 51, 3, 3}};
+    static const Row table[] = {{LEAN_PLAIN, 25, 1, 4}, {LEAN_PLAIN, 30, 1, 4}, {LEAN_PLAIN, 20, 1, 4}, {LEAN_PLAIN, 10, 4, 4}, {LEAN_PLAIN, 50, 3, 3},
+                                {LEAN_WALLS, 50, 3, 3}, {LEAN_ROBOT_ROW, 26, 1, 4}, {LEAN_ROBOT_ROW, 6, 4, 4}, {LEAN_ROBOT_ROW, 11, 4, 4}, {LEAN_ROBOT_ROW, 51, 3, 3}};
     for (const Row& r : table)
         if (r.kind == kind && r.rows == rows) return Variant{64, crowded ? r.occ_crowded : r.occ_sparse, rows, kind, true};
     // any other row count: the run-time partner loop keeps the budget of THREE waves per SIMD on every grid: its 128-VGPR build
@@ -297,15 +297,14 @@ kfn variant_kernel(const Variant& v, int type)
 }
 
 // The robot's no-train policy decided in the step launch's head (cs_gym_step_policy; sfmstep_kernel.h POLICY).  A build that decides is
-// the TWIN of the build the plain Gym step runs for the same worlds -- same budget, same row count, LEAN + 8 -- so that everything behind
+// the TWIN of the build the plain Gym step runs for the same worlds -- same budget, same row count, LEAN | LEAN_POLICY -- so that everything behind
 // the decision is the same instruction stream on the same operands; worlds whose build has no twin (walls, the DPP-row kernel's small
 // worlds, the compile-time row counts nobody asked a twin for) decide in a launch of their own.
 struct PolicyArgs { int id; float time_step; const float* params; float* d_action; };
-constexpr int LEAN_POLICY = 8;
 
 Variant policy_twin(Variant v)
 {
-    if (v.maxt == 64 && v.peq && (v.lean == 1 || v.lean == 3)) { v.lean += LEAN_POLICY; return v; }
+    if (v.maxt == 64 && v.peq && (v.lean == LEAN_PLAIN || v.lean == LEAN_ROBOT_ROW)) { v.lean |= LEAN_POLICY; return v; }
     return Variant{0, 0, 0, 0, v.peq};
 }
 
@@ -329,14 +328,14 @@ GymHead gym_head(float* d_out, const float* d_global_time, float T, const float*
     return g;
 }
 
-// Dynamic LDS of a k_sfm_step block, and the two kernel arguments that follow from it (one function for the launch and for
-// cs_step_variant, which reports the figure: the blocks a CU holds are decided by it -- sixteen of the 25-row build, twelve of the 50-row
-// wall build -- and a region added for one build on every launch costs the others a block without any test noticing; tests/test_gpu_parity.py
-// asserts the figures of the benched builds).
 // independent one-wavefront blocks per workgroup of the step kernels (sfmstep_kernel.h); CROWDSTEP_WG_WAVES = 1 / 2 / 4 for A/B, read once
-int step_wg_waves();
+int step_wg_waves()
+{
+    static const int v = []{ const char* e = std::getenv("CROWDSTEP_WG_WAVES"); const int x = e ? std::atoi(e) : 4; return (x == 1 || x == 2 || x == 4) ? x : 4; }();
+    return v;
+}
 // ... as launched for a block of `shmem` bytes of dynamic LDS: halved until the workgroup stays within the default 64 KB dynamic-LDS limit
-// (one helper for launch_step and cs_step_variant: the reported width is the launched one)
+// (step_plan: the reported width is the launched one)
 int step_wg_waves_for(size_t shmem)
 {
     int wg = step_wg_waves();
@@ -344,15 +343,13 @@ int step_wg_waves_for(size_t shmem)
     while (wg > 1 && per_wave * (size_t)wg > 64 * 1024) wg /= 2;
     return wg;
 }
-int step_wg_waves()
-{
-    static const int v = []{ const char* e = std::getenv("CROWDSTEP_WG_WAVES"); const int x = e ? std::atoi(e) : 4; return (x == 1 || x == 2 || x == 4) ? x : 4; }();
-    return v;
-}
 
-size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, bool peq, int* seg_tab_out, int* wall_pairs_out)
+// Dynamic LDS of a k_sfm_step block, and the two kernel arguments that follow from it (step_plan: one figure for the launch and for
+// cs_step_variant, which reports it: the blocks a CU holds are decided by it -- sixteen of the 25-row build, twelve of the 50-row
+// wall build -- and a region added for one build on every launch costs the others a block without any test noticing; tests/test_gpu_parity.py
+// asserts the figures of the benched builds).
+size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, bool peq, int& seg_tab, int& wall_pairs)
 {
-    struct { int seg_tab, wall_pairs; } a = {0, 0};
     // lds_p [2][2T+PADR] float4, lds_v [2][2T+PADR] float2, lds_vr [2][T] float2, respawn scratch 2 x [T] x 4 B,
     // reaction accumulators [UA][2T] float2 (pair-once loop: all_params_equal, block of one wavefront)
     size_t shmem = (size_t)g.block * (4 * sizeof(float4) + 4 * sizeof(float2) + 2 * sizeof(float2) + 2 * sizeof(float)) +
@@ -362,46 +359,79 @@ size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, bool peq, int* seg_
     if (!peq && g.block == 64 && w->type % 3 != 2)
         shmem += (size_t)UA * ACC_PITCH * sizeof(float2) + (size_t)(2 * g.block + PADR) * sizeof(float4);
     // wall segment table (x1, y1, e, 1/|e|^2), shared or one per world of the block, when it is small enough
-    const long seg_tab = (long)w->O * w->Smax * ((w->flags & CS_OBSTACLES_SHARED) ? 1 : g.wpb);
-    a.seg_tab = (seg_tab > 0 && seg_tab * 20 <= 16 * 1024) ? (int)seg_tab : 0;
-    shmem += (size_t)a.seg_tab * (sizeof(float4) + sizeof(float)) + 16 + (size_t)(a.seg_tab > 0 ? a.seg_tab / w->Smax : 0) * sizeof(float4);
+    const long segs = (long)w->O * w->Smax * ((w->flags & CS_OBSTACLES_SHARED) ? 1 : g.wpb);
+    seg_tab = (segs > 0 && segs * 20 <= 16 * 1024) ? (int)segs : 0;
+    shmem += (size_t)seg_tab * (sizeof(float4) + sizeof(float)) + 16 + (size_t)(seg_tab > 0 ? seg_tab / w->Smax : 0) * sizeof(float4);
     {
         // one (agent, polygon) pair per lane: Helbing-type walls (no tangential term outside a contact), at most 4 polygons staged in LDS, no
         // respawn rule (the only way an agent jumps); CROWDSTEP_WALL_PAIRS=0 keeps every launch on the all-lanes pass (A/B)
         static const bool wp_env = []{ const char* e = std::getenv("CROWDSTEP_WALL_PAIRS"); return !(e && e[0] == '0'); }();
         const bool guo_walls = w->type == 1 || w->type == 4 || w->type == 7;
-        a.wall_pairs = (wp_env && peq && a.seg_tab > 0 && a.seg_tab < 4096 && w->O > 0 && w->O <= 4 && !guo_walls && !(w->flags & CS_RESPAWN) && g.block == 64) ? 1 : 0;
+        wall_pairs = (wp_env && peq && seg_tab > 0 && seg_tab < 4096 && w->O > 0 && w->O <= 4 && !guo_walls && !(w->flags & CS_RESPAWN) && g.block == 64) ? 1 : 0;
     }
     // wall pairs (sfmstep_kernel.h): the pairs' records and forces, the wall law -- the LAST region of the block's LDS, only where it is used
     // (on every launch it cost the 25-row build its sixteenth block per CU: 8192 worlds 51 -> 60 us, 32768 worlds 160 -> 181 us)
-    if (a.wall_pairs) shmem += 128 * sizeof(int) + 130 * sizeof(float2) + sizeof(float4);
-    if (seg_tab_out) *seg_tab_out = a.seg_tab;
-    if (wall_pairs_out) *wall_pairs_out = a.wall_pairs;
+    if (wall_pairs) shmem += 128 * sizeof(int) + 130 * sizeof(float2) + sizeof(float4);
     return shmem;
 }
 
-int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, const float* d_action,
-                float* d_peek, hipStream_t stream, float4* d_snap = nullptr, float* d_trace = nullptr, const RobotModel* rm = nullptr,
-                float* d_obs = nullptr, int obs_cols = 0, const GymHead* gym = nullptr, const PolicyArgs* pol = nullptr)
+// What a step launch of `w` in `mode` runs, decided ONCE per call (as orca_plan is for ORCA): the launch, the one-launch queries of the Gym
+// entries and the diagnostic entries (cs_step_variant, cs_gym_step_policy_variant) all read the same plan, so what is reported is what is launched.
+struct StepPlan {
+    Geometry g; bool big;              // big: worlds beyond one block -- the grid path (bigworld.hip), nothing below applies
+    Variant v, twin; kfn fn, twin_fn;  // the build and the one that also decides the robot's policy (where asked for and there is one), their kernels
+    size_t lds; int seg_tab, wall_pairs, wg;   // dynamic LDS of a block with the two kernel arguments that follow from it; blocks per workgroup
+};
+
+int step_plan(const cs_worlds* w, int mode, StepPlan& p, bool need_snap = false, bool robot_model = false, bool policy = false)
 {
-    int rc = check_worlds(w);
-    if (rc) return rc;
-    Geometry g;
-    rc = geometry(w, g);
-    if (rc) return rc;
+    p = StepPlan{};
+    int rc;
+    if ((rc = check_worlds(w)) || (rc = geometry(w, p.g))) return rc;
+    p.big = rows_of(w) > csimpl::big_world_min_rows(1024);
+    if (p.big) return CS_OK;
+    p.v = select_variant(w, mode, p.g, need_snap, robot_model);
+    p.wg = 1;
+    if (p.v.maxt != 64 && p.v.maxt != 1024) return CS_OK;
+    p.fn = variant_kernel(p.v, w->type);
+    if (policy) { p.twin = policy_twin(p.v); p.twin_fn = variant_kernel(p.twin, w->type); }
+    p.lds = step_lds_bytes(w, p.g, p.v.peq, p.seg_tab, p.wall_pairs);
+    if (p.g.block == 64) p.wg = step_wg_waves_for(p.lds);
+    return CS_OK;
+}
+
+// One step launch: StepLaunch r{dt, nsub, mode, stream}, then what the entry sets by name; the rest stays zero
+struct StepLaunch {
+    float dt; int nsub, mode; hipStream_t stream;
+    float* d_out; const float* d_action; float* d_peek;
+    float4* snap; float* trace; const RobotModel* robot_model;
+    float* obs; int obs_cols;
+    const GymHead* gym; const PolicyArgs* policy;
+};
+
+int obs_cols_of(int theta_and_omega_visible) { return theta_and_omega_visible ? 7 : 5; }
+
+// `made`: the plan of the same worlds, mode and options where the caller has decided on it already
+int launch_step(const cs_worlds* w, const StepLaunch& r, const StepPlan* made = nullptr)
+{
+    StepPlan own;
+    if (!made)
+        if (const int rc = step_plan(w, r.mode, own, r.snap != nullptr, r.robot_model != nullptr, r.policy != nullptr)) return rc;
+    const StepPlan& p = made ? *made : own;
+    const Geometry& g = p.g;
     const int rows = rows_of(w);
-    if (rows > csimpl::big_world_min_rows(1024))   // worlds beyond one block: partners through a uniform grid in HBM (bigworld.hip)
-        return csimpl::sfm_big_launch(w, dt, nsub, d_out ? d_out : w->d_state, (mode & M_MUTATE_INPUT) ? 1 : 0,
-                                      (mode & M_ROBOT_FROM_ARRAY) != 0, d_action, (mode & M_PEEK) ? d_peek : nullptr, stream, d_trace);
+    if (p.big)   // worlds beyond one block: partners through a uniform grid in HBM (bigworld.hip)
+        return csimpl::sfm_big_launch(w, r.dt, r.nsub, r.d_out ? r.d_out : w->d_state, (r.mode & M_MUTATE_INPUT) ? 1 : 0,
+                                      (r.mode & M_ROBOT_FROM_ARRAY) != 0, r.d_action, (r.mode & M_PEEK) ? r.d_peek : nullptr, r.stream, r.trace);
     KArgs a;
     std::memset(&a, 0, sizeof(a));
     a.W = w->W; a.n = w->n; a.rows = rows; a.G = w->G; a.O = w->O; a.Smax = w->Smax;
-    a.type = w->type; a.flags = w->flags; a.mode = mode; a.nsub = nsub; a.wpb = g.wpb; a.ws = g.ws; a.dt = dt;
-    a.Sin = w->d_state; a.Sout = d_out ? d_out : w->d_state;
+    a.type = w->type; a.flags = w->flags; a.mode = r.mode; a.nsub = r.nsub; a.wpb = g.wpb; a.ws = g.ws; a.dt = r.dt;
+    a.Sin = w->d_state; a.Sout = r.d_out ? r.d_out : w->d_state;
     state_strides(w, a.in_as, a.in_fs);
     a.out_as = a.in_as; a.out_fs = a.in_fs;
     a.goals = w->d_goals; a.params = w->d_params; a.safety = w->d_safety; a.obstacles = w->d_obstacles;
-    a.robot = w->d_robot; a.action = d_action; a.peek_out = d_peek;
+    a.robot = w->d_robot; a.action = r.d_action; a.peek_out = r.d_peek;
     a.bx = w->respawn_bound_x; a.by = w->respawn_bound_y;
     a.world_flags = w->d_world_flags;
     {   // The reach of a wall's force: beyond 22 e-folding lengths it is below |A| e^-22 = 5.6e-7 N for the reference's A = 2000 N -- less than
@@ -415,46 +445,123 @@ int launch_step(const cs_worlds* w, float dt, int nsub, int mode, float* d_out, 
 #ifdef CS_STAMPS
     a.stamps = g_stamp_buf;
 #endif
-    a.snap = d_snap;
-    a.trace = d_trace;
-    a.obs = d_obs; a.obs_cols = obs_cols;
-    Variant v = select_variant(w, mode, g, d_snap != nullptr, rm != nullptr);
-    if (pol) {   // (callers ask policy_step_is_one_launch first)
-        v = policy_twin(v);
-        if (!gym || rm || !variant_kernel(v, w->type)) return fail(CS_ERR_ARG, "no step build decides the robot's policy for these worlds");
+    a.snap = r.snap;
+    a.trace = r.trace;
+    a.obs = r.obs; a.obs_cols = r.obs_cols;
+    const Variant& v = r.policy ? p.twin : p.v;
+    const kfn fn = r.policy ? p.twin_fn : p.fn;
+    if (const PolicyArgs* pol = r.policy) {   // (the Gym step asks the plan for the twin first)
+        if (!r.gym || r.robot_model || !fn) return fail(CS_ERR_ARG, "no step build decides the robot's policy for these worlds");
         a.pnt_policy = pol->id; a.pnt_time_step = pol->time_step; a.pnt_action = pol->d_action;
         if (pol->params) { std::memcpy(a.pnt_P, pol->params, sizeof(a.pnt_P)); a.pnt_mass = pol->params[CS_PNT_MASS]; }
     }
-    if (gym) {
+    if (r.gym) {
         if (v.maxt != 64) return fail(CS_ERR_ARG, "the Gym head runs inside the step launch of blocks of one wavefront only");
-        a.gym = *gym;
+        a.gym = *r.gym;
     }
-    if (rm) {
-        if (v.lean != 4) return fail(CS_ERR_ARG, "the robot's motion model runs inside the crowd's launch only for the plain crowd batch with a robot row");
+    if (const RobotModel* rm = r.robot_model) {
+        if (v.lean != LEAN_IMITATION) return fail(CS_ERR_ARG, "the robot's motion model runs inside the crowd's launch only for the plain crowd batch with a robot row");
         a.rm_type = rm->type; a.rm_margin = rm->margin; a.rm_hmargin = rm->d_human_margin; a.rm_memory = rm->d_memory;
         std::memcpy(a.rm_P, rm->params, sizeof(a.rm_P));
     }
-    const bool peq = v.peq;
-    if (v.maxt == 16) return csimpl::row16_launch(a, stream);
-    const kfn fn = variant_kernel(v, w->type);
+    if (v.maxt == 16) return csimpl::row16_launch(a, r.stream);
     if (!fn) return fail(CS_ERR_ARG, "no kernel build for this variant");
-    const size_t shmem = step_lds_bytes(w, g, peq, &a.seg_tab, &a.wall_pairs);
-    if (shmem > 64 * 1024) // one world per block with > ~600 rows
-        HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    a.seg_tab = p.seg_tab; a.wall_pairs = p.wall_pairs;
+    if (p.lds > 64 * 1024) // one world per block with > ~600 rows
+        HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     // two one-wavefront blocks per SIMD (the benchmark's 4096 x 25): the second half of the grid shares each SIMD with an older wavefront
     a.young_from = (g.block == 64 && g.grid == 2 * csimpl::device_simds()) ? g.grid / 2 : 0x7fffffff;
-    a.wg_waves = 1; a.lds_per_wave = 0;
+    a.wg_waves = p.wg; a.lds_per_wave = 0;
     if (g.block == 64) {
         // one-wavefront builds: wg_waves independent wavefronts per workgroup (sfmstep_kernel.h)
-        a.lds_per_wave = (int)((shmem + 15) & ~(size_t)15);
-        a.wg_waves = step_wg_waves_for(shmem);
-        hipLaunchKernelGGL(fn, dim3((g.grid + a.wg_waves - 1) / a.wg_waves), dim3(64 * a.wg_waves), (size_t)a.lds_per_wave * a.wg_waves, stream, a);
-        HIP_TRY(hipGetLastError());
-        return CS_OK;
-    }
-    hipLaunchKernelGGL(fn, dim3(g.grid), dim3(g.block), shmem, stream, a);
+        a.lds_per_wave = (int)((p.lds + 15) & ~(size_t)15);
+        hipLaunchKernelGGL(fn, dim3((g.grid + a.wg_waves - 1) / a.wg_waves), dim3(64 * a.wg_waves), (size_t)a.lds_per_wave * a.wg_waves, r.stream, a);
+    } else
+        hipLaunchKernelGGL(fn, dim3(g.grid), dim3(g.block), p.lds, r.stream, a);
     HIP_TRY(hipGetLastError());
     return CS_OK;
+}
+
+// the wave-per-world reward kernel (n <= 64) with the Gym head `g`: cs_collision_reward (reward row only) and cs_collision_reward_gym
+int launch_reward_wave(const cs_worlds* w, const float* d_action, const GymHead& g, void* stream)
+{
+    long as, fs;
+    state_strides(w, as, fs);
+    const int wpb = 64 / w->n, grid = (w->W + wpb - 1) / wpb;
+    hipLaunchKernelGGL(k_collision_reward_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w->W, w->n, rows_of(w), wpb,
+                       (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action, g);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// cs_gym_step_is_one_launch, with the step's plan `p` (and the policy's twin where `policy` asks for it) where the answer is not 0: ONE launch
+// where the step kernel is the LDS kernel of one wavefront per block (SFM / HSFM worlds of up to 64 rows); the two launches everywhere else
+// (ORCA, social momentum, the DPP-row kernel's small worlds keep their own launch: same results)
+int gym_one_launch(const cs_worlds* w, StepPlan& p, bool policy = false)
+{
+    if (!w || w->type < 0 || w->type > 8 || rows_of(w) > 64 || w->W <= 0 || w->n <= 0) return 0;
+    if (step_plan(w, commit_mode(w), p, false, false, policy) || p.v.maxt != 64) return 0;
+    return w->O > 0 ? 1 : 2;   // 2: cs_gym_step_staged as well (the take-over in the epilogue is compiled into the builds without walls: sfmstep_kernel.h FOLD)
+}
+
+// the staged take-over of cs_gym_step_staged / cs_gym_step_staged_policy, and what the step needs of its books
+struct Staged { const cs_generator* gen; const cs_worlds* staging; const cs_stage_book* book; };
+
+int check_staged(const cs_gym_book* book, const cs_stage_book* sb)
+{
+    if (const int rc = check_stage_book(sb)) return rc;
+    if (!sb->d_pending || !sb->d_failed) return fail(CS_ERR_ARG, "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed");
+    if (!book->auto_reset && !book->d_prev_mask) return fail(CS_ERR_ARG, "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)");
+    if (book->d_seeds != sb->d_seeds) return fail(CS_ERR_ARG, "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer");
+    return CS_OK;
+}
+
+// the robot's policy of cs_gym_step_policy / cs_gym_step_staged_policy
+int check_policy(const cs_worlds* w, const PolicyArgs& p)
+{
+    if (p.id < CS_PNT_BP || p.id > CS_PNT_SFM_MOUSSAID) return fail(CS_ERR_ARG, "unknown no-train policy id (CS_PNT_*)");
+    if (!(p.time_step > 0.0f)) return fail(CS_ERR_ARG, "the policy's time_step must be positive");
+    if (w->flags & CS_ROBOT_UNICYCLE) return fail(CS_ERR_ARG, "the no-train policies act in ActionXY: a unicycle batch (CS_ROBOT_UNICYCLE) cannot take them");
+    if (!w->d_robot) return fail(CS_ERR_ARG, "the robot's policy needs the robot rows (cs_worlds.d_robot is null)");
+    if (!p.d_action) return fail(CS_ERR_ARG, "null action buffer: the decided actions are stored there");
+    if (p.id >= CS_PNT_SFM_HELBING) {
+        if (!p.params) return fail(CS_ERR_ARG, "the social-force policies need their parameters");
+        if (!(p.params[CS_PNT_MASS] != 0.0f) || !(p.params[0] != 0.0f)) return fail(CS_ERR_ARG, "mass and relaxation_time must be non-zero");
+    }
+    return CS_OK;
+}
+
+// The one body of cs_gym_step, cs_gym_step_staged (`st`), cs_gym_step_policy (`pol`) and cs_gym_step_staged_policy (both): every check before
+// the first device call, the plan made once.  Worlds that do not take the one launch run cs_collision_reward_gym + cs_step_observe; a policy
+// whose worlds have no deciding build runs cs_policy_no_train in front of the same step: the same results.
+int gym_step(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float T, float* d_global_time, const float* reward_cfg,
+             float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, void* stream, const Staged* st = nullptr, const PolicyArgs* pol = nullptr)
+{
+    if (!w || !book || !d_obs || (st && (!st->gen || !st->staging || !st->book))) return fail(CS_ERR_ARG, "null argument");
+    if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
+    int rc;
+    if (pol && (rc = check_policy(w, *pol))) return rc;
+    if ((rc = check_gym_book(book))) return rc;
+    if (st && (rc = check_staged(book, st->book))) return rc;
+    StepPlan plan;
+    const int one = gym_one_launch(w, plan, pol != nullptr);
+    if (st && one != 2) return fail(CS_ERR_ARG, "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)");
+    const int cols = obs_cols_of(theta_and_omega_visible);
+    if (!one) {
+        if (pol && (rc = cs_policy_no_train(pol->id, w->W, w->n, w->d_robot, d_obs, cols, pol->time_step, pol->params, pol->d_action, stream))) return rc;
+        rc = cs_collision_reward_gym(w, d_action, T, d_global_time, reward_cfg, d_out, book, stream);
+        return rc ? rc : cs_step_observe(w, dt, n_substeps, d_action, theta_and_omega_visible, d_obs, stream);
+    }
+    if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
+    GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
+    if (st && (rc = csimpl::stage_fold(st->gen, st->staging, w, st->book, cols, d_obs, gh.fold))) return rc;
+    if (pol && !plan.twin_fn) {   // decide from the observation rows, then the Gym step as it is
+        if ((rc = cs_policy_no_train(pol->id, w->W, w->n, w->d_robot, d_obs, cols, pol->time_step, pol->params, pol->d_action, stream))) return rc;
+        pol = nullptr;
+    }
+    StepLaunch r{dt, n_substeps, commit_mode(w), (hipStream_t)stream};
+    r.d_action = d_action; r.obs = d_obs; r.obs_cols = cols; r.gym = &gh; r.policy = pol;
+    return launch_step(w, r, &plan);
 }
 
 } // namespace
@@ -543,7 +650,9 @@ int cs_update_humans_parallel(const cs_worlds* w, float dt, float* d_out, void* 
     cs_worlds ww = *w;
     ww.flags &= ~CS_RESPAWN;
     ww.d_robot = nullptr;
-    return launch_step(&ww, dt, 1, mode, d_out, nullptr, nullptr, (hipStream_t)stream);
+    StepLaunch r{dt, 1, mode, (hipStream_t)stream};
+    r.d_out = d_out;
+    return launch_step(&ww, r);
 }
 
 int cs_step(const cs_worlds* w, float dt, int n_substeps, const float* d_action, void* stream)
@@ -553,8 +662,9 @@ int cs_step(const cs_worlds* w, float dt, int n_substeps, const float* d_action,
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
     if (w->type == CS_ORCA) return csimpl::orca_launch(w, dt, n_substeps, d_action, nullptr, (hipStream_t)stream);
     if (w->type == CS_SOCIAL_MOMENTUM) return csimpl::social_momentum_launch(w, dt, n_substeps, d_action, nullptr, (hipStream_t)stream);
-    const int mode = commit_mode(w);
-    return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream);
+    StepLaunch r{dt, n_substeps, commit_mode(w), (hipStream_t)stream};
+    r.d_action = d_action;
+    return launch_step(w, r);
 }
 
 int cs_step_observe(const cs_worlds* w, float dt, int n_substeps, const float* d_action, int theta_and_omega_visible, float* d_obs,
@@ -569,114 +679,37 @@ int cs_step_observe(const cs_worlds* w, float dt, int n_substeps, const float* d
         return rc ? rc : cs_gym_observe(w, theta_and_omega_visible, d_obs, stream);
     }
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
-    const int mode = commit_mode(w);
-    return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
-                       theta_and_omega_visible ? 7 : 5);
+    StepLaunch r{dt, n_substeps, commit_mode(w), (hipStream_t)stream};
+    r.d_action = d_action; r.obs = d_obs; r.obs_cols = obs_cols_of(theta_and_omega_visible);
+    return launch_step(w, r);
 }
 
 int cs_gym_step_is_one_launch(const cs_worlds* w)
 {
-    // ONE launch where the step kernel is the LDS kernel of one wavefront per block (SFM / HSFM worlds of up to 64 rows); the two
-    // launches everywhere else (ORCA, social momentum, the DPP-row kernel's small worlds keep their own launch: same results)
-    if (!w) return 0;
-    const int rows = rows_of(w);
-    bool fused = w->type >= 0 && w->type <= 8 && rows <= 64 && w->W > 0 && w->n > 0;
-    if (fused) {
-        if (check_worlds(w)) fused = false;
-        else {
-            Geometry g;
-            if (geometry(w, g)) fused = false;
-            else {
-                fused = select_variant(w, commit_mode(w), g).maxt == 64;   // (small plain worlds keep the DPP-row kernel and its own reward launch)
-            }
-        }
-    }
-    if (!fused) return 0;
-    // 2: cs_gym_step_staged as well (the take-over in the epilogue is compiled into the builds without walls: sfmstep_kernel.h FOLD)
-    return w->O > 0 ? 1 : 2;
+    StepPlan p;
+    return gym_one_launch(w, p);
 }
 
 int cs_gym_step(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float T, float* d_global_time, const float* reward_cfg,
                 float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, void* stream)
 {
-    if (!w || !book || !d_obs) return fail(CS_ERR_ARG, "null argument");
-    if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    const bool fused = cs_gym_step_is_one_launch(w) != 0;
-    if (!fused) {
-        const int rc = cs_collision_reward_gym(w, d_action, T, d_global_time, reward_cfg, d_out, book, stream);
-        return rc ? rc : cs_step_observe(w, dt, n_substeps, d_action, theta_and_omega_visible, d_obs, stream);
-    }
-    if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    if (const int rc = check_gym_book(book)) return rc;
-    const int mode = commit_mode(w);
-    const GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
-    return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
-                       theta_and_omega_visible ? 7 : 5, &gh);
+    return gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream);
 }
 
 int cs_gym_step_staged(const cs_worlds* w, float dt, int n_substeps, const float* d_action, float T, float* d_global_time, const float* reward_cfg,
                        float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, const cs_generator* gen,
                        const cs_worlds* staging, const cs_stage_book* stage_book, void* stream)
 {
-    if (!w || !book || !d_obs || !gen || !staging || !stage_book) return fail(CS_ERR_ARG, "null argument");
-    if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    if (!stage_book->d_pending || !stage_book->d_failed) return fail(CS_ERR_ARG, "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed");
-    if (!book->auto_reset && !book->d_prev_mask) return fail(CS_ERR_ARG, "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)");
-    if (cs_gym_step_is_one_launch(w) != 2) return fail(CS_ERR_ARG, "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)");
-    if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    if (const int rc = check_gym_book(book)) return rc;
-    if (book->d_seeds != stage_book->d_seeds) return fail(CS_ERR_ARG, "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer");
-    const int mode = commit_mode(w);
-    GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
-    const int rc = csimpl::stage_fold(gen, staging, w, stage_book, theta_and_omega_visible ? 7 : 5, d_obs, gh.fold);
-    if (rc) return rc;
-    return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
-                       theta_and_omega_visible ? 7 : 5, &gh);
-}
-
-// cs_gym_step_policy / cs_gym_step_staged_policy: the argument checks of the two (no device call before they pass)
-static int check_policy_step(const cs_worlds* w, int n_substeps, const float* d_action, const cs_gym_book* book, const float* d_obs,
-                             int policy, float time_step, const float* params)
-{
-    if (!w || !book || !d_obs) return fail(CS_ERR_ARG, "null argument");
-    if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
-    if (policy < CS_PNT_BP || policy > CS_PNT_SFM_MOUSSAID) return fail(CS_ERR_ARG, "unknown no-train policy id (CS_PNT_*)");
-    if (!(time_step > 0.0f)) return fail(CS_ERR_ARG, "the policy's time_step must be positive");
-    if (w->flags & CS_ROBOT_UNICYCLE) return fail(CS_ERR_ARG, "the no-train policies act in ActionXY: a unicycle batch (CS_ROBOT_UNICYCLE) cannot take them");
-    if (!w->d_robot) return fail(CS_ERR_ARG, "the robot's policy needs the robot rows (cs_worlds.d_robot is null)");
-    if (!d_action) return fail(CS_ERR_ARG, "null action buffer: the decided actions are stored there");
-    if (policy >= CS_PNT_SFM_HELBING) {
-        if (!params) return fail(CS_ERR_ARG, "the social-force policies need their parameters");
-        if (!(params[CS_PNT_MASS] != 0.0f) || !(params[0] != 0.0f)) return fail(CS_ERR_ARG, "mass and relaxation_time must be non-zero");
-    }
-    return check_gym_book(book);
-}
-
-// 0: the decision is a launch of its own in front of the Gym step's; 1: cs_gym_step_policy is ONE launch; 2: cs_gym_step_staged_policy too
-static int policy_step_is_one_launch(const cs_worlds* w)
-{
-    const int one = cs_gym_step_is_one_launch(w);
-    if (!one) return 0;
-    Geometry g;
-    if (geometry(w, g)) return 0;
-    return variant_kernel(policy_twin(select_variant(w, commit_mode(w), g)), w->type) ? one : 0;
+    const Staged st{gen, staging, stage_book};
+    return gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream, &st);
 }
 
 int cs_gym_step_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time, const float* reward_cfg,
                        float* d_out, const cs_gym_book* book, int theta_and_omega_visible, float* d_obs, int policy, float policy_time_step,
                        const float* policy_params, void* stream)
 {
-    if (const int rc = check_policy_step(w, n_substeps, d_action, book, d_obs, policy, policy_time_step, policy_params)) return rc;
-    if (!policy_step_is_one_launch(w)) {   // decide from the observation rows, then the Gym step as it is: the same results
-        const int rc = cs_policy_no_train(policy, w->W, w->n, w->d_robot, d_obs, theta_and_omega_visible ? 7 : 5, policy_time_step, policy_params,
-                                          d_action, stream);
-        return rc ? rc : cs_gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream);
-    }
-    if (!d_global_time || !reward_cfg || !d_out) return fail(CS_ERR_ARG, "null argument");
-    const GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
     const PolicyArgs pol{policy, policy_time_step, policy_params, d_action};
-    return launch_step(w, dt, n_substeps, commit_mode(w), nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
-                       theta_and_omega_visible ? 7 : 5, &gh, &pol);
+    return gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream, nullptr, &pol);
 }
 
 int cs_gym_step_staged_policy(const cs_worlds* w, float dt, int n_substeps, float* d_action, float T, float* d_global_time, const float* reward_cfg,
@@ -684,37 +717,19 @@ int cs_gym_step_staged_policy(const cs_worlds* w, float dt, int n_substeps, floa
                               const cs_worlds* staging, const cs_stage_book* stage_book, int policy, float policy_time_step,
                               const float* policy_params, void* stream)
 {
-    if (const int rc = check_policy_step(w, n_substeps, d_action, book, d_obs, policy, policy_time_step, policy_params)) return rc;
-    if (!gen || !staging || !stage_book) return fail(CS_ERR_ARG, "null argument");
-    if (const int rc = check_stage_book(stage_book)) return rc;
-    if (!stage_book->d_pending || !stage_book->d_failed) return fail(CS_ERR_ARG, "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed");
-    if (!book->auto_reset && !book->d_prev_mask) return fail(CS_ERR_ARG, "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)");
-    if (book->d_seeds != stage_book->d_seeds) return fail(CS_ERR_ARG, "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer");
-    if (cs_gym_step_is_one_launch(w) != 2) return fail(CS_ERR_ARG, "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)");
-    if (policy_step_is_one_launch(w) != 2) {
-        const int rc = cs_policy_no_train(policy, w->W, w->n, w->d_robot, d_obs, theta_and_omega_visible ? 7 : 5, policy_time_step, policy_params,
-                                          d_action, stream);
-        return rc ? rc : cs_gym_step_staged(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, gen,
-                                            staging, stage_book, stream);
-    }
-    if (!d_global_time || !reward_cfg || !d_out) return fail(CS_ERR_ARG, "null argument");
-    GymHead gh = gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags);
-    const int rc = csimpl::stage_fold(gen, staging, w, stage_book, theta_and_omega_visible ? 7 : 5, d_obs, gh.fold);
-    if (rc) return rc;
+    const Staged st{gen, staging, stage_book};
     const PolicyArgs pol{policy, policy_time_step, policy_params, d_action};
-    return launch_step(w, dt, n_substeps, commit_mode(w), nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, d_obs,
-                       theta_and_omega_visible ? 7 : 5, &gh, &pol);
+    return gym_step(w, dt, n_substeps, d_action, T, d_global_time, reward_cfg, d_out, book, theta_and_omega_visible, d_obs, stream, &st, &pol);
 }
 
 int cs_gym_step_policy_variant(const cs_worlds* w, char* buf, size_t buflen)
 {
     if (!w || !buf || buflen == 0) return fail(CS_ERR_ARG, "null argument");
-    if (policy_step_is_one_launch(w)) {
-        Geometry g;
-        if (const int rc = geometry(w, g)) return rc;
-        const Variant v = policy_twin(select_variant(w, commit_mode(w), g));
+    StepPlan p;
+    if (gym_one_launch(w, p, true) && p.twin_fn) {
+        const Variant& v = p.twin;
         std::snprintf(buf, buflen, "k_sfm_step<SOC=%d,HEADED=%d,PEQ=1,MAXT=%d,OCC=%d,ROWS_CT=%d,LEAN=%d+%d> grid=%d block=%d wpb=%d (policy decided in the head)",
-                      w->type % 3, w->type / 3, v.maxt, v.occ, v.rows_ct, LEAN_POLICY, v.lean - LEAN_POLICY, g.grid, g.block, g.wpb);
+                      w->type % 3, w->type / 3, v.maxt, v.occ, v.rows_ct, LEAN_POLICY, v.lean - LEAN_POLICY, p.g.grid, p.g.block, p.g.wpb);
         return CS_OK;
     }
     const int n0 = std::snprintf(buf, buflen, "k_policy_no_train + ");
@@ -728,8 +743,9 @@ int cs_step_trace(const cs_worlds* w, float dt, int n_substeps, const float* d_a
     if (n_substeps <= 0) return fail(CS_ERR_ARG, "n_substeps must be positive");
     if (d_action && !w->d_robot) return fail(CS_ERR_ARG, "robot action given but cs_worlds.d_robot is null");
     if (w->type < 0 || w->type > 8) return fail(CS_ERR_ARG, "cs_step_trace covers the SFM / HSFM models (types 0..8)");
-    const int mode = commit_mode(w);
-    return launch_step(w, dt, n_substeps, mode, nullptr, d_action, nullptr, (hipStream_t)stream, nullptr, d_trace);
+    StepLaunch r{dt, n_substeps, commit_mode(w), (hipStream_t)stream};
+    r.d_action = d_action; r.trace = d_trace;
+    return launch_step(w, r);
 }
 
 int cs_peek(const cs_worlds* w, float dt, float* d_next, void* stream)
@@ -741,7 +757,9 @@ int cs_peek(const cs_worlds* w, float dt, float* d_next, void* stream)
     if ((w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
     cs_worlds ww = *w;
     ww.flags &= ~CS_RESPAWN; // update_humans(0, dt, post_update=False), motion_model_manager.py:705
-    return launch_step(&ww, dt, 1, mode, nullptr, nullptr, d_next, (hipStream_t)stream);
+    StepLaunch r{dt, 1, mode, (hipStream_t)stream};
+    r.d_peek = d_next;
+    return launch_step(&ww, r);
 }
 
 int cs_collision_reward(const cs_worlds* w, const float* d_action, float T, const float* d_global_time,
@@ -752,20 +770,13 @@ int cs_collision_reward(const cs_worlds* w, const float* d_action, float T, cons
     int rc;
     if ((rc = check_rows(w, false)) || (rc = check_layout(w))) return rc;
     if (!d_action || !d_global_time || !reward_cfg || !d_out || !w->d_robot) return fail(CS_ERR_ARG, "null argument");
-    const int rows = rows_of(w);
+    if (w->n <= 64) return launch_reward_wave(w, d_action, gym_head(d_out, d_global_time, T, reward_cfg, nullptr, w->W, w->flags), stream);
     long as, fs;
     state_strides(w, as, fs);
-    if (w->n <= 64) {
-        const int wpb = 64 / w->n, grid = (w->W + wpb - 1) / wpb;
-        hipLaunchKernelGGL(k_collision_reward_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w->W, w->n, rows, wpb,
-                           (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action,
-                           gym_head(d_out, d_global_time, T, reward_cfg, nullptr, w->W, w->flags));
-    } else {
-        const int block = 64, grid = (w->W + block - 1) / block;
-        hipLaunchKernelGGL(k_collision_reward, dim3(grid), dim3(block), 0, (hipStream_t)stream, w->W, w->n, rows,
-                           (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action, T, d_global_time,
-                           reward_cfg[0], reward_cfg[1], reward_cfg[2], reward_cfg[3], reward_cfg[4], d_out, (w->flags & CS_ROBOT_UNICYCLE) ? 1 : 0);
-    }
+    const int block = 64, grid = (w->W + block - 1) / block;
+    hipLaunchKernelGGL(k_collision_reward, dim3(grid), dim3(block), 0, (hipStream_t)stream, w->W, w->n, rows_of(w),
+                       (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action, T, d_global_time,
+                       reward_cfg[0], reward_cfg[1], reward_cfg[2], reward_cfg[3], reward_cfg[4], d_out, (w->flags & CS_ROBOT_UNICYCLE) ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return CS_OK;
 }
@@ -787,15 +798,7 @@ int cs_collision_reward_gym(const cs_worlds* w, const float* d_action, float T, 
         return cs_gym_bookkeeping(w->W, d_out, book->d_counter, book->d_seeds, book->d_mask, d_global_time, book->d_clock, book->clock_len,
                                   book->auto_reset, book->d_reward, book->d_terminated, book->d_truncated, book->d_info, book->seed_stride, stream);
     }
-    const int rows = rows_of(w);
-    long as, fs;
-    state_strides(w, as, fs);
-    const int wpb = 64 / w->n, grid = (w->W + wpb - 1) / wpb;
-    hipLaunchKernelGGL(k_collision_reward_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w->W, w->n, rows, wpb,
-                       (const float*)w->d_state, as, fs, (const float*)w->d_robot, d_action,
-                       gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags));
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
+    return launch_reward_wave(w, d_action, gym_head(d_out, d_global_time, T, reward_cfg, book, w->W, w->flags), stream);
 }
 
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream)
@@ -838,8 +841,9 @@ int cs_imitation_block(const cs_worlds* w, int32_t robot_type, const float* robo
         float4* snap = nullptr;
         int rc = csimpl::scratch((void**)&snap, csimpl::imitation_scratch_bytes(w, n_substeps), csimpl::SCRATCH_IMITATION, (hipStream_t)stream);
         if (rc) return rc;
-        rc = launch_step(w, dt, n_substeps, M_COMMIT_GOALS, nullptr, nullptr, nullptr, (hipStream_t)stream, snap);
-        if (rc) return rc;
+        StepLaunch r{dt, n_substeps, M_COMMIT_GOALS, (hipStream_t)stream};
+        r.snap = snap;
+        if ((rc = launch_step(w, r))) return rc;
         return csimpl::robot_block_launch(w, robot_type, robot_params, robot_margin, d_human_margin, d_robot_memory, dt, n_substeps, snap,
                                           (hipStream_t)stream);
     }
@@ -851,7 +855,9 @@ int cs_imitation_block(const cs_worlds* w, int32_t robot_type, const float* robo
                                  !(std::getenv("CROWDSTEP_IMITATION_FUSED") && std::getenv("CROWDSTEP_IMITATION_FUSED")[0] == '0');
     if (fusable_visible) {
         const RobotModel rm{robot_type, robot_params, robot_margin, d_human_margin ? d_human_margin : w->d_safety, d_robot_memory};
-        return launch_step(w, dt, n_substeps, M_COMMIT_GOALS | M_ROBOT_FROM_ARRAY, nullptr, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, &rm);
+        StepLaunch r{dt, n_substeps, M_COMMIT_GOALS | M_ROBOT_FROM_ARRAY, (hipStream_t)stream};
+        r.robot_model = &rm;
+        return launch_step(w, r);
     }
     for (int k = 0; k < n_substeps; ++k) {   // ORCA on either side, walls with a visible robot: the reference's strict alternation
         int rc = cs_robot_model_step(w, robot_type, robot_params, robot_margin, d_human_margin, d_robot_memory, dt, stream);
@@ -892,29 +898,26 @@ int cs_step_variant(const cs_worlds* w, int entry, char* buf, size_t buflen)
     if (entry < 0 || entry > 2) return fail(CS_ERR_ARG, "entry must be 0 (cs_step), 1 (cs_update_humans_parallel, out of place) or 2 (cs_peek)");
     if (w->type == CS_ORCA) return csimpl::orca_variant(w, buf, buflen);
     if (w->type == CS_SOCIAL_MOMENTUM) { std::snprintf(buf, buflen, "k_sm_step"); return CS_OK; }
-    int rc = check_worlds(w);
-    if (rc) return rc;
-    Geometry g;
-    rc = geometry(w, g);
-    if (rc) return rc;
     int mode = entry == 2 ? (int)M_PEEK : (int)M_COMMIT_GOALS;
     if (entry == 1) mode |= M_MUTATE_INPUT;
     if (entry != 1 && (w->flags & CS_ROBOT_ROW) && w->d_robot) mode |= M_ROBOT_FROM_ARRAY;
-    if (rows_of(w) > csimpl::big_world_min_rows(1024)) {
+    StepPlan p;
+    if (const int rc = step_plan(w, mode, p)) return rc;
+    const Geometry& g = p.g;
+    const Variant& v = p.v;
+    if (p.big) {
         std::snprintf(buf, buflen, "k_bw_sfm_step<SOC=%d,HEADED=%d,PEQ=%d> grid=%d block=256 (uniform grid in HBM)", w->type % 3, w->type / 3,
                       (w->flags & CS_ALL_PARAMS_EQUAL) ? 1 : 0, g.grid);
         return CS_OK;
     }
-    const Variant v = select_variant(w, mode, g);
     if (v.maxt == 16) {
         std::snprintf(buf, buflen, "k_sfm_step_row16<SOC=%d,HEADED=%d,ROWS=%d> grid=%d block=64 wpb=4", w->type % 3, w->type / 3, v.rows_ct, (w->W + 3) / 4);
         return CS_OK;
     }
-    const size_t lds = step_lds_bytes(w, g, v.peq, nullptr, nullptr);
     char wg[16] = "";
-    if (g.block == 64) std::snprintf(wg, sizeof(wg), " wg=%d", step_wg_waves_for(lds));
+    if (g.block == 64) std::snprintf(wg, sizeof(wg), " wg=%d", p.wg);
     std::snprintf(buf, buflen, "k_sfm_step<SOC=%d,HEADED=%d,PEQ=%d,MAXT=%d,OCC=%d,ROWS_CT=%d,LEAN=%d> grid=%d block=%d wpb=%d lds=%d%s",
-                  w->type % 3, w->type / 3, v.peq ? 1 : 0, v.maxt, v.occ, v.rows_ct, v.lean, g.grid, g.block, g.wpb, (int)lds, wg);
+                  w->type % 3, w->type / 3, v.peq ? 1 : 0, v.maxt, v.occ, v.rows_ct, v.lean, g.grid, g.block, g.wpb, (int)p.lds, wg);
     return CS_OK;
 }
 

@@ -60,6 +60,9 @@ constexpr int ACC_PITCH = 128; // float2 slots per accumulator row (block = one 
 //            + 8 (9 = 8 + 1, 11 = 8 + 3; the template argument is LEAN_ARG, the kernel's LEAN its low three bits) = POLICY: the robot's
 //            no-train policy (policy_no_train.h) is decided in the prologue from the rows the launch has loaded, before the Gym head
 //            consumes the action: cs_gym_step_policy.  New instantiations beside the old ones (sfmstep_policy*.hip), which do not change.
+// the LEAN values by name (the template parameter stays the int: no instantiation's name moves)
+constexpr int LEAN_GENERIC = 0, LEAN_PLAIN = 1, LEAN_WALLS = 2, LEAN_ROBOT_ROW = 3, LEAN_IMITATION = 4, LEAN_ROBOT_ROW_WALLS = 5;
+constexpr int LEAN_POLICY = 8;   // the policy bit, on top of LEAN_PLAIN / LEAN_ROBOT_ROW
 constexpr int WG_WAVES_MAX = 4;   // (launch bound of the one-wavefront builds: four independent wavefronts per workgroup; a bound of eight -- which measures the same as
                                   //  four -- makes the compiler allocate the Moussaid builds ten registers fewer and their launches 2 us longer)
 template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEAN_ARG>
@@ -71,9 +74,9 @@ template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEA
 // the eight XCDs, whatever the workgroup size: HISTORY.md.)
 __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_sfm_step(const KArgs a)
 {
-    constexpr int LEAN = LEAN_ARG & 7;
-    constexpr bool POLICY = LEAN_ARG >= 8;
-    static_assert(!POLICY || (MAXT == 64 && (LEAN == 1 || LEAN == 3)), "the policy is decided in the head of the plain crowd batch's builds without walls");
+    constexpr int LEAN = LEAN_ARG & (LEAN_POLICY - 1);
+    constexpr bool POLICY = (LEAN_ARG & LEAN_POLICY) != 0;
+    static_assert(!POLICY || (MAXT == 64 && (LEAN == LEAN_PLAIN || LEAN == LEAN_ROBOT_ROW)), "the policy is decided in the head of the plain crowd batch's builds without walls");
     extern __shared__ __align__(16) unsigned char smem_raw0[];
     const int wave_in_wg = MAXT == 64 ? (int)(threadIdx.x >> 6) : 0;
     unsigned char* smem_raw = smem_raw0 + (MAXT == 64 ? (size_t)wave_in_wg * a.lds_per_wave : 0);
@@ -118,9 +121,9 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     float2* lds_wcv = reinterpret_cast<float2*>(lds_g0x);                                        // [T] the agents' refreshed linear velocities (contact terms)
     const int tid = MAXT == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     static_assert(!LEAN || (PEQ && MAXT == 64), "the lean build is a pair-once build");
-    constexpr bool LEAN_ROBOT = LEAN == 3 || LEAN == 4 || LEAN == 5;   // the robot is the last row (5: with walls)
-    constexpr bool IMIT = LEAN == 4;                       // ... and follows its own human motion model
-    constexpr bool NO_WALLS = LEAN == 1 || LEAN == 3 || LEAN == 4;     // wall code compiled out
+    constexpr bool LEAN_ROBOT = LEAN == LEAN_ROBOT_ROW || LEAN == LEAN_IMITATION || LEAN == LEAN_ROBOT_ROW_WALLS;   // the robot is the last row
+    constexpr bool IMIT = LEAN == LEAN_IMITATION;          // ... and follows its own human motion model
+    constexpr bool NO_WALLS = LEAN == LEAN_PLAIN || LEAN == LEAN_ROBOT_ROW || LEAN == LEAN_IMITATION;     // wall code compiled out
     const int rows = ROWS_CT > 0 ? ROWS_CT : a.rows;
     const int n = LEAN_ROBOT ? rows - 1 : (LEAN ? rows : a.n);
     const int kmode = LEAN_ROBOT ? ((int)M_COMMIT_GOALS | (a.mode & (int)M_ROBOT_FROM_ARRAY)) : (LEAN ? (int)M_COMMIT_GOALS : a.mode);

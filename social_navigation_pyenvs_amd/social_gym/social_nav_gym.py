@@ -567,8 +567,96 @@ class BatchedSocialNavGym:
         if tail_mask is not None and self.FOLD_RESET and _lib.load().cs_gym_step_is_one_launch(dref) == 2:
             a_fold = a_step[:-1] + (C.byref(dl["gen"]), C.byref(dl["staging_desc"]), C.byref(dl["stage_book"]), A)
         keep = (d, cfg, book)              # the structs the byref arguments point into
-        dl[key] = dict(step=a_step, tail=a_tail, fold=a_fold, keep=keep)
+        dl[key] = dict(step=a_step, tail=a_tail, fold=a_fold, keep=keep, results=(dl["obs"],) + dl["results"][parity])
         return dl[key]
+
+    def _open_step(self, dl, auto_reset):
+        """The head of a step: the auto-reset mode (no change while a NEXT_STEP reset is pending), the parity flip, its _step_pieces."""
+        import torch
+
+        mode = "next_step" if auto_reset == "next_step" else ("same_step" if auto_reset else "none")
+        if mode == "next_step":
+            if "ns_masks" not in dl:
+                dl["ns_masks"] = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
+                torch.cuda.synchronize()
+        elif dl.get("mode") == "next_step" and "ns_masks" in dl and any(bool(m.any().item()) for m in dl["ns_masks"]):
+            raise RuntimeError("a NEXT_STEP auto-reset is pending for some world: keep auto_reset=\"next_step\" (or reset()) before changing the mode")
+        dl["mode"] = mode
+        parity = dl["parity"]
+        dl["parity"] ^= 1
+        return self._step_pieces(dl, parity, mode)
+
+    @staticmethod
+    def _stream_handshake(dl, cur, before):
+        """Device-side ordering of a call on the library's stream with the caller's ``cur``: before it with whatever produced the actions,
+        after it with whoever reads the results.  Nothing where the caller already works on the library's stream (``device_stream()``)."""
+        side = dl["stream"]
+        if cur.cuda_stream != side.cuda_stream:
+            side.wait_stream(cur) if before else cur.wait_stream(side)
+
+    def _issue_step(self, dl, c, pargs=None):
+        """One step's library calls: the one-launch fold, or the step + tail; with ``pargs`` the entries that decide the action first."""
+        lib, chk = _lib.load(), _lib.check
+        if c["fold"] is not None:
+            if pargs is None:
+                chk(lib.cs_gym_step_staged(*c["fold"]))
+            else:
+                chk(lib.cs_gym_step_staged_policy(*c["fold"][:-1], *pargs, c["fold"][-1]))
+            self._maybe_refill(dl)
+            return
+        if pargs is None:
+            chk(lib.cs_gym_step(*c["step"]))
+        else:
+            chk(lib.cs_gym_step_policy(*c["step"][:-1], *pargs, c["step"][-1]))
+        if c["tail"] is not None:
+            chk(lib.cs_consume_staged_worlds(*c["tail"]))
+            self._maybe_refill(dl)
+
+    def _no_train_policy(self, dl, policy, who):
+        """The no-train policy behind a policy_factory name or an instance, refused where this batch cannot take it (``who`` asks)."""
+        from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
+
+        if isinstance(policy, str):
+            from ..crowd_nav.policy_no_train.policy_factory import policy_factory
+
+            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
+        else:
+            pol = policy
+        if not isinstance(pol, NoTrainPolicy):
+            raise TypeError(f"{who} takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}")
+        if pol.kinematics != "holonomic" or self.cw.unicycle:
+            raise ValueError(f"{who}: the no-train policies act in ActionXY and need a holonomic robot")
+        if self.cw.d_robot is None:
+            raise ValueError(f"{who} needs the robot rows")
+        return pol
+
+    def _policy_args(self, dl, pol):
+        """The policy's ctypes arguments, bound once per (id, time step, parameters): for the Gym step's policy entries, for cs_policy_no_train."""
+        import ctypes as C
+
+        ts = self.robot_time_step if pol.time_step is None else pol.time_step
+        prm = pol.packed_params()
+        key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
+        bound = dl.setdefault("pnt_args", {})
+        b = bound.get(key)
+        if b is None:
+            P = lambda t: C.c_void_p(t.data_ptr())
+            step = (C.c_int(pol.pnt_id), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p))
+            act = (step[0], C.c_int(self.W), C.c_int(self.n), C.c_void_p(self.cw.d_robot.ptr), P(dl["obs"]), C.c_int(dl["obs"].shape[2]), step[1], step[2],
+                   P(dl["act"]), C.c_void_p(dl["stream"].cuda_stream))
+            b = bound[key] = dict(step=step, act=act, keep=prm)
+        return b
+
+    def _observe_if_stale(self, dl):
+        """No step since the batch was generated: the observation of the resident rows (what a decision in a launch of its own reads)."""
+        import ctypes as C
+
+        if dl.get("obs_fresh"):
+            return
+        d = self.cw.descriptor(respawn=False)
+        _lib.check(_lib.load().cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()),
+                                              C.c_void_p(dl["stream"].cuda_stream)))
+        dl["obs_fresh"] = True
 
     def step_device(self, actions, auto_reset=True):
         """``step`` without leaving the GPU: ``actions`` is a float32 torch CUDA tensor [W, 2] (holonomic vx, vy) -- or
@@ -583,38 +671,16 @@ class BatchedSocialNavGym:
         import torch
 
         dl = self._device_loop_state()
-        mode = "next_step" if auto_reset == "next_step" else ("same_step" if auto_reset else "none")
-        if mode == "next_step":
-            if "ns_masks" not in dl:
-                dl["ns_masks"] = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
-                torch.cuda.synchronize()
-        elif dl.get("mode") == "next_step" and "ns_masks" in dl and any(bool(m.any().item()) for m in dl["ns_masks"]):
-            raise RuntimeError("a NEXT_STEP auto-reset is pending for some world: keep auto_reset=\"next_step\" (or reset()) before changing the mode")
-        dl["mode"] = mode
-        parity = dl["parity"]
-        dl["parity"] ^= 1
-        c = self._step_pieces(dl, parity, mode)
-        lib, chk = _lib.load(), _lib.check
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        same = cur.cuda_stream == side.cuda_stream   # the caller already works on the library's stream (`with torch.cuda.stream(env.device_stream())`)
-        if not same:
-            side.wait_stream(cur)                  # device-side ordering with whatever produced the actions
+        c = self._open_step(dl, auto_reset)
+        cur = torch.cuda.current_stream()
+        self._stream_handshake(dl, cur, True)
         if actions is not dl["act"]:
-            with torch.cuda.stream(side):
+            with torch.cuda.stream(dl["stream"]):
                 dl["act"].copy_(actions.to(device="cuda", dtype=torch.float32), non_blocking=True)
-        if c["fold"] is not None:
-            chk(lib.cs_gym_step_staged(*c["fold"]))
-            self._maybe_refill(dl)
-        else:
-            chk(lib.cs_gym_step(*c["step"]))
-            if c["tail"] is not None:
-                chk(lib.cs_consume_staged_worlds(*c["tail"]))
-                self._maybe_refill(dl)
-        if not same:
-            cur.wait_stream(side)                  # ... and with whoever reads the results
+        self._issue_step(dl, c)
+        self._stream_handshake(dl, cur, False)
         dl["obs_fresh"] = True                     # the step wrote the observation buffer act_device reads
-        reward, terminated, truncated, info = dl["results"][parity]
-        return dl["obs"], reward, terminated, truncated, info
+        return c["results"]
 
     def reset_failed_mask(self):
         """int32 CUDA tensor [W], no synchronisation: 1 where the world's LAST device-side auto-reset could not be generated
@@ -652,8 +718,6 @@ class BatchedSocialNavGym:
         when the policy's ``query_env`` is false) -> cs_lookahead -> cs_value_net_decide, all on ``device_stream()``.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
         values and choices of that decision stay readable through ``last_values_device()``."""
-        import ctypes as C
-
         import torch
 
         dl = self._device_loop_state()
@@ -664,44 +728,12 @@ class BatchedSocialNavGym:
                 return self._act_device_value(dl, policy, explore)
         if explore is not None:
             raise ValueError("act_device: explore= belongs to the value-based policies (CADRL, SARL)")
-        if isinstance(policy, str):
-            from ..crowd_nav.policy_no_train.policy_factory import policy_factory
-
-            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
-        else:
-            pol = policy
-        from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
-
-        if not isinstance(pol, NoTrainPolicy):
-            raise TypeError(f"act_device takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}")
-        if pol.kinematics != "holonomic" or self.cw.unicycle:
-            raise ValueError("act_device: the no-train policies act in ActionXY and need a holonomic robot")
-        if self.cw.d_robot is None:
-            raise ValueError("act_device needs the robot rows")
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        same = cur.cuda_stream == side.cuda_stream
-        if not same:
-            side.wait_stream(cur)
-        lib = _lib.load()
-        if not dl.get("obs_fresh"):                # no step since the batch was generated: take the observation of the resident rows
-            d = self.cw.descriptor(respawn=False)
-            _lib.check(lib.cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()),
-                                          C.c_void_p(side.cuda_stream)))
-            dl["obs_fresh"] = True
-        # the ctypes arguments bound once per (policy, time step, parameters): a decision is one library call
-        ts = self.robot_time_step if pol.time_step is None else pol.time_step
-        prm = pol.packed_params()
-        key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
-        bound = dl.setdefault("pnt_args", {})
-        args = bound.get(key)
-        if args is None:
-            args = (C.c_int(pol.pnt_id), C.c_int(self.W), C.c_int(self.n), C.c_void_p(self.cw.d_robot.ptr), C.c_void_p(dl["obs"].data_ptr()),
-                    C.c_int(dl["obs"].shape[2]), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p),
-                    C.c_void_p(dl["act"].data_ptr()), C.c_void_p(side.cuda_stream), prm)
-            bound[key] = args
-        _lib.check(lib.cs_policy_no_train(*args[:-1]))
-        if not same:
-            cur.wait_stream(side)
+        pol = self._no_train_policy(dl, policy, "act_device")
+        cur = torch.cuda.current_stream()
+        self._stream_handshake(dl, cur, True)
+        self._observe_if_stale(dl)
+        _lib.check(_lib.load().cs_policy_no_train(*self._policy_args(dl, pol)["act"]))     # a decision is one library call
+        self._stream_handshake(dl, cur, False)
         return dl["act"]
 
     def act_step_device(self, policy, auto_reset=True):
@@ -712,8 +744,6 @@ class BatchedSocialNavGym:
         actions in ``action_buffer()``; runs on ``device_stream()``, nothing crosses to the host.  Bit for bit the results of the two
         calls.  The other crowds (ORCA, social momentum, walls, the smallest worlds) run the decision kernel and the step's launches
         inside the same call.  A CADRL / SARL instance decides in milliseconds and gains nothing here: ``act_device``, then ``step_device``."""
-        import ctypes as C
-
         import torch
 
         from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
@@ -722,57 +752,15 @@ class BatchedSocialNavGym:
             raise TypeError(f"act_step_device takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}: "
                             "a value-based policy (CADRL, SARL) decides with act_device, then step_device")
         dl = self._device_loop_state()
-        if isinstance(policy, str):
-            from ..crowd_nav.policy_no_train.policy_factory import policy_factory
-
-            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
-        else:
-            pol = policy
-        if pol.kinematics != "holonomic" or self.cw.unicycle:
-            raise ValueError("act_step_device: the no-train policies act in ActionXY and need a holonomic robot")
-        if self.cw.d_robot is None:
-            raise ValueError("act_step_device needs the robot rows")
-        mode = "next_step" if auto_reset == "next_step" else ("same_step" if auto_reset else "none")
-        if mode == "next_step":
-            if "ns_masks" not in dl:
-                dl["ns_masks"] = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
-                torch.cuda.synchronize()
-        elif dl.get("mode") == "next_step" and "ns_masks" in dl and any(bool(m.any().item()) for m in dl["ns_masks"]):
-            raise RuntimeError("a NEXT_STEP auto-reset is pending for some world: keep auto_reset=\"next_step\" (or reset()) before changing the mode")
-        dl["mode"] = mode
-        parity = dl["parity"]
-        dl["parity"] ^= 1
-        c = self._step_pieces(dl, parity, mode)
-        # the policy's three ctypes arguments bound once per (policy, time step, parameters), as act_device binds its own
-        ts = self.robot_time_step if pol.time_step is None else pol.time_step
-        prm = pol.packed_params()
-        key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
-        bound = dl.setdefault("pnt_step_args", {})
-        pargs = bound.get(key)
-        if pargs is None:
-            pargs = (C.c_int(pol.pnt_id), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p), prm)
-            bound[key] = pargs
-        lib, chk = _lib.load(), _lib.check
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        same = cur.cuda_stream == side.cuda_stream
-        if not same:
-            side.wait_stream(cur)
-        if not dl.get("obs_fresh"):                # no step since the batch was generated: the observation of the resident rows (what
-            d = self.cw.descriptor(respawn=False)  # the worlds that decide in a launch of their own read; act_device does the same)
-            chk(lib.cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()), C.c_void_p(side.cuda_stream)))
-            dl["obs_fresh"] = True
-        if c["fold"] is not None:
-            chk(lib.cs_gym_step_staged_policy(*c["fold"][:-1], *pargs[:3], c["fold"][-1]))
-            self._maybe_refill(dl)
-        else:
-            chk(lib.cs_gym_step_policy(*c["step"][:-1], *pargs[:3], c["step"][-1]))
-            if c["tail"] is not None:
-                chk(lib.cs_consume_staged_worlds(*c["tail"]))
-                self._maybe_refill(dl)
-        if not same:
-            cur.wait_stream(side)
-        reward, terminated, truncated, info = dl["results"][parity]
-        return dl["obs"], reward, terminated, truncated, info
+        pol = self._no_train_policy(dl, policy, "act_step_device")
+        c = self._open_step(dl, auto_reset)
+        pargs = self._policy_args(dl, pol)["step"]
+        cur = torch.cuda.current_stream()
+        self._stream_handshake(dl, cur, True)
+        self._observe_if_stale(dl)
+        self._issue_step(dl, c, pargs)
+        self._stream_handshake(dl, cur, False)
+        return c["results"]
 
     def act_step_variant(self) -> str:
         """Which kernels ``act_step_device`` runs for this batch (cs_gym_step_policy_variant): the step build that decides in its head, or
@@ -812,9 +800,7 @@ class BatchedSocialNavGym:
             dl["vn_values"] = torch.zeros((W, A), dtype=torch.float32, device="cuda")
             dl["vn_choice"] = torch.zeros(W, dtype=torch.int32, device="cuda")
         side, cur = dl["stream"], torch.cuda.current_stream()
-        same = cur.cuda_stream == side.cuda_stream
-        if not same:
-            side.wait_stream(cur)
+        self._stream_handshake(dl, cur, True)
         with torch.cuda.stream(side):
             nxt = None
             if not pol.query_env:                    # cadrl.py:92-105: the humans keep their velocity over the robot's step
@@ -827,8 +813,7 @@ class BatchedSocialNavGym:
                              dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream)
             for t in (rot, rew, rob) + (() if explore is None else (explore,)) + (() if nxt is None else (nxt,)):
                 t.record_stream(side)
-        if not same:
-            cur.wait_stream(side)
+        self._stream_handshake(dl, cur, False)
         return dl["act"]
 
     def last_values_device(self):

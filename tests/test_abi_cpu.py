@@ -188,6 +188,20 @@ def test_new_entry_points_reject_bad_arguments_before_touching_a_device():
 # hands over a cs_gym_book without buffers.  A row whose descriptor carries a dummy pointer into an entry that launches kernels is only run
 # where no GPU is visible: nothing may ever hand such a pointer to a launch on a real device.
 _ORCA = dict(type=9, orca_neighbor_dist=10.0, orca_time_horizon=5.0, orca_time_horizon_obst=5.0, orca_max_neighbors=10)
+# worlds the Gym step takes in ONE launch on a 64-lane build (25 humans, Guo's SFM, CS_ALL_PARAMS_EQUAL, no walls), with one fault per row:
+# "call" replaces one argument of the call (None, or a dummy address), "sb" / "book" = dict(...) one field of the cs_stage_book / cs_gym_book,
+# "walls" adds one polygon (with a dummy d_obstacles)
+_FUSED = dict(dev=1, robot=1, n=25, type=1, flags=1)
+_STAGED_FAULTS = [
+    (dict(_FUSED, sb=dict(d_pending=0)), "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed"),
+    (dict(_FUSED, sb=dict(d_failed=0)), "cs_gym_step_staged needs cs_stage_book.d_pending and d_failed"),
+    (dict(_FUSED, book=dict(auto_reset=0)), "cs_gym_step_staged is the auto-reset step (cs_gym_book.auto_reset or the NEXT_STEP masks)"),
+    (dict(_FUSED, book=dict(d_seeds=0x2000)), "cs_gym_book.d_seeds and cs_stage_book.d_seeds must be one buffer"),
+    (dict(_FUSED, call=dict(gen=None)), "null argument"),
+    (dict(_FUSED, call=dict(staging=None)), "null argument"),
+    (dict(_FUSED, call=dict(sb=None)), "null argument"),
+    (dict(_FUSED, walls=1), "cs_gym_step_staged: these worlds take the two launches (cs_gym_step, then cs_consume_staged_worlds)"),
+]
 _BAD_CS_WORLDS = [
     ("cs_step", None, -1, "null cs_worlds"),
     ("cs_step", dict(W=0), -1, "W, n, G must be positive"),
@@ -303,13 +317,22 @@ _BAD_CS_WORLDS = [
     ("cs_step_variant", dict(_ORCA, dev=1, orca_math=3), 0, "math=fma"),
     ("cs_step_variant", dict(_ORCA, dev=1, orca_math=7), -1, "cs_worlds.orca_math"),
     ("cs_step_variant", dict(_ORCA, dev=1, orca_max_neighbors=17), -1, "orca_max_neighbors must be in 0..16"),
+    # one fault per call on worlds that take the one-launch path (appended: the ids of the rows above carry their index)
+    *[("cs_gym_step_staged", f, -1, m) for f, m in _STAGED_FAULTS],
+    *[("cs_gym_step_staged_policy", f, -1, m) for f, m in _STAGED_FAULTS],
+    ("cs_gym_step", dict(_FUSED, call=dict(action=None)), -1, "null argument"),
+    ("cs_gym_step", dict(_FUSED, call=dict(out=None)), -1, "null argument"),
+    ("cs_gym_step", dict(_FUSED, call=dict(cfg=None)), -1, "null argument"),
+    ("cs_step_observe", dict(dev=1, n=25, type=1, flags=1, call=dict(action=0x1000)), -1, "robot action given but cs_worlds.d_robot is null"),
+    ("cs_step_trace", dict(dev=1, n=25, type=1, flags=1, call=dict(action=0x1000)), -1, "robot action given but cs_worlds.d_robot is null"),
 ]
 _QUERY_ENTRIES = {"cs_step_variant", "cs_launch_geometry", "cs_gym_step_is_one_launch"}
 
 
-def _bad_cs_worlds_call(entry, w, book):
+def _bad_cs_worlds_call(entry, w, book, sb_fields=None, over=None):
     """Calls `entry` with descriptor `w` (a ctypes pointer or None) and otherwise well-formed arguments: dummy device pointers for every
-    buffer an entry checks for NULL before it reads the descriptor, host arrays for host arguments."""
+    buffer an entry checks for NULL before it reads the descriptor, host arrays for host arguments.  `sb_fields` changes fields of the
+    cs_stage_book, `over` replaces named arguments of the Gym-step / step calls (None, or a dummy address)."""
     import ctypes as C
 
     from social_navigation_pyenvs_amd import _lib
@@ -324,19 +347,26 @@ def _bad_cs_worlds_call(entry, w, book):
                        traffic_length=14.0, traffic_height=3.0, robot_radius=0.3, human_mass=75.0, robot_mass=80.0, robot_desired_speed=1.0)
     sb = _lib.cs_stage_book(d_seeds=0x1000, d_base_seed=0x1000, d_epoch=0x1000, d_staged_seed=0x1000, d_staged_status=0x1000, d_failed=0x1000,
                             seed_stride=0, depth=1, d_pending=0x1000)
+    for k, v in (sb_fields or {}).items():
+        setattr(sb, k, v)
+    over = over or {}
+    ptr = lambda name, default: default if name not in over else (None if over[name] is None else C.c_void_p(over[name]))
+    ref = lambda name, obj: None if name in over else (obj if name == "staging" else C.byref(obj))
     gb = C.byref(book)
     buf = C.create_string_buffer(256)
+    gym = lambda: (w, f(0.01), i(1), ptr("action", dev), f(0.25), dev, ptr("cfg", cfg), ptr("out", dev), gb, i(0), dev)
+    staged = lambda: (ref("gen", gen), ref("staging", w), ref("sb", sb))
     calls = {
         "cs_step": lambda: lib.cs_step(w, f(0.01), i(1), null, null),
         "cs_peek": lambda: lib.cs_peek(w, f(0.01), dev, null),
         "cs_update_humans_parallel": lambda: lib.cs_update_humans_parallel(w, f(0.01), dev, null),
-        "cs_step_trace": lambda: lib.cs_step_trace(w, f(0.01), i(1), null, dev, null),
-        "cs_step_observe": lambda: lib.cs_step_observe(w, f(0.01), i(1), null, i(0), dev, null),
+        "cs_step_trace": lambda: lib.cs_step_trace(w, f(0.01), i(1), ptr("action", null), dev, null),
+        "cs_step_observe": lambda: lib.cs_step_observe(w, f(0.01), i(1), ptr("action", null), i(0), dev, null),
         "cs_collision_reward": lambda: lib.cs_collision_reward(w, dev, f(0.25), dev, cfg, dev, null),
         "cs_collision_reward_gym": lambda: lib.cs_collision_reward_gym(w, dev, f(0.25), dev, cfg, dev, gb, null),
-        "cs_gym_step": lambda: lib.cs_gym_step(w, f(0.01), i(1), dev, f(0.25), dev, cfg, dev, gb, i(0), dev, null),
-        "cs_gym_step_staged": lambda: lib.cs_gym_step_staged(w, f(0.01), i(1), dev, f(0.25), dev, cfg, dev, gb, i(0), dev, C.byref(gen), w,
-                                                             C.byref(sb), null),
+        "cs_gym_step": lambda: lib.cs_gym_step(*gym(), null),
+        "cs_gym_step_staged": lambda: lib.cs_gym_step_staged(*gym(), *staged(), null),
+        "cs_gym_step_staged_policy": lambda: lib.cs_gym_step_staged_policy(*gym(), *staged(), i(0), f(0.25), None, null),   # CS_PNT_BP: no parameters
         "cs_actual_collision_reward": lambda: lib.cs_actual_collision_reward(w, f(0.25), dev, cfg, dev, null),
         "cs_robot_model_step": lambda: lib.cs_robot_model_step(w, i(0), rp, f(0.0), dev, dev, f(0.01), null),
         "cs_robot_model_velocities": lambda: lib.cs_robot_model_velocities(w, i(0), rp, f(0.0), dev, dev, f(0.01), null),
@@ -368,21 +398,29 @@ def test_cs_worlds_entry_points_check_their_arguments(entry, fields, rc, fragmen
 
     from social_navigation_pyenvs_amd import _lib
 
+    sb_fields = over = None
     w, book = None, _lib.cs_gym_book(**{k: 0x1000 for k in ("d_counter", "d_seeds", "d_mask", "d_clock", "d_reward", "d_terminated",
                                                             "d_truncated", "d_info")}, clock_len=4, auto_reset=1)
     if fields is not None:
         fields = dict(fields)
         dummy = fields.pop("dev", 0)
         robot = fields.pop("robot", 0)
-        if fields.pop("book", None) == "null":
+        book_fields = fields.pop("book", None)
+        if book_fields == "null":
             book = _lib.cs_gym_book(clock_len=4, auto_reset=1)
+        else:
+            for k, v in (book_fields or {}).items():
+                setattr(book, k, v)
+        sb_fields, over, walls = fields.pop("sb", None), fields.pop("call", None), fields.pop("walls", 0)
         desc = _lib.cs_worlds(**{"W": 4, "n": 5, "G": 2, "type": 0, "layout": _lib.CS_LAYOUT_AOS, **fields})
         if dummy:
             desc.d_state = desc.d_goals = desc.d_params = desc.d_safety = 0x1000
+        if walls:
+            desc.O, desc.Smax, desc.d_obstacles = 1, 4, 0x1000
         if robot:
             desc.d_robot = 0x1000
         if (dummy or robot) and entry not in _QUERY_ENTRIES and _lib.device_count() > 0:
             pytest.skip("a GPU is visible: a dummy device pointer is never handed to an entry point that launches kernels there")
         w = C.byref(desc)
-    got_rc, msg = _bad_cs_worlds_call(entry, w, book)
+    got_rc, msg = _bad_cs_worlds_call(entry, w, book, sb_fields, over)
     assert (got_rc, fragment in msg) == (rc, True), msg
