@@ -143,8 +143,9 @@ VnLds lds_map(const VnPlan& p, int M, int n)
 }
 
 // One layer of a tile: dst[rows][ncb * 32] = act(src[rows][K] x Wt + b) for `rbs` row blocks of 32.  The A operand of row r comes from
-// src (k-groups below kg_split) and then from src2[grp[r]] (the per-group second source: SARL's mean of mlp1); columns beyond N come out
-// as act(0) = 0 (zero weights and bias in the blob), so the next layer may read its K rounded up to 8.
+// src (k-groups below kg_split) and then from src2[grp[r]] (the per-group second source: SARL's mean of mlp1); columns beyond N are
+// stored as 0 whatever the inputs (their zero weights and bias give 0 only for finite inputs: 0 * inf is a NaN, which the next layer's
+// zero weights would hand on where torch returns +-inf), so the next layer may read its K rounded up to 8.
 __device__ __forceinline__ void layer_fwd(const VnLayer& L, const float* __restrict__ wb, const float* src, int lds_, const float* src2, int lds2,
                                           const int* grp, int rbs, float* dst, int ldd, int rot)
 {
@@ -189,11 +190,12 @@ __device__ __forceinline__ void layer_fwd(const VnLayer& L, const float* __restr
         }
         // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
         float* d = dst + (rb * 32 + 4 * h) * ldd + cb * 32 + li;
+        const bool pad = cb * 32 + li >= L.N;          // (the zero weights give 0 * inf = NaN there when an input is infinite)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float v = acc[r];
             if (L.relu) v = v < 0.0f ? 0.0f : v;      // (a NaN stays a NaN, as torch's ReLU leaves it)
-            d[((r & 3) + 8 * (r >> 2)) * ldd] = v;
+            d[((r & 3) + 8 * (r >> 2)) * ldd] = pad ? 0.0f : v;
         }
     }
 }

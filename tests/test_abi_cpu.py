@@ -325,6 +325,10 @@ _BAD_CS_WORLDS = [
     ("cs_gym_step", dict(_FUSED, call=dict(cfg=None)), -1, "null argument"),
     ("cs_step_observe", dict(dev=1, n=25, type=1, flags=1, call=dict(action=0x1000)), -1, "robot action given but cs_worlds.d_robot is null"),
     ("cs_step_trace", dict(dev=1, n=25, type=1, flags=1, call=dict(action=0x1000)), -1, "robot action given but cs_worlds.d_robot is null"),
+    # cs_lookahead takes no cs_worlds (the descriptor of the row is not handed over): its two argument checks behind the null pointers, both
+    # before the launch -- 1920 actions fill the 60 KiB of LDS its frame table may take
+    ("cs_lookahead", dict(call=dict(A=1921)), -1, "action set too large"),
+    ("cs_lookahead", dict(call=dict(robot_stride=7)), -1, "robot rows need at least 8 columns"),
 ]
 _QUERY_ENTRIES = {"cs_step_variant", "cs_launch_geometry", "cs_gym_step_is_one_launch"}
 
@@ -385,6 +389,7 @@ def _bad_cs_worlds_call(entry, w, book, sb_fields=None, over=None):
         "cs_reserve_scratch": lambda: lib.cs_reserve_scratch(w, i(1), null),
         "cs_launch_geometry": lambda: lib.cs_launch_geometry(w, null, null, null),
         "cs_step_variant": lambda: lib.cs_step_variant(w, i(0), buf, C.c_size_t(len(buf))),
+        "cs_lookahead": lambda: lib.cs_lookahead(i(3), i(5), i(over.get("A", 81)), i(0), dev, dev, dev, dev, i(over.get("robot_stride", 9)), f(0.25), dev, dev, null),
     }
     rc = calls[entry]()
     return rc, (buf.value if entry == "cs_step_variant" and rc == 0 else lib.cs_last_error()).decode()

@@ -236,7 +236,7 @@ WIDE = dict(sarl__mlp1_dims="256, 256", sarl__mlp2_dims="256, 256", sarl__attent
                                               ("cadrl", 33, {}), ("sarl", 7, {}), ("sarl", 1, WIDE), ("sarl", 2, WIDE), ("sarl", 40, WIDE),
                                               ("cadrl", 3, dict(cadrl__mlp_dims="256, 256, 256, 1"))])
 def test_any_number_of_humans_on_synthetic_rows(name, n, overrides):
-    """The kernel alone on random look-ahead rows: n = 1, n beyond one 64-row tile (chunks of a group), group sizes that leave a tile partly
+    """The kernel alone on random look-ahead rows: n = 1, n beyond one 32-row tile (chunks of a group), group sizes that leave a tile partly
     empty, and the widest networks the entry point takes (every width 256: the largest LDS maps, at 1 and 2 humans).  Reference: the torch
     float32 forward, SARL with the calm attention layer so that every world is compared.  And a world alone (W = 1) equals the same world inside
     the batch, bit for bit.  (1 and 70 humans run here through value_net.decide on synthetic rows, not through act_device: the device
