@@ -14,6 +14,12 @@
 // every lane's neighbour list / ORCA lines / LP3 projection lines in per-lane LDS columns (the 2-D
 // linear programme is divergent by nature; lanes walk their own constraints).  n_substeps are fused in
 // one launch.  IEEE divide / sqrt and no FMA contraction, to follow the CPU restatement op for op.
+//
+// What is stated once and where: the register-resident solve (orca_solve_fast10: crowd, robot and grid kernels) and the generic
+// LDS-column solve (orca_solve_generic + insert_neighbor + agent_params_of: the same three homes) take a walk / fetch functor from the
+// kernel; pref_velocity is update_goals_orca's preferred velocity in all four arithmetics; robot_load / robot_store serve both robot
+// kernels; the goal list's scan / rotation / peek head live in goals.h (also rk45.hip, social_momentum.hip); every kernel's dynamic LDS
+// is laid out in orca_lds.h, which the host sizes the launches by (tests/test_orca_lds_cpu.py).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,6 +28,8 @@
 #include <cstring>
 
 #include "common.h"
+#include "goals.h"
+#include "orca_lds.h"
 #include "orca_sortnet.h"
 #include "robotstep.h"
 #include "respawnx.h"
@@ -147,6 +155,29 @@ template <int FM> __device__ __forceinline__ float odot(float ax, float ay, floa
 template <int FM> __device__ __forceinline__ float omad(float t, float d, float p)
 {
     if constexpr (FM >= 2) return fmaf(t, d, p); else return p + t * d;
+}
+
+// FM_PLAIN: the compiler's own sqrtf and `/` (correctly rounded, with their range handling) -- what the grid kernel and the robot's model
+// use for an agent's preferred velocity; only olen / pref_velocity take it
+constexpr int FM_PLAIN = -1;
+// |(x, y)|
+template <int FM> __device__ __forceinline__ float olen(float x, float y)
+{
+    if constexpr (FM == FM_PLAIN) return sqrtf(x * x + y * y); else return osqrt<FM>(x * x + y * y);
+}
+// update_goals_orca's preferred velocity (motion_model_manager.py:125-141): the vector to the goal, of unit length beyond maxSpeed
+template <int FM> __device__ __forceinline__ void pref_velocity(float ddx, float ddy, float vmax, float& pvx, float& pvy)
+{
+    const float nrm = olen<FM>(ddx, ddy);
+    if constexpr (FM == FM_PLAIN) {
+        if (nrm > vmax) { pvx = ddx / nrm; pvy = ddy / nrm; } else { pvx = ddx; pvy = ddy; }
+    } else if constexpr (FM != 0) {
+        const float inrm = __builtin_amdgcn_rcpf(nrm);
+        const bool far = nrm > vmax;
+        pvx = far ? ddx * inrm : ddx; pvy = far ? ddy * inrm : ddy;
+    } else {
+        if (nrm > vmax) { pvx = ieee_div(ddx, nrm); pvy = ieee_div(ddy, nrm); } else { pvx = ddx; pvy = ddy; }
+    }
 }
 
 // per-lane column views into LDS: element i of lane tid lives at base[i * T + tid]
@@ -922,6 +953,82 @@ __device__ __forceinline__ void orca_velocity_fast10(bool active, bool lp3_stati
                       pvx, pvy, time_horizon, dt, L, R, nvx, nvy, g_ost, g_ost_last);
 }
 
+// ---- the generic solve: any maxNeighbors <= 16, static obstacles, per-agent parameters; everything in per-lane LDS columns ----------
+// an agent's own RVO2 parameters: the launch's scalars, or its row of agent_params where the caller gave some (constant over the launch)
+struct AgentParams { float nbd, thz, tho; int K; };
+__device__ __forceinline__ AgentParams agent_params_of(const float* agent_params, long agent, float nbd, float thz, float tho, int K)
+{
+    AgentParams p{nbd, thz, tho, K};
+    if (agent_params != nullptr) {
+        const float* ap = agent_params + agent * 4;
+        p.nbd = ap[0]; p.thz = ap[2]; p.tho = ap[3];
+        p.K = (int)ap[1] < K ? (int)ap[1] : K;
+    }
+    return p;
+}
+// the per-lane columns of the generic solve, T lanes wide: ORCA lines, LP3 projection lines, neighbours (distSq, row), obstacle edges
+struct SolveCols { Lines L, P; float* nd; int* ni; float* od; int* oi; int T, tid; };
+// RVO2 insertAgentNeighbor into the K sorted slots.  LEX = false: RVO2's own form for a walk in index order -- strict <, ties keep the
+// order, rangeSq shrinks to the farthest kept neighbour once the list is full.  LEX = true: the lexicographic (distSq, row) comparison,
+// which yields the same list from ANY visiting order (the grid's); rangeSq stays.
+template <bool LEX>
+__device__ __forceinline__ void insert_neighbor(const SolveCols& C, int K, int& cnt, float& rangeSq, float dsq, int b)
+{
+    float* nd = C.nd + C.tid;
+    int* ni = C.ni + C.tid;
+    const int T = C.T;
+    auto before = [&](int s) {
+        const float d = nd[s * T];
+        if constexpr (LEX) return dsq < d || (dsq == d && b < ni[s * T]); else return dsq < d;
+    };
+    int s;
+    if constexpr (LEX) {
+        if (cnt < K) s = cnt++;
+        else if (before(K - 1)) s = K - 1;
+        else return;
+    } else {
+        if (cnt < K) ++cnt;
+        s = cnt - 1;
+    }
+    while (s != 0 && before(s - 1)) {
+        nd[s * T] = nd[(s - 1) * T];
+        ni[s * T] = ni[(s - 1) * T];
+        --s;
+    }
+    nd[s * T] = dsq;
+    ni[s * T] = b;
+    if constexpr (!LEX) { if (cnt == K) rangeSq = nd[(cnt - 1) * T]; }
+}
+// Agent::computeNeighbors + computeNewVelocity of one agent.  walk(rangeSq, visit): calls visit(distSq, b) for every other agent b with
+// distSq < rangeSq (read at every candidate: it shrinks under LEX = false); fetch(b, q, rad): (x, y, vx, vy) and radius + margin of b.
+template <bool LEX, class Walk, class Fetch>
+__device__ __forceinline__ void orca_solve_generic(const AgentParams& ap, const float* verts, int nv, int KO, Walk&& walk, Fetch&& fetch, float px, float py,
+                                                   float vx, float vy, float my_r, float vmax, float pvx, float pvy, float dt, const SolveCols& C,
+                                                   float& nvx, float& nvy)
+{
+    int cnt = 0;
+    float rangeSq = ap.nbd * ap.nbd;
+    if (ap.K > 0) walk(rangeSq, [&](float dsq, int b) { insert_neighbor<LEX>(C, ap.K, cnt, rangeSq, dsq, b); });
+    // obstacle half-planes first (static-obstacle worlds), then one per neighbour
+    int nobst = 0;
+    if (nv > 0) {
+        const float rng = ap.tho * vmax + my_r;   // rangeSq = sqr(timeHorizonObst * maxSpeed + radius)
+        const int no = obstacle_neighbors(verts, nv, KO, px, py, rng * rng, C.od, C.oi, C.T, C.tid);
+        nobst = obstacle_lines(verts, C.oi, no, C.T, C.tid, px, py, vx, vy, my_r, 1.0f / ap.tho, C.L);
+    }
+    const float invT = 1.0f / ap.thz;
+    const float invDt = 1.0f / dt;
+    for (int k = 0; k < cnt; ++k) {
+        float4 q;
+        float rad;
+        fetch(C.ni[k * C.T + C.tid], q, rad);
+        C.L.set(nobst + k, orca_line(px, py, vx, vy, q, my_r + rad, invT, invDt));
+    }
+    const int total = nobst + cnt;
+    const int failed = lp2(C.L, total, vmax, pvx, pvy, false, nvx, nvy);
+    if (failed < total) lp3(C.L, C.P, total, nobst, failed, vmax, nvx, nvy);
+}
+
 // MAXT = 64: floor(64 / rows) worlds per one-wavefront block; MAXT = 256 / 512: one world of up to MAXT rows per block
 // FM: the arithmetic of the register-resident build (0 exact / 1 fast / 2 fast + fma, see odiv above); the generic build is always exact
 // at most two wavefronts per SIMD: the register-resident build needs ~220 VGPRs whatever the scheduler is told, and knowing the
@@ -933,6 +1040,8 @@ __global__ __launch_bounds__(MAXT) ORCA_WPE_ATTR void k_orca_step(const OArgs a)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int T = blockDim.x;
     const int K = a.K;
+    // (the regions in the order of OrcaStepLds, orca_lds.h, which the host sizes the launch by.  Taking the pointers from that layout's
+    //  offsets as the other three kernels do cost the register-resident builds SGPR spill reloads inside the substep loop: HISTORY.md)
     const int KL = FAST10 ? 0 : a.K + a.KO;                          // lines per agent: obstacle lines first, then agents
     const int KLL = FAST10 ? 10 : KL;                                // FAST10 keeps a copy of its ten lines for LP3's run-time line index
     // per-lane columns are TL = wpb * rows lanes wide (the lanes that hold an agent: 50 of 64 for 25-agent worlds); the
@@ -996,7 +1105,8 @@ __global__ __launch_bounds__(MAXT) ORCA_WPE_ATTR void k_orca_step(const OArgs a)
     if (valid) { lds_pv[tid] = make_float4(px, py, vx, vy); lds_r[tid] = r + margin; lds_rp[tid] = r; }
     __syncthreads();
 
-    const Lines L{lds_L, TL, tid}, P{lds_P, TL, tid};
+    const Lines L{lds_L, TL, tid};
+    const SolveCols C{L, Lines{lds_P, TL, tid}, lds_nd, lds_ni, lds_od, lds_oi, TL, tid};
     const RowLds RL{lds_rowP, lds_rowA, lds_q, lds_sel};
     unsigned long long ost_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long* g_ost = nullptr;
@@ -1024,77 +1134,30 @@ __global__ __launch_bounds__(MAXT) ORCA_WPE_ATTR void k_orca_step(const OArgs a)
             const float4* pv = lds_pv + cur * T + base;
             const float* rr = lds_r + base;
             if constexpr (!FAST10) {
-                // this agent's own RVO2 parameters, where the caller gave some (constant over the launch)
-                float nbd = a.neighbor_dist, thz = a.time_horizon, tho = a.time_horizon_obst;
-                int Kme = K;
-                if (a.agent_params != nullptr) {
-                    const float* ap = a.agent_params + ((long)w * rows + row) * 4;
-                    nbd = ap[0]; thz = ap[2]; tho = ap[3];
-                    Kme = (int)ap[1] < K ? (int)ap[1] : K;
-                }
-                // ---- Agent::computeNeighbors / insertAgentNeighbor (index order; strict <, ties keep order)
-                int cnt = 0;
-                float rangeSq = nbd * nbd;
-                if (Kme > 0) {
+                const AgentParams ap = agent_params_of(a.agent_params, (long)w * rows + row, a.neighbor_dist, a.time_horizon, a.time_horizon_obst, K);
+                // the world's rows in index order (RVO2's own insertion)
+                auto walk = [&](const float& rangeSq, auto&& visit) {
                     for (int b = 0; b < rows; ++b) {
                         if (b == row) continue;
                         const float4 q = pv[b];
                         const float ddx = px - q.x, ddy = py - q.y;
                         const float dsq = ddx * ddx + ddy * ddy;
-                        if (dsq < rangeSq) {
-                            if (cnt < Kme) ++cnt;
-                            int i = cnt - 1;
-                            while (i != 0 && dsq < lds_nd[(i - 1) * TL + tid]) {
-                                lds_nd[i * TL + tid] = lds_nd[(i - 1) * TL + tid];
-                                lds_ni[i * TL + tid] = lds_ni[(i - 1) * TL + tid];
-                                --i;
-                            }
-                            lds_nd[i * TL + tid] = dsq;
-                            lds_ni[i * TL + tid] = b;
-                            if (cnt == Kme) rangeSq = lds_nd[(cnt - 1) * TL + tid];
-                        }
+                        if (dsq < rangeSq) visit(dsq, b);
                     }
-                }
-                // ---- Agent::computeNewVelocity: obstacle half-planes first (static-obstacle worlds), then one per neighbour
-                int nobst = 0;
-                if (a.nv > 0) {
-                    const float rng = tho * vmax + (r + margin);   // rangeSq = sqr(timeHorizonObst * maxSpeed + radius)
-                    const int no = obstacle_neighbors(a.verts, a.nv, a.KO, px, py, rng * rng, lds_od, lds_oi, TL, tid);
-                    nobst = obstacle_lines(a.verts, lds_oi, no, TL, tid, px, py, vx, vy, r + margin, 1.0f / tho, L);
-                }
-                const float invT = 1.0f / thz;
-                const float invDt = 1.0f / dt;
-                for (int k = 0; k < cnt; ++k) {
-                    const int b = lds_ni[k * TL + tid];
-                    L.set(nobst + k, orca_line(px, py, vx, vy, pv[b], (r + margin) + rr[b], invT, invDt));
-                }
-                const int total = nobst + cnt;
-                const int failed = lp2(L, total, vmax, pvx, pvy, false, nvx, nvy);
-                if (failed < total) lp3(L, P, total, nobst, failed, vmax, nvx, nvy);
+                };
+                orca_solve_generic<false>(ap, a.verts, a.nv, a.KO, walk, [&](int b, float4& q, float& rad) { q = pv[b]; rad = rr[b]; }, px, py, vx, vy,
+                                          r + margin, vmax, pvx, pvy, dt, C, nvx, nvy);
             }
             // ---- Agent::update, then the reference's read-back + update_goals_orca (:390-394, :125-133)
             vx = nvx; vy = nvy;
             px += vx * dt; py += vy * dt;
             float ddx = g0x - px, ddy = g0y - py;
             if (osqrt<FM>(ddx * ddx + ddy * ddy) < r) { // update_goals: strict <  (:66-70)
-                int k = a.G;
-                for (int g = 0; g < a.G; ++g) if (isnan(gi[2 * g])) { k = g; break; }
-                if (a.peek_out == nullptr) {
-                    const float r0 = gi[0], r1 = gi[1];
-                    for (int g = 0; g + 1 < k; ++g) { gi[2 * g] = gi[2 * g + 2]; gi[2 * g + 1] = gi[2 * g + 3]; }
-                    if (k > 0) { gi[2 * (k - 1)] = r0; gi[2 * (k - 1) + 1] = r1; }
-                    g0x = gi[0]; g0y = gi[1];
-                } else if (k > 1) { g0x = gi[2]; g0y = gi[3]; }
+                const int k = goal_count(gi, a.G);
+                if (a.peek_out == nullptr) goal_rotate(gi, k, g0x, g0y); else goal_peek_head(gi, k, g0x, g0y);
                 ddx = g0x - px; ddy = g0y - py;
             }
-            const float nrm = osqrt<FM>(ddx * ddx + ddy * ddy);
-            if constexpr (FM != 0) {
-                const float inrm = __builtin_amdgcn_rcpf(nrm);
-                const bool far = nrm > vmax;
-                pvx = far ? ddx * inrm : ddx; pvy = far ? ddy * inrm : ddy;
-            } else {
-                if (nrm > vmax) { pvx = ieee_div(ddx, nrm); pvy = ieee_div(ddy, nrm); } else { pvx = ddx; pvy = ddy; }
-            }
+            pref_velocity<FM>(ddx, ddy, vmax, pvx, pvy);
             lds_pv[nxt * T + tid] = make_float4(px, py, vx, vy);
         } else if (is_robot) {
             // set_state_orca(robot) AFTER doStep (:389): the simulator's robot agent takes the true state (moved by the
@@ -1181,76 +1244,60 @@ struct ORArgs {
                             // stays (the reference puts the robot's simulator agent back on robot.position)
 };
 
-__global__ __launch_bounds__(64) void k_orca_robot_step(const ORArgs a)
+// the robot lane's state: radius with the robot's margin, goal, maxSpeed (rb: the world's row of ORArgs.robot)
+struct RobotLane { float px, py, vx, vy, r, gx, gy, vmax; };
+__device__ __forceinline__ RobotLane robot_load(const ORArgs& a, const float* rb)
 {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int T = 64, tid = threadIdx.x;
-    const int KL = a.K + a.KO;
-    float4* lds_L = reinterpret_cast<float4*>(smem_raw);             // [KL][T]
-    float4* lds_P = lds_L + KL * T;                                  // [KL][T]
-    float* lds_nd = reinterpret_cast<float*>(lds_P + KL * T);        // [K][T]
-    int* lds_ni = reinterpret_cast<int*>(lds_nd + a.K * T);          // [K][T]
-    float* lds_od = reinterpret_cast<float*>(lds_ni + a.K * T);      // [KO][T]
-    int* lds_oi = reinterpret_cast<int*>(lds_od + a.KO * T);         // [KO][T]
-    const int w = blockIdx.x * a.wpb + tid;
-    if (tid >= a.wpb || w >= a.W) return;
-    float* rb = a.robot + (long)w * 13;
-    float px = rb[0], py = rb[1], vx = rb[3], vy = rb[4];
-    const float r = rb[8] + a.robot_margin, gx = rb[10], gy = rb[11], vmax = rb[12];
-    float pvx, pvy;
-    {
-        const float ddx = gx - px, ddy = gy - py;
-        const float nrm = sqrtf(ddx * ddx + ddy * ddy);
-        if (nrm > vmax) { pvx = ddx / nrm; pvy = ddy / nrm; } else { pvx = ddx; pvy = ddy; }
-    }
-    const Lines L{lds_L, T, tid}, P{lds_P, T, tid};
-    const float* Sw = a.S + (long)w * a.rows * a.as;
-    int cnt = 0;
-    float rangeSq = a.neighbor_dist * a.neighbor_dist;
-    if (a.K > 0) {
-        for (int b = 0; b < a.n; ++b) {
-            const float* s = Sw + (long)b * a.as;
-            const float ddx = px - s[0], ddy = py - s[a.fs];
-            const float dsq = ddx * ddx + ddy * ddy;
-            if (dsq < rangeSq) {
-                if (cnt < a.K) ++cnt;
-                int i = cnt - 1;
-                while (i != 0 && dsq < lds_nd[(i - 1) * T + tid]) {
-                    lds_nd[i * T + tid] = lds_nd[(i - 1) * T + tid];
-                    lds_ni[i * T + tid] = lds_ni[(i - 1) * T + tid];
-                    --i;
-                }
-                lds_nd[i * T + tid] = dsq;
-                lds_ni[i * T + tid] = b;
-                if (cnt == a.K) rangeSq = lds_nd[(cnt - 1) * T + tid];
-            }
-        }
-    }
-    int nobst = 0;
-    if (a.nv > 0) {
-        const float rng = a.time_horizon_obst * vmax + r;
-        const int no = obstacle_neighbors(a.verts, a.nv, a.KO, px, py, rng * rng, lds_od, lds_oi, T, tid);
-        nobst = obstacle_lines(a.verts, lds_oi, no, T, tid, px, py, vx, vy, r, 1.0f / a.time_horizon_obst, L);
-    }
-    const float invT = 1.0f / a.time_horizon;
-    const float invDt = 1.0f / a.dt;
-    for (int k = 0; k < cnt; ++k) {
-        const int b = lds_ni[k * T + tid];
-        const float* s = Sw + (long)b * a.as;
-        const float4 q = make_float4(s[0], s[a.fs], s[3 * a.fs], s[4 * a.fs]);
-        L.set(nobst + k, orca_line(px, py, vx, vy, q, r + (s[8 * a.fs] + a.hmargin[(long)w * a.rows + b]), invT, invDt));
-    }
-    const int total = nobst + cnt;
-    float nvx, nvy;
-    const int failed = lp2(L, total, vmax, pvx, pvy, false, nvx, nvy);
-    if (failed < total) lp3(L, P, total, nobst, failed, vmax, nvx, nvy);
-    vx = nvx; vy = nvy;
+    return RobotLane{rb[0], rb[1], rb[3], rb[4], rb[8] + a.robot_margin, rb[10], rb[11], rb[12]};
+}
+// Agent::update with the new velocity (the position stays under just_velocities), written to rb and, where asked, to the state row
+__device__ __forceinline__ void robot_store(const ORArgs& a, int w, float* rb, float px, float py, float vx, float vy)
+{
     if (!a.just_velocities) { px += vx * a.dt; py += vy * a.dt; }
     rb[0] = px; rb[1] = py; rb[3] = vx; rb[4] = vy;
     if (a.write_row) {
         float* s = a.S + ((long)w * a.rows + a.n) * a.as;
         s[0] = px; s[a.fs] = py; s[3 * a.fs] = vx; s[4 * a.fs] = vy;
     }
+}
+
+__global__ __launch_bounds__(64) void k_orca_robot_step(const ORArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int T = 64, tid = threadIdx.x;
+    const OrcaRobotLds lay = orca_robot_lds(a.K, a.KO);
+    float4* lds_L = reinterpret_cast<float4*>(smem_raw + lay.L.off);
+    float4* lds_P = reinterpret_cast<float4*>(smem_raw + lay.P.off);
+    float* lds_nd = reinterpret_cast<float*>(smem_raw + lay.nd.off);
+    int* lds_ni = reinterpret_cast<int*>(smem_raw + lay.ni.off);
+    float* lds_od = reinterpret_cast<float*>(smem_raw + lay.od.off);
+    int* lds_oi = reinterpret_cast<int*>(smem_raw + lay.oi.off);
+    const int w = blockIdx.x * a.wpb + tid;
+    if (tid >= a.wpb || w >= a.W) return;
+    float* rb = a.robot + (long)w * 13;
+    const RobotLane me = robot_load(a, rb);
+    const float px = me.px, py = me.py, vx = me.vx, vy = me.vy, r = me.r, vmax = me.vmax;
+    float pvx, pvy;
+    pref_velocity<FM_PLAIN>(me.gx - px, me.gy - py, vmax, pvx, pvy);
+    const SolveCols C{Lines{lds_L, T, tid}, Lines{lds_P, T, tid}, lds_nd, lds_ni, lds_od, lds_oi, T, tid};
+    const float* Sw = a.S + (long)w * a.rows * a.as;
+    auto walk = [&](const float& rangeSq, auto&& visit) {   // the humans in index order
+        for (int b = 0; b < a.n; ++b) {
+            const float* s = Sw + (long)b * a.as;
+            const float ddx = px - s[0], ddy = py - s[a.fs];
+            const float dsq = ddx * ddx + ddy * ddy;
+            if (dsq < rangeSq) visit(dsq, b);
+        }
+    };
+    auto fetch = [&](int b, float4& q, float& rad) {
+        const float* s = Sw + (long)b * a.as;
+        q = make_float4(s[0], s[a.fs], s[3 * a.fs], s[4 * a.fs]);
+        rad = s[8 * a.fs] + a.hmargin[(long)w * a.rows + b];
+    };
+    float nvx, nvy;
+    orca_solve_generic<false>(AgentParams{a.neighbor_dist, a.time_horizon, a.time_horizon_obst, a.K}, a.verts, a.nv, a.KO, walk, fetch, px, py, vx, vy, r,
+                              vmax, pvx, pvy, a.dt, C, nvx, nvy);
+    robot_store(a, w, rb, px, py, nvx, nvy);
 }
 
 
@@ -1260,13 +1307,14 @@ __global__ __launch_bounds__(64) void k_orca_robot_step_fast(const ORArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int tid = threadIdx.x, ent = a.n + 1;                       // the humans and the robot itself as the last row
-    float4* lds_pv = reinterpret_cast<float4*>(smem_raw);            // [wpb][ent] x, y, vx, vy
-    float* lds_rr = reinterpret_cast<float*>(lds_pv + a.wpb * ent);  // [wpb][ent] radius + margin
-    float4* lds_ln = reinterpret_cast<float4*>(lds_rr + ((a.wpb * ent + 3) & ~3));   // [10][64] the lanes' ORCA lines for LP3
-    float4* lds_pr = lds_ln + 10 * 64;                               // [9][8] projected lines of the rows in flight (lp3_rows)
-    float2* lds_pa = reinterpret_cast<float2*>(lds_pr + 72);         // [9][8] their chords
-    float4* lds_q = reinterpret_cast<float4*>(lds_pa + 72);          // [64]
-    int* lds_sel = reinterpret_cast<int*>(lds_q + 64);               // [64]
+    const OrcaRobotFastLds lay = orca_robot_fast_lds(a.wpb, a.n);
+    float4* lds_pv = reinterpret_cast<float4*>(smem_raw + lay.pv.off);
+    float* lds_rr = reinterpret_cast<float*>(smem_raw + lay.rr.off);
+    float4* lds_ln = reinterpret_cast<float4*>(smem_raw + lay.ln.off);
+    float4* lds_pr = reinterpret_cast<float4*>(smem_raw + lay.pr.off);
+    float2* lds_pa = reinterpret_cast<float2*>(smem_raw + lay.pa.off);
+    float4* lds_q = reinterpret_cast<float4*>(smem_raw + lay.q.off);
+    int* lds_sel = reinterpret_cast<int*>(smem_raw + lay.sel.off);
     const int w0 = blockIdx.x * a.wpb;
     for (int k = tid; k < a.wpb * a.n; k += 64) {
         const int wl = k / a.n, b = k - wl * a.n, w = w0 + wl;
@@ -1278,36 +1326,24 @@ __global__ __launch_bounds__(64) void k_orca_robot_step_fast(const ORArgs a)
     }
     const int w = w0 + tid;
     const bool mine = tid < a.wpb && w < a.W;
-    float px = 0, py = 0, vx = 0, vy = 0, r = 1, gx = 0, gy = 0, vmax = 1;
+    RobotLane me{0, 0, 0, 0, 1, 0, 0, 1};                             // a lane without a world: at rest on its goal
     float* rb = a.robot + (long)(mine ? w : 0) * 13;
     if (mine) {
-        px = rb[0]; py = rb[1]; vx = rb[3]; vy = rb[4];
-        r = rb[8] + a.robot_margin; gx = rb[10]; gy = rb[11]; vmax = rb[12];
-        lds_pv[tid * ent + a.n] = make_float4(px, py, vx, vy);
-        lds_rr[tid * ent + a.n] = r;
+        me = robot_load(a, rb);
+        lds_pv[tid * ent + a.n] = make_float4(me.px, me.py, me.vx, me.vy);
+        lds_rr[tid * ent + a.n] = me.r;
     }
     __syncthreads();
     float pvx, pvy;
-    {
-        const float ddx = gx - px, ddy = gy - py;
-        const float nrm = sqrtf(ddx * ddx + ddy * ddy);
-        if (nrm > vmax) { pvx = ddx / nrm; pvy = ddy / nrm; } else { pvx = ddx; pvy = ddy; }
-    }
+    pref_velocity<FM_PLAIN>(me.gx - me.px, me.gy - me.py, me.vmax, pvx, pvy);
     float nvx, nvy;
     unsigned long long ost_last = 0;
     const Lines L{lds_ln, 64, tid};
     const RowLds RL{lds_pr, lds_pa, lds_q, lds_sel};
     const int mt = mine ? tid : 0;                                    // all 64 lanes take part (lp3_rows re-deals them)
-    orca_velocity_fast10<0>(mine, false, lds_pv + mt * ent, lds_rr + mt * ent, ent, a.n, px, py, vx, vy, r, vmax, pvx, pvy, a.neighbor_dist,
-                         a.time_horizon, a.dt, L, RL, nvx, nvy, nullptr, ost_last);
-    if (!mine) return;
-    vx = nvx; vy = nvy;
-    if (!a.just_velocities) { px += vx * a.dt; py += vy * a.dt; }
-    rb[0] = px; rb[1] = py; rb[3] = vx; rb[4] = vy;
-    if (a.write_row) {
-        float* s = a.S + ((long)w * a.rows + a.n) * a.as;
-        s[0] = px; s[a.fs] = py; s[3 * a.fs] = vx; s[4 * a.fs] = vy;
-    }
+    orca_velocity_fast10<0>(mine, false, lds_pv + mt * ent, lds_rr + mt * ent, ent, a.n, me.px, me.py, me.vx, me.vy, me.r, me.vmax, pvx, pvy,
+                         a.neighbor_dist, a.time_horizon, a.dt, L, RL, nvx, nvy, nullptr, ost_last);
+    if (mine) robot_store(a, w, rb, me.px, me.py, nvx, nvy);
 }
 
 // ---- worlds beyond one block (second half): neighbour search through a uniform grid ---------------------
@@ -1341,16 +1377,16 @@ template <bool FAST10>
 __global__ __launch_bounds__(64) void k_bw_orca_step(const BigArgs a)
 {
     extern __shared__ __align__(16) unsigned char bw_smem[];
-    const int KL = FAST10 ? 10 : a.K + a.KO;
-    float4* lds_ln = reinterpret_cast<float4*>(bw_smem);                         // [KL][64] ORCA lines
-    float4* lds_pr = lds_ln + KL * 64;                                           // FAST10: [72] lp3_rows projections; generic: [KL][64] LP3 projections
-    float2* lds_pa = reinterpret_cast<float2*>(lds_pr + (FAST10 ? 72 : KL * 64)); // FAST10: [72] chords
-    float4* lds_q = reinterpret_cast<float4*>(lds_pa + (FAST10 ? 72 : 0));       // FAST10: [64]
-    int* lds_sel = reinterpret_cast<int*>(lds_q + (FAST10 ? 64 : 0));            // FAST10: [64]
-    float* lds_nd = reinterpret_cast<float*>(lds_sel + (FAST10 ? 64 : 0));       // generic: [K][64] neighbour distSq
-    int* lds_ni = reinterpret_cast<int*>(lds_nd + (FAST10 ? 0 : a.K * 64));      // generic: [K][64] neighbour row
-    float* lds_od = reinterpret_cast<float*>(lds_ni + (FAST10 ? 0 : a.K * 64));  // generic: [KO][64] obstacle edge distSq
-    int* lds_oi = reinterpret_cast<int*>(lds_od + (FAST10 ? 0 : a.KO * 64));     // generic: [KO][64] obstacle edge
+    const OrcaGridLds lay = orca_grid_lds(FAST10, a.K, a.KO);
+    float4* lds_ln = reinterpret_cast<float4*>(bw_smem + lay.ln.off);
+    float4* lds_pr = reinterpret_cast<float4*>(bw_smem + lay.pr.off);
+    float2* lds_pa = reinterpret_cast<float2*>(bw_smem + lay.pa.off);
+    float4* lds_q = reinterpret_cast<float4*>(bw_smem + lay.q.off);
+    int* lds_sel = reinterpret_cast<int*>(bw_smem + lay.sel.off);
+    float* lds_nd = reinterpret_cast<float*>(bw_smem + lay.nd.off);
+    int* lds_ni = reinterpret_cast<int*>(bw_smem + lay.ni.off);
+    float* lds_od = reinterpret_cast<float*>(bw_smem + lay.od.off);
+    int* lds_oi = reinterpret_cast<int*>(bw_smem + lay.oi.off);
     const int tid = threadIdx.x, i = blockIdx.x * 64 + tid, w = blockIdx.y, n = a.n, rows = a.rows;
     const bool human = i < n;
     const bool is_robot = a.robot_row && i == n;
@@ -1367,17 +1403,10 @@ __global__ __launch_bounds__(64) void k_bw_orca_step(const BigArgs a)
     const int* st = a.start + (long)w * a.NB;          // positions in the job-wide sorted list
     const int* so = a.sorted;
     const float* mg = a.margin + (long)w * rows;
-    // this agent's own RVO2 parameters, where the caller gave some (the grid's cell edge is the scalar neighborDist: the largest one)
-    float nbd = a.neighbor_dist, thz = a.time_horizon, tho = a.time_horizon_obst;
-    int Kme = a.K;
-    if (a.agent_params != nullptr && human) {
-        const float* ap = a.agent_params + ((long)w * rows + i) * 4;
-        nbd = ap[0]; thz = ap[2]; tho = ap[3];
-        Kme = (int)ap[1] < a.K ? (int)ap[1] : a.K;
-    }
-    const float range2 = nbd * nbd;
+    // (the grid's cell edge is the scalar neighborDist: the largest one)
+    const AgentParams ap = agent_params_of(human ? a.agent_params : nullptr, (long)w * rows + i, a.neighbor_dist, a.time_horizon, a.time_horizon_obst, a.K);
     // Agent::computeNeighbors through the grid: the 3 x 3 cells around mine hold every agent closer than neighborDist
-    auto walk = [&](auto&& visit) {
+    auto walk = [&](const float& rangeSq, auto&& visit) {
         const int2 mc = cxy[i];
         for (int dy = -1; dy <= 1; ++dy)
             for (int dx = -1; dx <= 1; ++dx) {
@@ -1390,63 +1419,29 @@ __global__ __launch_bounds__(64) void k_bw_orca_step(const BigArgs a)
                     const float* sb = Sw + (long)b * a.as;
                     const float ddx = px - sb[0], ddy = py - sb[fs];
                     const float dsq = ddx * ddx + ddy * ddy;
-                    if (dsq < range2) visit(dsq, b);
+                    if (dsq < rangeSq) visit(dsq, b);
                 }
             }
+    };
+    auto fetch = [&](int b, float4& q, float& rad) {
+        const float* sb = Sw + (long)b * a.as;
+        q = make_float4(sb[0], sb[fs], sb[3 * fs], sb[4 * fs]);
+        rad = sb[8 * fs] + mg[b];
     };
     float nvx = 0.0f, nvy = 0.0f;
     if constexpr (FAST10) {
         double key[10];
 #pragma unroll
         for (int s = 0; s < 10; ++s) key[s] = key_sentinel();
-        if (human) walk([&](float dsq, int b) { key_insert10(key, __hiloint2double((int)__float_as_uint(dsq), b)); });
+        if (human) walk(ap.nbd * ap.nbd, [&](float dsq, int b) { key_insert10(key, __hiloint2double((int)__float_as_uint(dsq), b)); });
         unsigned long long ost_last = 0;
         const Lines L{lds_ln, 64, tid};
         const RowLds RL{lds_pr, lds_pa, lds_q, lds_sel};
-        orca_solve_fast10<0>(human, a.lp3_static != 0, key, human ? i : 0,
-                          [&](int b, float4& q, float& rad) {
-                              const float* sb = Sw + (long)b * a.as;
-                              q = make_float4(sb[0], sb[fs], sb[3 * fs], sb[4 * fs]);
-                              rad = sb[8 * fs] + mg[b];
-                          },
-                          px, py, vx, vy, r + margin, vmax, pvx, pvy, a.time_horizon, a.dt, L, RL, nvx, nvy, nullptr, ost_last);
+        orca_solve_fast10<0>(human, a.lp3_static != 0, key, human ? i : 0, fetch, px, py, vx, vy, r + margin, vmax, pvx, pvy, a.time_horizon, a.dt, L, RL, nvx, nvy, nullptr, ost_last);
     } else if (human) {
-        const int K = Kme;
-        int cnt = 0;
-        if (K > 0)
-            walk([&](float dsq, int b) {
-                // insertAgentNeighbor over an index-order walk keeps the K smallest (distSq, row) pairs, ties by row: the same list
-                // from any visiting order when the comparison is lexicographic
-                auto before = [&](int s) { const float d = lds_nd[s * 64 + tid]; return dsq < d || (dsq == d && b < lds_ni[s * 64 + tid]); };
-                int s;
-                if (cnt < K) s = cnt++;
-                else if (before(K - 1)) s = K - 1;
-                else return;
-                while (s != 0 && before(s - 1)) {
-                    lds_nd[s * 64 + tid] = lds_nd[(s - 1) * 64 + tid];
-                    lds_ni[s * 64 + tid] = lds_ni[(s - 1) * 64 + tid];
-                    --s;
-                }
-                lds_nd[s * 64 + tid] = dsq;
-                lds_ni[s * 64 + tid] = b;
-            });
-        const Lines L{lds_ln, 64, tid}, P{lds_pr, 64, tid};
-        int nobst = 0;
-        if (a.nv > 0) {
-            const float rng = tho * vmax + (r + margin);   // rangeSq = sqr(timeHorizonObst * maxSpeed + radius)
-            const int no = obstacle_neighbors(a.verts, a.nv, a.KO, px, py, rng * rng, lds_od, lds_oi, 64, tid);
-            nobst = obstacle_lines(a.verts, lds_oi, no, 64, tid, px, py, vx, vy, r + margin, 1.0f / tho, L);
-        }
-        const float invT = 1.0f / thz;
-        const float invDt = 1.0f / a.dt;
-        for (int k = 0; k < cnt; ++k) {
-            const int b = lds_ni[k * 64 + tid];
-            const float* sb = Sw + (long)b * a.as;
-            L.set(nobst + k, orca_line(px, py, vx, vy, make_float4(sb[0], sb[fs], sb[3 * fs], sb[4 * fs]), (r + margin) + (sb[8 * fs] + mg[b]), invT, invDt));
-        }
-        const int total = nobst + cnt;
-        const int failed = lp2(L, total, vmax, pvx, pvy, false, nvx, nvy);
-        if (failed < total) lp3(L, P, total, nobst, failed, vmax, nvx, nvy);
+        // (the lexicographic insertion: the same list from the grid's visiting order as from RVO2's index-order walk)
+        const SolveCols C{Lines{lds_ln, 64, tid}, Lines{lds_pr, 64, tid}, lds_nd, lds_ni, lds_od, lds_oi, 64, tid};
+        orca_solve_generic<true>(ap, a.verts, a.nv, a.KO, walk, fetch, px, py, vx, vy, r + margin, vmax, pvx, pvy, a.dt, C, nvx, nvy);
     }
     // the true robot: robot.step(action, dt) (holonomic), then set_state_orca(robot) AFTER doStep (motion_model_manager.py:389): the
     // humans of this substep saw the row as the previous substep left it
@@ -1475,18 +1470,11 @@ __global__ __launch_bounds__(64) void k_bw_orca_step(const BigArgs a)
     float g0x = gi[0], g0y = gi[1];
     float ddx = g0x - px, ddy = g0y - py;
     if (sqrtf(ddx * ddx + ddy * ddy) < r) { // update_goals: strict <  (:66-70)
-        int k = a.G;
-        for (int g = 0; g < a.G; ++g) if (isnan(gi[2 * g])) { k = g; break; }
-        if (a.peek_out == nullptr) {
-            const float r0 = gi[0], r1 = gi[1];
-            for (int g = 0; g + 1 < k; ++g) { gi[2 * g] = gi[2 * g + 2]; gi[2 * g + 1] = gi[2 * g + 3]; }
-            if (k > 0) { gi[2 * (k - 1)] = r0; gi[2 * (k - 1) + 1] = r1; }
-            g0x = gi[0]; g0y = gi[1];
-        } else if (k > 1) { g0x = gi[2]; g0y = gi[3]; }   // cs_peek commits nothing: the head the rotated list would have
+        const int k = goal_count(gi, a.G);
+        if (a.peek_out == nullptr) goal_rotate(gi, k, g0x, g0y); else goal_peek_head(gi, k, g0x, g0y);   // (cs_peek commits nothing)
         ddx = g0x - px; ddy = g0y - py;
     }
-    const float nrm = sqrtf(ddx * ddx + ddy * ddy);
-    if (nrm > vmax) { pvx = ddx / nrm; pvy = ddy / nrm; } else { pvx = ddx; pvy = ddy; }
+    pref_velocity<FM_PLAIN>(ddx, ddy, vmax, pvx, pvy);
     if (a.peek_out != nullptr) {   // get_human_states(include_goal=True, headed=False) of the next state (:294-298)
         float* q = a.peek_out + ((long)w * n + i) * 8;
         q[0] = px; q[1] = py; q[2] = srow[2 * fs]; q[3] = vx; q[4] = vy; q[5] = srow[7 * fs]; q[6] = g0x; q[7] = g0y;
@@ -1573,6 +1561,11 @@ struct OrcaPlan {
     size_t shmem;       // dynamic LDS of a block
 };
 
+// the two rules orca_plan and orca_robot_launch share: obstacle lines kept per agent, and when the register-resident solve applies
+// (each caller adds its own conditions)
+static int orca_obstacles_kept(int nv) { return nv > 0 ? (nv < KOBST ? nv : KOBST) : 0; }
+static bool orca_register_resident(int K, int nv) { return K == 10 && nv == 0; }
+
 OrcaPlan orca_plan(const cs_worlds* w)
 {
     OrcaPlan p;
@@ -1580,24 +1573,17 @@ OrcaPlan orca_plan(const cs_worlds* w)
     p.T = p.rows <= 64 ? 64 : (p.rows <= 256 ? 256 : 512);
     p.wpb = p.rows <= 64 ? 64 / p.rows : 1;
     const int K = w->orca_max_neighbors, nv = w->orca_n_vertices;
-    p.KO = nv > 0 ? (nv < KOBST ? nv : KOBST) : 0;
-    p.fast10 = K == 10 && nv == 0 && w->d_orca_agent_params == nullptr;
+    p.KO = orca_obstacles_kept(nv);
+    p.fast10 = orca_register_resident(K, nv) && w->d_orca_agent_params == nullptr;
     p.fm = p.fast10 ? orca_math_of(w) : 0;
     const char* lp3_env = std::getenv("CROWDSTEP_ORCA_LP3");   // A/B switch: =static keeps every build on the unrolled walk
     const bool lp3_env_static = lp3_env && std::strcmp(lp3_env, "static") == 0;
-    // dynamic LDS of the one-block kernel (k_orca_step): [2][T] rows + radii / respawn scratch, and either the register-resident build's line
-    // copies or the generic build's per-agent columns (TL = lanes that hold an agent: the width of the per-lane LDS columns)
-    const int TL = p.wpb * p.rows;
-    auto block_shmem = [&](bool lp3_static) {
-        return (size_t)p.T * (2 * sizeof(float4) + 4 * sizeof(float)) +
-               (p.fast10 ? (size_t)10 * TL * sizeof(float4) + (lp3_static ? 0 : 72 * (sizeof(float4) + sizeof(float2))) + (size_t)p.T * (sizeof(float4) + sizeof(int))
-                         : (size_t)(K + p.KO) * TL * (2 * sizeof(float4) + 2 * sizeof(float)));
-    };
+    // dynamic LDS of the one-block kernel (k_orca_step), from the layout the kernel itself reads (orca_lds.h)
+    auto block_shmem = [&](bool lp3_static) { return (size_t)orca_step_lds(p.fast10, lp3_static, p.T, p.wpb, p.rows, K, p.KO).total; };
     p.grid = p.rows > big_world_min_rows(512) || block_shmem(true) > 160 * 1024;
     if (p.grid) {
         p.lp3_static = lp3_env_static ? 1 : 0;
-        p.shmem = p.fast10 ? (size_t)(10 * 64 + 72 + 64) * sizeof(float4) + 72 * sizeof(float2) + 64 * sizeof(int)
-                           : (size_t)(K + p.KO) * 64 * (2 * sizeof(float4)) + (size_t)(K + p.KO) * 64 * (sizeof(float) + sizeof(int));
+        p.shmem = orca_grid_lds(p.fast10, K, p.KO).total;
     } else {
         // linearProgram3 of the register-resident build: one 16-lane row per (agent, violated line) (lp3_rows) in one-wavefront blocks;
         // worlds of more than 64 rows keep the statically unrolled walk (their blocks have no LDS left for the projected lines)
@@ -1656,8 +1642,8 @@ static int orca_big_launch(const cs_worlds* w, const OrcaPlan& p, float dt, int 
     float* S2 = (float*)base;
     void* grid_mem = base + state_pad;
     const size_t shmem = p.shmem;
-    if (shmem > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_bw_orca_step<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    const void* kernel = p.fast10 ? (const void*)k_bw_orca_step<true> : (const void*)k_bw_orca_step<false>;
+    if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     HIP_TRY(hipMemcpyAsync(S2, w->d_state, state_bytes, hipMemcpyDeviceToDevice, stream));   // the columns a step does not write
     const float* cur = w->d_state;
     float* nxt = S2;
@@ -1749,22 +1735,21 @@ int orca_robot_launch(const cs_worlds* w, float robot_margin, const float* d_hum
     std::memset(&a, 0, sizeof(a));
     a.W = w->W; a.n = w->n; a.rows = rows_of(w); a.robot_row = a.rows - a.n;
     a.write_row = a.robot_row && w->type != CS_ORCA;   // an ORCA crowd takes the moved robot after its own doStep (:389)
-    a.K = w->orca_max_neighbors; a.nv = w->orca_n_vertices; a.KO = a.nv > 0 ? (a.nv < KOBST ? a.nv : KOBST) : 0;
+    a.K = w->orca_max_neighbors; a.nv = w->orca_n_vertices; a.KO = orca_obstacles_kept(a.nv);
     a.dt = dt; a.neighbor_dist = w->orca_neighbor_dist; a.time_horizon = w->orca_time_horizon;
     a.time_horizon_obst = w->orca_time_horizon_obst; a.robot_margin = robot_margin;
     a.S = w->d_state;
     state_strides(w, a.as, a.fs);
     a.hmargin = d_human_margin; a.robot = w->d_robot; a.verts = w->d_orca_vertices; a.just_velocities = just_velocities ? 1 : 0;
-    const size_t shmem = (size_t)(a.K + a.KO) * 64 * (2 * sizeof(float4) + 2 * sizeof(float));
+    const size_t shmem = orca_robot_lds(a.K, a.KO).total;
     if (shmem > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void*)k_orca_robot_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     // one lane per world, 16 worlds per wavefront: the linear programme is a serial, divergent chain per lane (one launch costs
     // about one ORCA substep, ~55 us, whatever the packing: 64 / 32 / 16 / 8 worlds per wavefront measured 1.27 / 1.24 / 1.18 /
     // 1.18 ms per 20-substep imitation step at 4096 worlds), so the packing only has to reach every CU
     a.wpb = 16;
-    if (a.K == 10 && a.nv == 0 && a.n + 1 <= 128) {   // the reference's defaults, no walls: register-resident solve
-        const size_t sh = (size_t)a.wpb * (a.n + 1) * sizeof(float4) + (size_t)(((a.wpb * (a.n + 1)) + 3) & ~3) * sizeof(float) +
-                          (10 + 1) * 64 * sizeof(float4) + 72 * (sizeof(float4) + sizeof(float2)) + 64 * sizeof(int);
+    if (orca_register_resident(a.K, a.nv) && a.n + 1 <= 128) {   // the reference's defaults, no walls: register-resident solve
+        const size_t sh = orca_robot_fast_lds(a.wpb, a.n).total;
         hipLaunchKernelGGL(k_orca_robot_step_fast, dim3((w->W + a.wpb - 1) / a.wpb), dim3(64), sh, stream, a);
         HIP_TRY(hipGetLastError());
         return CS_OK;

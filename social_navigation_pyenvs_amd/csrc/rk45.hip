@@ -21,6 +21,7 @@
 #include <string>
 
 #include "common.h"
+#include "goals.h"
 #include "crowdstep.h"
 #include "robot_model.h"
 
@@ -262,14 +263,7 @@ __global__ __launch_bounds__(64) void k_rk45_step(const KArgsRk a)
             }
             // update_goals at the trial position (:66-70, strict <): rotate the list
             const float ddx = g0x - px, ddy = g0y - py;
-            if (sqrtf(ddx * ddx + ddy * ddy) < radius) {
-                int k = a.G;
-                for (int g = 0; g < a.G; ++g) if (isnan(gi[2 * g])) { k = g; break; }
-                const float r0 = gi[0], r1 = gi[1];
-                for (int g = 0; g + 1 < k; ++g) { gi[2 * g] = gi[2 * g + 2]; gi[2 * g + 1] = gi[2 * g + 3]; }
-                if (k > 0) { gi[2 * (k - 1)] = r0; gi[2 * (k - 1) + 1] = r1; }
-                g0x = gi[0]; g0y = gi[1];
-            }
+            if (sqrtf(ddx * ddx + ddy * ddy) < radius) goal_rotate(gi, goal_count(gi, a.G), g0x, g0y);
             if (HEADED) {
                 sincosf(th, &sn, &cs);
                 vx = cs * bvx - sn * bvy; vy = sn * bvx + cs * bvy;

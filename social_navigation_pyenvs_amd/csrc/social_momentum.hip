@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "goals.h"
 #include "robotstep.h"
 #include "respawnx.h"
 
@@ -100,14 +101,8 @@ __global__ __launch_bounds__(64) void k_sm_step(const MArgs a)
             {
                 const float ddx = g0x - px, ddy = g0y - py;
                 if (sqrtf(ddx * ddx + ddy * ddy) < r) {
-                    int k = a.G;
-                    for (int g = 0; g < a.G; ++g) if (isnan(gi[2 * g])) { k = g; break; }
-                    if (a.peek_out == nullptr) {
-                        const float r0 = gi[0], r1 = gi[1];
-                        for (int g = 0; g + 1 < k; ++g) { gi[2 * g] = gi[2 * g + 2]; gi[2 * g + 1] = gi[2 * g + 3]; }
-                        if (k > 0) { gi[2 * (k - 1)] = r0; gi[2 * (k - 1) + 1] = r1; }
-                        g0x = gi[0]; g0y = gi[1];
-                    } else if (k > 1) { g0x = gi[2]; g0y = gi[3]; }
+                    const int k = goal_count(gi, a.G);
+                    if (a.peek_out == nullptr) goal_rotate(gi, k, g0x, g0y); else goal_peek_head(gi, k, g0x, g0y);
                 }
             }
             const float4* pv = &lds_pv[cur][base];

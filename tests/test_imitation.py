@@ -112,7 +112,7 @@ def test_gym_imitation_learning_step_g11():
         assert abs(env.global_time - 0.25 * len(c["rewards"])) < 1e-9
 
 
-def _orca_robot_oracle(S, n, robot, verts, human_margin, robot_margin, dt):
+def _orca_robot_oracle(S, n, robot, verts, human_margin, robot_margin, dt, max_nb=10):
     """One doStep of the robot's own simulator (motion_model_manager.py:641-653) on the C restatement: humans with preferred
     velocity 0 and the robot last; only the robot's row is used."""
     pos = np.vstack([S[:n, 0:2], robot[None, 0:2]]).astype(np.float32)
@@ -124,9 +124,9 @@ def _orca_robot_oracle(S, n, robot, verts, human_margin, robot_margin, dt):
     radius = np.concatenate([S[:n, 8] + human_margin, [robot[8] + robot_margin]]).astype(np.float32)
     maxspeed = np.concatenate([S[:n, 12], [robot[12]]]).astype(np.float32)
     if verts is None:
-        v = orc.orca_new_velocities(pos, vel, pref, radius, maxspeed, time_step=dt)
+        v = orc.orca_new_velocities(pos, vel, pref, radius, maxspeed, max_nb=max_nb, time_step=dt)
     else:
-        v = orc.orca_new_velocities_obst(pos, vel, pref, radius, maxspeed, verts, time_step=dt)[0]
+        v = orc.orca_new_velocities_obst(pos, vel, pref, radius, maxspeed, verts, max_nb=max_nb, time_step=dt)[0]
     out = robot.copy()
     out[3:5] = v[n]
     out[0:2] = robot[0:2] + v[n] * np.float32(dt)
@@ -172,6 +172,36 @@ def test_orca_robot_model_matches_restatement(walls):
     np.testing.assert_array_equal(after[:, 3:5], full[:, 3:5])
     np.testing.assert_array_equal(after[:, 0:2], before[:, 0:2])
     assert np.any(full[:, 0:2] != before[:, 0:2])
+
+
+@pytest.mark.gpu
+def test_orca_robot_model_generic_solve_with_five_neighbours_matches_restatement():
+    """maxNeighbors = 5 takes the robot's generic (LDS-column) solve without walls; five humans fill its neighbour list exactly.
+    The robot's row of the C restatement, bit for bit, over 20 substeps."""
+    from social_navigation_pyenvs_amd import scenarios as sc
+    from social_navigation_pyenvs_amd.batched import CrowdWorlds
+
+    W, n = 3, 5
+    rng = np.random.default_rng(11)
+    pos, yaw, g = sc.circular_crossing(W, n, 3.0, 778)
+    S = sc.make_states(pos, yaw, g).astype(np.float32)
+    S[:, :, 3:5] = rng.normal(0, 0.3, (W, n, 2))
+    P = np.tile(sc.default_params("sfm_helbing"), (n, 1))
+    robot = np.zeros((W, 13), np.float32)
+    robot[:, 0:2] = rng.uniform(-0.5, 0.5, (W, 2)) + [-2.0, 0.0]
+    robot[:, 8], robot[:, 9], robot[:, 12] = 0.3, 80.0, 1.0
+    robot[:, 10:12] = [3.0, 0.2]
+    cw = CrowdWorlds(S, g, P, np.zeros((W, n), np.float32), None, type="sfm_helbing", all_params_equal=True, robot=robot)
+    cw.orca_params = dict(cw.orca_params, max_neighbors=5)
+    cw.set_robot_model("orca", None, 0.01 + 0.05, np.full((W, n), 0.06, np.float32))
+    ref_robot = robot.copy()
+    for k in range(20):
+        Sg = cw.get_states()
+        for w in range(W):
+            ref_robot[w] = _orca_robot_oracle(Sg[w], n, ref_robot[w], None, np.float32(0.06), np.float32(0.06), DT, max_nb=5)
+        cw.imitation_block(DT, 1)
+        np.testing.assert_array_equal(cw.get_robot()[:, [0, 1, 3, 4]], ref_robot[:, [0, 1, 3, 4]])
+    assert np.all(ref_robot[:, 0] > robot[:, 0] + 0.1)   # the robots did move towards their goals
 
 
 @pytest.mark.gpu
