@@ -592,6 +592,32 @@ int cs_value_net_decide(int kind, const int32_t* dims, int n_dims, const float* 
                         int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values, int32_t* d_choice,
                         float* d_action_out, void* stream);
 
+/*
+ * cs_value_net_decide_bf16  the same decision with the opt-in bf16 arithmetic (csrc/value_net_bf16.hip): the arguments,
+ *   results, errors and messages of cs_value_net_decide, with d_weights the blob cs_value_net_pack_bf16 writes and n_weight_bytes its
+ *   length in bytes; the LDS-fit check is made for this entry's own tile buffers.  A layer whose input holds raw rotated-state columns
+ *   (CADRL value_network layer 0, SARL mlp1 layer 0, all of mlp3) stays float32; every other layer runs on v_mfma_f32_32x32x16_bf16
+ *   with bf16 weights (rounded to nearest even at pack time), float32 biases and float32 accumulation in a fixed k order.  An
+ *   activation is rounded to bf16 once, when it is stored as the operand of a bf16 layer (after bias and ReLU); what a reduction
+ *   consumes (attention scores, mlp2 features, CADRL's per-human value) is not rounded; the crowd mean is summed in float32 from the
+ *   rounded mlp1 outputs and rounded once.  Softmax, minimum, weighted sum, the action value and the pick are cs_value_net_decide's.
+ *   A (world, action) gives the same bits for W = 1 as inside any batch.
+ * cs_value_net_pack_bf16  (host only) params as cs_value_net_pack; blob == NULL: only *n_bytes is set.  Layout, layer after layer in
+ *   the order of `dims`, every offset a multiple of 16 bytes:
+ *     a float32 layer   as cs_value_net_pack lays it out: float [ncb][kg][64 lanes][4] with ncb = ceil(N / 32) column blocks and kg =
+ *                       ceil(K / 8) k-groups -- lane l holds Wt[k = 8 g + 4 (l >> 5) + s][column 32 cb + (l & 31)], s = 0..3 --, then
+ *                       float bias[32 ncb];
+ *     a bf16 layer      bfloat16 [ncb][ks][64 lanes][8] with ks = ceil(K1 / 16) + ceil(K2 / 16) k-steps (K2: the attention's
+ *                       crowd-mean half, its k-steps behind the first source's) -- lane l holds Wt[k = 16 s + 8 (l >> 5) + e][column
+ *                       32 cb + (l & 31)], e = 0..7, of k-step s --, then float bias[32 ncb].
+ *   Weights and biases beyond N or K are zero.
+ */
+int cs_value_net_pack_bf16(int kind, const int32_t* dims, int n_dims, int cols, const float* const* params, void* blob, size_t* n_bytes);
+int cs_value_net_decide_bf16(int kind, const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n,
+                             int cols, const float* d_rotated, const float* d_rewards, const float* d_actions, const float* d_robot,
+                             int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values, int32_t* d_choice,
+                             float* d_action_out, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

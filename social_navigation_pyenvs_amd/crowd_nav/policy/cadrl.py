@@ -153,6 +153,7 @@ class CADRL(Policy):
             setattr(self, attribute, value)
         self._net = None
         self._acts_device = None
+        self.decision_precision = "f32"
 
     # ------------------------------------------------------------------ configuration
     def configure(self, config):
@@ -177,6 +178,13 @@ class CADRL(Policy):
     def set_epsilon(self, epsilon):
         self.epsilon = epsilon
 
+    def set_decision_precision(self, precision):
+        """The arithmetic of the decision kernel, for ``predict`` and ``act_device`` alike: "f32" (the default) or the opt-in "bf16"
+        (bf16 matrix instructions behind the first layer, float32 accumulation and reductions)."""
+        from .value_net import check_precision
+
+        self.decision_precision = check_precision(precision)
+
     def build_action_space(self, v_pref):
         """(0, 0) plus rotation_samples headings x speed_samples exponentially spaced speeds up to v_pref."""
         self.action_space_ndarray = build_action_space_array(v_pref, self.speed_samples, self.rotation_samples)
@@ -187,12 +195,12 @@ class CADRL(Policy):
 
     # ------------------------------------------------------------------ the decision
     def device_net(self):
-        """The network as the kernel reads it (value_net.DeviceNet), its blob repacked only after a parameter changed."""
+        """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
         from .value_net import DeviceNet
 
         if self._net is None or self._net.model is not self.model:
             self._net = DeviceNet(self.model, self.joint_state_dim)
-        self._net.refresh()
+        self._net.refresh(self.decision_precision)
         return self._net
 
     def device_action_space(self):
@@ -238,7 +246,7 @@ class CADRL(Policy):
                                        C.c_void_p(d_n.data_ptr()), C.c_void_p(d_c.data_ptr()), C.c_void_p(d_r.data_ptr()), C.c_int(len(ROBOT_FIELDS)),
                                        C.c_float(self.time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(stream)))
         value_net.decide(net, 1, A, n, rot.data_ptr(), rew.data_ptr(), d_a.data_ptr(), d_r.data_ptr(), len(ROBOT_FIELDS), self.gamma, self.time_step,
-                         ovr.data_ptr(), vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+                         ovr.data_ptr(), vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream, precision=self.decision_precision)
         self._last_rotated = rot
         return vals[0].cpu().numpy(), int(pick.item()), act[0].cpu().numpy()
 

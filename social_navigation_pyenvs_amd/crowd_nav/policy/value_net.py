@@ -2,7 +2,10 @@
 
 ``describe(policy)`` turns a policy's torch module into the kernel's layer description, ``DeviceNet`` keeps the packed weight blob on the
 GPU and repacks it only when a parameter changed (the tensors' version counters), ``decide`` is the one library call of a decision.
-There is no host implementation of the decision: without the library or a GPU these raise."""
+There is no host implementation of the decision: without the library or a GPU these raise.
+
+Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_value_net_decide_bf16, csrc/value_net_bf16.hip) with its
+own blob; a policy chooses with ``set_decision_precision``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,6 +13,13 @@ import ctypes as C
 import numpy as np
 
 CS_VN_CADRL, CS_VN_SARL = 0, 1     # include/crowdstep.h
+PRECISIONS = ("f32", "bf16")
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"decision precision {precision!r}: one of {', '.join(map(repr, PRECISIONS))}")
+    return precision
 
 
 def _linears(seq):
@@ -31,51 +41,72 @@ def describe(model):
     return CS_VN_SARL, np.array(dims, np.int32), layers
 
 
-def pack(kind, dims, cols, arrays):
-    """The kernel's weight blob (float32 numpy) from [weight_0, bias_0, weight_1, ...] float32 arrays.  Host only: no GPU needed."""
+def pack(kind, dims, cols, arrays, precision="f32"):
+    """The kernel's weight blob from [weight_0, bias_0, weight_1, ...] float32 arrays: float32 numpy for "f32", the bytes (uint8 numpy)
+    of cs_value_net_pack_bf16's layout for "bf16".  Host only: no GPU needed."""
     from ... import _lib
 
     lib = _lib.load()
+    if check_precision(precision) == "bf16":
+        return _pack_with(lib.cs_value_net_pack_bf16, np.uint8, kind, dims, cols, arrays)
+    return _pack_with(lib.cs_value_net_pack, np.float32, kind, dims, cols, arrays)
+
+
+def _pack_with(entry, unit, kind, dims, cols, arrays):
+    """The size query and the packing call of one of the two pack entries; `unit`: what the entry counts its blob in."""
+    from ... import _lib
+
     dims = np.ascontiguousarray(dims, np.int32)
     arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
     d = dims.ctypes.data_as(C.c_void_p)
-    _lib.check(lib.cs_value_net_pack(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), None, None, C.byref(nf)))
-    blob = np.zeros(nf.value, np.float32)
-    _lib.check(lib.cs_value_net_pack(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
+    _lib.check(entry(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), None, None, C.byref(nf)))
+    blob = np.zeros(nf.value, unit)
+    _lib.check(entry(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
     return blob
 
 
 class DeviceNet:
-    """A policy's network as the kernel reads it: description + packed blob in HBM, rebuilt when the module's parameters changed."""
+    """A policy's network as the kernel reads it: description + one packed blob per precision in HBM, each rebuilt when the module's
+    parameters changed (the same version-counter key for both).  ``blob`` is the float32 one."""
 
     def __init__(self, model, cols):
         self.model, self.cols = model, int(cols)
         self.kind, self.dims, self.layers = describe(model)
-        self._key = None
-        self.blob = None
+        self._keys = dict.fromkeys(PRECISIONS)
+        self.blobs = dict.fromkeys(PRECISIONS)
+
+    @property
+    def blob(self):
+        return self.blobs["f32"]
 
     def _versions(self):
         return tuple((p.data_ptr(), p._version) for l in self.layers for p in (l.weight, l.bias))
 
-    def refresh(self):
+    def refresh(self, precision="f32"):
         import torch
 
         key = self._versions()
-        if key != self._key:
+        if key != self._keys[check_precision(precision)]:
             arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in (l.weight, l.bias)]
-            self.blob = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays)).to("cuda")
-            self._key = key
-        return self.blob
+            self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision)).to("cuda")
+            self._keys[precision] = key
+        return self.blobs[precision]
 
 
-def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None):
-    """cs_value_net_decide on device pointers (ints); `net` a DeviceNet whose blob is current (refresh())."""
+def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None,
+           precision="f32"):
+    """cs_value_net_decide (`precision` "f32") or cs_value_net_decide_bf16 ("bf16") on device pointers (ints); `net` a DeviceNet whose
+    blob of that precision is current (refresh(precision))."""
     from ... import _lib
 
     P = C.c_void_p
-    _lib.check(_lib.load().cs_value_net_decide(
-        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(net.blob.data_ptr()), C.c_size_t(net.blob.numel()),
+    blob = net.blobs[check_precision(precision)]
+    if blob is None:
+        raise ValueError(f"decide: the network has no {precision} blob yet (DeviceNet.refresh({precision!r}))")
+    entry = _lib.load().cs_value_net_decide_bf16 if precision == "bf16" else _lib.load().cs_value_net_decide
+    _lib.check(entry(
+        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
         C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), P(rotated), P(rewards), P(actions), P(robot), C.c_int(robot_stride),
         C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))

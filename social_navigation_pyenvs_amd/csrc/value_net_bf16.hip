@@ -1,0 +1,393 @@
+// value_net_bf16.hip -- the value-network decision of value_net.hip with the opt-in bf16 arithmetic (cs_value_net_decide_bf16; Python:
+// policy.set_decision_precision("bf16")).  Same groups, tiles and workgroups: a group is one (world, action), 32 groups per workgroup,
+// tiles of 32 rows, mlp3 once per workgroup as one 32-row block, no activation leaves the CU, the pick kernel follows.
+//
+// The arithmetic:
+//   float32 layers   a layer whose input holds raw rotated-state columns: CADRL value_network layer 0, SARL mlp1 layer 0, all of mlp3.
+//                    They are value_net.hip's layer (value_net_plan.h layer_fwd) on v_mfma_f32_32x32x2_f32.  dg, px1, da reach 10 m, where
+//                    one bf16 step is 3 cm; layer 0 has K = 13 / 15, about 1/10 of the next layer's work; mlp3 runs once per group.
+//   bf16 layers      every other layer, on v_mfma_f32_32x32x16_bf16.  Weights rounded to bf16 (nearest even) at pack time; biases
+//                    float32, they start the accumulator; float32 accumulation, the k-steps of 16 in order: one fixed order per
+//                    output element that depends on the layer's widths alone.
+//   rounding points  an activation is rounded to bf16 (nearest even) exactly once: when the epilogue stores it to LDS as the operand of a
+//                    bf16 layer, after the bias and the ReLU.  An output that a reduction consumes is NOT rounded: the attention
+//                    scores, mlp2's features, CADRL's per-human value.  with_global_state: the crowd mean is summed in float32, in
+//                    human order, from the bf16-rounded mlp1 outputs, divided by n, and rounded once as the attention operand.
+//   float32 as before  the masked softmax exp(s) * (s != 0) without maximum subtraction, the minimum, the weighted sum,
+//                    rewards + gamma^(dt v_pref) out, k_value_pick.
+//   NaN / +-inf      follow IEEE through the conversion; padding columns are stored as 0 (0 * inf, as in the float32 kernel).
+// A (world, action) gives the same bits alone (W = 1) and anywhere inside a batch.  No atomics.  gfx950 only.
+//
+// LDS image of a bf16 operand: row-major bfloat16, row stride S = 2 * ld elements where ld = 4 * odd floats, so a row is 16 * odd bytes.
+// Lane l of a wavefront reads the 16 bytes (8 k) of row l & 31 at k = 16 s + 8 (l >> 5) with one ds_read_b128; that instruction is served
+// in the 16-lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same two + 32: each group holds 16 rows that are distinct
+// modulo 16 at one column offset, and row * (16 * odd) bytes puts them on the 16 different 16-byte slots of the 256-byte bank row:
+// conflict-free (the float32 file's width + 4 floats does the same for 8 rows of its 32-byte k-groups).
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "value_net_plan.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+__host__ __device__ inline bool vn_mlp3(const VnPlan& p, int l) { return p.kind == CS_VN_SARL && l >= p.c0[3]; }
+// a float32 layer: its input holds raw rotated-state columns
+__host__ __device__ inline bool vn_f32_layer(const VnPlan& p, int l) { return l == p.c0[0] || vn_mlp3(p, l); }
+// a layer whose output is the operand of a bf16 layer (a chain's last output goes to a reduction, except mlp1's)
+inline bool vn_out_bf16(const VnPlan& p, int l)
+{
+    if (vn_mlp3(p, l)) return false;
+    for (int c = 1; c <= 4; ++c)
+        if (l == p.c0[c] - 1) return p.kind == CS_VN_SARL && c == 1;
+    return true;
+}
+
+// build_plan's table with the bf16 layers counted in k-steps of 16 (kg_split, kg_total), the blob offsets that follow (still in floats:
+// a lane's 8 bf16 are 4 floats wide, so a layer keeps the size formula ncb * kg_total * 64 * 4 + ncb * 32) and the LDS strides of
+// bf16 rows (floats; header comment)
+void replan_bf16(VnPlan& p)
+{
+    int off = 0, widest = 36;
+    for (int l = 0; l < p.n_layers; ++l) {
+        VnLayer& L = p.L[l];
+        if (!vn_f32_layer(p, l)) {
+            L.kg_split = up(L.K1, 16) / 16;
+            L.kg_total = L.kg_split + up(L.K2, 16) / 16;
+        }
+        L.w_off = off;
+        off += L.ncb * L.kg_total * 64 * 4;
+        L.b_off = off;
+        off += L.ncb * 32;
+        const int ld = vn_out_bf16(p, l) ? L.ncb * 16 + 4 : L.ncb * 32 + 4;
+        widest = ld > widest ? ld : widest;
+    }
+    p.ld_pq = widest;
+    p.ld_m1 = up(p.m1w > 0 ? p.m1w : 1, 32) / 2 + 4;
+    p.total_floats = off;
+}
+
+inline uint16_t bf16_bits(float f)       // round to nearest even; a NaN becomes the quiet NaN 0x7fc0 (what torch's .bfloat16() gives)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+__device__ __forceinline__ float h2f(const float* buf, int ld, int r, int c) { return static_cast<float>(reinterpret_cast<const __bf16*>(buf)[r * 2 * ld + c]); }
+__device__ __forceinline__ void f2h(float* buf, int ld, int r, int c, float v) { reinterpret_cast<__bf16*>(buf)[r * 2 * ld + c] = static_cast<__bf16>(v); }
+
+// One bf16 layer of a tile: layer_fwd's contract with bfloat16 rows in src / src2 (strides in floats) and the weights as
+// [ncb][k-steps][64 lanes][8 bf16]: lane l holds Wt[k = 16 s + 8 (l >> 5) + j][column 32 cb + (l & 31)], j = 0..7, of k-step s.
+template <bool OUT_BF16>
+__device__ __forceinline__ void layer_fwd_h(const VnLayer& L, const float* __restrict__ wb, const float* src, int lds_, const float* src2, int lds2,
+                                            const int* grp, int rbs, float* dst, int ldd, int rot)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, li = lane & 31;
+    const int items = rbs * L.ncb;
+    const int KS = L.kg_total, split = L.kg_split;
+    for (int it = (wave + rot) & 3; it < items; it += 4) {
+        const int rb = it % rbs, cb = it / rbs;
+        const int row = rb * 32 + li;
+        const bf16x8* a1 = reinterpret_cast<const bf16x8*>(src + row * lds_) + h;
+        const bf16x8* a2 = src2 ? reinterpret_cast<const bf16x8*>(src2 + grp[row] * lds2) + h : a1;
+        const bf16x8* bw = reinterpret_cast<const bf16x8*>(wb + L.w_off) + (long)cb * KS * 64 + lane;
+        const float bias = wb[L.b_off + cb * 32 + li];
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias;
+        bf16x8 nb0 = bw[0], nb1 = bw[(1 < KS ? 1 : KS - 1) * 64], nb2 = bw[(2 < KS ? 2 : KS - 1) * 64], nb3 = bw[(3 < KS ? 3 : KS - 1) * 64];
+        for (int ks0 = 0; ks0 < KS; ks0 += 4) {
+            const bf16x8 b0 = nb0, b1 = nb1, b2 = nb2, b3 = nb3;
+            {   // the next four k-steps' weights are on their way while these four multiply (clamped: a tail re-reads the last step)
+                const int q0 = ks0 + 4, q1 = ks0 + 5, q2 = ks0 + 6, q3 = ks0 + 7, last = KS - 1;
+                nb0 = bw[(q0 < KS ? q0 : last) * 64];
+                nb1 = bw[(q1 < KS ? q1 : last) * 64];
+                nb2 = bw[(q2 < KS ? q2 : last) * 64];
+                nb3 = bw[(q3 < KS ? q3 : last) * 64];
+            }
+#define VN_STEP(U, B)                                                                            \
+    if (ks0 + U < KS) {                                                                          \
+        const int ks = ks0 + U;                                                                  \
+        const bf16x8 a = ks < split ? a1[2 * ks] : a2[2 * (ks - split)];                         \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, B, acc, 0, 0, 0);                       \
+    }
+            VN_STEP(0, b0)
+            VN_STEP(1, b1)
+            VN_STEP(2, b2)
+            VN_STEP(3, b3)
+#undef VN_STEP
+        }
+        // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+        const bool pad = cb * 32 + li >= L.N;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = acc[r];
+            if (L.relu) v = v < 0.0f ? 0.0f : v;
+            v = pad ? 0.0f : v;
+            const int orow = rb * 32 + 4 * h + (r & 3) + 8 * (r >> 2), ocol = cb * 32 + li;
+            if constexpr (OUT_BF16) f2h(dst, ldd, orow, ocol, v);
+            else dst[orow * ldd + ocol] = v;
+        }
+    }
+}
+
+struct VnBufs { float *X0, *M1, *P, *Q, *G, *Gf, *J, *sc, *den, *val; int* grp; };
+
+enum { CH_MLP1, CH_REDUCED, CH_MLP3, CH_CADRL };   // mlp1 (ends in M1); mlp2 / attention (bf16 in, float32 out); mlp3; CADRL's value_network
+
+// layers [first, last) from `src`; outputs alternate P, Q; the last one goes to final_dst when given.  Returns where the result is.
+// The chain's kind fixes which arithmetic a layer may take, so that a call site carries only those.
+template <int CH>
+__device__ __forceinline__ const float* run_chain(const VnPlan& p, const float* __restrict__ wb, const VnBufs& b, int first, int last, const float* src,
+                                                  int lds_, const float* src2, int lds2, int rbs, float* final_dst, int final_ld, int& out_ld)
+{
+    const float* cur = src;
+    int cur_ld = lds_;
+    for (int l = first; l < last; ++l) {
+        const bool fin = l == last - 1;
+        float* dst = fin && final_dst ? final_dst : (((l - first) & 1) ? b.Q : b.P);
+        const int ldd = fin && final_dst ? final_ld : p.ld_pq;
+        const float* s2 = l == first ? src2 : nullptr;
+        const int rot = l + (int)blockIdx.x;
+        if constexpr (CH == CH_MLP3) layer_fwd<false>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+        else if constexpr (CH == CH_MLP1) {
+            if (l == first) layer_fwd<true>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+            else layer_fwd_h<true>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+        } else if constexpr (CH == CH_REDUCED) {
+            if (fin) layer_fwd_h<false>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+            else layer_fwd_h<true>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+        } else {
+            if (l == first && fin) layer_fwd<false>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+            else if (l == first) layer_fwd<true>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+            else if (fin) layer_fwd_h<false>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+            else layer_fwd_h<true>(p.L[l], wb, cur, cur_ld, s2, lds2, b.grp, rbs, dst, ldd, rot);
+        }
+        __syncthreads();
+        cur = dst;
+        cur_ld = ldd;
+    }
+    out_ld = cur_ld;
+    return cur;
+}
+
+// rows of the rotated array into the input tile, zero beyond the rows and the columns; grp[r] = the tile-local group of row r
+__device__ __forceinline__ void load_tile(const VnBufs& b, const float* __restrict__ rows_src, int rows, int cols, int per_group, int M)
+{
+    for (int i = threadIdx.x; i < M * 16; i += NT) {
+        const int r = i >> 4, c = i & 15;
+        b.X0[r * LDX + c] = (r < rows && c < cols) ? rows_src[(long)r * cols + c] : 0.0f;
+    }
+    for (int r = threadIdx.x; r < M; r += NT) b.grp[r] = r < rows ? r / per_group : 0;
+}
+
+// value_net.hip's k_value_net with M1 and G as bfloat16 rows and the layers' arithmetic of the header comment; `Gf`: the float32 running
+// sum of the crowd mean of a group in chunks (floats from the start of the dynamic block)
+__global__ __launch_bounds__(NT) void k_value_net_bf16(VnPlan p, VnLds m, int Gf, int M, const float* __restrict__ wb, int NG, int A, int n,
+                                                       const float* __restrict__ rotated, const float* __restrict__ rewards,
+                                                       const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
+{
+    extern __shared__ float lds[];
+    VnBufs b;
+    b.X0 = lds + m.X0; b.M1 = lds + m.M1; b.P = lds + m.P; b.Q = lds + m.Q; b.G = lds + m.G; b.Gf = lds + Gf; b.J = lds + m.J;
+    b.sc = lds + m.sc; b.den = lds + m.den; b.val = lds + m.val; b.grp = reinterpret_cast<int*>(lds + m.grp);
+    const int tid = threadIdx.x;
+    const int rbs = M / 32, cols = p.cols;
+    const bool sarl = p.kind == CS_VN_SARL;
+    const int chunks = n <= M ? 1 : (n + M - 1) / M;
+    const int gpt = n <= M ? M / n : 1;
+    const int m1pad = (p.m1w + 15) & ~15;          // the columns the attention's k-steps read of the mean
+    int out_ld;
+
+    for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
+        const int gbase = job * JROWS;
+        const int ng = NG - gbase < JROWS ? NG - gbase : JROWS;
+        if (sarl) {
+            for (int i = tid; i < JROWS * p.ld_j; i += NT) b.J[i] = 0.0f;
+            if (tid < JROWS) b.den[tid] = 0.0f;
+        } else if (tid < JROWS) b.val[tid] = INFINITY;
+        __syncthreads();
+
+        for (int t0 = 0; t0 < ng; t0 += gpt) {
+            const int tg = ng - t0 < gpt ? ng - t0 : gpt;
+            const float* grows = rotated + (long)(gbase + t0) * n * cols;
+            if (sarl && p.with_global && chunks > 1) {
+                // more humans than a tile holds: a first pass over the chunks for the mean of mlp1 (sarl.py:42), a float32 running sum in Gf
+                for (int c = tid; c < m1pad; c += NT) b.Gf[c] = 0.0f;
+                for (int ch = 0; ch < chunks; ++ch) {
+                    const int rows = n - ch * M < M ? n - ch * M : M;
+                    load_tile(b, grows + (long)ch * M * cols, rows, cols, n, M);
+                    __syncthreads();
+                    run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
+                    for (int c = tid; c < m1pad; c += NT) {
+                        float s = b.Gf[c];
+                        for (int r = 0; r < rows; ++r) s += h2f(b.M1, p.ld_m1, r, c);
+                        b.Gf[c] = s;
+                    }
+                    __syncthreads();
+                }
+                for (int c = tid; c < m1pad; c += NT) f2h(b.G, p.ld_m1, 0, c, b.Gf[c] / (float)n);
+                __syncthreads();
+            }
+            // phase 0: a tile holds its groups whole -- denominator, weights and weighted sum in one visit.  A group in chunks needs the
+            // softmax denominator of ALL its humans before the first weight (sarl.py:52-53): phase 1 sums it, phase 2 recomputes and weighs.
+            for (int phase = chunks > 1 ? 1 : 0; phase <= (chunks > 1 ? 2 : 0); ++phase)
+            for (int ch = 0; ch < chunks; ++ch) {
+                const int per = chunks > 1 ? (n - ch * M < M ? n - ch * M : M) : n;      // humans of each group in this tile
+                const int rows = chunks > 1 ? per : tg * n;
+                load_tile(b, grows + (long)ch * M * cols, rows, cols, per, M);
+                __syncthreads();
+                if (!sarl) {
+                    if (phase == 1) continue;
+                    const float* out = run_chain<CH_CADRL>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, nullptr, 0, out_ld);
+                    if (tid < tg) {         // cadrl.py:269: the minimum over the humans
+                        float v = b.val[t0 + tid];
+                        for (int j = 0; j < per; ++j) {      // (torch.min's order: a NaN stays)
+                            const float x = out[(tid * per + j) * out_ld];
+                            v = (x < v || x != x) ? x : v;
+                        }
+                        b.val[t0 + tid] = v;
+                    }
+                    __syncthreads();
+                    continue;
+                }
+                if (ch == 0)                // sarl.py:36: the self state is read from the first human's row
+                    for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * LDX + i % SELF_DIM];
+                run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
+                if (p.with_global && chunks == 1 && n > 1) {
+                    for (int i = tid; i < tg * m1pad; i += NT) {
+                        const int k = i / m1pad, c = i - k * m1pad;
+                        float s = 0.0f;
+                        for (int j = 0; j < n; ++j) s += h2f(b.M1, p.ld_m1, k * n + j, c);
+                        f2h(b.G, p.ld_m1, k, c, s / (float)n);
+                    }
+                    __syncthreads();
+                }
+                {   // attention scores and the masked softmax's terms exp(s) * (s != 0) (sarl.py:48-52)
+                    const float* out = run_chain<CH_REDUCED>(p, wb, b, p.c0[2], p.c0[3], b.M1, p.ld_m1, p.with_global ? b.G : nullptr, p.ld_m1, rbs, nullptr, 0, out_ld);
+                    for (int r = tid; r < M; r += NT) {
+                        const float s = out[r * out_ld];
+                        b.sc[r] = (r < rows && s != 0.0f) ? expf(s) : 0.0f;
+                    }
+                    __syncthreads();
+                }
+                if (phase != 2) {           // the denominator, in human order
+                    if (tid < tg) {
+                        float s = b.den[t0 + tid];
+                        for (int j = 0; j < per; ++j) s += b.sc[tid * per + j];
+                        b.den[t0 + tid] = s;
+                    }
+                    __syncthreads();
+                    if (phase == 1) continue;
+                }
+                for (int r = tid; r < rows; r += NT) b.sc[r] = b.sc[r] / b.den[t0 + r / per];
+                __syncthreads();
+                {   // mlp2 and the weighted sum of its rows (sarl.py:57-60)
+                    const float* f = run_chain<CH_REDUCED>(p, wb, b, p.c0[1], p.c0[2], b.M1, p.ld_m1, nullptr, 0, rbs, nullptr, 0, out_ld);
+                    const int fw = p.feat;
+                    for (int i = tid; i < tg * fw; i += NT) {
+                        const int k = i / fw, c = i - k * fw;
+                        float s = b.J[(t0 + k) * p.ld_j + SELF_DIM + c];
+                        for (int j = 0; j < per; ++j) s = fmaf(b.sc[k * per + j], f[(k * per + j) * out_ld + c], s);
+                        b.J[(t0 + k) * p.ld_j + SELF_DIM + c] = s;
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+
+        if (sarl) {
+            const float* out = run_chain<CH_MLP3>(p, wb, b, p.c0[3], p.c0[4], b.J, p.ld_j, nullptr, 0, 1, nullptr, 0, out_ld);
+            if (tid < ng) b.val[tid] = out[tid * out_ld];
+            __syncthreads();
+        }
+        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
+            const int g = gbase + tid;
+            const float vpref = robot[(long)(g / A) * rstride + 7];
+            values[g] = rewards[g] + powf(gamma, dt * vpref) * b.val[tid];
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace
+
+#include "value_net_pick.h"
+
+extern "C" int cs_value_net_pack_bf16(int kind, const int32_t* dims, int n_dims, int cols, const float* const* params, void* blob, size_t* n_bytes)
+{
+    VnPlan p;
+    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    if (rc != CS_OK) return rc;
+    replan_bf16(p);
+    if (!n_bytes) return fail(CS_ERR_ARG, "null argument");
+    *n_bytes = (size_t)p.total_floats * sizeof(float);
+    if (!blob) return CS_OK;
+    if (!params) return fail(CS_ERR_ARG, "null argument");
+    for (int l = 0; l < p.n_layers; ++l)
+        if (!params[2 * l] || !params[2 * l + 1]) return fail(CS_ERR_ARG, "null weight or bias array");
+    memset(blob, 0, *n_bytes);
+    float* fb = static_cast<float*>(blob);
+    for (int l = 0; l < p.n_layers; ++l) {
+        const VnLayer& L = p.L[l];
+        const float* wgt = params[2 * l];       // torch.nn.Linear.weight: [N][K1 + K2]
+        const float* bias = params[2 * l + 1];
+        if (vn_f32_layer(p, l)) { pack_layer_f32(L, wgt, bias, fb); continue; }
+        uint16_t* hb = reinterpret_cast<uint16_t*>(fb + L.w_off);
+        const int K = L.K1 + L.K2;
+        for (int cb = 0; cb < L.ncb; ++cb)
+            for (int ks = 0; ks < L.kg_total; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = cb * 32 + (lane & 31);
+                        const int kk = ks * 16 + 8 * (lane >> 5) + e;
+                        int k = -1;
+                        if (ks < L.kg_split) { if (kk < L.K1) k = kk; }
+                        else if (kk - L.kg_split * 16 < L.K2) k = L.K1 + kk - L.kg_split * 16;
+                        if (j < L.N && k >= 0) hb[((size_t)(cb * L.kg_total + ks) * 64 + lane) * 8 + e] = bf16_bits(wgt[(size_t)j * K + k]);
+                    }
+        for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
+    }
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_decide_bf16(int kind, const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n,
+                                        int cols, const float* d_rotated, const float* d_rewards, const float* d_actions, const float* d_robot,
+                                        int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values, int32_t* d_choice,
+                                        float* d_action_out, void* stream)
+{
+    VnPlan p;
+    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    if (rc != CS_OK) return rc;
+    replan_bf16(p);
+    // (a length that is no whole number of floats is no blob of any network: it fails the size check as SIZE_MAX floats)
+    const size_t n_floats = n_weight_bytes % sizeof(float) ? (size_t)-1 : n_weight_bytes / sizeof(float);
+    const int rc2 = check_decide_args(p, d_weights, n_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    if (rc2 != CS_OK) return rc2;
+    const size_t lds_limit = 160 * 1024;
+    const int M = TILE_M;
+    VnLds m = lds_map(p, M, n);
+    int Gf = 0;
+    if (p.kind == CS_VN_SARL && p.with_global && n > M) {
+        Gf = m.total;
+        m.total += up(p.m1w, 16);
+    }
+    const size_t shmem = (size_t)m.total * sizeof(float);
+    if (shmem > lds_limit) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    if (shmem > 64 * 1024) VN_GRANT_LDS(k_value_net_bf16, shmem);
+    const int NG = W * A;
+    const int jobs = (NG + JROWS - 1) / JROWS;
+    const int grid = jobs < 4096 ? jobs : 4096;
+    hipLaunchKernelGGL(k_value_net_bf16, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, p, m, Gf, M, static_cast<const float*>(d_weights), NG, A, n,
+                       d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
+                       d_override, d_choice, d_action_out);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}

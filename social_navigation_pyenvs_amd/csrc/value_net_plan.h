@@ -1,0 +1,245 @@
+// value_net_plan.h -- what the two arithmetics of the value-network decision share (value_net.hip: float32; value_net_bf16.hip: the opt-in
+// bf16 layers): the layer table of a network description, the LDS map of a launch and the float32 layer of a tile.  Everything sits in an
+// unnamed namespace: each translation unit gets its own copy, the kernels keep their names.  The per-world pick is value_net_pick.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+
+namespace {
+
+using csimpl::fail;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NT = 256;            // 4 wavefronts
+constexpr int TILE_M = 32;         // rows of a tile: one 32-row MFMA block (a 64-row tile measured 15 - 40 % slower: one workgroup per CU)
+constexpr int JROWS = 32;          // groups per workgroup = rows of the mlp3 block
+constexpr int VN_MAX_LAYERS = 16;
+constexpr int VN_MAX_WIDTH = 256;
+constexpr int SELF_DIM = 6;        // sarl.py self_state_dim: dg, v_pref, theta, radius, vx, vy
+constexpr int LDX = 20;            // row stride of the input tile (13 or 15 columns padded to 16)
+
+struct VnLayer {
+    int K1, K2, N;                 // input columns from the first / second source, output columns
+    int kg_split, kg_total;        // k-groups of 8 from the first source; in all
+    int ncb;                       // 32-column output blocks
+    int relu;
+    int w_off, b_off;              // floats into the blob: [ncb][kg_total][64 lanes][4], then [ncb * 32] biases
+};
+
+struct VnPlan {
+    int kind, cols, with_global, n_layers;
+    int c0[5];                     // CADRL: c0[0..1] = value_network; SARL: mlp1, mlp2, attention, mlp3 = [c0[i], c0[i + 1])
+    VnLayer L[VN_MAX_LAYERS];
+    int feat;                      // width of mlp2's output
+    int m1w;                       // width of mlp1's output
+    int ld_m1, ld_pq, ld_j;        // LDS row strides
+    int total_floats;
+};
+
+inline int up(int x, int m) { return (x + m - 1) / m * m; }
+
+// the layer table of a network description (include/crowdstep.h cs_value_net_decide: `dims`); CS_OK or the fail() status
+inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, VnPlan& p)
+{
+    memset(&p, 0, sizeof p);
+    if (kind != CS_VN_CADRL && kind != CS_VN_SARL) return fail(CS_ERR_ARG, "unknown value network kind (CS_VN_CADRL, CS_VN_SARL)");
+    if (cols != 13 && cols != 15) return fail(CS_ERR_ARG, "rotated rows have 13 or 15 columns");
+    if (!dims || n_dims < 2) return fail(CS_ERR_ARG, "null or empty layer description");
+    p.kind = kind;
+    p.cols = cols;
+    int at = 0;
+    const int n_chains = kind == CS_VN_CADRL ? 1 : 4;
+    if (kind == CS_VN_SARL) p.with_global = dims[at++] ? 1 : 0;
+    int off = 0;
+    for (int c = 0; c < n_chains; ++c) {
+        if (at >= n_dims) return fail(CS_ERR_ARG, "layer description ends early");
+        const int nl = dims[at++];
+        if (nl < 1 || at + nl > n_dims) return fail(CS_ERR_ARG, "a chain needs at least one layer and its widths");
+        if (p.n_layers + nl > VN_MAX_LAYERS) return fail(CS_ERR_ARG, "at most 16 layers in all");
+        p.c0[c] = p.n_layers;
+        // what the chain reads (sarl.py:15-25): mlp1 the rotated row; mlp2 mlp1's output; attention (mlp1, mean of mlp1) or mlp1; mlp3 (self state, feature)
+        int k1 = cols, k2 = 0;
+        if (c == 1) k1 = p.m1w;
+        if (c == 2) { k1 = p.m1w; k2 = p.with_global ? p.m1w : 0; }
+        if (c == 3) k1 = SELF_DIM + p.feat;
+        for (int i = 0; i < nl; ++i) {
+            const int wdt = dims[at++];
+            if (wdt < 1 || wdt > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "layer widths must be between 1 and 256");
+            VnLayer& l = p.L[p.n_layers++];
+            l.K1 = k1; l.K2 = k2; l.N = wdt;
+            l.kg_split = up(k1, 8) / 8;
+            l.kg_total = l.kg_split + up(k2, 8) / 8;
+            l.ncb = up(wdt, 32) / 32;
+            l.relu = (i != nl - 1 || (kind == CS_VN_SARL && c == 0)) ? 1 : 0;     // cadrl.py mlp(): last_relu only for mlp1
+            l.w_off = off;
+            off += l.ncb * l.kg_total * 64 * 4;
+            l.b_off = off;
+            off += l.ncb * 32;
+            k1 = wdt; k2 = 0;
+        }
+        const int last = p.L[p.n_layers - 1].N;
+        if (c == 0 && kind == CS_VN_SARL) p.m1w = last;
+        if (c == 1) p.feat = last;
+        if ((kind == CS_VN_CADRL || c >= 2) && last != 1) return fail(CS_ERR_ARG, "value_network, attention and mlp3 end in one output");
+    }
+    p.c0[n_chains] = p.n_layers;
+    if (at != n_dims) return fail(CS_ERR_ARG, "layer description has trailing entries");
+    int widest = 32;
+    for (int i = 0; i < p.n_layers; ++i) widest = p.L[i].ncb * 32 > widest ? p.L[i].ncb * 32 : widest;
+    p.ld_pq = widest + 4;
+    p.ld_m1 = up(p.m1w > 0 ? p.m1w : 1, 32) + 4;
+    p.ld_j = up(SELF_DIM + p.feat, 8) + 4;
+    p.total_floats = off;
+    return CS_OK;
+}
+
+// the checks of a decision's arguments that follow the layer table, in the order cs_value_net_decide gives them; n_weight_floats is
+// the length of the caller's blob in floats
+inline int check_decide_args(const VnPlan& p, const void* d_weights, size_t n_weight_floats, int W, int A, int n, const void* d_rotated,
+                             const void* d_rewards, const void* d_actions, const void* d_robot, int robot_stride, const void* d_values,
+                             const void* d_action_out)
+{
+    if (W < 1 || A < 1) return fail(CS_ERR_ARG, "W and A must be positive");
+    if (n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
+    if ((long)W * A > INT_MAX / 2 || (long)W * A * n > (1L << 40)) return fail(CS_ERR_ARG, "W * A * n is too large");
+    if (!d_weights || !d_rotated || !d_rewards || !d_actions || !d_robot || !d_values || !d_action_out) return fail(CS_ERR_ARG, "null argument");
+    if (n_weight_floats != (size_t)p.total_floats) return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack)");
+    if (robot_stride < 8) return fail(CS_ERR_ARG, "robot rows need at least 8 columns: px,py,vx,vy,r,gx,gy,v_pref");
+    return CS_OK;
+}
+
+// one layer's float32 weights and biases where the lanes of layer_fwd read them: wgt = torch.nn.Linear.weight [N][K1 + K2], blob zeroed before
+inline void pack_layer_f32(const VnLayer& L, const float* wgt, const float* bias, float* blob)
+{
+    const int K = L.K1 + L.K2;
+    for (int cb = 0; cb < L.ncb; ++cb)
+        for (int kg = 0; kg < L.kg_total; ++kg)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int s = 0; s < 4; ++s) {
+                    const int j = cb * 32 + (lane & 31);
+                    const int kk = kg * 8 + 4 * (lane >> 5) + s;
+                    int k = -1;
+                    if (kg < L.kg_split) { if (kk < L.K1) k = kk; }
+                    else if (kk - L.kg_split * 8 < L.K2) k = L.K1 + kk - L.kg_split * 8;
+                    if (j < L.N && k >= 0) blob[L.w_off + ((cb * L.kg_total + kg) * 64 + lane) * 4 + s] = wgt[(size_t)j * K + k];
+                }
+    for (int j = 0; j < L.N; ++j) blob[L.b_off + j] = bias[j];
+}
+
+// LDS map of a launch (floats from the start of the dynamic block)
+struct VnLds { int X0, M1, P, Q, G, J, sc, den, val, self, grp, total; };
+
+inline VnLds lds_map(const VnPlan& p, int M, int n)
+{
+    VnLds m{};
+    int o = 0;
+    auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
+    m.X0 = take(M * LDX);
+    m.P = take(M * p.ld_pq);
+    m.Q = take(M * p.ld_pq);
+    if (p.kind == CS_VN_SARL) {
+        const int gpt = n <= M ? M / n : 1;
+        m.M1 = take(M * p.ld_m1);
+        m.G = n == 1 ? m.M1 : take(gpt * p.ld_m1);     // one human: the mean of mlp1 over the group IS its row (x / 1, exactly)
+        m.J = take(JROWS * p.ld_j);
+    }
+    m.sc = take(M);
+    m.den = take(JROWS);
+    m.val = take(JROWS);
+    m.grp = take(M);
+    m.total = o;
+    return m;
+}
+
+// the dynamic LDS of a launch beyond a kernel's default 64 KiB: raised per device to the largest size asked for so far
+#define VN_GRANT_LDS(kernel, shmem)                                                                                                   \
+    do {                                                                                                                              \
+        static std::atomic<int> granted[64];                                                                                          \
+        int dev = 0;                                                                                                                  \
+        HIP_TRY(hipGetDevice(&dev));                                                                                                  \
+        const bool slot = dev >= 0 && dev < 64;                                                                                       \
+        if (!slot || granted[dev].load(std::memory_order_acquire) < (int)(shmem)) {                                                   \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(shmem))); \
+            if (slot) granted[dev].store((int)(shmem), std::memory_order_release);                                                    \
+        }                                                                                                                             \
+    } while (0)
+
+// One float32 layer of a tile: dst[rows][ncb * 32] = act(src[rows][K] x Wt + b) for `rbs` row blocks of 32.  The A operand of row r comes
+// from src (k-groups below kg_split) and then from src2[grp[r]] (the per-group second source: SARL's mean of mlp1); columns beyond N are
+// stored as 0 whatever the inputs (their zero weights and bias give 0 only for finite inputs: 0 * inf is a NaN, which the next layer's
+// zero weights would hand on where torch returns +-inf), so the next layer may read its K rounded up to 8.
+// OUT_BF16 (value_net_bf16.hip): the output is the operand of a bf16 layer -- dst holds bfloat16 rows of 2 * ldd elements, each value
+// rounded to nearest even after the bias and the ReLU.
+template <bool OUT_BF16>
+__device__ __forceinline__ void layer_fwd(const VnLayer& L, const float* __restrict__ wb, const float* src, int lds_, const float* src2, int lds2,
+                                          const int* grp, int rbs, float* dst, int ldd, int rot)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, li = lane & 31;
+    const int items = rbs * L.ncb;
+    const int KG = L.kg_total, split = L.kg_split;
+    for (int it = (wave + rot) & 3; it < items; it += 4) {
+        const int rb = it % rbs, cb = it / rbs;
+        const int row = rb * 32 + li;
+        const float* a1 = src + row * lds_ + 4 * h;
+        const float* a2 = src2 ? src2 + grp[row] * lds2 + 4 * h : a1;
+        const float4* bw = reinterpret_cast<const float4*>(wb + L.w_off) + (long)cb * KG * 64 + lane;
+        const float bias = wb[L.b_off + cb * 32 + li];
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias;
+        float4 nb0 = bw[0], nb1 = bw[(1 < KG ? 1 : KG - 1) * 64], nb2 = bw[(2 < KG ? 2 : KG - 1) * 64], nb3 = bw[(3 < KG ? 3 : KG - 1) * 64];
+        for (int kg0 = 0; kg0 < KG; kg0 += 4) {
+            const float4 b0 = nb0, b1 = nb1, b2 = nb2, b3 = nb3;
+            {   // the next four k-groups' weights are on their way while these four multiply (clamped: a tail re-reads the last group)
+                const int q0 = kg0 + 4, q1 = kg0 + 5, q2 = kg0 + 6, q3 = kg0 + 7, last = KG - 1;
+                nb0 = bw[(q0 < KG ? q0 : last) * 64];
+                nb1 = bw[(q1 < KG ? q1 : last) * 64];
+                nb2 = bw[(q2 < KG ? q2 : last) * 64];
+                nb3 = bw[(q3 < KG ? q3 : last) * 64];
+            }
+#define VN_STEP(U, B)                                                                                                        \
+    if (kg0 + U < KG) {                                                                                                      \
+        const int kg = kg0 + U;                                                                                              \
+        const float4 a = *reinterpret_cast<const float4*>(kg < split ? a1 + kg * 8 : a2 + (kg - split) * 8);                 \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, B.x, acc, 0, 0, 0);                                                  \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, B.y, acc, 0, 0, 0);                                                  \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, B.z, acc, 0, 0, 0);                                                  \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, B.w, acc, 0, 0, 0);                                                  \
+    }
+            VN_STEP(0, b0)
+            VN_STEP(1, b1)
+            VN_STEP(2, b2)
+            VN_STEP(3, b3)
+#undef VN_STEP
+        }
+        // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+        if constexpr (OUT_BF16) {
+            __bf16* d = reinterpret_cast<__bf16*>(dst) + (rb * 32 + 4 * h) * (2 * ldd) + cb * 32 + li;
+            const bool pad = cb * 32 + li >= L.N;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = acc[r];
+                if (L.relu) v = v < 0.0f ? 0.0f : v;
+                d[((r & 3) + 8 * (r >> 2)) * (2 * ldd)] = static_cast<__bf16>(pad ? 0.0f : v);
+            }
+        } else {
+            float* d = dst + (rb * 32 + 4 * h) * ldd + cb * 32 + li;
+            const bool pad = cb * 32 + li >= L.N;          // (the zero weights give 0 * inf = NaN there when an input is infinite)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = acc[r];
+                if (L.relu) v = v < 0.0f ? 0.0f : v;      // (a NaN stays a NaN, as torch's ReLU leaves it)
+                d[((r & 3) + 8 * (r >> 2)) * ldd] = pad ? 0.0f : v;
+            }
+        }
+    }
+}
+
+} // namespace

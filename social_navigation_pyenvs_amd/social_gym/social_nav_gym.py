@@ -715,7 +715,8 @@ class BatchedSocialNavGym:
         holonomic robot (the policies act in ActionXY, robot_agent.py:112-114).
 
         A ``crowd_nav.policy`` CADRL / SARL instance decides with its value network instead: cs_peek (or the constant-velocity model
-        when the policy's ``query_env`` is false) -> cs_lookahead -> cs_value_net_decide, all on ``device_stream()``.  ``explore``: an
+        when the policy's ``query_env`` is false) -> cs_lookahead -> cs_value_net_decide (cs_value_net_decide_bf16 after the policy's
+        ``set_decision_precision("bf16")``), all on ``device_stream()``.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
         values and choices of that decision stay readable through ``last_values_device()``."""
         import torch
@@ -810,7 +811,7 @@ class BatchedSocialNavGym:
             rot, rew, rob = self._lookahead_on_side_stream(dl, acts, next_humans=nxt, with_robot=True)
             value_net.decide(net, W, A, self.n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], pol.gamma,
                              self.robot_time_step, None if explore is None else explore.data_ptr(), dl["vn_values"].data_ptr(),
-                             dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream)
+                             dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream, precision=pol.decision_precision)
             for t in (rot, rew, rob) + (() if explore is None else (explore,)) + (() if nxt is None else (nxt,)):
                 t.record_stream(side)
         self._stream_handshake(dl, cur, False)

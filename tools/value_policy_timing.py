@@ -11,6 +11,7 @@ interquartile range) of the baseline.  FLOP are the useful ones (2 x in x out pe
 tile is not counted), the fraction is against the 157 TFLOP/s float32 matrix peak.  Writes profiles/value_policy_timing.json and prints it.
 
     python tools/value_policy_timing.py [--worlds 4096] [--humans 5 25] [--policies cadrl sarl] [--repeats 20] [--out FILE]
+    python tools/value_policy_timing.py --precision f32 bf16   # both arithmetics, alternated inside every repeat; one record each
     python tools/value_policy_timing.py --trace-only        # a few act_device decisions, for a kernel trace of `decide`
 """
 import argparse
@@ -86,6 +87,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--torch-chunk", type=int, default=1024, help="worlds per torch forward (the whole batch's intermediates at once need tens of GB)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "value_policy_timing.json"))
+    ap.add_argument("--precision", nargs="+", default=["f32"], choices=["f32", "bf16"], help="decision arithmetics to time, alternated inside every repeat")
+    ap.add_argument("--no-torch", action="store_true", help="skip the torch baseline (an A/B of two libraries needs only the kernels)")
     ap.add_argument("--trace-only", action="store_true")
     a = ap.parse_args()
 
@@ -109,15 +112,19 @@ def main():
                 rot, rew = env.lookahead_device(acts)
                 rob = env.cw.d_robot.torch().view(W, 13)[:, [0, 1, 3, 4, 8, 10, 11, 12, 2]].contiguous()
                 disc = torch.pow(torch.tensor(pol.gamma, dtype=torch.float64, device="cuda"), env.robot_time_step * rob[:, 7].double()).float()[:, None]
-                net = pol.device_net()
                 vals = torch.zeros((W, 81), device="cuda")
                 pick = torch.zeros(W, dtype=torch.int32, device="cuda")
                 act = torch.zeros((W, 2), device="cuda")
                 stream = env.device_stream().cuda_stream
 
-                def kernel():
-                    value_net.decide(net, W, 81, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), 9, pol.gamma, env.robot_time_step,
-                                     None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+                def kernel(prec):
+                    pol.set_decision_precision(prec)
+                    value_net.decide(pol.device_net(), W, 81, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), 9, pol.gamma,
+                                     env.robot_time_step, None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream, precision=prec)
+
+                def decide(prec):
+                    pol.set_decision_precision(prec)
+                    env.act_device(pol)
 
                 def timed(fn):
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -127,31 +134,47 @@ def main():
                     e1.synchronize()
                     return e0.elapsed_time(e1)
 
+                run_torch = lambda: torch_decide(pol, rot, rew, disc, a.torch_chunk)
                 for _ in range(3):
-                    kernel()
-                    torch_decide(pol, rot, rew, disc, a.torch_chunk)
-                tv, tp = torch_decide(pol, rot, rew, disc, a.torch_chunk)
+                    for prec in a.precision:
+                        kernel(prec)
+                        decide(prec)
+                    if not a.no_torch:
+                        run_torch()
+                tv, tp = run_torch()
                 scale = torch.clamp(tv.abs().max(dim=1).values, min=1.0)
-                rel = float(((vals - tv).abs().max(dim=1).values / scale).max())
-                tk, tt, td = [], [], []
+                rel, same = {}, {}
+                for prec in a.precision:
+                    kernel(prec)
+                    rel[prec] = float(((vals - tv).abs().max(dim=1).values / scale).max())
+                    same[prec] = float((pick.long() == tp).float().mean())
+                tk, td, tt = {p: [] for p in a.precision}, {p: [] for p in a.precision}, []
                 for _ in range(a.repeats):
-                    tk.append(timed(kernel))
-                    tt.append(timed(lambda: torch_decide(pol, rot, rew, disc, a.torch_chunk)))
-                    td.append(timed(lambda: env.act_device(pol)))
+                    for prec in a.precision:
+                        tk[prec].append(timed(lambda: kernel(prec)))
+                    if not a.no_torch:
+                        tt.append(timed(run_torch))
+                    for prec in a.precision:
+                        td[prec].append(timed(lambda: decide(prec)))
+                pol.set_decision_precision("f32")
                 flop = useful_flop(pol, W * 81 * n, W * 81)
                 q = lambda xs, p: float(np.percentile(xs, p))
-                r = dict(policy=name, worlds=W, actions=81, humans=n, repeats=a.repeats, useful_gflop=flop / 1e9,
-                         kernel_ms=q(tk, 50), kernel_min_ms=min(tk), kernel_max_ms=max(tk),
-                         decide_ms=q(td, 50), decide_min_ms=min(td), decide_max_ms=max(td),
-                         torch_ms=q(tt, 50), torch_min_ms=min(tt), torch_max_ms=max(tt), torch_iqr_ms=q(tt, 75) - q(tt, 25),
-                         torch_chunk_worlds=a.torch_chunk, kernel_tflops=flop / (q(tk, 50) * 1e-3) / 1e12,
-                         kernel_fraction_of_f32_matrix_peak=flop / (q(tk, 50) * 1e-3) / PEAK_F32_MATRIX,
-                         torch_tflops=flop / (q(tt, 50) * 1e-3) / 1e12, speedup_vs_torch=q(tt, 50) / q(tk, 50),
-                         kernel_not_slower_than_torch=bool(q(tk, 50) <= q(tt, 50) + (max(tt) - min(tt))),
-                         worst_rel_value_diff_vs_torch=rel, same_pick_fraction=float((pick.long() == tp).float().mean()),
-                         tile_rows=os.environ.get("CROWDSTEP_VN_TILE", "default"), device=_lib.device_name(0))
-                print(json.dumps(r), flush=True)
-                results.append(r)
+                for prec in a.precision:
+                    k, d = tk[prec], td[prec]
+                    r = dict(policy=name, precision=prec, worlds=W, actions=81, humans=n, repeats=a.repeats, useful_gflop=flop / 1e9,
+                             kernel_ms=q(k, 50), kernel_min_ms=min(k), kernel_max_ms=max(k),
+                             decide_ms=q(d, 50), decide_min_ms=min(d), decide_max_ms=max(d),
+                             kernel_tflops=flop / (q(k, 50) * 1e-3) / 1e12,
+                             kernel_fraction_of_f32_matrix_peak=flop / (q(k, 50) * 1e-3) / PEAK_F32_MATRIX,
+                             worst_rel_value_diff_vs_torch=rel[prec], same_pick_fraction=same[prec],
+                             tile_rows=os.environ.get("CROWDSTEP_VN_TILE", "default"), device=_lib.device_name(0),
+                             library=os.environ.get("CROWDSTEP_LIB", "product build"))
+                    if tt:
+                        r.update(torch_ms=q(tt, 50), torch_min_ms=min(tt), torch_max_ms=max(tt), torch_iqr_ms=q(tt, 75) - q(tt, 25),
+                                 torch_chunk_worlds=a.torch_chunk, torch_tflops=flop / (q(tt, 50) * 1e-3) / 1e12, speedup_vs_torch=q(tt, 50) / q(k, 50),
+                                 kernel_not_slower_than_torch=bool(q(k, 50) <= q(tt, 50) + (max(tt) - min(tt))))
+                    print(json.dumps(r), flush=True)
+                    results.append(r)
         env.close()
     if results and a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
