@@ -618,6 +618,25 @@ int cs_value_net_decide_bf16(int kind, const int32_t* dims, int n_dims, const vo
                              int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values, int32_t* d_choice,
                              float* d_action_out, void* stream);
 
+/*
+ * cs_value_net_decide_worlds  cs_lookahead followed by cs_value_net_decide as ONE entry point, without the look-ahead tensor
+ *   (csrc/value_net_worlds.hip): the network kernel generates a tile's input rows in LDS from the worlds' own rows, so
+ *   rotated [W][A][n][13|15] -- an A-fold expansion of its inputs, 431 MB at 4096 worlds x 81 actions x 25 humans -- is never written.
+ *   d_actions [A][2], d_next [W][n][4|6], d_current [W][n][5|7], d_robot [W][robot_stride], robot_stride and dt are exactly what
+ *   cs_lookahead takes; kind, dims, d_weights (cs_value_net_pack's blob for cols = 13, or 15 with theta_and_omega_visible), gamma,
+ *   d_override, d_values, d_choice and d_action_out exactly what cs_value_net_decide takes.  d_rewards_out (may be NULL) receives
+ *   [W][A], the rewards the kernel computed.  d_values, d_choice, d_action_out and d_rewards_out are, bit for bit, those of
+ *   cs_lookahead followed by cs_value_net_decide on the same inputs; a (world, action) gives the same bits for W = 1 as inside any
+ *   batch.  Device memory touched: the inputs above, the blob, and one float per (world, action) (two with d_rewards_out).  Two kernels
+ *   on `stream`: the network, then the per-world pick.  Errors (CS_ERR_ARG, before any device call): those of cs_value_net_decide and
+ *   of cs_lookahead with their messages (d_next and d_current are required; robot_stride >= 8); the LDS-fit check is made for this
+ *   kernel's own LDS (the tile buffers and a table of 32 x 8 floats).
+ */
+int cs_value_net_decide_worlds(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                               int theta_and_omega_visible, const float* d_actions, const float* d_next, const float* d_current,
+                               const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
+                               float* d_rewards_out /* may be NULL */, float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

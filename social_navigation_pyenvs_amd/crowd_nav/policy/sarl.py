@@ -65,6 +65,8 @@ class SARL(MultiHumanRL):
         """The attention over the humans for the LAST action of the last decision (what a per-action model() loop leaves behind, and what
         the reference's renderer shows): one forward of the torch module on that action's rows, on demand -- not on the hot path."""
         rot = getattr(self, "_last_rotated", None)
+        if callable(rot):               # a "fused" decision wrote no rows: the last action's are generated now
+            rot = rot()[0]
         if rot is not None:
             with torch.no_grad():
                 self.model(rot[0, -1:].to(next(self.model.parameters()).device))

@@ -5,7 +5,8 @@ GPU and repacks it only when a parameter changed (the tensors' version counters)
 There is no host implementation of the decision: without the library or a GPU these raise.
 
 Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_value_net_decide_bf16, csrc/value_net_bf16.hip) with its
-own blob; a policy chooses with ``set_decision_precision``."""
+own blob; a policy chooses with ``set_decision_precision``.  Two inputs: "tensor", the default (cs_lookahead's rows in HBM), and the opt-in
+"fused" (``decide_worlds``: cs_value_net_decide_worlds generates the rows in the kernel, float32 only); ``set_decision_input``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,12 +15,24 @@ import numpy as np
 
 CS_VN_CADRL, CS_VN_SARL = 0, 1     # include/crowdstep.h
 PRECISIONS = ("f32", "bf16")
+DECISION_INPUTS = ("tensor", "fused")
 
 
 def check_precision(precision):
     if precision not in PRECISIONS:
         raise ValueError(f"decision precision {precision!r}: one of {', '.join(map(repr, PRECISIONS))}")
     return precision
+
+
+def check_decision_input(decision_input, precision):
+    """The pair (decision input, precision) a policy may hold: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel,
+    no look-ahead tensor) exists for the float32 arithmetic only."""
+    if decision_input not in DECISION_INPUTS:
+        raise ValueError(f"decision input {decision_input!r}: one of {', '.join(map(repr, DECISION_INPUTS))}")
+    if decision_input == "fused" and check_precision(precision) == "bf16":
+        raise ValueError('decision input "fused" with decision precision "bf16": the bf16 kernel has its own tile loader and reads the '
+                         'look-ahead tensor; choose "tensor" or "f32"')
+    return decision_input
 
 
 def _linears(seq):
@@ -110,3 +123,22 @@ def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, 
         C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
         C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), P(rotated), P(rewards), P(actions), P(robot), C.c_int(robot_stride),
         C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))
+
+
+def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out, values, choice, action_out,
+                  stream=None):
+    """cs_value_net_decide_worlds on device pointers (ints): the decision of ``decide`` from the worlds' own rows -- what cs_lookahead takes
+    (actions [A][2], nxt [W][n][4|6], cur [W][n][5|7], robot [W][robot_stride]) -- without the look-ahead tensor.  `net` a DeviceNet whose
+    float32 blob is current and whose cols match `headed`; rewards_out [W][A] or None."""
+    from ... import _lib
+
+    P = C.c_void_p
+    blob = net.blobs["f32"]
+    if blob is None:
+        raise ValueError("decide_worlds: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    if net.cols != (15 if headed else 13):
+        raise ValueError(f"decide_worlds: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    _lib.check(_lib.load().cs_value_net_decide_worlds(
+        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
+        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(int(bool(headed))), P(actions), P(nxt), P(cur), P(robot), C.c_int(robot_stride),
+        C.c_float(gamma), C.c_float(dt), P(override), P(rewards_out), P(values), P(choice), P(action_out), P(stream)))

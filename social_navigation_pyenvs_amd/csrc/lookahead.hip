@@ -6,13 +6,15 @@
 //
 // One block per world.  Phase 1: one lane per action runs the swept collision test over the humans (sequential, with
 // the reference's early break) and the agent-centric frame of that action into LDS.  Phase 2: one lane per
-// (action, human) element writes a 13- or 15-float row.  The output is the HBM cost: 4 * 13 * A * n bytes per world
+// (action, human) element writes a 13- or 15-float row.  The arithmetic of both phases is lookahead_math.h's, shared with the
+// value-network kernel that generates the same rows in LDS (value_net.hip, cs_value_net_decide_worlds).  The output is the HBM cost: 4 * 13 * A * n bytes per world
 // (81 actions x 25 humans: 105 KB), written once; inputs are ~1 KB per world.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "common.h"
+#include "lookahead_math.h"
 
 namespace {
 
@@ -26,59 +28,32 @@ __global__ __launch_bounds__(256) void k_lookahead(int W, int n, int A, int head
     const int w = blockIdx.x;
     const int nc = headed ? 6 : 4, cc = headed ? 7 : 5, oc = headed ? 15 : 13;
     const float* rb = robot + (long)w * rstride;
-    const float rpx = rb[0], rpy = rb[1], rr = rb[4], rgx = rb[5], rgy = rb[6], rvd = rb[7];
+    const float rr = rb[4], rvd = rb[7];
     const float* curw = cur + (long)w * n * cc;
     const float* nxtw = next + (long)w * n * nc;
     for (int a = threadIdx.x; a < A; a += blockDim.x) {
         const float ax = actions[2 * a], ay = actions[2 * a + 1];
-        const float nrx = rpx + ax * dt, nry = rpy + ay * dt;
-        float dmin = 9223372036854775807.0f;
-        bool collision = false;
-        for (int j = 0; j < n; ++j) { // cadrl.py:56-64, utils.py:22-36
-            const float* c = curw + (long)j * cc;
-            const float x1 = c[0] - rpx, y1 = c[1] - rpy;
-            const float x2 = x1 + (c[2] - ax) * dt, y2 = y1 + (c[3] - ay) * dt;
-            const float px = x2 - x1, py = y2 - y1;
-            float d;
-            if (px == 0.0f && py == 0.0f) d = sqrtf(x1 * x1 + y1 * y1);
-            else {
-                float u = ((0.0f - x1) * px + (0.0f - y1) * py) / (px * px + py * py);
-                u = u > 1.0f ? 1.0f : (u < 0.0f ? 0.0f : u);
-                const float qx = x1 + u * px, qy = y1 + u * py;
-                d = sqrtf(qx * qx + qy * qy);
-            }
-            const float dist = d - c[4] - rr;
-            if (dist < 0.0f) { collision = true; break; }
-            else if (dist < dmin) dmin = dist;
-        }
-        const float gdx = rgx - nrx, gdy = rgy - nry;
-        const float dg = sqrtf(gdx * gdx + gdy * gdy);
-        float rew = 0.0f;                      // literals of cadrl.py:69-72
-        if (collision) rew = -0.25f;
-        else if (dg < rr) rew = 1.0f;
-        else if (dmin < 0.2f) rew = (dmin - 0.2f) * 0.5f * dt;
-        rewards[(long)w * A + a] = rew;
-        const float rot = atan2f(gdy, gdx);    // x axis: next robot position -> goal (:22)
-        float* s = lds + 8 * a;
-        s[0] = ax; s[1] = ay; s[2] = nrx; s[3] = nry; s[4] = cosf(rot); s[5] = sinf(rot); s[6] = dg;
+        const LaStep st = la_step(rb, ax, ay, dt);
+        rewards[(long)w * A + a] = la_reward(curw, n, cc, rb, ax, ay, dt, st.dg);
+        float* s = lds + LA_FRAME_FLOATS * a;
+        s[0] = ax; s[1] = ay; s[2] = st.nrx; s[3] = st.nry; s[6] = st.dg;
+        la_frame(st, s[4], s[5]);
     }
     __syncthreads();
     float* outw = rotated + (long)w * A * n * oc;
     for (int idx = threadIdx.x; idx < A * n; idx += blockDim.x) {
         const int a = idx / n, j = idx - a * n;
-        const float* s = lds + 8 * a;
-        const float ax = s[0], ay = s[1], nrx = s[2], nry = s[3], cr = s[4], sr = s[5];
+        const float* s = lds + LA_FRAME_FLOATS * a;
         const float* q = nxtw + (long)j * nc;
-        const float hx = q[0] - nrx, hy = q[1] - nry;
-        const float hvx = headed ? q[3] : q[2], hvy = headed ? q[4] : q[3];
         const float hr = curw[(long)j * cc + 4];
+        const float4 c0 = la_row_quad<0>(s, q, hr, rvd, rr, headed), c1 = la_row_quad<1>(s, q, hr, rvd, rr, headed);
+        const float4 c2 = la_row_quad<2>(s, q, hr, rvd, rr, headed), c3 = la_row_quad<3>(s, q, hr, rvd, rr, headed);
         float* o = outw + (long)idx * oc;
-        o[0] = s[6]; o[1] = rvd; o[2] = 0.0f; o[3] = rr;
-        o[4] = ax * cr + ay * sr; o[5] = ay * cr - ax * sr;
-        o[6] = hx * cr + hy * sr; o[7] = hy * cr - hx * sr;
-        o[8] = hvx * cr + hvy * sr; o[9] = hvy * cr - hvx * sr;
-        o[10] = hr; o[11] = sqrtf(hx * hx + hy * hy); o[12] = rr + hr;
-        if (headed) { o[13] = q[2] - 0.0f; o[14] = q[5]; }
+        o[0] = c0.x; o[1] = c0.y; o[2] = c0.z; o[3] = c0.w;
+        o[4] = c1.x; o[5] = c1.y; o[6] = c1.z; o[7] = c1.w;
+        o[8] = c2.x; o[9] = c2.y; o[10] = c2.z; o[11] = c2.w;
+        o[12] = c3.x;
+        if (headed) { o[13] = c3.y; o[14] = c3.z; }
     }
 }
 

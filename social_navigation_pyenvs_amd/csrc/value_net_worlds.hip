@@ -1,0 +1,134 @@
+// value_net_worlds.hip -- the value-network decision of value_net.hip with its input rows generated inside the kernel: CADRL and SARL decide
+// for W worlds from the resident rows, and the look-ahead tensor rotated [W][A][n][13|15] (an A-fold expansion of the ~1 KB a world's
+// look-ahead reads: 431 MB at 4096 worlds x 81 actions x 25 humans) is never written.  Replaces cs_lookahead + cs_value_net_decide, whose
+// results it reproduces bit for bit.
+//
+// The kernel is value_net.hip's (value_net_body.inc: the same groups, tiles, workgroups, layers and reductions) with another tile loader.
+// Once per job, lane k of wavefront 0 computes the frame of the job's group k -- world g / A, action g % A: a job of 32 groups crosses
+// worlds, so world and action are per group -- and lane k of wavefront 1 its reward (the swept collision loop over the humans), into a
+// table of 32 x 8 floats behind the LDS map; the job's first barrier publishes both.  A tile is then written by one lane per (row, four
+// columns): wavefront Q writes columns [4 Q, 4 Q + 4) of row r = lane with one ds_write_b128 (rows are 80 bytes apart), zero beyond the
+// rows and the columns as load_tile pads.  A group in chunks (n > 32) regenerates the rows of a chunk at each of SARL's three passes
+// (human ch * 32 + r); its frame is computed once.  The arithmetic of frame, row and reward is lookahead_math.h's, shared with
+// k_lookahead, so the rows are cs_lookahead's to the last bit.  HBM traffic: the worlds' rows, the weight blob, one float per group (two
+// with d_rewards_out).  No atomics.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "lookahead_math.h"
+#include "value_net_f32.h"
+
+namespace {
+
+struct WorldRows {
+    const float* __restrict__ actions;
+    const float* __restrict__ next;        // [W][n][4 | 6]
+    const float* __restrict__ cur;         // [W][n][5 | 7]
+    const float* __restrict__ robot;
+    float* __restrict__ rewards_out;       // [W][A] or null
+    float* frames;                         // LDS [JROWS][LA_FRAME_FLOATS]: ax, ay, nrx, nry, cos, sin, dg, reward of the job's groups
+    int rstride, headed, A, n;
+};
+
+__device__ __forceinline__ void begin_job(const WorldRows& s, int gbase, int ng, float dt)
+{
+    const int wave = threadIdx.x >> 6, k = threadIdx.x & 63;
+    if (wave > 1 || k >= ng) return;
+    const int g = gbase + k, w = g / s.A, a = g - w * s.A;
+    const float* rb = s.robot + (long)w * s.rstride;
+    const float ax = s.actions[2 * a], ay = s.actions[2 * a + 1];
+    const LaStep st = la_step(rb, ax, ay, dt);
+    float* f = s.frames + LA_FRAME_FLOATS * k;
+    if (wave == 0) {
+        f[0] = ax; f[1] = ay; f[2] = st.nrx; f[3] = st.nry; f[6] = st.dg;
+        la_frame(st, f[4], f[5]);
+    } else {
+        const int cc = s.headed ? 7 : 5;
+        const float rew = la_reward(s.cur + (long)w * s.n * cc, s.n, cc, rb, ax, ay, dt, st.dg);
+        f[7] = rew;
+        if (s.rewards_out) s.rewards_out[g] = rew;
+    }
+}
+
+// columns [4 Q, 4 Q + 4) of the tile's rows: row r belongs to the tile's group r / per (the job's group t0 + r / per, the launch's g0 + r / per)
+// and is its human ch * M + r % per
+template <int Q>
+__device__ __forceinline__ void generate_quad(const WorldRows& s, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
+{
+    const int r = threadIdx.x & 63;
+    if (r >= M) return;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (r < rows) {
+        const int k = r / per, j = ch * M + r - k * per;
+        const int w = (g0 + k) / s.A;
+        const float* rb = s.robot + (long)w * s.rstride;
+        const float* q = s.next + ((long)w * s.n + j) * (s.headed ? 6 : 4);
+        const float hr = s.cur[((long)w * s.n + j) * (s.headed ? 7 : 5) + 4];
+        v = la_row_quad<Q>(s.frames + LA_FRAME_FLOATS * (t0 + k), q, hr, rb[7], rb[4], s.headed != 0);
+    }
+    *reinterpret_cast<float4*>(b.X0 + r * LDX + 4 * Q) = v;
+    if (Q == 0) b.grp[r] = r < rows ? r / per : 0;
+}
+
+__device__ __forceinline__ void generate_tile(const WorldRows& s, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
+{
+    switch (threadIdx.x >> 6) {
+    case 0: generate_quad<0>(s, b, t0, g0, ch, rows, per, M); break;
+    case 1: generate_quad<1>(s, b, t0, g0, ch, rows, per, M); break;
+    case 2: generate_quad<2>(s, b, t0, g0, ch, rows, per, M); break;
+    default: generate_quad<3>(s, b, t0, g0, ch, rows, per, M); break;
+    }
+}
+
+// `frames`: floats from the start of the dynamic block to the frame table, behind the map m that the other two kernels share
+__global__ __launch_bounds__(NT) void k_value_net_worlds(VnPlan p, VnLds m, int frames, int M, const float* __restrict__ wb, int NG, int A, int n,
+                                                         int headed, const float* __restrict__ actions, const float* __restrict__ next,
+                                                         const float* __restrict__ cur, const float* __restrict__ robot, int rstride, float gamma,
+                                                         float dt, float* __restrict__ rewards_out, float* __restrict__ values)
+{
+    extern __shared__ float lds[];
+    const WorldRows world{actions, next, cur, robot, rewards_out, lds + frames, rstride, headed, A, n};
+#define VN_BEGIN_JOB(gbase, ng) begin_job(world, gbase, ng, dt)
+#define VN_TILE_SOURCE(g0) const int tile_g0 = (g0)
+#define VN_LOAD_TILE(ch, rows, per) generate_tile(world, b, t0, tile_g0, ch, rows, per, M)
+#define VN_REWARD(g, k) world.frames[LA_FRAME_FLOATS * (k) + 7]
+#include "value_net_body.inc"
+#undef VN_BEGIN_JOB
+#undef VN_TILE_SOURCE
+#undef VN_LOAD_TILE
+#undef VN_REWARD
+}
+
+} // namespace
+
+#include "value_net_pick.h"
+
+extern "C" int cs_value_net_decide_worlds(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                                          int theta_and_omega_visible, const float* d_actions, const float* d_next, const float* d_current,
+                                          const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
+                                          float* d_rewards_out, float* d_values, int32_t* d_choice, float* d_action_out, void* stream)
+{
+    VnPlan p;
+    const int rc = build_plan(kind, dims, n_dims, theta_and_omega_visible ? 15 : 13, p);
+    if (rc != CS_OK) return rc;
+    // (the worlds' two arrays stand where cs_value_net_decide has cs_lookahead's two outputs: cs_lookahead's own checks are among these)
+    const int rc2 = check_decide_args(p, d_weights, n_weight_floats, W, A, n, d_next, d_current, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    if (rc2 != CS_OK) return rc2;
+    const int M = TILE_M;
+    const VnLds m = lds_map(p, M, n);
+    const int frames = m.total;
+    const size_t shmem = (size_t)(frames + JROWS * LA_FRAME_FLOATS) * sizeof(float);
+    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    if (shmem > 64 * 1024) VN_GRANT_LDS(k_value_net_worlds, shmem);
+    const int NG = W * A;
+    const int jobs = (NG + JROWS - 1) / JROWS;
+    const int grid = jobs < 4096 ? jobs : 4096;
+    hipLaunchKernelGGL(k_value_net_worlds, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, p, m, frames, M, d_weights, NG, A, n,
+                       theta_and_omega_visible ? 1 : 0, d_actions, d_next, d_current, d_robot, robot_stride, gamma, dt, d_rewards_out, d_values);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
+                       d_override, d_choice, d_action_out);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}

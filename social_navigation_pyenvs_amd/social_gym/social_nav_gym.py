@@ -716,7 +716,8 @@ class BatchedSocialNavGym:
 
         A ``crowd_nav.policy`` CADRL / SARL instance decides with its value network instead: cs_peek (or the constant-velocity model
         when the policy's ``query_env`` is false) -> cs_lookahead -> cs_value_net_decide (cs_value_net_decide_bf16 after the policy's
-        ``set_decision_precision("bf16")``), all on ``device_stream()``.  ``explore``: an
+        ``set_decision_precision("bf16")``), all on ``device_stream()``; after the policy's ``set_decision_input("fused")``, cs_peek ->
+        cs_value_net_decide_worlds, which generates the look-ahead rows in the kernel and allocates no look-ahead tensor.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
         values and choices of that decision stay readable through ``last_values_device()``."""
         import torch
@@ -808,11 +809,19 @@ class BatchedSocialNavGym:
                 o, T = self.observe_device(), self.robot_time_step
                 nxt = (torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 5] + o[..., 6] * T, o[..., 2], o[..., 3], o[..., 6]], -1)
                        if self.headed_obs else torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 2], o[..., 3]], -1)).contiguous()
-            rot, rew, rob = self._lookahead_on_side_stream(dl, acts, next_humans=nxt, with_robot=True)
-            value_net.decide(net, W, A, self.n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], pol.gamma,
-                             self.robot_time_step, None if explore is None else explore.data_ptr(), dl["vn_values"].data_ptr(),
-                             dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream, precision=pol.decision_precision)
-            for t in (rot, rew, rob) + (() if explore is None else (explore,)) + (() if nxt is None else (nxt,)):
+            if pol.decision_input == "fused":        # one library call on the worlds' own rows: no rot / rew
+                nxt_, cur_, rob = self._worlds_on_side_stream(dl, nxt)
+                value_net.decide_worlds(net, W, A, self.n, self.headed_obs, acts.data_ptr(), nxt_.data_ptr(), cur_.data_ptr(), rob.data_ptr(),
+                                        rob.shape[1], pol.gamma, self.robot_time_step, None if explore is None else explore.data_ptr(), None,
+                                        dl["vn_values"].data_ptr(), dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream)
+                used = (nxt_, cur_, rob)
+            else:
+                rot, rew, rob = self._lookahead_on_side_stream(dl, acts, next_humans=nxt, with_robot=True)
+                value_net.decide(net, W, A, self.n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], pol.gamma,
+                                 self.robot_time_step, None if explore is None else explore.data_ptr(), dl["vn_values"].data_ptr(),
+                                 dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream, precision=pol.decision_precision)
+                used = (rot, rew, rob) + (() if nxt is None else (nxt,))
+            for t in used + (() if explore is None else (explore,)):
                 t.record_stream(side)
         self._stream_handshake(dl, cur, False)
         return dl["act"]
@@ -856,6 +865,24 @@ class BatchedSocialNavGym:
                                dtype=torch.float32, device="cuda").contiguous()
         A = acts.shape[0]
         lib = _lib.load()
+        nxt, cur, rob = self._worlds_on_side_stream(dl, next_humans)
+        rot = torch.empty((W, A, n, 15 if self.headed_obs else 13), dtype=torch.float32, device="cuda")
+        rew = torch.empty((W, A), dtype=torch.float32, device="cuda")
+        _lib.check(lib.cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(self.headed_obs)), C.c_void_p(acts.data_ptr()),
+                                    C.c_void_p(nxt.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(rob.data_ptr()), C.c_int(9),
+                                    C.c_float(self.robot_time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()),
+                                    C.c_void_p(cw.stream)))
+        return (rot, rew, rob) if with_robot else (rot, rew)
+
+    def _worlds_on_side_stream(self, dl, next_humans=None):
+        """What a look-ahead reads of the resident worlds, as contiguous CUDA tensors: (next humans [W, n, 4 | 6] -- cs_peek's, or the caller's
+        --, current humans [W, n, 5 | 7], robot rows [W, 9] in FullState order)."""
+        import ctypes as C
+
+        import torch
+
+        cw, W, n = self.cw, self.W, self.n
+        lib = _lib.load()
         d = cw.descriptor(respawn=False)
         peek = cw._buffer("peek", (W, n, 8))
         if next_humans is None:
@@ -868,13 +895,7 @@ class BatchedSocialNavGym:
         nxt = peek.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous() if next_humans is None else next_humans
         cur = dl["state"][:, :n].index_select(2, dl["cols"]).contiguous()
         rob = dl["la_robot"].index_select(1, dl["la_robot_cols"]).contiguous()
-        rot = torch.empty((W, A, n, 15 if self.headed_obs else 13), dtype=torch.float32, device="cuda")
-        rew = torch.empty((W, A), dtype=torch.float32, device="cuda")
-        _lib.check(lib.cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(self.headed_obs)), C.c_void_p(acts.data_ptr()),
-                                    C.c_void_p(nxt.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(rob.data_ptr()), C.c_int(9),
-                                    C.c_float(self.robot_time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()),
-                                    C.c_void_p(cw.stream)))
-        return (rot, rew, rob) if with_robot else (rot, rew)
+        return nxt, cur, rob
 
     # ------------------------------------------------------------------ imitation learning, W worlds at once
     def set_human_motion_model_as_robot_policy(self, policy_name, runge_kutta=False, safety_space=0.0):

@@ -1,0 +1,340 @@
+"""GPU suite of the value-network decision from the resident worlds (cs_value_net_decide_worlds, csrc/value_net_worlds.hip): the kernel that
+generates its input rows in LDS against cs_lookahead -> cs_value_net_decide on the same buffers, bit for bit; a world alone against the
+batch; the batched Gym with ``set_decision_input("fused")`` against ``"tensor"``; and the reference's recorded decisions (golden G16).
+
+Every comparison between the two paths is bitwise (np.array_equal on the float32 / int32 arrays) and every compared value is finite."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_gpu_value_policy import REL_BAR, _batched, _calm, _compare, _ready
+from test_policy_seam import _groups
+from test_value_policy_cpu import fixture_state_dict, make_policy, seeded_weights
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+GAMMA, DT, STRIDE = 0.9, 0.25, 9
+HEADED = dict(sarl__with_theta_and_omega_visible="true")
+NETS = {
+    "cadrl": ("cadrl", {}),
+    "sarl": ("sarl", {}),
+    "sarl-local": ("sarl", dict(sarl__with_global_state="false")),
+    # the two non-default width sets of test_gpu_value_policy.VARIANTS
+    "cadrl-narrow": ("cadrl", dict(cadrl__mlp_dims="64, 37, 1")),
+    "sarl-odd": ("sarl", dict(sarl__mlp1_dims="40, 72", sarl__mlp2_dims="33", sarl__attention_dims="20, 1", sarl__mlp3_dims="90, 1")),
+}
+
+
+def _actions(A):
+    """The first A actions of CADRL's set for v_pref 1: (0, 0), then five speeds along each heading (the first heading is +x)"""
+    from social_navigation_pyenvs_amd.crowd_nav.policy.cadrl import build_action_space_array
+
+    return np.ascontiguousarray(build_action_space_array(1.0)[:A], F32)
+
+
+def worlds(W, n, A, headed, seed, on_goal=False):
+    """Synthetic worlds as cs_lookahead takes them: (actions [A, 2], next [W, n, 4 | 6], current [W, n, 5 | 7], robot [W, 9]) float32.
+    Humans lie 2 - 5 m from their robot (no action of one 0.25 s step comes within the discomfort distance), except where a world is
+    arranged for a reward branch (its first human; the world's index modulo 4 when the batch has that many worlds):
+      world 0   a standing human 0.05 m beyond touching, in +x: discomfort for the actions that stay (0 < dmin < 0.2), collision for the
+                faster actions towards it
+      world 1   nothing near: reward 0
+      world 2   the goal where action min(3, A - 1) ends: reward 1 for it
+      world 3   a human overlapping the robot: collision for every action (the only way to one with A = 1)
+    on_goal: every robot stands on its goal (the pick writes (0, 0))."""
+    rng = np.random.default_rng(seed)
+    acts = _actions(A)
+    rob = np.zeros((W, STRIDE), F32)
+    rob[:, 0:2] = rng.uniform(-2, 2, (W, 2))
+    rob[:, 2:4] = rng.uniform(-1, 1, (W, 2))
+    rob[:, 4] = 0.3
+    rob[:, 5:7] = rob[:, 0:2] + rng.uniform(3, 6, (W, 2)) * rng.choice([-1.0, 1.0], (W, 2))
+    rob[:, 7] = rng.uniform(0.5, 1.5, W)
+    rob[:, 8] = rng.uniform(-3, 3, W)
+    cur = np.zeros((W, n, 7 if headed else 5), F32)
+    ang, dist = rng.uniform(0, 2 * np.pi, (W, n)), rng.uniform(2, 5, (W, n))
+    cur[..., 0] = rob[:, None, 0] + dist * np.cos(ang)
+    cur[..., 1] = rob[:, None, 1] + dist * np.sin(ang)
+    cur[..., 2:4] = rng.uniform(-1, 1, (W, n, 2))
+    cur[..., 4] = rng.uniform(0.2, 0.4, (W, n))
+    if headed:
+        cur[..., 5] = rng.uniform(-3, 3, (W, n))
+        cur[..., 6] = rng.uniform(-1, 1, (W, n))
+    for w in range(W):
+        if w % 4 == 0:
+            cur[w, 0, :5] = [rob[w, 0] + 0.65, rob[w, 1], 0.0, 0.0, 0.3]
+        elif w % 4 == 2:
+            rob[w, 5:7] = rob[w, 0:2] + acts[min(3, A - 1)] * F32(DT)
+        elif w % 4 == 3:
+            cur[w, 0, :5] = [rob[w, 0] + 0.5, rob[w, 1], 0.0, 0.0, 0.3]
+    if on_goal:
+        rob[:, 5:7] = rob[:, 0:2]
+    nxt = np.zeros((W, n, 6 if headed else 4), F32)
+    nxt[..., 0:2] = cur[..., 0:2] + cur[..., 2:4] * F32(DT)
+    if headed:
+        nxt[..., 2] = cur[..., 5] + cur[..., 6] * F32(DT)
+        nxt[..., 3:5], nxt[..., 5] = cur[..., 2:4], cur[..., 6]
+    else:
+        nxt[..., 2:4] = cur[..., 2:4]
+    return acts, nxt, cur, rob
+
+
+@pytest.fixture(scope="module")
+def nets():
+    """(net name, headed) -> (policy, DeviceNet), built once: seeded weights, SARL's attention calmed so that no value overflows"""
+    made = {}
+
+    def get(net, headed=False):
+        if (net, headed) not in made:
+            name, overrides = NETS[net]
+            pol = _ready(make_policy(name, **overrides, **(HEADED if headed else {})))
+            seeded_weights(pol.model, 2300 + 2 * sorted(NETS).index(net) + int(headed))
+            if name == "sarl":
+                _calm(pol)
+            made[net, headed] = (pol, pol.device_net())
+        return made[net, headed]
+
+    return get
+
+
+def _up(a, dtype=None):
+    import torch
+
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
+
+
+def _outputs(W, A):
+    import torch
+
+    return (torch.full((W, A), np.nan, device="cuda"), torch.full((W,), -7, dtype=torch.int32, device="cuda"), torch.full((W, 2), np.nan, device="cuda"))
+
+
+def decide_fused(net, case, override=None, rewards=True):
+    """cs_value_net_decide_worlds on a case of worlds(): (rewards [W, A] or None, values [W, A], choice [W], action [W, 2]) as numpy"""
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    acts, nxt, cur, rob = (_up(x) for x in case)
+    W, n, A, headed = cur.shape[0], cur.shape[1], acts.shape[0], cur.shape[2] == 7
+    vals, pick, act = _outputs(W, A)
+    rew = torch.full((W, A), np.nan, device="cuda") if rewards else None
+    ovr = None if override is None else _up(override, torch.int32)
+    value_net.decide_worlds(net, W, A, n, headed, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), rob.data_ptr(), STRIDE, GAMMA, DT,
+                            None if ovr is None else ovr.data_ptr(), None if rew is None else rew.data_ptr(), vals.data_ptr(), pick.data_ptr(),
+                            act.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return (None if rew is None else rew.cpu().numpy(), vals.cpu().numpy(), pick.cpu().numpy(), act.cpu().numpy())
+
+
+def decide_tensor(net, case, override=None):
+    """cs_lookahead -> cs_value_net_decide on the same case: (rewards, values, choice, action) as numpy"""
+    import torch
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    acts, nxt, cur, rob = (_up(x) for x in case)
+    W, n, A, headed = cur.shape[0], cur.shape[1], acts.shape[0], cur.shape[2] == 7
+    rot = torch.full((W, A, n, 15 if headed else 13), np.nan, device="cuda")
+    rew = torch.full((W, A), np.nan, device="cuda")
+    vals, pick, act = _outputs(W, A)
+    ovr = None if override is None else _up(override, torch.int32)
+    stream = torch.cuda.current_stream().cuda_stream
+    P = C.c_void_p
+    _lib.check(_lib.load().cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(headed)), P(acts.data_ptr()), P(nxt.data_ptr()),
+                                        P(cur.data_ptr()), P(rob.data_ptr()), C.c_int(STRIDE), C.c_float(DT), P(rot.data_ptr()), P(rew.data_ptr()), P(stream)))
+    value_net.decide(net, W, A, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), STRIDE, GAMMA, DT,
+                     None if ovr is None else ovr.data_ptr(), vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+    torch.cuda.synchronize()
+    return rew.cpu().numpy(), vals.cpu().numpy(), pick.cpu().numpy(), act.cpu().numpy()
+
+
+def assert_same_bits(got, want, label):
+    for name, g, w in zip(("rewards", "values", "choice", "action"), got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape, (label, name)
+        assert np.all(np.isfinite(w)) and np.all(np.isfinite(g)), (label, name)
+        assert np.array_equal(g.view(np.int32), w.view(np.int32)), (label, name, int(np.sum(g != w)), g.size)
+
+
+def reward_branches(rew):
+    """Which of the four rewards of cadrl.py:69-72 occur in [W, A] rewards computed with dt = DT"""
+    discomfort = (rew < 0) & (rew > -0.2 * 0.5 * DT - 1e-6) & (rew != F32(-0.25))
+    return {"collision": bool(np.any(rew == F32(-0.25))), "goal": bool(np.any(rew == 1.0)), "discomfort": bool(np.any(discomfort)),
+            "none": bool(np.any(rew == 0.0))}
+
+
+# n: whole groups in a tile (1, 5), groups that leave a tile partly empty (25, 31), one full tile (32), chunks (33: 32 + 1; 70: 32 + 32 + 6), with
+# W * A = 243 groups -- eight jobs, the last of 19 groups, tiles and jobs that straddle worlds; A = 7 with n = 5: six groups a tile cross a
+# world in every tile; W * A of 1, 31, 32, 33 around one job
+CASES = ([(net, W, A, n, False) for n in (1, 5, 25, 31, 32, 33, 70) for net, W, A in (("cadrl", 3, 81), ("sarl", 3, 81), ("sarl-local", 3, 81))]
+         + [(net, 5, 7, 5, False) for net in ("cadrl", "sarl")]
+         + [(net, W, A, 5, False) for W, A in ((1, 1), (31, 1), (1, 32), (3, 11)) for net in ("cadrl", "sarl")]
+         + [(net, 3, 81, n, True) for n in (5, 33) for net in ("cadrl", "sarl")]
+         + [("cadrl-narrow", 3, 81, 5, False), ("sarl-odd", 3, 81, 25, False), ("sarl-odd", 3, 81, 33, False)])
+
+
+@pytest.mark.parametrize("net,W,A,n,headed", CASES)
+def test_fused_equals_lookahead_then_decide(nets, net, W, A, n, headed):
+    """rewards_out, values, choice and action_out of cs_value_net_decide_worlds are those of cs_lookahead -> cs_value_net_decide, bit for
+    bit.  With three or more worlds the inputs hold all four reward branches (asserted): a wrong reward cannot hide behind a zero."""
+    _, dnet = nets(net, headed)
+    case = worlds(W, n, A, headed, seed=1000 * n + 10 * W + A)
+    want = decide_tensor(dnet, case)
+    got = decide_fused(dnet, case)
+    label = f"{net} W={W} A={A} n={n}{' headed' if headed else ''}"
+    assert_same_bits(got, want, label)
+    if W >= 4 or (W >= 3 and A >= 7):
+        assert all(reward_branches(want[0]).values()), (label, reward_branches(want[0]))
+    # without d_rewards_out: the same decision
+    assert_same_bits(decide_fused(dnet, case, rewards=False)[1:], want[1:], label + " (no rewards_out)")
+
+
+def test_fused_with_an_override_column_and_robots_on_their_goal(nets):
+    """A forced action per world (and -1 = greedy, and an index outside the action set = greedy) and robots standing on their goal: choice
+    and action_out follow cs_value_net_decide's pick, the goal reward is everywhere."""
+    _, dnet = nets("sarl")
+    W, A, n = 6, 81, 5
+    override = np.array([5, -1, 80, 81, 0, 17], np.int32)
+    for on_goal in (False, True):
+        case = worlds(W, n, A, False, seed=77, on_goal=on_goal)
+        want = decide_tensor(dnet, case, override)
+        got = decide_fused(dnet, case, override)
+        assert_same_bits(got, want, f"override on_goal={on_goal}")
+        assert got[2][[0, 2, 4, 5]].tolist() == [5, 80, 0, 17]
+        if on_goal:
+            assert not got[3].any() and np.all((got[0] == 1.0) | (got[0] == F32(-0.25)))
+        else:
+            rob = case[3]
+            there = np.hypot(rob[:, 0] - rob[:, 5], rob[:, 1] - rob[:, 6]) < rob[:, 4]          # (world 2 was put one action from its goal)
+            assert there.tolist() == [False, False, True, False, False, False]
+            np.testing.assert_array_equal(got[3], np.where(there[:, None], F32(0), case[0][got[2]]))
+            assert all(reward_branches(got[0]).values())
+
+
+@pytest.mark.parametrize("net", ["cadrl", "sarl"])
+@pytest.mark.parametrize("n", [5, 33])
+def test_a_world_alone_equals_the_batch(nets, net, n):
+    """Rows 0, 1 and W - 1 of a W = 64 fused call equal three W = 1 fused calls: a (world, action) has the same bits wherever its rows fall
+    in a tile or a job."""
+    _, dnet = nets(net)
+    W = 64
+    case = worlds(W, n, 81, False, seed=500 + n)
+    batch = decide_fused(dnet, case)
+    assert all(np.all(np.isfinite(x)) for x in batch)
+    assert all(reward_branches(batch[0]).values())
+    acts, nxt, cur, rob = case
+    for w in (0, 1, W - 1):
+        alone = decide_fused(dnet, (acts, nxt[w:w + 1], cur[w:w + 1], rob[w:w + 1]))
+        assert_same_bits(alone, tuple(x[w:w + 1] for x in batch), f"{net} n={n} world {w}")
+
+
+@pytest.mark.parametrize("name,query_env", [("cadrl", True), ("cadrl", False), ("sarl", True), ("sarl", False)])
+def test_the_env_decides_the_same_with_either_input(name, query_env):
+    """64 resident worlds, five act -> step rounds: act_device with ``set_decision_input("fused")`` leaves the actions, values and choices of
+    ``"tensor"`` on the same worlds.  A fused decision allocates less than one look-ahead tensor (W * A * n * cols * 4 bytes, derived) --
+    and the tensor path, measured the same way, does allocate it."""
+    import torch
+
+    env = _batched(5, W=64)
+    pol = _ready(make_policy(name, action_space__query_env=str(query_env).lower()), env)
+    seeded_weights(pol.model, 2400)
+    if name == "sarl":
+        _calm(pol)
+    assert pol.decision_input == "tensor"
+    rot_bytes = env.W * 81 * env.n * 13 * 4
+
+    def decide(how):
+        pol.set_decision_input(how)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        act = env.act_device(pol)
+        assert act is env.action_buffer()
+        torch.cuda.synchronize()
+        grown = torch.cuda.max_memory_allocated() - before
+        values, choice = env.last_values_device()
+        return act.cpu().numpy().copy(), values.cpu().numpy().copy(), choice.cpu().numpy().copy(), grown
+
+    for k in range(5):
+        a_t, v_t, c_t, grown_t = decide("tensor")
+        a_f, v_f, c_f, grown_f = decide("fused")
+        assert np.all(np.isfinite(v_t)) and np.all(np.isfinite(v_f)) and np.all(np.isfinite(a_f))
+        assert np.array_equal(v_f.view(np.int32), v_t.view(np.int32)), (k, int(np.sum(v_f != v_t)))
+        assert np.array_equal(c_f, c_t) and np.array_equal(a_f.view(np.int32), a_t.view(np.int32)), k
+        print(f"{name} query_env={query_env} round {k}: a decision allocates {grown_t} bytes (tensor), {grown_f} bytes (fused); rot is {rot_bytes}")
+        if k > 0:                       # (the first round also allocates what stays: the values and choices of last_values_device)
+            assert grown_f < rot_bytes <= grown_t, (k, grown_f, grown_t, rot_bytes)
+        env.step_device(env.action_buffer())
+    env.close()
+
+
+class _Recorded:
+    """What predict() asks its env for: the reference's own peeked next states of one recorded decision"""
+
+    def __init__(self, nxt):
+        self.motion_model_manager = self
+        self._nxt = np.asarray(nxt, np.float64)
+
+    def get_next_human_observable_states(self, dt, theta_and_omega_visible=False):
+        return self._nxt
+
+
+def test_g16_through_predict_with_the_fused_input():
+    """The reference's 135 recorded decisions (golden G16), each through the W = 1 ``predict`` with ``set_decision_input("fused")``: the
+    reference's action 135 / 135, every action value within 1e-4 (relative; test_gpu_value_policy._compare and its bar) of the recorded
+    ones -- the fused path on the reference itself, not only on its sibling."""
+    from social_navigation_pyenvs_amd.crowd_nav.utils.state import FullState, JointState, ObservableState
+
+    groups, w = _groups()
+    total = same = 0
+    worst = 0.0
+    for key, cs in groups.items():
+        c0 = cs[0]
+        pol = _ready(make_policy(str(c0["policy"])))
+        pol.model.load_state_dict(fixture_state_dict(w[key]), strict=True)
+        pol.gamma, pol.time_step, pol.query_env = float(c0["gamma"]), float(c0["dt"]), True
+        pol.build_action_space(float(c0["robot"][7]))
+        np.testing.assert_allclose(pol.action_space_ndarray, c0["action_space"], atol=1e-12)
+        pol.set_decision_input("fused")
+        values, choice = [], []
+        for c in cs:
+            state = JointState(FullState(*[float(x) for x in c["robot"]]), [ObservableState(*[float(x) for x in h]) for h in c["obs"]])
+            pol.set_env(_Recorded(c["next_humans"]))
+            a = pol.predict(state)
+            values.append(np.asarray(pol.action_values, np.float64))
+            choice.append(int(np.argmax(np.asarray(pol.action_values, np.float32))))
+            assert (F32(a.vx), F32(a.vy)) == tuple(pol.action_space_ndarray.astype(F32)[choice[-1]])
+            assert choice[-1] == int(c["chosen"]), (key, c["test_case"], c["step"])
+        ref = np.stack([np.asarray(c["action_values"], np.float64) for c in cs])
+        wv, s, t = _compare(np.stack(values), np.array(choice), ref, f"G16 fused predict {key}", need_all=True)
+        worst, same, total = max(worst, wv), same + s, total + t
+    print(f"G16 through predict, fused input: {same}/{total} decisions with the reference's action, worst relative action-value error {worst:.3e}")
+    assert total == 135 and same == total, (same, total)
+    assert worst < REL_BAR, worst
+
+
+def test_predict_and_attention_weights_with_either_input():
+    """The W = 1 ``predict`` of a SARL on one synthetic world: the action and the 81 action values of "fused" are those of "tensor", bit for
+    bit, and ``get_attention_weights`` -- the torch forward on the last action's rows, which a fused decision never wrote and generates on
+    demand -- returns the same weights."""
+    from social_navigation_pyenvs_amd.crowd_nav.utils.state import FullState, JointState, ObservableState
+
+    pol = _ready(make_policy("sarl"))
+    seeded_weights(pol.model, 2500)
+    _calm(pol)
+    pol.time_step, pol.query_env = DT, True
+    pol.build_action_space(1.0)
+    _, nxt, cur, rob = worlds(2, 7, 81, False, seed=9)
+    state = JointState(FullState(*[float(x) for x in rob[1]]), [ObservableState(*[float(x) for x in h]) for h in cur[1]])
+    pol.set_env(_Recorded(nxt[1]))
+    got = {}
+    for how in ("tensor", "fused"):
+        pol.set_decision_input(how)
+        a = pol.predict(state)
+        got[how] = (np.array([a.vx, a.vy], F32), np.asarray(pol.action_values, F32), np.asarray(pol.get_attention_weights(), F32).copy())
+        assert all(np.all(np.isfinite(x)) for x in got[how]) and got[how][2].shape == (7,) and abs(float(got[how][2].sum()) - 1.0) < 1e-5
+    for t, f in zip(got["tensor"], got["fused"]):
+        assert np.array_equal(t.view(np.int32), f.view(np.int32))
