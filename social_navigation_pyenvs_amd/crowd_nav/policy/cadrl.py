@@ -230,20 +230,9 @@ class CADRL(Policy):
             return np.asarray(manager.get_next_human_observable_states(self.time_step, theta_and_omega_visible=True))[:, :6]
         return np.asarray(manager.get_next_human_observable_states(self.time_step))
 
-    def _lookahead_rows(self, d_a, d_n, d_c, d_r, headed):
-        """cs_lookahead for this one robot on the current stream: CUDA tensors (rotated [1, A, n, 13 | 15], rewards [1, A])."""
-        A, n = d_a.shape[0], d_c.shape[0]
-        rot = torch.empty((1, A, n, 15 if headed else 13), dtype=torch.float32, device="cuda")
-        rew = torch.empty((1, A), dtype=torch.float32, device="cuda")
-        check(_lib.load().cs_lookahead(C.c_int(1), C.c_int(n), C.c_int(A), C.c_int(int(headed)), C.c_void_p(d_a.data_ptr()),
-                                       C.c_void_p(d_n.data_ptr()), C.c_void_p(d_c.data_ptr()), C.c_void_p(d_r.data_ptr()), C.c_int(len(ROBOT_FIELDS)),
-                                       C.c_float(self.time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return rot, rew
-
     def _decide_one(self, state, override=-1):
-        """cs_lookahead + cs_value_net_decide for this one robot (W = 1), or cs_value_net_decide_worlds with ``decision_input`` "fused":
-        (action values [A], chosen index, ActionXY row float32)."""
+        """value_net.decide_for_worlds for this one robot (W = 1) on the current stream: (action values [A], chosen index, ActionXY row
+        float32)."""
         from . import value_net
 
         _lib.require_gpu()
@@ -256,21 +245,15 @@ class CADRL(Policy):
         nxt = self._next_humans(cur)
         net = self.device_net()
         up = lambda a, dtype=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-        d_a, d_n, d_c, d_r = self.device_action_space(), up(np.asarray(nxt, np.float32)), up(cur.astype(np.float32)), up(rows[:1, :len(ROBOT_FIELDS)])
-        fused = self.decision_input == "fused"        # (no look-ahead tensor: the kernel generates its rows)
-        rot, rew = (None, None) if fused else self._lookahead_rows(d_a, d_n, d_c, d_r, headed)
+        d_a, d_n, d_c, d_r = self.device_action_space(), up(np.asarray(nxt, np.float32))[None], up(cur.astype(np.float32))[None], up(rows[:1, :len(ROBOT_FIELDS)])
         vals = torch.empty((1, A), dtype=torch.float32, device="cuda")
         pick = torch.empty(1, dtype=torch.int32, device="cuda")
         act = torch.empty((1, 2), dtype=torch.float32, device="cuda")
-        ovr = up(np.array([override]), torch.int32)
-        stream = torch.cuda.current_stream().cuda_stream
-        if fused:
-            value_net.decide_worlds(net, 1, A, n, headed, d_a.data_ptr(), d_n.data_ptr(), d_c.data_ptr(), d_r.data_ptr(), len(ROBOT_FIELDS),
-                                    self.gamma, self.time_step, ovr.data_ptr(), None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
-        else:
-            value_net.decide(net, 1, A, n, rot.data_ptr(), rew.data_ptr(), d_a.data_ptr(), d_r.data_ptr(), len(ROBOT_FIELDS), self.gamma, self.time_step,
-                             ovr.data_ptr(), vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream, precision=self.decision_precision)
-        self._last_rotated = rot if not fused else (lambda: self._lookahead_rows(d_a[-1:].contiguous(), d_n, d_c, d_r, headed))
+        stream = lambda: torch.cuda.current_stream().cuda_stream
+        rot, _ = value_net.decide_for_worlds(net, self.decision_input, self.decision_precision, d_a, d_n, d_c, d_r, self.gamma, self.time_step,
+                                             up(np.array([override]), torch.int32), vals, pick, act, stream())
+        # (SARL's attention weights read the last action's rows; without the look-ahead tensor they are made when asked for)
+        self._last_rotated = rot if rot is not None else (lambda: value_net.lookahead(d_a[-1:].contiguous(), d_n, d_c, d_r, self.time_step, stream()))
         return vals[0].cpu().numpy(), int(pick.item()), act[0].cpu().numpy()
 
     def _require_ready(self):

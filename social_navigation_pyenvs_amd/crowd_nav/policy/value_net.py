@@ -1,7 +1,8 @@
 """The seam between the value-based policies (CADRL, SARL) and the fused decision kernel (cs_value_net_decide, csrc/value_net.hip).
 
 ``describe(policy)`` turns a policy's torch module into the kernel's layer description, ``DeviceNet`` keeps the packed weight blob on the
-GPU and repacks it only when a parameter changed (the tensors' version counters), ``decide`` is the one library call of a decision.
+GPU and repacks it only when a parameter changed (the tensors' version counters), ``decide`` is the one library call of a decision and
+``decide_for_worlds`` the whole sequence from the worlds' rows that CADRL's ``predict`` (W = 1) and the batched Gym's ``act_device`` share.
 There is no host implementation of the decision: without the library or a GPU these raise.
 
 Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_value_net_decide_bf16, csrc/value_net_bf16.hip) with its
@@ -142,3 +143,37 @@ def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, 
         C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
         C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(int(bool(headed))), P(actions), P(nxt), P(cur), P(robot), C.c_int(robot_stride),
         C.c_float(gamma), C.c_float(dt), P(override), P(rewards_out), P(values), P(choice), P(action_out), P(stream)))
+
+
+def lookahead(acts, nxt, cur, robot, dt, stream=None):
+    """cs_lookahead on CUDA tensors: actions [A, 2], next humans [W, n, 4 | 6], current humans [W, n, 5 | 7], robot rows [W, 8+] ->
+    (rotated [W, A, n, 13 | 15], rewards [W, A]), allocated here and written on `stream` (an int)."""
+    import torch
+
+    from ... import _lib
+
+    P = C.c_void_p
+    (W, n, cc), A = cur.shape, acts.shape[0]
+    rot = torch.empty((W, A, n, 15 if cc == 7 else 13), dtype=torch.float32, device="cuda")
+    rew = torch.empty((W, A), dtype=torch.float32, device="cuda")
+    _lib.check(_lib.load().cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(cc == 7)), P(acts.data_ptr()), P(nxt.data_ptr()),
+                                        P(cur.data_ptr()), P(robot.data_ptr()), C.c_int(robot.shape[1]), C.c_float(dt), P(rot.data_ptr()),
+                                        P(rew.data_ptr()), P(stream)))
+    return rot, rew
+
+
+def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None):
+    """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
+    values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
+    decide with `precision`.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
+    "fused"."""
+    (W, n, cc), A = cur.shape, acts.shape[0]
+    ovr = None if override is None else override.data_ptr()
+    if check_decision_input(decision_input, precision) == "fused":      # one library call on the worlds' own rows
+        decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
+                      None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return None, None
+    rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
+    decide(net, W, A, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr, values.data_ptr(),
+           choice.data_ptr(), action_out.data_ptr(), stream, precision=precision)
+    return rot, rew

@@ -21,8 +21,6 @@
 // tile.  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "value_net_f32.h"
 
 namespace {
@@ -32,6 +30,7 @@ __global__ __launch_bounds__(NT) void k_value_net(VnPlan p, VnLds m, int M, cons
                                                   const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
 {
     extern __shared__ float lds[];
+    const int gsum = m.G;
 #define VN_BEGIN_JOB(gbase, ng)
 #define VN_TILE_SOURCE(g0) const float* grows = rotated + (long)(g0) * n * cols
 #define VN_LOAD_TILE(ch, rows, per) load_tile(b, grows + (long)(ch) * M * cols, rows, cols, per, M)
@@ -50,15 +49,9 @@ __global__ __launch_bounds__(NT) void k_value_net(VnPlan p, VnLds m, int M, cons
 extern "C" int cs_value_net_pack(int kind, const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, p);
-    if (rc != CS_OK) return rc;
-    if (!n_floats) return fail(CS_ERR_ARG, "null argument");
-    *n_floats = (size_t)p.total_floats;
-    if (!blob) return CS_OK;
-    if (!params) return fail(CS_ERR_ARG, "null argument");
-    for (int l = 0; l < p.n_layers; ++l)
-        if (!params[2 * l] || !params[2 * l + 1]) return fail(CS_ERR_ARG, "null weight or bias array");
-    memset(blob, 0, (size_t)p.total_floats * sizeof(float));
+    bool fill;
+    const int rc = begin_pack(kind, dims, n_dims, cols, nullptr, 1, params, blob, n_floats, p, fill);
+    if (rc != CS_OK || !fill) return rc;
     for (int l = 0; l < p.n_layers; ++l)
         pack_layer_f32(p.L[l], params[2 * l], params[2 * l + 1], blob);
     return CS_OK;
@@ -74,21 +67,10 @@ extern "C" int cs_value_net_decide(int kind, const int32_t* dims, int n_dims, co
     if (rc != CS_OK) return rc;
     const int rc2 = check_decide_args(p, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;
-    const size_t lds_limit = 160 * 1024;
-    const int M = TILE_M;
-    const VnLds m = lds_map(p, M, n);
-    const size_t shmem = (size_t)m.total * sizeof(float);
-    // (cannot happen within the limits above -- 16 layers of up to 256 columns need about 150 KiB at most, at n = 2 -- kept as the guard of the launch)
-    if (shmem > lds_limit) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    if (shmem > 64 * 1024) VN_GRANT_LDS(k_value_net, shmem);
-    const int NG = W * A;
-    const int jobs = (NG + JROWS - 1) / JROWS;
-    const int grid = jobs < 4096 ? jobs : 4096;
-    hipLaunchKernelGGL(k_value_net, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, p, m, M, d_weights, NG, A, n, d_rotated, d_rewards, d_robot,
-                       robot_stride, gamma, dt, d_values);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
-                       d_override, d_choice, d_action_out);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
+    VnLaunch q;
+    const int rc3 = prepare_launch<k_value_net>(p, n, 0, W, A, q);
+    if (rc3 != CS_OK) return rc3;
+    hipLaunchKernelGGL(k_value_net, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)stream, p, q.m, TILE_M, d_weights, q.NG, A, n, d_rotated, d_rewards,
+                       d_robot, robot_stride, gamma, dt, d_values);
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }

@@ -1,6 +1,7 @@
 // value_net_bf16.hip -- the value-network decision of value_net.hip with the opt-in bf16 arithmetic (cs_value_net_decide_bf16; Python:
-// policy.set_decision_precision("bf16")).  Same groups, tiles and workgroups: a group is one (world, action), 32 groups per workgroup,
-// tiles of 32 rows, mlp3 once per workgroup as one 32-row block, no activation leaves the CU, the pick kernel follows.
+// policy.set_decision_precision("bf16")).  The kernel is value_net.hip's: the same body (value_net_body.inc: groups, tiles, workgroups, phases,
+// reductions) with the same copying loader; this file states the arithmetic the body runs on -- the bf16 layer, the chain of layers and the
+// handful of functions the body asks an arithmetic for -- the pack entry of its blob and the decide entry.  The pick kernel follows.
 //
 // The arithmetic:
 //   float32 layers   a layer whose input holds raw rotated-state columns: CADRL value_network layer 0, SARL mlp1 layer 0, all of mlp3.
@@ -24,8 +25,6 @@
 // modulo 16 at one column offset, and row * (16 * odd) bytes puts them on the 16 different 16-byte slots of the 256-byte bank row:
 // conflict-free (the float32 file's width + 4 floats does the same for 8 rows of its 32-byte k-groups).
 #include <hip/hip_runtime.h>
-
-#include <atomic>
 
 #include "value_net_plan.h"
 
@@ -78,8 +77,15 @@ inline uint16_t bf16_bits(float f)       // round to nearest even; a NaN becomes
     return (uint16_t)(u >> 16);
 }
 
-__device__ __forceinline__ float h2f(const float* buf, int ld, int r, int c) { return static_cast<float>(reinterpret_cast<const __bf16*>(buf)[r * 2 * ld + c]); }
 __device__ __forceinline__ void f2h(float* buf, int ld, int r, int c, float v) { reinterpret_cast<__bf16*>(buf)[r * 2 * ld + c] = static_cast<__bf16>(v); }
+
+// what value_net_body.inc asks of an arithmetic beside run_chain (below): M1 and G hold bfloat16 rows, the attention's k-steps of 16 read
+// m1pad columns of the mean, the running sum of a chunked mean is the float32 tail behind the LDS map, needed only with the global state
+__device__ __forceinline__ float vn_m1(const float* buf, int ld, int r, int c) { return static_cast<float>(reinterpret_cast<const __bf16*>(buf)[r * 2 * ld + c]); }
+__device__ __forceinline__ void vn_mean_store(float* buf, int ld, int k, int c, float v) { f2h(buf, ld, k, c, v); }
+__device__ __forceinline__ int vn_m1pad(const VnPlan& p) { return (p.m1w + 15) & ~15; }
+__device__ __forceinline__ int vn_sum_cols(const VnPlan&, int m1pad) { return m1pad; }
+__device__ __forceinline__ bool vn_mean_pass(const VnPlan& p) { return p.with_global != 0; }
 
 // One bf16 layer of a tile: layer_fwd's contract with bfloat16 rows in src / src2 (strides in floats) and the weights as
 // [ncb][k-steps][64 lanes][8 bf16]: lane l holds Wt[k = 16 s + 8 (l >> 5) + j][column 32 cb + (l & 31)], j = 0..7, of k-step s.
@@ -137,10 +143,6 @@ __device__ __forceinline__ void layer_fwd_h(const VnLayer& L, const float* __res
     }
 }
 
-struct VnBufs { float *X0, *M1, *P, *Q, *G, *Gf, *J, *sc, *den, *val; int* grp; };
-
-enum { CH_MLP1, CH_REDUCED, CH_MLP3, CH_CADRL };   // mlp1 (ends in M1); mlp2 / attention (bf16 in, float32 out); mlp3; CADRL's value_network
-
 // layers [first, last) from `src`; outputs alternate P, Q; the last one goes to final_dst when given.  Returns where the result is.
 // The chain's kind fixes which arithmetic a layer may take, so that a call site carries only those.
 template <int CH>
@@ -176,143 +178,22 @@ __device__ __forceinline__ const float* run_chain(const VnPlan& p, const float* 
     return cur;
 }
 
-// rows of the rotated array into the input tile, zero beyond the rows and the columns; grp[r] = the tile-local group of row r
-__device__ __forceinline__ void load_tile(const VnBufs& b, const float* __restrict__ rows_src, int rows, int cols, int per_group, int M)
-{
-    for (int i = threadIdx.x; i < M * 16; i += NT) {
-        const int r = i >> 4, c = i & 15;
-        b.X0[r * LDX + c] = (r < rows && c < cols) ? rows_src[(long)r * cols + c] : 0.0f;
-    }
-    for (int r = threadIdx.x; r < M; r += NT) b.grp[r] = r < rows ? r / per_group : 0;
-}
-
-// value_net.hip's k_value_net with M1 and G as bfloat16 rows and the layers' arithmetic of the header comment; `Gf`: the float32 running
-// sum of the crowd mean of a group in chunks (floats from the start of the dynamic block)
-__global__ __launch_bounds__(NT) void k_value_net_bf16(VnPlan p, VnLds m, int Gf, int M, const float* __restrict__ wb, int NG, int A, int n,
+// value_net.hip's k_value_net with this file's arithmetic; `gsum`: floats from the start of the dynamic block to the float32 running
+// sum of the crowd mean of a group in chunks, behind the map m
+__global__ __launch_bounds__(NT) void k_value_net_bf16(VnPlan p, VnLds m, int gsum, int M, const float* __restrict__ wb, int NG, int A, int n,
                                                        const float* __restrict__ rotated, const float* __restrict__ rewards,
                                                        const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
 {
     extern __shared__ float lds[];
-    VnBufs b;
-    b.X0 = lds + m.X0; b.M1 = lds + m.M1; b.P = lds + m.P; b.Q = lds + m.Q; b.G = lds + m.G; b.Gf = lds + Gf; b.J = lds + m.J;
-    b.sc = lds + m.sc; b.den = lds + m.den; b.val = lds + m.val; b.grp = reinterpret_cast<int*>(lds + m.grp);
-    const int tid = threadIdx.x;
-    const int rbs = M / 32, cols = p.cols;
-    const bool sarl = p.kind == CS_VN_SARL;
-    const int chunks = n <= M ? 1 : (n + M - 1) / M;
-    const int gpt = n <= M ? M / n : 1;
-    const int m1pad = (p.m1w + 15) & ~15;          // the columns the attention's k-steps read of the mean
-    int out_ld;
-
-    for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
-        const int gbase = job * JROWS;
-        const int ng = NG - gbase < JROWS ? NG - gbase : JROWS;
-        if (sarl) {
-            for (int i = tid; i < JROWS * p.ld_j; i += NT) b.J[i] = 0.0f;
-            if (tid < JROWS) b.den[tid] = 0.0f;
-        } else if (tid < JROWS) b.val[tid] = INFINITY;
-        __syncthreads();
-
-        for (int t0 = 0; t0 < ng; t0 += gpt) {
-            const int tg = ng - t0 < gpt ? ng - t0 : gpt;
-            const float* grows = rotated + (long)(gbase + t0) * n * cols;
-            if (sarl && p.with_global && chunks > 1) {
-                // more humans than a tile holds: a first pass over the chunks for the mean of mlp1 (sarl.py:42), a float32 running sum in Gf
-                for (int c = tid; c < m1pad; c += NT) b.Gf[c] = 0.0f;
-                for (int ch = 0; ch < chunks; ++ch) {
-                    const int rows = n - ch * M < M ? n - ch * M : M;
-                    load_tile(b, grows + (long)ch * M * cols, rows, cols, n, M);
-                    __syncthreads();
-                    run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
-                    for (int c = tid; c < m1pad; c += NT) {
-                        float s = b.Gf[c];
-                        for (int r = 0; r < rows; ++r) s += h2f(b.M1, p.ld_m1, r, c);
-                        b.Gf[c] = s;
-                    }
-                    __syncthreads();
-                }
-                for (int c = tid; c < m1pad; c += NT) f2h(b.G, p.ld_m1, 0, c, b.Gf[c] / (float)n);
-                __syncthreads();
-            }
-            // phase 0: a tile holds its groups whole -- denominator, weights and weighted sum in one visit.  A group in chunks needs the
-            // softmax denominator of ALL its humans before the first weight (sarl.py:52-53): phase 1 sums it, phase 2 recomputes and weighs.
-            for (int phase = chunks > 1 ? 1 : 0; phase <= (chunks > 1 ? 2 : 0); ++phase)
-            for (int ch = 0; ch < chunks; ++ch) {
-                const int per = chunks > 1 ? (n - ch * M < M ? n - ch * M : M) : n;      // humans of each group in this tile
-                const int rows = chunks > 1 ? per : tg * n;
-                load_tile(b, grows + (long)ch * M * cols, rows, cols, per, M);
-                __syncthreads();
-                if (!sarl) {
-                    if (phase == 1) continue;
-                    const float* out = run_chain<CH_CADRL>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, nullptr, 0, out_ld);
-                    if (tid < tg) {         // cadrl.py:269: the minimum over the humans
-                        float v = b.val[t0 + tid];
-                        for (int j = 0; j < per; ++j) {      // (torch.min's order: a NaN stays)
-                            const float x = out[(tid * per + j) * out_ld];
-                            v = (x < v || x != x) ? x : v;
-                        }
-                        b.val[t0 + tid] = v;
-                    }
-                    __syncthreads();
-                    continue;
-                }
-                if (ch == 0)                // sarl.py:36: the self state is read from the first human's row
-                    for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * LDX + i % SELF_DIM];
-                run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
-                if (p.with_global && chunks == 1 && n > 1) {
-                    for (int i = tid; i < tg * m1pad; i += NT) {
-                        const int k = i / m1pad, c = i - k * m1pad;
-                        float s = 0.0f;
-                        for (int j = 0; j < n; ++j) s += h2f(b.M1, p.ld_m1, k * n + j, c);
-                        f2h(b.G, p.ld_m1, k, c, s / (float)n);
-                    }
-                    __syncthreads();
-                }
-                {   // attention scores and the masked softmax's terms exp(s) * (s != 0) (sarl.py:48-52)
-                    const float* out = run_chain<CH_REDUCED>(p, wb, b, p.c0[2], p.c0[3], b.M1, p.ld_m1, p.with_global ? b.G : nullptr, p.ld_m1, rbs, nullptr, 0, out_ld);
-                    for (int r = tid; r < M; r += NT) {
-                        const float s = out[r * out_ld];
-                        b.sc[r] = (r < rows && s != 0.0f) ? expf(s) : 0.0f;
-                    }
-                    __syncthreads();
-                }
-                if (phase != 2) {           // the denominator, in human order
-                    if (tid < tg) {
-                        float s = b.den[t0 + tid];
-                        for (int j = 0; j < per; ++j) s += b.sc[tid * per + j];
-                        b.den[t0 + tid] = s;
-                    }
-                    __syncthreads();
-                    if (phase == 1) continue;
-                }
-                for (int r = tid; r < rows; r += NT) b.sc[r] = b.sc[r] / b.den[t0 + r / per];
-                __syncthreads();
-                {   // mlp2 and the weighted sum of its rows (sarl.py:57-60)
-                    const float* f = run_chain<CH_REDUCED>(p, wb, b, p.c0[1], p.c0[2], b.M1, p.ld_m1, nullptr, 0, rbs, nullptr, 0, out_ld);
-                    const int fw = p.feat;
-                    for (int i = tid; i < tg * fw; i += NT) {
-                        const int k = i / fw, c = i - k * fw;
-                        float s = b.J[(t0 + k) * p.ld_j + SELF_DIM + c];
-                        for (int j = 0; j < per; ++j) s = fmaf(b.sc[k * per + j], f[(k * per + j) * out_ld + c], s);
-                        b.J[(t0 + k) * p.ld_j + SELF_DIM + c] = s;
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-
-        if (sarl) {
-            const float* out = run_chain<CH_MLP3>(p, wb, b, p.c0[3], p.c0[4], b.J, p.ld_j, nullptr, 0, 1, nullptr, 0, out_ld);
-            if (tid < ng) b.val[tid] = out[tid * out_ld];
-            __syncthreads();
-        }
-        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
-            const int g = gbase + tid;
-            const float vpref = robot[(long)(g / A) * rstride + 7];
-            values[g] = rewards[g] + powf(gamma, dt * vpref) * b.val[tid];
-        }
-        __syncthreads();
-    }
+#define VN_BEGIN_JOB(gbase, ng)
+#define VN_TILE_SOURCE(g0) const float* grows = rotated + (long)(g0) * n * cols
+#define VN_LOAD_TILE(ch, rows, per) load_tile(b, grows + (long)(ch) * M * cols, rows, cols, per, M)
+#define VN_REWARD(g, k) rewards[g]
+#include "value_net_body.inc"
+#undef VN_BEGIN_JOB
+#undef VN_TILE_SOURCE
+#undef VN_LOAD_TILE
+#undef VN_REWARD
 }
 
 } // namespace
@@ -322,16 +203,9 @@ __global__ __launch_bounds__(NT) void k_value_net_bf16(VnPlan p, VnLds m, int Gf
 extern "C" int cs_value_net_pack_bf16(int kind, const int32_t* dims, int n_dims, int cols, const float* const* params, void* blob, size_t* n_bytes)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, p);
-    if (rc != CS_OK) return rc;
-    replan_bf16(p);
-    if (!n_bytes) return fail(CS_ERR_ARG, "null argument");
-    *n_bytes = (size_t)p.total_floats * sizeof(float);
-    if (!blob) return CS_OK;
-    if (!params) return fail(CS_ERR_ARG, "null argument");
-    for (int l = 0; l < p.n_layers; ++l)
-        if (!params[2 * l] || !params[2 * l + 1]) return fail(CS_ERR_ARG, "null weight or bias array");
-    memset(blob, 0, *n_bytes);
+    bool fill;
+    const int rc = begin_pack(kind, dims, n_dims, cols, replan_bf16, sizeof(float), params, blob, n_bytes, p, fill);
+    if (rc != CS_OK || !fill) return rc;
     float* fb = static_cast<float*>(blob);
     for (int l = 0; l < p.n_layers; ++l) {
         const VnLayer& L = p.L[l];
@@ -369,25 +243,12 @@ extern "C" int cs_value_net_decide_bf16(int kind, const int32_t* dims, int n_dim
     const size_t n_floats = n_weight_bytes % sizeof(float) ? (size_t)-1 : n_weight_bytes / sizeof(float);
     const int rc2 = check_decide_args(p, d_weights, n_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;
-    const size_t lds_limit = 160 * 1024;
-    const int M = TILE_M;
-    VnLds m = lds_map(p, M, n);
-    int Gf = 0;
-    if (p.kind == CS_VN_SARL && p.with_global && n > M) {
-        Gf = m.total;
-        m.total += up(p.m1w, 16);
-    }
-    const size_t shmem = (size_t)m.total * sizeof(float);
-    if (shmem > lds_limit) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    if (shmem > 64 * 1024) VN_GRANT_LDS(k_value_net_bf16, shmem);
-    const int NG = W * A;
-    const int jobs = (NG + JROWS - 1) / JROWS;
-    const int grid = jobs < 4096 ? jobs : 4096;
-    hipLaunchKernelGGL(k_value_net_bf16, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, p, m, Gf, M, static_cast<const float*>(d_weights), NG, A, n,
-                       d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
-                       d_override, d_choice, d_action_out);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
+    // (the tail: the float32 running sum of a chunked crowd mean, where the kernel keeps one)
+    const int tail = p.kind == CS_VN_SARL && p.with_global && n > TILE_M ? up(p.m1w, 16) : 0;
+    VnLaunch q;
+    const int rc3 = prepare_launch<k_value_net_bf16>(p, n, tail, W, A, q);
+    if (rc3 != CS_OK) return rc3;
+    hipLaunchKernelGGL(k_value_net_bf16, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)stream, p, q.m, q.tail, TILE_M, static_cast<const float*>(d_weights),
+                       q.NG, A, n, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }

@@ -1,14 +1,15 @@
-// value_net_f32.h -- what the two float32 kernels of the value-network decision share beside their body (value_net_body.inc): the LDS
-// buffers of a launch, a chain of layers and the loader that copies rows (value_net.hip: rows from cs_lookahead's tensor;
-// value_net_worlds.hip: rows generated from the worlds).  Unnamed namespace, as value_net_plan.h.
+// value_net_f32.h -- the float32 arithmetic of the value-network decision, as value_net_body.inc asks for an arithmetic (its header comment
+// lists the names): every layer of every chain is value_net_plan.h's layer_fwd, mlp1's output and the crowd mean are float rows.  Included
+// by the two float32 kernels (value_net.hip: rows from cs_lookahead's tensor; value_net_worlds.hip: rows generated from the worlds); the
+// bf16 arithmetic is stated in value_net_bf16.hip.  Unnamed namespace, as value_net_plan.h.
 #pragma once
 #include "value_net_plan.h"
 
 namespace {
 
-struct VnBufs { float *X0, *M1, *P, *Q, *G, *J, *sc, *den, *val; int* grp; };
-
 // layers [first, last) from `src`; outputs alternate P, Q; the last one goes to final_dst when given.  Returns where the result is.
+// (the chain's tag changes nothing here: one arithmetic for every layer)
+template <int>
 __device__ __forceinline__ const float* run_chain(const VnPlan& p, const float* __restrict__ wb, const VnBufs& b, int first, int last, const float* src,
                                                   int lds_, const float* src2, int lds2, int rbs, float* final_dst, int final_ld, int& out_ld)
 {
@@ -27,14 +28,13 @@ __device__ __forceinline__ const float* run_chain(const VnPlan& p, const float* 
     return cur;
 }
 
-// rows of the rotated array into the input tile, zero beyond the rows and the columns; grp[r] = the tile-local group of row r
-__device__ __forceinline__ void load_tile(const VnBufs& b, const float* __restrict__ rows_src, int rows, int cols, int per_group, int M)
-{
-    for (int i = threadIdx.x; i < M * 16; i += NT) {
-        const int r = i >> 4, c = i & 15;
-        b.X0[r * LDX + c] = (r < rows && c < cols) ? rows_src[(long)r * cols + c] : 0.0f;
-    }
-    for (int r = threadIdx.x; r < M; r += NT) b.grp[r] = r < rows ? r / per_group : 0;
-}
+__device__ __forceinline__ float vn_m1(const float* buf, int ld, int r, int c) { return buf[r * ld + c]; }
+__device__ __forceinline__ void vn_mean_store(float* buf, int ld, int k, int c, float v) { buf[k * ld + c] = v; }
+__device__ __forceinline__ int vn_m1pad(const VnPlan& p) { return (p.m1w + 7) & ~7; }
+// the running sum of a chunked mean is G's first row itself (the kernels' gsum = m.G), zeroed over the whole row
+__device__ __forceinline__ int vn_sum_cols(const VnPlan& p, int) { return p.ld_m1; }
+// A quirk, kept because removing it changes the float32 instruction stream: the pre-pass also runs without the global state, where
+// nothing reads the mean it leaves in G.
+__device__ __forceinline__ bool vn_mean_pass(const VnPlan&) { return true; }
 
 } // namespace

@@ -1,5 +1,5 @@
-// value_net_pick.h -- the per-world pick that follows the network kernel of either arithmetic (value_net.hip, value_net_bf16.hip).
-// Included behind the translation unit's network kernel; unnamed namespace, as value_net_plan.h.
+// value_net_pick.h -- the per-world pick that follows the network kernel of every decide entry (value_net.hip, value_net_worlds.hip,
+// value_net_bf16.hip), and its launch.  Included behind the translation unit's network kernel; unnamed namespace, as value_net_plan.h.
 #pragma once
 #include "value_net_plan.h"
 
@@ -42,6 +42,17 @@ __global__ __launch_bounds__(256) void k_value_pick(int W, int A, const float* _
     if (choice) choice[w] = bi;
     action_out[2 * w] = there ? 0.0f : actions[2 * bi];
     action_out[2 * w + 1] = there ? 0.0f : actions[2 * bi + 1];
+}
+
+// what the decide entries do alike after their kernel's launch: its launch status, then the pick on the same stream
+inline int launch_pick(int W, int A, const float* d_values, const float* d_actions, const float* d_robot, int robot_stride, const int32_t* d_override,
+                       int32_t* d_choice, float* d_action_out, void* stream)
+{
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
+                       d_override, d_choice, d_action_out);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
 }
 
 } // namespace

@@ -1,9 +1,13 @@
-// value_net_plan.h -- what the two arithmetics of the value-network decision share (value_net.hip: float32; value_net_bf16.hip: the opt-in
-// bf16 layers): the layer table of a network description, the LDS map of a launch and the float32 layer of a tile.  Everything sits in an
-// unnamed namespace: each translation unit gets its own copy, the kernels keep their names.  The per-world pick is value_net_pick.h.
+// value_net_plan.h -- what the three kernels of the value-network decision share beside their body (value_net_body.inc) and their
+// arithmetic (value_net_f32.h: float32, for value_net.hip and value_net_worlds.hip; value_net_bf16.hip: the opt-in bf16 layers).  Host: the
+// layer table of a network description, the argument checks, the LDS map, what the decide entries do before their launch and the pack
+// entries before they fill.  Device: the LDS buffers, the chain tags, the tile loader that copies rows and the float32 layer of a tile.
+// Everything sits in an unnamed namespace: each translation unit gets its own copy, the kernels keep their names.  The per-world pick and
+// its launch are value_net_pick.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -157,18 +161,70 @@ inline VnLds lds_map(const VnPlan& p, int M, int n)
     return m;
 }
 
-// the dynamic LDS of a launch beyond a kernel's default 64 KiB: raised per device to the largest size asked for so far
-#define VN_GRANT_LDS(kernel, shmem)                                                                                                   \
-    do {                                                                                                                              \
-        static std::atomic<int> granted[64];                                                                                          \
-        int dev = 0;                                                                                                                  \
-        HIP_TRY(hipGetDevice(&dev));                                                                                                  \
-        const bool slot = dev >= 0 && dev < 64;                                                                                       \
-        if (!slot || granted[dev].load(std::memory_order_acquire) < (int)(shmem)) {                                                   \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(shmem))); \
-            if (slot) granted[dev].store((int)(shmem), std::memory_order_release);                                                    \
-        }                                                                                                                             \
-    } while (0)
+// What the decide entries do alike before their kernel's launch.  The dynamic block is the map plus `tail_floats` of the kernel's own
+// (at float `tail`); beyond a kernel's default 64 KiB it is granted per device, raised to the largest size asked for so far.
+struct VnLaunch { VnLds m; int tail; size_t shmem; int NG, grid; };
+
+template <auto Kernel>
+inline int prepare_launch(const VnPlan& p, int n, int tail_floats, int W, int A, VnLaunch& q)
+{
+    q.m = lds_map(p, TILE_M, n);
+    q.tail = q.m.total;
+    q.shmem = (size_t)(q.m.total + tail_floats) * sizeof(float);
+    // (the float32 tensor path cannot get here within build_plan's limits -- 16 layers of up to 256 columns need about 150 KiB at most, at n = 2)
+    if (q.shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    if (q.shmem > 64 * 1024) {
+        static std::atomic<int> granted[64];
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        const bool slot = dev >= 0 && dev < 64;
+        if (!slot || granted[dev].load(std::memory_order_acquire) < (int)q.shmem) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.shmem));
+            if (slot) granted[dev].store((int)q.shmem, std::memory_order_release);
+        }
+    }
+    q.NG = W * A;
+    const int jobs = (q.NG + JROWS - 1) / JROWS;
+    q.grid = jobs < 4096 ? jobs : 4096;
+    return CS_OK;
+}
+
+// What the pack entries do alike before they fill the blob: the plan (`replan`: the arithmetic's changes to it, or null), the size query
+// through n_units (`units_per_float`: 1 for a blob counted in floats, 4 in bytes), the null checks, the zeroed blob.  `fill` tells whether
+// there is a blob to fill.
+inline int begin_pack(int kind, const int32_t* dims, int n_dims, int cols, void (*replan)(VnPlan&), int units_per_float, const float* const* params,
+                      void* blob, size_t* n_units, VnPlan& p, bool& fill)
+{
+    fill = false;
+    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    if (rc != CS_OK) return rc;
+    if (replan) replan(p);
+    if (!n_units) return fail(CS_ERR_ARG, "null argument");
+    *n_units = (size_t)p.total_floats * units_per_float;
+    if (!blob) return CS_OK;
+    if (!params) return fail(CS_ERR_ARG, "null argument");
+    for (int l = 0; l < p.n_layers; ++l)
+        if (!params[2 * l] || !params[2 * l + 1]) return fail(CS_ERR_ARG, "null weight or bias array");
+    memset(blob, 0, (size_t)p.total_floats * sizeof(float));
+    fill = true;
+    return CS_OK;
+}
+
+// the LDS buffers of a launch; Gsum: the float32 running sum of the crowd mean of a group in chunks
+struct VnBufs { float *X0, *M1, *P, *Q, *G, *Gsum, *J, *sc, *den, *val; int* grp; };
+
+// the chains of value_net_body.inc: mlp1 (ends in M1); mlp2 / attention (their output goes to a reduction); mlp3; CADRL's value_network
+enum { CH_MLP1, CH_REDUCED, CH_MLP3, CH_CADRL };
+
+// rows of the rotated array into the input tile, zero beyond the rows and the columns; grp[r] = the tile-local group of row r
+__device__ __forceinline__ void load_tile(const VnBufs& b, const float* __restrict__ rows_src, int rows, int cols, int per_group, int M)
+{
+    for (int i = threadIdx.x; i < M * 16; i += NT) {
+        const int r = i >> 4, c = i & 15;
+        b.X0[r * LDX + c] = (r < rows && c < cols) ? rows_src[(long)r * cols + c] : 0.0f;
+    }
+    for (int r = threadIdx.x; r < M; r += NT) b.grp[r] = r < rows ? r / per_group : 0;
+}
 
 // One float32 layer of a tile: dst[rows][ncb * 32] = act(src[rows][K] x Wt + b) for `rbs` row blocks of 32.  The A operand of row r comes
 // from src (k-groups below kg_split) and then from src2[grp[r]] (the per-group second source: SARL's mean of mlp1); columns beyond N are

@@ -14,8 +14,6 @@
 // with d_rewards_out).  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "lookahead_math.h"
 #include "value_net_f32.h"
 
@@ -88,6 +86,7 @@ __global__ __launch_bounds__(NT) void k_value_net_worlds(VnPlan p, VnLds m, int 
                                                          float dt, float* __restrict__ rewards_out, float* __restrict__ values)
 {
     extern __shared__ float lds[];
+    const int gsum = m.G;
     const WorldRows world{actions, next, cur, robot, rewards_out, lds + frames, rstride, headed, A, n};
 #define VN_BEGIN_JOB(gbase, ng) begin_job(world, gbase, ng, dt)
 #define VN_TILE_SOURCE(g0) const int tile_g0 = (g0)
@@ -115,20 +114,10 @@ extern "C" int cs_value_net_decide_worlds(int kind, const int32_t* dims, int n_d
     // (the worlds' two arrays stand where cs_value_net_decide has cs_lookahead's two outputs: cs_lookahead's own checks are among these)
     const int rc2 = check_decide_args(p, d_weights, n_weight_floats, W, A, n, d_next, d_current, d_actions, d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;
-    const int M = TILE_M;
-    const VnLds m = lds_map(p, M, n);
-    const int frames = m.total;
-    const size_t shmem = (size_t)(frames + JROWS * LA_FRAME_FLOATS) * sizeof(float);
-    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    if (shmem > 64 * 1024) VN_GRANT_LDS(k_value_net_worlds, shmem);
-    const int NG = W * A;
-    const int jobs = (NG + JROWS - 1) / JROWS;
-    const int grid = jobs < 4096 ? jobs : 4096;
-    hipLaunchKernelGGL(k_value_net_worlds, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, p, m, frames, M, d_weights, NG, A, n,
+    VnLaunch q;
+    const int rc3 = prepare_launch<k_value_net_worlds>(p, n, JROWS * LA_FRAME_FLOATS, W, A, q);      // (the tail: the frame table)
+    if (rc3 != CS_OK) return rc3;
+    hipLaunchKernelGGL(k_value_net_worlds, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)stream, p, q.m, q.tail, TILE_M, d_weights, q.NG, A, n,
                        theta_and_omega_visible ? 1 : 0, d_actions, d_next, d_current, d_robot, robot_stride, gamma, dt, d_rewards_out, d_values);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_value_pick, dim3((W + 3) / 4), dim3(256), 0, (hipStream_t)stream, W, A, d_values, d_actions, d_robot, robot_stride,
-                       d_override, d_choice, d_action_out);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }

@@ -809,20 +809,12 @@ class BatchedSocialNavGym:
                 o, T = self.observe_device(), self.robot_time_step
                 nxt = (torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 5] + o[..., 6] * T, o[..., 2], o[..., 3], o[..., 6]], -1)
                        if self.headed_obs else torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 2], o[..., 3]], -1)).contiguous()
-            if pol.decision_input == "fused":        # one library call on the worlds' own rows: no rot / rew
-                nxt_, cur_, rob = self._worlds_on_side_stream(dl, nxt)
-                value_net.decide_worlds(net, W, A, self.n, self.headed_obs, acts.data_ptr(), nxt_.data_ptr(), cur_.data_ptr(), rob.data_ptr(),
-                                        rob.shape[1], pol.gamma, self.robot_time_step, None if explore is None else explore.data_ptr(), None,
-                                        dl["vn_values"].data_ptr(), dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream)
-                used = (nxt_, cur_, rob)
-            else:
-                rot, rew, rob = self._lookahead_on_side_stream(dl, acts, next_humans=nxt, with_robot=True)
-                value_net.decide(net, W, A, self.n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], pol.gamma,
-                                 self.robot_time_step, None if explore is None else explore.data_ptr(), dl["vn_values"].data_ptr(),
-                                 dl["vn_choice"].data_ptr(), dl["act"].data_ptr(), side.cuda_stream, precision=pol.decision_precision)
-                used = (rot, rew, rob) + (() if nxt is None else (nxt,))
-            for t in used + (() if explore is None else (explore,)):
-                t.record_stream(side)
+            nxt, cur_, rob = self._worlds_on_side_stream(dl, nxt)
+            rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
+                                                   explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream)
+            for t in (nxt, cur_, rob, rot, rew, explore):
+                if t is not None:
+                    t.record_stream(side)
         self._stream_handshake(dl, cur, False)
         return dl["act"]
 
@@ -841,38 +833,21 @@ class BatchedSocialNavGym:
         tensors (rotated_states [W, A, N, 13] -- 15 columns with ``headed_obs`` (theta and omega visible) --, rewards [W, A]) ready for ONE
         batched value-network call -- no host copy.
         Needs worlds generated on the device (``reset(..., device=True)``), like ``step_device``."""
-        import ctypes as C
-
         import torch
 
+        from ..crowd_nav.policy import value_net
+
         dl = self._device_loop_state()
+        if self.cw.d_robot is None:
+            raise ValueError("lookahead_device needs the robot rows")
         side, cur_stream = dl["stream"], torch.cuda.current_stream()
         side.wait_stream(cur_stream)
         with torch.cuda.stream(side):               # the library launches on this stream (cw.stream); the torch ops between them follow
-            out = self._lookahead_on_side_stream(dl, action_space)
+            acts = torch.as_tensor(np.asarray(action_space, dtype=np.float32) if not torch.is_tensor(action_space) else action_space,
+                                   dtype=torch.float32, device="cuda").contiguous()
+            out = value_net.lookahead(acts, *self._worlds_on_side_stream(dl), self.robot_time_step, side.cuda_stream)
         cur_stream.wait_stream(side)
         return out
-
-    def _lookahead_on_side_stream(self, dl, action_space, next_humans=None, with_robot=False):
-        import ctypes as C
-
-        import torch
-
-        cw, W, n = self.cw, self.W, self.n
-        if cw.d_robot is None:
-            raise ValueError("lookahead_device needs the robot rows")
-        acts = torch.as_tensor(np.asarray(action_space, dtype=np.float32) if not torch.is_tensor(action_space) else action_space,
-                               dtype=torch.float32, device="cuda").contiguous()
-        A = acts.shape[0]
-        lib = _lib.load()
-        nxt, cur, rob = self._worlds_on_side_stream(dl, next_humans)
-        rot = torch.empty((W, A, n, 15 if self.headed_obs else 13), dtype=torch.float32, device="cuda")
-        rew = torch.empty((W, A), dtype=torch.float32, device="cuda")
-        _lib.check(lib.cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(self.headed_obs)), C.c_void_p(acts.data_ptr()),
-                                    C.c_void_p(nxt.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(rob.data_ptr()), C.c_int(9),
-                                    C.c_float(self.robot_time_step), C.c_void_p(rot.data_ptr()), C.c_void_p(rew.data_ptr()),
-                                    C.c_void_p(cw.stream)))
-        return (rot, rew, rob) if with_robot else (rot, rew)
 
     def _worlds_on_side_stream(self, dl, next_humans=None):
         """What a look-ahead reads of the resident worlds, as contiguous CUDA tensors: (next humans [W, n, 4 | 6] -- cs_peek's, or the caller's
