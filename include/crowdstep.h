@@ -637,6 +637,27 @@ int cs_value_net_decide_worlds(int kind, const int32_t* dims, int n_dims, const 
                                const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
                                float* d_rewards_out /* may be NULL */, float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
 
+/*
+ * cs_value_net_state  the value network on the worlds' CURRENT state, for a trainer (csrc/value_net_state.hip): what
+ *   policy.transform hands to a replay memory (crowd_nav/policy/multi_human_rl.py:115-128 -> cadrl.py rotate) and the target value
+ *   reward + gamma^(time_step * v_pref) * V(state) (crowd_nav/utils/explorer.py:120-153), for W worlds in one kernel on `stream`.
+ *   d_current [W][n][5|7] (px, py, vx, vy, radius [, theta, omega]) and d_robot [W][robot_stride] (px, py, vx, vy, radius, gx, gy,
+ *   v_pref, ...) are what cs_lookahead takes; kind, dims and d_weights (cs_value_net_pack's float32 blob for cols = 13, or 15 with
+ *   theta_and_omega_visible) what cs_value_net_decide takes.  A world's n rows are, by definition and bit for bit, cs_lookahead's rows
+ *   for the one action (robot vx, vy), dt = 0 and d_next = the humans' current (px, py, vx, vy | px, py, theta, vx, vy, omega).
+ *   d_rotated_out (may be NULL) receives them, dense [W][n][13|15].  d_values [W] = d_rewards[w] + gamma^(dt * v_pref[w]) * V(w), with
+ *   V the network's output on the world's rows (CADRL: the minimum over the humans) exactly as cs_value_net_decide computes it on such
+ *   rows; d_rewards may be NULL (0): with it NULL and dt = 0 the value is the network's output itself.  A world gives the same bits
+ *   for W = 1 as inside any batch.  float32 only.  Device memory touched: the inputs, the blob, d_values, d_rotated_out.
+ *   Errors (CS_ERR_ARG, before any device call): those of cs_value_net_decide's network description with their messages, W < 1,
+ *   n < 1, a null d_weights, d_current, d_robot or d_values, a blob of another size, robot_stride < 8, a network whose tile buffers
+ *   (with this kernel's table of 32 x 8 floats) do not fit the LDS.
+ */
+int cs_value_net_state(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int n,
+                       int theta_and_omega_visible, const float* d_current, const float* d_robot, int robot_stride,
+                       const float* d_rewards /* may be NULL */, float gamma, float dt, float* d_rotated_out /* may be NULL */,
+                       float* d_values, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "cs_orca_default_math", "cs_gym_step_is_one_launch", "cs_gym_step_staged", "cs_policy_no_train",
     "cs_gym_step_policy", "cs_gym_step_staged_policy", "cs_gym_step_policy_variant",
     "cs_value_net_pack", "cs_value_net_decide", "cs_value_net_pack_bf16", "cs_value_net_decide_bf16",
-    "cs_value_net_decide_worlds",
+    "cs_value_net_decide_worlds", "cs_value_net_state",
 ]
 
 

@@ -152,6 +152,7 @@ class CADRL(Policy):
         for attribute, value in _INITIAL_ATTRIBUTES.items():
             setattr(self, attribute, value)
         self._net = None
+        self._state_nets = []
         self._acts_device = None
         self.decision_precision = "f32"
         self.decision_input = "tensor"
@@ -212,6 +213,49 @@ class CADRL(Policy):
             self._net = DeviceNet(self.model, self.joint_state_dim)
         self._net.refresh(self.decision_precision)
         return self._net
+
+    _STATE_NETS_KEPT = 4
+
+    def state_net(self, model=None):
+        """The float32 DeviceNet that evaluates states (cs_value_net_state) with ``model``'s weights -- None: the policy's own module, the
+        DeviceNet of ``device_net()``.  Another module (a trainer's deep-copied target network) must have the policy's architecture; its
+        DeviceNet is kept per module, apart from the policy's own, and repacked only after a parameter changed."""
+        from .value_net import DeviceNet
+
+        if self._net is None or self._net.model is not self.model:
+            self._net = DeviceNet(self.model, self.joint_state_dim)
+        net = own = self._net
+        if model is not None and model is not self.model:
+            net = next((kept for kept in self._state_nets if kept.model is model), None)
+            if net is None:
+                net = DeviceNet(model, self.joint_state_dim)
+                if net.kind != own.kind or not np.array_equal(net.dims, own.dims):
+                    raise ValueError(f"{self.name}: the module to evaluate has another architecture than the policy's "
+                                     f"({net.dims.tolist()} against {own.dims.tolist()})")
+                self._state_nets = (self._state_nets + [net])[-self._STATE_NETS_KEPT:]
+        net.refresh("f32")
+        return net
+
+    def state_value(self, state, model=None):
+        """V(state): the value network (``model``: another module of the same architecture, e.g. a target network) on the rotated joint
+        state of ``state`` as it stands -- no look-ahead, no reward; CADRL: the minimum over the humans.  The W = 1 launch of the kernel
+        behind ``BatchedSocialNavGym.value_device`` (cs_value_net_state), float32; returns a Python float."""
+        from . import value_net
+
+        _lib.require_gpu()
+        if self.model is None:
+            raise AttributeError(f"{self.name}: configure() the policy before it evaluates a state")
+        headed = bool(self.with_theta_and_omega_visible)
+        rows = joint_rows(state, headed)
+        if rows.shape[0] < 1:
+            raise ValueError(f"{self.name}.state_value needs at least one human")
+        net = self.state_net(model)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
+        d_c, d_r = up(rows[:, len(ROBOT_FIELDS):]), up(rows[:1, :len(ROBOT_FIELDS)])
+        value = torch.empty(1, dtype=torch.float32, device="cuda")
+        value_net.state_values(net, 1, rows.shape[0], headed, d_c.data_ptr(), d_r.data_ptr(), d_r.shape[1], None, self.gamma, 0.0, None,
+                               value.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return float(value.item())
 
     def device_action_space(self):
         """The action table as a CUDA tensor [A, 2], uploaded again only when action_space_ndarray holds other values."""

@@ -7,7 +7,10 @@ There is no host implementation of the decision: without the library or a GPU th
 
 Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_value_net_decide_bf16, csrc/value_net_bf16.hip) with its
 own blob; a policy chooses with ``set_decision_precision``.  Two inputs: "tensor", the default (cs_lookahead's rows in HBM), and the opt-in
-"fused" (``decide_worlds``: cs_value_net_decide_worlds generates the rows in the kernel, float32 only); ``set_decision_input``."""
+"fused" (``decide_worlds``: cs_value_net_decide_worlds generates the rows in the kernel, float32 only); ``set_decision_input``.
+
+``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
+rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -143,6 +146,25 @@ def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, 
         C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
         C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(int(bool(headed))), P(actions), P(nxt), P(cur), P(robot), C.c_int(robot_stride),
         C.c_float(gamma), C.c_float(dt), P(override), P(rewards_out), P(values), P(choice), P(action_out), P(stream)))
+
+
+def state_values(net, W, n, headed, cur, robot, robot_stride, rewards, gamma, dt, rotated_out, values, stream=None):
+    """cs_value_net_state on device pointers (ints): the network on the worlds' CURRENT state, for a trainer -- cur [W][n][5|7], robot
+    [W][robot_stride] as cs_lookahead takes them; rotated_out [W][n][13|15] or None receives the rotated joint states (``transform``),
+    values [W] = rewards[w] + gamma^(dt * v_pref) * V(w), rewards [W] or None (0): with None and dt = 0 the network's own output.  `net` a
+    DeviceNet whose float32 blob is current and whose cols match `headed`."""
+    from ... import _lib
+
+    P = C.c_void_p
+    blob = net.blobs["f32"]
+    if blob is None:
+        raise ValueError("state_values: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    if net.cols != (15 if headed else 13):
+        raise ValueError(f"state_values: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    _lib.check(_lib.load().cs_value_net_state(
+        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
+        C.c_int(W), C.c_int(n), C.c_int(int(bool(headed))), P(cur), P(robot), C.c_int(robot_stride), P(rewards), C.c_float(gamma), C.c_float(dt),
+        P(rotated_out), P(values), P(stream)))
 
 
 def lookahead(acts, nxt, cur, robot, dt, stream=None):

@@ -1,5 +1,6 @@
 // lookahead_math.h -- the arithmetic of the robot's one-step look-ahead, stated once for the two kernels that evaluate it: k_lookahead
-// (lookahead.hip), which writes the rows to HBM, and k_value_net_worlds (value_net.hip), whose tile loader generates them in LDS.
+// (lookahead.hip), which writes the rows to HBM, and k_value_net_worlds (value_net.hip), whose tile loader generates them in LDS -- and, at
+// the end of this header, for k_value_net_state (value_net_state.hip), whose rows are the look-ahead's of a step of no length.
 // Replaces compute_rotated_states_and_reward + transform_state_to_agent_centric (crowd_nav/policy/cadrl.py:42-83, :13-39).
 //
 // The two kernels must agree to the last bit, and hipcc contracts a * b + c * d by context.  Every function therefore switches the
@@ -101,6 +102,18 @@ __device__ __forceinline__ float4 la_row_quad(const float* f, const float* __res
         return make_float4(la_dot(hvx, cr, hvy, sr), la_cross(hvy, cr, hvx, sr), hr, sqrtf(la_dot(hx, hx, hy, hy)));
     } else
         return make_float4(rr + hr, headed ? q[2] - 0.0f : 0.0f, headed ? q[5] : 0.0f, 0.0f);
+}
+
+// The network's row of a world's CURRENT state (what a trainer stores: CADRL.transform / MultiHumanRL.transform, cadrl.py:305-345) is, by
+// definition, the look-ahead row above for the action (robot vx, vy), a step of dt = 0 -- fmaf(ax, 0, px) is px exactly -- and the humans'
+// current rows as their next ones.  The frame of that row (f[0..6] of LA_FRAME_FLOATS; f[7], the reward, is the caller's), for
+// k_value_net_state (value_net_state.hip); la_row_quad then takes the human's current (px, py, vx, vy | x, y, yaw, Vx, Vy, Omega).
+__device__ __forceinline__ void la_state_frame(const float* __restrict__ rb, float* f)
+{
+    const float ax = rb[2], ay = rb[3];
+    const LaStep st = la_step(rb, ax, ay, 0.0f);
+    f[0] = ax; f[1] = ay; f[2] = st.nrx; f[3] = st.nry; f[6] = st.dg;
+    la_frame(st, f[4], f[5]);
 }
 
 } // namespace

@@ -826,6 +826,67 @@ class BatchedSocialNavGym:
             return None
         return dl["vn_values"], dl["vn_choice"]
 
+    def joint_state_device(self, policy):
+        """What a trainer stores for the decision every robot is about to take: ``policy.transform`` of every world's resident state -- the
+        rotated joint state of the robot with each human, what ``predict`` leaves in ``last_state`` -- as a new CUDA tensor [W, n, 13|15].
+        ``policy``: a configured CADRL / SARL instance.  One launch of cs_value_net_state on ``device_stream()`` (which also evaluates the
+        network: ``value_device(policy, with_state=True)`` returns both); nothing crosses to the host."""
+        return self._state_values_device("joint_state_device", policy, None, None, 0.0, True)[1]
+
+    def value_device(self, policy, model=None, rewards=None, bootstrap=False, with_state=False):
+        """The value network on every world's resident state: a new float32 CUDA tensor [W] of V(s) -- CADRL: the minimum over the humans,
+        SARL: the network's output --, with ``with_state`` the pair (values, rows [W, n, 13|15] as ``joint_state_device`` returns them).
+        ``model``: the module to evaluate instead of ``policy.model`` -- any module of the policy's architecture, such as a trainer's
+        ``copy.deepcopy`` target network; its packed weights are kept per module and repacked only after a parameter changed.
+        ``bootstrap=True`` evaluates the trainer's target of the state the worlds are in, ``rewards + gamma^(robot_time_step * v_pref) * V``
+        (crowd_nav/utils/explorer.py:120-153; ``rewards``: a float32 CUDA tensor [W], None = 0); a terminal step's target is its reward
+        alone: ``torch.where(done, rewards, target)``.  Without ``bootstrap`` ``rewards`` must be None.  float32 arithmetic whatever the
+        policy's decision precision.  One launch of cs_value_net_state on ``device_stream()``; nothing crosses to the host."""
+        if rewards is not None and not bootstrap:
+            raise ValueError("value_device: rewards= belongs to bootstrap=True (rewards + gamma^(robot_time_step * v_pref) * V)")
+        values, rows = self._state_values_device("value_device", policy, model, rewards, self.robot_time_step if bootstrap else 0.0, with_state)
+        return (values, rows) if with_state else values
+
+    def _state_values_device(self, who, pol, model, rewards, dt, with_rows):
+        """cs_value_net_state on the resident worlds, with act_device's refusals (made before anything touches the device), stream handshake
+        and record_stream discipline: (values [W], rows [W, n, cols] or None)."""
+        from ..crowd_nav.policy.cadrl import CADRL
+
+        if not isinstance(pol, CADRL):
+            raise TypeError(f"{who} takes a value-based policy (CADRL, SARL), not {pol!r}")
+        if pol.model is None:
+            raise AttributeError(f"{pol.name}: configure() the policy before it evaluates a state")
+        if pol.kinematics != "holonomic" or (self.cw is not None and self.cw.unicycle):
+            raise ValueError(f"{who}: the value-based policies act in ActionXY and need a holonomic robot")
+        if bool(pol.with_theta_and_omega_visible) != self.headed_obs:
+            raise ValueError(f"{who}: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
+        if self.cw is not None and self.cw.d_robot is None:
+            raise ValueError(f"{who} needs the robot rows")
+        import torch
+
+        from ..crowd_nav.policy import value_net
+
+        dl = self._device_loop_state()
+        W, n = self.W, self.n
+        if rewards is not None:
+            if not (torch.is_tensor(rewards) and rewards.is_cuda and rewards.dtype == torch.float32 and tuple(rewards.shape) == (W,)):
+                raise ValueError(f"{who}: rewards is a float32 CUDA tensor [W]")
+            rewards = rewards.contiguous()
+        net = pol.state_net(model)                   # (repacked here, on the caller's stream, only when a parameter changed)
+        side, cur = dl["stream"], torch.cuda.current_stream()
+        self._stream_handshake(dl, cur, True)
+        with torch.cuda.stream(side):
+            _, cur_, rob = self._worlds_on_side_stream(dl, peek=False)
+            values = torch.empty(W, dtype=torch.float32, device="cuda")
+            rows = torch.empty((W, n, pol.joint_state_dim), dtype=torch.float32, device="cuda") if with_rows else None
+            value_net.state_values(net, W, n, self.headed_obs, cur_.data_ptr(), rob.data_ptr(), rob.shape[1], None if rewards is None else rewards.data_ptr(),
+                                   pol.gamma, dt, None if rows is None else rows.data_ptr(), values.data_ptr(), side.cuda_stream)
+            for t in (cur_, rob, rewards, values, rows):
+                if t is not None:
+                    t.record_stream(cur if t is values or t is rows else side)
+        self._stream_handshake(dl, cur, False)
+        return values, rows
+
     def lookahead_device(self, action_space):
         """The per-decision array work of CADRL / SARL for every world, on the device: one-step look-ahead of the humans
         (``get_next_human_observable_states``, cadrl.py:258-259 -> cs_peek) and ``compute_rotated_states_and_reward``
@@ -849,9 +910,9 @@ class BatchedSocialNavGym:
         cur_stream.wait_stream(side)
         return out
 
-    def _worlds_on_side_stream(self, dl, next_humans=None):
-        """What a look-ahead reads of the resident worlds, as contiguous CUDA tensors: (next humans [W, n, 4 | 6] -- cs_peek's, or the caller's
-        --, current humans [W, n, 5 | 7], robot rows [W, 9] in FullState order)."""
+    def _worlds_on_side_stream(self, dl, next_humans=None, peek=True):
+        """What a look-ahead reads of the resident worlds, as contiguous CUDA tensors: (next humans [W, n, 4 | 6] -- cs_peek's, or the caller's;
+        None without ``peek``: the current state alone is asked for --, current humans [W, n, 5 | 7], robot rows [W, 9] in FullState order)."""
         import ctypes as C
 
         import torch
@@ -859,15 +920,15 @@ class BatchedSocialNavGym:
         cw, W, n = self.cw, self.W, self.n
         lib = _lib.load()
         d = cw.descriptor(respawn=False)
-        peek = cw._buffer("peek", (W, n, 8))
-        if next_humans is None:
-            _lib.check(lib.cs_peek(C.byref(d), C.c_float(self.robot_time_step), C.c_void_p(peek.ptr), C.c_void_p(cw.stream)))
+        peek_buf = cw._buffer("peek", (W, n, 8))
+        if next_humans is None and peek:
+            _lib.check(lib.cs_peek(C.byref(d), C.c_float(self.robot_time_step), C.c_void_p(peek_buf.ptr), C.c_void_p(cw.stream)))
         if "la_cols" not in dl:
             # next humans: (px, py, vx, vy), or (x, y, yaw, Vx, Vy, Omega) with theta / omega visible (cadrl.py:42-83) = cs_peek's first six
             dl["la_cols"] = torch.as_tensor([0, 1, 2, 3, 4, 5] if self.headed_obs else [0, 1, 3, 4], device="cuda")
             dl["la_robot_cols"] = torch.as_tensor([0, 1, 3, 4, 8, 10, 11, 12, 2], device="cuda")   # FullState order
             dl["la_robot"] = cw.d_robot.torch().view(W, 13)
-        nxt = peek.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous() if next_humans is None else next_humans
+        nxt = peek_buf.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous() if next_humans is None and peek else next_humans
         cur = dl["state"][:, :n].index_select(2, dl["cols"]).contiguous()
         rob = dl["la_robot"].index_select(1, dl["la_robot_cols"]).contiguous()
         return nxt, cur, rob

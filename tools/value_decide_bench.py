@@ -12,6 +12,13 @@ repeat, median with minimum and maximum.  The two inputs' values are compared bi
 
     python tools/value_decide_bench.py [--worlds 4096] [--humans 5 25] [--policies cadrl sarl] [--repeats 20] [--inputs tensor fused]
     CROWDSTEP_LIB=<another build> python tools/value_decide_bench.py --inputs tensor      # the tensor path of a build without the fused entry
+
+`--state` times the value network on the worlds' CURRENT state instead (cs_value_net_state, k_value_net_state): `kernel_ms`, the library
+call alone on fixed device inputs (rows written and not written); `value_device_ms`, the whole ``env.value_device(policy)`` (the gathers,
+the allocations, the kernel); and `torch_forward_ms`, the only way to the same numbers without the kernel: the torch module's float32
+forward under no_grad on the same rows on the same device (the rows given: torch has no ``rotate`` for the worlds' tensors).
+
+    python tools/value_decide_bench.py --state [--worlds 4096] [--humans 5 25] [--policies cadrl sarl] [--repeats 20]
 """
 import argparse
 import ctypes as C
@@ -25,18 +32,80 @@ for _d in ("tools", "tests", os.path.join("tests", "golden")):
     sys.path.insert(0, os.path.join(ROOT, _d))
 
 
+def _timed(fn):
+    import torch
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def state_rows(a):
+    """The `--state` cases: one JSON line per (humans, policy)."""
+    import numpy as np
+    import torch
+    from value_policy_timing import _env, _policy
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    _lib.require_gpu()
+    for n in a.humans:
+        env = _env(n, a.worlds)
+        W = env.W
+        for name in a.policies:
+            pol = _policy(name, env)
+            with torch.cuda.stream(env.device_stream()):
+                stream = env.device_stream().cuda_stream
+                net = pol.state_net()
+                _, cur, rob = env._worlds_on_side_stream(env._device_loop_state(), peek=False)
+                vals = torch.zeros(W, device="cuda")
+                rows = torch.zeros((W, n, 13), device="cuda")
+
+                def kernel(with_rows):
+                    value_net.state_values(net, W, n, False, cur.data_ptr(), rob.data_ptr(), 9, None, pol.gamma, 0.0,
+                                           rows.data_ptr() if with_rows else None, vals.data_ptr(), stream)
+
+                def forward():
+                    with torch.no_grad():
+                        out = pol.model(rows)
+                        return out[..., 0].min(dim=-1).values if pol.name == "CADRL" else out[:, 0]
+
+                for _ in range(3):
+                    kernel(True), kernel(False), env.value_device(pol), forward()
+                torch.cuda.synchronize()
+                want = forward().double()
+                rel = float((vals.double() - want).abs().max() / want.abs().max().clamp(min=1.0))
+                t = dict(kernel_ms=[], kernel_without_rows_ms=[], value_device_ms=[], torch_forward_ms=[])
+                for _ in range(a.repeats):
+                    t["kernel_ms"].append(_timed(lambda: kernel(True)))
+                    t["kernel_without_rows_ms"].append(_timed(lambda: kernel(False)))
+                    t["value_device_ms"].append(_timed(lambda: env.value_device(pol)))
+                    t["torch_forward_ms"].append(_timed(forward))
+                stat = lambda xs: dict(median=float(np.median(xs)), min=float(min(xs)), max=float(max(xs)))
+                print(json.dumps(dict(state=True, policy=name, worlds=W, humans=n, repeats=a.repeats, relative_error_against_torch=rel,
+                                      device=_lib.device_name(0), **{k: stat(v) for k, v in t.items()})), flush=True)
+        env.close()
+
+
 def main():
     import numpy as np
     import torch
     from value_policy_timing import _env, _policy
 
     ap = argparse.ArgumentParser()
+    ap.add_argument("--state", action="store_true", help="time cs_value_net_state / value_device beside the torch forward on the same rows")
     ap.add_argument("--worlds", type=int, default=4096)
     ap.add_argument("--humans", type=int, nargs="+", default=[5, 25])
     ap.add_argument("--policies", nargs="+", default=["cadrl", "sarl"])
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--inputs", nargs="+", default=["tensor", "fused"], choices=["tensor", "fused"])
     a = ap.parse_args()
+    if a.state:
+        return state_rows(a)
 
     from social_navigation_pyenvs_amd import _lib
     from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
