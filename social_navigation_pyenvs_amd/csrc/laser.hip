@@ -48,8 +48,10 @@ __global__ __launch_bounds__(64) void k_laser_scan(const LArgs a)
         const float* s = a.S + ((long)w * a.rows + i) * a.as;
         const float sx = x3 - s[0], sy = y3 - s[a.fs], r = s[8 * a.fs];
         const float b = sx * dx + sy * dy;
-        const float c = sx * sx + sy * sy - r * r;
-        const float h = b * b - c;
+        // sensors.py:27-28 has h = b * b - (|s|^2 - r^2): two numbers of ~100 at 10 m whose difference is at most r^2, so float32 keeps
+        // ~1e-5 of h and 1e-5 / (2 sqrt(h)) of t.  (dx, dy) is a unit vector: b^2 + (s x d)^2 = |s|^2, the same h without the cancellation
+        const float x = sx * dy - sy * dx;
+        const float h = r * r - x * x;
         if (h < 0.0f) continue;
         const float t = -b - sqrtf(h);
         if (t < 0.0f) continue;

@@ -12,6 +12,8 @@ from golden_io import load_cases  # noqa: E402
 
 from oracle import crowd_oracle as orc  # noqa: E402
 
+import laser_cases as lc  # noqa: E402
+
 
 def test_oracle_matches_golden_g9():
     n_rays = 0
@@ -88,5 +90,8 @@ def test_batched_scan_on_resident_worlds_equals_oracle():
                                     dtype=np.float64)
             bad = np.abs(got[w] - ref) > 5e-5
             assert bad.sum() <= 1
+        # every world and every ray under the bound of tests/laser_cases.py: 1e-5 plus what the ray's own sensitivity to its angle allows
+        ref = lc.bound(robot[:, 0:3], St[:, :, 0:2], St[:, :, 8], walls, np.pi, 61, 8.0)
+        assert lc.excess(got, ref).max() <= lc.BAR and ref["edge"].mean() <= 0.01
     with pytest.raises(ValueError):
         cw.laser_scan(np.pi, 61, 12.0)
