@@ -658,6 +658,45 @@ int cs_value_net_state(int kind, const int32_t* dims, int n_dims, const float* d
                        const float* d_rewards /* may be NULL */, float gamma, float dt, float* d_rotated_out /* may be NULL */,
                        float* d_values, void* stream);
 
+/*
+ * Float64 worlds (csrc/sfmstep_f64.hip): the SFM / HSFM substep in the reference's own precision (PRECISION = np.float64),
+ * an opt-in arithmetic beside the float32 entries above.  cs_worlds_f64 carries the fields of cs_worlds that apply, with double buffers:
+ * the state is CS_LAYOUT_AOS [W][rows][13] only, a world holds up to 64 rows (one wavefront per world), the types are 0..8, the robot is
+ * holonomic.  Flag bits: CS_ALL_PARAMS_EQUAL, CS_ROBOT_ROW, CS_PARAMS_SHARED, CS_OBSTACLES_SHARED, CS_RESPAWN.  IEEE division and square
+ * root, the device library's double exp / atan2 / sin / cos (the two atan2 of Moussaid's theta_ij correctly rounded: their last bit decides
+ * its sign in a crowd at rest), no contraction and no float32 intermediate: a world tracks the float64 CPU
+ * restatement (oracle/sfm_step.inc) to ~1e-10 m over a 2000-substep episode, where a float32 world is centimetres to metres away.
+ *   cs_step_f64                    cs_step: n_substeps x { robot.step(action, dt) ; states[-1] = robot row ; update_humans ; respawn } in one
+ *                                  launch, in place.  d_action [W][2] (vx, vy) held for the block, or NULL.
+ *   cs_update_humans_parallel_f64  cs_update_humans_parallel: one substep of update_humans_parallel (forces_parallel.py:185-284) with its
+ *                                  in-place side effects on d_state / d_goals; d_out may equal w->d_state.  w->d_robot is ignored.
+ *   cs_peek_f64                    cs_peek: one step of dt into d_next [W][n][8] = x, y, yaw, Vx, Vy, Omega, Gx, Gy; state and goals untouched.
+ * Errors (CS_ERR_ARG with a message, before any device call): a type outside 0..8 ("Type <t> does not exist for this implementation", the
+ * reference's text), W, n or G < 1, more than 64 rows, n_substeps < 1, a null d_state / d_goals / d_params / d_safety, a layout other than
+ * CS_LAYOUT_AOS, CS_ROBOT_UNICYCLE, a bad obstacle description, an action without d_robot, a null output.
+ */
+typedef struct cs_worlds_f64 {
+    int32_t W;          /* worlds                                                                */
+    int32_t n;          /* humans per world (rows = n + 1 with CS_ROBOT_ROW; rows <= 64)         */
+    int32_t G;          /* goal slots per human                                                  */
+    int32_t O;          /* polygons (0 = no walls)                                               */
+    int32_t Smax;       /* segment slots per polygon                                             */
+    int32_t type;       /* 0..8                                                                  */
+    int32_t flags;      /* CS_* bits                                                             */
+    int32_t layout;     /* CS_LAYOUT_AOS                                                         */
+    double* d_state;    /* [W][rows][13]                  in/out                                 */
+    double* d_goals;    /* [W][n][G][2] NaN padded        in/out (rotated on goal switch)        */
+    const double* d_params;    /* [W][n][20] or [n][20]                                          */
+    const double* d_safety;    /* [W][rows]                                                      */
+    const double* d_obstacles; /* [W][O][Smax][2][2] or shared, NULL when O == 0                 */
+    double* d_robot;    /* [W][13] robot safe-state rows or NULL (as cs_worlds.d_robot)          */
+    const int32_t* d_world_flags; /* optional [W]: bit0 = respawn enabled in this world          */
+    double  respawn_bound_x, respawn_bound_y;
+} cs_worlds_f64;
+int cs_step_f64(const cs_worlds_f64* w, double dt, int n_substeps, const double* d_action, void* stream);
+int cs_update_humans_parallel_f64(const cs_worlds_f64* w, double dt, double* d_out, void* stream);
+int cs_peek_f64(const cs_worlds_f64* w, double dt, double* d_next /* [W][n][8] */, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "cs_gym_step_policy", "cs_gym_step_staged_policy", "cs_gym_step_policy_variant",
     "cs_value_net_pack", "cs_value_net_decide", "cs_value_net_pack_bf16", "cs_value_net_decide_bf16",
     "cs_value_net_decide_worlds", "cs_value_net_state",
+    "cs_step_f64", "cs_update_humans_parallel_f64", "cs_peek_f64",
 ]
 
 
@@ -82,6 +83,16 @@ class cs_worlds(C.Structure):
         ("d_orca_vertices", C.c_void_p), ("orca_n_vertices", C.c_int32),
         ("d_orca_agent_params", C.c_void_p),
         ("orca_math", C.c_int32),
+    ]
+
+
+class cs_worlds_f64(C.Structure):   # include/crowdstep.h cs_worlds_f64: float64 worlds (cs_step_f64, cs_update_humans_parallel_f64, cs_peek_f64)
+    _fields_ = [
+        ("W", C.c_int32), ("n", C.c_int32), ("G", C.c_int32), ("O", C.c_int32), ("Smax", C.c_int32),
+        ("type", C.c_int32), ("flags", C.c_int32), ("layout", C.c_int32),
+        ("d_state", C.c_void_p), ("d_goals", C.c_void_p), ("d_params", C.c_void_p), ("d_safety", C.c_void_p),
+        ("d_obstacles", C.c_void_p), ("d_robot", C.c_void_p), ("d_world_flags", C.c_void_p),
+        ("respawn_bound_x", C.c_double), ("respawn_bound_y", C.c_double),
     ]
 
 

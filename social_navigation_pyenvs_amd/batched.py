@@ -22,6 +22,21 @@ HUMAN_MODELS = SFMS + ["orca"]  # social_nav_gym.py:11-12
 CROWD_MODELS = HUMAN_MODELS + ["social_momentum"]
 # motion_model_manager.py:14  neighbor_dist, max_neighbors, time_horizon, time_horizon_obstacles
 ORCA_DEFAULTS = dict(neighbor_dist=10.0, max_neighbors=10, time_horizon=5.0, time_horizon_obst=5.0)
+# arithmetic of the resident worlds behind the reference-shaped seam: "f32" (CrowdWorlds, the default) or "f64" (CrowdWorlds64)
+PRECISIONS = ("f32", "f64")
+
+
+def check_precision(precision) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"world precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
+def default_precision() -> str:
+    """CROWDSTEP_PRECISION=f32|f64 if set, else "f32"."""
+    import os
+
+    return check_precision(os.environ.get("CROWDSTEP_PRECISION") or "f32")
 
 
 def _ptr(x) -> int | None:
@@ -463,3 +478,162 @@ class CrowdWorlds:
         st.d_robot = None if self.d_robot is None else DeviceBuffer(grow(self.d_robot.shape))
         st.d_world_flags = None if self.d_world_flags is None else DeviceBuffer(grow(self.d_world_flags.shape), np.int32)
         return st
+
+
+class CrowdWorlds64:
+    """W worlds x n humans (+ optional robot row) resident in HBM in FLOAT64 -- the reference's own precision (PRECISION =
+    np.float64) -- stepped by cs_step_f64 / cs_update_humans_parallel_f64 / cs_peek_f64 (csrc/sfmstep_f64.hip).
+
+    The arguments of ``CrowdWorlds`` that apply: SFM / HSFM ``type`` 0..8, up to 64 rows per world, AoS rows, a holonomic robot.
+    An opt-in arithmetic beside the float32 default: ORCA, social momentum, RK45, the robot's own models, the unicycle robot,
+    the laser and worlds beyond 64 rows stay float32 (``CrowdWorlds``)."""
+
+    MAX_ROWS = 64
+
+    def __init__(self, states, goals, params, safety=None, obstacles=None, *, type, all_params_equal=False, robot_row=False,
+                 robot=None, respawn_bounds=None, respawn_worlds=None, device=None, stream=None):
+        if isinstance(type, str):
+            if type not in SFMS:
+                raise NotImplementedError(f"float64 worlds cover the SFM / HSFM models {SFMS}, not {type!r}")
+            type = SFMS.index(type)
+        if type < 0 or type > 8:
+            raise ValueError(f"Type {type} does not exist for this implementation")
+        states = np.asarray(states, dtype=np.float64)
+        if states.ndim == 2:
+            states = states[None]
+        if states.shape[1] > self.MAX_ROWS:
+            raise NotImplementedError(f"float64 worlds hold up to {self.MAX_ROWS} rows (one wavefront per world), got {states.shape[1]}")
+        _lib.require_gpu()
+        if device is not None:
+            _lib.set_device(device)
+        self.type = int(type)
+        self.stream = stream
+        self.W, self.rows = states.shape[0], states.shape[1]
+        self.robot_row = bool(robot_row)
+        self.n = self.rows - int(self.robot_row)
+        goals = np.asarray(goals, dtype=np.float64)
+        if goals.ndim == 3:
+            goals = goals[None]
+        if goals.shape[0] != self.W or goals.shape[1] != self.n:
+            raise ValueError(f"goals shape {goals.shape} does not match W={self.W}, n={self.n}")
+        self.G = goals.shape[2]
+        params = np.asarray(params, dtype=np.float64)
+        self.params_shared = params.ndim == 2
+        if params.shape[-2:] != (self.n, 20):
+            raise ValueError(f"params must be [..., {self.n}, 20], got {params.shape}")
+        if safety is None:
+            safety = np.zeros((self.W, self.rows), dtype=np.float64)
+        safety = np.ascontiguousarray(np.broadcast_to(np.asarray(safety, dtype=np.float64), (self.W, self.rows)))
+        self.all_params_equal = bool(all_params_equal)
+        self.respawn_bounds = respawn_bounds
+        f64 = np.float64
+        self.d_state = DeviceBuffer.from_numpy(states, f64)
+        self.d_goals = DeviceBuffer.from_numpy(goals, f64)
+        self.d_params = DeviceBuffer.from_numpy(params, f64)
+        self.d_safety = DeviceBuffer.from_numpy(safety, f64)
+        self.O = self.Smax = 0
+        self.d_obstacles = None
+        self.obstacles_shared = True
+        if obstacles is not None:
+            obstacles = np.asarray(obstacles, dtype=np.float64)
+            self.obstacles_shared = obstacles.ndim == 4
+            self.O, self.Smax = obstacles.shape[-4], obstacles.shape[-3]
+            self.d_obstacles = DeviceBuffer.from_numpy(obstacles, f64)
+        self.d_robot = None
+        if robot is not None:
+            self.set_robot(robot)
+        self.d_world_flags = None
+        if respawn_worlds is not None:  # per-world respawn switch
+            wf = np.ascontiguousarray(np.broadcast_to(np.asarray(respawn_worlds), (self.W,)).astype(np.int32) & 1)
+            self.d_world_flags = DeviceBuffer.from_numpy(wf, dtype=np.int32)
+        self._scratch = {}
+
+    def descriptor(self, respawn=None) -> "_lib.cs_worlds_f64":
+        d = _lib.cs_worlds_f64()
+        d.W, d.n, d.G, d.O, d.Smax = self.W, self.n, self.G, self.O, self.Smax
+        d.type = self.type
+        f = 0
+        if self.all_params_equal:
+            f |= _lib.CS_ALL_PARAMS_EQUAL
+        if self.robot_row:
+            f |= _lib.CS_ROBOT_ROW
+        if self.params_shared:
+            f |= _lib.CS_PARAMS_SHARED
+        if self.obstacles_shared:
+            f |= _lib.CS_OBSTACLES_SHARED
+        if (self.respawn_bounds is not None) if respawn is None else respawn:
+            f |= _lib.CS_RESPAWN
+        d.flags = f
+        d.layout = _lib.CS_LAYOUT_AOS
+        d.d_state, d.d_goals, d.d_params, d.d_safety = _ptr(self.d_state), _ptr(self.d_goals), _ptr(self.d_params), _ptr(self.d_safety)
+        d.d_obstacles, d.d_robot, d.d_world_flags = _ptr(self.d_obstacles), _ptr(self.d_robot), _ptr(self.d_world_flags)
+        bx, by = self.respawn_bounds if self.respawn_bounds is not None else (0.0, 0.0)
+        d.respawn_bound_x, d.respawn_bound_y = float(bx), float(by)
+        return d
+
+    def _buffer(self, name, shape, dtype=np.float64) -> DeviceBuffer:
+        buf = self._scratch.get(name)
+        if buf is None or buf.shape != tuple(shape) or buf.dtype != np.dtype(dtype):
+            buf = DeviceBuffer(tuple(shape), dtype)
+            self._scratch[name] = buf
+        return buf
+
+    # ------------------------------------------------------------------ hot path
+    def update_humans_parallel(self, dt: float, in_place: bool = True):
+        """One substep, semantics of forces_parallel.py:185.  Returns the device buffer holding the updated rows (the state
+        buffer itself when ``in_place``)."""
+        d = self.descriptor(respawn=False)
+        out = self.d_state if in_place else DeviceBuffer(self.d_state.shape, np.float64)
+        check(_lib.load().cs_update_humans_parallel_f64(C.byref(d), C.c_double(dt), C.c_void_p(_ptr(out)), C.c_void_p(self.stream)))
+        return out
+
+    def step(self, dt: float, n_substeps: int = 1, action=None) -> None:
+        """n_substeps fused substeps (robot move + update_humans + respawn), in place.  ``action``: (vx, vy) per world, held."""
+        d = self.descriptor()
+        a_ptr = None
+        if action is not None:
+            if isinstance(action, (np.ndarray, list, tuple)):
+                act = np.ascontiguousarray(np.broadcast_to(np.asarray(action, dtype=np.float64), (self.W, 2)))
+                buf = self._buffer("action", act.shape)
+                buf.upload(act, self.stream)
+                a_ptr = buf.ptr
+            else:
+                a_ptr = _ptr(action)
+        check(_lib.load().cs_step_f64(C.byref(d), C.c_double(dt), C.c_int(n_substeps), C.c_void_p(a_ptr), C.c_void_p(self.stream)))
+
+    def peek(self, dt: float) -> np.ndarray:
+        """[W, n, 8] rows x, y, yaw, Vx, Vy, Omega, Gx, Gy of the next state; nothing is committed."""
+        d = self.descriptor(respawn=False)
+        out = self._buffer("peek", (self.W, self.n, 8))
+        check(_lib.load().cs_peek_f64(C.byref(d), C.c_double(dt), C.c_void_p(out.ptr), C.c_void_p(self.stream)))
+        return out.download(self.stream)
+
+    # ------------------------------------------------------------------ state access
+    def sync(self):
+        _lib.stream_sync(self.stream)
+
+    def get_states(self, buf=None) -> np.ndarray:
+        return (buf or self.d_state).download(self.stream).reshape(self.W, self.rows, 13)
+
+    def set_states(self, states) -> None:
+        self.d_state.upload(np.asarray(states, dtype=np.float64).reshape(self.W, self.rows, 13), self.stream)
+
+    def get_goals(self) -> np.ndarray:
+        return self.d_goals.download(self.stream)
+
+    def set_goals(self, goals) -> None:
+        self.d_goals.upload(np.asarray(goals, dtype=np.float64).reshape(self.W, self.n, self.G, 2), self.stream)
+
+    def get_robot(self) -> np.ndarray:
+        return self.d_robot.download(self.stream)
+
+    def set_robot(self, robot) -> None:
+        robot = np.ascontiguousarray(np.broadcast_to(np.asarray(robot, dtype=np.float64), (self.W, 13)))
+        if self.d_robot is None:
+            self.d_robot = DeviceBuffer.from_numpy(robot, np.float64)
+        else:
+            self.d_robot.upload(robot, self.stream)
+
+    def set_safety(self, safety) -> None:
+        safety = np.ascontiguousarray(np.broadcast_to(np.asarray(safety, dtype=np.float64), (self.W, self.rows)))
+        self.d_safety.upload(safety, self.stream)

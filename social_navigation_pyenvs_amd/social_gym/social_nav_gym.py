@@ -253,6 +253,10 @@ class BatchedSocialNavGym:
     ``social_gym.src.info.INFO_BY_CODE``).  Worlds are generated by the exact reference generators from
     seeds ``offset[phase] + case`` (one per world) through a scratch ``SocialNavGym``; every world needs the
     same human count and goal-slot count (a hybrid batch pads traffic goals with NaN).
+
+    This class is float32 whatever the world precision of the W = 1 facade (``SocialNavSim.set_world_precision``): its Gym head, device
+    generators and auto-reset are float32 kernels.  A batch of float64 worlds is ``batched.CrowdWorlds64`` with float64 initial states
+    from the host generators.
     """
 
     def __init__(self, config, n_worlds: int, robot_visible=False, robot_radius=None, headed_obs=False):

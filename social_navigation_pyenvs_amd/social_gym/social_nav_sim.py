@@ -70,6 +70,16 @@ class SocialNavSim:
             self.robot.policy.time_step = time_step
         self.robot_env_same_timestep = (self.sampling_time == self.robot_sampling_time)
 
+    def set_world_precision(self, precision: str):
+        """Arithmetic of the resident world behind motion_model_manager: "f32" (the default; CROWDSTEP_PRECISION overrides it) or
+        "f64" -- the reference's own float64 for update_humans, update_humans_block and get_next_human_observable_states of an Euler
+        SFM / HSFM crowd of up to 64 rows with a holonomic robot (everything else raises NotImplementedError).  Kept across reset_sim."""
+        from ..batched import check_precision
+
+        self.world_precision = check_precision(precision)
+        if getattr(self, "motion_model_manager", None) is not None:
+            self.motion_model_manager.precision = self.world_precision
+
     # ------------------------------------------------------------------ reset (:97-198)
     def reset_sim(self, restart_gui=False, reset_robot=True):
         cfg = self.config_data
@@ -106,6 +116,8 @@ class SocialNavSim:
             robot_model, robot_rk = self._pending_robot_model   # asked for before the first world existed
         self.motion_model_manager = MotionModelManager(self.motion_model, self.robot_visible, self.runge_kutta, self.humans,
                                                        self.robot, self.walls, parallelize=self.parallelize_humans)
+        if getattr(self, "world_precision", None) is not None:   # set_world_precision: kept across resets
+            self.motion_model_manager.precision = self.world_precision
         self.robot_controlled = False
         if robot_model is not None:
             self.motion_model_manager.set_robot_motion_model(robot_model, robot_rk)

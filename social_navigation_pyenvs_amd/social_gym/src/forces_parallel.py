@@ -11,23 +11,37 @@ Like the reference, the call mutates its inputs in place: ``goals`` rows are rot
 reached, ``agents_state[:, 10:12]`` follows, and for the headed types ``agents_state[:, 3:5]`` receives
 ``R(theta) @ body_velocity`` (forces_parallel.py:231-234, 256).  Host arrays travel over PCIe on every
 call; resident worlds (``batched.CrowdWorlds`` / ``MotionModelManager``) avoid that.
+
+``precision``: "f32" (the float32 kernels) or "f64" (``cs_update_humans_parallel_f64``: the reference's own float64, worlds of up
+to 64 rows, no float32 round trip of the caller's arrays); None = ``CROWDSTEP_PRECISION`` if set, else "f32".
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ...batched import CrowdWorlds
+from ...batched import CrowdWorlds, CrowdWorlds64, check_precision, default_precision
 
 
 def update_humans_parallel(type: int, agents_state: np.ndarray, goals: np.ndarray, obstacles, agents_params: np.ndarray,
-                           dt: float, safety_space: np.ndarray, all_params_equal=False, last_is_robot=False):
+                           dt: float, safety_space: np.ndarray, all_params_equal=False, last_is_robot=False, precision=None):
     if type < 0 or type > 8:
         raise ValueError(f"Type {type} does not exist for this implementation")
+    precision = default_precision() if precision is None else check_precision(precision)
     single = agents_state.ndim == 2
     S = agents_state[None] if single else agents_state
     G = goals[None] if single else goals
     P = agents_params
     saf = safety_space[None] if (single and safety_space is not None) else safety_space
+    if precision == "f64":
+        cw = CrowdWorlds64(S, G, P, saf, obstacles, type=type, all_params_equal=all_params_equal, robot_row=last_is_robot)
+        out = cw.get_states(cw.update_humans_parallel(dt, in_place=False)).astype(agents_state.dtype)
+        s_in = cw.get_states()
+        n = S.shape[1] - int(bool(last_is_robot))
+        S[:, :n, 10:12] = s_in[:, :n, 10:12]
+        if type >= 3:
+            S[:, :n, 3:5] = s_in[:, :n, 3:5]
+        G[...] = cw.get_goals()   # the device rotated the caller's own float64 values
+        return out[0] if single else out
     cw = CrowdWorlds(S, G, P, saf, obstacles, type=type, all_params_equal=all_params_equal, robot_row=last_is_robot)
     out_buf = cw.update_humans_parallel(dt, in_place=False)
     out = cw.get_states(out_buf).astype(agents_state.dtype)

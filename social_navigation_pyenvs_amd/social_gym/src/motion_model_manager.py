@@ -11,7 +11,8 @@ Reference: social_gym/src/motion_model_manager.py.  Same constructor, attributes
   update_goals / rewind_goals / bound_velocity                :52-70
 
 plus ``update_humans_block(dt, n_substeps, action)``: the substep loop of SocialNavGym.step fused in
-one kernel launch.  The arithmetic runs in libcrowdstep.so on the GPU (float32); the numpy arrays kept
+one kernel launch.  The arithmetic runs in libcrowdstep.so on the GPU (float32, or float64 with ``precision = "f64"`` for the
+Euler SFM / HSFM crowd: SocialNavSim.set_world_precision); the numpy arrays kept
 here are float64 mirrors refreshed after every call, and each ``HumanAgent`` holds views into
 ``self.states`` exactly as in the reference (agent.py:260-266).  Out of scope on this path, as in the
 Gym env: RK45 integration, social momentum, the robot's own SFM / ORCA policies (they raise).
@@ -21,7 +22,7 @@ from __future__ import annotations
 import numpy as np
 
 from ... import _lib
-from ...batched import CrowdWorlds, HUMAN_MODELS, ORCA_DEFAULTS as _ORCA, SFMS
+from ...batched import CrowdWorlds, CrowdWorlds64, HUMAN_MODELS, ORCA_DEFAULTS as _ORCA, SFMS, check_precision, default_precision
 from .agent import Agent
 from .forces_parallel import mirror_goal_rotation
 from .utils import PRECISION, bound_angle
@@ -48,6 +49,9 @@ class MotionModelManager:
         self.parallel_traffic_humans_respawn = False
         self.respawn_bounds = None
         self._cw = None
+        # arithmetic of the resident world: "f32", or "f64" = the reference's own float64 (CrowdWorlds64) for update_humans,
+        # update_humans_block and get_next_human_observable_states of an Euler SFM / HSFM crowd (SocialNavSim.set_world_precision)
+        self.precision = default_precision()
         self.set_human_motion_model(motion_model_title)
         self.robot_motion_model_title = None
 
@@ -245,6 +249,77 @@ class MotionModelManager:
                              verts=None if verts is None else np.array(verts, copy=True))
         return self._cw
 
+    # ------------------------------------------------------------------ float64 worlds (precision == "f64")
+    def _f64(self) -> bool:
+        return check_precision(self.precision) == "f64"
+
+    def _f64_refuse(self, unicycle=False) -> None:
+        """What float64 worlds do not cover raises here, before anything touches the device."""
+        limit = None
+        if self.orca or self.sm:
+            limit = "ORCA and social-momentum crowds (RVO2 is float32 itself)"
+        elif self.runge_kutta:
+            limit = "RK45 integration"
+        elif self.robot_motion_model_title is not None:
+            limit = "a robot under a human motion model"
+        elif unicycle:
+            limit = "a unicycle robot"
+        elif self.robot is not None and getattr(self.robot, "laser", None) is not None:
+            limit = "the laser"
+        elif self.states.shape[0] > CrowdWorlds64.MAX_ROWS:
+            limit = f"worlds beyond {CrowdWorlds64.MAX_ROWS} rows (this one has {self.states.shape[0]})"
+        if limit is not None:
+            raise NotImplementedError(f'world precision "f64" does not cover {limit}: float64 worlds step Euler SFM / HSFM crowds of up to '
+                                      f'{CrowdWorlds64.MAX_ROWS} rows with a holonomic robot; use set_world_precision("f32")')
+
+    def _device64(self, respawn: bool = None) -> CrowdWorlds64:
+        """_device() for the float64 world: the host mirrors go up as they are (no float32 round trip), into the buffers of the
+        previous call when nothing about their shapes or the kernel build changed."""
+        if self.consider_robot:
+            self.states[-1] = self.robot.get_safe_state()
+        robot_rows = self.robot.get_safe_state() if (self.robot is not None and len(self.robot.goals) > 0) else None
+        if respawn is None:
+            respawn = self.parallel_traffic_humans_respawn
+        bounds = self.respawn_bounds if respawn else None
+        sig = (self.states.shape, self.goals.shape, int(self.sfm_type), bool(self.all_equal_humans), bool(self.consider_robot), robot_rows is not None,
+               None if self.obstacles is None else np.shape(self.obstacles), np.shape(self.params))
+        cw = getattr(self, "_cw64", None)
+        if cw is not None and getattr(self, "_cw64_sig", None) == sig:
+            cw.set_states(self.states)
+            cw.set_goals(self.goals)
+            if robot_rows is not None:
+                cw.set_robot(robot_rows)
+            held = self._cw64_held
+            if not np.array_equal(self.safety_space, held["margin"]):
+                cw.set_safety(self.safety_space); held["margin"] = np.array(self.safety_space, copy=True)
+            if not np.array_equal(self.params, held["params"]):
+                cw.d_params.upload(np.asarray(self.params, dtype=np.float64).reshape(cw.d_params.shape), cw.stream); held["params"] = np.array(self.params, copy=True)
+            if self.obstacles is not None and not np.array_equal(self.obstacles, held["obstacles"], equal_nan=True):
+                cw.d_obstacles.upload(np.asarray(self.obstacles, dtype=np.float64), cw.stream); held["obstacles"] = np.array(self.obstacles, copy=True)
+            cw.respawn_bounds = bounds
+            return cw
+        self._cw64 = CrowdWorlds64(self.states, self.goals, self.params, self.safety_space, self.obstacles, type=self.sfm_type,
+                                   all_params_equal=self.all_equal_humans, robot_row=self.consider_robot, robot=robot_rows, respawn_bounds=bounds)
+        self._cw64_sig = sig
+        self._cw64_held = dict(margin=np.array(self.safety_space, copy=True), params=np.array(self.params, copy=True),
+                               obstacles=None if self.obstacles is None else np.array(self.obstacles, copy=True))
+        return self._cw64
+
+    def _readback64(self, cw: CrowdWorlds64, robot_moved=False):
+        new = cw.get_states()[0]
+        n = len(self.humans)
+        self.states[:n, 0:8] = new[:n, 0:8]
+        self.states[:n, 10:12] = new[:n, 10:12]
+        if self.consider_robot:
+            self.states[n] = new[n]
+        self.goals[...] = cw.get_goals()[0]   # the device rotated the mirror's own float64 values
+        self._sync_goal_lists_from_array()
+        if robot_moved:
+            rb = cw.get_robot()[0]
+            self.robot.position = rb[0:2].copy()
+            self.robot.yaw = float(rb[2])
+            self.robot.linear_velocity = rb[3:5].copy()
+
     def _readback(self, cw: CrowdWorlds, robot_moved=False):
         new = cw.get_states()[0].astype(PRECISION)
         n = len(self.humans)
@@ -269,6 +344,12 @@ class MotionModelManager:
     def update_humans(self, t: float, dt: float, post_update=True):
         """One substep of every human (:354-422): Euler SFM / HSFM, or ORCA; parallel-traffic respawn when
         ``post_update``."""
+        if self._f64():
+            self._f64_refuse()
+            cw = self._device64(respawn=bool(post_update and self.parallel_traffic_humans_respawn))
+            cw.step(dt, 1, None)
+            self._readback64(cw)
+            return
         if self.runge_kutta and not (self.orca or self.sm):   # RK45 of the SFM / HSFM crowd (:374-384); ORCA is Euler only
             cw = self._device(respawn=bool(post_update and self.parallel_traffic_humans_respawn))   # respawn behind the solve (:405-422)
             if not hasattr(self, "_desired_force"):   # agent.desired_force of the single-agent force functions (forces.py:12-16)
@@ -291,6 +372,8 @@ class MotionModelManager:
         """ONE adaptive RK45 solve over (t, t + final_time) with the solution sampled at np.arange(t, final_time, dt) through the
         solver's dense output (:461-498) -> human_states [len(times), n, 6 | 4] (x, y, yaw, BVx, BVy, Omega | x, y, Vx, Vy).  The humans
         are left as the last right-hand-side evaluation leaves them (the state at t + final_time), like the reference's."""
+        if self._f64():
+            self._f64_refuse()
         if not self.runge_kutta or self.orca or self.sm:
             raise ValueError("complete_rk45_simulation integrates an SFM / HSFM crowd created with runge_kutta=True")
         times = np.arange(t, final_time, dt, dtype=PRECISION)
@@ -308,6 +391,12 @@ class MotionModelManager:
     def update_humans_block(self, dt: float, n_substeps: int, action=None, unicycle=False):
         """``n_substeps`` x { robot.step(action, dt) ; update_humans(t, dt) } fused in one launch -- the loop of
         SocialNavGym.step (social_nav_gym.py:240-245).  ``action``: (vx, vy) or (v, r) for a unicycle robot."""
+        if self._f64():
+            self._f64_refuse(unicycle=bool(unicycle))
+            cw = self._device64()
+            cw.step(dt, n_substeps, None if action is None else np.asarray(action, dtype=np.float64).reshape(1, 2))
+            self._readback64(cw, robot_moved=action is not None)
+            return
         if self.runge_kutta and not (self.orca or self.sm):
             raise NotImplementedError("the fused Gym block is Euler (SocialNavGym never sets runge_kutta, social_nav_gym.py:141-143); "
                                       "call update_humans(t, dt) for RK45")
@@ -362,8 +451,11 @@ class MotionModelManager:
     def get_next_human_observable_states(self, dt: float, theta_and_omega_visible=False):
         """Next human states after ONE Euler step of size dt, without committing it (:691-709).
         [N, 4] = px, py, vx, vy  or  [N, 8] = x, y, yaw, Vx, Vy, Omega, Gx, Gy."""
-        cw = self._device()
-        nxt = cw.peek(dt)[0].astype(PRECISION)
+        if self._f64():
+            self._f64_refuse()
+            nxt = self._device64().peek(dt)[0]
+        else:
+            nxt = self._device().peek(dt)[0].astype(PRECISION)
         if self.headed:  # set_human_states(saved) recomputes the linear velocity from the body velocity (:324,333)
             n = len(self.humans)
             c, s = np.cos(self.states[:n, 2]), np.sin(self.states[:n, 2])
@@ -459,6 +551,8 @@ class MotionModelManager:
 
     def update_robot(self, t, dt, just_velocities=False):
         """One substep of the robot under its motion model (:615-653)."""
+        if self._f64():
+            self._f64_refuse()
         cw = self._device_with_robot_model()
         if getattr(self, "robot_runge_kutta", False) and not self.robot_orca:
             if just_velocities:   # the reference's own error (:631)
@@ -471,6 +565,8 @@ class MotionModelManager:
     def imitation_block(self, dt: float, n_substeps: int):
         """``n_substeps`` x { update_robot(t, dt) ; update_humans(t, dt) } without leaving the device -- the loop of
         SocialNavGym.imitation_learning_step (social_nav_gym.py:259-263)."""
+        if self._f64():
+            self._f64_refuse()
         cw = self._device_with_robot_model()
         if getattr(self, "robot_runge_kutta", False) and not self.robot_orca:
             # the robot under RK45 (:631-640): one solve over dt per substep with the humans standing, then the crowd's Euler substep --
