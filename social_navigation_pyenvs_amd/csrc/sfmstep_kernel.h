@@ -147,20 +147,37 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     // base priority 1: above the generator's wavefronts of a refill pass on the side stream (priority 0, and OLDER than any of mine, so a tie
     // would go to them): the Gym step in NEXT_STEP mode 43.3 -> 41.5 us, a plain launch unchanged
     if constexpr (MAXT == 64) __builtin_amdgcn_s_setprio(1);
-    for (int sub = 0; sub < a.nsub; ++sub) {
-        // head of a substep: priority turn, recorders (imitation snapshot, cs_step_trace), the robot under its own motion model (LEAN = 4), partner-row fetch helpers, the goal switch
-#include "sfmstep_sub_head.inc"
-        // part A: what does not depend on this substep's social force -- the wall pairs' pass, refreshed velocity, desired force, the all-lanes wall pass, heading and torque
-#include "sfmstep_sub_part_a.inc"
-        // the pair-once loop (each unordered pair evaluated once, reaction handed over through LDS), the reaction sum, and the contact pass behind a wave vote
-#include "sfmstep_sub_pairloop.inc"
-        // all partners per lane (per-agent parameters on Moussaid, worlds of more than one wavefront), part B: total force, body frame, torque, the Euler step, the rows published for the next substep
-#include "sfmstep_sub_tail.inc"
-        // the parallel-traffic respawn rule, sequential inside a world, by wave ballot
-#include "sfmstep_sub_respawn.inc"
-        STAMP(5);
-        LDS_ORDER_FENCE(); // rows republished by the respawn rule are read by other lanes in the next substep
-        cur = nxt;
+    // The plain one-wavefront builds with a compile-time row count run the substep loop inside ONE exec region: human == valid in them (no robot
+    // row, n == rows), and the lanes outside are the idle ones behind the last world plus those of a ragged last wavefront.  Stated phase by
+    // phase, `if (valid)` / `if (human)` opened four regions per substep -- a saveexec / branch pair each, and a default (a v_mov) for every
+    // value live out of one.  Inside the region the fragments see both as compile-time `true`.  What is at loop scope outside those regions
+    // is wave-uniform (priority turn, recorders' scalar test, stamps, the buffer index) or tests its lanes itself (the goal switch, the
+    // respawn flag); the ballots of the contact passes and of the respawn rule were taken inside `if (valid)` / `if (flag)` before.
+    // Same bits in every build it reaches; 4096 x 25: 27.06 -> 26.50 us per launch, 25 scalar instructions and 7 exec regions fewer per
+    // substep.  (Two substeps per trip with the buffer index and the priority turn as constants of each half measured 26.56 us and moved
+    // the compiler's contraction choices, i.e. the bits: HISTORY.md.)
+    constexpr bool ONE_REGION = MAXT == 64 && LEAN == LEAN_PLAIN && ROWS_CT > 0;
+    // ... and carry the refreshed linear velocity (part A: R(theta) bv) from the tail, which forms the new stored velocity from the same
+    // operands by the same expression -- in x also by the same instructions, in y with the other product rounded first (the compiler's
+    // contraction; sfmstep_sub_tail.inc writes both out as they have always been compiled, so that no bit moves).  Substep 0 forms it from
+    // the INCOMING row (whose stored velocity may differ), the respawn rule -- which overwrites bvy (motion_model_manager.py:421) behind
+    // the tail -- forms it again.
+    constexpr bool CARRY_CV = ONE_REGION && HEADED > 0;
+    float cvx_c = vx, cvy_c = vy;
+    if constexpr (ONE_REGION) {
+        if (valid) {
+            constexpr bool valid = true, human = true;   // (shadow the lane tests: this region holds the valid lanes only)
+            if constexpr (CARRY_CV) { cvx_c = fmaf(cs, bvx, -(sn * bvy)); cvy_c = fmaf(cs, bvy, sn * bvx); }
+            for (int sub = 0; sub < a.nsub; ++sub) {
+#include "sfmstep_substep.inc"
+                cur = nxt;
+            }
+        }
+    } else {
+        for (int sub = 0; sub < a.nsub; ++sub) {
+#include "sfmstep_substep.inc"
+            cur = nxt;
+        }
     }
 #ifdef CS_STAMPS
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_loop_end)::"memory");

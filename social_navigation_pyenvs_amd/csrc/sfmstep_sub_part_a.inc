@@ -86,10 +86,11 @@
         // -- part A of the per-agent update: everything that does not need this substep's social force
         const float c = cs, s = sn;          // rotation matrix of the incoming heading, :254-256
         float cvx = vx, cvy = vy;            // refreshed linear velocity
+        if constexpr (CARRY_CV) { cvx = cvx_c; cvy = cvy_c; }   // (carried from the previous substep's tail: sfmstep_kernel.h)
         float fdx = 0.0f, fdy = 0.0f, fox = 0.0f, foy = 0.0f;
         float th_n = th, sn_n = sn, cs_n = cs, torque_a = 0.0f;
         if (human) {
-            if constexpr (HEADED > 0) {
+            if constexpr (HEADED > 0 && !CARRY_CV) {
                 cvx = c * bvx + (-s) * bvy;
                 cvy = s * bvx + c * bvy;
             }

@@ -44,6 +44,7 @@
                     publish(nxt);
                     g0y = py;               // human.set_goals([[goals[0][0], position[1]]])   :418
                     bvy = g0x; om = g0y;    // states[i,6:8] = goal  (reference writes cols 6:8) :421
+                    if constexpr (CARRY_CV) { cvx_c = fmaf(cs, bvx, -(sn * bvy)); cvy_c = fmaf(cs, bvy, sn * bvx); }   // (the carried refreshed velocity saw the old bvy)
                     for (int g = 0; g < a.G; ++g) { gi[2 * g] = g0x; gi[2 * g + 1] = g0y; } //   :422
                     gk = a.G; g1x = g0x; g1y = g0y;
                 }

@@ -130,8 +130,18 @@
                 if (nb2 * ninv > vd) { const float sc = vd * ninv; bvx *= sc; bvy *= sc; }
                 om = fmaf(torque, dt_inertia, om);
                 sn = sn_n; cs = cs_n;
+                if constexpr (CARRY_CV) {
+                    // The stored velocity and the next substep's refreshed velocity are the same expression of the same operands, but not
+                    // the same bits: the compiler contracts a b + c d into fma(a, b, c d) or fma(c, d, a b) as it sees fit, and chose
+                    // differently for the y component here and in part A.  Both are written out as it chose them (the bits of every build
+                    // so far), so x is carried and y costs one multiply and one FMA instead of two of each.
+                    vx = fmaf(cs, bvx, -(sn * bvy));
+                    vy = fmaf(sn, bvx, cs * bvy);
+                    cvx_c = vx; cvy_c = fmaf(cs, bvy, sn * bvx);
+                } else {
                 vx = cs * bvx + (-sn) * bvy;
                 vy = sn * bvx + cs * bvy;
+                }
             } else {
                 vx = fmaf(gfx, dt_m, vx); vy = fmaf(gfy, dt_m, vy);
                 const float nb2 = fmaf(vx, vx, vy * vy);
