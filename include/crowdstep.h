@@ -659,6 +659,37 @@ int cs_value_net_state(int kind, const int32_t* dims, int n_dims, const float* d
                        float* d_values, void* stream);
 
 /*
+ * cs_occupancy_maps  OM-SARL's local occupancy maps (crowd_nav/policy/multi_human_rl.py:133-187 build_occupancy_maps) for W worlds in
+ *   one kernel on `stream` (csrc/occupancy_map.hip).  d_humans [W][n][stride] holds a human's position at columns 0, 1
+ *   and its velocity at vel_col, vel_col + 1: cs_lookahead's d_next [W][n][4|6] (vel_col 2 | 3) and d_current [W][n][5|7] (vel_col 2)
+ *   are read in place.  d_maps [W][n][C], C = cell_num^2 * channels, laid out [cell][channel]: for centre human i and every other human j
+ *   of its world, d = p_j - p_i is taken into the frame whose x axis is v_i (the world's frame when v_i = 0), its cell is
+ *   cell_num * floor(y / cell_size + cell_num / 2) + floor(x / cell_size + cell_num / 2) when both indices lie in 0..cell_num-1 (a NaN
+ *   lies nowhere; a coincident pair is (0, 0)).  channels 1: 1 for an occupied cell, else 0;  2: the mean of the members' velocities in
+ *   that frame, (0, 0) for an empty cell;  3: (occupied, mean vx, mean vy).  The means are summed in ascending j by one lane per cell:
+ *   no atomics, and a world gives the same bits for W = 1 as inside any batch.  n = 1 writes zeros.  float32.
+ *   Errors (CS_ERR_ARG, before any device call): W or n < 1, null pointers, stride < 4, vel_col outside 2..stride-2, cell_num < 1,
+ *   cell_size not > 0, channels outside 1..3, C > 241 (so that 15 + C <= 256, the widest layer input), W * n * C beyond an int.
+ * cs_value_net_decide_om  cs_value_net_decide for OM-SARL (sarl.with_om = true; csrc/value_net_om.hip): row (w, a, j) of the network's
+ *   input is d_rotated[w][a][j][0..cols) followed by d_maps[w][j][0..om_cols) -- one map row serves the A actions of its world, the
+ *   maps are never expanded A-fold.  Every other argument, the results, the two kernels on `stream`, the position independence and the
+ *   errors are cs_value_net_decide's, the LDS-fit check made for this kernel's own LDS (its input tile has rows of cols + om_cols rounded
+ *   up to 8, plus 4 floats).  d_weights is cs_value_net_pack_om's blob.  float32, CS_VN_SARL only.  mlp3's self state is still the first
+ *   six columns of the first human's row.
+ * cs_value_net_pack_om  (host only) cs_value_net_pack for a SARL network whose mlp1 reads cols + om_cols columns: the same layout, the
+ *   first layer with ceil((cols + om_cols) / 8) k-groups.
+ *   Further errors of both (CS_ERR_ARG): kind != CS_VN_SARL, om_cols < 1, cols + om_cols > 256, a null d_maps.
+ */
+int cs_occupancy_maps(int W, int n, const float* d_humans, int stride, int vel_col, int cell_num, float cell_size, int channels,
+                      float* d_maps /* [W][n][cell_num^2 * channels] */, void* stream);
+int cs_value_net_pack_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* const* params, float* blob,
+                         size_t* n_floats);
+int cs_value_net_decide_om(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                           int cols, int om_cols, const float* d_rotated, const float* d_maps, const float* d_rewards,
+                           const float* d_actions, const float* d_robot, int robot_stride, float gamma, float dt,
+                           const int32_t* d_override, float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * Float64 worlds (csrc/sfmstep_f64.hip): the SFM / HSFM substep in the reference's own precision (PRECISION = np.float64),
  * an opt-in arithmetic beside the float32 entries above.  cs_worlds_f64 carries the fields of cs_worlds that apply, with double buffers:
  * the state is CS_LAYOUT_AOS [W][rows][13] only, a world holds up to 64 rows (one wavefront per world), the types are 0..8, the robot is

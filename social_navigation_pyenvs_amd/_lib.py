@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "cs_gym_step_policy", "cs_gym_step_staged_policy", "cs_gym_step_policy_variant",
     "cs_value_net_pack", "cs_value_net_decide", "cs_value_net_pack_bf16", "cs_value_net_decide_bf16",
     "cs_value_net_decide_worlds", "cs_value_net_state",
+    "cs_occupancy_maps", "cs_value_net_pack_om", "cs_value_net_decide_om",
     "cs_step_f64", "cs_update_humans_parallel_f64", "cs_peek_f64",
 ]
 

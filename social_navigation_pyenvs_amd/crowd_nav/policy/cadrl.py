@@ -185,7 +185,7 @@ class CADRL(Policy):
         (bf16 matrix instructions behind the first layer, float32 accumulation and reductions)."""
         from .value_net import check_decision_input, check_precision
 
-        check_decision_input(self.decision_input, check_precision(precision))
+        check_decision_input(self.decision_input, check_precision(precision), self.map_columns())
         self.decision_precision = precision
 
     def set_decision_input(self, decision_input):
@@ -194,7 +194,7 @@ class CADRL(Policy):
         the rows in LDS from the worlds' own rows, bit for bit the same decision).  "fused" is float32 only."""
         from .value_net import check_decision_input
 
-        self.decision_input = check_decision_input(decision_input, self.decision_precision)
+        self.decision_input = check_decision_input(decision_input, self.decision_precision, self.map_columns())
 
     def build_action_space(self, v_pref):
         """(0, 0) plus rotation_samples headings x speed_samples exponentially spaced speeds up to v_pref."""
@@ -205,12 +205,19 @@ class CADRL(Policy):
         self.action_space = [ActionXY(float(vx), float(vy)) for vx, vy in self.action_space_ndarray]
 
     # ------------------------------------------------------------------ the decision
-    def device_net(self):
-        """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
+    def map_columns(self):
+        """Occupancy-map columns behind the rotated ones in a network input row: none but for OM-SARL."""
+        return 0
+
+    def _new_device_net(self, model):
         from .value_net import DeviceNet
 
+        return DeviceNet(model, self.joint_state_dim)
+
+    def device_net(self):
+        """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
         if self._net is None or self._net.model is not self.model:
-            self._net = DeviceNet(self.model, self.joint_state_dim)
+            self._net = self._new_device_net(self.model)
         self._net.refresh(self.decision_precision)
         return self._net
 
@@ -220,15 +227,13 @@ class CADRL(Policy):
         """The float32 DeviceNet that evaluates states (cs_value_net_state) with ``model``'s weights -- None: the policy's own module, the
         DeviceNet of ``device_net()``.  Another module (a trainer's deep-copied target network) must have the policy's architecture; its
         DeviceNet is kept per module, apart from the policy's own, and repacked only after a parameter changed."""
-        from .value_net import DeviceNet
-
         if self._net is None or self._net.model is not self.model:
-            self._net = DeviceNet(self.model, self.joint_state_dim)
+            self._net = self._new_device_net(self.model)
         net = own = self._net
         if model is not None and model is not self.model:
             net = next((kept for kept in self._state_nets if kept.model is model), None)
             if net is None:
-                net = DeviceNet(model, self.joint_state_dim)
+                net = self._new_device_net(model)
                 if net.kind != own.kind or not np.array_equal(net.dims, own.dims):
                     raise ValueError(f"{self.name}: the module to evaluate has another architecture than the policy's "
                                      f"({net.dims.tolist()} against {own.dims.tolist()})")

@@ -9,7 +9,7 @@ from .cadrl import CADRL, joint_rows
 
 class MultiHumanRL(CADRL):
     def input_dim(self):
-        """Columns of one network input row.  Occupancy maps would widen it; they are not available here (SARL.configure raises)."""
+        """Columns of one network input row.  OM-SARL (om_sarl.py) widens it by its occupancy maps."""
         return self.joint_state_dim
 
     def transform(self, state):

@@ -1,6 +1,7 @@
 """policy_factory with the reference's keys (crowd_nav/policy/policy_factory.py): the no-train policies plus the trained value-based ones."""
 from ..policy_no_train.policy_factory import policy_factory as _no_train
 from .cadrl import CADRL
+from .om_sarl import OMSARL
 from .sarl import SARL
 
 
@@ -12,4 +13,5 @@ def lstm_rl(*args, **kwargs):
 policy_factory = dict(_no_train)
 policy_factory["cadrl"] = CADRL
 policy_factory["sarl"] = SARL
+policy_factory["om_sarl"] = OMSARL
 policy_factory["lstm_rl"] = lstm_rl

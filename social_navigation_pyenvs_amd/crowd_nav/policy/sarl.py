@@ -53,8 +53,8 @@ class SARL(MultiHumanRL):
         section = self.config_section
         self.with_om = config.getboolean(section, "with_om")
         if self.with_om:
-            raise NotImplementedError("OM-SARL (sarl.with_om = true) is not available: the occupancy maps of the humans' neighbourhoods are "
-                                      "not computed on the device and the decision kernel takes 13- or 15-column rows only")
+            raise NotImplementedError("OM-SARL (sarl.with_om = true) is a policy of its own here: the rows widened by the humans' occupancy maps "
+                                      "have their own decision kernel; build it with policy_factory[\"om_sarl\"]")
         widths = {key: width_list(config.get(section, key)) for key in ("mlp1_dims", "mlp2_dims", "mlp3_dims", "attention_dims")}
         self.model = ValueNetwork(self.input_dim(), self.self_state_dim, widths["mlp1_dims"], widths["mlp2_dims"], widths["mlp3_dims"],
                                   widths["attention_dims"], config.getboolean(section, "with_global_state"))

@@ -9,6 +9,10 @@ Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_v
 own blob; a policy chooses with ``set_decision_precision``.  Two inputs: "tensor", the default (cs_lookahead's rows in HBM), and the opt-in
 "fused" (``decide_worlds``: cs_value_net_decide_worlds generates the rows in the kernel, float32 only); ``set_decision_input``.
 
+OM-SARL (crowd_nav/policy/om_sarl.py) widens every human's row by its occupancy map: a ``DeviceNet`` with ``om_cols`` > 0 packs through
+cs_value_net_pack_om, ``occupancy_maps`` is cs_occupancy_maps, ``decide_om`` cs_value_net_decide_om (csrc/value_net_om.hip), and
+``decide_for_worlds`` runs lookahead -> occupancy_maps(next humans) -> decide_om for such a net; float32 on the look-ahead tensor only.
+
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes."""
 from __future__ import annotations
@@ -28,11 +32,15 @@ def check_precision(precision):
     return precision
 
 
-def check_decision_input(decision_input, precision):
+def check_decision_input(decision_input, precision, om_cols=0):
     """The pair (decision input, precision) a policy may hold: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel,
-    no look-ahead tensor) exists for the float32 arithmetic only."""
+    no look-ahead tensor) exists for the float32 arithmetic only.  A network with occupancy-map columns (``om_cols`` > 0) has the one
+    kernel cs_value_net_decide_om: float32 on the look-ahead tensor."""
     if decision_input not in DECISION_INPUTS:
         raise ValueError(f"decision input {decision_input!r}: one of {', '.join(map(repr, DECISION_INPUTS))}")
+    if om_cols and (decision_input == "fused" or check_precision(precision) == "bf16"):
+        raise ValueError(f'decision input {decision_input!r} with decision precision {precision!r} for a network with occupancy-map columns: no '
+                         'kernel pairs the map columns with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"')
     if decision_input == "fused" and check_precision(precision) == "bf16":
         raise ValueError('decision input "fused" with decision precision "bf16": the bf16 kernel has its own tile loader and reads the '
                          'look-ahead tensor; choose "tensor" or "f32"')
@@ -58,19 +66,24 @@ def describe(model):
     return CS_VN_SARL, np.array(dims, np.int32), layers
 
 
-def pack(kind, dims, cols, arrays, precision="f32"):
+def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     """The kernel's weight blob from [weight_0, bias_0, weight_1, ...] float32 arrays: float32 numpy for "f32", the bytes (uint8 numpy)
-    of cs_value_net_pack_bf16's layout for "bf16".  Host only: no GPU needed."""
+    of cs_value_net_pack_bf16's layout for "bf16"; with ``om_cols`` > 0 cs_value_net_pack_om's (float32 only: mlp1 reads cols + om_cols
+    columns).  Host only: no GPU needed."""
     from ... import _lib
 
     lib = _lib.load()
+    if om_cols:
+        check_decision_input("tensor", precision, om_cols)
+        return _pack_with(lib.cs_value_net_pack_om, np.float32, kind, dims, cols, arrays, om_cols)
     if check_precision(precision) == "bf16":
         return _pack_with(lib.cs_value_net_pack_bf16, np.uint8, kind, dims, cols, arrays)
     return _pack_with(lib.cs_value_net_pack, np.float32, kind, dims, cols, arrays)
 
 
-def _pack_with(entry, unit, kind, dims, cols, arrays):
-    """The size query and the packing call of one of the two pack entries; `unit`: what the entry counts its blob in."""
+def _pack_with(entry, unit, kind, dims, cols, arrays, om_cols=None):
+    """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `om_cols`: the argument
+    cs_value_net_pack_om takes behind cols."""
     from ... import _lib
 
     dims = np.ascontiguousarray(dims, np.int32)
@@ -78,18 +91,22 @@ def _pack_with(entry, unit, kind, dims, cols, arrays):
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
     d = dims.ctypes.data_as(C.c_void_p)
-    _lib.check(entry(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), None, None, C.byref(nf)))
+    head = (C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols)) + (() if om_cols is None else (C.c_int(om_cols),))
+    _lib.check(entry(*head, None, None, C.byref(nf)))
     blob = np.zeros(nf.value, unit)
-    _lib.check(entry(C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols), ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
+    _lib.check(entry(*head, ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
     return blob
 
 
 class DeviceNet:
     """A policy's network as the kernel reads it: description + one packed blob per precision in HBM, each rebuilt when the module's
-    parameters changed (the same version-counter key for both).  ``blob`` is the float32 one."""
+    parameters changed (the same version-counter key for both).  ``blob`` is the float32 one.  ``om_cols`` > 0: an OM-SARL network whose
+    mlp1 reads cols + om_cols columns (cs_value_net_pack_om's blob); ``om_grid`` = (cell_num, cell_size, om_channel_size) of its maps;
+    ``last_maps``: the maps [W, n, om_cols] of its last ``decide_for_worlds``."""
 
-    def __init__(self, model, cols):
-        self.model, self.cols = model, int(cols)
+    def __init__(self, model, cols, om_cols=0, om_grid=None):
+        self.model, self.cols, self.om_cols, self.om_grid = model, int(cols), int(om_cols), om_grid
+        self.last_maps = None
         self.kind, self.dims, self.layers = describe(model)
         self._keys = dict.fromkeys(PRECISIONS)
         self.blobs = dict.fromkeys(PRECISIONS)
@@ -107,7 +124,7 @@ class DeviceNet:
         key = self._versions()
         if key != self._keys[check_precision(precision)]:
             arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in (l.weight, l.bias)]
-            self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision)).to("cuda")
+            self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision, self.om_cols)).to("cuda")
             self._keys[precision] = key
         return self.blobs[precision]
 
@@ -127,6 +144,92 @@ def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, 
         C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
         C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), P(rotated), P(rewards), P(actions), P(robot), C.c_int(robot_stride),
         C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))
+
+
+def occupancy_maps(W, n, humans, stride, vel_col, cell_num, cell_size, channels, maps, stream=None):
+    """cs_occupancy_maps on device pointers (ints): humans [W][n][stride] with the position at columns 0, 1 and the velocity at vel_col,
+    vel_col + 1 -> maps [W][n][cell_num^2 * channels]."""
+    from ... import _lib
+
+    P = C.c_void_p
+    _lib.check(_lib.load().cs_occupancy_maps(C.c_int(W), C.c_int(n), P(humans), C.c_int(stride), C.c_int(vel_col), C.c_int(cell_num),
+                                             C.c_float(cell_size), C.c_int(channels), P(maps), P(stream)))
+
+
+def maps_of(humans, vel_col, grid, stream=None):
+    """occupancy_maps for a CUDA tensor [W, n, stride] of human rows: a new tensor [W, n, C]; `grid` = (cell_num, cell_size, channels).
+    Worlds of one human have no other human to map: ValueError, before any launch (the reference's build_occupancy_maps raises it too)."""
+    import torch
+
+    W, n, stride = humans.shape
+    cell_num, cell_size, channels = grid
+    if n < 2:
+        raise ValueError("occupancy maps need at least two humans: a lone human has no other human to map")
+    maps = torch.empty((W, n, cell_num * cell_num * channels), dtype=torch.float32, device="cuda")
+    occupancy_maps(W, n, humans.data_ptr(), stride, vel_col, cell_num, cell_size, channels, maps.data_ptr(), stream)
+    return maps
+
+
+def decide_om(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None):
+    """cs_value_net_decide_om on device pointers (ints): ``decide`` for a DeviceNet with map columns, maps [W][n][net.om_cols]."""
+    from ... import _lib
+
+    P = C.c_void_p
+    blob = net.blobs["f32"]
+    if blob is None:
+        raise ValueError("decide_om: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    if net.om_cols < 1:
+        raise ValueError("decide_om: the network has no occupancy-map columns (DeviceNet(model, cols, om_cols))")
+    _lib.check(_lib.load().cs_value_net_decide_om(
+        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
+        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), C.c_int(net.om_cols), P(rotated), P(maps), P(rewards), P(actions), P(robot),
+        C.c_int(robot_stride), C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))
+
+
+_ROWS_BLOB = {}
+
+
+def rotated_rows(cur, robot, stream=None):
+    """The rotated joint states [W, n, 13 | 15] of the worlds' CURRENT state (cur [W, n, 5 | 7], robot [W, 8+], CUDA tensors), written by
+    cs_value_net_state's loader: the entry is given a one-layer network of zero weights, whose value nobody reads."""
+    import torch
+
+    from ... import _lib
+
+    P = C.c_void_p
+    W, n, cc = cur.shape
+    cols = 15 if cc == 7 else 13
+    dims = np.array([1, 1], np.int32)
+    key = (cols, torch.cuda.current_device())
+    if key not in _ROWS_BLOB:
+        _ROWS_BLOB[key] = torch.from_numpy(pack(CS_VN_CADRL, dims, cols, [np.zeros((1, cols), np.float32), np.zeros(1, np.float32)])).to("cuda")
+    blob = _ROWS_BLOB[key]
+    rows = torch.empty((W, n, cols), dtype=torch.float32, device="cuda")
+    unread = torch.empty(W, dtype=torch.float32, device="cuda")
+    _lib.check(_lib.load().cs_value_net_state(
+        C.c_int(CS_VN_CADRL), dims.ctypes.data_as(P), C.c_int(len(dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()), C.c_int(W), C.c_int(n),
+        C.c_int(int(cc == 7)), P(cur.data_ptr()), P(robot.data_ptr()), C.c_int(robot.shape[1]), None, C.c_float(1.0), C.c_float(0.0),
+        P(rows.data_ptr()), P(unread.data_ptr()), P(stream)))
+    return rows
+
+
+def state_values_om(net, cur, robot, rewards, gamma, dt, stream=None):
+    """``state_values`` for a DeviceNet with map columns, composed of three launches where a 13-column network has one: the rotated rows
+    of the current state (``rotated_rows``), the maps of the CURRENT humans, and cs_value_net_decide_om with A = 1 -- a one-row action
+    table, no choice, a scratch action row.  CUDA tensors cur [W, n, 5 | 7], robot [W, 8+], rewards [W] or None (0).  Returns (values [W],
+    wide rows [W, n, cols + om_cols]: what ``transform`` gives per world)."""
+    import torch
+
+    W, n, _ = cur.shape
+    maps = maps_of(cur, 2, net.om_grid, stream)
+    rows = rotated_rows(cur, robot, stream)
+    values = torch.empty(W, dtype=torch.float32, device="cuda")
+    zeros = torch.zeros(max(W, 2), dtype=torch.float32, device="cuda")     # the null rewards; its first two floats the one-row action table
+    scratch = torch.empty((W, 2), dtype=torch.float32, device="cuda")
+    rew = rewards if rewards is not None else zeros
+    decide_om(net, W, 1, n, rows.data_ptr(), maps.data_ptr(), rew.data_ptr(), zeros.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt,
+              None, values.data_ptr(), None, scratch.data_ptr(), stream)
+    return values, torch.cat([rows, maps], dim=2)
 
 
 def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out, values, choice, action_out,
@@ -187,10 +290,18 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
-    decide with `precision`.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
+    decide with `precision`; a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
+    branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
     "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
+    if net.om_cols:
+        check_decision_input(decision_input, precision, net.om_cols)
+        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
+        net.last_maps = maps_of(nxt, 3 if cc == 7 else 2, net.om_grid, stream)
+        decide_om(net, W, A, n, rot.data_ptr(), net.last_maps.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma,
+                  dt, ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return rot, rew
     if check_decision_input(decision_input, precision) == "fused":      # one library call on the worlds' own rows
         decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
                       None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)

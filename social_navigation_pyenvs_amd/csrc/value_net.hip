@@ -50,7 +50,7 @@ extern "C" int cs_value_net_pack(int kind, const int32_t* dims, int n_dims, int 
 {
     VnPlan p;
     bool fill;
-    const int rc = begin_pack(kind, dims, n_dims, cols, nullptr, 1, params, blob, n_floats, p, fill);
+    const int rc = begin_pack(kind, dims, n_dims, cols, 0, nullptr, 1, params, blob, n_floats, p, fill);
     if (rc != CS_OK || !fill) return rc;
     for (int l = 0; l < p.n_layers; ++l)
         pack_layer_f32(p.L[l], params[2 * l], params[2 * l + 1], blob);
@@ -63,7 +63,7 @@ extern "C" int cs_value_net_decide(int kind, const int32_t* dims, int n_dims, co
                                    float* d_action_out, void* stream)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    const int rc = build_plan(kind, dims, n_dims, cols, 0, p);
     if (rc != CS_OK) return rc;
     const int rc2 = check_decide_args(p, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;

@@ -204,7 +204,7 @@ extern "C" int cs_value_net_pack_bf16(int kind, const int32_t* dims, int n_dims,
 {
     VnPlan p;
     bool fill;
-    const int rc = begin_pack(kind, dims, n_dims, cols, replan_bf16, sizeof(float), params, blob, n_bytes, p, fill);
+    const int rc = begin_pack(kind, dims, n_dims, cols, 0, replan_bf16, sizeof(float), params, blob, n_bytes, p, fill);
     if (rc != CS_OK || !fill) return rc;
     float* fb = static_cast<float*>(blob);
     for (int l = 0; l < p.n_layers; ++l) {
@@ -236,7 +236,7 @@ extern "C" int cs_value_net_decide_bf16(int kind, const int32_t* dims, int n_dim
                                         float* d_action_out, void* stream)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    const int rc = build_plan(kind, dims, n_dims, cols, 0, p);
     if (rc != CS_OK) return rc;
     replan_bf16(p);
     // (a length that is no whole number of floats is no blob of any network: it fails the size check as SIZE_MAX floats)

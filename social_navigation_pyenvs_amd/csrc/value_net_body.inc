@@ -14,6 +14,8 @@
 //   vn_m1pad(p)                    the columns of mlp1's output that the attention's k-steps read of the mean
 //   vn_sum_cols(p, m1pad)          the columns of the running sum that a chunked mean zeroes
 //   vn_mean_pass(p)                whether a group in chunks runs the mean pre-pass
+// The input tile's row stride is LDX, a compile-time constant, unless the kernel defines VN_INPUT_STRIDE (k_value_net_om: an int
+// argument, the wide first layer's K rounded up to 8, plus 4).
     VnBufs b;
     b.X0 = lds + m.X0; b.M1 = lds + m.M1; b.P = lds + m.P; b.Q = lds + m.Q; b.G = lds + m.G; b.Gsum = lds + gsum; b.J = lds + m.J;
     b.sc = lds + m.sc; b.den = lds + m.den; b.val = lds + m.val; b.grp = reinterpret_cast<int*>(lds + m.grp);
@@ -23,6 +25,11 @@
     const int chunks = n <= M ? 1 : (n + M - 1) / M;
     const int gpt = n <= M ? M / n : 1;
     const int m1pad = vn_m1pad(p);
+#ifdef VN_INPUT_STRIDE
+    const int ldx = VN_INPUT_STRIDE;
+#else
+    constexpr int ldx = LDX;
+#endif
     int out_ld;
 
     for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
@@ -45,7 +52,7 @@
                     const int rows = n - ch * M < M ? n - ch * M : M;
                     VN_LOAD_TILE(ch, rows, n);
                     __syncthreads();
-                    run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
+                    run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, ldx, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
                     for (int c = tid; c < m1pad; c += NT) {
                         float s = b.Gsum[c];
                         for (int r = 0; r < rows; ++r) s += vn_m1(b.M1, p.ld_m1, r, c);
@@ -66,7 +73,7 @@
                 __syncthreads();
                 if (!sarl) {
                     if (phase == 1) continue;
-                    const float* out = run_chain<CH_CADRL>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, nullptr, 0, out_ld);
+                    const float* out = run_chain<CH_CADRL>(p, wb, b, p.c0[0], p.c0[1], b.X0, ldx, nullptr, 0, rbs, nullptr, 0, out_ld);
                     if (tid < tg) {         // cadrl.py:269: the minimum over the humans
                         float v = b.val[t0 + tid];
                         for (int j = 0; j < per; ++j) {      // (torch.min's order: a NaN stays)
@@ -79,8 +86,8 @@
                     continue;
                 }
                 if (ch == 0)                // sarl.py:36: the self state is read from the first human's row
-                    for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * LDX + i % SELF_DIM];
-                run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
+                    for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * ldx + i % SELF_DIM];
+                run_chain<CH_MLP1>(p, wb, b, p.c0[0], p.c0[1], b.X0, ldx, nullptr, 0, rbs, b.M1, p.ld_m1, out_ld);
                 if (p.with_global && chunks == 1 && n > 1) {
                     for (int i = tid; i < tg * m1pad; i += NT) {
                         const int k = i / m1pad, c = i - k * m1pad;

@@ -26,7 +26,7 @@ constexpr int JROWS = 32;          // groups per workgroup = rows of the mlp3 bl
 constexpr int VN_MAX_LAYERS = 16;
 constexpr int VN_MAX_WIDTH = 256;
 constexpr int SELF_DIM = 6;        // sarl.py self_state_dim: dg, v_pref, theta, radius, vx, vy
-constexpr int LDX = 20;            // row stride of the input tile (13 or 15 columns padded to 16)
+constexpr int LDX = 20;            // row stride of the input tile (13 or 15 columns padded to 16); k_value_net_om has its own
 
 struct VnLayer {
     int K1, K2, N;                 // input columns from the first / second source, output columns
@@ -49,11 +49,15 @@ struct VnPlan {
 inline int up(int x, int m) { return (x + m - 1) / m * m; }
 
 // the layer table of a network description (include/crowdstep.h cs_value_net_decide: `dims`); CS_OK or the fail() status
-inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, VnPlan& p)
+// om_cols: the occupancy-map columns behind the rotated ones in the first layer's input (cs_value_net_decide_om; 0: none)
+inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, VnPlan& p)
 {
     memset(&p, 0, sizeof p);
     if (kind != CS_VN_CADRL && kind != CS_VN_SARL) return fail(CS_ERR_ARG, "unknown value network kind (CS_VN_CADRL, CS_VN_SARL)");
     if (cols != 13 && cols != 15) return fail(CS_ERR_ARG, "rotated rows have 13 or 15 columns");
+    if (om_cols && kind != CS_VN_SARL) return fail(CS_ERR_ARG, "occupancy maps belong to SARL's network");
+    if (om_cols < 0) return fail(CS_ERR_ARG, "om_cols must be at least 1");
+    if (cols + om_cols > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "rotated and map columns together exceed a layer's 256 inputs");
     if (!dims || n_dims < 2) return fail(CS_ERR_ARG, "null or empty layer description");
     p.kind = kind;
     p.cols = cols;
@@ -68,7 +72,7 @@ inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, VnPla
         if (p.n_layers + nl > VN_MAX_LAYERS) return fail(CS_ERR_ARG, "at most 16 layers in all");
         p.c0[c] = p.n_layers;
         // what the chain reads (sarl.py:15-25): mlp1 the rotated row; mlp2 mlp1's output; attention (mlp1, mean of mlp1) or mlp1; mlp3 (self state, feature)
-        int k1 = cols, k2 = 0;
+        int k1 = cols + om_cols, k2 = 0;
         if (c == 1) k1 = p.m1w;
         if (c == 2) { k1 = p.m1w; k2 = p.with_global ? p.m1w : 0; }
         if (c == 3) k1 = SELF_DIM + p.feat;
@@ -139,12 +143,13 @@ inline void pack_layer_f32(const VnLayer& L, const float* wgt, const float* bias
 // LDS map of a launch (floats from the start of the dynamic block)
 struct VnLds { int X0, M1, P, Q, G, J, sc, den, val, self, grp, total; };
 
-inline VnLds lds_map(const VnPlan& p, int M, int n)
+// ldx: the input tile's row stride
+inline VnLds lds_map(const VnPlan& p, int M, int n, int ldx)
 {
     VnLds m{};
     int o = 0;
     auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
-    m.X0 = take(M * LDX);
+    m.X0 = take(M * ldx);
     m.P = take(M * p.ld_pq);
     m.Q = take(M * p.ld_pq);
     if (p.kind == CS_VN_SARL) {
@@ -166,9 +171,9 @@ inline VnLds lds_map(const VnPlan& p, int M, int n)
 struct VnLaunch { VnLds m; int tail; size_t shmem; int NG, grid; };
 
 template <auto Kernel>
-inline int prepare_launch(const VnPlan& p, int n, int tail_floats, int W, int A, VnLaunch& q)
+inline int prepare_launch(const VnPlan& p, int n, int tail_floats, int W, int A, VnLaunch& q, int ldx = LDX)
 {
-    q.m = lds_map(p, TILE_M, n);
+    q.m = lds_map(p, TILE_M, n, ldx);
     q.tail = q.m.total;
     q.shmem = (size_t)(q.m.total + tail_floats) * sizeof(float);
     // (the float32 tensor path cannot get here within build_plan's limits -- 16 layers of up to 256 columns need about 150 KiB at most, at n = 2)
@@ -192,11 +197,11 @@ inline int prepare_launch(const VnPlan& p, int n, int tail_floats, int W, int A,
 // What the pack entries do alike before they fill the blob: the plan (`replan`: the arithmetic's changes to it, or null), the size query
 // through n_units (`units_per_float`: 1 for a blob counted in floats, 4 in bytes), the null checks, the zeroed blob.  `fill` tells whether
 // there is a blob to fill.
-inline int begin_pack(int kind, const int32_t* dims, int n_dims, int cols, void (*replan)(VnPlan&), int units_per_float, const float* const* params,
+inline int begin_pack(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, void (*replan)(VnPlan&), int units_per_float, const float* const* params,
                       void* blob, size_t* n_units, VnPlan& p, bool& fill)
 {
     fill = false;
-    const int rc = build_plan(kind, dims, n_dims, cols, p);
+    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, p);
     if (rc != CS_OK) return rc;
     if (replan) replan(p);
     if (!n_units) return fail(CS_ERR_ARG, "null argument");

@@ -128,7 +128,7 @@ extern "C" int cs_value_net_state(int kind, const int32_t* dims, int n_dims, con
                                   const float* d_rewards, float gamma, float dt, float* d_rotated_out, float* d_values, void* stream)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, theta_and_omega_visible ? 15 : 13, p);
+    const int rc = build_plan(kind, dims, n_dims, theta_and_omega_visible ? 15 : 13, 0, p);
     if (rc != CS_OK) return rc;
     // (check_decide_args' checks in its order, without the action table: d_rewards and d_rotated_out may be null)
     if (W < 1) return fail(CS_ERR_ARG, "W must be positive");

@@ -109,7 +109,7 @@ extern "C" int cs_value_net_decide_worlds(int kind, const int32_t* dims, int n_d
                                           float* d_rewards_out, float* d_values, int32_t* d_choice, float* d_action_out, void* stream)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, theta_and_omega_visible ? 15 : 13, p);
+    const int rc = build_plan(kind, dims, n_dims, theta_and_omega_visible ? 15 : 13, 0, p);
     if (rc != CS_OK) return rc;
     // (the worlds' two arrays stand where cs_value_net_decide has cs_lookahead's two outputs: cs_lookahead's own checks are among these)
     const int rc2 = check_decide_args(p, d_weights, n_weight_floats, W, A, n, d_next, d_current, d_actions, d_robot, robot_stride, d_values, d_action_out);

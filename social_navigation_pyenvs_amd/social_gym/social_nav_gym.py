@@ -723,7 +723,8 @@ class BatchedSocialNavGym:
         ``set_decision_precision("bf16")``), all on ``device_stream()``; after the policy's ``set_decision_input("fused")``, cs_peek ->
         cs_value_net_decide_worlds, which generates the look-ahead rows in the kernel and allocates no look-ahead tensor.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
-        values and choices of that decision stay readable through ``last_values_device()``."""
+        values and choices of that decision stay readable through ``last_values_device()``.  An OM-SARL instance
+        (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om."""
         import torch
 
         dl = self._device_loop_state()
@@ -792,6 +793,8 @@ class BatchedSocialNavGym:
             raise ValueError("act_device: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
         if self.cw.d_robot is None:
             raise ValueError("act_device needs the robot rows")
+        if pol.map_columns() and self._human_count() < 2:
+            raise ValueError(f"act_device: {pol.name}'s occupancy maps need at least two humans a world")
         if pol.action_space_ndarray is None:
             pol.build_action_space(float(self._gen_kw["robot_desired_speed"]))
         W = self.W
@@ -834,7 +837,9 @@ class BatchedSocialNavGym:
         """What a trainer stores for the decision every robot is about to take: ``policy.transform`` of every world's resident state -- the
         rotated joint state of the robot with each human, what ``predict`` leaves in ``last_state`` -- as a new CUDA tensor [W, n, 13|15].
         ``policy``: a configured CADRL / SARL instance.  One launch of cs_value_net_state on ``device_stream()`` (which also evaluates the
-        network: ``value_device(policy, with_state=True)`` returns both); nothing crosses to the host."""
+        network: ``value_device(policy, with_state=True)`` returns both); nothing crosses to the host.  For an OM-SARL instance the rows are
+        [W, n, 13|15 + C]: the maps of the CURRENT humans appended, as its ``transform`` gives them per world (three launches, see
+        ``value_device``)."""
         return self._state_values_device("joint_state_device", policy, None, None, 0.0, True)[1]
 
     def value_device(self, policy, model=None, rewards=None, bootstrap=False, with_state=False):
@@ -845,7 +850,9 @@ class BatchedSocialNavGym:
         ``bootstrap=True`` evaluates the trainer's target of the state the worlds are in, ``rewards + gamma^(robot_time_step * v_pref) * V``
         (crowd_nav/utils/explorer.py:120-153; ``rewards``: a float32 CUDA tensor [W], None = 0); a terminal step's target is its reward
         alone: ``torch.where(done, rewards, target)``.  Without ``bootstrap`` ``rewards`` must be None.  float32 arithmetic whatever the
-        policy's decision precision.  One launch of cs_value_net_state on ``device_stream()``; nothing crosses to the host."""
+        policy's decision precision.  One launch of cs_value_net_state on ``device_stream()``; nothing crosses to the host.  An OM-SARL
+        instance gives the same quantities from THREE launches instead of one: cs_value_net_state for the rotated rows, cs_occupancy_maps
+        on the current humans, cs_value_net_decide_om with A = 1 (a one-row action table, no choice); its rows are [W, n, 13|15 + C]."""
         if rewards is not None and not bootstrap:
             raise ValueError("value_device: rewards= belongs to bootstrap=True (rewards + gamma^(robot_time_step * v_pref) * V)")
         values, rows = self._state_values_device("value_device", policy, model, rewards, self.robot_time_step if bootstrap else 0.0, with_state)
@@ -866,6 +873,8 @@ class BatchedSocialNavGym:
             raise ValueError(f"{who}: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
         if self.cw is not None and self.cw.d_robot is None:
             raise ValueError(f"{who} needs the robot rows")
+        if pol.map_columns() and self._human_count() < 2:
+            raise ValueError(f"{who}: {pol.name}'s occupancy maps need at least two humans a world")
         import torch
 
         from ..crowd_nav.policy import value_net
@@ -881,15 +890,49 @@ class BatchedSocialNavGym:
         self._stream_handshake(dl, cur, True)
         with torch.cuda.stream(side):
             _, cur_, rob = self._worlds_on_side_stream(dl, peek=False)
-            values = torch.empty(W, dtype=torch.float32, device="cuda")
-            rows = torch.empty((W, n, pol.joint_state_dim), dtype=torch.float32, device="cuda") if with_rows else None
-            value_net.state_values(net, W, n, self.headed_obs, cur_.data_ptr(), rob.data_ptr(), rob.shape[1], None if rewards is None else rewards.data_ptr(),
-                                   pol.gamma, dt, None if rows is None else rows.data_ptr(), values.data_ptr(), side.cuda_stream)
+            if net.om_cols:                      # OM-SARL: rows, maps of the current humans and the network are three launches
+                values, rows = value_net.state_values_om(net, cur_, rob, rewards, pol.gamma, dt, side.cuda_stream)
+            else:
+                values = torch.empty(W, dtype=torch.float32, device="cuda")
+                rows = torch.empty((W, n, pol.joint_state_dim), dtype=torch.float32, device="cuda") if with_rows else None
+                value_net.state_values(net, W, n, self.headed_obs, cur_.data_ptr(), rob.data_ptr(), rob.shape[1], None if rewards is None else rewards.data_ptr(),
+                                       pol.gamma, dt, None if rows is None else rows.data_ptr(), values.data_ptr(), side.cuda_stream)
             for t in (cur_, rob, rewards, values, rows):
                 if t is not None:
                     t.record_stream(cur if t is values or t is rows else side)
         self._stream_handshake(dl, cur, False)
         return values, rows
+
+    def _human_count(self):
+        """Humans a world: of the generated batch, or what the configuration will generate"""
+        n = getattr(self, "n", None)
+        return int(n) if n is not None else self.config.getint("sim", "human_num")
+
+    def occupancy_maps_device(self, cell_num, cell_size, channels, which="current"):
+        """OM-SARL's local occupancy maps of every world's humans (cs_occupancy_maps; ``build_occupancy_maps`` for W worlds), for a network
+        of the caller's own: a new float32 CUDA tensor [W, n, cell_num^2 * channels].  ``which``: "current" -- the humans as they stand,
+        what ``transform`` appends -- or "next" -- one robot step ahead (cs_peek), what a decision appends.  On ``device_stream()``;
+        nothing crosses to the host.  Worlds of one human have nobody to map: ValueError, before anything touches the device."""
+        import torch
+
+        from ..crowd_nav.policy import value_net
+
+        if which not in ("current", "next"):
+            raise ValueError(f'occupancy_maps_device: which={which!r}: "current" or "next"')
+        if self._human_count() < 2:
+            raise ValueError("occupancy_maps_device: occupancy maps need at least two humans a world")
+        grid = (int(cell_num), float(cell_size), int(channels))
+        dl = self._device_loop_state()
+        side, cur = dl["stream"], torch.cuda.current_stream()
+        self._stream_handshake(dl, cur, True)
+        with torch.cuda.stream(side):
+            nxt, cur_, _ = self._worlds_on_side_stream(dl, peek=which == "next")
+            maps = value_net.maps_of(*((nxt, 3 if self.headed_obs else 2) if which == "next" else (cur_, 2)), grid, side.cuda_stream)
+            for t in (nxt, cur_, maps):
+                if t is not None:
+                    t.record_stream(cur if t is maps else side)
+        self._stream_handshake(dl, cur, False)
+        return maps
 
     def lookahead_device(self, action_space):
         """The per-decision array work of CADRL / SARL for every world, on the device: one-step look-ahead of the humans
