@@ -31,27 +31,6 @@ ABI_VERSION = 4   # include/crowdstep.h CS_ABI_VERSION
 CS_ORCA_MATH_DEFAULT, CS_ORCA_MATH_EXACT, CS_ORCA_MATH_FAST, CS_ORCA_MATH_FMA = 0, 1, 2, 3
 ORCA_MATH_NAMES = {"default": 0, "exact": 1, "fast": 2, "fma": 3}
 
-# every symbol include/crowdstep.h declares (tests check the .so exports all of them)
-ABI_SYMBOLS = [
-    "cs_last_error", "cs_abi_version", "cs_device_count", "cs_set_device", "cs_device_name", "cs_device_pci_bus_id", "cs_malloc",
-    "cs_free", "cs_memcpy_h2d", "cs_memcpy_d2h", "cs_memcpy_d2d", "cs_memset", "cs_stream_create", "cs_stream_create_with_priority",
-    "cs_stream_destroy", "cs_stream_sync", "cs_event_create", "cs_event_destroy", "cs_event_record",
-    "cs_event_elapsed_ms", "cs_event_query", "cs_stream_wait_event", "cs_graph_begin_capture", "cs_graph_end_capture", "cs_graph_launch", "cs_graph_destroy",
-    "cs_update_humans_parallel", "cs_step", "cs_peek", "cs_collision_reward",
-    "cs_state_aos_to_soa", "cs_state_soa_to_aos", "cs_launch_geometry", "cs_lookahead",
-    "cs_generate_scratch_bytes", "cs_generate_worlds", "cs_laser_scan", "cs_robot_model_step", "cs_actual_collision_reward",
-    "cs_update_humans_rk45", "cs_gym_bookkeeping", "cs_step_variant", "cs_debug_divsqrt_check", "cs_gym_observe", "cs_copy_worlds_masked", "cs_imitation_block", "cs_gym_bookkeeping_next_step", "cs_robot_model_velocities",
-    "cs_step_trace", "cs_reserve_scratch", "cs_release_scratch", "cs_complete_rk45_simulation", "cs_robot_model_rk45", "cs_copy_worlds_masked_status",
-    "cs_collision_reward_gym", "cs_step_observe", "cs_copy_worlds_masked_observe", "cs_refill_staged_worlds", "cs_consume_staged_worlds", "cs_gym_step",
-    "cs_orca_default_math", "cs_gym_step_is_one_launch", "cs_gym_step_staged", "cs_policy_no_train",
-    "cs_gym_step_policy", "cs_gym_step_staged_policy", "cs_gym_step_policy_variant",
-    "cs_value_net_pack", "cs_value_net_decide", "cs_value_net_pack_bf16", "cs_value_net_decide_bf16",
-    "cs_value_net_decide_worlds", "cs_value_net_state",
-    "cs_occupancy_maps", "cs_value_net_pack_om", "cs_value_net_decide_om",
-    "cs_step_f64", "cs_update_humans_parallel_f64", "cs_peek_f64",
-]
-
-
 class CrowdstepError(RuntimeError):
     pass
 
@@ -95,6 +74,108 @@ class cs_worlds_f64(C.Structure):   # include/crowdstep.h cs_worlds_f64: float64
         ("d_obstacles", C.c_void_p), ("d_robot", C.c_void_p), ("d_world_flags", C.c_void_p),
         ("respawn_bound_x", C.c_double), ("respawn_bound_y", C.c_double),
     ]
+
+
+class cs_generator(C.Structure):   # include/crowdstep.h cs_generator: what cs_generate_worlds draws a world from
+    _fields_ = [
+        ("scenario", C.c_int32), ("n", C.c_int32), ("insert_robot", C.c_int32), ("randomize_attributes", C.c_int32),
+        ("randomize_positions", C.c_int32), ("max_tries", C.c_int32),
+        ("circle_radius", C.c_double), ("traffic_length", C.c_double), ("traffic_height", C.c_double),
+        ("robot_radius", C.c_double), ("human_mass", C.c_double), ("robot_mass", C.c_double),
+        ("robot_desired_speed", C.c_double),
+    ]
+
+
+# The prototypes of include/crowdstep.h, one line each: symbol -> (restype, argtypes).  load() binds them, so a call passes plain Python
+# values (ints, floats, device addresses, None, a descriptor struct or byref of one) and ctypes converts or refuses them by the header's
+# types; tests/test_abi_cpu.py derives this table from the header.  I / U / ULL / Z: int (int32_t), unsigned (uint32_t), unsigned long long,
+# size_t; F / D: float, double; S: const char*; the descriptors by pointer; P: every other pointer (device buffers, streams, events, host
+# arrays, out-parameters).  cs_build_id and cs_debug_set_stamp_buffer are exported but not declared in the header: not bound here.
+I, U, ULL, Z, F, D, S, P = C.c_int, C.c_uint, C.c_ulonglong, C.c_size_t, C.c_float, C.c_double, C.c_char_p, C.c_void_p
+WORLDS, WORLDS64, GEN = C.POINTER(cs_worlds), C.POINTER(cs_worlds_f64), C.POINTER(cs_generator)
+GYM_BOOK, STAGE_BOOK = C.POINTER(cs_gym_book), C.POINTER(cs_stage_book)
+ABI = {
+    "cs_last_error": (S, []),
+    "cs_abi_version": (I, []),
+    "cs_device_count": (I, [P]),
+    "cs_set_device": (I, [I]),
+    "cs_device_name": (I, [I, P, Z]),
+    "cs_device_pci_bus_id": (I, [I, P, Z]),
+    "cs_malloc": (I, [P, Z]),
+    "cs_free": (I, [P]),
+    "cs_memcpy_h2d": (I, [P, P, Z, P]),
+    "cs_memcpy_d2h": (I, [P, P, Z, P]),
+    "cs_memcpy_d2d": (I, [P, P, Z, P]),
+    "cs_memset": (I, [P, I, Z, P]),
+    "cs_stream_create": (I, [P]),
+    "cs_stream_create_with_priority": (I, [P, I]),
+    "cs_stream_destroy": (I, [P]),
+    "cs_stream_sync": (I, [P]),
+    "cs_event_create": (I, [P]),
+    "cs_event_destroy": (I, [P]),
+    "cs_event_record": (I, [P, P]),
+    "cs_event_elapsed_ms": (I, [P, P, P]),
+    "cs_event_query": (I, [P, P]),
+    "cs_stream_wait_event": (I, [P, P]),
+    "cs_graph_begin_capture": (I, [P]),
+    "cs_graph_end_capture": (I, [P, P]),
+    "cs_graph_launch": (I, [P, P]),
+    "cs_graph_destroy": (I, [P]),
+    "cs_update_humans_parallel": (I, [WORLDS, F, P, P]),
+    "cs_step": (I, [WORLDS, F, I, P, P]),
+    "cs_step_trace": (I, [WORLDS, F, I, P, P, P]),
+    "cs_peek": (I, [WORLDS, F, P, P]),
+    "cs_collision_reward": (I, [WORLDS, P, F, P, P, P, P]),
+    "cs_lookahead": (I, [I, I, I, I, P, P, P, P, I, F, P, P, P]),
+    "cs_generate_scratch_bytes": (Z, [I]),
+    "cs_generate_worlds": (I, [GEN, WORLDS, P, P, P, P, P, P]),
+    "cs_laser_scan": (I, [WORLDS, P, I, F, I, F, P, P]),
+    "cs_robot_model_step": (I, [WORLDS, I, P, F, P, P, F, P]),
+    "cs_robot_model_velocities": (I, [WORLDS, I, P, F, P, P, F, P]),
+    "cs_imitation_block": (I, [WORLDS, I, P, F, P, P, F, I, P]),
+    "cs_reserve_scratch": (I, [WORLDS, I, P]),
+    "cs_release_scratch": (I, []),
+    "cs_actual_collision_reward": (I, [WORLDS, F, P, P, P, P]),
+    "cs_update_humans_rk45": (I, [WORLDS, F, P, P, P]),
+    "cs_complete_rk45_simulation": (I, [WORLDS, F, F, P, P, I, P, P]),
+    "cs_robot_model_rk45": (I, [WORLDS, I, P, F, P, P, F, P, P]),
+    "cs_gym_bookkeeping": (I, [I, P, P, P, P, P, P, I, I, P, P, P, P, U, P]),
+    "cs_gym_observe": (I, [WORLDS, I, P, P]),
+    "cs_copy_worlds_masked": (I, [WORLDS, WORLDS, P, P]),
+    "cs_copy_worlds_masked_status": (I, [WORLDS, WORLDS, P, P, P]),
+    "cs_step_observe": (I, [WORLDS, F, I, P, I, P, P]),
+    "cs_copy_worlds_masked_observe": (I, [WORLDS, WORLDS, P, P, I, P, P]),
+    "cs_gym_bookkeeping_next_step": (I, [I, P, P, P, P, P, P, P, I, P, P, P, P, U, P]),
+    "cs_collision_reward_gym": (I, [WORLDS, P, F, P, P, P, GYM_BOOK, P]),
+    "cs_gym_step": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, P]),
+    "cs_refill_staged_worlds": (I, [GEN, WORLDS, STAGE_BOOK, P]),
+    "cs_consume_staged_worlds": (I, [GEN, WORLDS, WORLDS, P, STAGE_BOOK, I, P, P]),
+    "cs_gym_step_is_one_launch": (I, [WORLDS]),
+    "cs_gym_step_staged": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, GEN, WORLDS, STAGE_BOOK, P]),
+    "cs_policy_no_train": (I, [I, I, I, P, P, I, F, P, P, P]),
+    "cs_gym_step_policy": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, I, F, P, P]),
+    "cs_gym_step_staged_policy": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, GEN, WORLDS, STAGE_BOOK, I, F, P, P]),
+    "cs_gym_step_policy_variant": (I, [WORLDS, P, Z]),
+    "cs_value_net_pack": (I, [I, P, I, I, P, P, P]),
+    "cs_value_net_decide": (I, [I, P, I, P, Z, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_pack_bf16": (I, [I, P, I, I, P, P, P]),
+    "cs_value_net_decide_bf16": (I, [I, P, I, P, Z, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_decide_worlds": (I, [I, P, I, P, Z, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P, P]),
+    "cs_value_net_state": (I, [I, P, I, P, Z, I, I, I, P, P, I, P, F, F, P, P, P]),
+    "cs_occupancy_maps": (I, [I, I, P, I, I, I, F, I, P, P]),
+    "cs_value_net_pack_om": (I, [I, P, I, I, I, P, P, P]),
+    "cs_value_net_decide_om": (I, [I, P, I, P, Z, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_step_f64": (I, [WORLDS64, D, I, P, P]),
+    "cs_update_humans_parallel_f64": (I, [WORLDS64, D, P, P]),
+    "cs_peek_f64": (I, [WORLDS64, D, P, P]),
+    "cs_state_aos_to_soa": (I, [P, P, I, I, P]),
+    "cs_state_soa_to_aos": (I, [P, P, I, I, P]),
+    "cs_launch_geometry": (I, [WORLDS, P, P, P]),
+    "cs_step_variant": (I, [WORLDS, I, P, Z]),
+    "cs_orca_default_math": (I, []),
+    "cs_debug_divsqrt_check": (I, [ULL, U, P, P]),
+}
+ABI_SYMBOLS = list(ABI)   # every symbol include/crowdstep.h declares (tests check the .so exports all of them)
 
 
 _lib = None
@@ -202,16 +283,13 @@ def load():
     fn = getattr(lib, "cs_abi_version", None)     # (a stale or foreign CROWDSTEP_LIB may lack the symbol: report it as ABI None, not as a ctypes AttributeError)
     got = None
     if fn is not None:
-        fn.restype = C.c_int
         got = fn()
     if got != ABI_VERSION:   # a stale or foreign build (CROWDSTEP_LIB): its structs and argument lists are not the ones bound here
         raise CrowdstepError(f"{LIB_PATH} speaks ABI {got}, this binding ABI {ABI_VERSION} (include/crowdstep.h CS_ABI_VERSION): rebuild the library")
-    lib.cs_last_error.restype = C.c_char_p
-    for name in ABI_SYMBOLS:
-        if name != "cs_last_error" and hasattr(lib, name):
-            getattr(lib, name).restype = C.c_int
-    if hasattr(lib, "cs_generate_scratch_bytes"):
-        lib.cs_generate_scratch_bytes.restype = C.c_size_t
+    for name, (restype, argtypes) in ABI.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -239,18 +317,18 @@ def require_gpu() -> None:
 
 
 def set_device(device: int) -> None:
-    check(load().cs_set_device(C.c_int(device)))
+    check(load().cs_set_device(device))
 
 
 def device_name(device: int = 0) -> str:
     buf = C.create_string_buffer(256)
-    check(load().cs_device_name(C.c_int(device), buf, C.c_size_t(256)))
+    check(load().cs_device_name(device, buf, 256))
     return buf.value.decode()
 
 
 def device_pci_bus_id(device: int = 0) -> str:
     buf = C.create_string_buffer(64)
-    check(load().cs_device_pci_bus_id(C.c_int(device), buf, C.c_size_t(64)))
+    check(load().cs_device_pci_bus_id(device, buf, 64))
     return buf.value.decode()
 
 
@@ -262,7 +340,7 @@ class DeviceBuffer:
         self.dtype = np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         p = C.c_void_p()
-        check(load().cs_malloc(C.byref(p), C.c_size_t(max(self.nbytes, 4))))
+        check(load().cs_malloc(C.byref(p), max(self.nbytes, 4)))
         self.ptr = p.value
 
     @classmethod
@@ -276,15 +354,13 @@ class DeviceBuffer:
         arr = np.ascontiguousarray(arr, dtype=self.dtype)
         if arr.nbytes != self.nbytes:
             raise ValueError(f"upload size mismatch {arr.shape} vs {self.shape}")
-        check(load().cs_memcpy_h2d(C.c_void_p(self.ptr), arr.ctypes.data_as(C.c_void_p), C.c_size_t(self.nbytes),
-                                   C.c_void_p(stream)))
+        check(load().cs_memcpy_h2d(self.ptr, arr.ctypes.data, self.nbytes, stream))
         if stream:
-            check(load().cs_stream_sync(C.c_void_p(stream)))
+            check(load().cs_stream_sync(stream))
 
     def download(self, stream=None) -> np.ndarray:
         out = np.empty(self.shape, dtype=self.dtype)
-        check(load().cs_memcpy_d2h(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), C.c_size_t(self.nbytes),
-                                   C.c_void_p(stream)))
+        check(load().cs_memcpy_d2h(out.ctypes.data, self.ptr, self.nbytes, stream))
         return out
 
     @property
@@ -305,7 +381,7 @@ class DeviceBuffer:
     def free(self):
         if getattr(self, "ptr", None):
             try:
-                load().cs_free(C.c_void_p(self.ptr))
+                load().cs_free(self.ptr)
             finally:
                 self.ptr = None
 
@@ -323,27 +399,27 @@ class Event:
         self.ptr = p.value
 
     def record(self, stream=None):
-        check(load().cs_event_record(C.c_void_p(self.ptr), C.c_void_p(stream)))
+        check(load().cs_event_record(self.ptr, stream))
 
     def wait(self, stream=None):
         """Make later work of `stream` wait for this event (device-side, the host does not block)."""
-        check(load().cs_stream_wait_event(C.c_void_p(stream), C.c_void_p(self.ptr)))
+        check(load().cs_stream_wait_event(stream, self.ptr))
 
     def done(self) -> bool:
         """True when the work recorded before this event has finished (never blocks)."""
         d = C.c_int(0)
-        check(load().cs_event_query(C.c_void_p(self.ptr), C.byref(d)))
+        check(load().cs_event_query(self.ptr, C.byref(d)))
         return bool(d.value)
 
     def elapsed_ms(self, stop: "Event") -> float:
         ms = C.c_float(0)
-        check(load().cs_event_elapsed_ms(C.c_void_p(self.ptr), C.c_void_p(stop.ptr), C.byref(ms)))
+        check(load().cs_event_elapsed_ms(self.ptr, stop.ptr, C.byref(ms)))
         return ms.value
 
     def __del__(self):
         try:
             if self.ptr:
-                load().cs_event_destroy(C.c_void_p(self.ptr))
+                load().cs_event_destroy(self.ptr)
         except Exception:
             pass
 
@@ -359,24 +435,24 @@ class Graph:
         return cls(stream)
 
     def __enter__(self):
-        check(load().cs_graph_begin_capture(C.c_void_p(self.stream)))
+        check(load().cs_graph_begin_capture(self.stream))
         return self
 
     def __exit__(self, exc_type, exc, tb):
         p = C.c_void_p()
-        rc = load().cs_graph_end_capture(C.c_void_p(self.stream), C.byref(p))
+        rc = load().cs_graph_end_capture(self.stream, C.byref(p))
         if exc_type is None:
             check(rc)
             self.exec = p.value
         return False
 
     def launch(self):
-        check(load().cs_graph_launch(C.c_void_p(self.exec), C.c_void_p(self.stream)))
+        check(load().cs_graph_launch(self.exec, self.stream))
 
     def __del__(self):
         try:
             if self.exec:
-                load().cs_graph_destroy(C.c_void_p(self.exec))
+                load().cs_graph_destroy(self.exec)
         except Exception:
             pass
 
@@ -385,15 +461,15 @@ def stream_create(priority: int = 0) -> int:
     """A non-blocking HIP stream; priority < 0: the device's highest, > 0: its lowest (background work)."""
     p = C.c_void_p()
     if priority:
-        check(load().cs_stream_create_with_priority(C.byref(p), C.c_int(priority)))
+        check(load().cs_stream_create_with_priority(C.byref(p), priority))
     else:
         check(load().cs_stream_create(C.byref(p)))
     return p.value
 
 
 def stream_sync(stream=None) -> None:
-    check(load().cs_stream_sync(C.c_void_p(stream)))
+    check(load().cs_stream_sync(stream))
 
 
 def stream_destroy(stream) -> None:
-    check(load().cs_stream_destroy(C.c_void_p(stream)))
+    check(load().cs_stream_destroy(stream))

@@ -53,6 +53,13 @@ def _ptr(x) -> int | None:
     raise TypeError(f"cannot take a device pointer from {type(x)}")
 
 
+def _world_flags(cw, respawn=None) -> int:
+    """The cs_worlds / cs_worlds_f64 flag bits both precisions have; respawn None: on when the worlds have respawn bounds."""
+    bits = ((_lib.CS_ALL_PARAMS_EQUAL, cw.all_params_equal), (_lib.CS_ROBOT_ROW, cw.robot_row), (_lib.CS_PARAMS_SHARED, cw.params_shared),
+            (_lib.CS_OBSTACLES_SHARED, cw.obstacles_shared), (_lib.CS_RESPAWN, (cw.respawn_bounds is not None) if respawn is None else respawn))
+    return sum(bit for bit, on in bits if on)
+
+
 class CrowdWorlds:
     """W worlds x n humans (+ optional robot row) resident in HBM.
 
@@ -159,20 +166,7 @@ class CrowdWorlds:
 
     # ------------------------------------------------------------------ descriptor
     def _flags(self, respawn=None) -> int:
-        f = 0
-        if self.all_params_equal:
-            f |= _lib.CS_ALL_PARAMS_EQUAL
-        if self.robot_row:
-            f |= _lib.CS_ROBOT_ROW
-        if self.params_shared:
-            f |= _lib.CS_PARAMS_SHARED
-        if self.obstacles_shared:
-            f |= _lib.CS_OBSTACLES_SHARED
-        if (self.respawn_bounds is not None) if respawn is None else respawn:
-            f |= _lib.CS_RESPAWN
-        if self.unicycle:
-            f |= _lib.CS_ROBOT_UNICYCLE
-        return f
+        return _world_flags(self, respawn) | (_lib.CS_ROBOT_UNICYCLE if self.unicycle else 0)
 
     def descriptor(self, respawn=None) -> cs_worlds:
         d = cs_worlds()
@@ -208,8 +202,7 @@ class CrowdWorlds:
         updated rows (the state buffer itself when ``in_place``)."""
         d = self.descriptor(respawn=False)
         out = self.d_state if in_place else DeviceBuffer(self.d_state.shape)
-        check(_lib.load().cs_update_humans_parallel(C.byref(d), C.c_float(dt), C.c_void_p(_ptr(out)),
-                                                    C.c_void_p(self.stream)))
+        check(_lib.load().cs_update_humans_parallel(d, dt, _ptr(out), self.stream))
         return out
 
     def step(self, dt: float, n_substeps: int = 1, action=None) -> None:
@@ -221,8 +214,7 @@ class CrowdWorlds:
                 a_ptr = self._upload("action", np.broadcast_to(np.asarray(action, dtype=np.float32), (self.W, 2))).ptr
             else:
                 a_ptr = _ptr(action)
-        check(_lib.load().cs_step(C.byref(d), C.c_float(dt), C.c_int(n_substeps), C.c_void_p(a_ptr),
-                                  C.c_void_p(self.stream)))
+        check(_lib.load().cs_step(d, dt, n_substeps, a_ptr, self.stream))
 
     def step_trace(self, dt: float, n_substeps: int = 1, action=None) -> np.ndarray:
         """step() through cs_step_trace: the same kernel build and arithmetic, and every human's row after every fused substep:
@@ -234,8 +226,7 @@ class CrowdWorlds:
             a_ptr = self._upload("action", np.broadcast_to(np.asarray(action, dtype=np.float32), (self.W, 2))).ptr
         a_ptr = a_ptr if (action is None or isinstance(action, (np.ndarray, list, tuple))) else _ptr(action)
         out = self._buffer("trace", (int(n_substeps), self.W, self.rows, 12))
-        check(_lib.load().cs_step_trace(C.byref(d), C.c_float(dt), C.c_int(n_substeps), C.c_void_p(a_ptr), C.c_void_p(out.ptr),
-                                        C.c_void_p(self.stream)))
+        check(_lib.load().cs_step_trace(d, dt, n_substeps, a_ptr, out.ptr, self.stream))
         return out.download(self.stream)
 
     def _buffer(self, name, shape, dtype=np.float32) -> DeviceBuffer:
@@ -255,7 +246,7 @@ class CrowdWorlds:
         """[W, n, 8] rows x, y, yaw, Vx, Vy, Omega, Gx, Gy of the next state; nothing is committed."""
         d = self.descriptor(respawn=False)
         out = self._buffer("peek", (self.W, self.n, 8))
-        check(_lib.load().cs_peek(C.byref(d), C.c_float(dt), C.c_void_p(out.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_peek(d, dt, out.ptr, self.stream))
         return out.download(self.stream)
 
     def collision_reward(self, action, T: float, global_time, reward_cfg=(50.0, 1.0, -0.25, 0.2, 0.5)) -> np.ndarray:
@@ -267,8 +258,7 @@ class CrowdWorlds:
         gt = self._upload("global_time", np.broadcast_to(np.asarray(global_time, dtype=np.float32), (self.W,)))
         out = self._buffer("reward_out", (self.W, 7))
         cfg = (C.c_float * 5)(*[float(x) for x in reward_cfg])
-        check(_lib.load().cs_collision_reward(C.byref(d), C.c_void_p(act.ptr), C.c_float(T), C.c_void_p(gt.ptr),
-                                              cfg, C.c_void_p(out.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_collision_reward(d, act.ptr, T, gt.ptr, cfg, out.ptr, self.stream))
         return out.download(self.stream)
 
     def laser_scan(self, range_: float, samples: int, max_distance: float, pose=None) -> np.ndarray:
@@ -281,8 +271,7 @@ class CrowdWorlds:
         if pose is not None:
             p_ptr = self._upload("laser_pose", np.broadcast_to(np.asarray(pose, dtype=np.float32), (self.W, 3))).ptr
         out = self._buffer("laser_out", (self.W, int(samples)))
-        check(_lib.load().cs_laser_scan(C.byref(d), C.c_void_p(p_ptr), C.c_int(3), C.c_float(range_), C.c_int(int(samples)),
-                                        C.c_float(max_distance), C.c_void_p(out.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_laser_scan(d, p_ptr, 3, range_, int(samples), max_distance, out.ptr, self.stream))
         return out.download(self.stream)
 
     # ------------------------------------------------------------------ RK45 integration (runge_kutta=True)
@@ -299,8 +288,7 @@ class CrowdWorlds:
             mem.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(desired_force, dtype=np.float32), (self.W, self.n, 2))), self.stream)
         d = self.descriptor()     # (with respawn bounds set: the parallel-traffic respawn rule runs behind the solve)
         nfev = self._buffer("rk_nfev", (self.W,), np.int32)
-        check(_lib.load().cs_update_humans_rk45(C.byref(d), C.c_float(dt), C.c_void_p(mem.ptr), C.c_void_p(nfev.ptr),
-                                                C.c_void_p(self.stream)))
+        check(_lib.load().cs_update_humans_rk45(d, dt, mem.ptr, nfev.ptr, self.stream))
         return nfev.download(self.stream)
 
     def complete_rk45_simulation(self, dt: float, final_time: float, n_eval: int, desired_force=None):
@@ -318,22 +306,16 @@ class CrowdWorlds:
         ns = 6 if self.type >= 3 else 4
         out = self._buffer("rk_dense", (self.W, int(n_eval), self.n, ns))
         nfev = self._buffer("rk_nfev", (self.W,), np.int32)
-        check(_lib.load().cs_complete_rk45_simulation(C.byref(d), C.c_float(dt), C.c_float(final_time), C.c_void_p(mem.ptr), C.c_void_p(out.ptr),
-                                                      C.c_int(int(n_eval)), C.c_void_p(nfev.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_complete_rk45_simulation(d, dt, final_time, mem.ptr, out.ptr, int(n_eval), nfev.ptr, self.stream))
         return out.download(self.stream), nfev.download(self.stream)
 
     def robot_model_rk45(self, dt: float, download: bool = True):
         """update_robot(t, dt) of a robot whose SFM / HSFM model is integrated with RK45 (motion_model_manager.py:631-640), every world,
         in place on the robot rows.  Returns the number of right-hand-side evaluations [W] (``download=False``: None, no
         synchronisation -- the loop of BatchedSocialNavGym.imitation_learning_step)."""
-        if getattr(self, "robot_model", None) is None:
-            raise ValueError("no robot motion model set")
-        d = self.descriptor()
-        pr = (C.c_float * 20)(*[float(x) for x in self.robot_params])
+        args = self._robot_model_args()
         nfev = self._buffer("robot_rk_nfev", (self.W,), np.int32)
-        check(_lib.load().cs_robot_model_rk45(C.byref(d), C.c_int(self.robot_model), pr, C.c_float(self.robot_margin),
-                                              C.c_void_p(_ptr(self.d_human_margin)), C.c_void_p(_ptr(self.d_robot_memory)), C.c_float(dt),
-                                              C.c_void_p(nfev.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_robot_model_rk45(*args, dt, nfev.ptr, self.stream))
         return nfev.download(self.stream) if download else None
 
     # ------------------------------------------------------------------ the robot under a human motion model
@@ -361,40 +343,37 @@ class CrowdWorlds:
             ov = np.ascontiguousarray(orca_vertices, dtype=np.float32).reshape(-1, 8)
             self.d_orca_vertices, self.orca_n_vertices = DeviceBuffer.from_numpy(ov), len(ov)
 
-    def robot_model_step(self, dt: float, just_velocities: bool = False) -> None:
-        """update_robot(t, dt, just_velocities) of every world (motion_model_manager.py:615-653), in place on the robot rows."""
+    def _robot_model_args(self):
+        """What the robot-model entries take in front of dt: descriptor, robot_type, robot_params (host), robot_margin, d_human_margin,
+        d_robot_memory."""
         if getattr(self, "robot_model", None) is None:
             raise ValueError("no robot motion model set")
-        d = self.descriptor()
         pr = (C.c_float * 20)(*[float(x) for x in self.robot_params])
+        return self.descriptor(), self.robot_model, pr, self.robot_margin, _ptr(self.d_human_margin), _ptr(self.d_robot_memory)
+
+    def robot_model_step(self, dt: float, just_velocities: bool = False) -> None:
+        """update_robot(t, dt, just_velocities) of every world (motion_model_manager.py:615-653), in place on the robot rows."""
         fn = _lib.load().cs_robot_model_velocities if just_velocities else _lib.load().cs_robot_model_step
-        check(fn(C.byref(d), C.c_int(self.robot_model), pr, C.c_float(self.robot_margin),
-                                              C.c_void_p(_ptr(self.d_human_margin)), C.c_void_p(_ptr(self.d_robot_memory)),
-                                              C.c_float(dt), C.c_void_p(self.stream)))
+        check(fn(*self._robot_model_args(), dt, self.stream))
 
     def imitation_block(self, dt: float, n_substeps: int, graph: bool = True) -> None:
         """The substep loop of SocialNavGym.imitation_learning_step (social_nav_gym.py:259-263):
         n_substeps x { update_robot(t, dt) ; update_humans(t, dt) } = cs_imitation_block: two launches when the robot is invisible
         to the crowd (the crowd's fused substeps record what the robot sees, the robot integrates behind them), the reference's
         strict alternation of 2 x n_substeps launches otherwise.  ``graph=False``: always the alternating launches."""
-        if getattr(self, "robot_model", None) is None:
-            raise ValueError("no robot motion model set")
+        args = self._robot_model_args()
         if not graph:
             for _ in range(int(n_substeps)):
                 self.robot_model_step(dt)
                 self.step(dt, 1, None)
             return
-        d = self.descriptor()
-        pr = (C.c_float * 20)(*[float(x) for x in self.robot_params])
-        check(_lib.load().cs_imitation_block(C.byref(d), C.c_int(self.robot_model), pr, C.c_float(self.robot_margin),
-                                             C.c_void_p(_ptr(self.d_human_margin)), C.c_void_p(_ptr(self.d_robot_memory)),
-                                             C.c_float(dt), C.c_int(int(n_substeps)), C.c_void_p(self.stream)))
+        check(_lib.load().cs_imitation_block(*args, dt, int(n_substeps), self.stream))
 
     def reserve_scratch(self, n_substeps: int = 20) -> None:
         """cs_reserve_scratch: allocate, outside any stream capture, the library-owned scratch that imitation_block (fused form) or
         step (worlds beyond one block) need for this batch on its stream -- required before the first such call is CAPTURED."""
         d = self.descriptor()
-        check(_lib.load().cs_reserve_scratch(C.byref(d), C.c_int(int(n_substeps)), C.c_void_p(self.stream)))
+        check(_lib.load().cs_reserve_scratch(d, int(n_substeps), self.stream))
 
     def actual_collision_reward(self, T: float, global_time, reward_cfg=(50.0, 1.0, -0.25, 0.2, 0.5)) -> np.ndarray:
         """[W, 7] like collision_reward, from the distances of the current state (social_nav_gym.py:107-118)."""
@@ -404,8 +383,7 @@ class CrowdWorlds:
         gt = self._upload("global_time", np.broadcast_to(np.asarray(global_time, dtype=np.float32), (self.W,)))
         out = self._buffer("reward_out", (self.W, 7))
         cfg = (C.c_float * 5)(*[float(x) for x in reward_cfg])
-        check(_lib.load().cs_actual_collision_reward(C.byref(d), C.c_float(T), C.c_void_p(gt.ptr), cfg, C.c_void_p(out.ptr),
-                                                     C.c_void_p(self.stream)))
+        check(_lib.load().cs_actual_collision_reward(d, T, gt.ptr, cfg, out.ptr, self.stream))
         return out.download(self.stream)
 
     # ------------------------------------------------------------------ state access
@@ -447,7 +425,7 @@ class CrowdWorlds:
     def launch_geometry(self):
         d = self.descriptor()
         g, b, wpb = C.c_int(), C.c_int(), C.c_int()
-        check(_lib.load().cs_launch_geometry(C.byref(d), C.byref(g), C.byref(b), C.byref(wpb)))
+        check(_lib.load().cs_launch_geometry(d, C.byref(g), C.byref(b), C.byref(wpb)))
         return g.value, b.value, wpb.value
 
     def step_variant(self, entry: str = "step") -> str:
@@ -455,7 +433,7 @@ class CrowdWorlds:
         "update" = cs_update_humans_parallel out of place, "peek" = cs_peek."""
         d = self.descriptor(respawn=False if entry != "step" else None)
         buf = C.create_string_buffer(256)
-        check(_lib.load().cs_step_variant(C.byref(d), C.c_int({"step": 0, "update": 1, "peek": 2}[entry]), buf, C.c_size_t(256)))
+        check(_lib.load().cs_step_variant(d, {"step": 0, "update": 1, "peek": 2}[entry], buf, 256))
         return buf.value.decode()
 
     def staging_copy(self, depth: int = 1):
@@ -552,18 +530,7 @@ class CrowdWorlds64:
         d = _lib.cs_worlds_f64()
         d.W, d.n, d.G, d.O, d.Smax = self.W, self.n, self.G, self.O, self.Smax
         d.type = self.type
-        f = 0
-        if self.all_params_equal:
-            f |= _lib.CS_ALL_PARAMS_EQUAL
-        if self.robot_row:
-            f |= _lib.CS_ROBOT_ROW
-        if self.params_shared:
-            f |= _lib.CS_PARAMS_SHARED
-        if self.obstacles_shared:
-            f |= _lib.CS_OBSTACLES_SHARED
-        if (self.respawn_bounds is not None) if respawn is None else respawn:
-            f |= _lib.CS_RESPAWN
-        d.flags = f
+        d.flags = _world_flags(self, respawn)
         d.layout = _lib.CS_LAYOUT_AOS
         d.d_state, d.d_goals, d.d_params, d.d_safety = _ptr(self.d_state), _ptr(self.d_goals), _ptr(self.d_params), _ptr(self.d_safety)
         d.d_obstacles, d.d_robot, d.d_world_flags = _ptr(self.d_obstacles), _ptr(self.d_robot), _ptr(self.d_world_flags)
@@ -584,7 +551,7 @@ class CrowdWorlds64:
         buffer itself when ``in_place``)."""
         d = self.descriptor(respawn=False)
         out = self.d_state if in_place else DeviceBuffer(self.d_state.shape, np.float64)
-        check(_lib.load().cs_update_humans_parallel_f64(C.byref(d), C.c_double(dt), C.c_void_p(_ptr(out)), C.c_void_p(self.stream)))
+        check(_lib.load().cs_update_humans_parallel_f64(d, dt, _ptr(out), self.stream))
         return out
 
     def step(self, dt: float, n_substeps: int = 1, action=None) -> None:
@@ -599,13 +566,13 @@ class CrowdWorlds64:
                 a_ptr = buf.ptr
             else:
                 a_ptr = _ptr(action)
-        check(_lib.load().cs_step_f64(C.byref(d), C.c_double(dt), C.c_int(n_substeps), C.c_void_p(a_ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_step_f64(d, dt, n_substeps, a_ptr, self.stream))
 
     def peek(self, dt: float) -> np.ndarray:
         """[W, n, 8] rows x, y, yaw, Vx, Vy, Omega, Gx, Gy of the next state; nothing is committed."""
         d = self.descriptor(respawn=False)
         out = self._buffer("peek", (self.W, self.n, 8))
-        check(_lib.load().cs_peek_f64(C.byref(d), C.c_double(dt), C.c_void_p(out.ptr), C.c_void_p(self.stream)))
+        check(_lib.load().cs_peek_f64(d, dt, out.ptr, self.stream))
         return out.download(self.stream)
 
     # ------------------------------------------------------------------ state access

@@ -4,7 +4,6 @@ W = 1 launch of the fused decision kernel (cs_lookahead + cs_value_net_decide) t
 (``BatchedSocialNavGym.act_device``), so one robot alone and a batch give the same bits.  There is no host path for the decision."""
 from __future__ import annotations
 
-import ctypes as C
 import itertools
 import logging
 
@@ -47,9 +46,8 @@ def compute_rotated_states_and_reward(action_space, next_humans_state, current_h
         raise ValueError("state column counts do not match theta_and_omega_visible")
     d_a, d_n, d_c, d_r = (DeviceBuffer.from_numpy(x) for x in (acts, nxt, cur32, rob))
     d_rot, d_rew = DeviceBuffer((W, A, n, oc)), DeviceBuffer((W, A))
-    check(_lib.load().cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(bool(theta_and_omega_visible))),
-                                   C.c_void_p(d_a.ptr), C.c_void_p(d_n.ptr), C.c_void_p(d_c.ptr), C.c_void_p(d_r.ptr),
-                                   C.c_int(rob.shape[-1]), C.c_float(dt), C.c_void_p(d_rot.ptr), C.c_void_p(d_rew.ptr), None))
+    check(_lib.load().cs_lookahead(W, n, A, int(bool(theta_and_omega_visible)), d_a.ptr, d_n.ptr, d_c.ptr, d_r.ptr, rob.shape[-1], dt, d_rot.ptr,
+                                   d_rew.ptr, None))
     dtype = cur.dtype if cur.dtype in (np.float32, np.float64) else np.float64
     rot, rew = d_rot.download().astype(dtype), d_rew.download().astype(dtype)
     return (rot[0], rew[0]) if single else (rot, rew)

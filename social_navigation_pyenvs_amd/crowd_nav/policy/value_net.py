@@ -90,11 +90,10 @@ def _pack_with(entry, unit, kind, dims, cols, arrays, om_cols=None):
     arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
-    d = dims.ctypes.data_as(C.c_void_p)
-    head = (C.c_int(kind), d, C.c_int(len(dims)), C.c_int(cols)) + (() if om_cols is None else (C.c_int(om_cols),))
+    head = (kind, dims.ctypes.data, len(dims), cols) + (() if om_cols is None else (om_cols,))
     _lib.check(entry(*head, None, None, C.byref(nf)))
     blob = np.zeros(nf.value, unit)
-    _lib.check(entry(*head, ptrs, blob.ctypes.data_as(C.c_void_p), C.byref(nf)))
+    _lib.check(entry(*head, ptrs, blob.ctypes.data, C.byref(nf)))
     return blob
 
 
@@ -128,6 +127,18 @@ class DeviceNet:
             self._keys[precision] = key
         return self.blobs[precision]
 
+    def head(self, caller, precision="f32"):
+        """The five arguments every network entry opens with, for the blob of `precision`; ValueError in `caller`'s name without one."""
+        blob = self.blobs[check_precision(precision)]
+        if blob is None:
+            raise ValueError(f"{caller}: the network has no {precision} blob yet (DeviceNet.refresh({precision!r}))")
+        return _head(self.kind, self.dims, blob)
+
+
+def _head(kind, dims, blob):
+    """kind, dims (host int32 array), its length, the packed blob (a CUDA tensor) and its length in the blob's own unit."""
+    return kind, dims.ctypes.data, len(dims), blob.data_ptr(), blob.numel()
+
 
 def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None,
            precision="f32"):
@@ -135,15 +146,10 @@ def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, 
     blob of that precision is current (refresh(precision))."""
     from ... import _lib
 
-    P = C.c_void_p
-    blob = net.blobs[check_precision(precision)]
-    if blob is None:
-        raise ValueError(f"decide: the network has no {precision} blob yet (DeviceNet.refresh({precision!r}))")
+    head = net.head("decide", precision)
     entry = _lib.load().cs_value_net_decide_bf16 if precision == "bf16" else _lib.load().cs_value_net_decide
-    _lib.check(entry(
-        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
-        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), P(rotated), P(rewards), P(actions), P(robot), C.c_int(robot_stride),
-        C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))
+    _lib.check(entry(*head, W, A, n, net.cols, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                     action_out, stream))
 
 
 def occupancy_maps(W, n, humans, stride, vel_col, cell_num, cell_size, channels, maps, stream=None):
@@ -151,9 +157,7 @@ def occupancy_maps(W, n, humans, stride, vel_col, cell_num, cell_size, channels,
     vel_col + 1 -> maps [W][n][cell_num^2 * channels]."""
     from ... import _lib
 
-    P = C.c_void_p
-    _lib.check(_lib.load().cs_occupancy_maps(C.c_int(W), C.c_int(n), P(humans), C.c_int(stride), C.c_int(vel_col), C.c_int(cell_num),
-                                             C.c_float(cell_size), C.c_int(channels), P(maps), P(stream)))
+    _lib.check(_lib.load().cs_occupancy_maps(W, n, humans, stride, vel_col, cell_num, cell_size, channels, maps, stream))
 
 
 def maps_of(humans, vel_col, grid, stream=None):
@@ -174,16 +178,11 @@ def decide_om(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride
     """cs_value_net_decide_om on device pointers (ints): ``decide`` for a DeviceNet with map columns, maps [W][n][net.om_cols]."""
     from ... import _lib
 
-    P = C.c_void_p
-    blob = net.blobs["f32"]
-    if blob is None:
-        raise ValueError("decide_om: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    head = net.head("decide_om")
     if net.om_cols < 1:
         raise ValueError("decide_om: the network has no occupancy-map columns (DeviceNet(model, cols, om_cols))")
-    _lib.check(_lib.load().cs_value_net_decide_om(
-        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
-        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(net.cols), C.c_int(net.om_cols), P(rotated), P(maps), P(rewards), P(actions), P(robot),
-        C.c_int(robot_stride), C.c_float(gamma), C.c_float(dt), P(override), P(values), P(choice), P(action_out), P(stream)))
+    _lib.check(_lib.load().cs_value_net_decide_om(*head, W, A, n, net.cols, net.om_cols, rotated, maps, rewards, actions, robot, robot_stride,
+                                                  gamma, dt, override, values, choice, action_out, stream))
 
 
 _ROWS_BLOB = {}
@@ -196,20 +195,16 @@ def rotated_rows(cur, robot, stream=None):
 
     from ... import _lib
 
-    P = C.c_void_p
     W, n, cc = cur.shape
     cols = 15 if cc == 7 else 13
     dims = np.array([1, 1], np.int32)
     key = (cols, torch.cuda.current_device())
     if key not in _ROWS_BLOB:
         _ROWS_BLOB[key] = torch.from_numpy(pack(CS_VN_CADRL, dims, cols, [np.zeros((1, cols), np.float32), np.zeros(1, np.float32)])).to("cuda")
-    blob = _ROWS_BLOB[key]
     rows = torch.empty((W, n, cols), dtype=torch.float32, device="cuda")
     unread = torch.empty(W, dtype=torch.float32, device="cuda")
-    _lib.check(_lib.load().cs_value_net_state(
-        C.c_int(CS_VN_CADRL), dims.ctypes.data_as(P), C.c_int(len(dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()), C.c_int(W), C.c_int(n),
-        C.c_int(int(cc == 7)), P(cur.data_ptr()), P(robot.data_ptr()), C.c_int(robot.shape[1]), None, C.c_float(1.0), C.c_float(0.0),
-        P(rows.data_ptr()), P(unread.data_ptr()), P(stream)))
+    _lib.check(_lib.load().cs_value_net_state(*_head(CS_VN_CADRL, dims, _ROWS_BLOB[key]), W, n, cc == 7, cur.data_ptr(), robot.data_ptr(),
+                                              robot.shape[1], None, 1.0, 0.0, rows.data_ptr(), unread.data_ptr(), stream))
     return rows
 
 
@@ -239,16 +234,11 @@ def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, 
     float32 blob is current and whose cols match `headed`; rewards_out [W][A] or None."""
     from ... import _lib
 
-    P = C.c_void_p
-    blob = net.blobs["f32"]
-    if blob is None:
-        raise ValueError("decide_worlds: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    head = net.head("decide_worlds")
     if net.cols != (15 if headed else 13):
         raise ValueError(f"decide_worlds: a network of {net.cols} input columns and headed={bool(headed)} differ")
-    _lib.check(_lib.load().cs_value_net_decide_worlds(
-        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
-        C.c_int(W), C.c_int(A), C.c_int(n), C.c_int(int(bool(headed))), P(actions), P(nxt), P(cur), P(robot), C.c_int(robot_stride),
-        C.c_float(gamma), C.c_float(dt), P(override), P(rewards_out), P(values), P(choice), P(action_out), P(stream)))
+    _lib.check(_lib.load().cs_value_net_decide_worlds(*head, W, A, n, bool(headed), actions, nxt, cur, robot, robot_stride, gamma, dt, override,
+                                                      rewards_out, values, choice, action_out, stream))
 
 
 def state_values(net, W, n, headed, cur, robot, robot_stride, rewards, gamma, dt, rotated_out, values, stream=None):
@@ -258,16 +248,11 @@ def state_values(net, W, n, headed, cur, robot, robot_stride, rewards, gamma, dt
     DeviceNet whose float32 blob is current and whose cols match `headed`."""
     from ... import _lib
 
-    P = C.c_void_p
-    blob = net.blobs["f32"]
-    if blob is None:
-        raise ValueError("state_values: the network has no f32 blob yet (DeviceNet.refresh('f32'))")
+    head = net.head("state_values")
     if net.cols != (15 if headed else 13):
         raise ValueError(f"state_values: a network of {net.cols} input columns and headed={bool(headed)} differ")
-    _lib.check(_lib.load().cs_value_net_state(
-        C.c_int(net.kind), net.dims.ctypes.data_as(P), C.c_int(len(net.dims)), P(blob.data_ptr()), C.c_size_t(blob.numel()),
-        C.c_int(W), C.c_int(n), C.c_int(int(bool(headed))), P(cur), P(robot), C.c_int(robot_stride), P(rewards), C.c_float(gamma), C.c_float(dt),
-        P(rotated_out), P(values), P(stream)))
+    _lib.check(_lib.load().cs_value_net_state(*head, W, n, bool(headed), cur, robot, robot_stride, rewards, gamma, dt, rotated_out, values,
+                                              stream))
 
 
 def lookahead(acts, nxt, cur, robot, dt, stream=None):
@@ -277,13 +262,11 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 
     from ... import _lib
 
-    P = C.c_void_p
     (W, n, cc), A = cur.shape, acts.shape[0]
     rot = torch.empty((W, A, n, 15 if cc == 7 else 13), dtype=torch.float32, device="cuda")
     rew = torch.empty((W, A), dtype=torch.float32, device="cuda")
-    _lib.check(_lib.load().cs_lookahead(C.c_int(W), C.c_int(n), C.c_int(A), C.c_int(int(cc == 7)), P(acts.data_ptr()), P(nxt.data_ptr()),
-                                        P(cur.data_ptr()), P(robot.data_ptr()), C.c_int(robot.shape[1]), C.c_float(dt), P(rot.data_ptr()),
-                                        P(rew.data_ptr()), P(stream)))
+    _lib.check(_lib.load().cs_lookahead(W, n, A, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], dt,
+                                        rot.data_ptr(), rew.data_ptr(), stream))
     return rot, rew
 
 

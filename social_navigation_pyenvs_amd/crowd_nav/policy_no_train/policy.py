@@ -5,8 +5,6 @@
 same bits.  There is no host implementation of the policies: without a GPU ``predict`` raises ``CrowdstepError``."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from ..utils.action import ActionXY
@@ -80,10 +78,8 @@ def launch(policy_id: int, W: int, n: int, d_robot13: int, d_obs: int, obs_cols:
     from ... import _lib
 
     p = None if params is None else np.ascontiguousarray(params, np.float32)
-    _lib.check(_lib.load().cs_policy_no_train(C.c_int(policy_id), C.c_int(W), C.c_int(n), C.c_void_p(d_robot13), C.c_void_p(d_obs),
-                                              C.c_int(obs_cols), C.c_float(0.0 if time_step is None else time_step),
-                                              None if p is None else p.ctypes.data_as(C.c_void_p), C.c_void_p(d_action),
-                                              C.c_void_p(stream)))
+    _lib.check(_lib.load().cs_policy_no_train(policy_id, W, n, d_robot13, d_obs, obs_cols, 0.0 if time_step is None else time_step,
+                                              None if p is None else p.ctypes.data, d_action, stream))
 
 
 class NoTrainPolicy(Policy):

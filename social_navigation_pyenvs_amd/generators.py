@@ -8,27 +8,15 @@ state / goal / robot rows straight into the device buffers of a ``CrowdWorlds``.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._lib import DeviceBuffer, check
+from ._lib import DeviceBuffer, check, cs_generator
 
 SCENARIOS = {"circle_crossing": 0, "parallel_traffic": 1, "circular_crossing_with_static_obstacles": 2,
              "hybrid_scenario": 3}
 SCENARIO_NAMES = {v: k for k, v in SCENARIOS.items()}
 MAX_PLACEMENT_TRIES = 100000  # same bound as the host generators (social_gym/social_nav_sim.py)
-
-
-class cs_generator(C.Structure):
-    _fields_ = [
-        ("scenario", C.c_int32), ("n", C.c_int32), ("insert_robot", C.c_int32), ("randomize_attributes", C.c_int32),
-        ("randomize_positions", C.c_int32), ("max_tries", C.c_int32),
-        ("circle_radius", C.c_double), ("traffic_length", C.c_double), ("traffic_height", C.c_double),
-        ("robot_radius", C.c_double), ("human_mass", C.c_double), ("robot_mass", C.c_double),
-        ("robot_desired_speed", C.c_double),
-    ]
 
 
 def phase_seeds(phase: str, first_case: int, W: int, case_capacity=None) -> np.ndarray:
@@ -61,12 +49,10 @@ def generate_worlds_device(cw, gen: cs_generator, d_seeds, d_mask=None, d_status
     from .batched import _ptr
 
     lib = _lib.load()
-    nbytes = int(lib.cs_generate_scratch_bytes(C.c_int(cw.W)))
+    nbytes = int(lib.cs_generate_scratch_bytes(cw.W))
     d_scratch = cw._buffer("gen_mt19937", (nbytes // 4,), np.uint32)
     d = cw.descriptor()
-    check(lib.cs_generate_worlds(C.byref(gen), C.byref(d), C.c_void_p(_ptr(d_seeds)), C.c_void_p(_ptr(d_mask)),
-                                 C.c_void_p(_ptr(d_status)), C.c_void_p(_ptr(d_scenario)), C.c_void_p(d_scratch.ptr),
-                                 C.c_void_p(cw.stream)))
+    check(lib.cs_generate_worlds(gen, d, _ptr(d_seeds), _ptr(d_mask), _ptr(d_status), _ptr(d_scenario), d_scratch.ptr, cw.stream))
 
 
 def generate_worlds(cw, scenario, seeds, *, mask=None, insert_robot=True, randomize_attributes=False,
@@ -77,29 +63,22 @@ def generate_worlds(cw, scenario, seeds, *, mask=None, insert_robot=True, random
 
     Returns ``(status [W] int32, scenario [W] int32)``; with ``raise_on_failure`` a non-zero status raises what the
     host generators raise (RuntimeError: could not place, ValueError: traffic too dense)."""
-    if isinstance(scenario, str):
-        scenario = SCENARIOS[scenario]
-    g = cs_generator()
-    g.scenario, g.n = int(scenario), int(cw.n)
-    g.insert_robot, g.randomize_attributes, g.randomize_positions = int(insert_robot), int(randomize_attributes), int(randomize_positions)
-    g.max_tries = int(max_tries)
-    g.circle_radius, g.traffic_length, g.traffic_height = float(circle_radius), float(traffic_length), float(traffic_height)
-    g.robot_radius, g.human_mass = float(robot_radius), float(human_mass)
-    g.robot_mass, g.robot_desired_speed = float(robot_mass), float(robot_desired_speed)
+    g = make_generator(cw, scenario, insert_robot=insert_robot, randomize_attributes=randomize_attributes, randomize_positions=randomize_positions,
+                       circle_radius=circle_radius, traffic_length=traffic_length, traffic_height=traffic_height, robot_radius=robot_radius,
+                       human_mass=human_mass, robot_mass=robot_mass, robot_desired_speed=robot_desired_speed, max_tries=max_tries)
     seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (cw.W,)))
     lib = _lib.load()
     d_seeds = cw._upload("gen_seeds", seeds, np.uint32)
     d_mask = None if mask is None else cw._upload("gen_mask", np.broadcast_to(np.asarray(mask).astype(np.int32), (cw.W,)), np.int32)
     d_status = cw._buffer("gen_status", (cw.W,), np.int32)
     d_scn = cw._buffer("gen_scenario", (cw.W,), np.int32)
-    nbytes = int(lib.cs_generate_scratch_bytes(C.c_int(cw.W)))
+    nbytes = int(lib.cs_generate_scratch_bytes(cw.W))
     d_scratch = cw._buffer("gen_mt19937", (nbytes // 4,), np.uint32)
     if mask is not None:
-        check(lib.cs_memset(C.c_void_p(d_status.ptr), C.c_int(0), C.c_size_t(cw.W * 4), C.c_void_p(cw.stream)))
-        check(lib.cs_memset(C.c_void_p(d_scn.ptr), C.c_int(0xFF), C.c_size_t(cw.W * 4), C.c_void_p(cw.stream)))
+        check(lib.cs_memset(d_status.ptr, 0, cw.W * 4, cw.stream))
+        check(lib.cs_memset(d_scn.ptr, 0xFF, cw.W * 4, cw.stream))
     d = cw.descriptor()
-    check(lib.cs_generate_worlds(C.byref(g), C.byref(d), C.c_void_p(d_seeds.ptr), C.c_void_p(None if d_mask is None else d_mask.ptr),
-                                 C.c_void_p(d_status.ptr), C.c_void_p(d_scn.ptr), C.c_void_p(d_scratch.ptr), C.c_void_p(cw.stream)))
+    check(lib.cs_generate_worlds(g, d, d_seeds.ptr, None if d_mask is None else d_mask.ptr, d_status.ptr, d_scn.ptr, d_scratch.ptr, cw.stream))
     status = d_status.download(cw.stream)
     scn = d_scn.download(cw.stream)
     if raise_on_failure and np.any(status != 0):

@@ -653,13 +653,10 @@ class BatchedSocialNavGym:
 
     def _observe_if_stale(self, dl):
         """No step since the batch was generated: the observation of the resident rows (what a decision in a launch of its own reads)."""
-        import ctypes as C
-
         if dl.get("obs_fresh"):
             return
         d = self.cw.descriptor(respawn=False)
-        _lib.check(_lib.load().cs_gym_observe(C.byref(d), C.c_int(int(self.headed_obs)), C.c_void_p(dl["obs"].data_ptr()),
-                                              C.c_void_p(dl["stream"].cuda_stream)))
+        _lib.check(_lib.load().cs_gym_observe(d, self.headed_obs, dl["obs"].data_ptr(), dl["stream"].cuda_stream))
         dl["obs_fresh"] = True
 
     def step_device(self, actions, auto_reset=True):
@@ -776,7 +773,7 @@ class BatchedSocialNavGym:
 
         d = self.cw.descriptor()
         buf = C.create_string_buffer(320)
-        _lib.check(_lib.load().cs_gym_step_policy_variant(C.byref(d), buf, C.c_size_t(320)))
+        _lib.check(_lib.load().cs_gym_step_policy_variant(d, buf, 320))
         return buf.value.decode()
 
     def _act_device_value(self, dl, pol, explore):
@@ -960,8 +957,6 @@ class BatchedSocialNavGym:
     def _worlds_on_side_stream(self, dl, next_humans=None, peek=True):
         """What a look-ahead reads of the resident worlds, as contiguous CUDA tensors: (next humans [W, n, 4 | 6] -- cs_peek's, or the caller's;
         None without ``peek``: the current state alone is asked for --, current humans [W, n, 5 | 7], robot rows [W, 9] in FullState order)."""
-        import ctypes as C
-
         import torch
 
         cw, W, n = self.cw, self.W, self.n
@@ -969,7 +964,7 @@ class BatchedSocialNavGym:
         d = cw.descriptor(respawn=False)
         peek_buf = cw._buffer("peek", (W, n, 8))
         if next_humans is None and peek:
-            _lib.check(lib.cs_peek(C.byref(d), C.c_float(self.robot_time_step), C.c_void_p(peek_buf.ptr), C.c_void_p(cw.stream)))
+            _lib.check(lib.cs_peek(d, self.robot_time_step, peek_buf.ptr, cw.stream))
         if "la_cols" not in dl:
             # next humans: (px, py, vx, vy), or (x, y, yaw, Vx, Vy, Omega) with theta / omega visible (cadrl.py:42-83) = cs_peek's first six
             dl["la_cols"] = torch.as_tensor([0, 1, 2, 3, 4, 5] if self.headed_obs else [0, 1, 3, 4], device="cuda")

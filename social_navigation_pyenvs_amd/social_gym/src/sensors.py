@@ -10,7 +10,6 @@ Deliberate deviation: the reference leaves ``self.uncertainty`` unset when the c
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
@@ -55,8 +54,7 @@ def laser_scan(states, pose, range_, samples, max_distance, obstacles=None, stre
         d.d_obstacles = d_obs.ptr
     d_pose = DeviceBuffer.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(pose, np.float32), (W, 3))))
     out = DeviceBuffer((W, int(samples)), np.float32)
-    check(_lib.load().cs_laser_scan(C.byref(d), C.c_void_p(d_pose.ptr), C.c_int(3), C.c_float(range_), C.c_int(int(samples)),
-                                    C.c_float(max_distance), C.c_void_p(out.ptr), C.c_void_p(stream)))
+    check(_lib.load().cs_laser_scan(d, d_pose.ptr, 3, range_, int(samples), max_distance, out.ptr, stream))
     return out.download(stream)
 
 

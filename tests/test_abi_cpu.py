@@ -26,6 +26,117 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert "#define CS_ABI_VERSION 4" in hdr          # header, library and binding name one ABI
 
 
+# include/crowdstep.h type -> ctypes, as social_navigation_pyenvs_amd/_lib.py ABI states them; every pointer not named here is a c_void_p
+_HEADER_TYPES = {"int": "c_int", "int32_t": "c_int", "unsigned": "c_uint", "uint32_t": "c_uint", "unsigned long long": "c_ulonglong",
+                 "size_t": "c_size_t", "float": "c_float", "double": "c_double"}
+_HEADER_STRUCTS = ("cs_worlds", "cs_worlds_f64", "cs_generator", "cs_gym_book", "cs_stage_book")
+_HEADER_RESULTS = {"int": "c_int", "size_t": "c_size_t", "const char*": "c_char_p"}
+
+
+def _header_prototypes(header):
+    """{symbol: (restype, [argtypes])} of every prototype of the header; ValueError on a parameter type the mapping does not know."""
+    import ctypes as C
+
+    from social_navigation_pyenvs_amd import _lib
+
+    out = {}
+    for m in re.finditer(r"^(int|size_t|const char\*) (cs_\w+)\(([^;]*?)\);", header, re.M | re.S):
+        res, name, params = m.groups()
+        args = []
+        for p in re.sub(r"/\*.*?\*/", " ", params, flags=re.S).split(","):
+            p = " ".join(p.split())
+            if p == "void":
+                continue
+            t = re.sub(r"\s*\*", "*", re.sub(r"\s*\b\w+$", "", p))     # without the parameter's name; "float *" -> "float*"
+            if t in _HEADER_TYPES:
+                args.append(getattr(C, _HEADER_TYPES[t]))
+            elif t.startswith("const cs_") and t[6:-1] in _HEADER_STRUCTS and t.endswith("*") and t.count("*") == 1:
+                args.append(C.POINTER(getattr(_lib, t[6:-1])))
+            elif re.fullmatch(r"(const )?(void|char|int|float|double|size_t|u?int(8|32)_t|unsigned long long)\*( const\*|\*)?", t):
+                args.append(C.c_void_p)
+            else:
+                raise ValueError(f"{name}: parameter type {t!r} ({p!r}) has no ctypes mapping")
+        out[name] = (getattr(C, _HEADER_RESULTS[res]), args)
+    return out
+
+
+def test_signature_table_is_the_header():
+    """Every prototype of include/crowdstep.h, parsed, is the (restype, argtypes) entry of _lib.ABI, and the loaded library's functions
+    carry exactly those."""
+    from social_navigation_pyenvs_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "crowdstep.h")).read()
+    protos = _header_prototypes(header)
+    declared = set(re.findall(r"\b(cs_[a-z0-9_]+)\s*\(", header)) - {"cs_status"}
+    assert set(protos) == declared == set(_lib.ABI)
+    lib = _lib.load()
+    for name, (restype, argtypes) in protos.items():
+        assert (_lib.ABI[name][0], list(_lib.ABI[name][1])) == (restype, argtypes), name
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
+    with pytest.raises(ValueError, match="no ctypes mapping"):
+        _header_prototypes("int cs_x(int a, long b);")
+    with pytest.raises(ValueError, match="no ctypes mapping"):
+        _header_prototypes("int cs_x(const cs_unknown* u);")
+
+
+def test_wrong_arguments_are_refused_in_python_before_c():
+    """A descriptor of the other precision, a float for an int, an int wrapper for a float, a short argument list: ctypes refuses each
+    by the header's types, nothing reaches the library."""
+    import ctypes as C
+
+    from social_navigation_pyenvs_amd import _lib
+
+    lib = _lib.load()
+    w32, w64 = _lib.cs_worlds(), _lib.cs_worlds_f64()
+    refused = (C.ArgumentError, TypeError)
+    with pytest.raises(refused):
+        lib.cs_step(C.byref(w64), 0.0125, 1, None, None)
+    with pytest.raises(refused):
+        lib.cs_step_f64(C.byref(w32), 0.0125, 1, None, None)
+    with pytest.raises(refused):
+        lib.cs_step(C.byref(w32), 0.0125, 1.5, None, None)               # n_substeps
+    with pytest.raises(refused):
+        lib.cs_step(C.byref(w32), C.c_int(1), 1, None, None)             # dt
+    with pytest.raises(refused):
+        lib.cs_step(C.byref(w32), 0.0125, 1, None)                       # no stream
+    assert lib.cs_step(C.byref(w32), 0.0125, 1, None, None) == _lib.CS_ERR_ARG      # the well-typed call gets as far as the library's own checks
+
+
+def test_bare_addresses_reach_c_whole():
+    """cs_value_net_pack (host only) with dims, the parameter-pointer array and the blob given as bare ints fills the bytes of the wrapped
+    call -- with the blob above 4 GiB, where an address cut to 32 bits would not arrive."""
+    import ctypes as C
+
+    import numpy as np
+
+    from social_navigation_pyenvs_amd import _lib
+
+    lib = _lib.load()
+    rng = np.random.default_rng(5)
+    dims = np.array([1, 2, 9, 6, 2, 7, 5, 2, 4, 1, 2, 6, 1], np.int32)     # SARL with the global state: mlp1 9-6, mlp2 7-5, attention 4-1, mlp3 6-1
+    ins = [13, 9, 6, 7, 12, 4, 11, 6]                                         # attention reads (mlp1, its mean) = 12, mlp3 (6 self columns, mlp2) = 11
+    outs = [9, 6, 7, 5, 4, 1, 6, 1]
+    arrays = [a for k, n in zip(ins, outs) for a in (rng.standard_normal((n, k)).astype(np.float32), rng.standard_normal(n).astype(np.float32))]
+    ptrs = np.array([a.ctypes.data for a in arrays], np.uint64)
+    nf = C.c_size_t(0)
+    assert lib.cs_value_net_pack(1, dims.ctypes.data, len(dims), 13, None, None, C.byref(nf)) == 0, lib.cs_last_error()
+    keep = []
+    while True:                                                               # a few MiB: mmap-backed, high in the address space
+        blob = np.full(max(nf.value, 1 << 20), np.float32(-7.0))
+        if blob.ctypes.data >= 2 ** 32:
+            break
+        keep.append(blob)
+        assert len(keep) < 64, "no allocation above 4 GiB"
+    assert blob.ctypes.data >= 2 ** 32
+    wrapped = np.full_like(blob, -7.0)
+    assert lib.cs_value_net_pack(C.c_int(1), dims.ctypes.data_as(C.c_void_p), C.c_int(len(dims)), C.c_int(13), ptrs.ctypes.data_as(C.c_void_p),
+                                 wrapped.ctypes.data_as(C.c_void_p), C.byref(nf)) == 0, lib.cs_last_error()
+    assert lib.cs_value_net_pack(1, dims.ctypes.data, len(dims), 13, ptrs.ctypes.data, blob.ctypes.data, C.byref(nf)) == 0, lib.cs_last_error()
+    assert np.any(wrapped[:nf.value] != -7.0)
+    assert blob.tobytes() == wrapped.tobytes()
+
+
 def test_library_on_disk_was_built_from_the_sources_on_disk():
     """The rebuild is keyed on a content hash of csrc/* + include/*: the id the LOADED library reports (cs_build_id) must
     be the hash of the sources in the tree, so a stale prebuilt .so cannot pass for the current code."""
@@ -157,9 +268,9 @@ def test_new_entry_points_reject_bad_arguments_before_touching_a_device():
 
     lib = _lib.load()
     null = C.c_void_p(None)
-    assert lib.cs_gym_step(null, C.c_float(0.0125), C.c_int(20), null, C.c_float(0.25), null, null, null, null, C.c_int(0), null, null) == _lib.CS_ERR_ARG
-    assert lib.cs_refill_staged_worlds(null, null, null, null) == _lib.CS_ERR_ARG
-    assert lib.cs_consume_staged_worlds(null, null, null, null, null, C.c_int(0), null, null) == _lib.CS_ERR_ARG
+    assert lib.cs_gym_step(None, C.c_float(0.0125), C.c_int(20), null, C.c_float(0.25), null, null, null, None, C.c_int(0), null, null) == _lib.CS_ERR_ARG
+    assert lib.cs_refill_staged_worlds(None, None, None, null) == _lib.CS_ERR_ARG
+    assert lib.cs_consume_staged_worlds(None, None, None, null, None, C.c_int(0), null, null) == _lib.CS_ERR_ARG
     buf = C.create_string_buffer(8)
     assert lib.cs_device_pci_bus_id(C.c_int(0), buf, C.c_size_t(8)) == _lib.CS_ERR_ARG          # buffer too small for "0000:00:00.0"
     done = C.c_int(0)
