@@ -348,13 +348,21 @@ int step_wg_waves_for(size_t shmem)
 // cs_step_variant, which reports it: the blocks a CU holds are decided by it -- sixteen of the 25-row build, twelve of the 50-row
 // wall build -- and a region added for one build on every launch costs the others a block without any test noticing; tests/test_gpu_parity.py
 // asserts the figures of the benched builds).
-size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, bool peq, int& seg_tab, int& wall_pairs)
+size_t step_lds_bytes(const cs_worlds* w, const Geometry& g, const Variant& v, int& seg_tab, int& wall_pairs)
 {
+    const bool peq = v.peq;
     // lds_p [2][2T+PADR] float4, lds_v [2][2T+PADR] float2, lds_vr [2][T] float2, respawn scratch 2 x [T] x 4 B,
     // reaction accumulators [UA][2T] float2 (pair-once loop: all_params_equal, block of one wavefront)
     size_t shmem = (size_t)g.block * (4 * sizeof(float4) + 4 * sizeof(float2) + 2 * sizeof(float2) + 2 * sizeof(float)) +
                    2 * PADR * (sizeof(float4) + sizeof(float2)) +
                    ((peq && g.block == 64) ? (size_t)UA * ACC_PITCH * sizeof(float2) : 0);
+    // the plain one-wavefront builds with a compile-time row count (sfmstep_kernel.h XY_ROWS, policy twins included): 8-byte position rows
+    // lds_xy [2][2T+PADR] float2 and lds_rs [T] float instead of lds_p, and lds_v only where the pair loop reads it (Moussaid)
+    if (xy_rows_build(v.maxt, v.lean, v.rows_ct)) {
+        const size_t rows2 = xy_rows_velocities(w->type % 3) ? 2 : 1;   // doubled float2 row sets: positions (+ velocities)
+        shmem = (size_t)g.block * (rows2 * 4 * sizeof(float2) + sizeof(float) + 2 * sizeof(float2) + 2 * sizeof(float)) +
+                2 * PADR * rows2 * sizeof(float2) + (size_t)UA * ACC_PITCH * sizeof(float2);
+    }
     // per-agent parameters on the pair-once loop (Helbing / Guo, block of one wavefront): reaction accumulators + the partners' parameter rows
     if (!peq && g.block == 64 && w->type % 3 != 2)
         shmem += (size_t)UA * ACC_PITCH * sizeof(float2) + (size_t)(2 * g.block + PADR) * sizeof(float4);
@@ -395,7 +403,7 @@ int step_plan(const cs_worlds* w, int mode, StepPlan& p, bool need_snap = false,
     if (p.v.maxt != 64 && p.v.maxt != 1024) return CS_OK;
     p.fn = variant_kernel(p.v, w->type);
     if (policy) { p.twin = policy_twin(p.v); p.twin_fn = variant_kernel(p.twin, w->type); }
-    p.lds = step_lds_bytes(w, p.g, p.v.peq, p.seg_tab, p.wall_pairs);
+    p.lds = step_lds_bytes(w, p.g, p.v, p.seg_tab, p.wall_pairs);
     if (p.g.block == 64) p.wg = step_wg_waves_for(p.lds);
     return CS_OK;
 }

@@ -63,6 +63,11 @@ constexpr int ACC_PITCH = 128; // float2 slots per accumulator row (block = one 
 // the LEAN values by name (the template parameter stays the int: no instantiation's name moves)
 constexpr int LEAN_GENERIC = 0, LEAN_PLAIN = 1, LEAN_WALLS = 2, LEAN_ROBOT_ROW = 3, LEAN_IMITATION = 4, LEAN_ROBOT_ROW_WALLS = 5;
 constexpr int LEAN_POLICY = 8;   // the policy bit, on top of LEAN_PLAIN / LEAN_ROBOT_ROW
+// The builds with 8-byte LDS position rows (XY_ROWS in the kernel): plain crowd batch (policy twins included), one wavefront, compile-time
+// row count -- and whether such a build keeps the velocity rows (Moussaid reads partner velocities in every pair).  One statement for the
+// kernel's LDS views and for the host's sizing of them (crowdstep.hip step_lds_bytes).
+constexpr bool xy_rows_build(int maxt, int lean_arg, int rows_ct) { return maxt == 64 && (lean_arg & (LEAN_POLICY - 1)) == LEAN_PLAIN && rows_ct > 0; }
+constexpr bool xy_rows_velocities(int soc) { return soc == 2; }
 constexpr int WG_WAVES_MAX = 4;   // (launch bound of the one-wavefront builds: four independent wavefronts per workgroup; a bound of eight -- which measures the same as
                                   //  four -- makes the compiler allocate the Moussaid builds ten registers fewer and their launches 2 us longer)
 template <int SOC, int HEADED, bool PEQ, int MAXT, int OCC, int ROWS_CT, int LEAN_ARG>
@@ -98,9 +103,22 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     // i+1 .. i+rows-1 at constant offsets from one base address -- no own-row slot, no modulo, no
     // per-partner compare (v_cmp + v_cndmask costs as much as a transcendental on this SIMD).
     const int TP = 2 * T + PADR;                                   // rows per position buffer (+ finite padding)
-    float4* lds_p = reinterpret_cast<float4*>(smem_raw);           // [2][TP] x, y, radius+safety, -
-    float2* lds_v = reinterpret_cast<float2*>(lds_p + 2 * TP);     // [2][TP] stored linear velocity (doubled rows like lds_p)
-    float2* lds_vr = lds_v + 2 * TP;                               // [2][T] velocity as refreshed in-place
+    float4* lds_p = xy_rows_build(MAXT, LEAN_ARG, ROWS_CT) ? nullptr : reinterpret_cast<float4*>(smem_raw);   // [2][TP] x, y, radius+safety, -
+    // The plain one-wavefront builds with a compile-time row count (XY_ROWS: the family of ONE_REGION below) publish 8-byte (x, y) rows
+    // instead: a substep reads nothing else of a partner (radius + safety space sits in registers, rsj[]).  (By the bank rule of the MI355X
+    // LDS table, (a / 4) mod 32 for the paired form, the lanes l and l + 8 of a group meet on one bank at a 16-byte stride and on none at
+    // an 8-byte one: a derivation; what the counters say of it is in HISTORY.md.)  radius + safety space is published once per launch in
+    // a 4-byte row per lane (lds_rs) for the two readers it has left: the prologue's rsj[] fill and the respawn rule's maximum radius.
+    // lds_p is not allocated in these builds (the pointer is null there: nothing may read through it), and neither is lds_v where nothing
+    // reads it (Helbing / Guo: partner velocities come from registers in the contact pass); step_lds_bytes (crowdstep.hip) sizes the
+    // block from the same two predicates: 10128 -> 6032 bytes (Moussaid: 8208) for a wavefront.
+    constexpr bool XY_ROWS = xy_rows_build(MAXT, LEAN_ARG, ROWS_CT);
+    constexpr bool XY_VEL = xy_rows_velocities(SOC);
+    float2* lds_xy = reinterpret_cast<float2*>(smem_raw);          // (XY_ROWS) [2][TP] x, y: doubled rows, same partner offsets as lds_p
+    float* lds_rs = reinterpret_cast<float*>(lds_xy + 2 * TP);     // (XY_ROWS) [T] radius + safety space of the lane's row
+    float2* lds_v = XY_ROWS ? reinterpret_cast<float2*>(lds_rs + T)
+                            : reinterpret_cast<float2*>(lds_p + 2 * TP);   // [2][TP] stored linear velocity (doubled rows like lds_p)
+    float2* lds_vr = lds_v + ((XY_ROWS && !XY_VEL) ? 0 : 2 * TP);  // [2][T] velocity as refreshed in-place
     float* lds_g0x = reinterpret_cast<float*>(lds_vr + 2 * T);     // [T] respawn scratch
     int* lds_flag = reinterpret_cast<int*>(lds_g0x + T);           // [T] respawn scratch
     float2* lds_acc = reinterpret_cast<float2*>(lds_flag + T);     // [UA][2T] reaction accumulators (N3L only)
@@ -156,7 +174,7 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     // Same bits in every build it reaches; 4096 x 25: 27.06 -> 26.50 us per launch, 25 scalar instructions and 7 exec regions fewer per
     // substep.  (Two substeps per trip with the buffer index and the priority turn as constants of each half measured 26.56 us and moved
     // the compiler's contraction choices, i.e. the bits: HISTORY.md.)
-    constexpr bool ONE_REGION = MAXT == 64 && LEAN == LEAN_PLAIN && ROWS_CT > 0;
+    constexpr bool ONE_REGION = XY_ROWS;
     // ... and carry the refreshed linear velocity (part A: R(theta) bv) from the tail, which forms the new stored velocity from the same
     // operands by the same expression -- in x also by the same instructions, in y with the other product rounded first (the compiler's
     // contraction; sfmstep_sub_tail.inc writes both out as they have always been compiled, so that no bit moves).  Substep 0 forms it from

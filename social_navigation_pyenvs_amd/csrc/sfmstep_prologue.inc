@@ -143,6 +143,11 @@
     // Helbing / Guo exponents with MY radius + safety space folded into the offset: (r_ij - d) cB + lA = (rs_j - d) cB + (lA + rs_i cB),
     // one add less per pair; the contact test rd > 0 becomes max(rs_j - d) > -rs_i
     float lAi = 0.0f, lCi = 0.0f;
+    // (XY_ROWS builds: no zeroing pass.  Nothing there reads a row that was not published: every LDS read of the substep loop and of the
+    // rsj[] fill sits inside `if (valid)`, and a valid lane reads the rows pbase + row + 1 + k, k <= (rows - 1) / 2, of the position
+    // (Moussaid: and velocity) buffer -- below pbase + 2 rows, the two copies its own world's lanes publish before the first read -- and
+    // the rows base .. base + rows - 1 of lds_rs; the padding behind the buffers is never touched.)
+    if constexpr (!XY_ROWS)
     for (int i = tid; i < 2 * TP; i += T) { // padding stays finite
         lds_p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         lds_v[i] = make_float2(0.0f, 0.0f);
@@ -169,12 +174,17 @@
         }
         lds_poly[q] = make_float4(cx, cy, cnt > 0.0f ? sqrtf(r2) : -1.0e30f, 0.0f);   // an empty polygon is never near
     }
-    // radius + safety space never changes during a launch: it is stored once in both buffers, a substep only rewrites
-    // (x, y) -- two 8-byte LDS stores instead of two 16-byte ones
+    // radius + safety space never changes during a launch: it is stored once (in both buffers' rows; XY_ROWS builds: in lds_rs, beside
+    // rows that hold nothing but (x, y)), a substep only rewrites (x, y) -- two 8-byte LDS stores instead of two 16-byte ones
     auto publish = [&](int buf) {      // my position, both copies
         const float2 me = make_float2(px, py);
+        if constexpr (XY_ROWS) {
+            lds_xy[buf * TP + pbase + row] = me;
+            lds_xy[buf * TP + pbase + rows + row] = me;
+        } else {
         *reinterpret_cast<float2*>(&lds_p[buf * TP + pbase + row]) = me;
         *reinterpret_cast<float2*>(&lds_p[buf * TP + pbase + rows + row]) = me;
+        }
     };
     // Helbing / Guo pair-once builds read partner velocities only in the (rare) contact pass, which publishes them itself
     constexpr bool VEL_ON_DEMAND = N3L && SOC != 2 && PEQ;
@@ -186,10 +196,16 @@
     };
     if (valid) {
         // (PP: the sign of my C / A goes along in the free fourth slot: the partner that evaluates my side needs it)
+        if constexpr (XY_ROWS) {
+            publish(0);
+            publish(1);
+            lds_rs[tid] = my_rs;   // (tid = base + row)
+        } else {
         const float4 me = make_float4(px, py, my_rs, PP ? sp.sAC : 0.0f);
         for (int buf = 0; buf < 2; ++buf) {
             lds_p[buf * TP + pbase + row] = me;
             lds_p[buf * TP + pbase + rows + row] = me;
+        }
         }
         if constexpr (PP) {
             // my side of a pair as my partner will evaluate it: exponent (rs_partner - dist) cB + (lA + cB rs_me); a row without
@@ -239,11 +255,14 @@
         if (valid) {
 #pragma unroll
             for (int k = 0; k < RSN; ++k) {
+                if constexpr (!XY_ROWS) {
                 const float4 pk = lds_p[pbase + row + 1 + k];
                 rsj[k] = pk.z;
                 if constexpr (PP) { sacj[k] = pk.w; ppj[k] = lds_pp[pbase + row + 1 + k]; }
+                }
                 const int t = row + 1 + k;
                 aoff[k] = t >= ROWS_CT ? t - ROWS_CT : t;
+                if constexpr (XY_ROWS) rsj[k] = lds_rs[base + aoff[k]];   // (a 4-byte read of the partner's own row: lds_rs is not doubled)
             }
         }
     }

@@ -13,8 +13,9 @@
                 write_trace(a.trace + (((long)(sub - 1) * a.W + w) * rows + row) * 12, px, py, th, vx, vy, bvx, bvy, om, gx, gy, g0x, g0y);
         }
         const int Hf = (rows - 1) >> 1;
-        const float4* rp = lds_p + cur * TP + pbase + row + 1;   // rp[k]: partner at ring distance k + 1
+        const float4* rp = XY_ROWS ? nullptr : lds_p + cur * TP + pbase + row + 1;   // rp[k]: partner at ring distance k + 1 (XY_ROWS builds: rxy below)
         const float2* rv = lds_v + cur * TP + pbase + row + 1;
+        const float2* rxy = lds_xy + cur * TP + pbase + row + 1;   // (XY_ROWS) the 8-byte rows: rxy[k] partner at ring distance k + 1
         const float4* rpp = lds_pp + pbase + row + 1;            // (PP) ... and its parameter row
         float4 qa[UA], pa[PP ? UA : 1];
         float2 va[UA];
@@ -30,7 +31,10 @@
         auto fetch = [&](float4 (&q)[UA], float2 (&vq)[UA], int kk) {
 #pragma unroll
             for (int u = 0; u < UA; ++u) {
-                if constexpr (ROWS_CT > 0 && N3L) {   // (kk is a compile-time constant at every call of these builds)
+                if constexpr (XY_ROWS) {
+                    const float2 xy = rxy[kk + u];
+                    q[u] = make_float4(xy.x, xy.y, rsj[kk + u], 0.0f);
+                } else if constexpr (ROWS_CT > 0 && N3L) {   // (kk is a compile-time constant at every call of these builds)
                     const float2 xy = *reinterpret_cast<const float2*>(&rp[kk + u]);
                     q[u] = make_float4(xy.x, xy.y, rsj[kk + u], PP ? sacj[kk + u] : 0.0f);
                 } else {
@@ -86,7 +90,8 @@
         float2 vz = make_float2(0.0f, 0.0f);
         if constexpr (LEAN && NO_WALLS) {
             if (valid && (rows & 1) == 0) {
-                if constexpr (ROWS_CT > 0 && N3L) { const float2 xy = *reinterpret_cast<const float2*>(&rp[(ROWS_CT - 1) / 2]); qz = make_float4(xy.x, xy.y, rsj[(ROWS_CT - 1) / 2], 0.0f); }
+                if constexpr (XY_ROWS) { const float2 xy = rxy[(ROWS_CT - 1) / 2]; qz = make_float4(xy.x, xy.y, rsj[(ROWS_CT - 1) / 2], 0.0f); }
+                else if constexpr (ROWS_CT > 0 && N3L) { const float2 xy = *reinterpret_cast<const float2*>(&rp[(ROWS_CT - 1) / 2]); qz = make_float4(xy.x, xy.y, rsj[(ROWS_CT - 1) / 2], 0.0f); }
                 else qz = rp[Hf];
                 if constexpr (SOC == 2) vz = rv[Hf];
             }

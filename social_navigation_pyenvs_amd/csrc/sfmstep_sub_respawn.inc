@@ -18,8 +18,29 @@
                     const unsigned long long fm = __builtin_amdgcn_ballot_w64(true);
                     const unsigned long long wm = (rows >= 64 ? ~0ull : ((1ull << rows) - 1ull)) << base;
                     const int c = __builtin_popcountll(fm & wm & ((1ull << tid) - 1ull));
-                    const float4* pvn = lds_p + nxt * TP + pbase;
-                    float mx = pvn[0].x, mr = pvn[0].z;
+                    const float4* pvn = XY_ROWS ? nullptr : lds_p + nxt * TP + pbase;
+                    float mx, mr;
+                    if constexpr (XY_ROWS) {
+                        // x from the 8-byte rows, radius + safety space from its own row (n == rows here: no robot row).  Up to 32 rows:
+                        // every row requested before the first wait (a scheduling barrier between the requests and the maxima) -- one LDS
+                        // round trip where the compiler, left alone, waited four times; the maxima in the order they have always had.
+                        const float2* xyn = lds_xy + nxt * TP + pbase;
+                        const float* rsn = lds_rs + base;
+                        if constexpr (ROWS_CT <= 32 && OCC == 1) {
+                            float xs[ROWS_CT], rss[ROWS_CT];
+#pragma unroll
+                            for (int j = 0; j < ROWS_CT; ++j) { xs[j] = xyn[j].x; rss[j] = rsn[j]; }
+                            __builtin_amdgcn_sched_barrier(0);
+                            mx = xs[0]; mr = rss[0];
+#pragma unroll
+                            for (int j = 1; j < ROWS_CT; ++j) { mx = fmaxf(mx, xs[j]); mr = fmaxf(mr, rss[j]); }
+                        } else {
+                            mx = xyn[0].x; mr = rsn[0];
+#pragma unroll 8
+                            for (int j = 1; j < ROWS_CT; ++j) { mx = fmaxf(mx, xyn[j].x); mr = fmaxf(mr, rsn[j]); }
+                        }
+                    } else {
+                    mx = pvn[0].x; mr = pvn[0].z;
                     // (the rows requested together -- all of them when the row count is a compile-time constant, eight per trip otherwise:
                     // one at a time was 24 dependent LDS round trips per respawn, and the launch waits for its slowest wavefront: 31.1 -> 29.9 us at cfg3)
                     if constexpr (ROWS_CT > 0 && ROWS_CT <= 32) {
@@ -38,6 +59,7 @@
                         const float4 qr = lds_p[cur * TP + pbase + n];
                         mx = fmaxf(mx, qr.x);
                         mr = fmaxf(mr, qr.z);
+                    }
                     }
                     px = csimpl::respawn_x(mx, mr, a.bx, c);   // (respawnx.h: the reference's float64 sum, rounded once)
                     py = (py >= 0.0f) ? fminf(py, a.by) : fmaxf(py, -a.by);
