@@ -690,6 +690,41 @@ int cs_value_net_decide_om(int kind, const int32_t* dims, int n_dims, const floa
                            const int32_t* d_override, float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_lstm  cs_value_net_decide for LSTM-RL (crowd_nav/policy/lstm_rl.py; csrc/value_net_lstm.hip): per
+ *   (world, action) the n rows of d_rotated [W][A][n][cols], [mlp1 on every row,] torch.nn.LSTM(batch_first) over the rows from zero
+ *   (h0, c0) -- gates = W_ih x_t + b_ih + W_hh h + b_hh in torch's order i, f, g, o; c = sigmoid(f) c + sigmoid(i) tanh(g); h =
+ *   sigmoid(o) tanh(c) --, then mlp on (the first six columns of the first row in evaluation order, h_n).  sorted_by_distance = 1 is the
+ *   decision's order (multi_human_rl.py:48-50): the rows sorted by column 11 descending, ties by DECREASING human index
+ *   (np.flip(np.argsort(da, kind="stable"))); a NaN distance sorts first.  sorted_by_distance = 0 evaluates the rows as they lie (what a
+ *   trainer's stored states ask for: A = 1, a one-row action table, d_choice NULL).  Every other argument, the results (d_values =
+ *   reward + gamma^(dt * v_pref) * V, d_choice, d_override, d_action_out, reach-destination), the two kernels on `stream` and the
+ *   position independence (a (world, action) gives the same bits for W = 1 as inside any batch) are cs_value_net_decide's.  float32.
+ *   `dims` (host): [H, L1, mlp1 widths.., L2, mlp widths..] -- H the LSTM's hidden width 1..256; L1 = 0: no interaction module
+ *   (ValueNetwork1), else mlp1 (ValueNetwork2; the LSTM reads its last width); mlp ends in 1.  ReLU follows every layer but a chain's
+ *   last.  Widths 1..256, at most 16 Linear layers.  n is at most CS_VN_LSTM_MAX_N humans a world.
+ * cs_value_net_pack_lstm  (host only) params in the order of `dims`: mlp1's (weight, bias) pairs; then weight_ih [4H][in], weight_hh
+ *   [4H][H], bias_ih [4H], bias_hh [4H] as torch holds them; then mlp's pairs.  blob == NULL: only *n_floats is set.  Layout, one piece
+ *   after the other, weights and biases beyond a width zero:
+ *     every mlp1 layer  as cs_value_net_pack lays a float32 layer out (cs_value_net_pack_bf16's comment states it): float
+ *                       [ncb][kg][64 lanes][4], then float bias[32 ncb];
+ *     the gates         float [nb][kg][64 lanes][4] with nb = ceil(H / 8) blocks of 8 hidden units and kg = ceil(H / 8) + ceil(in / 8)
+ *                       k-groups (h's, then the input's): lane l, element s of k-group g of block b holds W[row][k] with row = (j >> 3) * H +
+ *                       8 b + (j & 7) for j = l & 31 (gate j >> 3 of unit 8 b + (j & 7)), W = weight_hh and k = 8 g + 4 (l >> 5) + s for
+ *                       g < ceil(H / 8), else W = weight_ih and k = 8 (g - ceil(H / 8)) + 4 (l >> 5) + s; then float bias[32 nb],
+ *                       bias[32 b + j] = bias_ih[row] + bias_hh[row] summed in float32;
+ *     every mlp layer   as the mlp1 layers; the first reads K = 6 + H columns.
+ *   Errors of both (CS_ERR_ARG, before any device call): cols not 13 or 15, H or a width outside 1..256, a malformed `dims`, more than
+ *   16 layers, an mlp that does not end in 1, null pointers; of the decision also cs_value_net_decide's (W, A, n < 1, a blob of another
+ *   size, robot_stride < 8), sorted_by_distance outside 0..1, n > CS_VN_LSTM_MAX_N, a network whose tile buffers do not fit the LDS.
+ */
+#define CS_VN_LSTM_MAX_N 128
+int cs_value_net_pack_lstm(const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats);
+int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n, int cols,
+                             int sorted_by_distance, const float* d_rotated, const float* d_rewards, const float* d_actions,
+                             const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values,
+                             int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * Float64 worlds (csrc/sfmstep_f64.hip): the SFM / HSFM substep in the reference's own precision (PRECISION = np.float64),
  * an opt-in arithmetic beside the float32 entries above.  cs_worlds_f64 carries the fields of cs_worlds that apply, with double buffers:
  * the state is CS_LAYOUT_AOS [W][rows][13] only, a world holds up to 64 rows (one wavefront per world), the types are 0..8, the robot is

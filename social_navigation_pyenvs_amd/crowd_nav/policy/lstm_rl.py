@@ -1,0 +1,111 @@
+"""LSTM-RL (Everett et al. 2018; reference: crowd_nav/policy/lstm_rl.py): the humans' rotated joint states, sorted by decreasing distance to
+the robot's next position, go through an LSTM whose last hidden state, next to the robot's own state, feeds the value MLP.  ValueNetwork1
+reads the rows themselves, ValueNetwork2 puts a pairwise interaction module (mlp1) in front of the LSTM.  Fixed from outside: the module,
+class and attribute names, the [lstm_rl] configuration keys and the checkpoint's keys and shapes (lstm.weight_ih_l0, lstm.weight_hh_l0,
+lstm.bias_ih_l0, lstm.bias_hh_l0, mlp.<2 i>.*, mlp1.<2 i>.*), so a reference checkpoint loads with strict=True.
+
+The decision is cs_lookahead -> cs_value_net_decide_lstm (csrc/value_net_lstm.hip): the sort by column 11, the interaction module, the n
+dependent LSTM steps and the value MLP of all (world, action) pairs in one kernel, float32 on the look-ahead tensor; ``predict`` is its
+W = 1 launch.  The reference sorts inside ``predict`` only: ``transform`` keeps the humans' own order, and its trainer evaluates the target
+network on those rows as stored, so ``state_value`` and ``value_device`` evaluate the rows in the order given.  It is a key of its own in
+policy_factory, "lstm_rl_device": ``policy_factory["lstm_rl"]`` keeps raising."""
+from __future__ import annotations
+
+import logging
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ... import _lib
+from .cadrl import ROBOT_FIELDS, joint_rows, mlp, width_list
+from .multi_human_rl import MultiHumanRL
+
+
+class ValueNetwork1(nn.Module):
+    def __init__(self, input_dim, self_state_dim, mlp_dims, lstm_hidden_dim):
+        super().__init__()
+        self.self_state_dim = int(self_state_dim)
+        self.lstm_hidden_dim = int(lstm_hidden_dim)
+        # submodules in the order of a reference checkpoint's keys
+        self.mlp = mlp(self.self_state_dim + self.lstm_hidden_dim, mlp_dims)
+        self.lstm = nn.LSTM(int(input_dim), self.lstm_hidden_dim, batch_first=True)
+
+    def forward(self, state):
+        """state [batch, humans, joint state], the humans in the order to scan -> value [batch, 1]"""
+        _, (h_n, _) = self.lstm(state)                      # from zero (h0, c0)
+        return self.mlp(torch.cat([state[:, 0, :self.self_state_dim], h_n.squeeze(0)], dim=1))
+
+
+class ValueNetwork2(nn.Module):
+    def __init__(self, input_dim, self_state_dim, mlp1_dims, mlp_dims, lstm_hidden_dim):
+        super().__init__()
+        self.self_state_dim = int(self_state_dim)
+        self.lstm_hidden_dim = int(lstm_hidden_dim)
+        self.mlp1 = mlp(input_dim, mlp1_dims)               # the pairwise interaction module (no ReLU behind its last layer)
+        self.mlp = mlp(self.self_state_dim + self.lstm_hidden_dim, mlp_dims)
+        self.lstm = nn.LSTM(int(mlp1_dims[-1]), self.lstm_hidden_dim, batch_first=True)
+
+    def forward(self, state):
+        batch, humans, _ = state.shape
+        embedding = self.mlp1(state.flatten(0, 1)).view(batch, humans, -1)
+        _, (h_n, _) = self.lstm(embedding)
+        return self.mlp(torch.cat([state[:, 0, :self.self_state_dim], h_n.squeeze(0)], dim=1))
+
+
+class LstmRL(MultiHumanRL):
+    display_name = "LSTM-RL"
+    config_section = "lstm_rl"
+
+    def __init__(self):
+        super().__init__()
+        self.with_interaction_module = None
+        self.interaction_module_dims = None
+
+    def configure(self, config):
+        self.set_common_parameters(config)
+        section = self.config_section
+        self.with_om = config.getboolean(section, "with_om")
+        if self.with_om:
+            raise NotImplementedError("OM-LSTM-RL (lstm_rl.with_om = true) is not available: the recurrent decision kernel reads the 13 | 15 rotated "
+                                      "columns only; rows widened by occupancy maps have no LSTM kernel")
+        mlp_dims = width_list(config.get(section, "mlp2_dims"))
+        hidden = config.getint(section, "global_state_dim")
+        self.with_interaction_module = config.getboolean(section, "with_interaction_module")
+        if self.with_interaction_module:
+            self.interaction_module_dims = width_list(config.get(section, "mlp1_dims"))
+            self.model = ValueNetwork2(self.input_dim(), self.self_state_dim, self.interaction_module_dims, mlp_dims, hidden)
+        else:
+            self.model = ValueNetwork1(self.input_dim(), self.self_state_dim, mlp_dims, hidden)
+        self.multiagent_training = config.getboolean(section, "multiagent_training")
+        logging.debug("%s: %s pairwise interaction module, hidden width %d", self.name, "with" if self.with_interaction_module else "without", hidden)
+
+    # this network has the one kernel: float32 on the look-ahead tensor
+    def set_decision_precision(self, precision):
+        from .value_net import check_decision_input, check_precision
+
+        check_decision_input(self.decision_input, check_precision(precision), recurrent=True)
+        self.decision_precision = precision
+
+    def set_decision_input(self, decision_input):
+        from .value_net import check_decision_input
+
+        self.decision_input = check_decision_input(decision_input, self.decision_precision, recurrent=True)
+
+    def state_value(self, state, model=None):
+        """V(state) on ``transform``'s rows, in the humans' own order (no sort: what the reference's trainer asks of its target network):
+        the W = 1 launches behind ``BatchedSocialNavGym.value_device`` for this policy (value_net.state_values_lstm), float32; returns a
+        Python float."""
+        from . import value_net
+
+        if self.model is None:
+            raise AttributeError(f"{self.name}: configure() the policy before it evaluates a state")
+        _lib.require_gpu()
+        rows = joint_rows(state, bool(self.with_theta_and_omega_visible))
+        if rows.shape[0] < 1:
+            raise ValueError(f"{self.name}.state_value needs at least one human")
+        net = self.state_net(model)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
+        d_c, d_r = up(rows[:, len(ROBOT_FIELDS):])[None], up(rows[:1, :len(ROBOT_FIELDS)])
+        values, _ = value_net.state_values_lstm(net, d_c, d_r, None, self.gamma, 0.0, torch.cuda.current_stream().cuda_stream)
+        return float(values.item())

@@ -1,13 +1,14 @@
 """policy_factory with the reference's keys (crowd_nav/policy/policy_factory.py): the no-train policies plus the trained value-based ones."""
 from ..policy_no_train.policy_factory import policy_factory as _no_train
 from .cadrl import CADRL
+from .lstm_rl import LstmRL
 from .om_sarl import OMSARL
 from .sarl import SARL
 
 
 def lstm_rl(*args, **kwargs):
-    raise NotImplementedError("policy 'lstm_rl' is not available: LSTM-RL runs a recurrent network over the humans sorted by distance; the "
-                              "fused decision kernel covers the feed-forward CADRL and SARL networks only")
+    raise NotImplementedError("policy 'lstm_rl' is not available under this key: LSTM-RL runs a recurrent network over the humans sorted by distance, "
+                              "which has a decision kernel of its own; build it with policy_factory[\"lstm_rl_device\"]")
 
 
 policy_factory = dict(_no_train)
@@ -15,3 +16,4 @@ policy_factory["cadrl"] = CADRL
 policy_factory["sarl"] = SARL
 policy_factory["om_sarl"] = OMSARL
 policy_factory["lstm_rl"] = lstm_rl
+policy_factory["lstm_rl_device"] = LstmRL

@@ -13,6 +13,11 @@ OM-SARL (crowd_nav/policy/om_sarl.py) widens every human's row by its occupancy 
 cs_value_net_pack_om, ``occupancy_maps`` is cs_occupancy_maps, ``decide_om`` cs_value_net_decide_om (csrc/value_net_om.hip), and
 ``decide_for_worlds`` runs lookahead -> occupancy_maps(next humans) -> decide_om for such a net; float32 on the look-ahead tensor only.
 
+LSTM-RL (crowd_nav/policy/lstm_rl.py) has a kernel of its own (cs_value_net_decide_lstm, csrc/value_net_lstm.hip) and its own description:
+``describe`` answers CS_VN_LSTM -- a tag of this module, not a `kind` of the C entries --, such a ``DeviceNet`` packs through
+cs_value_net_pack_lstm, ``decide_lstm`` is the library call and ``decide_for_worlds`` runs lookahead -> decide_lstm(sorted_by_distance=1);
+``state_values_lstm`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor only.
+
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes."""
 from __future__ import annotations
@@ -22,6 +27,7 @@ import ctypes as C
 import numpy as np
 
 CS_VN_CADRL, CS_VN_SARL = 0, 1     # include/crowdstep.h
+CS_VN_LSTM = "lstm"                # this module's tag of an LSTM-RL network: the C entries of that network take no `kind`
 PRECISIONS = ("f32", "bf16")
 DECISION_INPUTS = ("tensor", "fused")
 
@@ -32,12 +38,15 @@ def check_precision(precision):
     return precision
 
 
-def check_decision_input(decision_input, precision, om_cols=0):
+def check_decision_input(decision_input, precision, om_cols=0, recurrent=False):
     """The pair (decision input, precision) a policy may hold: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel,
     no look-ahead tensor) exists for the float32 arithmetic only.  A network with occupancy-map columns (``om_cols`` > 0) has the one
-    kernel cs_value_net_decide_om: float32 on the look-ahead tensor."""
+    kernel cs_value_net_decide_om: float32 on the look-ahead tensor.  So has a ``recurrent`` one (LSTM-RL: cs_value_net_decide_lstm)."""
     if decision_input not in DECISION_INPUTS:
         raise ValueError(f"decision input {decision_input!r}: one of {', '.join(map(repr, DECISION_INPUTS))}")
+    if recurrent and (decision_input == "fused" or check_precision(precision) == "bf16"):
+        raise ValueError(f'decision input {decision_input!r} with decision precision {precision!r} for a recurrent network: LSTM-RL has the one '
+                         'kernel, float32 on the look-ahead tensor; it decides with "tensor" and "f32"')
     if om_cols and (decision_input == "fused" or check_precision(precision) == "bf16"):
         raise ValueError(f'decision input {decision_input!r} with decision precision {precision!r} for a network with occupancy-map columns: no '
                          'kernel pairs the map columns with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"')
@@ -54,7 +63,13 @@ def _linears(seq):
 
 
 def describe(model):
-    """(kind, dims int32 array, [Linear ...] in the order of dims) of a cadrl.ValueNetwork / sarl.ValueNetwork."""
+    """(kind, dims int32 array, [Linear ...] in the order of dims) of a cadrl.ValueNetwork / sarl.ValueNetwork; for an lstm_rl.ValueNetwork1 /
+    ValueNetwork2 (CS_VN_LSTM, cs_value_net_decide_lstm's dims [H, L1, mlp1 widths.., L2, mlp widths..], [mlp1's Linear .., the nn.LSTM,
+    mlp's Linear ..])."""
+    if hasattr(model, "lstm"):
+        first, last = _linears(getattr(model, "mlp1", ())), _linears(model.mlp)
+        dims = [model.lstm.hidden_size, len(first)] + [l.out_features for l in first] + [len(last)] + [l.out_features for l in last]
+        return CS_VN_LSTM, np.array(dims, np.int32), first + [model.lstm] + last
     if hasattr(model, "value_network"):
         ls = _linears(model.value_network)
         return CS_VN_CADRL, np.array([len(ls)] + [l.out_features for l in ls], np.int32), ls
@@ -66,13 +81,26 @@ def describe(model):
     return CS_VN_SARL, np.array(dims, np.int32), layers
 
 
+def layer_params(layer):
+    """The tensors a pack entry takes of one entry of ``describe``'s list: a Linear's (weight, bias), an nn.LSTM's four."""
+    if hasattr(layer, "weight_ih_l0"):
+        return layer.weight_ih_l0, layer.weight_hh_l0, layer.bias_ih_l0, layer.bias_hh_l0
+    return layer.weight, layer.bias
+
+
 def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     """The kernel's weight blob from [weight_0, bias_0, weight_1, ...] float32 arrays: float32 numpy for "f32", the bytes (uint8 numpy)
     of cs_value_net_pack_bf16's layout for "bf16"; with ``om_cols`` > 0 cs_value_net_pack_om's (float32 only: mlp1 reads cols + om_cols
-    columns).  Host only: no GPU needed."""
+    columns); for CS_VN_LSTM cs_value_net_pack_lstm's (float32 only; the LSTM's four arrays between mlp1's and mlp's).  Host only: no GPU
+    needed."""
     from ... import _lib
 
     lib = _lib.load()
+    if kind == CS_VN_LSTM:
+        check_decision_input("tensor", precision, om_cols, recurrent=True)
+        if om_cols:
+            raise ValueError("an LSTM-RL network reads the rotated columns only: no occupancy-map columns")
+        return _pack_with(lib.cs_value_net_pack_lstm, np.float32, None, dims, cols, arrays)
     if om_cols:
         check_decision_input("tensor", precision, om_cols)
         return _pack_with(lib.cs_value_net_pack_om, np.float32, kind, dims, cols, arrays, om_cols)
@@ -83,14 +111,14 @@ def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
 
 def _pack_with(entry, unit, kind, dims, cols, arrays, om_cols=None):
     """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `om_cols`: the argument
-    cs_value_net_pack_om takes behind cols."""
+    cs_value_net_pack_om takes behind cols; `kind` None: cs_value_net_pack_lstm, which takes none."""
     from ... import _lib
 
     dims = np.ascontiguousarray(dims, np.int32)
     arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
-    head = (kind, dims.ctypes.data, len(dims), cols) + (() if om_cols is None else (om_cols,))
+    head = (() if kind is None else (kind,)) + (dims.ctypes.data, len(dims), cols) + (() if om_cols is None else (om_cols,))
     _lib.check(entry(*head, None, None, C.byref(nf)))
     blob = np.zeros(nf.value, unit)
     _lib.check(entry(*head, ptrs, blob.ctypes.data, C.byref(nf)))
@@ -101,12 +129,14 @@ class DeviceNet:
     """A policy's network as the kernel reads it: description + one packed blob per precision in HBM, each rebuilt when the module's
     parameters changed (the same version-counter key for both).  ``blob`` is the float32 one.  ``om_cols`` > 0: an OM-SARL network whose
     mlp1 reads cols + om_cols columns (cs_value_net_pack_om's blob); ``om_grid`` = (cell_num, cell_size, om_channel_size) of its maps;
-    ``last_maps``: the maps [W, n, om_cols] of its last ``decide_for_worlds``."""
+    ``last_maps``: the maps [W, n, om_cols] of its last ``decide_for_worlds``.  ``lstm``: an LSTM-RL network (cs_value_net_pack_lstm's blob,
+    float32 only; the version key covers the LSTM's four tensors)."""
 
     def __init__(self, model, cols, om_cols=0, om_grid=None):
         self.model, self.cols, self.om_cols, self.om_grid = model, int(cols), int(om_cols), om_grid
         self.last_maps = None
         self.kind, self.dims, self.layers = describe(model)
+        self.lstm = self.kind == CS_VN_LSTM
         self._keys = dict.fromkeys(PRECISIONS)
         self.blobs = dict.fromkeys(PRECISIONS)
 
@@ -115,24 +145,25 @@ class DeviceNet:
         return self.blobs["f32"]
 
     def _versions(self):
-        return tuple((p.data_ptr(), p._version) for l in self.layers for p in (l.weight, l.bias))
+        return tuple((p.data_ptr(), p._version) for l in self.layers for p in layer_params(l))
 
     def refresh(self, precision="f32"):
         import torch
 
         key = self._versions()
         if key != self._keys[check_precision(precision)]:
-            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in (l.weight, l.bias)]
+            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
             self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision, self.om_cols)).to("cuda")
             self._keys[precision] = key
         return self.blobs[precision]
 
     def head(self, caller, precision="f32"):
-        """The five arguments every network entry opens with, for the blob of `precision`; ValueError in `caller`'s name without one."""
+        """The five arguments every network entry opens with (four for an LSTM-RL network, whose entries take no kind), for the blob of
+        `precision`; ValueError in `caller`'s name without one."""
         blob = self.blobs[check_precision(precision)]
         if blob is None:
             raise ValueError(f"{caller}: the network has no {precision} blob yet (DeviceNet.refresh({precision!r}))")
-        return _head(self.kind, self.dims, blob)
+        return _head(self.kind, self.dims, blob)[1 if self.lstm else 0:]
 
 
 def _head(kind, dims, blob):
@@ -183,6 +214,37 @@ def decide_om(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride
         raise ValueError("decide_om: the network has no occupancy-map columns (DeviceNet(model, cols, om_cols))")
     _lib.check(_lib.load().cs_value_net_decide_om(*head, W, A, n, net.cols, net.om_cols, rotated, maps, rewards, actions, robot, robot_stride,
                                                   gamma, dt, override, values, choice, action_out, stream))
+
+
+def decide_lstm(net, W, A, n, sorted_by_distance, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out,
+                stream=None):
+    """cs_value_net_decide_lstm on device pointers (ints): ``decide`` for a DeviceNet of an LSTM-RL network; ``sorted_by_distance`` 1: every
+    (world, action)'s rows by decreasing column 11 (the decision's order), 0: as they lie."""
+    from ... import _lib
+
+    if not net.lstm:
+        raise ValueError("decide_lstm: the network is not an LSTM-RL one (lstm_rl.ValueNetwork1 / ValueNetwork2)")
+    head = net.head("decide_lstm")
+    _lib.check(_lib.load().cs_value_net_decide_lstm(*head, W, A, n, net.cols, int(bool(sorted_by_distance)), rotated, rewards, actions, robot,
+                                                    robot_stride, gamma, dt, override, values, choice, action_out, stream))
+
+
+def state_values_lstm(net, cur, robot, rewards, gamma, dt, stream=None):
+    """``state_values`` for a DeviceNet of an LSTM-RL network, two launches where a feed-forward network has one: the rotated rows of the
+    current state (``rotated_rows``) and cs_value_net_decide_lstm on them as they lie (sorted_by_distance = 0) with A = 1 -- a one-row
+    action table, no choice, a scratch action row.  CUDA tensors cur [W, n, 5 | 7], robot [W, 8+], rewards [W] or None (0).  Returns
+    (values [W], rows [W, n, cols]: what ``transform`` gives per world)."""
+    import torch
+
+    W, n, _ = cur.shape
+    rows = rotated_rows(cur, robot, stream)
+    values = torch.empty(W, dtype=torch.float32, device="cuda")
+    zeros = torch.zeros(max(W, 2), dtype=torch.float32, device="cuda")     # the null rewards; its first two floats the one-row action table
+    scratch = torch.empty((W, 2), dtype=torch.float32, device="cuda")
+    rew = rewards if rewards is not None else zeros
+    decide_lstm(net, W, 1, n, 0, rows.data_ptr(), rew.data_ptr(), zeros.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, None,
+                values.data_ptr(), None, scratch.data_ptr(), stream)
+    return values, rows
 
 
 _ROWS_BLOB = {}
@@ -273,11 +335,17 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
-    decide with `precision`; a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
+    decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order; a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
     branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
     "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
+    if net.lstm:
+        check_decision_input(decision_input, precision, recurrent=True)
+        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
+        decide_lstm(net, W, A, n, 1, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
+                    values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return rot, rew
     if net.om_cols:
         check_decision_input(decision_input, precision, net.om_cols)
         rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)

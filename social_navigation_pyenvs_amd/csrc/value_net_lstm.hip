@@ -1,0 +1,452 @@
+// value_net_lstm.hip -- LSTM-RL's decision (crowd_nav/policy/lstm_rl.py with multi_human_rl.py:46-63): for every (world, action) the n
+// rotated rows sorted by decreasing distance to the robot's next position (column 11), [mlp1 on every row,] an LSTM over the rows from
+// zero (h, c), mlp on (the first six columns of the first row, h_n), then compute_action_value and the per-world pick of the other
+// decision kernels (value_net_pick.h).  Not a variant of value_net_body.inc: the order of a group's rows depends on the action, and the
+// network is n dependent steps.
+//
+// Shape of the work.  A workgroup (4 wavefronts) owns a tile of 32 sequences = 32 consecutive (world, action) pairs.
+//   order       the sort keys of the tile's 32 x n distances go to LDS as integers that order like the floats (NaN above everything, the
+//               zeros equal); the rank of row j is the number of rows k with key_k > key_j, or key_k == key_j and k > j -- O(n^2) compares,
+//               always a permutation; perm[s][rank] = j stays in LDS.  sorted_by_distance = 0: the identity.
+//   step t      the 32 rows perm[s][t] are gathered from d_rotated (the gather of step t + 1 is issued before the products of step t);
+//               network 2 runs mlp1 on them (lstm_layer: layer_fwd of value_net_plan.h for one row block).  A sequence's joint row in LDS
+//               is (h of the step before | x_t), double-buffered: the gates read one row, with no choice of source per k-group.
+//   gates       the TRANSPOSED product on v_mfma_f32_32x32x2_f32: the A operand is the gate weights, the B operand the sequences' joint
+//               rows from LDS, so the MFMA's column (lane & 31) is the sequence and its 32 rows are gate rows.  The pack orders the gate
+//               rows of block b as 8 * gate + unit (8 hidden units x the gates i, f, g, o; ceil(H / 8) blocks); with the C/D map row =
+//               (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) a lane holds i, f, g, o of four hidden units of one sequence in its own 16
+//               accumulators: the pointwise part needs no LDS round trip, c stays in registers for all n steps, and only h goes back to
+//               LDS (into the other joint-row buffer, one barrier per step) as the next step's B operand.  Wavefront w owns the blocks w, w + 4, ...
+//   weights     a network of at most 8 blocks and at most 14 k-groups of 8 (H <= 64 and, each rounded up to 8, inputs + H <= 112: the
+//               reference's defaults are H = 50 on 13 columns, 7 blocks x 9 k-groups, and on mlp1's 50, 7 x 14) keeps its wavefront's gate
+//               weights in registers across steps and tiles (k_value_net_lstm<true, .>); wider ones read them from the blob at every step
+//               (<false, .>).  Same operations in the same order.  The second template argument is network 2's mlp1 in the step loop.
+//   end         mlp on the 32 joint rows (self state, h_n) as one 32-row block, the action value, one float per sequence goes out.
+//
+// Numerics: float32.  Every gate pre-activation is one fixed fmaf chain from b_ih + b_hh (summed in float32 by the pack) over the k-groups in
+// descending order (x_t's, then h's); sigmoid(x) = rcp(1 + exp2(-x * log2 e)), tanh(x) = sign(x) * (1 - e) * rcp(1 + e) with e = exp2(-2 |x| * log2 e) on
+// v_exp_f32 and v_rcp_f32 (1 ulp each): an absolute error below 3e-7 each, no overflow (e <= 1; exp2 -> inf gives sigmoid 0), NaN stays.
+// Hidden units beyond H are stored as 0 whatever the inputs.  A sequence's result depends on its own rows alone: the same bits for W = 1 as
+// inside any batch, at any position of a tile.  No atomics.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include "value_net_plan.h"
+
+namespace {
+
+constexpr int LSTM_MAX_N = CS_VN_LSTM_MAX_N;
+constexpr int RB = 2, RKG = 14;    // register-resident gate weights: blocks a wavefront, k-groups a block
+constexpr int GB = 8;              // blocks a wavefront at the widest H (256 / 8 / 4)
+
+struct LstmPlan {
+    VnPlan v;                      // the Linear layers: mlp1 = [c0[0], c0[1]) (empty for network 1), mlp = [c0[1], c0[2]); cols, total_floats
+    VnLayer g;                     // the gates as a layer: K1 = H (h comes first in a joint row), K2 = the LSTM's input width, ncb = blocks of 8 units
+    int H, xin, hpad, ld_xh;       // xin: the LSTM's input width (cols, or mlp1's last width); hpad: H rounded up to 8; the joint rows' stride
+};
+
+struct LstmLds { int key, perm, X, XH, P, Q, J, LT, total; };
+
+inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& q)
+{
+    memset(&q, 0, sizeof q);
+    VnPlan& p = q.v;
+    if (cols != 13 && cols != 15) return fail(CS_ERR_ARG, "rotated rows have 13 or 15 columns");
+    if (!dims || n_dims < 4) return fail(CS_ERR_ARG, "null or empty layer description");
+    p.cols = cols;
+    q.H = dims[0];
+    if (q.H < 1 || q.H > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "the LSTM's hidden width must be between 1 and 256");
+    q.hpad = up(q.H, 8);
+    int at = 1, off = 0, k1 = cols;
+    for (int c = 0; c < 2; ++c) {
+        if (at >= n_dims) return fail(CS_ERR_ARG, "layer description ends early");
+        const int nl = dims[at++];
+        if (nl < (c == 0 ? 0 : 1) || at + nl > n_dims) return fail(CS_ERR_ARG, "mlp1 has zero or more layers, mlp at least one, each with its widths");
+        if (p.n_layers + nl > VN_MAX_LAYERS) return fail(CS_ERR_ARG, "at most 16 layers in all");
+        p.c0[c] = p.n_layers;
+        if (c == 1) {               // the gates lie between the two chains in the blob
+            q.xin = k1;
+            VnLayer& g = q.g;
+            g.K1 = q.H; g.K2 = k1; g.N = 4 * q.H;
+            g.kg_split = q.hpad / 8;
+            g.kg_total = g.kg_split + up(k1, 8) / 8;
+            g.ncb = q.hpad / 8;
+            g.w_off = off;
+            off += g.ncb * g.kg_total * 64 * 4;
+            g.b_off = off;
+            off += g.ncb * 32;
+            k1 = SELF_DIM + q.H;
+        }
+        for (int i = 0; i < nl; ++i) {
+            const int wdt = dims[at++];
+            if (wdt < 1 || wdt > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "layer widths must be between 1 and 256");
+            VnLayer& l = p.L[p.n_layers++];
+            l.K1 = k1; l.K2 = 0; l.N = wdt;
+            l.kg_split = l.kg_total = up(k1, 8) / 8;
+            l.ncb = up(wdt, 32) / 32;
+            l.relu = i != nl - 1;                                                  // lstm_rl.py: mlp() without last_relu for both chains
+            l.w_off = off;
+            off += l.ncb * l.kg_total * 64 * 4;
+            l.b_off = off;
+            off += l.ncb * 32;
+            k1 = wdt;
+        }
+        if (c == 1 && k1 != 1) return fail(CS_ERR_ARG, "mlp ends in one output");
+    }
+    p.c0[2] = p.n_layers;
+    if (at != n_dims) return fail(CS_ERR_ARG, "layer description has trailing entries");
+    int widest = 32;
+    for (int i = 0; i < p.n_layers; ++i) widest = p.L[i].ncb * 32 > widest ? p.L[i].ncb * 32 : widest;
+    p.ld_pq = widest + 4;
+    q.ld_xh = q.hpad + (p.c0[1] > 0 ? up(q.xin, 32) : 16) + 4;        // (mlp1's last layer stores whole 32-column blocks)
+    p.ld_j = up(SELF_DIM + q.H, 8) + 4;
+    p.total_floats = off;
+    return CS_OK;
+}
+
+inline LstmLds lstm_lds_map(const LstmPlan& q, int n)
+{
+    LstmLds m{};
+    int o = 0;
+    auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
+    m.key = take(TILE_M * n);
+    m.perm = take(TILE_M * n);
+    m.XH = take(2 * TILE_M * q.ld_xh);
+    m.X = q.v.c0[1] > 0 ? take(2 * TILE_M * LDX) : m.XH;
+    m.P = take(TILE_M * q.v.ld_pq);
+    m.Q = take(TILE_M * q.v.ld_pq);
+    m.J = take(JROWS * q.v.ld_j);
+    m.LT = take(VN_MAX_LAYERS * 8);
+    m.total = o;
+    return m;
+}
+
+// the gate rows where the lanes of the transposed product read them: row 8 * gate + u of block b is torch's row gate * H + 8 b + u of
+// weight_hh (k-groups below kg_split: h comes first in a joint row) and weight_ih (behind them); bias = b_ih + b_hh in float32; blob zeroed before
+inline void pack_gates(const LstmPlan& q, const float* wih, const float* whh, const float* bih, const float* bhh, float* blob)
+{
+    const VnLayer& g = q.g;
+    for (int cb = 0; cb < g.ncb; ++cb) {
+        for (int j = 0; j < 32; ++j) {
+            const int unit = cb * 8 + (j & 7), row = (j >> 3) * q.H + unit;
+            if (unit >= q.H) continue;
+            blob[g.b_off + cb * 32 + j] = bih[row] + bhh[row];
+            for (int kg = 0; kg < g.kg_total; ++kg)
+                for (int hh = 0; hh < 2; ++hh)
+                    for (int s = 0; s < 4; ++s) {
+                        const int kk = kg * 8 + 4 * hh + s;
+                        float w = 0.0f;
+                        if (kg < g.kg_split) { if (kk < g.K1) w = whh[(size_t)row * g.K1 + kk]; }
+                        else if (kk - g.kg_split * 8 < g.K2) w = wih[(size_t)row * g.K2 + kk - g.kg_split * 8];
+                        blob[g.w_off + ((cb * g.kg_total + kg) * 64 + hh * 32 + j) * 4 + s] = w;
+                    }
+        }
+    }
+}
+
+__device__ __forceinline__ float lstm_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
+
+__device__ __forceinline__ float lstm_tanh(float x)
+{
+    const float e = __builtin_amdgcn_exp2f(-2.88539008f * fabsf(x));
+    const float t = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
+    return x != x ? x : copysignf(t, x);
+}
+
+// an integer that orders like the distance: NaN above everything (numpy's argsort leaves it last, the flip first), -0 = +0
+__device__ __forceinline__ unsigned lstm_key(float x)
+{
+    if (x != x) return 0xFFFFFFFFu;
+    unsigned u = __float_as_uint(x);
+    if (x == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// rows perm[s][t] of the tile's sequences into rows of stride ld: 16 columns a row, zeros beyond the columns and the sequences
+__device__ __forceinline__ void lstm_gather(float* X, int ld, const float* __restrict__ rotated, const int* perm, long gbase, int ng, int n, int cols, int t)
+{
+    for (int i = threadIdx.x; i < TILE_M * 16; i += NT) {
+        const int s = i >> 4, c = i & 15;
+        float v = 0.0f;
+        if (s < ng && c < cols) v = rotated[((gbase + s) * n + perm[s * n + t]) * cols + c];
+        X[s * ld + c] = v;
+    }
+}
+
+// One float32 layer of the tile's 32 rows, dst[32][ncb * 32] = act(src[32][K] x Wt + b): value_net_plan.h's layer_fwd for one row block and
+// one source -- the same blob layout, the same k order, zeros beyond N -- with a one-deep weight prefetch.
+// The layer's fields come from the table the kernel keeps in LDS (LT_*), one register each.  Fetched from the kernel's arguments (p.L[l], as
+// layer_fwd does) beside the gates, the build reported a private segment of 20 - 36 bytes that no instruction used: a dead 16-byte spill slot
+// of the scalar allocator and its scavenging slot.  With the table it reports 0.
+enum { LT_N, LT_KG, LT_NCB, LT_RELU, LT_W, LT_B, LT_STRIDE = 8 };
+
+__device__ __forceinline__ void lstm_layer(const int* lt, const float* __restrict__ wb, const float* src, int lds_, float* dst, int ldd)
+{
+    const auto field = [&](int k) { return __builtin_amdgcn_readfirstlane(lt[k]); };
+    const struct { int N, kg_total, ncb, relu, w_off, b_off; } L{field(LT_N), field(LT_KG), field(LT_NCB), field(LT_RELU), field(LT_W), field(LT_B)};
+    const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31, KG = L.kg_total;
+    const float* a1 = src + li * lds_ + 4 * h;
+    for (int cb = threadIdx.x >> 6; cb < L.ncb; cb += 4) {
+        const float4* bw = reinterpret_cast<const float4*>(wb + L.w_off) + cb * KG * 64 + lane;
+        const float bias = wb[L.b_off + cb * 32 + li];
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias;
+        float4 nw = bw[0];
+        for (int kg = 0; kg < KG; ++kg) {
+            const float4 w = nw;
+            nw = bw[(kg + 1 < KG ? kg + 1 : kg) * 64];
+            const float4 a = *reinterpret_cast<const float4*>(a1 + kg * 8);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
+        }
+        float* d = dst + 4 * h * ldd + cb * 32 + li;
+        const bool pad = cb * 32 + li >= L.N;              // (the zero weights give 0 * inf = NaN there when an input is infinite)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = acc[r];
+            if (L.relu) v = v < 0.0f ? 0.0f : v;          // (a NaN stays a NaN, as torch's ReLU leaves it)
+            d[((r & 3) + 8 * (r >> 2)) * ldd] = pad ? 0.0f : v;
+        }
+    }
+}
+
+// layers [first, last) from `src`, a barrier behind each; outputs alternate P, Q, the last one goes to final_dst when given.  Returns where
+// the result is, out_ld its row stride.
+__device__ __forceinline__ const float* lstm_chain(const int* ltab, int ld_pq, const float* __restrict__ wb, float* P, float* Q, int first, int last, const float* src,
+                                                   int lds_, float* final_dst, int final_ld, int& out_ld)
+{
+    const float* cur = src;
+    int cur_ld = lds_;
+    for (int l = first; l < last; ++l) {
+        const bool fin = l == last - 1 && final_dst;
+        float* dst = fin ? final_dst : (((l - first) & 1) ? Q : P);
+        const int ldd = fin ? final_ld : ld_pq;
+        lstm_layer(ltab + l * LT_STRIDE, wb, cur, cur_ld, dst, ldd);
+        __syncthreads();
+        cur = dst;
+        cur_ld = ldd;
+    }
+    out_ld = cur_ld;
+    return cur;
+}
+
+#define LSTM_KSTEP(WV, KGI)                                                                                                  \
+    {                                                                                                                        \
+        const float4 xv = *reinterpret_cast<const float4*>(brow + (KGI) * 8);                                                \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.x, xv.x, acc, 0, 0, 0);                                                \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.y, xv.y, acc, 0, 0, 0);                                                \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.z, xv.z, acc, 0, 0, 0);                                                \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.w, xv.w, acc, 0, 0, 0);                                                \
+    }
+
+template <bool WREG, bool MLP1>
+__global__ __launch_bounds__(NT) void k_value_net_lstm(LstmPlan q, LstmLds m, const float* __restrict__ wb, int NG, int A, int n, int sorted,
+                                                       const float* __restrict__ rotated, const float* __restrict__ rewards,
+                                                       const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
+{
+    extern __shared__ float lds[];
+    constexpr int NB = WREG ? RB : GB;
+    const VnPlan& p = q.v;
+    float *P = lds + m.P, *Q = lds + m.Q, *J = lds + m.J;
+    unsigned* key = reinterpret_cast<unsigned*>(lds + m.key);
+    int* perm = reinterpret_cast<int*>(lds + m.perm);
+    float* XH = lds + m.XH;                                 // [2][32][ld_xh]: a sequence's joint row (h of the step before | x_t)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5, li = lane & 31;
+    const int row8 = tid >> 3;
+    const int cols = p.cols, H = q.H, hpad = q.hpad, ldxh = q.ld_xh, KG = q.g.kg_total;
+    const int nbw = (q.g.ncb - wave + 3) >> 2;              // this wavefront's blocks: wave, wave + 4, ...
+    constexpr bool with_mlp1 = MLP1;
+    // where the gather puts a step's rows: network 1 straight into the joint rows' x part, network 2 into a tile of their own for mlp1
+    float* G = with_mlp1 ? lds + m.X : XH + hpad;
+    const int ldg = with_mlp1 ? LDX : ldxh, gbuf = TILE_M * ldg;
+    const float4* gw = reinterpret_cast<const float4*>(wb + q.g.w_off) + lane;
+    int out_ld;
+
+    int* ltab = reinterpret_cast<int*>(lds + m.LT);
+    if (tid == 0)
+        for (int l = 0; l < p.n_layers; ++l) {
+            int* e = ltab + l * LT_STRIDE;
+            e[LT_N] = p.L[l].N; e[LT_KG] = p.L[l].kg_total; e[LT_NCB] = p.L[l].ncb; e[LT_RELU] = p.L[l].relu; e[LT_W] = p.L[l].w_off; e[LT_B] = p.L[l].b_off;
+        }
+    // (the first barrier of the first job publishes the table)
+
+    float4 wreg[RB][RKG];
+    if constexpr (WREG) {
+#pragma unroll
+        for (int bi = 0; bi < RB; ++bi)
+#pragma unroll
+            for (int kg = 0; kg < RKG; ++kg) {
+                const int at = ((tid >> 6) + 4 * bi) * KG + kg;    // (clamped: what lies beyond the wavefront's blocks and k-groups is never used)
+                wreg[bi][kg] = gw[(at < q.g.ncb * KG ? at : 0) * 64];
+            }
+    }
+
+    for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
+        const long gbase = (long)job * JROWS;
+        const int ng = NG - gbase < JROWS ? (int)(NG - gbase) : JROWS;
+        for (int i = tid; i < ng * n; i += NT) key[i] = lstm_key(rotated[(gbase * n + i) * cols + 11]);
+        for (int i = tid; i < JROWS * p.ld_j; i += NT) J[i] = 0.0f;
+        for (int i = tid; i < TILE_M * ldxh; i += NT) XH[i] = 0.0f;                                  // h0 = 0
+        __syncthreads();
+        for (int j = tid & 7; j < n && row8 < ng; j += 8) {          // eight lanes a sequence
+            int rank = j;
+            if (sorted) {
+                const unsigned kj = key[row8 * n + j];
+                rank = 0;
+#pragma unroll 1
+                for (int k = 0; k < n; ++k) {
+                    const unsigned kk = key[row8 * n + k];
+                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
+                }
+            }
+            perm[row8 * n + rank] = j;
+        }
+        __syncthreads();
+        lstm_gather(G, ldg, rotated, perm, gbase, ng, n, cols, 0);
+        float c[NB][4];
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) c[bi][u] = 0.0f;
+        __syncthreads();
+        // lstm_rl.py:25 / :53: the self state is read from the first row in evaluation order
+        if (row8 < ng && (tid & 7) < SELF_DIM) J[row8 * p.ld_j + (tid & 7)] = G[row8 * ldg + (tid & 7)];
+
+        for (int t = 0; t < n; ++t) {
+            float* cur = XH + (t & 1) * TILE_M * ldxh;
+            float* nxt = XH + ((t + 1) & 1) * TILE_M * ldxh;
+            if (t + 1 < n) lstm_gather(G + ((t + 1) & 1) * (with_mlp1 ? gbuf : TILE_M * ldxh), ldg, rotated, perm, gbase, ng, n, cols, t + 1);
+            if constexpr (with_mlp1) lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, LDX, cur + hpad, ldxh, out_ld);
+            const float* brow = cur + li * ldxh + 4 * hh;
+#pragma unroll
+            for (int bi = 0; bi < NB; ++bi) {
+                if (bi >= nbw) break;
+                const int blk = wave + 4 * bi;
+                f32x16 acc;
+                const float* bias = wb + q.g.b_off + blk * 32 + 4 * hh;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = bias[(r & 3) + 8 * (r >> 2)];
+                // the k-groups in descending order (x_t's, then h's), whichever kernel
+                if constexpr (WREG) {
+                    switch (KG) {
+                    case 14: LSTM_KSTEP(wreg[bi][13], 13) [[fallthrough]];
+                    case 13: LSTM_KSTEP(wreg[bi][12], 12) [[fallthrough]];
+                    case 12: LSTM_KSTEP(wreg[bi][11], 11) [[fallthrough]];
+                    case 11: LSTM_KSTEP(wreg[bi][10], 10) [[fallthrough]];
+                    case 10: LSTM_KSTEP(wreg[bi][9], 9) [[fallthrough]];
+                    case 9: LSTM_KSTEP(wreg[bi][8], 8) [[fallthrough]];
+                    case 8: LSTM_KSTEP(wreg[bi][7], 7) [[fallthrough]];
+                    case 7: LSTM_KSTEP(wreg[bi][6], 6) [[fallthrough]];
+                    case 6: LSTM_KSTEP(wreg[bi][5], 5) [[fallthrough]];
+                    case 5: LSTM_KSTEP(wreg[bi][4], 4) [[fallthrough]];
+                    case 4: LSTM_KSTEP(wreg[bi][3], 3) [[fallthrough]];
+                    case 3: LSTM_KSTEP(wreg[bi][2], 2) [[fallthrough]];
+                    default: LSTM_KSTEP(wreg[bi][1], 1) LSTM_KSTEP(wreg[bi][0], 0)
+                    }
+                } else {
+                    const float4* w = gw + (long)blk * KG * 64;
+                    float4 nw = w[(long)(KG - 1) * 64];
+                    for (int kg = KG - 1; kg >= 0; --kg) {
+                        const float4 wv = nw;
+                        nw = w[(long)(kg > 0 ? kg - 1 : 0) * 64];
+                        LSTM_KSTEP(wv, kg)
+                    }
+                }
+                float hv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float ig = lstm_sigmoid(acc[u]), fg = lstm_sigmoid(acc[4 + u]), gg = lstm_tanh(acc[8 + u]), og = lstm_sigmoid(acc[12 + u]);
+                    const float cn = fg * c[bi][u] + ig * gg;
+                    c[bi][u] = cn;
+                    hv[u] = blk * 8 + 4 * hh + u < H ? og * lstm_tanh(cn) : 0.0f;      // (zero weights give 0 for finite inputs only)
+                }
+                *reinterpret_cast<float4*>(nxt + li * ldxh + blk * 8 + 4 * hh) = make_float4(hv[0], hv[1], hv[2], hv[3]);
+            }
+            __syncthreads();
+        }
+
+        const float* hn = XH + (n & 1) * TILE_M * ldxh;
+        for (int u = tid & 7; u < H; u += 8) J[row8 * p.ld_j + SELF_DIM + u] = hn[row8 * ldxh + u];
+        __syncthreads();
+        const float* out = lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
+        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
+            const long g = gbase + tid;
+            const float vpref = robot[(g / A) * rstride + 7];
+            values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
+        }
+        __syncthreads();
+    }
+}
+#undef LSTM_KSTEP
+
+template <auto Kernel>
+inline int grant_lds(size_t shmem)
+{
+    if (shmem <= 64 * 1024) return CS_OK;
+    static std::atomic<int> granted[64];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const bool slot = dev >= 0 && dev < 64;
+    if (!slot || granted[dev].load(std::memory_order_acquire) < (int)shmem) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        if (slot) granted[dev].store((int)shmem, std::memory_order_release);
+    }
+    return CS_OK;
+}
+
+} // namespace
+
+#include "value_net_pick.h"
+
+extern "C" int cs_value_net_pack_lstm(const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    if (rc != CS_OK) return rc;
+    if (!n_floats) return fail(CS_ERR_ARG, "null argument");
+    *n_floats = (size_t)q.v.total_floats;
+    if (!blob) return CS_OK;
+    if (!params) return fail(CS_ERR_ARG, "null argument");
+    const int n1 = q.v.c0[1], n_params = 2 * q.v.n_layers + 4;
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i]) return fail(CS_ERR_ARG, "null weight or bias array");
+    memset(blob, 0, (size_t)q.v.total_floats * sizeof(float));
+    for (int l = 0; l < n1; ++l) pack_layer_f32(q.v.L[l], params[2 * l], params[2 * l + 1], blob);
+    pack_gates(q, params[2 * n1], params[2 * n1 + 1], params[2 * n1 + 2], params[2 * n1 + 3], blob);
+    for (int l = n1; l < q.v.n_layers; ++l) pack_layer_f32(q.v.L[l], params[2 * l + 4], params[2 * l + 5], blob);
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n, int cols,
+                                        int sorted_by_distance, const float* d_rotated, const float* d_rewards, const float* d_actions,
+                                        const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values,
+                                        int32_t* d_choice, float* d_action_out, void* stream)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    if (rc != CS_OK) return rc;
+    const int rc2 = check_decide_args(q.v, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    if (rc2 != CS_OK) return rc2;
+    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
+    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
+    const LstmLds m = lstm_lds_map(q, n);
+    const size_t shmem = (size_t)m.total * sizeof(float);
+    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    const int NG = W * A, jobs = (NG + JROWS - 1) / JROWS, grid = jobs < 4096 ? jobs : 4096;
+    const bool wreg = q.g.ncb <= 4 * RB && q.g.kg_total <= RKG, mlp1 = q.v.c0[1] > 0;
+#define LSTM_LAUNCH(WR, M1)                                                                                                          \
+    {                                                                                                                                \
+        const int rc3 = grant_lds<k_value_net_lstm<WR, M1>>(shmem);                                                                  \
+        if (rc3 != CS_OK) return rc3;                                                                                                \
+        hipLaunchKernelGGL((k_value_net_lstm<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n,  \
+                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);                    \
+    }
+    if (wreg && mlp1) LSTM_LAUNCH(true, true)
+    else if (wreg) LSTM_LAUNCH(true, false)
+    else if (mlp1) LSTM_LAUNCH(false, true)
+    else LSTM_LAUNCH(false, false)
+#undef LSTM_LAUNCH
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
+}

@@ -721,7 +721,9 @@ class BatchedSocialNavGym:
         cs_value_net_decide_worlds, which generates the look-ahead rows in the kernel and allocates no look-ahead tensor.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
         values and choices of that decision stay readable through ``last_values_device()``.  An OM-SARL instance
-        (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om."""
+        (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om, an
+        LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
+        (world, action)'s humans by decreasing distance inside the kernel."""
         import torch
 
         dl = self._device_loop_state()
@@ -849,7 +851,9 @@ class BatchedSocialNavGym:
         alone: ``torch.where(done, rewards, target)``.  Without ``bootstrap`` ``rewards`` must be None.  float32 arithmetic whatever the
         policy's decision precision.  One launch of cs_value_net_state on ``device_stream()``; nothing crosses to the host.  An OM-SARL
         instance gives the same quantities from THREE launches instead of one: cs_value_net_state for the rotated rows, cs_occupancy_maps
-        on the current humans, cs_value_net_decide_om with A = 1 (a one-row action table, no choice); its rows are [W, n, 13|15 + C]."""
+        on the current humans, cs_value_net_decide_om with A = 1 (a one-row action table, no choice); its rows are [W, n, 13|15 + C].  An
+        LSTM-RL instance takes TWO: cs_value_net_state for the rows, cs_value_net_decide_lstm with A = 1 on them in the humans' own order
+        (``transform`` does not sort; the reference's trainer evaluates its target network on the rows as stored)."""
         if rewards is not None and not bootstrap:
             raise ValueError("value_device: rewards= belongs to bootstrap=True (rewards + gamma^(robot_time_step * v_pref) * V)")
         values, rows = self._state_values_device("value_device", policy, model, rewards, self.robot_time_step if bootstrap else 0.0, with_state)
@@ -889,6 +893,8 @@ class BatchedSocialNavGym:
             _, cur_, rob = self._worlds_on_side_stream(dl, peek=False)
             if net.om_cols:                      # OM-SARL: rows, maps of the current humans and the network are three launches
                 values, rows = value_net.state_values_om(net, cur_, rob, rewards, pol.gamma, dt, side.cuda_stream)
+            elif net.lstm:                       # LSTM-RL: the rows, then the recurrent kernel on them in the humans' own order
+                values, rows = value_net.state_values_lstm(net, cur_, rob, rewards, pol.gamma, dt, side.cuda_stream)
             else:
                 values = torch.empty(W, dtype=torch.float32, device="cuda")
                 rows = torch.empty((W, n, pol.joint_state_dim), dtype=torch.float32, device="cuda") if with_rows else None

@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""Time LSTM-RL's decision on the GPU: 4096 worlds x 81 actions x n humans, seeded inputs, device events, no reference.
+
+  (i)   cs_value_net_decide_lstm (sort + LSTM + MLP + pick, csrc/value_net_lstm.hip)
+  (ii)  cs_value_net_decide with SARL's default network on the same tensor, for scale
+  (iii) what a user has without the kernel: the same torch module on the GPU, evaluated by PyTorch on the same rows, the per-action sort
+        done with torch ops (argsort of column 11, flip, take_along_dim), compute_action_value and the arg-max
+
+Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5] [--only lstm|sarl|torch]
+        [--out profiles/lstm_rl_decision.txt]
+With --only one variant runs alone, for a `rocprofv3 --kernel-trace --stats -- python tools/time_value_lstm.py --only lstm` run of its own.
+Times are per decision of all worlds: median, minimum and maximum over --reps repetitions, each between two device events.  The work per
+decision is counted from the shapes.  Without a GPU the script fails."""
+import argparse
+import configparser
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+POLICY = {
+    "rl": {"gamma": "0.9"},
+    "om": {"cell_num": "4", "cell_size": "1", "om_channel_size": "3"},
+    "action_space": {"kinematics": "holonomic", "speed_samples": "5", "rotation_samples": "16", "sampling": "exponential", "query_env": "true"},
+    "sarl": {"mlp1_dims": "150, 100", "mlp2_dims": "100, 50", "attention_dims": "100, 100, 1", "mlp3_dims": "150, 100, 100, 1",
+             "multiagent_training": "true", "with_om": "false", "with_global_state": "true", "with_theta_and_omega_visible": "false"},
+    "lstm_rl": {"global_state_dim": "50", "mlp1_dims": "150, 100, 100, 50", "mlp2_dims": "150, 100, 100, 1", "multiagent_training": "true",
+                "with_om": "false", "with_interaction_module": "false"},
+}
+
+
+def make_policy(name, network=1):
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy.policy_factory import policy_factory
+
+    cfg = configparser.RawConfigParser()
+    cfg.read_dict(POLICY)
+    cfg.set("lstm_rl", "with_interaction_module", "true" if network == 2 else "false")
+    pol = policy_factory[name]()
+    pol.configure(cfg)
+    g = torch.Generator().manual_seed(7)
+    with torch.no_grad():
+        for prm in pol.model.parameters():
+            prm.copy_(torch.randn(prm.shape, generator=g) * 0.1)
+    pol.set_device(torch.device("cuda"))
+    return pol
+
+
+def work_per_decision(model, W, A, n, cols):
+    """(multiply-adds, bytes read of the look-ahead tensor) of one decision of all worlds, from the shapes"""
+    lin = lambda seq: sum(m.in_features * m.out_features for m in seq if hasattr(m, "in_features"))
+    per_row = (lin(model.mlp1) if hasattr(model, "mlp1") else 0) + 4 * model.lstm.hidden_size * (model.lstm.input_size + model.lstm.hidden_size)
+    return W * A * (n * per_row + lin(model.mlp)), W * A * n * cols * 4
+
+
+def timed(fn, reps, warmup):
+    import torch
+
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--worlds", type=int, default=4096)
+    ap.add_argument("--humans", type=int, nargs="+", default=[5, 25])
+    ap.add_argument("--network", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", choices=("lstm", "sarl", "torch"))
+    ap.add_argument("--out")
+    args = ap.parse_args()
+
+    import torch
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+    from social_navigation_pyenvs_amd.crowd_nav.policy.cadrl import build_action_space_array
+
+    _lib.require_gpu()
+    W, cols, gamma, dt = args.worlds, 13, 0.9, 0.25
+    acts = torch.as_tensor(build_action_space_array(1.0).astype(np.float32), device="cuda")
+    A = acts.shape[0]
+    lstm, sarl = make_policy("lstm_rl_device", args.network), make_policy("sarl")
+    nets = {"lstm": value_net.DeviceNet(lstm.model, cols), "sarl": value_net.DeviceNet(sarl.model, cols)}
+    for net in nets.values():
+        net.refresh()
+    stream = torch.cuda.current_stream().cuda_stream
+    lines = [f"LSTM-RL decision, network {args.network}: {W} worlds x {A} actions, {args.reps} repetitions after {args.warmup} warm-up, ms per decision "
+             f"of all worlds (median, min .. max); device {torch.cuda.get_device_name(0)}"]
+    for n in args.humans:
+        g = torch.Generator(device="cuda").manual_seed(100 + n)
+        rot = torch.rand((W, A, n, cols), generator=g, device="cuda") * 4 - 2
+        rot[..., 11] = torch.rand((W, A, n), generator=g, device="cuda") * 5 + 0.3
+        rew = torch.rand((W, A), generator=g, device="cuda") - 0.25
+        rob = torch.tensor([0, 0, 0, 0, 0.3, 5, 5, 1.0, 0], device="cuda").repeat(W, 1).contiguous()
+        vals = torch.empty((W, A), device="cuda")
+        pick = torch.empty(W, dtype=torch.int32, device="cuda")
+        act = torch.empty((W, 2), device="cuda")
+        tail = (rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), rob.shape[1], gamma, dt, None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+        disc = torch.pow(torch.tensor(gamma, device="cuda"), dt * rob[:, 7])
+
+        def by_torch(chunk=512):
+            with torch.no_grad():
+                best = torch.empty(W, dtype=torch.int64, device="cuda")
+                for w0 in range(0, W, chunk):
+                    x = rot[w0:w0 + chunk].reshape(-1, n, cols)
+                    idx = torch.flip(torch.argsort(x[:, :, 11], dim=1, stable=True), dims=[1])
+                    x = torch.take_along_dim(x, idx[:, :, None], dim=1)
+                    v = lstm.model(x)[:, 0].view(-1, A)
+                    best[w0:w0 + chunk] = torch.argmax(rew[w0:w0 + chunk] + disc[w0:w0 + chunk, None] * v, dim=1)
+                return best
+
+        variants = {
+            "lstm": ("(i)   cs_value_net_decide_lstm", lambda: value_net.decide_lstm(nets["lstm"], W, A, n, 1, rot.data_ptr(), *tail)),
+            "sarl": ("(ii)  cs_value_net_decide, SARL", lambda: value_net.decide(nets["sarl"], W, A, n, rot.data_ptr(), *tail)),
+            "torch": ("(iii) torch module on the GPU", by_torch),
+        }
+        macs, nbytes = work_per_decision(lstm.model, W, A, n, cols)
+        lines.append(f"n = {n}: {macs / 1e9:.2f} G multiply-adds, {nbytes / 1e6:.0f} MB of look-ahead rows per decision")
+        results = {}
+        for key, (label, fn) in variants.items():
+            if args.only and key != args.only:
+                continue
+            try:
+                results[key] = timed(fn, args.reps, args.warmup)
+                med, lo, hi = results[key]
+                extra = f"  {2 * macs / med / 1e9:.1f} TFLOP/s, {nbytes / med / 1e6:.0f} GB/s of rows" if key == "lstm" else ""
+                lines.append(f"  {label:34s} {med:9.3f}  ({lo:.3f} .. {hi:.3f}){extra}")
+            except Exception as e:          # (MIOpen may refuse the module: said plainly, the other variants still run)
+                lines.append(f"  {label:34s} did not run: {type(e).__name__}: {str(e).splitlines()[0][:120]}")
+        if "lstm" in results and "torch" in results:
+            value_net.decide_lstm(nets["lstm"], W, A, n, 1, rot.data_ptr(), *tail)      # (the SARL run wrote the same outputs since)
+            torch.cuda.synchronize()
+            agree = float((by_torch() == pick.long()).float().mean())
+            lines.append(f"  (iii) / (i) = {results['torch'][0] / results['lstm'][0]:.1f}; the two pick the same action in {100 * agree:.2f} % of the worlds")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
