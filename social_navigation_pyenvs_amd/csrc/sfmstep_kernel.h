@@ -182,15 +182,37 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     // the tail -- forms it again.
     constexpr bool CARRY_CV = ONE_REGION && HEADED > 0;
     float cvx_c = vx, cvy_c = vy;
+    // ... and put their two rare events behind wave votes taken early.  The respawn rule tests the position the Euler step has just produced
+    // against goals[0], the goal switch of the NEXT substep tests the same position -- its incoming row -- against the same goals[0]: one
+    // squared distance, formed once where the tail forms the position (sfmstep_sub_tail.inc), and two wave votes from it: does any lane
+    // stand within r (hit_next), does any lane of a respawning world stand within 3 m (flag_any).  flag_any is one scalar branch around the
+    // respawn rule behind the rest of the tail, hit_next (handed to carried_hit there) one scalar branch around the goal switch at the
+    // next head.  The votes only gate: the per-lane tests behind them are the old expressions on the same stored row, so a vote has no
+    // false negative ((-x)^2 = x^2 makes |g - p|^2 and |p - g|^2 the same bits) and may have false positives.  Substep 0 runs the goal
+    // switch unasked (nobody voted on the incoming row), and so does the substep behind a respawn (the rule moves the row and its
+    // goals[0]); the switch stays at the head, so a launch of k substeps leaves the goal lists that k launches of one leave.  No vector
+    // value is live across the pair loop for it: the votes are scalars.  respawn_mask: the lanes of the worlds the rule applies to,
+    // balloted once (0 without CS_RESPAWN).  Headline build, common path of a substep: 286 -> 271 vector instructions (7 compares /
+    // selects and 4 moves among them), 21 -> 17 scalar ones, 3 -> 1 exec regions (HISTORY.md).
+    constexpr bool EARLY_VOTES = ONE_REGION;
+    // (The branch around the goal switch stays out of the one pair of builds that spills, the 30-row Moussaid HSFM twins at the four-wave
+    // budget: with the switch in a block of its own they spill one register more, 36 bytes of scratch instead of 32.  They keep the
+    // predicated switch on every substep and take the respawn rule's branch only.)
+    constexpr bool VOTED_SWITCH = EARLY_VOTES && !(SOC == 2 && HEADED > 0 && OCC == 4 && ROWS_CT == 30);
+    unsigned long long carried_hit = ~0ull, hit_next = ~0ull;   // (the votes as the ballots left them: non-zero = run the goal switch)
+    bool flag_any = true;
+    unsigned long long respawn_mask = 0ull, gdirty_votes = 0ull;   // (gdirty_votes: the lanes whose two-goal list rotated, gdirty's bits until the loop ends)
     if constexpr (ONE_REGION) {
         if (valid) {
             constexpr bool valid = true, human = true;   // (shadow the lane tests: this region holds the valid lanes only)
             if constexpr (CARRY_CV) { cvx_c = fmaf(cs, bvx, -(sn * bvy)); cvy_c = fmaf(cs, bvy, sn * bvx); }
+            if (a.flags & CS_RESPAWN) respawn_mask = __builtin_amdgcn_ballot_w64(respawn_here);
             for (int sub = 0; sub < a.nsub; ++sub) {
 #include "sfmstep_substep.inc"
                 cur = nxt;
             }
         }
+        if constexpr (VOTED_SWITCH) gdirty = ((gdirty_votes >> tid) & 1ull) != 0ull;
     } else {
         for (int sub = 0; sub < a.nsub; ++sub) {
 #include "sfmstep_substep.inc"

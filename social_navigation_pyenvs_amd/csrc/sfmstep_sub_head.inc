@@ -97,15 +97,20 @@
             }
         }
         if constexpr (LEAN) {
-            // -- goal switch, forces_parallel.py:226-234, predicated: lists of <= 2 goals rotate in registers
-            const float gdx = g0x - px, gdy = g0y - py;
-            const bool hit = human && fmaf(gdx, gdx, gdy * gdy) <= r * r;
-            const bool sw = hit && gk == 2;
-            const float t0 = g0x, t1 = g0y;
-            g0x = sw ? g1x : g0x; g0y = sw ? g1y : g0y;
-            g1x = sw ? t0 : g1x; g1y = sw ? t1 : g1y;
-            gdirty = gdirty || sw;
-            gx = hit ? g0x : gx; gy = hit ? g0y : gy;
+            // -- goal switch, forces_parallel.py:226-234, predicated: lists of <= 2 goals rotate in registers.  In the plain one-wavefront
+            //    builds (VOTED_SWITCH, sfmstep_kernel.h) behind one scalar branch on the vote the previous substep's tail took on this
+            //    very row: a wavefront none of whose lanes stands within r of its goal -- the common case -- skips the block.
+            if (!VOTED_SWITCH || carried_hit != 0ull) {
+                const float gdx = g0x - px, gdy = g0y - py;
+                const bool hit = human && fmaf(gdx, gdx, gdy * gdy) <= r * r;
+                const bool sw = hit && gk == 2;
+                const float t0 = g0x, t1 = g0y;
+                g0x = sw ? g1x : g0x; g0y = sw ? g1y : g0y;
+                g1x = sw ? t0 : g1x; g1y = sw ? t1 : g1y;
+                if constexpr (VOTED_SWITCH) gdirty_votes |= __builtin_amdgcn_ballot_w64(sw);   // (a scalar pair: a lane mask carried round a uniform branch costs four scalar instructions on the path around it)
+                else gdirty = gdirty || sw;
+                gx = hit ? g0x : gx; gy = hit ? g0y : gy;
+            }
         } else if (human) {
             // -- goal switch, forces_parallel.py:226-234 (on the incoming position)
             const float gdx = g0x - px, gdy = g0y - py;

@@ -122,6 +122,14 @@
             // -- explicit Euler, :273-283 (position uses the velocity stored in the incoming row)
             const float in_vx = cvx, in_vy = cvy; // what the reference leaves in agents_state[i,3:5]
             px += vx * dt; py += vy * dt;
+            if constexpr (EARLY_VOTES) {
+                // the row this tail stores against the goals[0] of behind the switch: what the respawn rule tests behind this tail and the
+                // goal switch at the next head, voted on here -- the rest of the tail away from the first branch, a back edge from the other
+                const float ndx = g0x - px, ndy = g0y - py;
+                const float nd2 = fmaf(ndx, ndx, ndy * ndy);
+                hit_next = __builtin_amdgcn_ballot_w64(nd2 <= r * r);
+                flag_any = (__builtin_amdgcn_ballot_w64(nd2 < 9.0f) & respawn_mask) != 0ull;
+            }
             if constexpr (HEADED > 0) {
                 th = th_n;
                 bvx = fmaf(gfx, dt_m, bvx); bvy = fmaf(gfy, dt_m, bvy);

@@ -11,7 +11,17 @@
 #include "sfmstep_sub_pairloop.inc"
         // all partners per lane (per-agent parameters on Moussaid, worlds of more than one wavefront), part B: total force, body frame, torque, the Euler step, the rows published for the next substep
 #include "sfmstep_sub_tail.inc"
-        // the parallel-traffic respawn rule, sequential inside a world, by wave ballot
+        // the parallel-traffic respawn rule, sequential inside a world, by wave ballot.  The plain one-wavefront builds enter it through one
+        // scalar branch on the tail's vote (EARLY_VOTES, sfmstep_kernel.h); a wavefront that does re-runs the next goal switch (the rule
+        // moves rows and their goals[0]: the tail's vote was on the rows of before), the others hand the tail's vote on as it is
+        if constexpr (EARLY_VOTES) {
+            if (flag_any) {
 #include "sfmstep_sub_respawn.inc"
+                hit_next = ~0ull;
+            }
+            carried_hit = hit_next;
+        } else {
+#include "sfmstep_sub_respawn.inc"
+        }
         STAMP(5);
         LDS_ORDER_FENCE(); // rows republished by the respawn rule are read by other lanes in the next substep
