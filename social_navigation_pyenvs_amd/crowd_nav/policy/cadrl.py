@@ -15,6 +15,7 @@ from ... import _lib
 from ..._lib import DeviceBuffer, check
 from ..policy_no_train.policy import Policy
 from ..utils.action import ActionXY
+from . import value_net
 
 
 def build_action_space_array(v_pref: float, speed_samples: int = 5, rotation_samples: int = 16) -> np.ndarray:
@@ -143,6 +144,7 @@ def joint_rows(state, headed):
 class CADRL(Policy):
     display_name = "CADRL"
     config_section = "cadrl"
+    family = value_net.FEED_FORWARD      # the row of value_net.Family the policy's network belongs to
 
     def __init__(self):
         super().__init__()
@@ -181,18 +183,14 @@ class CADRL(Policy):
     def set_decision_precision(self, precision):
         """The arithmetic of the decision kernel, for ``predict`` and ``act_device`` alike: "f32" (the default) or the opt-in "bf16"
         (bf16 matrix instructions behind the first layer, float32 accumulation and reductions)."""
-        from .value_net import check_decision_input, check_precision
-
-        check_decision_input(self.decision_input, check_precision(precision), self.map_columns())
+        value_net.check_mode(self.family, self.decision_input, value_net.check_precision(precision))
         self.decision_precision = precision
 
     def set_decision_input(self, decision_input):
         """Where the decision kernel's rows come from, for ``predict`` and ``act_device`` alike: "tensor" (the default: cs_lookahead writes
         rotated [W][A][n][13|15] to HBM, cs_value_net_decide reads it back) or the opt-in "fused" (cs_value_net_decide_worlds generates
         the rows in LDS from the worlds' own rows, bit for bit the same decision).  "fused" is float32 only."""
-        from .value_net import check_decision_input
-
-        self.decision_input = check_decision_input(decision_input, self.decision_precision, self.map_columns())
+        self.decision_input = value_net.check_mode(self.family, decision_input, self.decision_precision)
 
     def build_action_space(self, v_pref):
         """(0, 0) plus rotation_samples headings x speed_samples exponentially spaced speeds up to v_pref."""
@@ -208,9 +206,7 @@ class CADRL(Policy):
         return 0
 
     def _new_device_net(self, model):
-        from .value_net import DeviceNet
-
-        return DeviceNet(model, self.joint_state_dim)
+        return value_net.DeviceNet(model, self.joint_state_dim)
 
     def device_net(self):
         """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
@@ -239,26 +235,29 @@ class CADRL(Policy):
         net.refresh("f32")
         return net
 
+    def _world_of(self, state, what):
+        """The W = 1 tensors of a JointState, for `what` ("predict", "state_value"): (the current humans [n, 5 | 7] on the host, the same [1, n, 5 | 7]
+        and the robot's row [1, 9] on the device); ValueError when the state has fewer humans than the policy's family needs."""
+        least = self.family.min_humans
+        if len(state.human_states) < least:
+            raise ValueError(f"{self.name}.{what} needs at least " + ("one human" if least == 1 else
+                                                                     "two humans: a lone human has no other human to map"))
+        _lib.require_gpu()
+        rows = joint_rows(state, bool(self.with_theta_and_omega_visible))
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
+        cur = rows[:, len(ROBOT_FIELDS):]
+        return cur, up(cur)[None], up(rows[:1, :len(ROBOT_FIELDS)])
+
     def state_value(self, state, model=None):
         """V(state): the value network (``model``: another module of the same architecture, e.g. a target network) on the rotated joint
-        state of ``state`` as it stands -- no look-ahead, no reward; CADRL: the minimum over the humans.  The W = 1 launch of the kernel
-        behind ``BatchedSocialNavGym.value_device`` (cs_value_net_state), float32; returns a Python float."""
-        from . import value_net
-
-        _lib.require_gpu()
+        state of ``state`` as it stands -- no look-ahead, no reward, the humans in their own order; CADRL: the minimum over the humans;
+        OM-SARL: on the wide rows of ``transform``.  The W = 1 launches behind ``BatchedSocialNavGym.value_device``
+        (value_net.state_values_for_worlds), float32; returns a Python float."""
         if self.model is None:
             raise AttributeError(f"{self.name}: configure() the policy before it evaluates a state")
-        headed = bool(self.with_theta_and_omega_visible)
-        rows = joint_rows(state, headed)
-        if rows.shape[0] < 1:
-            raise ValueError(f"{self.name}.state_value needs at least one human")
-        net = self.state_net(model)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
-        d_c, d_r = up(rows[:, len(ROBOT_FIELDS):]), up(rows[:1, :len(ROBOT_FIELDS)])
-        value = torch.empty(1, dtype=torch.float32, device="cuda")
-        value_net.state_values(net, 1, rows.shape[0], headed, d_c.data_ptr(), d_r.data_ptr(), d_r.shape[1], None, self.gamma, 0.0, None,
-                               value.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        return float(value.item())
+        _, d_c, d_r = self._world_of(state, "state_value")
+        values, _ = value_net.state_values_for_worlds(self.state_net(model), d_c, d_r, None, self.gamma, 0.0, False, torch.cuda.current_stream().cuda_stream)
+        return float(values.item())
 
     def device_action_space(self):
         """The action table as a CUDA tensor [A, 2], uploaded again only when action_space_ndarray holds other values."""
@@ -280,19 +279,11 @@ class CADRL(Policy):
     def _decide_one(self, state, override=-1):
         """value_net.decide_for_worlds for this one robot (W = 1) on the current stream: (action values [A], chosen index, ActionXY row
         float32)."""
-        from . import value_net
-
-        _lib.require_gpu()
-        headed = bool(self.with_theta_and_omega_visible)
-        rows = joint_rows(state, headed)
-        n, A = rows.shape[0], len(self.action_space_ndarray)
-        if n < 1:
-            raise ValueError(f"{self.name}.predict needs at least one human")
-        cur = rows[:, len(ROBOT_FIELDS):].astype(np.float64)
-        nxt = self._next_humans(cur)
+        cur, d_c, d_r = self._world_of(state, "predict")
+        A = len(self.action_space_ndarray)
         net = self.device_net()
         up = lambda a, dtype=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-        d_a, d_n, d_c, d_r = self.device_action_space(), up(np.asarray(nxt, np.float32))[None], up(cur.astype(np.float32))[None], up(rows[:1, :len(ROBOT_FIELDS)])
+        d_a, d_n = self.device_action_space(), up(np.asarray(self._next_humans(cur.astype(np.float64)), np.float32))[None]
         vals = torch.empty((1, A), dtype=torch.float32, device="cuda")
         pick = torch.empty(1, dtype=torch.int32, device="cuda")
         act = torch.empty((1, 2), dtype=torch.float32, device="cuda")

@@ -13,12 +13,11 @@ from __future__ import annotations
 
 import logging
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from ... import _lib
-from .cadrl import ROBOT_FIELDS, joint_rows, mlp, width_list
+from . import value_net
+from .cadrl import mlp, width_list
 from .multi_human_rl import MultiHumanRL
 
 
@@ -56,6 +55,7 @@ class ValueNetwork2(nn.Module):
 class LstmRL(MultiHumanRL):
     display_name = "LSTM-RL"
     config_section = "lstm_rl"
+    family = value_net.RECURRENT         # the one kernel: float32 on the look-ahead tensor
 
     def __init__(self):
         super().__init__()
@@ -79,33 +79,3 @@ class LstmRL(MultiHumanRL):
             self.model = ValueNetwork1(self.input_dim(), self.self_state_dim, mlp_dims, hidden)
         self.multiagent_training = config.getboolean(section, "multiagent_training")
         logging.debug("%s: %s pairwise interaction module, hidden width %d", self.name, "with" if self.with_interaction_module else "without", hidden)
-
-    # this network has the one kernel: float32 on the look-ahead tensor
-    def set_decision_precision(self, precision):
-        from .value_net import check_decision_input, check_precision
-
-        check_decision_input(self.decision_input, check_precision(precision), recurrent=True)
-        self.decision_precision = precision
-
-    def set_decision_input(self, decision_input):
-        from .value_net import check_decision_input
-
-        self.decision_input = check_decision_input(decision_input, self.decision_precision, recurrent=True)
-
-    def state_value(self, state, model=None):
-        """V(state) on ``transform``'s rows, in the humans' own order (no sort: what the reference's trainer asks of its target network):
-        the W = 1 launches behind ``BatchedSocialNavGym.value_device`` for this policy (value_net.state_values_lstm), float32; returns a
-        Python float."""
-        from . import value_net
-
-        if self.model is None:
-            raise AttributeError(f"{self.name}: configure() the policy before it evaluates a state")
-        _lib.require_gpu()
-        rows = joint_rows(state, bool(self.with_theta_and_omega_visible))
-        if rows.shape[0] < 1:
-            raise ValueError(f"{self.name}.state_value needs at least one human")
-        net = self.state_net(model)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
-        d_c, d_r = up(rows[:, len(ROBOT_FIELDS):])[None], up(rows[:1, :len(ROBOT_FIELDS)])
-        values, _ = value_net.state_values_lstm(net, d_c, d_r, None, self.gamma, 0.0, torch.cuda.current_stream().cuda_stream)
-        return float(values.item())

@@ -16,12 +16,14 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .cadrl import ROBOT_FIELDS, joint_rows, width_list
+from . import value_net
+from .cadrl import width_list
 from .sarl import SARL, ValueNetwork
 
 
 class OMSARL(SARL):
     display_name = "OM-SARL"
+    family = value_net.MAPPED            # (two humans at least for ``predict`` and ``state_value``: a lone human has nobody to map)
 
     def configure(self, config):
         self.set_common_parameters(config)
@@ -49,16 +51,12 @@ class OMSARL(SARL):
         return int(self.cell_num), float(self.cell_size), int(self.om_channel_size)
 
     def _new_device_net(self, model):
-        from .value_net import DeviceNet
-
-        return DeviceNet(model, self.joint_state_dim, self.map_columns(), self.om_grid())
+        return value_net.DeviceNet(model, self.joint_state_dim, self.map_columns(), self.om_grid())
 
     # ------------------------------------------------------------------ the maps
     def build_occupancy_maps(self, human_states):
         """The reference's method (multi_human_rl.py:133-187): float32 tensor [humans, cell_num^2 * om_channel_size], row i the map around
         human i of the other humans.  The W = 1 launch of cs_occupancy_maps.  One human has nobody to map: ValueError, as there."""
-        from . import value_net
-
         if len(human_states) < 2:
             raise ValueError("build_occupancy_maps needs at least two humans: a lone human has no other human to map")
         _lib.require_gpu()
@@ -70,29 +68,6 @@ class OMSARL(SARL):
         """What a trainer stores for this decision: tensor [humans, 13 | 15 + C], every human's rotated joint state and its map."""
         maps = self.build_occupancy_maps(state.human_states).to(self.device)
         return torch.cat([super().transform(state), maps], dim=1)
-
-    # ------------------------------------------------------------------ the decision and the state's value
-    def _decide_one(self, state, override=-1):
-        if len(state.human_states) < 2:
-            raise ValueError(f"{self.name}.predict needs at least two humans: a lone human has no other human to map")
-        return super()._decide_one(state, override)
-
-    def state_value(self, state, model=None):
-        """V(state) on the wide rows of ``transform``: the W = 1 launches behind ``BatchedSocialNavGym.value_device`` for this policy
-        (value_net.state_values_om), float32; returns a Python float."""
-        from . import value_net
-
-        if self.model is None:
-            raise AttributeError(f"{self.name}: configure() the policy before it evaluates a state")
-        if len(state.human_states) < 2:
-            raise ValueError(f"{self.name}.state_value needs at least two humans: a lone human has no other human to map")
-        _lib.require_gpu()
-        rows = joint_rows(state, bool(self.with_theta_and_omega_visible))
-        net = self.state_net(model)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
-        d_c, d_r = up(rows[:, len(ROBOT_FIELDS):])[None], up(rows[:1, :len(ROBOT_FIELDS)])
-        values, _ = value_net.state_values_om(net, d_c, d_r, None, self.gamma, 0.0, torch.cuda.current_stream().cuda_stream)
-        return float(values.item())
 
     def get_attention_weights(self):
         """SARL's, on the wide rows: the last action's rotated rows beside the maps of that decision."""

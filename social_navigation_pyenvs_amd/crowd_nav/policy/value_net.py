@@ -16,13 +16,20 @@ cs_value_net_pack_om, ``occupancy_maps`` is cs_occupancy_maps, ``decide_om`` cs_
 LSTM-RL (crowd_nav/policy/lstm_rl.py) has a kernel of its own (cs_value_net_decide_lstm, csrc/value_net_lstm.hip) and its own description:
 ``describe`` answers CS_VN_LSTM -- a tag of this module, not a `kind` of the C entries --, such a ``DeviceNet`` packs through
 cs_value_net_pack_lstm, ``decide_lstm`` is the library call and ``decide_for_worlds`` runs lookahead -> decide_lstm(sorted_by_distance=1);
-``state_values_lstm`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor only.
+``state_values_for_worlds`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor only.
+
+Which entries a network uses, with which arguments, and which modes it may run in is stated once, in the three rows of ``Family``
+(FEED_FORWARD, MAPPED, RECURRENT); a ``DeviceNet`` holds its row, a policy class names its own, and ``pack``, ``decide_rows``,
+``decide_for_worlds``, ``state_values_for_worlds`` and ``check_mode`` ask it.
 
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
-rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes."""
+rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes;
+``state_values_for_worlds`` is that for every family."""
 from __future__ import annotations
 
 import ctypes as C
+from types import MappingProxyType as frozen
+from typing import NamedTuple
 
 import numpy as np
 
@@ -38,22 +45,67 @@ def check_precision(precision):
     return precision
 
 
-def check_decision_input(decision_input, precision, om_cols=0, recurrent=False):
-    """The pair (decision input, precision) a policy may hold: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel,
-    no look-ahead tensor) exists for the float32 arithmetic only.  A network with occupancy-map columns (``om_cols`` > 0) has the one
-    kernel cs_value_net_decide_om: float32 on the look-ahead tensor.  So has a ``recurrent`` one (LSTM-RL: cs_value_net_decide_lstm)."""
+class Family(NamedTuple):
+    """What one family of value networks states about itself; everything else in this module, the policies and the Gym ask a row of this
+    table."""
+    pack: frozen            # precision -> (pack entry, what it counts its blob in)
+    takes_kind: bool        # the C entries open with a `kind`
+    decide: frozen          # precision -> the decide entry on the look-ahead tensor
+    decide_int: str         # the integer that entry takes behind cols: "", "om_cols" or "sorted_by_distance"
+    takes_maps: bool        # that entry takes the maps behind rotated; the pack entry om_cols behind cols
+    modes: tuple            # the (decision input, precision) pairs the family runs
+    refusal: str            # the sentence every other pair is refused with ({0!r}: the input, {1!r}: the precision)
+    min_humans: int         # humans a world needs
+    state_launch: bool      # V(s) is one cs_value_net_state launch; else rows, [maps,] the decide entry with A = 1
+
+    def lead(self, kind):
+        return (kind,) if self.takes_kind else ()
+
+
+FEED_FORWARD = Family(
+    pack=frozen({"f32": ("cs_value_net_pack", np.float32), "bf16": ("cs_value_net_pack_bf16", np.uint8)}), takes_kind=True,
+    decide=frozen({"f32": "cs_value_net_decide", "bf16": "cs_value_net_decide_bf16"}), decide_int="", takes_maps=False,
+    modes=(("tensor", "f32"), ("tensor", "bf16"), ("fused", "f32")),
+    refusal='decision input "fused" with decision precision "bf16": the bf16 kernel has its own tile loader and reads the look-ahead tensor; '
+            'choose "tensor" or "f32"',
+    min_humans=1, state_launch=True)
+MAPPED = Family(
+    pack=frozen({"f32": ("cs_value_net_pack_om", np.float32)}), takes_kind=True,
+    decide=frozen({"f32": "cs_value_net_decide_om"}), decide_int="om_cols", takes_maps=True,
+    modes=(("tensor", "f32"),),
+    refusal='decision input {0!r} with decision precision {1!r} for a network with occupancy-map columns: no kernel pairs the map columns '
+            'with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"',
+    min_humans=2, state_launch=False)
+RECURRENT = Family(
+    pack=frozen({"f32": ("cs_value_net_pack_lstm", np.float32)}), takes_kind=False,
+    decide=frozen({"f32": "cs_value_net_decide_lstm"}), decide_int="sorted_by_distance", takes_maps=False,
+    modes=(("tensor", "f32"),),
+    refusal='decision input {0!r} with decision precision {1!r} for a recurrent network: LSTM-RL has the one kernel, float32 on the '
+            'look-ahead tensor; it decides with "tensor" and "f32"',
+    min_humans=1, state_launch=False)
+
+
+def family_of(kind, om_cols=0):
+    """The family of a description (``describe``'s kind) with ``om_cols`` map columns."""
+    return RECURRENT if kind == CS_VN_LSTM else MAPPED if om_cols else FEED_FORWARD
+
+
+def check_mode(family, decision_input, precision):
+    """The pair (decision input, precision) a network of `family` may hold: one of the family's modes.  An input the family runs in every
+    precision asks nothing of the precision (``check_precision`` is the setters' and ``DeviceNet.head``'s)."""
     if decision_input not in DECISION_INPUTS:
         raise ValueError(f"decision input {decision_input!r}: one of {', '.join(map(repr, DECISION_INPUTS))}")
-    if recurrent and (decision_input == "fused" or check_precision(precision) == "bf16"):
-        raise ValueError(f'decision input {decision_input!r} with decision precision {precision!r} for a recurrent network: LSTM-RL has the one '
-                         'kernel, float32 on the look-ahead tensor; it decides with "tensor" and "f32"')
-    if om_cols and (decision_input == "fused" or check_precision(precision) == "bf16"):
-        raise ValueError(f'decision input {decision_input!r} with decision precision {precision!r} for a network with occupancy-map columns: no '
-                         'kernel pairs the map columns with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"')
-    if decision_input == "fused" and check_precision(precision) == "bf16":
-        raise ValueError('decision input "fused" with decision precision "bf16": the bf16 kernel has its own tile loader and reads the '
-                         'look-ahead tensor; choose "tensor" or "f32"')
+    runs = [p for i, p in family.modes if i == decision_input]
+    if len(runs) < len(PRECISIONS) and (not runs or check_precision(precision) not in runs):
+        raise ValueError(family.refusal.format(decision_input, precision))
     return decision_input
+
+
+def check_decision_input(decision_input, precision, om_cols=0, recurrent=False):
+    """``check_mode`` for who holds no family: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel, no look-ahead
+    tensor) exists for the float32 arithmetic only.  A network with occupancy-map columns (``om_cols`` > 0) has the one kernel
+    cs_value_net_decide_om: float32 on the look-ahead tensor.  So has a ``recurrent`` one (LSTM-RL: cs_value_net_decide_lstm)."""
+    return check_mode(RECURRENT if recurrent else MAPPED if om_cols else FEED_FORWARD, decision_input, precision)
 
 
 def _linears(seq):
@@ -95,33 +147,27 @@ def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     needed."""
     from ... import _lib
 
-    lib = _lib.load()
-    if kind == CS_VN_LSTM:
-        check_decision_input("tensor", precision, om_cols, recurrent=True)
-        if om_cols:
-            raise ValueError("an LSTM-RL network reads the rotated columns only: no occupancy-map columns")
-        return _pack_with(lib.cs_value_net_pack_lstm, np.float32, None, dims, cols, arrays)
-    if om_cols:
-        check_decision_input("tensor", precision, om_cols)
-        return _pack_with(lib.cs_value_net_pack_om, np.float32, kind, dims, cols, arrays, om_cols)
-    if check_precision(precision) == "bf16":
-        return _pack_with(lib.cs_value_net_pack_bf16, np.uint8, kind, dims, cols, arrays)
-    return _pack_with(lib.cs_value_net_pack, np.float32, kind, dims, cols, arrays)
+    family = family_of(kind, om_cols)
+    check_mode(family, "tensor", precision)
+    if family is RECURRENT and om_cols:
+        raise ValueError("an LSTM-RL network reads the rotated columns only: no occupancy-map columns")
+    entry, unit = family.pack[check_precision(precision)]
+    dims = np.ascontiguousarray(dims, np.int32)
+    lead = family.lead(kind) + (dims.ctypes.data, len(dims), cols) + ((om_cols,) if family.takes_maps else ())
+    return _pack_with(getattr(_lib.load(), entry), unit, lead, arrays)
 
 
-def _pack_with(entry, unit, kind, dims, cols, arrays, om_cols=None):
-    """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `om_cols`: the argument
-    cs_value_net_pack_om takes behind cols; `kind` None: cs_value_net_pack_lstm, which takes none."""
+def _pack_with(entry, unit, lead, arrays):
+    """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `lead`: the arguments
+    it takes before the arrays."""
     from ... import _lib
 
-    dims = np.ascontiguousarray(dims, np.int32)
     arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
-    head = (() if kind is None else (kind,)) + (dims.ctypes.data, len(dims), cols) + (() if om_cols is None else (om_cols,))
-    _lib.check(entry(*head, None, None, C.byref(nf)))
+    _lib.check(entry(*lead, None, None, C.byref(nf)))
     blob = np.zeros(nf.value, unit)
-    _lib.check(entry(*head, ptrs, blob.ctypes.data, C.byref(nf)))
+    _lib.check(entry(*lead, ptrs, blob.ctypes.data, C.byref(nf)))
     return blob
 
 
@@ -130,13 +176,14 @@ class DeviceNet:
     parameters changed (the same version-counter key for both).  ``blob`` is the float32 one.  ``om_cols`` > 0: an OM-SARL network whose
     mlp1 reads cols + om_cols columns (cs_value_net_pack_om's blob); ``om_grid`` = (cell_num, cell_size, om_channel_size) of its maps;
     ``last_maps``: the maps [W, n, om_cols] of its last ``decide_for_worlds``.  ``lstm``: an LSTM-RL network (cs_value_net_pack_lstm's blob,
-    float32 only; the version key covers the LSTM's four tensors)."""
+    float32 only; the version key covers the LSTM's four tensors).  ``family``: its row of the family table, which says all of that."""
 
     def __init__(self, model, cols, om_cols=0, om_grid=None):
         self.model, self.cols, self.om_cols, self.om_grid = model, int(cols), int(om_cols), om_grid
         self.last_maps = None
         self.kind, self.dims, self.layers = describe(model)
-        self.lstm = self.kind == CS_VN_LSTM
+        self.family = family_of(self.kind, self.om_cols)
+        self.lstm = self.family is RECURRENT
         self._keys = dict.fromkeys(PRECISIONS)
         self.blobs = dict.fromkeys(PRECISIONS)
 
@@ -158,29 +205,38 @@ class DeviceNet:
         return self.blobs[precision]
 
     def head(self, caller, precision="f32"):
-        """The five arguments every network entry opens with (four for an LSTM-RL network, whose entries take no kind), for the blob of
-        `precision`; ValueError in `caller`'s name without one."""
+        """The arguments every network entry of the family opens with, for the blob of `precision`; ValueError in `caller`'s name
+        without one."""
         blob = self.blobs[check_precision(precision)]
         if blob is None:
             raise ValueError(f"{caller}: the network has no {precision} blob yet (DeviceNet.refresh({precision!r}))")
-        return _head(self.kind, self.dims, blob)[1 if self.lstm else 0:]
+        return _head(self.family.lead(self.kind), self.dims, blob)
 
 
-def _head(kind, dims, blob):
-    """kind, dims (host int32 array), its length, the packed blob (a CUDA tensor) and its length in the blob's own unit."""
-    return kind, dims.ctypes.data, len(dims), blob.data_ptr(), blob.numel()
+def _head(lead, dims, blob):
+    """[kind,] dims (host int32 array), its length, the packed blob (a CUDA tensor) and its length in the blob's own unit."""
+    return lead + (dims.ctypes.data, len(dims), blob.data_ptr(), blob.numel())
+
+
+def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):
+    """The tensor decide entry of `net`'s family on device pointers (ints).  `extra`: what that entry takes beyond
+    cs_value_net_decide's arguments -- the maps [W][n][net.om_cols], or sorted_by_distance; `tail`: rewards, actions, robot, robot_stride,
+    gamma, dt, override, values, choice, action_out, stream."""
+    from ... import _lib
+
+    family = net.family
+    head = net.head(family.decide["f32"].removeprefix("cs_value_net_"), precision)
+    behind_cols = {"": (), "om_cols": (net.om_cols,), "sorted_by_distance": (int(bool(extra)),)}[family.decide_int]
+    behind_rotated = (extra,) if family.takes_maps else ()
+    _lib.check(getattr(_lib.load(), family.decide[precision])(*head, W, A, n, net.cols, *behind_cols, rotated, *behind_rotated, *tail))
 
 
 def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None,
            precision="f32"):
     """cs_value_net_decide (`precision` "f32") or cs_value_net_decide_bf16 ("bf16") on device pointers (ints); `net` a DeviceNet whose
     blob of that precision is current (refresh(precision))."""
-    from ... import _lib
-
-    head = net.head("decide", precision)
-    entry = _lib.load().cs_value_net_decide_bf16 if precision == "bf16" else _lib.load().cs_value_net_decide
-    _lib.check(entry(*head, W, A, n, net.cols, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
-                     action_out, stream))
+    decide_rows(net, W, A, n, rotated, None, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream,
+                precision=precision)
 
 
 def occupancy_maps(W, n, humans, stride, vel_col, cell_num, cell_size, channels, maps, stream=None):
@@ -207,44 +263,28 @@ def maps_of(humans, vel_col, grid, stream=None):
 
 def decide_om(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None):
     """cs_value_net_decide_om on device pointers (ints): ``decide`` for a DeviceNet with map columns, maps [W][n][net.om_cols]."""
-    from ... import _lib
-
-    head = net.head("decide_om")
-    if net.om_cols < 1:
+    if net.family is not MAPPED:
         raise ValueError("decide_om: the network has no occupancy-map columns (DeviceNet(model, cols, om_cols))")
-    _lib.check(_lib.load().cs_value_net_decide_om(*head, W, A, n, net.cols, net.om_cols, rotated, maps, rewards, actions, robot, robot_stride,
-                                                  gamma, dt, override, values, choice, action_out, stream))
+    decide_rows(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream)
 
 
 def decide_lstm(net, W, A, n, sorted_by_distance, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out,
                 stream=None):
     """cs_value_net_decide_lstm on device pointers (ints): ``decide`` for a DeviceNet of an LSTM-RL network; ``sorted_by_distance`` 1: every
     (world, action)'s rows by decreasing column 11 (the decision's order), 0: as they lie."""
-    from ... import _lib
-
-    if not net.lstm:
+    if net.family is not RECURRENT:
         raise ValueError("decide_lstm: the network is not an LSTM-RL one (lstm_rl.ValueNetwork1 / ValueNetwork2)")
-    head = net.head("decide_lstm")
-    _lib.check(_lib.load().cs_value_net_decide_lstm(*head, W, A, n, net.cols, int(bool(sorted_by_distance)), rotated, rewards, actions, robot,
-                                                    robot_stride, gamma, dt, override, values, choice, action_out, stream))
+    decide_rows(net, W, A, n, rotated, sorted_by_distance, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                action_out, stream)
 
 
-def state_values_lstm(net, cur, robot, rewards, gamma, dt, stream=None):
-    """``state_values`` for a DeviceNet of an LSTM-RL network, two launches where a feed-forward network has one: the rotated rows of the
-    current state (``rotated_rows``) and cs_value_net_decide_lstm on them as they lie (sorted_by_distance = 0) with A = 1 -- a one-row
-    action table, no choice, a scratch action row.  CUDA tensors cur [W, n, 5 | 7], robot [W, 8+], rewards [W] or None (0).  Returns
-    (values [W], rows [W, n, cols]: what ``transform`` gives per world)."""
-    import torch
-
-    W, n, _ = cur.shape
-    rows = rotated_rows(cur, robot, stream)
-    values = torch.empty(W, dtype=torch.float32, device="cuda")
-    zeros = torch.zeros(max(W, 2), dtype=torch.float32, device="cuda")     # the null rewards; its first two floats the one-row action table
-    scratch = torch.empty((W, 2), dtype=torch.float32, device="cuda")
-    rew = rewards if rewards is not None else zeros
-    decide_lstm(net, W, 1, n, 0, rows.data_ptr(), rew.data_ptr(), zeros.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, None,
-                values.data_ptr(), None, scratch.data_ptr(), stream)
-    return values, rows
+def _extra_input(net, humans, vel_col, in_order, stream):
+    """What ``decide_rows`` takes as `extra` for `net`: (the argument, the tensor behind it or None) -- the maps of `humans` [W, n, stride]
+    for a family with maps (a launch), `in_order` as sorted_by_distance for a recurrent one, nothing otherwise."""
+    if net.family.takes_maps:
+        maps = maps_of(humans, vel_col, net.om_grid, stream)
+        return maps.data_ptr(), maps
+    return (in_order if net.family.decide_int == "sorted_by_distance" else None), None
 
 
 _ROWS_BLOB = {}
@@ -265,28 +305,35 @@ def rotated_rows(cur, robot, stream=None):
         _ROWS_BLOB[key] = torch.from_numpy(pack(CS_VN_CADRL, dims, cols, [np.zeros((1, cols), np.float32), np.zeros(1, np.float32)])).to("cuda")
     rows = torch.empty((W, n, cols), dtype=torch.float32, device="cuda")
     unread = torch.empty(W, dtype=torch.float32, device="cuda")
-    _lib.check(_lib.load().cs_value_net_state(*_head(CS_VN_CADRL, dims, _ROWS_BLOB[key]), W, n, cc == 7, cur.data_ptr(), robot.data_ptr(),
+    _lib.check(_lib.load().cs_value_net_state(*_head((CS_VN_CADRL,), dims, _ROWS_BLOB[key]), W, n, cc == 7, cur.data_ptr(), robot.data_ptr(),
                                               robot.shape[1], None, 1.0, 0.0, rows.data_ptr(), unread.data_ptr(), stream))
     return rows
 
 
-def state_values_om(net, cur, robot, rewards, gamma, dt, stream=None):
-    """``state_values`` for a DeviceNet with map columns, composed of three launches where a 13-column network has one: the rotated rows
-    of the current state (``rotated_rows``), the maps of the CURRENT humans, and cs_value_net_decide_om with A = 1 -- a one-row action
-    table, no choice, a scratch action row.  CUDA tensors cur [W, n, 5 | 7], robot [W, 8+], rewards [W] or None (0).  Returns (values [W],
-    wide rows [W, n, cols + om_cols]: what ``transform`` gives per world)."""
+def state_values_for_worlds(net, cur, robot, rewards, gamma, dt, want_rows, stream=None):
+    """The network on the worlds' CURRENT state, for a trainer: (values [W] = rewards + gamma^(dt * v_pref) * V, rows [W, n, cols
+    (+ om_cols)] -- what ``transform`` gives per world -- or None).  CUDA tensors cur [W, n, 5 | 7], robot [W, 8+], rewards [W] or None (0).
+    A feed-forward network takes one launch (``state_values``) and makes the rows only when asked.  The other families compose it, rows
+    in any case: the maps of the CURRENT humans where the family has maps, the rotated rows (``rotated_rows``), and the family's decide
+    entry on them as they lie (sorted_by_distance = 0) with A = 1 -- a one-row action table, no choice, a scratch action row."""
     import torch
 
-    W, n, _ = cur.shape
-    maps = maps_of(cur, 2, net.om_grid, stream)
+    W, n, cc = cur.shape
+    if net.family.state_launch:
+        values = torch.empty(W, dtype=torch.float32, device="cuda")
+        rows = torch.empty((W, n, net.cols), dtype=torch.float32, device="cuda") if want_rows else None
+        state_values(net, W, n, cc == 7, cur.data_ptr(), robot.data_ptr(), robot.shape[1], None if rewards is None else rewards.data_ptr(), gamma, dt,
+                     None if rows is None else rows.data_ptr(), values.data_ptr(), stream)
+        return values, rows
+    extra, maps = _extra_input(net, cur, 2, 0, stream)
     rows = rotated_rows(cur, robot, stream)
     values = torch.empty(W, dtype=torch.float32, device="cuda")
     zeros = torch.zeros(max(W, 2), dtype=torch.float32, device="cuda")     # the null rewards; its first two floats the one-row action table
     scratch = torch.empty((W, 2), dtype=torch.float32, device="cuda")
     rew = rewards if rewards is not None else zeros
-    decide_om(net, W, 1, n, rows.data_ptr(), maps.data_ptr(), rew.data_ptr(), zeros.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt,
-              None, values.data_ptr(), None, scratch.data_ptr(), stream)
-    return values, torch.cat([rows, maps], dim=2)
+    decide_rows(net, W, 1, n, rows.data_ptr(), extra, rew.data_ptr(), zeros.data_ptr(), robot.data_ptr(), robot.shape[1],
+                gamma, dt, None, values.data_ptr(), None, scratch.data_ptr(), stream)
+    return values, rows if maps is None else torch.cat([rows, maps], dim=2)
 
 
 def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out, values, choice, action_out,
@@ -340,24 +387,14 @@ def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gam
     "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
-    if net.lstm:
-        check_decision_input(decision_input, precision, recurrent=True)
-        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
-        decide_lstm(net, W, A, n, 1, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
-                    values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
-        return rot, rew
-    if net.om_cols:
-        check_decision_input(decision_input, precision, net.om_cols)
-        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
-        net.last_maps = maps_of(nxt, 3 if cc == 7 else 2, net.om_grid, stream)
-        decide_om(net, W, A, n, rot.data_ptr(), net.last_maps.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma,
-                  dt, ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
-        return rot, rew
-    if check_decision_input(decision_input, precision) == "fused":      # one library call on the worlds' own rows
+    if check_mode(net.family, decision_input, precision) == "fused":      # one library call on the worlds' own rows
         decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
                       None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
         return None, None
     rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
-    decide(net, W, A, n, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr, values.data_ptr(),
-           choice.data_ptr(), action_out.data_ptr(), stream, precision=precision)
+    extra, maps = _extra_input(net, nxt, 3 if cc == 7 else 2, 1, stream)
+    if maps is not None:
+        net.last_maps = maps
+    decide_rows(net, W, A, n, rot.data_ptr(), extra, rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt,
+                ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream, precision=precision)
     return rot, rew

@@ -78,25 +78,15 @@ inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& 
         }
         for (int i = 0; i < nl; ++i) {
             const int wdt = dims[at++];
-            if (wdt < 1 || wdt > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "layer widths must be between 1 and 256");
-            VnLayer& l = p.L[p.n_layers++];
-            l.K1 = k1; l.K2 = 0; l.N = wdt;
-            l.kg_split = l.kg_total = up(k1, 8) / 8;
-            l.ncb = up(wdt, 32) / 32;
-            l.relu = i != nl - 1;                                                  // lstm_rl.py: mlp() without last_relu for both chains
-            l.w_off = off;
-            off += l.ncb * l.kg_total * 64 * 4;
-            l.b_off = off;
-            off += l.ncb * 32;
+            const int rc = add_layer(p, k1, 0, wdt, i != nl - 1, off);             // lstm_rl.py: mlp() without last_relu for both chains
+            if (rc != CS_OK) return rc;
             k1 = wdt;
         }
         if (c == 1 && k1 != 1) return fail(CS_ERR_ARG, "mlp ends in one output");
     }
     p.c0[2] = p.n_layers;
     if (at != n_dims) return fail(CS_ERR_ARG, "layer description has trailing entries");
-    int widest = 32;
-    for (int i = 0; i < p.n_layers; ++i) widest = p.L[i].ncb * 32 > widest ? p.L[i].ncb * 32 : widest;
-    p.ld_pq = widest + 4;
+    set_ld_pq(p);
     q.ld_xh = q.hpad + (p.c0[1] > 0 ? up(q.xin, 32) : 16) + 4;        // (mlp1's last layer stores whole 32-column blocks)
     p.ld_j = up(SELF_DIM + q.H, 8) + 4;
     p.total_floats = off;
@@ -381,21 +371,6 @@ __global__ __launch_bounds__(NT) void k_value_net_lstm(LstmPlan q, LstmLds m, co
 }
 #undef LSTM_KSTEP
 
-template <auto Kernel>
-inline int grant_lds(size_t shmem)
-{
-    if (shmem <= 64 * 1024) return CS_OK;
-    static std::atomic<int> granted[64];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const bool slot = dev >= 0 && dev < 64;
-    if (!slot || granted[dev].load(std::memory_order_acquire) < (int)shmem) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        if (slot) granted[dev].store((int)shmem, std::memory_order_release);
-    }
-    return CS_OK;
-}
-
 } // namespace
 
 #include "value_net_pick.h"
@@ -434,7 +409,8 @@ extern "C" int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const f
     const LstmLds m = lstm_lds_map(q, n);
     const size_t shmem = (size_t)m.total * sizeof(float);
     if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    const int NG = W * A, jobs = (NG + JROWS - 1) / JROWS, grid = jobs < 4096 ? jobs : 4096;
+    int NG, grid;
+    job_grid(W, A, NG, grid);
     const bool wreg = q.g.ncb <= 4 * RB && q.g.kg_total <= RKG, mlp1 = q.v.c0[1] > 0;
 #define LSTM_LAUNCH(WR, M1)                                                                                                          \
     {                                                                                                                                \

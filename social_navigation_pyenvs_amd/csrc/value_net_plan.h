@@ -48,6 +48,32 @@ struct VnPlan {
 
 inline int up(int x, int m) { return (x + m - 1) / m * m; }
 
+// one Linear layer of `wdt` outputs behind the table's last: k1 (+ k2) inputs, its weights and biases at float `off` of the blob, which
+// moves behind them; CS_OK or the fail() status
+inline int add_layer(VnPlan& p, int k1, int k2, int wdt, int relu, int& off)
+{
+    if (wdt < 1 || wdt > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "layer widths must be between 1 and 256");
+    VnLayer& l = p.L[p.n_layers++];
+    l.K1 = k1; l.K2 = k2; l.N = wdt;
+    l.kg_split = up(k1, 8) / 8;
+    l.kg_total = l.kg_split + up(k2, 8) / 8;
+    l.ncb = up(wdt, 32) / 32;
+    l.relu = relu;
+    l.w_off = off;
+    off += l.ncb * l.kg_total * 64 * 4;
+    l.b_off = off;
+    off += l.ncb * 32;
+    return CS_OK;
+}
+
+// the row stride of the P / Q buffers: the widest layer's whole 32-column blocks
+inline void set_ld_pq(VnPlan& p)
+{
+    int widest = 32;
+    for (int i = 0; i < p.n_layers; ++i) widest = p.L[i].ncb * 32 > widest ? p.L[i].ncb * 32 : widest;
+    p.ld_pq = widest + 4;
+}
+
 // the layer table of a network description (include/crowdstep.h cs_value_net_decide: `dims`); CS_OK or the fail() status
 // om_cols: the occupancy-map columns behind the rotated ones in the first layer's input (cs_value_net_decide_om; 0: none)
 inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, VnPlan& p)
@@ -78,17 +104,8 @@ inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, int o
         if (c == 3) k1 = SELF_DIM + p.feat;
         for (int i = 0; i < nl; ++i) {
             const int wdt = dims[at++];
-            if (wdt < 1 || wdt > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "layer widths must be between 1 and 256");
-            VnLayer& l = p.L[p.n_layers++];
-            l.K1 = k1; l.K2 = k2; l.N = wdt;
-            l.kg_split = up(k1, 8) / 8;
-            l.kg_total = l.kg_split + up(k2, 8) / 8;
-            l.ncb = up(wdt, 32) / 32;
-            l.relu = (i != nl - 1 || (kind == CS_VN_SARL && c == 0)) ? 1 : 0;     // cadrl.py mlp(): last_relu only for mlp1
-            l.w_off = off;
-            off += l.ncb * l.kg_total * 64 * 4;
-            l.b_off = off;
-            off += l.ncb * 32;
+            const int rc = add_layer(p, k1, k2, wdt, (i != nl - 1 || (kind == CS_VN_SARL && c == 0)) ? 1 : 0, off);     // cadrl.py mlp(): last_relu only for mlp1
+            if (rc != CS_OK) return rc;
             k1 = wdt; k2 = 0;
         }
         const int last = p.L[p.n_layers - 1].N;
@@ -98,9 +115,7 @@ inline int build_plan(int kind, const int32_t* dims, int n_dims, int cols, int o
     }
     p.c0[n_chains] = p.n_layers;
     if (at != n_dims) return fail(CS_ERR_ARG, "layer description has trailing entries");
-    int widest = 32;
-    for (int i = 0; i < p.n_layers; ++i) widest = p.L[i].ncb * 32 > widest ? p.L[i].ncb * 32 : widest;
-    p.ld_pq = widest + 4;
+    set_ld_pq(p);
     p.ld_m1 = up(p.m1w > 0 ? p.m1w : 1, 32) + 4;
     p.ld_j = up(SELF_DIM + p.feat, 8) + 4;
     p.total_floats = off;
@@ -166,8 +181,32 @@ inline VnLds lds_map(const VnPlan& p, int M, int n, int ldx)
     return m;
 }
 
+// A dynamic LDS block beyond a kernel's default 64 KiB is granted per device, raised to the largest size asked for so far.
+template <auto Kernel>
+inline int grant_lds(size_t shmem)
+{
+    if (shmem <= 64 * 1024) return CS_OK;
+    static std::atomic<int> granted[64];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const bool slot = dev >= 0 && dev < 64;
+    if (!slot || granted[dev].load(std::memory_order_acquire) < (int)shmem) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        if (slot) granted[dev].store((int)shmem, std::memory_order_release);
+    }
+    return CS_OK;
+}
+
+// the groups of a decision and the workgroups of its launch: JROWS groups a job, the jobs strided over at most 4096 workgroups
+inline void job_grid(int W, int A, int& NG, int& grid)
+{
+    NG = W * A;
+    const int jobs = (NG + JROWS - 1) / JROWS;
+    grid = jobs < 4096 ? jobs : 4096;
+}
+
 // What the decide entries do alike before their kernel's launch.  The dynamic block is the map plus `tail_floats` of the kernel's own
-// (at float `tail`); beyond a kernel's default 64 KiB it is granted per device, raised to the largest size asked for so far.
+// (at float `tail`), granted by grant_lds.
 struct VnLaunch { VnLds m; int tail; size_t shmem; int NG, grid; };
 
 template <auto Kernel>
@@ -178,19 +217,9 @@ inline int prepare_launch(const VnPlan& p, int n, int tail_floats, int W, int A,
     q.shmem = (size_t)(q.m.total + tail_floats) * sizeof(float);
     // (the float32 tensor path cannot get here within build_plan's limits -- 16 layers of up to 256 columns need about 150 KiB at most, at n = 2)
     if (q.shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    if (q.shmem > 64 * 1024) {
-        static std::atomic<int> granted[64];
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        const bool slot = dev >= 0 && dev < 64;
-        if (!slot || granted[dev].load(std::memory_order_acquire) < (int)q.shmem) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.shmem));
-            if (slot) granted[dev].store((int)q.shmem, std::memory_order_release);
-        }
-    }
-    q.NG = W * A;
-    const int jobs = (q.NG + JROWS - 1) / JROWS;
-    q.grid = jobs < 4096 ? jobs : 4096;
+    const int rc = grant_lds<Kernel>(q.shmem);
+    if (rc != CS_OK) return rc;
+    job_grid(W, A, q.NG, q.grid);
     return CS_OK;
 }
 

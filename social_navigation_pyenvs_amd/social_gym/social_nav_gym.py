@@ -792,8 +792,7 @@ class BatchedSocialNavGym:
             raise ValueError("act_device: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
         if self.cw.d_robot is None:
             raise ValueError("act_device needs the robot rows")
-        if pol.map_columns() and self._human_count() < 2:
-            raise ValueError(f"act_device: {pol.name}'s occupancy maps need at least two humans a world")
+        self._require_humans("act_device", pol)
         if pol.action_space_ndarray is None:
             pol.build_action_space(float(self._gen_kw["robot_desired_speed"]))
         W = self.W
@@ -874,16 +873,14 @@ class BatchedSocialNavGym:
             raise ValueError(f"{who}: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
         if self.cw is not None and self.cw.d_robot is None:
             raise ValueError(f"{who} needs the robot rows")
-        if pol.map_columns() and self._human_count() < 2:
-            raise ValueError(f"{who}: {pol.name}'s occupancy maps need at least two humans a world")
+        self._require_humans(who, pol)
         import torch
 
         from ..crowd_nav.policy import value_net
 
         dl = self._device_loop_state()
-        W, n = self.W, self.n
         if rewards is not None:
-            if not (torch.is_tensor(rewards) and rewards.is_cuda and rewards.dtype == torch.float32 and tuple(rewards.shape) == (W,)):
+            if not (torch.is_tensor(rewards) and rewards.is_cuda and rewards.dtype == torch.float32 and tuple(rewards.shape) == (self.W,)):
                 raise ValueError(f"{who}: rewards is a float32 CUDA tensor [W]")
             rewards = rewards.contiguous()
         net = pol.state_net(model)                   # (repacked here, on the caller's stream, only when a parameter changed)
@@ -891,15 +888,7 @@ class BatchedSocialNavGym:
         self._stream_handshake(dl, cur, True)
         with torch.cuda.stream(side):
             _, cur_, rob = self._worlds_on_side_stream(dl, peek=False)
-            if net.om_cols:                      # OM-SARL: rows, maps of the current humans and the network are three launches
-                values, rows = value_net.state_values_om(net, cur_, rob, rewards, pol.gamma, dt, side.cuda_stream)
-            elif net.lstm:                       # LSTM-RL: the rows, then the recurrent kernel on them in the humans' own order
-                values, rows = value_net.state_values_lstm(net, cur_, rob, rewards, pol.gamma, dt, side.cuda_stream)
-            else:
-                values = torch.empty(W, dtype=torch.float32, device="cuda")
-                rows = torch.empty((W, n, pol.joint_state_dim), dtype=torch.float32, device="cuda") if with_rows else None
-                value_net.state_values(net, W, n, self.headed_obs, cur_.data_ptr(), rob.data_ptr(), rob.shape[1], None if rewards is None else rewards.data_ptr(),
-                                       pol.gamma, dt, None if rows is None else rows.data_ptr(), values.data_ptr(), side.cuda_stream)
+            values, rows = value_net.state_values_for_worlds(net, cur_, rob, rewards, pol.gamma, dt, with_rows, side.cuda_stream)
             for t in (cur_, rob, rewards, values, rows):
                 if t is not None:
                     t.record_stream(cur if t is values or t is rows else side)
@@ -910,6 +899,11 @@ class BatchedSocialNavGym:
         """Humans a world: of the generated batch, or what the configuration will generate"""
         n = getattr(self, "n", None)
         return int(n) if n is not None else self.config.getint("sim", "human_num")
+
+    def _require_humans(self, who, pol):
+        """The refusal of a batch whose worlds have fewer humans than the policy's network family needs (value_net.Family.min_humans)"""
+        if 1 < pol.family.min_humans and self._human_count() < pol.family.min_humans:      # (only a family with maps asks for more than one)
+            raise ValueError(f"{who}: {pol.name}'s occupancy maps need at least two humans a world")
 
     def occupancy_maps_device(self, cell_num, cell_size, channels, which="current"):
         """OM-SARL's local occupancy maps of every world's humans (cs_occupancy_maps; ``build_occupancy_maps`` for W worlds), for a network

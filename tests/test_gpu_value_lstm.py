@@ -11,29 +11,13 @@ import numpy as np
 import pytest
 
 import lstm_cases as lc
+from value_calls import _stream, _up, decide_call, same_bits
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 DT, GAMMA = 0.25, 0.9
 MARGIN = 4.0
-
-
-def _up(a, dtype=None):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-def _stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
 def _ready(pol):
@@ -43,25 +27,6 @@ def _ready(pol):
     pol.set_device(torch.device("cuda"))
     pol.time_step = DT
     return pol
-
-
-def decide_call(dnet, rot, rew, acts, rob, sorted_by_distance=1, gamma=GAMMA, dt=DT, override=None):
-    """cs_value_net_decide_lstm on host arrays rot [W, A, n, cols], rew [W, A], acts [A, 2], rob [W, 9]: (values [W, A], choice [W],
-    action [W, 2]) numpy.  The outputs are NaN- / -5-filled before: every element must be written."""
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    W, A, n, _ = rot.shape
-    vals = torch.full((W, A), np.nan, device="cuda")
-    pick = torch.full((W,), -5, dtype=torch.int32, device="cuda")
-    act = torch.full((W, 2), np.nan, device="cuda")
-    d_rot, d_rew, d_acts, d_rob = _up(rot, torch.float32), _up(rew, torch.float32), _up(acts, torch.float32), _up(rob, torch.float32)
-    d_ovr = None if override is None else _up(override, torch.int32)
-    value_net.decide_lstm(dnet, W, A, n, sorted_by_distance, d_rot.data_ptr(), d_rew.data_ptr(), d_acts.data_ptr(), d_rob.data_ptr(), d_rob.shape[1],
-                          gamma, dt, None if d_ovr is None else d_ovr.data_ptr(), vals.data_ptr(), pick.data_ptr(), act.data_ptr(), _stream())
-    torch.cuda.synchronize()
-    return vals.cpu().numpy(), pick.cpu().numpy(), act.cpu().numpy()
 
 
 def device_net(pol):

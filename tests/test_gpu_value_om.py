@@ -14,6 +14,7 @@ from test_gpu_value_policy import REL_BAR, _batched, _ready, _torch_values
 from test_gpu_value_worlds import GAMMA, HEADED, worlds
 from test_value_om_cpu import g20, g20_policy, om_policy
 from test_value_policy_cpu import make_policy
+from value_calls import _stream, _up, decide_call, lookahead_call, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -22,22 +23,6 @@ DT = 0.25
 MEAN_BAR = 1e-5         # the project's per-substep contract; speeds are <= 1.5 m/s, float32 rounding two orders below
 GUARD = (5, 8)
 ALL_CONFIGS = om_cases.CONFIGS + (om_cases.WIDE_CONFIG,)
-
-
-def _up(a, dtype=None):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-def _stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
 def maps_call(humans, vel_col, cfg):
@@ -135,37 +120,6 @@ def test_one_human_writes_zeros_and_a_nan_stays_in_its_pairs():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the decision
-def lookahead_call(acts, nxt, cur, rob, dt=DT):
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    out = value_net.lookahead(_up(acts), _up(nxt), _up(cur), _up(rob), dt, _stream())
-    torch.cuda.synchronize()
-    return out
-
-
-def decide_call(dnet, rot, rew, acts, rob, maps=None, gamma=GAMMA, dt=DT, override=None):
-    """cs_value_net_decide (maps None) or cs_value_net_decide_om on device tensors: (values [W, A], choice [W], action [W, 2]) numpy"""
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    W, A, n, _ = rot.shape
-    vals = torch.full((W, A), np.nan, device="cuda")
-    pick = torch.full((W,), -5, dtype=torch.int32, device="cuda")
-    act = torch.full((W, 2), np.nan, device="cuda")
-    d_acts, d_rob = _up(acts), _up(rob)
-    common = (d_acts.data_ptr(), d_rob.data_ptr(), d_rob.shape[1], gamma, dt, override, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), _stream())
-    if maps is None:
-        value_net.decide(dnet, W, A, n, rot.data_ptr(), rew.data_ptr(), *common)
-    else:
-        assert tuple(maps.shape) == (W, n, dnet.om_cols) and maps.is_contiguous()
-        value_net.decide_om(dnet, W, A, n, rot.data_ptr(), maps.data_ptr(), rew.data_ptr(), *common)
-    torch.cuda.synchronize()
-    return vals.cpu().numpy(), pick.cpu().numpy(), act.cpu().numpy()
-
-
 @pytest.fixture(scope="module")
 def twins():
     """(with_global, headed) -> (SARL DeviceNet, its OM twin's DeviceNet): the same weights, zeros on the map columns of mlp1's first layer"""

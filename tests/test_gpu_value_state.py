@@ -15,6 +15,7 @@ from test_gpu_value_policy import REL_BAR, _batched, _calm, _ready
 from test_gpu_value_worlds import GAMMA, HEADED, NETS, worlds
 from test_value_policy_cpu import make_policy, seeded_weights
 from test_value_state_cpu import ROW_SLACK, g19, g19_policy, g19_reference_row_error
+from value_calls import _up, decide_call, lookahead_call, same_bits, state_call
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,6 @@ DT = 0.25
 # W: around one job of 32 worlds and into a third (65), so jobs end ragged
 N_LIST = (1, 5, 25, 32, 33, 70)
 W_LIST = (1, 31, 32, 33, 65)
-GUARD = (5, 8)          # floats before / behind the rows: the output starts 4 bytes behind a 16-byte boundary
 
 
 @pytest.fixture(scope="module")
@@ -59,40 +59,6 @@ def cases():
     return get
 
 
-def _up(a, dtype=None):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
-
-
-def state_call(dnet, cur, rob, rewards=None, dt=0.0, rows=True):
-    """cs_value_net_state on host arrays: (values [W], rows [W, n, cols] or None) as numpy.  The rows are written between guard floats,
-    which must come back untouched: the output is dense, nothing is stored for the tile's padded columns or rows."""
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    d_cur, d_rob = _up(cur), _up(rob)
-    W, n, headed = cur.shape[0], cur.shape[1], cur.shape[2] == 7
-    cols = 15 if headed else 13
-    vals = torch.full((W,), np.nan, device="cuda")
-    flat = torch.full((GUARD[0] + W * n * cols + GUARD[1],), -77.0, device="cuda") if rows else None
-    d_rew = None if rewards is None else _up(rewards)
-    value_net.state_values(dnet, W, n, headed, d_cur.data_ptr(), d_rob.data_ptr(), rob.shape[1], None if d_rew is None else d_rew.data_ptr(), GAMMA, dt,
-                           None if flat is None else flat.data_ptr() + 4 * GUARD[0], vals.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    out = None
-    if rows:
-        flat = flat.cpu().numpy()
-        assert np.all(flat[:GUARD[0]] == F32(-77.0)) and np.all(flat[-GUARD[1]:] == F32(-77.0)), "a store outside [W, n, cols]"
-        out = flat[GUARD[0]:-GUARD[1]].reshape(W, n, cols)
-    return vals.cpu().numpy(), out
-
-
 def next_from_current(cur):
     """The humans' current rows where cs_lookahead reads their next ones: (px, py, vx, vy), or (px, py, theta, vx, vy, omega)"""
     return np.ascontiguousarray(cur[..., [0, 1, 5, 2, 3, 6]] if cur.shape[-1] == 7 else cur[..., :4])
@@ -100,29 +66,13 @@ def next_from_current(cur):
 
 def lookahead_rows(cur, rob, w):
     """value_net.lookahead for world w alone (W = 1, A = 1): action = the robot's velocity, next = current, dt = 0 -> [n, cols]"""
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    rot, _ = value_net.lookahead(_up(rob[w:w + 1, 2:4]), _up(next_from_current(cur[w:w + 1])), _up(cur[w:w + 1]), _up(rob[w:w + 1]), 0.0,
-                                 torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
+    rot, _ = lookahead_call(rob[w:w + 1, 2:4], next_from_current(cur[w:w + 1]), cur[w:w + 1], rob[w:w + 1], 0.0)
     return rot.cpu().numpy()[0, 0]
 
 
 def decide_on_rows(dnet, rows, rob, rewards, dt):
     """value_net.decide (cs_value_net_decide) with A = 1 on rows [W, n, cols]: values [W]"""
-    import torch
-
-    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
-
-    W, n, _ = rows.shape
-    d_rows, d_rob, d_rew, d_act = _up(rows), _up(rob), _up(rewards.reshape(W, 1)), _up(np.zeros((1, 2), F32))
-    vals, pick, act = torch.full((W, 1), np.nan, device="cuda"), torch.zeros(W, dtype=torch.int32, device="cuda"), torch.zeros((W, 2), device="cuda")
-    value_net.decide(dnet, W, 1, n, d_rows.data_ptr(), d_rew.data_ptr(), d_act.data_ptr(), d_rob.data_ptr(), rob.shape[1], GAMMA, dt, None,
-                     vals.data_ptr(), pick.data_ptr(), act.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return vals.cpu().numpy()[:, 0]
+    return decide_call(dnet, rows[:, None], rewards.reshape(-1, 1), np.zeros((1, 2), F32), rob, gamma=GAMMA, dt=dt)[0][:, 0]
 
 
 def torch_values(pol, rows):

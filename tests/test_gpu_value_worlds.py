@@ -11,6 +11,7 @@ import pytest
 from test_gpu_value_policy import REL_BAR, _batched, _calm, _compare, _ready
 from test_policy_seam import _groups
 from test_value_policy_cpu import fixture_state_dict, make_policy, seeded_weights
+from value_calls import _up
 
 pytestmark = pytest.mark.gpu
 
@@ -97,12 +98,6 @@ def nets():
         return made[net, headed]
 
     return get
-
-
-def _up(a, dtype=None):
-    import torch
-
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
 def _outputs(W, A):
