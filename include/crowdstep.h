@@ -725,6 +725,39 @@ int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_wei
                              int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_lstm_om  cs_value_net_decide_lstm for OM-LSTM-RL (lstm_rl.with_om = true; csrc/value_net_lstm.hip
+ *   k_value_net_lstm_om): the rows of the recurrent network carry om_cols occupancy-map columns behind the rotated ones.
+ *   With perm_a the evaluation order of (w, a) -- cs_value_net_decide_lstm's rank rule on column 11 of that pair's rows, the identity
+ *   for sorted_by_distance = 0 -- the input row at step t of (w, a) is d_rotated[w][a][perm_a[t]][0..cols) followed by
+ *   d_maps[w][m][0..om_cols), d_maps [W][n][om_cols] being cs_occupancy_maps' output, read in place and never expanded A-fold:
+ *     map_order = CS_VN_MAPS_OWN           m = perm_a[t]: every human beside its own map (what multi_human_rl.py:115-128 transform stores
+ *                                          and a trainer evaluates);
+ *     map_order = CS_VN_MAPS_FIRST_ACTION  m = perm_0[t], perm_0 the order of (w, action index 0) under the same rule, computed from that
+ *                                          pair's own rows of d_rotated whichever tile they lie in: the reference's serial decision
+ *                                          (multi_human_rl.py:75-78 builds the maps once, on the first action's sorted humans, and attaches
+ *                                          them by position to every later action's rows).
+ *   With sorted_by_distance = 0 both orders are the identity.  Network 1: the LSTM reads cols + om_cols columns, its gates
+ *   ceil(H / 8) + ceil((cols + om_cols) / 8) k-groups in the same descending order; network 2: mlp1's first layer reads cols + om_cols
+ *   columns, the gates are cs_value_net_decide_lstm's.  Everything else -- dims, the NaN key, the self state from the first row in
+ *   evaluation order, the pick, d_override, reach-destination, the two kernels on `stream` -- is cs_value_net_decide_lstm's.  A world
+ *   alone (W = 1, all A actions) gives the bits it gives inside any batch; with CS_VN_MAPS_OWN a single (world, action) does too.  No
+ *   atomics.  float32.  With all-zero map weights and finite maps the values equal cs_value_net_decide_lstm's bit for bit.
+ * cs_value_net_pack_lstm_om  (host only) cs_value_net_pack_lstm's layout with the one wider K: weight_ih (network 1) or mlp1's first
+ *   weight (network 2) is [..][cols + om_cols].
+ *   Further errors of both (CS_ERR_ARG, before any device call): om_cols < 1, cols + om_cols > 256; of the decision a null d_maps,
+ *   map_order outside 0..1, and the LDS-fit refusal made for this kernel's own LDS (joint rows or gather tile of cols + om_cols rounded
+ *   up to 8, plus 4 floats; the keys and the order of action 0, 2 x 32 n words).
+ */
+enum { CS_VN_MAPS_OWN = 0, CS_VN_MAPS_FIRST_ACTION = 1 };
+int cs_value_net_pack_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, const float* const* params, float* blob,
+                              size_t* n_floats);
+int cs_value_net_decide_lstm_om(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                                int cols, int om_cols, int sorted_by_distance, int map_order, const float* d_rotated,
+                                const float* d_maps /* [W][n][om_cols] */, const float* d_rewards, const float* d_actions,
+                                const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
+                                float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * Float64 worlds (csrc/sfmstep_f64.hip): the SFM / HSFM substep in the reference's own precision (PRECISION = np.float64),
  * an opt-in arithmetic beside the float32 entries above.  cs_worlds_f64 carries the fields of cs_worlds that apply, with double buffers:
  * the state is CS_LAYOUT_AOS [W][rows][13] only, a world holds up to 64 rows (one wavefront per world), the types are 0..8, the robot is

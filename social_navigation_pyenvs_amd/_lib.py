@@ -167,6 +167,8 @@ ABI = {
     "cs_value_net_decide_om": (I, [I, P, I, P, Z, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_pack_lstm": (I, [P, I, I, P, P, P]),
     "cs_value_net_decide_lstm": (I, [P, I, P, Z, I, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_pack_lstm_om": (I, [P, I, I, I, P, P, P]),
+    "cs_value_net_decide_lstm_om": (I, [P, I, P, Z, I, I, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_step_f64": (I, [WORLDS64, D, I, P, P]),
     "cs_update_humans_parallel_f64": (I, [WORLDS64, D, P, P]),
     "cs_peek_f64": (I, [WORLDS64, D, P, P]),

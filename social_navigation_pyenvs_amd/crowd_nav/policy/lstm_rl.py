@@ -67,8 +67,8 @@ class LstmRL(MultiHumanRL):
         section = self.config_section
         self.with_om = config.getboolean(section, "with_om")
         if self.with_om:
-            raise NotImplementedError("OM-LSTM-RL (lstm_rl.with_om = true) is not available: the recurrent decision kernel reads the 13 | 15 rotated "
-                                      "columns only; rows widened by occupancy maps have no LSTM kernel")
+            raise NotImplementedError("OM-LSTM-RL (lstm_rl.with_om = true) is a policy of its own here: the rows widened by the humans' occupancy "
+                                      "maps have their own recurrent decision kernel; build it with policy_factory[\"om_lstm_rl\"]")
         mlp_dims = width_list(config.get(section, "mlp2_dims"))
         hidden = config.getint(section, "global_state_dim")
         self.with_interaction_module = config.getboolean(section, "with_interaction_module")

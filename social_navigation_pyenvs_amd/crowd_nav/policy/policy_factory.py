@@ -2,6 +2,7 @@
 from ..policy_no_train.policy_factory import policy_factory as _no_train
 from .cadrl import CADRL
 from .lstm_rl import LstmRL
+from .om_lstm_rl import OMLstmRL
 from .om_sarl import OMSARL
 from .sarl import SARL
 
@@ -17,3 +18,4 @@ policy_factory["sarl"] = SARL
 policy_factory["om_sarl"] = OMSARL
 policy_factory["lstm_rl"] = lstm_rl
 policy_factory["lstm_rl_device"] = LstmRL
+policy_factory["om_lstm_rl"] = OMLstmRL

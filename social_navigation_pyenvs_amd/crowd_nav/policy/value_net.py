@@ -18,8 +18,14 @@ LSTM-RL (crowd_nav/policy/lstm_rl.py) has a kernel of its own (cs_value_net_deci
 cs_value_net_pack_lstm, ``decide_lstm`` is the library call and ``decide_for_worlds`` runs lookahead -> decide_lstm(sorted_by_distance=1);
 ``state_values_for_worlds`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor only.
 
-Which entries a network uses, with which arguments, and which modes it may run in is stated once, in the three rows of ``Family``
-(FEED_FORWARD, MAPPED, RECURRENT); a ``DeviceNet`` holds its row, a policy class names its own, and ``pack``, ``decide_rows``,
+OM-LSTM-RL (crowd_nav/policy/om_lstm_rl.py: lstm_rl.with_om = true) is the recurrent network on rows widened by the maps: a CS_VN_LSTM
+``DeviceNet`` with ``om_cols`` > 0 packs through cs_value_net_pack_lstm_om and decides through cs_value_net_decide_lstm_om
+(``decide_lstm_om``), which takes the maps, sorted_by_distance and ``map_order`` -- which map a step's row is paired with: MAP_ORDERS'
+"reference" (the map at that place of action 0's order, what the reference's serial decision does) or "own" (every human beside its own map,
+what ``transform`` stores).
+
+Which entries a network uses, with which arguments, and which modes it may run in is stated once, in the four rows of ``Family``
+(FEED_FORWARD, MAPPED, RECURRENT, RECURRENT_MAPPED); a ``DeviceNet`` holds its row, a policy class names its own, and ``pack``, ``decide_rows``,
 ``decide_for_worlds``, ``state_values_for_worlds`` and ``check_mode`` ask it.
 
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
@@ -35,6 +41,7 @@ import numpy as np
 
 CS_VN_CADRL, CS_VN_SARL = 0, 1     # include/crowdstep.h
 CS_VN_LSTM = "lstm"                # this module's tag of an LSTM-RL network: the C entries of that network take no `kind`
+MAP_ORDERS = frozen({"own": 0, "reference": 1})      # include/crowdstep.h CS_VN_MAPS_OWN, CS_VN_MAPS_FIRST_ACTION
 PRECISIONS = ("f32", "bf16")
 DECISION_INPUTS = ("tensor", "fused")
 
@@ -51,7 +58,8 @@ class Family(NamedTuple):
     pack: frozen            # precision -> (pack entry, what it counts its blob in)
     takes_kind: bool        # the C entries open with a `kind`
     decide: frozen          # precision -> the decide entry on the look-ahead tensor
-    decide_int: str         # the integer that entry takes behind cols: "", "om_cols" or "sorted_by_distance"
+    decide_int: str         # the integers that entry takes behind cols: "", "om_cols", "sorted_by_distance" or "om_cols sorted_by_distance
+                            # map_order"
     takes_maps: bool        # that entry takes the maps behind rotated; the pack entry om_cols behind cols
     modes: tuple            # the (decision input, precision) pairs the family runs
     refusal: str            # the sentence every other pair is refused with ({0!r}: the input, {1!r}: the precision)
@@ -83,11 +91,26 @@ RECURRENT = Family(
     refusal='decision input {0!r} with decision precision {1!r} for a recurrent network: LSTM-RL has the one kernel, float32 on the '
             'look-ahead tensor; it decides with "tensor" and "f32"',
     min_humans=1, state_launch=False)
+RECURRENT_MAPPED = Family(
+    pack=frozen({"f32": ("cs_value_net_pack_lstm_om", np.float32)}), takes_kind=False,
+    decide=frozen({"f32": "cs_value_net_decide_lstm_om"}), decide_int="om_cols sorted_by_distance map_order", takes_maps=True,
+    modes=(("tensor", "f32"),),
+    refusal='decision input {0!r} with decision precision {1!r} for a recurrent network with occupancy-map columns: OM-LSTM-RL has the one '
+            'kernel, float32 on the look-ahead tensor and the maps; it decides with "tensor" and "f32"',
+    min_humans=2, state_launch=False)
 
 
 def family_of(kind, om_cols=0):
     """The family of a description (``describe``'s kind) with ``om_cols`` map columns."""
-    return RECURRENT if kind == CS_VN_LSTM else MAPPED if om_cols else FEED_FORWARD
+    if kind == CS_VN_LSTM:
+        return RECURRENT_MAPPED if om_cols else RECURRENT
+    return MAPPED if om_cols else FEED_FORWARD
+
+
+def check_map_order(map_order):
+    if map_order not in MAP_ORDERS:
+        raise ValueError(f"map order {map_order!r}: one of {', '.join(map(repr, sorted(MAP_ORDERS, reverse=True)))}")
+    return map_order
 
 
 def check_mode(family, decision_input, precision):
@@ -105,7 +128,7 @@ def check_decision_input(decision_input, precision, om_cols=0, recurrent=False):
     """``check_mode`` for who holds no family: "fused" (cs_value_net_decide_worlds: the rows are generated in the kernel, no look-ahead
     tensor) exists for the float32 arithmetic only.  A network with occupancy-map columns (``om_cols`` > 0) has the one kernel
     cs_value_net_decide_om: float32 on the look-ahead tensor.  So has a ``recurrent`` one (LSTM-RL: cs_value_net_decide_lstm)."""
-    return check_mode(RECURRENT if recurrent else MAPPED if om_cols else FEED_FORWARD, decision_input, precision)
+    return check_mode(family_of(CS_VN_LSTM if recurrent else CS_VN_SARL, om_cols), decision_input, precision)
 
 
 def _linears(seq):
@@ -143,14 +166,12 @@ def layer_params(layer):
 def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     """The kernel's weight blob from [weight_0, bias_0, weight_1, ...] float32 arrays: float32 numpy for "f32", the bytes (uint8 numpy)
     of cs_value_net_pack_bf16's layout for "bf16"; with ``om_cols`` > 0 cs_value_net_pack_om's (float32 only: mlp1 reads cols + om_cols
-    columns); for CS_VN_LSTM cs_value_net_pack_lstm's (float32 only; the LSTM's four arrays between mlp1's and mlp's).  Host only: no GPU
-    needed."""
+    columns); for CS_VN_LSTM cs_value_net_pack_lstm's (float32 only; the LSTM's four arrays between mlp1's and mlp's), with ``om_cols`` > 0
+    cs_value_net_pack_lstm_om's.  Host only: no GPU needed."""
     from ... import _lib
 
     family = family_of(kind, om_cols)
     check_mode(family, "tensor", precision)
-    if family is RECURRENT and om_cols:
-        raise ValueError("an LSTM-RL network reads the rotated columns only: no occupancy-map columns")
     entry, unit = family.pack[check_precision(precision)]
     dims = np.ascontiguousarray(dims, np.int32)
     lead = family.lead(kind) + (dims.ctypes.data, len(dims), cols) + ((om_cols,) if family.takes_maps else ())
@@ -176,14 +197,16 @@ class DeviceNet:
     parameters changed (the same version-counter key for both).  ``blob`` is the float32 one.  ``om_cols`` > 0: an OM-SARL network whose
     mlp1 reads cols + om_cols columns (cs_value_net_pack_om's blob); ``om_grid`` = (cell_num, cell_size, om_channel_size) of its maps;
     ``last_maps``: the maps [W, n, om_cols] of its last ``decide_for_worlds``.  ``lstm``: an LSTM-RL network (cs_value_net_pack_lstm's blob,
-    float32 only; the version key covers the LSTM's four tensors).  ``family``: its row of the family table, which says all of that."""
+    float32 only; the version key covers the LSTM's four tensors); with ``om_cols`` > 0 an OM-LSTM-RL one, ``map_order`` (MAP_ORDERS) the
+    pairing of its decisions.  ``family``: its row of the family table, which says all of that."""
 
-    def __init__(self, model, cols, om_cols=0, om_grid=None):
+    def __init__(self, model, cols, om_cols=0, om_grid=None, map_order="reference"):
         self.model, self.cols, self.om_cols, self.om_grid = model, int(cols), int(om_cols), om_grid
+        self.map_order = check_map_order(map_order)
         self.last_maps = None
         self.kind, self.dims, self.layers = describe(model)
         self.family = family_of(self.kind, self.om_cols)
-        self.lstm = self.family is RECURRENT
+        self.lstm = self.kind == CS_VN_LSTM
         self._keys = dict.fromkeys(PRECISIONS)
         self.blobs = dict.fromkeys(PRECISIONS)
 
@@ -220,14 +243,18 @@ def _head(lead, dims, blob):
 
 def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):
     """The tensor decide entry of `net`'s family on device pointers (ints).  `extra`: what that entry takes beyond
-    cs_value_net_decide's arguments -- the maps [W][n][net.om_cols], or sorted_by_distance; `tail`: rewards, actions, robot, robot_stride,
-    gamma, dt, override, values, choice, action_out, stream."""
+    cs_value_net_decide's arguments -- the maps [W][n][net.om_cols], or sorted_by_distance, or the pair (maps, sorted_by_distance) for a
+    family that takes both (``net.map_order`` goes with them); `tail`: rewards, actions, robot, robot_stride, gamma, dt, override, values,
+    choice, action_out, stream."""
     from ... import _lib
 
     family = net.family
     head = net.head(family.decide["f32"].removeprefix("cs_value_net_"), precision)
-    behind_cols = {"": (), "om_cols": (net.om_cols,), "sorted_by_distance": (int(bool(extra)),)}[family.decide_int]
-    behind_rotated = (extra,) if family.takes_maps else ()
+    both = "sorted_by_distance" in family.decide_int and family.takes_maps
+    maps, in_order = extra if both else (extra, extra)
+    given = {"om_cols": lambda: net.om_cols, "sorted_by_distance": lambda: int(bool(in_order)), "map_order": lambda: MAP_ORDERS[net.map_order]}
+    behind_cols = tuple(given[name]() for name in family.decide_int.split())
+    behind_rotated = (maps,) if family.takes_maps else ()
     _lib.check(getattr(_lib.load(), family.decide[precision])(*head, W, A, n, net.cols, *behind_cols, rotated, *behind_rotated, *tail))
 
 
@@ -278,13 +305,25 @@ def decide_lstm(net, W, A, n, sorted_by_distance, rotated, rewards, actions, rob
                 action_out, stream)
 
 
+def decide_lstm_om(net, W, A, n, sorted_by_distance, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                   action_out, stream=None):
+    """cs_value_net_decide_lstm_om on device pointers (ints): ``decide_lstm`` for a DeviceNet of an OM-LSTM-RL network, maps
+    [W][n][net.om_cols] paired with the rows by ``net.map_order``."""
+    if net.family is not RECURRENT_MAPPED:
+        raise ValueError("decide_lstm_om: the network is not an LSTM-RL one with occupancy-map columns (DeviceNet(model, cols, om_cols))")
+    decide_rows(net, W, A, n, rotated, (maps, sorted_by_distance), rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                action_out, stream)
+
+
 def _extra_input(net, humans, vel_col, in_order, stream):
     """What ``decide_rows`` takes as `extra` for `net`: (the argument, the tensor behind it or None) -- the maps of `humans` [W, n, stride]
-    for a family with maps (a launch), `in_order` as sorted_by_distance for a recurrent one, nothing otherwise."""
+    for a family with maps (a launch), `in_order` as sorted_by_distance for a recurrent one, the pair for a family with both, nothing
+    otherwise."""
+    ordered = "sorted_by_distance" in net.family.decide_int
     if net.family.takes_maps:
         maps = maps_of(humans, vel_col, net.om_grid, stream)
-        return maps.data_ptr(), maps
-    return (in_order if net.family.decide_int == "sorted_by_distance" else None), None
+        return ((maps.data_ptr(), in_order) if ordered else maps.data_ptr()), maps
+    return (in_order if ordered else None), None
 
 
 _ROWS_BLOB = {}
@@ -382,7 +421,8 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
-    decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order; a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
+    decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order (with map columns: lookahead,
+    occupancy_maps on the NEXT humans, decide_lstm_om in that order with the net's ``map_order``); a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
     branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
     "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]

@@ -22,6 +22,14 @@
 //               weights in registers across steps and tiles (k_value_net_lstm<true, .>); wider ones read them from the blob at every step
 //               (<false, .>).  Same operations in the same order.  The second template argument is network 2's mlp1 in the step loop.
 //   end         mlp on the 32 joint rows (self state, h_n) as one 32-row block, the action value, one float per sequence goes out.
+//   map columns OM-LSTM-RL (lstm_rl.with_om = true; cs_value_net_decide_lstm_om) is the same body, value_net_lstm_body.inc, included a second
+//               time as k_value_net_lstm_om<WREG, MLP1>: a row is the rotated row followed by the om_cols columns of a map row of its world,
+//               d_maps [W][n][om_cols] read in place.  Which map: the row's own (CS_VN_MAPS_OWN) or the one at that place of the order of the
+//               world's action 0 (CS_VN_MAPS_FIRST_ACTION, the reference's serial decision), for which every workgroup ranks the rows of its
+//               sequences' (world, action 0) itself: a second key array and rank pass in LDS.  Network 1's joint row and gate k range widen,
+//               network 2's gather tile and mlp1's first layer do; the register-resident build holds 15 k-groups (16 would leave one wave per
+//               SIMD: DESIGN.md 4.5), and network 1's P buffer lies over the joint rows, dead by then, to keep two workgroups a CU.  The four
+//               builds of k_value_net_lstm are the preprocessor's LSTM_OM 0 text: the instructions they had before.
 //
 // Numerics: float32.  Every gate pre-activation is one fixed fmaf chain from b_ih + b_hh (summed in float32 by the pack) over the k-groups in
 // descending order (x_t's, then h's); sigmoid(x) = rcp(1 + exp2(-x * log2 e)), tanh(x) = sign(x) * (1 - e) * rcp(1 + e) with e = exp2(-2 |x| * log2 e) on
@@ -36,6 +44,7 @@ namespace {
 
 constexpr int LSTM_MAX_N = CS_VN_LSTM_MAX_N;
 constexpr int RB = 2, RKG = 14;    // register-resident gate weights: blocks a wavefront, k-groups a block
+constexpr int RKG_OM = 15;         // ... of the kernel with map columns: the reference's [om] defaults are 7 blocks x (7 + 8) k-groups
 constexpr int GB = 8;              // blocks a wavefront at the widest H (256 / 8 / 4)
 
 struct LstmPlan {
@@ -46,17 +55,20 @@ struct LstmPlan {
 
 struct LstmLds { int key, perm, X, XH, P, Q, J, LT, total; };
 
-inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& q)
+// om_cols: the occupancy-map columns behind the rotated ones in a row (cs_value_net_decide_lstm_om; 0 with om = false: none)
+inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& q, bool om = false, int om_cols = 0)
 {
     memset(&q, 0, sizeof q);
     VnPlan& p = q.v;
     if (cols != 13 && cols != 15) return fail(CS_ERR_ARG, "rotated rows have 13 or 15 columns");
+    if (om && om_cols < 1) return fail(CS_ERR_ARG, "om_cols must be at least 1");
+    if (om && cols + om_cols > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "rotated and map columns together exceed a layer's 256 inputs");
     if (!dims || n_dims < 4) return fail(CS_ERR_ARG, "null or empty layer description");
     p.cols = cols;
     q.H = dims[0];
     if (q.H < 1 || q.H > VN_MAX_WIDTH) return fail(CS_ERR_ARG, "the LSTM's hidden width must be between 1 and 256");
     q.hpad = up(q.H, 8);
-    int at = 1, off = 0, k1 = cols;
+    int at = 1, off = 0, k1 = cols + om_cols;
     for (int c = 0; c < 2; ++c) {
         if (at >= n_dims) return fail(CS_ERR_ARG, "layer description ends early");
         const int nl = dims[at++];
@@ -87,13 +99,15 @@ inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& 
     p.c0[2] = p.n_layers;
     if (at != n_dims) return fail(CS_ERR_ARG, "layer description has trailing entries");
     set_ld_pq(p);
-    q.ld_xh = q.hpad + (p.c0[1] > 0 ? up(q.xin, 32) : 16) + 4;        // (mlp1's last layer stores whole 32-column blocks)
+    q.ld_xh = q.hpad + (p.c0[1] > 0 ? up(q.xin, 32) : up(cols + om_cols, 8)) + 4;        // (mlp1's last layer stores whole 32-column blocks)
     p.ld_j = up(SELF_DIM + q.H, 8) + 4;
     p.total_floats = off;
     return CS_OK;
 }
 
-inline LstmLds lstm_lds_map(const LstmPlan& q, int n)
+// ldg: the row stride of network 2's gather tile.  share_p: network 1's P lies over the joint rows, which are dead when mlp starts (h_n has
+// gone to J, a barrier behind it) -- the kernel with map columns asks for it where P fits, to stay at two workgroups a CU with its wider rows
+inline LstmLds lstm_lds_map(const LstmPlan& q, int n, int ldg = LDX, bool share_p = false)
 {
     LstmLds m{};
     int o = 0;
@@ -101,8 +115,8 @@ inline LstmLds lstm_lds_map(const LstmPlan& q, int n)
     m.key = take(TILE_M * n);
     m.perm = take(TILE_M * n);
     m.XH = take(2 * TILE_M * q.ld_xh);
-    m.X = q.v.c0[1] > 0 ? take(2 * TILE_M * LDX) : m.XH;
-    m.P = take(TILE_M * q.v.ld_pq);
+    m.X = q.v.c0[1] > 0 ? take(2 * TILE_M * ldg) : m.XH;
+    m.P = share_p && q.v.c0[1] == 0 && q.v.ld_pq <= 2 * q.ld_xh ? m.XH : take(TILE_M * q.v.ld_pq);
     m.Q = take(TILE_M * q.v.ld_pq);
     m.J = take(JROWS * q.v.ld_j);
     m.LT = take(VN_MAX_LAYERS * 8);
@@ -158,6 +172,29 @@ __device__ __forceinline__ void lstm_gather(float* X, int ld, const float* __res
         const int s = i >> 4, c = i & 15;
         float v = 0.0f;
         if (s < ng && c < cols) v = rotated[((gbase + s) * n + perm[s * n + t]) * cols + c];
+        X[s * ld + c] = v;
+    }
+}
+
+// What the rows with map columns add to a launch (cs_value_net_decide_lstm_om): the maps [W][n][om_cols], which map a step pairs with its
+// row, xw = cols + om_cols rounded up to 8 (the columns a gathered row holds) and where the keys and the order of a world's action 0 lie in LDS.
+struct LstmOm { const float* maps; int om_cols, map_order, xw, key0, perm0; };
+
+// lstm_gather for such rows, eight lanes a sequence: rotated[g][perm[s][t]][0..cols) | maps[world of g][mperm[s][t]][0..om_cols), zeros up to xw
+__device__ __forceinline__ void lstm_gather_om(float* X, int ld, const float* __restrict__ rotated, const LstmOm& om, const int* perm, const int* mperm,
+                                               long gbase, int ng, int A, int n, int cols, int t)
+{
+    const int s = threadIdx.x >> 3;
+    const bool live = s < ng;
+    long rrow = 0, mrow = 0;
+    if (live) {
+        rrow = ((gbase + s) * n + perm[s * n + t]) * cols;
+        mrow = (((gbase + s) / A) * n + mperm[s * n + t]) * om.om_cols;
+    }
+    for (int c = threadIdx.x & 7; c < om.xw; c += 8) {
+        float v = 0.0f;
+        if (live && c < cols) v = rotated[rrow + c];
+        else if (live && c < cols + om.om_cols) v = om.maps[mrow + c - cols];
         X[s * ld + c] = v;
     }
 }
@@ -236,150 +273,27 @@ __global__ __launch_bounds__(NT) void k_value_net_lstm(LstmPlan q, LstmLds m, co
                                                        const float* __restrict__ rotated, const float* __restrict__ rewards,
                                                        const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
 {
-    extern __shared__ float lds[];
-    constexpr int NB = WREG ? RB : GB;
-    const VnPlan& p = q.v;
-    float *P = lds + m.P, *Q = lds + m.Q, *J = lds + m.J;
-    unsigned* key = reinterpret_cast<unsigned*>(lds + m.key);
-    int* perm = reinterpret_cast<int*>(lds + m.perm);
-    float* XH = lds + m.XH;                                 // [2][32][ld_xh]: a sequence's joint row (h of the step before | x_t)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5, li = lane & 31;
-    const int row8 = tid >> 3;
-    const int cols = p.cols, H = q.H, hpad = q.hpad, ldxh = q.ld_xh, KG = q.g.kg_total;
-    const int nbw = (q.g.ncb - wave + 3) >> 2;              // this wavefront's blocks: wave, wave + 4, ...
-    constexpr bool with_mlp1 = MLP1;
-    // where the gather puts a step's rows: network 1 straight into the joint rows' x part, network 2 into a tile of their own for mlp1
-    float* G = with_mlp1 ? lds + m.X : XH + hpad;
-    const int ldg = with_mlp1 ? LDX : ldxh, gbuf = TILE_M * ldg;
-    const float4* gw = reinterpret_cast<const float4*>(wb + q.g.w_off) + lane;
-    int out_ld;
+#define LSTM_OM 0
+#include "value_net_lstm_body.inc"
+#undef LSTM_OM
+}
 
-    int* ltab = reinterpret_cast<int*>(lds + m.LT);
-    if (tid == 0)
-        for (int l = 0; l < p.n_layers; ++l) {
-            int* e = ltab + l * LT_STRIDE;
-            e[LT_N] = p.L[l].N; e[LT_KG] = p.L[l].kg_total; e[LT_NCB] = p.L[l].ncb; e[LT_RELU] = p.L[l].relu; e[LT_W] = p.L[l].w_off; e[LT_B] = p.L[l].b_off;
-        }
-    // (the first barrier of the first job publishes the table)
-
-    float4 wreg[RB][RKG];
-    if constexpr (WREG) {
-#pragma unroll
-        for (int bi = 0; bi < RB; ++bi)
-#pragma unroll
-            for (int kg = 0; kg < RKG; ++kg) {
-                const int at = ((tid >> 6) + 4 * bi) * KG + kg;    // (clamped: what lies beyond the wavefront's blocks and k-groups is never used)
-                wreg[bi][kg] = gw[(at < q.g.ncb * KG ? at : 0) * 64];
-            }
-    }
-
-    for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
-        const long gbase = (long)job * JROWS;
-        const int ng = NG - gbase < JROWS ? (int)(NG - gbase) : JROWS;
-        for (int i = tid; i < ng * n; i += NT) key[i] = lstm_key(rotated[(gbase * n + i) * cols + 11]);
-        for (int i = tid; i < JROWS * p.ld_j; i += NT) J[i] = 0.0f;
-        for (int i = tid; i < TILE_M * ldxh; i += NT) XH[i] = 0.0f;                                  // h0 = 0
-        __syncthreads();
-        for (int j = tid & 7; j < n && row8 < ng; j += 8) {          // eight lanes a sequence
-            int rank = j;
-            if (sorted) {
-                const unsigned kj = key[row8 * n + j];
-                rank = 0;
-#pragma unroll 1
-                for (int k = 0; k < n; ++k) {
-                    const unsigned kk = key[row8 * n + k];
-                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
-                }
-            }
-            perm[row8 * n + rank] = j;
-        }
-        __syncthreads();
-        lstm_gather(G, ldg, rotated, perm, gbase, ng, n, cols, 0);
-        float c[NB][4];
-#pragma unroll
-        for (int bi = 0; bi < NB; ++bi)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) c[bi][u] = 0.0f;
-        __syncthreads();
-        // lstm_rl.py:25 / :53: the self state is read from the first row in evaluation order
-        if (row8 < ng && (tid & 7) < SELF_DIM) J[row8 * p.ld_j + (tid & 7)] = G[row8 * ldg + (tid & 7)];
-
-        for (int t = 0; t < n; ++t) {
-            float* cur = XH + (t & 1) * TILE_M * ldxh;
-            float* nxt = XH + ((t + 1) & 1) * TILE_M * ldxh;
-            if (t + 1 < n) lstm_gather(G + ((t + 1) & 1) * (with_mlp1 ? gbuf : TILE_M * ldxh), ldg, rotated, perm, gbase, ng, n, cols, t + 1);
-            if constexpr (with_mlp1) lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, LDX, cur + hpad, ldxh, out_ld);
-            const float* brow = cur + li * ldxh + 4 * hh;
-#pragma unroll
-            for (int bi = 0; bi < NB; ++bi) {
-                if (bi >= nbw) break;
-                const int blk = wave + 4 * bi;
-                f32x16 acc;
-                const float* bias = wb + q.g.b_off + blk * 32 + 4 * hh;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = bias[(r & 3) + 8 * (r >> 2)];
-                // the k-groups in descending order (x_t's, then h's), whichever kernel
-                if constexpr (WREG) {
-                    switch (KG) {
-                    case 14: LSTM_KSTEP(wreg[bi][13], 13) [[fallthrough]];
-                    case 13: LSTM_KSTEP(wreg[bi][12], 12) [[fallthrough]];
-                    case 12: LSTM_KSTEP(wreg[bi][11], 11) [[fallthrough]];
-                    case 11: LSTM_KSTEP(wreg[bi][10], 10) [[fallthrough]];
-                    case 10: LSTM_KSTEP(wreg[bi][9], 9) [[fallthrough]];
-                    case 9: LSTM_KSTEP(wreg[bi][8], 8) [[fallthrough]];
-                    case 8: LSTM_KSTEP(wreg[bi][7], 7) [[fallthrough]];
-                    case 7: LSTM_KSTEP(wreg[bi][6], 6) [[fallthrough]];
-                    case 6: LSTM_KSTEP(wreg[bi][5], 5) [[fallthrough]];
-                    case 5: LSTM_KSTEP(wreg[bi][4], 4) [[fallthrough]];
-                    case 4: LSTM_KSTEP(wreg[bi][3], 3) [[fallthrough]];
-                    case 3: LSTM_KSTEP(wreg[bi][2], 2) [[fallthrough]];
-                    default: LSTM_KSTEP(wreg[bi][1], 1) LSTM_KSTEP(wreg[bi][0], 0)
-                    }
-                } else {
-                    const float4* w = gw + (long)blk * KG * 64;
-                    float4 nw = w[(long)(KG - 1) * 64];
-                    for (int kg = KG - 1; kg >= 0; --kg) {
-                        const float4 wv = nw;
-                        nw = w[(long)(kg > 0 ? kg - 1 : 0) * 64];
-                        LSTM_KSTEP(wv, kg)
-                    }
-                }
-                float hv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float ig = lstm_sigmoid(acc[u]), fg = lstm_sigmoid(acc[4 + u]), gg = lstm_tanh(acc[8 + u]), og = lstm_sigmoid(acc[12 + u]);
-                    const float cn = fg * c[bi][u] + ig * gg;
-                    c[bi][u] = cn;
-                    hv[u] = blk * 8 + 4 * hh + u < H ? og * lstm_tanh(cn) : 0.0f;      // (zero weights give 0 for finite inputs only)
-                }
-                *reinterpret_cast<float4*>(nxt + li * ldxh + blk * 8 + 4 * hh) = make_float4(hv[0], hv[1], hv[2], hv[3]);
-            }
-            __syncthreads();
-        }
-
-        const float* hn = XH + (n & 1) * TILE_M * ldxh;
-        for (int u = tid & 7; u < H; u += 8) J[row8 * p.ld_j + SELF_DIM + u] = hn[row8 * ldxh + u];
-        __syncthreads();
-        const float* out = lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
-        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
-            const long g = gbase + tid;
-            const float vpref = robot[(g / A) * rstride + 7];
-            values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
-        }
-        __syncthreads();
-    }
+// the rows widened by occupancy-map columns (OM-LSTM-RL, cs_value_net_decide_lstm_om)
+template <bool WREG, bool MLP1>
+__global__ __launch_bounds__(NT) void k_value_net_lstm_om(LstmPlan q, LstmLds m, const float* __restrict__ wb, int NG, int A, int n, int sorted,
+                                                          const float* __restrict__ rotated, const float* __restrict__ rewards,
+                                                          const float* __restrict__ robot, int rstride, float gamma, float dt,
+                                                          float* __restrict__ values, LstmOm om)
+{
+#define LSTM_OM 1
+#include "value_net_lstm_body.inc"
+#undef LSTM_OM
 }
 #undef LSTM_KSTEP
 
-} // namespace
-
-#include "value_net_pick.h"
-
-extern "C" int cs_value_net_pack_lstm(const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats)
+// the pack entries' common part
+inline int pack_lstm(const LstmPlan& q, const float* const* params, float* blob, size_t* n_floats)
 {
-    LstmPlan q;
-    const int rc = build_lstm_plan(dims, n_dims, cols, q);
-    if (rc != CS_OK) return rc;
     if (!n_floats) return fail(CS_ERR_ARG, "null argument");
     *n_floats = (size_t)q.v.total_floats;
     if (!blob) return CS_OK;
@@ -392,6 +306,27 @@ extern "C" int cs_value_net_pack_lstm(const int32_t* dims, int n_dims, int cols,
     pack_gates(q, params[2 * n1], params[2 * n1 + 1], params[2 * n1 + 2], params[2 * n1 + 3], blob);
     for (int l = n1; l < q.v.n_layers; ++l) pack_layer_f32(q.v.L[l], params[2 * l + 4], params[2 * l + 5], blob);
     return CS_OK;
+}
+
+} // namespace
+
+#include "value_net_pick.h"
+
+extern "C" int cs_value_net_pack_lstm(const int32_t* dims, int n_dims, int cols, const float* const* params, float* blob, size_t* n_floats)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    if (rc != CS_OK) return rc;
+    return pack_lstm(q, params, blob, n_floats);
+}
+
+extern "C" int cs_value_net_pack_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, const float* const* params, float* blob,
+                                         size_t* n_floats)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q, true, om_cols);
+    if (rc != CS_OK) return rc;
+    return pack_lstm(q, params, blob, n_floats);
 }
 
 extern "C" int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n, int cols,
@@ -418,6 +353,45 @@ extern "C" int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const f
         if (rc3 != CS_OK) return rc3;                                                                                                \
         hipLaunchKernelGGL((k_value_net_lstm<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n,  \
                            sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);                    \
+    }
+    if (wreg && mlp1) LSTM_LAUNCH(true, true)
+    else if (wreg) LSTM_LAUNCH(true, false)
+    else if (mlp1) LSTM_LAUNCH(false, true)
+    else LSTM_LAUNCH(false, false)
+#undef LSTM_LAUNCH
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
+}
+
+extern "C" int cs_value_net_decide_lstm_om(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n, int cols,
+                                           int om_cols, int sorted_by_distance, int map_order, const float* d_rotated, const float* d_maps,
+                                           const float* d_rewards, const float* d_actions, const float* d_robot, int robot_stride, float gamma, float dt,
+                                           const int32_t* d_override, float* d_values, int32_t* d_choice, float* d_action_out, void* stream)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q, true, om_cols);
+    if (rc != CS_OK) return rc;
+    const int rc2 = check_decide_args(q.v, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    if (rc2 != CS_OK) return rc2;
+    if (!d_maps) return fail(CS_ERR_ARG, "null argument");
+    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
+    if (map_order != CS_VN_MAPS_OWN && map_order != CS_VN_MAPS_FIRST_ACTION) return fail(CS_ERR_ARG, "map_order is CS_VN_MAPS_OWN or CS_VN_MAPS_FIRST_ACTION");
+    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm_om takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
+    LstmOm om{d_maps, om_cols, map_order, up(cols + om_cols, 8), 0, 0};
+    LstmLds m = lstm_lds_map(q, n, om.xw + 4, true);
+    om.key0 = m.total;                          // the keys and the order of action 0, behind the narrow kernel's map
+    om.perm0 = om.key0 + up(TILE_M * n, 4);
+    m.total = om.perm0 + up(TILE_M * n, 4);
+    const size_t shmem = (size_t)m.total * sizeof(float);
+    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    int NG, grid;
+    job_grid(W, A, NG, grid);
+    const bool wreg = q.g.ncb <= 4 * RB && q.g.kg_total <= RKG_OM, mlp1 = q.v.c0[1] > 0;
+#define LSTM_LAUNCH(WR, M1)                                                                                                             \
+    {                                                                                                                                   \
+        const int rc3 = grant_lds<k_value_net_lstm_om<WR, M1>>(shmem);                                                                  \
+        if (rc3 != CS_OK) return rc3;                                                                                                   \
+        hipLaunchKernelGGL((k_value_net_lstm_om<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n,  \
+                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values, om);                   \
     }
     if (wreg && mlp1) LSTM_LAUNCH(true, true)
     else if (wreg) LSTM_LAUNCH(true, false)

@@ -723,7 +723,8 @@ class BatchedSocialNavGym:
         values and choices of that decision stay readable through ``last_values_device()``.  An OM-SARL instance
         (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om, an
         LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
-        (world, action)'s humans by decreasing distance inside the kernel."""
+        (world, action)'s humans by decreasing distance inside the kernel; an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
+        the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order."""
         import torch
 
         dl = self._device_loop_state()

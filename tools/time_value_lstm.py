@@ -6,8 +6,13 @@
   (iii) what a user has without the kernel: the same torch module on the GPU, evaluated by PyTorch on the same rows, the per-action sort
         done with torch ops (argsort of column 11, flip, take_along_dim), compute_action_value and the arg-max
 
-Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5] [--only lstm|sarl|torch]
-        [--out profiles/lstm_rl_decision.txt]
+With --om the rows are OM-LSTM-RL's (lstm_rl.with_om = true: 48 map columns behind the 13 rotated ones) and three more lines are timed:
+  (iv)  cs_value_net_decide_lstm_om with the reference's pairing and with the own pairing, the maps already in HBM
+  (v)   cs_occupancy_maps on the next humans of all worlds, on its own
+  (vi)  the wide torch module on the GPU: the sort as in (iii), the maps gathered in action 0's order and concatenated by torch ops
+
+Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5]
+        [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--out profiles/lstm_rl_decision.txt]
 With --only one variant runs alone, for a `rocprofv3 --kernel-trace --stats -- python tools/time_value_lstm.py --only lstm` run of its own.
 Times are per decision of all worlds: median, minimum and maximum over --reps repetitions, each between two device events.  The work per
 decision is counted from the shapes.  Without a GPU the script fails."""
@@ -33,7 +38,7 @@ POLICY = {
 }
 
 
-def make_policy(name, network=1):
+def make_policy(name, network=1, with_om=False):
     import torch
 
     from social_navigation_pyenvs_amd.crowd_nav.policy.policy_factory import policy_factory
@@ -41,6 +46,7 @@ def make_policy(name, network=1):
     cfg = configparser.RawConfigParser()
     cfg.read_dict(POLICY)
     cfg.set("lstm_rl", "with_interaction_module", "true" if network == 2 else "false")
+    cfg.set("lstm_rl", "with_om", "true" if with_om else "false")
     pol = policy_factory[name]()
     pol.configure(cfg)
     g = torch.Generator().manual_seed(7)
@@ -56,6 +62,11 @@ def work_per_decision(model, W, A, n, cols):
     lin = lambda seq: sum(m.in_features * m.out_features for m in seq if hasattr(m, "in_features"))
     per_row = (lin(model.mlp1) if hasattr(model, "mlp1") else 0) + 4 * model.lstm.hidden_size * (model.lstm.input_size + model.lstm.hidden_size)
     return W * A * (n * per_row + lin(model.mlp)), W * A * n * cols * 4
+
+
+def gate_work(model):
+    """multiply-adds of the gates per row"""
+    return 4 * model.lstm.hidden_size * (model.lstm.input_size + model.lstm.hidden_size)
 
 
 def timed(fn, reps, warmup):
@@ -82,7 +93,8 @@ def main():
     ap.add_argument("--network", type=int, default=1, choices=(1, 2))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--only", choices=("lstm", "sarl", "torch"))
+    ap.add_argument("--only", choices=("lstm", "sarl", "torch", "om", "maps", "omtorch"))
+    ap.add_argument("--om", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
 
@@ -98,6 +110,11 @@ def main():
     A = acts.shape[0]
     lstm, sarl = make_policy("lstm_rl_device", args.network), make_policy("sarl")
     nets = {"lstm": value_net.DeviceNet(lstm.model, cols), "sarl": value_net.DeviceNet(sarl.model, cols)}
+    if args.om:
+        wide = make_policy("om_lstm_rl", args.network, with_om=True)
+        C, grid = wide.map_columns(), wide.om_grid()
+        for order in ("reference", "own"):
+            nets["om " + order] = value_net.DeviceNet(wide.model, cols, C, grid, order)
     for net in nets.values():
         net.refresh()
     stream = torch.cuda.current_stream().cuda_stream
@@ -131,11 +148,36 @@ def main():
             "sarl": ("(ii)  cs_value_net_decide, SARL", lambda: value_net.decide(nets["sarl"], W, A, n, rot.data_ptr(), *tail)),
             "torch": ("(iii) torch module on the GPU", by_torch),
         }
+        if args.om:
+            nxt = torch.rand((W, n, 4), generator=g, device="cuda") * 4 - 2
+            maps = value_net.maps_of(nxt, 2, grid, stream)
+            scratch = torch.empty_like(maps)
+
+            def wide_by_torch(chunk=512):
+                with torch.no_grad():
+                    best = torch.empty(W, dtype=torch.int64, device="cuda")
+                    for w0 in range(0, W, chunk):
+                        x = rot[w0:w0 + chunk]
+                        idx = torch.flip(torch.argsort(x[..., 11], dim=2, stable=True), dims=[2])
+                        x = torch.take_along_dim(x, idx[..., None], dim=2)
+                        m = torch.take_along_dim(maps[w0:w0 + chunk], idx[:, 0, :, None], dim=1)            # action 0's order, by position
+                        x = torch.cat([x, m[:, None].expand(-1, A, -1, -1)], dim=3).reshape(-1, n, cols + C)
+                        v = wide.model(x)[:, 0].view(-1, A)
+                        best[w0:w0 + chunk] = torch.argmax(rew[w0:w0 + chunk] + disc[w0:w0 + chunk, None] * v, dim=1)
+                    return best
+
+            om_tail = (rot.data_ptr(), maps.data_ptr()) + tail
+            variants.update({
+                "om": ("(iv)  cs_value_net_decide_lstm_om", lambda: value_net.decide_lstm_om(nets["om reference"], W, A, n, 1, *om_tail)),
+                "om own": ("(iv)  ... with the own pairing", lambda: value_net.decide_lstm_om(nets["om own"], W, A, n, 1, *om_tail)),
+                "maps": ("(v)   cs_occupancy_maps", lambda: value_net.occupancy_maps(W, n, nxt.data_ptr(), 4, 2, *grid, scratch.data_ptr(), stream)),
+                "omtorch": ("(vi)  wide torch module on the GPU", wide_by_torch),
+            })
         macs, nbytes = work_per_decision(lstm.model, W, A, n, cols)
         lines.append(f"n = {n}: {macs / 1e9:.2f} G multiply-adds, {nbytes / 1e6:.0f} MB of look-ahead rows per decision")
         results = {}
         for key, (label, fn) in variants.items():
-            if args.only and key != args.only:
+            if args.only and key.split()[0] != args.only:
                 continue
             try:
                 results[key] = timed(fn, args.reps, args.warmup)
@@ -149,6 +191,15 @@ def main():
             torch.cuda.synchronize()
             agree = float((by_torch() == pick.long()).float().mean())
             lines.append(f"  (iii) / (i) = {results['torch'][0] / results['lstm'][0]:.1f}; the two pick the same action in {100 * agree:.2f} % of the worlds")
+        if "om" in results and "lstm" in results:
+            wmacs, _ = work_per_decision(wide.model, W, A, n, cols + C)
+            lines.append(f"  (iv) / (i) = {results['om'][0] / results['lstm'][0]:.2f} in time; {wmacs / macs:.2f} in multiply-adds ({wmacs / 1e9:.2f} G), "
+                         f"{gate_work(wide.model) / gate_work(lstm.model):.2f} in the gates alone; (iv) runs at {2 * wmacs / results['om'][0] / 1e9:.1f} TFLOP/s")
+        if "om" in results and "omtorch" in results:
+            value_net.decide_lstm_om(nets["om reference"], W, A, n, 1, *om_tail)
+            torch.cuda.synchronize()
+            agree = float((wide_by_torch() == pick.long()).float().mean())
+            lines.append(f"  (vi) / (iv) = {results['omtorch'][0] / results['om'][0]:.1f}; the two pick the same action in {100 * agree:.2f} % of the worlds")
     text = "\n".join(lines)
     print(text)
     if args.out:
