@@ -659,7 +659,35 @@ int cs_value_net_state(int kind, const int32_t* dims, int n_dims, const float* d
                        float* d_values, void* stream);
 
 /*
- * cs_occupancy_maps  OM-SARL's local occupancy maps (crowd_nav/policy/multi_human_rl.py:133-187 build_occupancy_maps) for W worlds in
+ * cs_value_net_loss_grad  one optimisation step's loss and gradient for a CADRL / SARL network, fused (csrc/value_net_grad.hip, DESIGN.md
+ *   4.5): what crowd_nav/utils/trainer.py:50-71 does per minibatch before optimizer.step() -- zero_grad, outputs = model(inputs), loss =
+ *   MSELoss(outputs, values), loss.backward() -- for the networks of crowd_nav/policy/sarl.py:28-65 (mlp1, the crowd mean, the attention
+ *   chain, the masked softmax, mlp2's weighted sum, mlp3) and crowd_nav/policy/cadrl.py:116-123 (value_network), in two launches on
+ *   `stream`.  kind, dims, d_weights are what cs_value_net_decide takes (cs_value_net_pack's float32 blob for `cols`).  d_params holds
+ *   the same parameters flat, in torch's own layout: for every layer in dims' order weight [N][K] row-major, then bias [N]
+ *   (n_param_floats: cs_value_net_grad_sizes).  d_rows [B][n][cols] are B stored states (policy.transform's rows, the humans in their own
+ *   order; cols 13 or 15), d_targets [B] their target values.  CADRL's trainer stores one human's row per sample: n must be 1 for it.
+ *   d_grad (the layout of d_params; written, not accumulated) = d/dtheta mean_b (V_b - target_b)^2, d_loss the loss, d_values [B] (may be
+ *   NULL) the network's outputs: bit for bit what cs_value_net_state returns for such rows with d_rewards NULL and dt 0.  d_scratch of
+ *   n_scratch_floats (at least cs_value_net_grad_sizes' figure) holds one partial gradient per workgroup, summed in a fixed order: no
+ *   atomics, the same call gives the same bytes; the bits may depend on B.  float32.
+ *   Errors (CS_ERR_ARG, before any device call): those of cs_value_net_decide's network description, B < 1, n < 1, CADRL with n > 1,
+ *   a null pointer other than d_values, a blob or parameter array of another size, a scratch that is too small, a network whose
+ *   tile (every layer's activations of 32 rows and two gradient buffers) does not fit the 160 KiB of LDS.
+ * cs_value_net_grad_sizes  (host only) the lengths of d_params and of d_scratch for such a call, in floats.
+ * cs_value_net_pack_device  cs_value_net_pack on the device, one launch on `stream`: d_blob (n_blob_floats = cs_value_net_pack's figure)
+ *   from the flat d_params, byte for byte what cs_value_net_pack writes for the same numbers, zero padding included -- the refresh after
+ *   every optimiser step of trainer.py:50-71 without a host round trip.
+ */
+int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats);
+int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                           float* d_loss, float* d_values /* may be NULL */, float* d_scratch, size_t n_scratch_floats, void* stream);
+int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
+                             size_t n_blob_floats, void* stream);
+
+/*
+ * cs_occupancy_maps OM-SARL's local occupancy maps (crowd_nav/policy/multi_human_rl.py:133-187 build_occupancy_maps) for W worlds in
  *   one kernel on `stream` (csrc/occupancy_map.hip).  d_humans [W][n][stride] holds a human's position at columns 0, 1
  *   and its velocity at vel_col, vel_col + 1: cs_lookahead's d_next [W][n][4|6] (vel_col 2 | 3) and d_current [W][n][5|7] (vel_col 2)
  *   are read in place.  d_maps [W][n][C], C = cell_num^2 * channels, laid out [cell][channel]: for centre human i and every other human j

@@ -162,6 +162,9 @@ ABI = {
     "cs_value_net_decide_bf16": (I, [I, P, I, P, Z, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_decide_worlds": (I, [I, P, I, P, Z, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P, P]),
     "cs_value_net_state": (I, [I, P, I, P, Z, I, I, I, P, P, I, P, F, F, P, P, P]),
+    "cs_value_net_grad_sizes": (I, [I, P, I, I, I, I, P, P]),
+    "cs_value_net_loss_grad": (I, [I, P, I, P, Z, P, Z, I, I, I, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_pack_device": (I, [I, P, I, I, P, Z, P, Z, P]),
     "cs_occupancy_maps": (I, [I, I, P, I, I, I, F, I, P, P]),
     "cs_value_net_pack_om": (I, [I, P, I, I, I, P, P, P]),
     "cs_value_net_decide_om": (I, [I, P, I, P, Z, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),

@@ -30,7 +30,13 @@ Which entries a network uses, with which arguments, and which modes it may run i
 
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes;
-``state_values_for_worlds`` is that for every family."""
+``state_values_for_worlds`` is that for every family.
+
+The optimisation step of the feed-forward family has kernels too (csrc/value_net_grad.hip; ``has_gradient_kernel``):
+``param_offsets`` is the flat parameter layout, ``pack_on_device`` (cs_value_net_pack_device) writes the float32 blob from the flat
+parameters without leaving the device, ``loss_and_grad`` (cs_value_net_loss_grad) is the forward, the mean-squared-error loss and the whole
+gradient of a minibatch of stored rows; ``DeviceNet.adopt_flat`` is a trainer's word that the module's parameters are views of such a flat
+tensor (crowd_nav/utils/trainer.py ``Trainer.set_gradient("device")``).  The other families are refused with GRADIENT_REFUSAL."""
 from __future__ import annotations
 
 import ctypes as C
@@ -105,6 +111,15 @@ def family_of(kind, om_cols=0):
     if kind == CS_VN_LSTM:
         return RECURRENT_MAPPED if om_cols else RECURRENT
     return MAPPED if om_cols else FEED_FORWARD
+
+
+GRADIENT_REFUSAL = ("{0}: the fused loss-and-gradient kernel (cs_value_net_loss_grad) covers the feed-forward networks, CADRL's and SARL's; "
+                    "a network with occupancy-map columns or an LSTM keeps torch's autograd")
+
+
+def has_gradient_kernel(family):
+    """Whether a family's networks have the fused loss-and-gradient kernel (cs_value_net_loss_grad): the feed-forward ones alone."""
+    return family is FEED_FORWARD
 
 
 def check_map_order(map_order):
@@ -209,6 +224,7 @@ class DeviceNet:
         self.lstm = self.kind == CS_VN_LSTM
         self._keys = dict.fromkeys(PRECISIONS)
         self.blobs = dict.fromkeys(PRECISIONS)
+        self.flat = None
 
     @property
     def blob(self):
@@ -221,11 +237,29 @@ class DeviceNet:
         import torch
 
         key = self._versions()
+        if self.flat is not None and precision == "f32":        # the parameters are views of `flat` (adopt_flat): packed where they lie
+            if key != self._keys[precision]:
+                pack_on_device(self, self.flat)
+                self._keys[precision] = key
+            return self.blobs[precision]
         if key != self._keys[check_precision(precision)]:
             arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
             self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision, self.om_cols)).to("cuda")
             self._keys[precision] = key
         return self.blobs[precision]
+
+    def adopt_flat(self, flat):
+        """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
+        ``Trainer.set_gradient("device")`` makes them): from now on ``refresh("f32")`` packs the blob on the device
+        (``pack_on_device``) when a parameter's version changed, with no host round trip.  None takes the word back."""
+        if flat is not None:
+            if not has_gradient_kernel(self.family):
+                raise ValueError(GRADIENT_REFUSAL.format("adopt_flat"))
+            total = param_offsets(self)[-1]
+            if not flat.is_cuda or flat.dtype != _torch().float32 or flat.dim() != 1 or flat.numel() != total or not flat.is_contiguous():
+                raise ValueError(f"adopt_flat: the flat parameters are one contiguous CUDA float32 tensor of {total} elements")
+        self.flat = flat
+        self._keys["f32"] = None
 
     def head(self, caller, precision="f32"):
         """The arguments every network entry of the family opens with, for the blob of `precision`; ValueError in `caller`'s name
@@ -239,6 +273,86 @@ class DeviceNet:
 def _head(lead, dims, blob):
     """[kind,] dims (host int32 array), its length, the packed blob (a CUDA tensor) and its length in the blob's own unit."""
     return lead + (dims.ctypes.data, len(dims), blob.data_ptr(), blob.numel())
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+def param_offsets(net):
+    """The flat layout cs_value_net_loss_grad and cs_value_net_pack_device read: where every tensor of ``describe``'s layers starts, in
+    elements -- weight_0, bias_0, weight_1, ... each dense in torch's own layout -- and, last, the total."""
+    offsets = [0]
+    for layer in net.layers:
+        for p in layer_params(layer):
+            offsets.append(offsets[-1] + p.numel())
+    return tuple(offsets)
+
+
+def _grad_lead(net, caller):
+    if not has_gradient_kernel(net.family):
+        raise ValueError(GRADIENT_REFUSAL.format(caller))
+    return (net.kind, net.dims.ctypes.data, len(net.dims))
+
+
+def _stream(stream):
+    return _torch().cuda.current_stream().cuda_stream if stream is None else stream
+
+
+def pack_on_device(net, flat, stream=None):
+    """cs_value_net_pack_device: `net`'s float32 blob from the flat parameters `flat` (``param_offsets``' layout, a CUDA tensor), one
+    launch on `stream` (None: torch's current one); byte for byte ``pack``'s blob.  The blob is allocated once and rewritten in place."""
+    from ... import _lib
+
+    lead = _grad_lead(net, "pack_on_device")
+    blob = net.blobs["f32"]
+    if blob is None:
+        nf = C.c_size_t(0)
+        _lib.check(_lib.load().cs_value_net_pack(*lead, net.cols, None, None, C.byref(nf)))
+        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
+    _lib.check(_lib.load().cs_value_net_pack_device(*lead, net.cols, flat.data_ptr(), flat.numel(), blob.data_ptr(), blob.numel(), _stream(stream)))
+    return blob
+
+
+def grad_sizes(net, B, n):
+    """cs_value_net_grad_sizes: (the length of the flat parameters, the scratch floats a minibatch of B samples of n humans needs)."""
+    from ... import _lib
+
+    n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.load().cs_value_net_grad_sizes(*_grad_lead(net, "grad_sizes"), net.cols, B, n, C.byref(n_params), C.byref(n_scratch)))
+    return n_params.value, n_scratch.value
+
+
+def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
+    """cs_value_net_loss_grad: the mean-squared-error loss of `net` on the minibatch rows [B, n, cols] (CADRL: n = 1, or [B, cols])
+    against targets [B] or [B, 1], and its gradient into `grad` (the layout of `flat`; written, not accumulated); values [B] or None
+    receives the network's outputs.  CUDA float32 tensors; `net`'s float32 blob must hold `flat`'s numbers (``pack_on_device``).
+    Returns the loss, a CUDA tensor of one element.  The scratch is kept on `net` and grown when a larger minibatch comes."""
+    from ... import _lib
+
+    torch = _torch()
+    lead = _grad_lead(net, "loss_and_grad")
+    head = net.head("loss_and_grad")
+    if rows.dim() == 2:
+        rows = rows[:, None, :]
+    B, n, cols = rows.shape
+    for name, t, numel in (("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()),
+                           ("values", values, B)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"loss_and_grad: {name} is a contiguous CUDA float32 tensor of {numel} elements")
+    if cols != net.cols:
+        raise ValueError(f"loss_and_grad: rows of {cols} columns for a network of {net.cols}")
+    _, need = grad_sizes(net, B, n)
+    scratch = getattr(net, "_grad_scratch", None)
+    if scratch is None or scratch.numel() < need or scratch.device != flat.device:
+        scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
+    loss = torch.empty(1, dtype=torch.float32, device=flat.device)
+    _lib.check(_lib.load().cs_value_net_loss_grad(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
+                                                  grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
+                                                  scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    return loss
 
 
 def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):

@@ -1,0 +1,237 @@
+"""GPU suite of the fused loss-and-gradient kernel (cs_value_net_loss_grad, cs_value_net_pack_device; csrc/value_net_grad.hip, DESIGN.md
+4.5) and of ``Trainer`` in "device" mode: gradients and loss against float64 CPU autograd under the yardstick of
+tests/value_grad_cases.py, golden G23's recorded gradients, the values against cs_value_net_state bit for bit, identical bytes from two
+calls, the device pack against the host pack byte for byte, the trainer against its "autograd" mode step by step, and the whole loop of
+INTEGRATION.md on resident worlds."""
+import copy
+import functools
+
+import numpy as np
+import pytest
+
+import value_grad_cases as vg
+from value_calls import same_bits, state_call
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (7, 5), (33, 3), (100, 5), (2, 33)]
+NETS = ["sarl_13_1", "sarl_13_0", "sarl_15_1", "sarl_15_0", "cadrl_13_0"]
+
+
+def _flat(net, model):
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    return torch.cat([p.detach().reshape(-1) for layer in net.layers for p in value_net.layer_params(layer)]).to("cuda", torch.float32).contiguous()
+
+
+def _dev(a):
+    import torch
+
+    return torch.as_tensor(a, dtype=torch.float32).to("cuda").contiguous()
+
+
+def kernel_gradient(model, cols, x, v, values=False):
+    """cs_value_net_pack_device + cs_value_net_loss_grad for `model` on one minibatch: (loss, [gradient per parameter in sorted-name order],
+    the flat gradient's bytes, values [B] or None)"""
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    net = value_net.DeviceNet(model, cols)
+    flat = _flat(net, model)
+    grad = torch.full_like(flat, np.nan)
+    vals = torch.full((x.shape[0],), np.nan, device="cuda") if values else None
+    value_net.pack_on_device(net, flat)
+    loss = value_net.loss_and_grad(net, flat, _dev(x), _dev(v).reshape(-1), grad, vals)
+    torch.cuda.synchronize()
+    offsets = value_net.param_offsets(net)
+    described = [p for layer in net.layers for p in value_net.layer_params(layer)]
+    host = grad.cpu().numpy()
+    by_id = {id(p): host[a:b].reshape(tuple(p.shape)).astype(np.float64) for p, a, b in zip(described, offsets, offsets[1:])}
+    return float(loss.item()), [by_id[id(p)] for p in vg.sorted_parameters(model)], host.tobytes(), None if vals is None else vals.cpu().numpy()
+
+
+def check_against_autograd(model, cols, x, v, what):
+    loss_k, g_k, _, _ = kernel_gradient(model, cols, x, v)
+    loss32, g32 = vg.autograd(model, x, v)
+    loss64, g64 = vg.autograd(model, x, v, double=True)
+    assert all(np.all(np.isfinite(g)) for g in g_k)
+    worst = vg.assert_within_yardstick(g_k, g32, g64, what)
+    e_k, e_t = abs(loss_k - loss64) / abs(loss64), abs(loss32 - loss64) / abs(loss64)
+    assert e_k <= vg.FACTOR * max(e_t, vg.FLOOR), (what, e_k, e_t)
+    return worst
+
+
+@functools.lru_cache(maxsize=None)
+def seeded_sarl(cols, with_global):
+    model = vg.sarl_module(cols, with_global)
+    vg.draw_weights(model, 2340 + cols + int(with_global), calm=True)
+    return model
+
+
+@pytest.mark.parametrize("B,n", SHAPES, ids=[f"B{b}n{n}" for b, n in SHAPES])
+@pytest.mark.parametrize("cols", [13, 15])
+@pytest.mark.parametrize("with_global", [True, False], ids=["global", "plain"])
+def test_sarl_gradients_and_loss_against_float64_autograd(with_global, cols, B, n):
+    check_against_autograd(seeded_sarl(cols, with_global), cols, *vg.batch(cols, B, n), f"SARL global={with_global} cols={cols} B={B} n={n}")
+
+
+@pytest.mark.parametrize("B", [1, 33, 100])
+def test_cadrl_gradients_and_loss_against_float64_autograd(B):
+    model = vg.cadrl_module(13)
+    vg.draw_weights(model, 2339, calm=False)
+    check_against_autograd(model, 13, *vg.batch(13, B, 1, cadrl=True), f"CADRL B={B}")
+
+
+def test_the_references_full_widths_fit_and_agree():
+    """mlp1 (150, 100), mlp2 (100, 50), attention (100, 100, 1), mlp3 (150, 100, 100, 1) at the reference's batch of 100 x 5 humans: the
+    real LDS map, several workgroups."""
+    model = vg.sarl_module(13, True, vg.SARL_FULL)
+    vg.draw_weights(model, 2338, calm=True)
+    x, v = vg.batch(13, 100, 5)
+    check_against_autograd(model, 13, x, v, "SARL full widths B=100 n=5")
+
+
+@pytest.mark.parametrize("net", NETS)
+def test_the_kernel_reproduces_g23s_recorded_gradients(net):
+    """The reference's own .grad in float32 autograd's place: the kernel within the yardstick of it, and of this project's autograd."""
+    model = vg.g23_module(net)
+    case = vg.g23()[net]
+    x, v = vg.g23_batches(net)[0]
+    loss_k, g_k, _, _ = kernel_gradient(model, int(case["cols"]), x, v)
+    _, g64 = vg.autograd(model, x, v, double=True)
+    vg.assert_within_yardstick(g_k, vg.split_like(case["grads"], vg.sorted_parameters(model)), g64, f"{net} kernel against G23")
+    assert abs(loss_k - case["loss"]) <= vg.FACTOR * vg.FLOOR * abs(case["loss"])
+
+
+@pytest.mark.parametrize("name,W,n", [("sarl", 7, 5), ("cadrl", 33, 1)])
+def test_the_values_are_cs_value_net_states_bit_for_bit(name, W, n):
+    from test_gpu_value_worlds import worlds
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    model = vg.g23_module("sarl_13_1" if name == "sarl" else "cadrl_13_0")
+    _, _, cur, rob = worlds(W, n, 1, False, 2323)
+    net = value_net.DeviceNet(model, 13)
+    net.refresh("f32")
+    want, rows = state_call(net, cur, rob)
+    _, _, _, got = kernel_gradient(model, 13, rows, np.zeros((W, 1), np.float32), values=True)
+    assert np.all(np.isfinite(want)) and same_bits(got, want)
+
+
+def test_two_calls_give_identical_bytes():
+    model = seeded_sarl(13, True)
+    x, v = vg.batch(13, 100, 5)
+    first, second = kernel_gradient(model, 13, x, v)[2], kernel_gradient(model, 13, x, v)[2]
+    assert first == second and len(first) == 4 * sum(p.numel() for p in model.parameters())
+
+
+@pytest.mark.parametrize("net", ["sarl_13_1", "sarl_13_0", "sarl_15_1", "sarl_15_0", "cadrl_13_0", "cadrl_15"])
+def test_pack_on_device_is_the_host_pack_byte_for_byte(net):
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    if net == "cadrl_15":
+        model, cols = vg.cadrl_module(15), 15
+        vg.draw_weights(model, 2337, calm=False)
+    else:
+        model, cols = vg.g23_module(net), int(vg.g23()[net]["cols"])
+    dn = value_net.DeviceNet(model, cols)
+    host = value_net.pack(dn.kind, dn.dims, cols, [p.detach().numpy() for layer in dn.layers for p in value_net.layer_params(layer)])
+    blob = value_net.pack_on_device(dn, _flat(dn, model))
+    torch.cuda.synchronize()
+    assert blob.cpu().numpy().tobytes() == host.tobytes() and np.any(host == 0.0) and np.any(host != 0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the trainer
+def _steps_agree(model, batches, what):
+    """"device" against "autograd" (float32, CPU) after every step, both measured against a float64 run of the same trainer"""
+    losses_d, snaps_d = vg.train_steps(model, batches, gradient="device", device="cuda")
+    losses32, snaps32 = vg.train_steps(model, batches)
+    losses64, snaps64 = vg.train_steps(model, batches, double=True)
+    for k in range(len(batches)):
+        vg.assert_within_yardstick(vg.updates(snaps_d[k], model), vg.updates(snaps32[k], model), vg.updates(snaps64[k], model), f"{what} step {k}")
+        e_d, e_t = abs(losses_d[k] - losses64[k]) / abs(losses64[k]), abs(losses32[k] - losses64[k]) / abs(losses64[k])
+        assert e_d <= vg.FACTOR * max(e_t, vg.FLOOR), (what, k, e_d, e_t)
+
+
+@pytest.mark.parametrize("net", NETS)
+def test_the_device_trainer_follows_the_autograd_trainer_over_g23s_batches(net):
+    _steps_agree(vg.g23_module(net), vg.g23_batches(net), f"{net} trainer")
+
+
+def test_the_device_trainer_over_a_replay_memory():
+    """12 steps of batch 16 from a ReplayMemory of 64 samples on the GPU: the minibatches the memory hands out are replayed through the
+    "autograd" trainer; and the trainer's own loader and optimize_epoch run on the memory."""
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.utils.memory import ReplayMemory
+    from social_navigation_pyenvs_amd.crowd_nav.utils.trainer import Trainer
+
+    model = vg.g23_module("sarl_13_1")
+    x, v = vg.batch(13, 64, 5)
+    memory = ReplayMemory(64)
+    memory.push_batch(x.cuda(), v.cuda().reshape(-1))
+    assert memory.is_full() and memory.device.type == "cuda"
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    batches = [tuple(t.cpu() for t in memory.sample(16, generator=gen)) for _ in range(12)]
+    assert batches[0][0].shape == (16, 5, 13) and batches[0][1].shape == (16, 1)
+    _steps_agree(model, batches, "replay memory")
+    m = copy.deepcopy(model).cuda()
+    trainer = Trainer(m, memory, torch.device("cuda"), 16)
+    trainer.set_learning_rate(0.01)
+    trainer.set_gradient("device")
+    before = [p.detach().clone() for p in m.parameters()]
+    assert np.isfinite(trainer.optimize_batch(2)) and np.isfinite(trainer.optimize_epoch(1))
+    assert all(not torch.equal(a, b) for a, b in zip(before, m.parameters()) if a.dim() > 1)       # every weight matrix moved
+    bad = ReplayMemory(4)
+    bad.push_batch(torch.zeros(2, 5, 14, device="cuda"), torch.zeros(2, device="cuda"))
+    with pytest.raises(ValueError, match="the memory's states"):
+        Trainer(copy.deepcopy(model).cuda(), bad, torch.device("cuda"), 2).set_gradient("device")
+
+
+def test_the_integration_loop_trains_the_policy_the_env_decides_with():
+    """INTEGRATION.md's loop on 8 worlds x 5 humans, 6 Gym steps: act_device -> joint_state_device -> step_device -> value_device(bootstrap)
+    -> push_batch -> optimize_batch(2) in "device" mode.  Afterwards the parameters have changed, and the policy's next act_device uses
+    them: its values are those of a fresh policy loaded with the updated state_dict, bit for bit."""
+    import torch
+
+    from test_gpu_value_policy import _batched, _ready
+    from test_value_policy_cpu import make_policy
+
+    from social_navigation_pyenvs_amd.crowd_nav.utils.memory import ReplayMemory
+    from social_navigation_pyenvs_amd.crowd_nav.utils.trainer import Trainer
+
+    env = _batched(5, W=8)
+    torch.manual_seed(2336)
+    policy = _ready(make_policy("sarl"), env)       # torch's own initialisation: values and targets of order one, a stable step at 0.01
+    start = copy.deepcopy(policy.model.state_dict())
+    target = copy.deepcopy(policy.model)
+    memory = ReplayMemory(64)
+    trainer = Trainer(policy.model, memory, torch.device("cuda"), 16)
+    trainer.set_learning_rate(0.01)
+    trainer.set_gradient("device", net=policy.device_net())
+    losses = []
+    for _ in range(6):
+        action = env.act_device(policy)
+        state = env.joint_state_device(policy)
+        _, reward, terminated, truncated, _ = env.step_device(action, auto_reset=False)
+        boot = env.value_device(policy, model=target, rewards=reward, bootstrap=True)
+        done = terminated | truncated
+        memory.push_batch(state, torch.where(done, reward, boot), keep=~done)
+        losses.append(trainer.optimize_batch(2))
+    assert np.all(np.isfinite(losses)) and 0 < len(memory) <= 48
+    trained = policy.model.state_dict()
+    assert all(not torch.equal(trained[k], start[k].to(trained[k].device)) for k in trained if k.endswith(".weight"))
+    assert policy.device_net().flat is trainer.flat
+    env.act_device(policy)
+    values, choice = (t.cpu().numpy().copy() for t in env.last_values_device())
+    fresh = _ready(make_policy("sarl"), env)
+    fresh.model.load_state_dict({k: v.detach().clone() for k, v in trained.items()})
+    env.act_device(fresh)
+    values2, choice2 = (t.cpu().numpy() for t in env.last_values_device())
+    assert np.all(np.isfinite(values)) and same_bits(values, values2) and np.array_equal(choice, choice2)
+    env.close()
