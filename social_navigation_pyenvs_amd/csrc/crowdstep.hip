@@ -242,6 +242,12 @@ int commit_mode(const cs_worlds* w) { return M_COMMIT_GOALS | (((w->flags & CS_R
 // diagnostic entry the parity tests use to assert that every benched build is the one they compared with the oracle).
 struct RobotModel { int type; const float* params; float margin; const float* d_human_margin; float* d_memory; };
 
+// The plain one-wavefront builds with a compile-time row count address their arrays as a kernel-argument base + an unsigned 32-bit byte
+// offset of the lane (sfmstep_kernel.h LAUNCH_TRIM).  The largest offset they form is a row's into the parameter array (80 bytes per row;
+// the state's 52, a two-slot goal list's 16, the margins' 4 lie below it), so every one fits while W x rows x 80 <= 2^32 -- 53.6 million
+// rows.  Worlds beyond that (a batch of > 8 GB) run the generic build, whose addresses are 64-bit throughout.
+bool offsets_fit_32(const cs_worlds* w) { return (unsigned long long)w->W * (unsigned long long)rows_of(w) * 80ull <= (1ull << 32); }
+
 Variant select_variant(const cs_worlds* w, int mode, const Geometry& g, bool need_snap = false, bool robot_model = false)
 {
     const bool robot = (w->flags & CS_ROBOT_ROW) != 0;
@@ -280,7 +286,10 @@ Variant select_variant(const cs_worlds* w, int mode, const Geometry& g, bool nee
     static const Row table[] = {{LEAN_PLAIN, 25, 1, 4}, {LEAN_PLAIN, 30, 1, 4}, {LEAN_PLAIN, 20, 1, 4}, {LEAN_PLAIN, 10, 4, 4}, {LEAN_PLAIN, 50, 3, 3},
                                 {LEAN_WALLS, 50, 3, 3}, {LEAN_ROBOT_ROW, 26, 1, 4}, {LEAN_ROBOT_ROW, 6, 4, 4}, {LEAN_ROBOT_ROW, 11, 4, 4}, {LEAN_ROBOT_ROW, 51, 3, 3}};
     for (const Row& r : table)
-        if (r.kind == kind && r.rows == rows) return Variant{64, crowded ? r.occ_crowded : r.occ_sparse, rows, kind, true};
+        if (r.kind == kind && r.rows == rows) {
+            if (kind == LEAN_PLAIN && !offsets_fit_32(w)) return Variant{64, 3, 0, LEAN_GENERIC, peq};   // (see offsets_fit_32)
+            return Variant{64, crowded ? r.occ_crowded : r.occ_sparse, rows, kind, true};
+        }
     // any other row count: the run-time partner loop keeps the budget of THREE waves per SIMD on every grid: its 128-VGPR build
     // spills (7 VGPRs lean, 35 with walls) and measured 6-17 % slower on crowded grids (8192 x 50 + walls: 355 vs 304 us;
     // 16384 x 30 Moussaid: 484 vs 402 us); the walls build needs exactly 168 VGPRs, and a build that tips over to 169 runs at

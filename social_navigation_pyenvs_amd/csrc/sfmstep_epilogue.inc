@@ -27,11 +27,28 @@
     int fold_code = 0;
     if constexpr (FOLD) fold_code = valid ? fold_code_world : 0;   // (from the head's lane, prologue; 0 in a launch without a head or without the fold)
     const bool taken_over = fold_code >= 2;
-    if (human && gdirty && (kmode & M_COMMIT_GOALS) && !taken_over) { gi[0] = g0x; gi[1] = g0y; gi[2] = g1x; gi[3] = g1y; }
+    if (human && gdirty && (kmode & M_COMMIT_GOALS) && !taken_over) {
+        if constexpr (LAUNCH_TRIM) {   // (the list's base read here, not held across the loop; goff: the load phase's offset)
+            float* gb = KARG(goals);
+            st_off(gb, goff, g0x); st_off(gb + 1, goff, g0y); st_off(gb + 2, goff, g1x); st_off(gb + 3, goff, g1y);
+        } else { gi[0] = g0x; gi[1] = g0y; gi[2] = g1x; gi[3] = g1y; }
+    }
+    if constexpr (LAUNCH_TRIM) {
+        // the same stores off scalar bases: column k of the output at Sout + k * out_fs, the lane's 32-bit byte offset in one register
+        // (these builds hold humans only: human == valid, no robot row; r, m and v_desired are written out of place only)
+        if (valid && !taken_over) {
+            float* o = KARG(Sout);
+            const long fs = KARG(out_fs);
+            const unsigned so = srow * (unsigned)KARG(out_as) * 4u;
+            st_off(o, so, px); st_off(o + fs, so, py); st_off(o + 2 * fs, so, th); st_off(o + 3 * fs, so, vx); st_off(o + 4 * fs, so, vy);
+            st_off(o + 5 * fs, so, bvx); st_off(o + 6 * fs, so, bvy); st_off(o + 7 * fs, so, om); st_off(o + 10 * fs, so, gx); st_off(o + 11 * fs, so, gy);
+            if (KARG(Sout) != KARG(Sin)) { st_off(o + 8 * fs, so, r); st_off(o + 9 * fs, so, m); st_off(o + 12 * fs, so, vd); }
+        }
+    }
     if (valid && !taken_over) {
         float* o = KARG(Sout) + sidx * KARG(out_as);
         const long fs = KARG(out_fs);
-        if (human || is_robot) {
+        if (!LAUNCH_TRIM && (human || is_robot)) {
             o[0] = px; o[fs] = py; o[2 * fs] = th; o[3 * fs] = vx; o[4 * fs] = vy; o[5 * fs] = bvx;
             o[6 * fs] = bvy; o[7 * fs] = om; o[10 * fs] = gx; o[11 * fs] = gy;
             if (KARG(Sout) != KARG(Sin) || is_robot) { o[8 * fs] = r; o[9 * fs] = m; o[12 * fs] = vd; }
@@ -104,7 +121,8 @@
             o[16] = pst_entry - pst_first;                      // first instruction -> kernel arguments loaded
             unsigned long long rt_end;
             asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_end)::"memory");
-            o[17] = pst_first_rt; o[18] = rt_end; o[19] = 0;    // the wall clock at the wavefront's first and last instruction (10 ns ticks)
+            o[17] = pst_first_rt; o[18] = rt_end;               // the wall clock at the wavefront's first and last instruction (10 ns ticks)
+            o[19] = pst_issued - pst_entry;                     // entry -> the last load of the load phase issued (the issue side of slot 12)
         }
     }
 #endif

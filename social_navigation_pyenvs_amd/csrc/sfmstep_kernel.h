@@ -156,6 +156,18 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     const int pbase = lw * a.ws;       // first row of my world in the doubled position buffers
     const float dt = a.dt;
     const int obs_type = (a.type == 1 || a.type == 4 || a.type == 7) ? 1 : 0;
+    // The plain one-wavefront builds with a compile-time row count (the family of XY_ROWS / ONE_REGION) also trim what a wavefront executes
+    // AROUND its substeps (sfmstep_load.inc, sfmstep_prologue.inc, sfmstep_epilogue.inc; HISTORY.md has the counts): no load that the launch
+    // cannot use (the action and the invisible robot's columns sit behind the wave-uniform tests of their kernel arguments), dword
+    // addresses as a kernel-argument base + an unsigned 32-bit lane offset (the launcher keeps shapes whose byte offsets do not fit 32 bits
+    // off these builds: crowdstep.hip offsets_fit_32), and no default for a value that only a lane with a human reads.  Same bits in every
+    // build: no arithmetic on a loaded value moves.
+    // (Not the one pair of builds that spills, the 30-row Moussaid HSFM twins at the four-wave budget: trimmed they take 36 bytes of scratch
+    // instead of 32, as with VOTED_SWITCH below; they stay as they were.)
+    constexpr bool LAUNCH_TRIM = XY_ROWS && !(SOC == 2 && HEADED > 0 && OCC == 4 && ROWS_CT == 30);
+    // (The branch around the invisible robot's five loads stays out of the policy twins: with it the ones with a heading gain a stack
+    // frame, 36 bytes of scratch where they had none; a policy launch always has a robot, so the branch would always be taken.)
+    constexpr bool ROBOT_LOADS_BRANCH = LAUNCH_TRIM && !POLICY;
 
     // the load phase: every global load of the prologue issued before the first use (one memory round trip); the row, the parameter rows, the goal list, the world flag, the action, the Gym head's inputs
 #include "sfmstep_load.inc"

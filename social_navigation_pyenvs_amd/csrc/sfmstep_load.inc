@@ -17,20 +17,42 @@
     const int wc = valid ? w : 0, rowh = human ? row : 0;
     const long sidx_c = valid ? sidx : 0;
     const float* dummy = a.Sin;
+    // LAUNCH_TRIM builds (sfmstep_kernel.h): every dword of this phase is addressed as (kernel argument + scalar terms) + an unsigned 32-bit
+    // byte offset of the lane -- a scalar base and ONE vector register per array, where the pointer arithmetic of the other arm costs two
+    // to five 64-bit vector instructions per load.  The byte offsets of the shapes these builds are launched for fit 32 bits
+    // (crowdstep.hip offsets_fit_32).  srow: my row in the per-row arrays (row 0 for a lane without a world), used again by the epilogue.
+    const unsigned srow = LAUNCH_TRIM ? (valid ? (unsigned)(w * rows + row) : 0u) : 0u;
     float px, py, th, vx, vy, bvx, bvy, om, r, m, gx, gy, vd;
-    {
+    if constexpr (LAUNCH_TRIM) {
+        const float* s = a.Sin;   // column k starts at s + k * fs: scalar arithmetic
+        const long fs = a.in_fs;
+        const unsigned so = srow * (unsigned)a.in_as * 4u;
+        px = ld_off(s, so); py = ld_off(s + fs, so); th = ld_off(s + 2 * fs, so); vx = ld_off(s + 3 * fs, so); vy = ld_off(s + 4 * fs, so);
+        bvx = ld_off(s + 5 * fs, so); bvy = ld_off(s + 6 * fs, so); om = ld_off(s + 7 * fs, so); r = ld_off(s + 8 * fs, so);
+        m = ld_off(s + 9 * fs, so); gx = ld_off(s + 10 * fs, so); gy = ld_off(s + 11 * fs, so); vd = ld_off(s + 12 * fs, so);
+    } else {
         const float* s = a.Sin + sidx_c * a.in_as;
         const long fs = a.in_fs;
         px = s[0]; py = s[fs]; th = s[2 * fs]; vx = s[3 * fs]; vy = s[4 * fs]; bvx = s[5 * fs];
         bvy = s[6 * fs]; om = s[7 * fs]; r = s[8 * fs]; m = s[9 * fs]; gx = s[10 * fs]; gy = s[11 * fs];
         vd = s[12 * fs];
     }
-    float safety = a.safety[sidx_c];
+    float safety = LAUNCH_TRIM ? ld_off(a.safety, srow * 4u) : a.safety[sidx_c];
     const bool has_wflags = a.world_flags != nullptr;
-    const int wflag_raw = *(has_wflags ? a.world_flags + wc : reinterpret_cast<const int*>(dummy));   // bit 0: the respawn rule applies to my world
+    // bit 0: the respawn rule applies to my world  (LAUNCH_TRIM without world flags: word wc of the state array, never used -- the state
+    // holds more words than there are worlds)
+    const int wflag_raw = LAUNCH_TRIM ? ld_off(has_wflags ? a.world_flags : reinterpret_cast<const int*>(dummy), (unsigned)wc * 4u)
+                                      : *(has_wflags ? a.world_flags + wc : reinterpret_cast<const int*>(dummy));
     const bool robot_moves = a.action != nullptr; // (lean build: only the invisible robot of the epilogue)
     float ax, ay;                                 // robot action (held for the whole block, social_nav_gym.py:240-243)
-    {
+    if constexpr (LAUNCH_TRIM) {
+        // behind the wave-uniform test of its kernel argument: a launch without an action issues no load for it; one with an action issues
+        // it here, ahead of the phase's one wait (its first use is in the prologue)
+        ax = 0.0f; ay = 0.0f;
+        if constexpr (!POLICY) {   // (POLICY: the action is decided in the prologue)
+            if (robot_moves) { ax = ld_off(a.action, (unsigned)wc * 8u); ay = ld_off(a.action + 1, (unsigned)wc * 8u); }
+        }
+    } else {
         const float* ap = (robot_moves && !POLICY) ? a.action + (long)wc * 2 : dummy;   // (POLICY: the action is decided in the prologue)
         ax = ap[0]; ay = ap[1];
     }
@@ -38,16 +60,34 @@
     // when all_params_equal (forces_parallel.py:220), else my own row (:261)
     const long pw = (a.flags & CS_PARAMS_SHARED) ? 0 : (long)wc * n * 20;
     const float* Prow = a.params + pw + (long)rowh * 20;
+    // (LAUNCH_TRIM: the same rows as byte offsets -- my world's table, my row in it -- and my goal list's, which the epilogue uses again)
+    const unsigned pwoff = LAUNCH_TRIM ? ((a.flags & CS_PARAMS_SHARED) ? 0u : (unsigned)wc * (unsigned)(n * 80)) : 0u;
+    const unsigned poff = LAUNCH_TRIM ? pwoff + (unsigned)rowh * 80u : 0u;
+    const unsigned goff = LAUNCH_TRIM ? (unsigned)(wc * n + rowh) * (unsigned)a.G * 8u : 0u;
     float Pm[11];                                 // my P[0], [2], [4], [6], [8], [10], [11], [16], [17], [18], [19]
+    if constexpr (LAUNCH_TRIM) {
+        const float* P = a.params;
+        Pm[0] = ld_off(P, poff); Pm[1] = ld_off(P + 2, poff); Pm[2] = ld_off(P + 4, poff); Pm[3] = ld_off(P + 6, poff); Pm[4] = ld_off(P + 8, poff);
+        Pm[5] = ld_off(P + 10, poff); Pm[6] = ld_off(P + 11, poff); Pm[7] = ld_off(P + 16, poff); Pm[8] = ld_off(P + 17, poff);
+        Pm[9] = ld_off(P + 18, poff); Pm[10] = ld_off(P + 19, poff);
+    } else {
     Pm[0] = Prow[0]; Pm[1] = Prow[2]; Pm[2] = Prow[4]; Pm[3] = Prow[6]; Pm[4] = Prow[8]; Pm[5] = Prow[10]; Pm[6] = Prow[11];
     Pm[7] = Prow[16]; Pm[8] = Prow[17]; Pm[9] = Prow[18]; Pm[10] = Prow[19];
-    const SocRaw sraw = load_socraw(PEQ ? a.params + pw : Prow);
-    float* gi = a.goals + ((long)wc * n + rowh) * a.G * 2;   // my goal list (row 0's for a lane without a human)
+    }
+    const SocRaw sraw = LAUNCH_TRIM ? load_socraw_off(a.params, PEQ ? pwoff : poff) : load_socraw(PEQ ? a.params + pw : Prow);
+    // my goal list (row 0's for a lane without a human)
+    float* gi = LAUNCH_TRIM ? reinterpret_cast<float*>(reinterpret_cast<char*>(a.goals) + goff) : a.goals + ((long)wc * n + rowh) * a.G * 2;
     float gl[4];                                  // its first two slots
+    if constexpr (LAUNCH_TRIM) {
+        const float* g2 = a.G >= 2 ? a.goals + 2 : a.goals;   // (a scalar choice of the base)
+        gl[0] = ld_off(a.goals, goff); gl[1] = ld_off(a.goals + 1, goff);
+        gl[2] = ld_off(g2, goff); gl[3] = ld_off(g2 + 1, goff);
+    } else {
     gl[0] = gi[0]; gl[1] = gi[1];
     {
         const float* g2 = a.G >= 2 ? gi + 2 : gi;
         gl[2] = g2[0]; gl[3] = g2[1];
+    }
     }
     if (valid && is_robot && (kmode & M_ROBOT_FROM_ARRAY)) {   // (divergent: the robot's lane)
         const float* rb = a.robot + (long)w * 13;
@@ -58,7 +98,9 @@
     // in the epilogue they were one more memory round trip at the end of every launch that moves a robot (~1 us of a Gym step)
     const bool moves_invisible_robot = valid && !robot_row && row == 0 && robot_moves && a.robot != nullptr && !(kmode & M_PEEK);
     float irb[5] = {0, 0, 0, 0, 0};
-    {
+    // (ROBOT_LOADS_BRANCH, sfmstep_kernel.h: behind the wave-uniform half of that test -- a launch that moves no invisible robot issues none
+    //  of the five; one that does issues them here, ahead of the phase's one wait, as the other arm does)
+    if (!ROBOT_LOADS_BRANCH || (robot_moves && a.robot != nullptr && !(kmode & M_PEEK))) {
         const float* rb = moves_invisible_robot ? a.robot + (long)w * 13 : dummy;
         irb[0] = rb[0]; irb[1] = rb[1]; irb[2] = rb[2]; irb[3] = rb[3]; irb[4] = rb[4];
     }
@@ -89,6 +131,10 @@
         if (human) rm_hm = a.rm_hmargin[sidx];
         if (is_robot) { rm_fdx = a.rm_memory[(long)w * 2]; rm_fdy = a.rm_memory[(long)w * 2 + 1]; }
     }
+#ifdef CS_STAMPS
+    unsigned long long pst_issued;   // the last load of the phase has been issued (none waited for): entry -> here is the issue side, here -> pst_loaded the round trip
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_issued)::"memory");
+#endif
 
     const float inv_O = a.O > 0 ? 1.0f / (float)a.O : 0.0f;
     const float* obst = nullptr;

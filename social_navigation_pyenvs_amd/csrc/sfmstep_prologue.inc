@@ -11,9 +11,12 @@
         safety = 0; ax = 0; ay = 0;
     }
     if (!robot_moves) { ax = 0; ay = 0; }
-    float m_tau = 0, Aw = 0, cBw = 0, Cw = 0, cDw = 0, k1 = 0, k2 = 0, ko = 0, kd = 0, alpha = 1, klam = 0;
-    float dt_m = 0, inv_alpha = 1, inertia = 1, dt_inertia = 0, wall_cut = 0;
-    SocP sp = {};
+    // (D: the default of a value that only lanes with a human read -- the substep loop's one exec region, the epilogue's `human &&`
+    //  stores.  LAUNCH_TRIM builds leave it unspecified: as a constant it is a v_mov per value on every launch for lanes that never read it)
+#define D(v) unread_default<LAUNCH_TRIM>(v)
+    float m_tau = D(0.0f), Aw = D(0.0f), cBw = D(0.0f), Cw = D(0.0f), cDw = D(0.0f), k1 = D(0.0f), k2 = D(0.0f), ko = D(0.0f), kd = D(0.0f), alpha = D(1.0f), klam = D(0.0f);
+    float dt_m = D(0.0f), inv_alpha = D(1.0f), inertia = D(1.0f), dt_inertia = D(0.0f), wall_cut = D(0.0f);
+    SocP sp = socp_unread_default<LAUNCH_TRIM>();
     float g0x = gx, g0y = gy, g1x = 0, g1y = 0;
     int gk = 0;          // length of the non-NaN prefix of my goal list
     bool gdirty = false; // a two-goal list rotated in registers, to be written back in the epilogue
@@ -238,13 +241,20 @@
     constexpr int RSN = (ROWS_CT > 0 && N3L) ? (ROWS_CT - 1) / 2 + 1 : 1;
     float rsj[RSN];
 #pragma unroll
-    for (int k = 0; k < RSN; ++k) rsj[k] = 0.0f;
+    for (int k = 0; k < RSN; ++k) rsj[k] = D(0.0f);
     // ... and the reaction slot of partner k: (row + 1 + k) mod rows.  With the modulo every slot of an accumulator row is written by
     // exactly one lane in every group, so the FIRST group stores instead of accumulating (no zeroing pass, no read), and a receiver reads
     // one slot per row instead of a low and a high copy -- a quarter of the loop's LDS bytes at 25 rows
     int aoff[RSN];
 #pragma unroll
-    for (int k = 0; k < RSN; ++k) aoff[k] = 0;
+    for (int k = 0; k < RSN; ++k) aoff[k] = D(0);
+#undef D
+    if constexpr (LAUNCH_TRIM) {
+        // a function of the lane's row alone: formed by every lane, outside the `if (valid)` below, so that no default is merged in behind
+        // it; and without a compare and a select per slot -- t - ROWS_CT wraps to a huge unsigned exactly when t < ROWS_CT
+#pragma unroll
+        for (int k = 0; k < RSN; ++k) aoff[k] = (int)min((unsigned)(row + 1 + k), (unsigned)(row + 1 + k - ROWS_CT));
+    }
     // ... and, with per-agent parameters (PP), its parameter row and the sign of its C / A: nothing but (x, y) is read per pair
     constexpr int PPN = (ROWS_CT > 0 && PP) ? RSN : 1;
     float4 ppj[PPN];
@@ -261,7 +271,7 @@
                 if constexpr (PP) { sacj[k] = pk.w; ppj[k] = lds_pp[pbase + row + 1 + k]; }
                 }
                 const int t = row + 1 + k;
-                aoff[k] = t >= ROWS_CT ? t - ROWS_CT : t;
+                if constexpr (!LAUNCH_TRIM) aoff[k] = t >= ROWS_CT ? t - ROWS_CT : t;
                 if constexpr (XY_ROWS) rsj[k] = lds_rs[base + aoff[k]];   // (a 4-byte read of the partner's own row: lds_rs is not doubled)
             }
         }

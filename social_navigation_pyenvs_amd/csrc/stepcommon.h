@@ -220,6 +220,34 @@ struct SocP {
 };
 
 // the social-force entries of a parameter row as loaded (no arithmetic: a caller issues its other loads before it uses them) ...
+// A dword at `base` (wave-uniform: a kernel argument and scalar terms) + an unsigned 32-bit byte offset of the lane: the global load /
+// store form with a scalar base and ONE vector register, instead of a 64-bit address formed per lane (k_sfm_step's LAUNCH_TRIM builds)
+template <class T>
+__device__ __forceinline__ T ld_off(const T* base, unsigned byte_off)
+{
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+template <class T>
+__device__ __forceinline__ void st_off(T* base, unsigned byte_off, T v)
+{
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+
+// The default of a value that no lane reads unless it has overwritten it: `v` itself, or (UNREAD: k_sfm_step's LAUNCH_TRIM builds) an
+// unspecified value of its type -- no instruction, where a constant costs a v_mov on every launch.  (An indeterminate local, on purpose:
+// the compiler's own "any value" -- __builtin_nondeterministic_value -- is frozen to a zero and moved into the register all the same.)
+template <bool UNREAD, class T>
+__device__ __forceinline__ T unread_default(T v)
+{
+    if constexpr (UNREAD) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wuninitialized"
+        T u;
+        return u;
+#pragma clang diagnostic pop
+    } else return v;
+}
+
 struct SocRaw { float v[11]; };   // P[1], [3], [5], [7], [9], [10] .. [15]
 __device__ __forceinline__ SocRaw load_socraw(const float* P)
 {
@@ -227,6 +255,23 @@ __device__ __forceinline__ SocRaw load_socraw(const float* P)
     q.v[0] = P[1]; q.v[1] = P[3]; q.v[2] = P[5]; q.v[3] = P[7]; q.v[4] = P[9];
 #pragma unroll
     for (int k = 0; k < 6; ++k) q.v[5 + k] = P[10 + k];
+    return q;
+}
+template <bool UNREAD>
+__device__ __forceinline__ SocP socp_unread_default()
+{
+    if constexpr (UNREAD) {
+        SocP s;
+        return s;
+    } else return SocP{};
+}
+// ... the same row at `base` + a 32-bit byte offset of the lane (ld_off)
+__device__ __forceinline__ SocRaw load_socraw_off(const float* P, unsigned off)
+{
+    SocRaw q;
+    q.v[0] = ld_off(P + 1, off); q.v[1] = ld_off(P + 3, off); q.v[2] = ld_off(P + 5, off); q.v[3] = ld_off(P + 7, off); q.v[4] = ld_off(P + 9, off);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) q.v[5 + k] = ld_off(P + 10 + k, off);
     return q;
 }
 // ... and the derived constants of the pair loop

@@ -105,6 +105,7 @@ if st[:, 18].mean() > 0:   # slots 16 / 17 / 18 of the last launch (not summed):
 print("  around the substeps (shader clocks per launch, mean over the wavefronts):")
 for k, nm in enumerate(fixed):
     print(f"    {nm:62s} {st[:, 12 + k].mean():9.0f} cycles  ({st[:, 12 + k].mean() / 2.4e3:5.2f} us at 2.4 GHz)")
+print(f"    {'entry -> last load of the load phase issued (issue side of the first line)':62s} {st[:, 19].mean():9.0f} cycles  ({st[:, 19].mean() / 2.4e3:5.2f} us at 2.4 GHz)")
 per_wave = st[:, :11].sum(1)
 print(f"  the launch waits for its slowest wavefront: slowest / mean wavefront = {per_wave.max() / per_wave.mean():.3f}, 99th percentile / mean = {np.percentile(per_wave, 99) / per_wave.mean():.3f}")
 print(f"  second half of the grid (the younger wavefront of each SIMD) / first half: {per_wave[len(per_wave) // 2:].mean() / per_wave[:len(per_wave) // 2].mean():.3f}")
