@@ -1,6 +1,8 @@
-"""What the two suites of the fused loss-and-gradient kernel share (tests/test_value_grad_cpu.py, tests/test_gpu_value_grad.py): golden G23
-(the reference's networks under autograd and its Trainer, tests/golden/make_golden_g23.py), this project's modules with G23's widths and
-weights, seeded minibatches, and the error yardstick.
+"""What the suites of the fused loss-and-gradient kernel share (tests/test_value_grad_cpu.py, tests/test_gpu_value_grad.py and the edge
+suites tests/test_value_grad_edges_cpu.py, tests/test_gpu_value_grad_edges.py): golden G23 (the reference's networks under autograd and
+its Trainer, tests/golden/make_golden_g23.py), this project's modules with G23's widths and weights, seeded minibatches, the error
+yardstick, the kernel call and its comparison with autograd, and the edge suites' cases (the job walks, the chunk edges, the depth and
+width descriptions, the masked humans, the spotlights).
 
 The yardstick.  g64 is the gradient of a ``copy.deepcopy(module).double()`` under CPU autograd.  Per parameter tensor
 e_x = max |g_x - g64| / max |g64|, and a candidate x passes when e_x <= 16 * max(e_torch, 2^-22) with e_torch the same measure of float32
@@ -82,11 +84,11 @@ def g23_batches(net):
     return [(torch.from_numpy(case[f"inputs{b}"]), torch.from_numpy(case[f"values{b}"])) for b in range(3)]
 
 
-def batch(cols, B, n, cadrl=False):
-    """A seeded minibatch: inputs [B, n, cols] ([B, cols] for CADRL) and values [B, 1], uniform in [-1, 1)"""
+def batch(cols, B, n, cadrl=False, salt=0):
+    """A seeded minibatch: inputs [B, n, cols] ([B, cols] for CADRL) and values [B, 1], uniform in [-1, 1); `salt`: another one of the shape"""
     import torch
 
-    rs = np.random.RandomState(1000 * B + n)
+    rs = np.random.RandomState(1000 * B + n + 7919 * salt)
     x = rs.uniform(-1, 1, (B, cols) if cadrl else (B, n, cols)).astype(F32)
     return torch.from_numpy(x), torch.from_numpy(rs.uniform(-1, 1, (B, 1)).astype(F32))
 
@@ -184,3 +186,231 @@ def train_steps(model, batches, gradient="autograd", double=False, device="cpu",
 def updates(snapshot, model):
     """What a training run added to the parameters of `model` (the seeded start), per tensor"""
     return [s - p.detach().double().cpu().numpy() for s, p in zip(snapshot, sorted_parameters(model))]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the kernel's call
+def flat_parameters(net, model):
+    """The module's parameters as cs_value_net_loss_grad reads them: one CUDA float32 tensor in value_net.param_offsets' layout"""
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    return torch.cat([p.detach().reshape(-1) for layer in net.layers for p in value_net.layer_params(layer)]).to("cuda", torch.float32).contiguous()
+
+
+def to_device(a):
+    import torch
+
+    return torch.as_tensor(a, dtype=torch.float32).to("cuda").contiguous()
+
+
+def kernel_gradient(model, cols, x, v, values=False):
+    """cs_value_net_pack_device + cs_value_net_loss_grad for `model` on one minibatch: (loss, [gradient per parameter in sorted-name order],
+    the flat gradient's bytes, values [B] or None)"""
+    import torch
+
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    net = value_net.DeviceNet(model, cols)
+    flat = flat_parameters(net, model)
+    grad = torch.full_like(flat, np.nan)
+    vals = torch.full((x.shape[0],), np.nan, device="cuda") if values else None
+    value_net.pack_on_device(net, flat)
+    loss = value_net.loss_and_grad(net, flat, to_device(x), to_device(v).reshape(-1), grad, vals)
+    torch.cuda.synchronize()
+    offsets = value_net.param_offsets(net)
+    described = [p for layer in net.layers for p in value_net.layer_params(layer)]
+    host = grad.cpu().numpy()
+    by_id = {id(p): host[a:b].reshape(tuple(p.shape)).astype(np.float64) for p, a, b in zip(described, offsets, offsets[1:])}
+    return float(loss.item()), [by_id[id(p)] for p in sorted_parameters(model)], host.tobytes(), None if vals is None else vals.cpu().numpy()
+
+
+def references(model, x, v):
+    """((loss32, g32), (loss64, g64)): float32 and float64 CPU autograd of `model` on one minibatch"""
+    return autograd(model, x, v), autograd(model, x, v, double=True)
+
+
+def check_against_autograd(model, cols, x, v, what, refs=None):
+    """The kernel's gradient per tensor and its loss against float64 autograd under the yardstick; `refs`: ``references`` computed before"""
+    loss_k, g_k, _, _ = kernel_gradient(model, cols, x, v)
+    (loss32, g32), (loss64, g64) = refs or references(model, x, v)
+    assert all(np.all(np.isfinite(g)) for g in g_k)
+    worst = assert_within_yardstick(g_k, g32, g64, what)
+    e_k, e_t = abs(loss_k - loss64) / abs(loss64), abs(loss32 - loss64) / abs(loss64)
+    assert e_k <= FACTOR * max(e_t, FLOOR), (what, e_k, e_t)
+    return worst
+
+
+def steps_agree(model, batches, what):
+    """The trainer in "device" mode against "autograd" (float32, CPU) after every step, both measured against a float64 run of the same trainer"""
+    losses_d, snaps_d = train_steps(model, batches, gradient="device", device="cuda")
+    losses32, snaps32 = train_steps(model, batches)
+    losses64, snaps64 = train_steps(model, batches, double=True)
+    for k in range(len(batches)):
+        assert_within_yardstick(updates(snaps_d[k], model), updates(snaps32[k], model), updates(snaps64[k], model), f"{what} step {k}")
+        e_d, e_t = abs(losses_d[k] - losses64[k]) / abs(losses64[k]), abs(losses32[k] - losses64[k]) / abs(losses64[k])
+        assert e_d <= FACTOR * max(e_t, FLOOR), (what, k, e_d, e_t)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the edge suites' cases
+# The job walks (csrc/value_net_grad.hip plan_grad: gpt = 32 / n groups a tile (1 above 32 humans), jrows = min(up(ceil(B / 256), gpt), 32)
+# groups a job, jobs = ceil(B / jrows), grid = min(jobs, 256) workgroups): (B, n, grid).  Each is the smallest B at which its walk exists.
+WALKS = [
+    (513, 16, 129),      # jrows 4: two tiles of two groups; the last job one group
+    (1537, 5, 129),      # jrows 12: two tiles of six; the last job one group
+    (257, 32, 129),      # jrows 2: two full 32-row tiles
+    (257, 33, 129),      # jrows 2: two groups in chunks per job
+    (8193, 5, 256),      # jrows 32: tiles of 6, 6, 6, 6, 6, 2 groups; 257 jobs: workgroup 0 takes a second job of one sample
+    (8193, 1, 256),      # 257 jobs of one tile
+]
+CHUNK_EDGES = [(2, 17), (1, 32), (3, 64), (2, 65)]       # padded rows in a whole tile, a full tile, two full chunks, a tail chunk of one row
+# even and odd attention depths, one-layer chains, mlp1 and feature widths at 5, 7, 8, 32, 64, 65 and 129
+DEPTHS = {
+    "shallow": dict(mlp1=[24], mlp2=[9], attention=[1], mlp3=[1]),
+    "even": dict(mlp1=[16, 40, 32], mlp2=[32, 8, 7], attention=[64, 1], mlp3=[33, 32, 5, 1]),
+    "att4": dict(mlp1=[8, 5], mlp2=[65], attention=[20, 12, 9, 1], mlp3=[129, 1]),
+}
+DEPTH_SHAPES = [(7, 5), (2, 33), (3, 1)]
+MASKED = [(7, 5, (1, 3)), (2, 40, (2, 31, 32, 39))]      # (B, n, the humans whose rows are 0): never the first; the second case masks the
+#                                                          last row of the first chunk and the first row of the tail chunk
+SPOTLIGHTS = [(8193, 5, 8192), (1537, 5, 776), (257, 33, 101)]      # workgroup 0's second job; a second tile of a middle job (job 64 holds
+#                                                                     samples 768 .. 779, its second tile 774 ..); a job's second group (job 50: 100, 101)
+
+
+@functools.lru_cache(maxsize=None)
+def seeded_sarl(cols, with_global):
+    model = sarl_module(cols, with_global)
+    draw_weights(model, 2340 + cols + int(with_global), calm=True)
+    return model
+
+
+@functools.lru_cache(maxsize=None)
+def full_sarl(with_global=True):
+    """The reference's full widths (test_gpu_value_grad.py's seed)"""
+    model = sarl_module(13, with_global, SARL_FULL)
+    draw_weights(model, 2338, calm=True)
+    return model
+
+
+@functools.lru_cache(maxsize=None)
+def depth_sarl(name, with_global):
+    model = sarl_module(13, with_global, DEPTHS[name])
+    draw_weights(model, 2350 + sorted(DEPTHS).index(name), calm=True)
+    return model
+
+
+@functools.lru_cache(maxsize=None)
+def masked_sarl():
+    """The plain network (no crowd mean) with mlp1's and the attention chain's biases 0: a human whose row is 0 scores exactly 0"""
+    import torch
+
+    model = copy.deepcopy(seeded_sarl(13, False))
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name.endswith(".bias") and name.split(".")[0] in ("mlp1", "attention"):
+                p.zero_()
+    return model
+
+
+KINK_MARGIN = 2.0 ** -16
+
+
+def relu_margins(model, x):
+    """Per sample, the smallest |input of a ReLU| in the float64 forward of `model` on x [B, ...]"""
+    import torch
+
+    m = copy.deepcopy(model).to("cpu").double()
+    B = x.shape[0]
+    least = torch.full((B,), float("inf"), dtype=torch.float64)
+
+    def hook(_, inputs, __):
+        nonlocal least
+        least = torch.minimum(least, inputs[0].detach().abs().reshape(B, -1).min(dim=1).values)
+
+    for mod in m.modules():
+        if isinstance(mod, torch.nn.ReLU):
+            mod.register_forward_hook(hook)
+    with torch.no_grad():
+        m(x.double())
+    return least.numpy()
+
+
+def batch_away_from_kinks(model, cols, B, n, cadrl=False):
+    """``batch`` with every sample redrawn (a seeded stream of its own) until no ReLU of the float64 module reads an input within
+    KINK_MARGIN of zero.  The gradient jumps at such an input: float32 and float64 may take it on different sides, and then differ by
+    one sample's whole term of a row -- 1e-4 and more of a tensor's scale among the millions of activations of 8193 x 5 -- which says
+    nothing of either's arithmetic, and which side a float32 forward falls on changes with the order of its sums, so from one CPU's torch
+    to another's.  The margin: a pre-activation here is a sum of at most 200 products of order one, float32 leaves it within about
+    200 * 2^-24 = 1.2e-5 in the worst case and 1e-6 typically; 2^-16 = 1.5e-5 is beyond both, and costs a few samples in a hundred."""
+    import torch
+
+    x, v = batch(cols, B, n, cadrl)
+    rs = np.random.RandomState(77000 + 1000 * B + n)
+    for _ in range(50):
+        near = relu_margins(model, x) < KINK_MARGIN
+        if not near.any():
+            return x, v
+        x[torch.from_numpy(near)] = torch.from_numpy(rs.uniform(-1, 1, (int(near.sum()),) + tuple(x.shape[1:])).astype(F32))
+    raise AssertionError("no minibatch away from the ReLUs' kinks in 50 draws")
+
+
+def masked_batch(B, n, zero_rows):
+    x, v = batch(13, B, n)
+    x[:, list(zero_rows), :] = 0.0
+    return x, v
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(family, key, B, n):
+    """(model, cols, x, v, references) of one case of the edge suites, computed once and shared by the CPU and the GPU suite.  `family`,
+    `key`: "sarl" (cols, with_global), "full" with_global, "depth" (name, with_global), "masked" zero rows, "cadrl" None."""
+    if family == "sarl":
+        model, cols = seeded_sarl(*key), key[0]
+    elif family == "full":
+        model, cols = full_sarl(key), 13
+    elif family == "depth":
+        model, cols = depth_sarl(*key), 13
+    elif family == "masked":
+        model, cols = masked_sarl(), 13
+    else:
+        model, cols = cadrl_module(13), 13
+        draw_weights(model, 2339, calm=False)
+    # (a masked human's zeros are exact in every precision: 0 > 0 is false on both sides, no kink to stay away from)
+    x, v = masked_batch(B, n, key) if family == "masked" else batch_away_from_kinks(model, cols, B, n, cadrl=family == "cadrl")
+    return model, cols, x, v, references(model, x, v)
+
+
+def grid_of(kind, dims, cols, B, n):
+    """(P, the workgroups cs_value_net_loss_grad launches for B samples of n humans): cs_value_net_grad_sizes gives P and
+    n_scratch = grid * up(P + 1, 4).  No device call."""
+    import ctypes as C
+
+    from social_navigation_pyenvs_amd import _lib
+
+    lib = _lib.load()
+    d = np.ascontiguousarray(dims, np.int32)
+    params, scratch = C.c_size_t(0), C.c_size_t(0)
+    rc = lib.cs_value_net_grad_sizes(kind, d.ctypes.data, len(d), cols, B, n, C.byref(params), C.byref(scratch))
+    assert rc == 0, lib.cs_last_error().decode()
+    region = (params.value + 1 + 3) // 4 * 4
+    assert scratch.value % region == 0
+    return params.value, scratch.value // region
+
+
+def spotlight(model, x, values, S):
+    """The spotlight construction: every sample outside S takes the kernel's own value (float32 [B], bit for bit) as its target -- its
+    d = V - target is exactly 0, so is its share of every sum -- and a sample of S takes value + 1.  Returns (targets [B, 1], (loss32, g32),
+    (loss64, g64)): what the whole minibatch's loss and gradient then are, from autograd on the sub-batch x[S] (MSELoss there divides by
+    |S|, the kernel by B: times |S| / B)."""
+    import torch
+
+    S = list(S)
+    t = np.array(values, F32, copy=True)
+    t[S] = t[S] + F32(1.0)
+    targets = torch.from_numpy(t.reshape(-1, 1))
+    scale = len(S) / x.shape[0]
+    out = []
+    for double in (False, True):
+        loss, g = autograd(model, x[S], targets[S], double=double)
+        out.append((loss * scale, [a * scale for a in g]))
+    return targets, out[0], out[1]
