@@ -55,12 +55,12 @@
         }
         // the Gym's observation of the stepped crowd (SocialNavGym.compute_humans_observable_state, social_nav_gym.py:100-105) straight
         // from the registers: what cs_gym_observe would read back from the rows just written
-        if (KARG(obs) != nullptr && human) {
+        if (CS_RARE(KARG(obs) != nullptr) && human) {
             float* ob = KARG(obs) + ((long)w * n + row) * KARG(obs_cols);
             ob[0] = px; ob[1] = py; ob[2] = vx; ob[3] = vy; ob[4] = r;
             if (KARG(obs_cols) == 7) { ob[5] = th; ob[6] = om; }
         }
-        if (is_robot && robot_moves && KARG(robot) != nullptr) {
+        if (CS_RARE(robot_moves && KARG(robot) != nullptr) && is_robot) {
             float* rb = KARG(robot) + (long)w * 13;
             rb[0] = px; rb[1] = py; rb[2] = th; rb[3] = vx; rb[4] = vy;
         }
@@ -73,7 +73,7 @@
         }
     }
     if constexpr (FOLD) {
-        if (KARG(gym.out) != nullptr && KARG(gym.fold.on)) {
+        if (CS_RARE(KARG(gym.out) != nullptr && KARG(gym.fold.on))) {
             // The take-over's arguments (GymFold: the copy's twenty pointers and strides) are read HERE, through a pointer the optimiser cannot
             // see through: read as kernel arguments they are all requested at the kernel's entry and held in scalar registers across the
             // substep loop -- the per-agent build spilled 350 of them to vector lanes and lost 4 % on every launch, folding or not.

@@ -40,6 +40,13 @@ __device__ __forceinline__ void for_each_index(F&& f, std::integer_sequence<int,
 // load above the store.  This compiler-only fence pins the program order of the LDS accesses around it.
 #define LDS_ORDER_FENCE() asm volatile("" ::: "memory")
 
+// A wave-uniform test whose block a launch rarely or never enters (a recorder, a vote on a rare event, a kernel argument a plain cs_step
+// leaves null): weighted so that the block is laid out behind the code that follows it and the common path falls through -- a branch
+// not taken instead of a jump over the block.  The weight moves blocks, never an instruction's operands.  RARE_WEIGHTS (k_sfm_step)
+// names the builds that take it.
+#define CS_RARE(c) (RARE_WEIGHTS ? __builtin_expect(!!(c), 0) : !!(c))
+#define CS_RARE_HEAD(c) (HEAD_WEIGHT ? __builtin_expect(!!(c), 0) : !!(c))   // (the Gym head's test: rare only where a plain cs_step is the usual launch)
+
 // reaction accumulator rows of the pair-once loop (independent LDS read-modify-write chains) = partners per group.  Measured at
 // 4096 x 25 (same-box A/B): 6 rows 38.5 us, 4 rows 35.9, 3 rows 34.2, 2 rows 32.5, 1 row 32.8 -- every row costs a 1 KB zeroing store
 // and two 512 B reads in the reaction sum per wavefront-substep, and the LDS pipe of a CU (128 B/clk, 8 wavefronts) is ~40 % busy
@@ -83,7 +90,10 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     constexpr bool POLICY = (LEAN_ARG & LEAN_POLICY) != 0;
     static_assert(!POLICY || (MAXT == 64 && (LEAN == LEAN_PLAIN || LEAN == LEAN_ROBOT_ROW)), "the policy is decided in the head of the plain crowd batch's builds without walls");
     extern __shared__ __align__(16) unsigned char smem_raw0[];
-    const int wave_in_wg = MAXT == 64 ? (int)(threadIdx.x >> 6) : 0;
+    // (the one-wavefront builds: a wavefront's number is the same in all of its lanes, but threadIdx.x is a vector register and whatever is
+    //  formed from it is divergent to the compiler -- a test of vblock then opens an exec region.  Read from the first lane it is a scalar,
+    //  and so is what is derived from it alone: the LDS slice, vblock, the priority turn's prio_young.)
+    const int wave_in_wg = MAXT == 64 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     unsigned char* smem_raw = smem_raw0 + (MAXT == 64 ? (size_t)wave_in_wg * a.lds_per_wave : 0);
     const int vblock = MAXT == 64 ? (int)blockIdx.x * a.wg_waves + wave_in_wg : (int)blockIdx.x;   // the one-wavefront block this wavefront is
 #ifdef CS_STAMPS
@@ -168,12 +178,25 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     // (The branch around the invisible robot's five loads stays out of the policy twins: with it the ones with a heading gain a stack
     // frame, 36 bytes of scratch where they had none; a policy launch always has a robot, so the branch would always be taken.)
     constexpr bool ROBOT_LOADS_BRANCH = LAUNCH_TRIM && !POLICY;
+    // The one-wavefront builds weight their rare wave-uniform tests (CS_RARE above): in the substep loop the recorders, the carried
+    // goal-switch vote, the contact votes and the respawn vote, around it the kernel-argument tests of what a plain cs_step never uses
+    // (Gym head, invisible robot, staged take-over, trace, observation and robot rows).  A quiet substep of the plain one-wavefront builds
+    // is straight-line code from the loop's head to the back edge, which is the older wavefront's priority test as well.
+    // No build takes more scratch or fewer waves for it (tools/kernel_resources.sh over every unit, HISTORY.md); three exceptions keep it so:
+    //  * the builds of one world per block (MAXT = 1024), which spill, take 8 to 16 bytes of scratch more weighted: unweighted;
+    //  * the Gym head's test is weighted only where a plain cs_step is the usual launch, the plain crowd batch with or without walls.  A
+    //    build with a robot row or a policy is stepped by a Gym, whose every launch runs the head, and the generic build serves whatever
+    //    no other build takes; in those the weight also cost a stack frame, 20 to 36 bytes of scratch where there was none;
+    //  * the generic one-wavefront Helbing HSFM build with per-agent parameters takes 36 bytes of scratch weighted, none without:
+    //    unweighted, as VOTED_SWITCH leaves out the pair that spills.
+    constexpr bool RARE_WEIGHTS = MAXT == 64 && !(LEAN_ARG == LEAN_GENERIC && SOC == 0 && HEADED == 1 && !PEQ && ROWS_CT == 0);
+    constexpr bool HEAD_WEIGHT = RARE_WEIGHTS && (LEAN_ARG == LEAN_PLAIN || LEAN_ARG == LEAN_WALLS);
 
     // the load phase: every global load of the prologue issued before the first use (one memory round trip); the row, the parameter rows, the goal list, the world flag, the action, the Gym head's inputs
 #include "sfmstep_load.inc"
     // the prologue: per-launch constants, wall segments and polygon circles staged in LDS, the Gym step's head (cs_gym_step), substep-0 rows published, the (agent, polygon) pairs of the wall pass numbered (LEAN = 2)
 #include "sfmstep_prologue.inc"
-    const bool prio_young = MAXT == 64 && vblock >= a.young_from;
+    const bool prio_young = MAXT == 64 && vblock >= a.young_from;   // (a scalar: vblock is one, see wave_in_wg)
     // base priority 1: above the generator's wavefronts of a refill pass on the side stream (priority 0, and OLDER than any of mine, so a tie
     // would go to them): the Gym step in NEXT_STEP mode 43.3 -> 41.5 us, a plain launch unchanged
     if constexpr (MAXT == 64) __builtin_amdgcn_s_setprio(1);
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(MAXT == 64 ? 64 * WG_WAVES_MAX : MAXT, OCC) void k_
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_loop_end)::"memory");
 #endif
 
-    if (a.trace != nullptr && (human || is_robot) && a.nsub > 0)
+    if (CS_RARE(a.trace != nullptr && a.nsub > 0) && (human || is_robot))
         write_trace(a.trace + (((long)(a.nsub - 1) * a.W + w) * rows + row) * 12, px, py, th, vx, vy, bvx, bvy, om, gx, gy, g0x, g0y);
 
     // the epilogue: the row written back once per launch, goal lists, observation rows, robot rows, and the take-over of a staged episode (cs_gym_step_staged)

@@ -50,7 +50,7 @@
         // it here, ahead of the phase's one wait (its first use is in the prologue)
         ax = 0.0f; ay = 0.0f;
         if constexpr (!POLICY) {   // (POLICY: the action is decided in the prologue)
-            if (robot_moves) { ax = ld_off(a.action, (unsigned)wc * 8u); ay = ld_off(a.action + 1, (unsigned)wc * 8u); }
+            if (CS_RARE(robot_moves)) { ax = ld_off(a.action, (unsigned)wc * 8u); ay = ld_off(a.action + 1, (unsigned)wc * 8u); }
         }
     } else {
         const float* ap = (robot_moves && !POLICY) ? a.action + (long)wc * 2 : dummy;   // (POLICY: the action is decided in the prologue)
@@ -100,7 +100,7 @@
     float irb[5] = {0, 0, 0, 0, 0};
     // (ROBOT_LOADS_BRANCH, sfmstep_kernel.h: behind the wave-uniform half of that test -- a launch that moves no invisible robot issues none
     //  of the five; one that does issues them here, ahead of the phase's one wait, as the other arm does)
-    if (!ROBOT_LOADS_BRANCH || (robot_moves && a.robot != nullptr && !(kmode & M_PEEK))) {
+    if (!ROBOT_LOADS_BRANCH || CS_RARE(robot_moves && a.robot != nullptr && !(kmode & M_PEEK))) {
         const float* rb = moves_invisible_robot ? a.robot + (long)w * 13 : dummy;
         irb[0] = rb[0]; irb[1] = rb[1]; irb[2] = rb[2]; irb[3] = rb[3]; irb[4] = rb[4];
     }
@@ -117,7 +117,7 @@
     GymPre hpre = {0.0f, 0, 0, 0, 0u, 0u};
     int fold_code_world = 0;   // (FOLD) the head's verdict for my world, in every lane of it (set in the prologue)
     if constexpr (MAXT == 64) {
-        if (a.gym.out != nullptr && valid) {
+        if (CS_RARE_HEAD(a.gym.out != nullptr) && valid) {
             const float* rb = a.robot + (long)w * 13;      // the robot BEFORE its move of substep 1
             hrb[0] = rb[0]; hrb[1] = rb[1]; hrb[2] = rb[8]; hrb[3] = rb[10]; hrb[4] = rb[11]; hrb[5] = rb[2];
             if constexpr (POLICY) { prb[0] = rb[3]; prb[1] = rb[4]; prb[2] = rb[12]; }

@@ -97,7 +97,7 @@
     //      distances by the humans' lanes, then the lane of row 0 walks its world's in index order and does the episode bookkeeping
     //      (gymhead.h: the very code of k_collision_reward_wave).  One scalar branch in a plain cs_step.
     if constexpr (MAXT == 64) {
-        if (a.gym.out != nullptr) {
+        if (CS_RARE_HEAD(a.gym.out != nullptr)) {
             float* clo = lds_g0x;                              // [T] (the block-respawn scratch: unused by a block of one wavefront)
             const float rpx = hrb[0], rpy = hrb[1], rr = hrb[2], rgx = hrb[3], rgy = hrb[4];   // (loaded at the top)
             float gax = hact[0], gay = hact[1];
@@ -120,7 +120,7 @@
     // invisible robot (it does not interact with the crowd): the lane of row 0 advances it over the launch's substeps from the columns the load
     // phase brought (the head above has the state BEFORE the move in its own registers) and stores it at once -- a world that takes a staged
     // episode over at the end of the launch overwrites the row behind this store (same wavefront, same address: program order)
-    if (moves_invisible_robot) {
+    if (CS_RARE(robot_moves && a.robot != nullptr) && moves_invisible_robot) {   // (the wave-uniform half first: a launch without a robot branches once)
         float* rb = a.robot + (long)w * 13;
         float qx = irb[0], qy = irb[1], qt = irb[2], qvx = irb[3], qvy = irb[4];
         if (a.flags & CS_ROBOT_UNICYCLE) {

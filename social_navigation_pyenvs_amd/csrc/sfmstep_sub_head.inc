@@ -2,10 +2,14 @@
 // Not a translation unit and not a function: it reads and writes the kernel's locals (the lane's row in registers, the LDS views, the
 // template parameters).  The split is textual -- the token stream of the kernel is what it was in one file -- so that each phase can be
 // read on its own; sfmstep_kernel.h lists the phases in order.  gfx950 only.
-        if constexpr (MAXT == 64) { if (prio_young) { if (sub & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); } }
+        // (prio_young is a scalar, sfmstep_kernel.h, where the test of a vector vblock opened an exec region in every substep.  As compiled in the
+        //  headline build the turn sits in front of the loop's head: the older wavefront of a SIMD takes the back edge straight to the head
+        //  -- its priority test IS the back edge --, the younger falls out of it, jumps to the turn and falls into the head.  The turn as
+        //  "1, then 2 on an odd substep": one branch inside it instead of two around its two arms; priorities as before, 2 / 1 on odd / even.)
+        if constexpr (MAXT == 64) { if (CS_RARE(prio_young)) { __builtin_amdgcn_s_setprio(1); if (sub & 1) __builtin_amdgcn_s_setprio(2); } }
         const int nxt = cur ^ 1;
         STAMP(7);
-        if (a.snap != nullptr || a.trace != nullptr) {   // (one scalar branch for both recorders: neither is on in a plain cs_step)
+        if (CS_RARE(a.snap != nullptr || a.trace != nullptr)) {   // (one scalar branch for both recorders: neither is on in a plain cs_step)
             // imitation block: what the robot's own integrator sees of the crowd at this substep (it runs before update_humans)
             if (a.snap != nullptr && human) a.snap[((long)sub * a.W + w) * n + row] = make_float4(px, py, vx, vy);
             // cs_step_trace: my row as the previous substep left it (the last one is written behind the loop)
@@ -100,7 +104,7 @@
             // -- goal switch, forces_parallel.py:226-234, predicated: lists of <= 2 goals rotate in registers.  In the plain one-wavefront
             //    builds (VOTED_SWITCH, sfmstep_kernel.h) behind one scalar branch on the vote the previous substep's tail took on this
             //    very row: a wavefront none of whose lanes stands within r of its goal -- the common case -- skips the block.
-            if (!VOTED_SWITCH || carried_hit != 0ull) {
+            if (!VOTED_SWITCH || CS_RARE(carried_hit != 0ull)) {
                 const float gdx = g0x - px, gdy = g0y - py;
                 const bool hit = human && fmaf(gdx, gdx, gdy * gdy) <= r * r;
                 const bool sw = hit && gk == 2;

@@ -250,7 +250,7 @@
                     // (the vote is taken on the UNREFINED distance d2 * v_rsq(d2), 2.5 ulp off: a tenth of a millimetre of slack -- a pair that is
                     //  not in contact after all adds exact zeros)
                     const bool touches = rdmax > -my_rs - 1.0e-4f;
-                    if (__builtin_amdgcn_ballot_w64(touches) != 0) {
+                    if (CS_RARE(__builtin_amdgcn_ballot_w64(touches) != 0)) {
 #ifdef CS_STAMPS
                         st_acc[11] += 1000;
 #endif
@@ -277,7 +277,7 @@
                 }
                 if constexpr (SOC != 2) {
                     fsx *= sp.sA; fsy *= sp.sA;
-                    if (__builtin_amdgcn_ballot_w64(rdmax > -my_rs) != 0) { // contact somewhere in this wavefront
+                    if (CS_RARE(__builtin_amdgcn_ballot_w64(rdmax > -my_rs) != 0)) { // contact somewhere in this wavefront
 #ifdef CS_STAMPS
                         st_acc[11] += 1000;   // (diagnostic: how often the contact pass runs, per mille of the substeps)
 #endif

@@ -83,7 +83,7 @@
                     }
                     fsx = sp.sA * eax; fsy = sp.sA * eay;
                     if constexpr (SOC == 1) { fsx = fmaf(sp.sC, ecx, fsx); fsy = fmaf(sp.sC, ecy, fsy); }
-                    if (__builtin_amdgcn_ballot_w64(rdmax > -my_rs) != 0) { // contact somewhere in this wavefront
+                    if (CS_RARE(__builtin_amdgcn_ballot_w64(rdmax > -my_rs) != 0)) { // contact somewhere in this wavefront
                         for (int j = 0; j < rows; ++j) {
                             const float4 q = pp[j];
                             const float2 vj = partner_vel(j);

@@ -15,7 +15,7 @@
         // scalar branch on the tail's vote (EARLY_VOTES, sfmstep_kernel.h); a wavefront that does re-runs the next goal switch (the rule
         // moves rows and their goals[0]: the tail's vote was on the rows of before), the others hand the tail's vote on as it is
         if constexpr (EARLY_VOTES) {
-            if (flag_any) {
+            if (CS_RARE(flag_any)) {
 #include "sfmstep_sub_respawn.inc"
                 hit_next = ~0ull;
             }

@@ -4,7 +4,7 @@ O = sys.argv[1]
 res = {}
 for ns in (1, 20):
     acc = collections.defaultdict(list)
-    for f in glob.glob(O + "/ns%d/**/*counter_collection.csv" % ns, recursive=True):
+    for f in glob.glob(O + "/ns%d/**/*counter_collection.csv" % ns, recursive=True) + glob.glob(O + "/ns%db/**/*counter_collection.csv" % ns, recursive=True):   # (ns<k>b: the branch counter's own pass)
         for r in csv.DictReader(open(f)):
             if "k_sfm_step" in r["Kernel_Name"]:
                 acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
