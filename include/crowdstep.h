@@ -753,6 +753,39 @@ int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_wei
                              int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_loss_grad_lstm  cs_value_net_loss_grad for LSTM-RL (crowd_nav/policy/lstm_rl.py:9-65, ValueNetwork1 and ValueNetwork2;
+ *   csrc/value_net_lstm_grad.hip): what crowd_nav/utils/trainer.py:50-71 does per minibatch before optimizer.step() -- zero_grad,
+ *   outputs = model(inputs), loss = MSELoss(outputs, values), loss.backward() -- by backpropagation through time, in two launches on `stream`.
+ *   dims, d_weights are what cs_value_net_decide_lstm takes (cs_value_net_pack_lstm's blob for `cols`).  d_params holds the same parameters
+ *   flat, in torch's own layout and cs_value_net_pack_lstm's order: mlp1's (weight [N][K] row-major, bias [N]) pairs, weight_ih [4H][in],
+ *   weight_hh [4H][H], bias_ih [4H], bias_hh [4H], mlp's pairs (n_param_floats: cs_value_net_grad_sizes_lstm).  d_rows [B][n][cols] are B
+ *   stored states, n <= CS_VN_LSTM_MAX_N; a sample's rows are evaluated as they lie (cs_value_net_decide_lstm's sorted_by_distance = 0; the
+ *   kernel does not sort), its self state is the first six columns of its first row.  d_targets [B] are the target values.  d_grad (the
+ *   layout of d_params; written, not accumulated) = d/dtheta mean_b (V_b - target_b)^2, d_loss the loss, d_values [B] (may be NULL) the
+ *   network's outputs: number for number what cs_value_net_decide_lstm returns for these rows with A = 1, sorted_by_distance = 0, zero
+ *   rewards and dt = 0 (the same fmaf chain per gate from b_ih + b_hh, the same sigmoid and tanh on v_exp_f32 / v_rcp_f32).  The backward
+ *   takes the derivatives from the stored activations (sigma' = s (1 - s), tanh' = 1 - t^2); bias_ih's and bias_hh's gradients are the same
+ *   bytes; with n = 1 weight_hh's gradient is exactly 0; hidden units beyond H (the blob's padding to 8) contribute and receive nothing.
+ *   d_scratch of n_scratch_floats (at least cs_value_net_grad_sizes_lstm's figure) holds per workgroup (one per 32 samples, at most 256) its
+ *   partial gradient [P + 1, rounded up to 4] and behind it its TAPE, the gates, the cell state and h of every step, [n][6][32][H rounded up
+ *   to 8] floats, which the workgroup writes in its forward and reads back itself in its backward.  The partial gradients are summed in a
+ *   fixed order: no atomics, the same call gives the same bytes; the bits may depend on B.  float32.
+ *   Errors (CS_ERR_ARG, before any device call): those of cs_value_net_decide_lstm's network description, B < 1, n < 1,
+ *   n > CS_VN_LSTM_MAX_N, a null pointer other than d_values, a blob or parameter array of another size, a scratch that is too small, a
+ *   network whose tile (every layer's activations of 32 rows, two gradient buffers, the gate gradients [32][4H]) does not fit the 160 KiB of LDS.
+ * cs_value_net_grad_sizes_lstm  (host only) the lengths of d_params and of d_scratch for such a call, in floats.
+ * cs_value_net_pack_lstm_device  cs_value_net_pack_lstm on the device, one launch on `stream`: d_blob (n_blob_floats =
+ *   cs_value_net_pack_lstm's figure) from the flat d_params, byte for byte what cs_value_net_pack_lstm writes for the same numbers -- the gate
+ *   rows in the order 8 * gate + unit, bias_ih + bias_hh summed in float32, the zero padding.
+ */
+int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats);
+int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                                float* d_loss, float* d_values /* may be NULL */, float* d_scratch, size_t n_scratch_floats, void* stream);
+int cs_value_net_pack_lstm_device(const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
+                                  size_t n_blob_floats, void* stream);
+
+/*
  * cs_value_net_decide_lstm_om  cs_value_net_decide_lstm for OM-LSTM-RL (lstm_rl.with_om = true; csrc/value_net_lstm.hip
  *   k_value_net_lstm_om): the rows of the recurrent network carry om_cols occupancy-map columns behind the rotated ones.
  *   With perm_a the evaluation order of (w, a) -- cs_value_net_decide_lstm's rank rule on column 11 of that pair's rows, the identity

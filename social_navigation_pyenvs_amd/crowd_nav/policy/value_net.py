@@ -36,7 +36,11 @@ The optimisation step of the feed-forward family has kernels too (csrc/value_net
 ``param_offsets`` is the flat parameter layout, ``pack_on_device`` (cs_value_net_pack_device) writes the float32 blob from the flat
 parameters without leaving the device, ``loss_and_grad`` (cs_value_net_loss_grad) is the forward, the mean-squared-error loss and the whole
 gradient of a minibatch of stored rows; ``DeviceNet.adopt_flat`` is a trainer's word that the module's parameters are views of such a flat
-tensor (crowd_nav/utils/trainer.py ``Trainer.set_gradient("device")``).  The other families are refused with GRADIENT_REFUSAL."""
+tensor (crowd_nav/utils/trainer.py ``Trainer.set_gradient("device")``).  The other families are refused with GRADIENT_REFUSAL.
+
+The recurrent family without map columns has the same three under names of its own (csrc/value_net_lstm_grad.hip: backpropagation through
+time; ``has_recurrent_gradient_kernel``): ``grad_sizes_lstm``, ``pack_lstm_on_device`` (cs_value_net_pack_lstm_device) and
+``loss_and_grad_lstm`` (cs_value_net_loss_grad_lstm), ``param_offsets`` and ``adopt_flat`` serve both; the trainer's mode is "device_lstm"."""
 from __future__ import annotations
 
 import ctypes as C
@@ -114,12 +118,21 @@ def family_of(kind, om_cols=0):
 
 
 GRADIENT_REFUSAL = ("{0}: the fused loss-and-gradient kernel (cs_value_net_loss_grad) covers the feed-forward networks, CADRL's and SARL's; "
-                    "a network with occupancy-map columns or an LSTM keeps torch's autograd")
+                    'an LSTM without map columns has its own (cs_value_net_loss_grad_lstm: the *_lstm helpers, Trainer.set_gradient("device_lstm")); '
+                    "a network with occupancy-map columns keeps torch's autograd")
+RECURRENT_GRADIENT_REFUSAL = ("{0}: the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm) covers LSTM-RL's two networks on rows of "
+                              '13 or 15 columns; CADRL and SARL have cs_value_net_loss_grad (Trainer.set_gradient("device")), a network with '
+                              "occupancy-map columns (OM-SARL, OM-LSTM-RL) keeps torch's autograd")
 
 
 def has_gradient_kernel(family):
     """Whether a family's networks have the fused loss-and-gradient kernel (cs_value_net_loss_grad): the feed-forward ones alone."""
     return family is FEED_FORWARD
+
+
+def has_recurrent_gradient_kernel(family):
+    """Whether a family's networks have the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm): LSTM-RL without map columns."""
+    return family is RECURRENT
 
 
 def check_map_order(map_order):
@@ -239,7 +252,7 @@ class DeviceNet:
         key = self._versions()
         if self.flat is not None and precision == "f32":        # the parameters are views of `flat` (adopt_flat): packed where they lie
             if key != self._keys[precision]:
-                pack_on_device(self, self.flat)
+                (pack_lstm_on_device if has_recurrent_gradient_kernel(self.family) else pack_on_device)(self, self.flat)
                 self._keys[precision] = key
             return self.blobs[precision]
         if key != self._keys[check_precision(precision)]:
@@ -250,10 +263,11 @@ class DeviceNet:
 
     def adopt_flat(self, flat):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
-        ``Trainer.set_gradient("device")`` makes them): from now on ``refresh("f32")`` packs the blob on the device
-        (``pack_on_device``) when a parameter's version changed, with no host round trip.  None takes the word back."""
+        ``Trainer.set_gradient("device")`` or ``("device_lstm")`` makes them): from now on ``refresh("f32")`` packs the blob on the device
+        (``pack_on_device``, or ``pack_lstm_on_device`` for a recurrent net) when a parameter's version changed, with no host round trip.
+        None takes the word back."""
         if flat is not None:
-            if not has_gradient_kernel(self.family):
+            if not has_gradient_kernel(self.family) and not has_recurrent_gradient_kernel(self.family):
                 raise ValueError(GRADIENT_REFUSAL.format("adopt_flat"))
             total = param_offsets(self)[-1]
             if not flat.is_cuda or flat.dtype != _torch().float32 or flat.dim() != 1 or flat.numel() != total or not flat.is_contiguous():
@@ -352,6 +366,65 @@ def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
     _lib.check(_lib.load().cs_value_net_loss_grad(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
                                                   grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
                                                   scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    return loss
+
+
+def _grad_lead_lstm(net, caller):
+    if not has_recurrent_gradient_kernel(net.family):
+        raise ValueError(RECURRENT_GRADIENT_REFUSAL.format(caller))
+    return (net.dims.ctypes.data, len(net.dims))
+
+
+def pack_lstm_on_device(net, flat, stream=None):
+    """cs_value_net_pack_lstm_device: ``pack_on_device`` for a recurrent `net` -- byte for byte ``pack``'s blob (cs_value_net_pack_lstm)."""
+    from ... import _lib
+
+    lead = _grad_lead_lstm(net, "pack_lstm_on_device")
+    blob = net.blobs["f32"]
+    if blob is None:
+        nf = C.c_size_t(0)
+        _lib.check(_lib.load().cs_value_net_pack_lstm(*lead, net.cols, None, None, C.byref(nf)))
+        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
+    _lib.check(_lib.load().cs_value_net_pack_lstm_device(*lead, net.cols, flat.data_ptr(), flat.numel(), blob.data_ptr(), blob.numel(), _stream(stream)))
+    return blob
+
+
+def grad_sizes_lstm(net, B, n):
+    """cs_value_net_grad_sizes_lstm: (the length of the flat parameters, the scratch floats a minibatch of B samples of n humans needs: a
+    partial gradient and the tape of n steps per workgroup)."""
+    from ... import _lib
+
+    n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.load().cs_value_net_grad_sizes_lstm(*_grad_lead_lstm(net, "grad_sizes_lstm"), net.cols, B, n, C.byref(n_params), C.byref(n_scratch)))
+    return n_params.value, n_scratch.value
+
+
+def loss_and_grad_lstm(net, flat, rows, targets, grad, values=None, stream=None):
+    """cs_value_net_loss_grad_lstm: ``loss_and_grad`` for a recurrent `net` on the minibatch rows [B, n, cols], every sample's rows in the
+    order they lie in; `net`'s float32 blob must hold `flat`'s numbers (``pack_lstm_on_device``).  Returns the loss, a CUDA tensor of one
+    element.  The scratch (partial gradients and tapes) is kept on `net` and grown when a larger minibatch comes."""
+    from ... import _lib
+
+    torch = _torch()
+    _grad_lead_lstm(net, "loss_and_grad_lstm")
+    head = net.head("loss_and_grad_lstm")
+    if rows.dim() != 3:
+        raise ValueError(f"loss_and_grad_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
+    B, n, cols = rows.shape
+    for name, t, numel in (("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()),
+                           ("values", values, B)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"loss_and_grad_lstm: {name} is a contiguous CUDA float32 tensor of {numel} elements")
+    if cols != net.cols:
+        raise ValueError(f"loss_and_grad_lstm: rows of {cols} columns for a network of {net.cols}")
+    _, need = grad_sizes_lstm(net, B, n)
+    scratch = getattr(net, "_grad_scratch", None)
+    if scratch is None or scratch.numel() < need or scratch.device != flat.device:
+        scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
+    loss = torch.empty(1, dtype=torch.float32, device=flat.device)
+    _lib.check(_lib.load().cs_value_net_loss_grad_lstm(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
+                                                       grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
+                                                       scratch.data_ptr(), scratch.numel(), _stream(stream)))
     return loss
 
 

@@ -2,13 +2,16 @@
 the mean-squared error between model(inputs) and the stored target values, an epoch over the memory (``optimize_epoch``) or a number of
 minibatches (``optimize_batch``).
 
-Two ways to the gradient, ``set_gradient``:
+Three ways to the gradient, ``set_gradient``:
 
   "autograd"  (the default) zero_grad, model(inputs), MSELoss, backward -- torch throughout, on any device.
   "device"    for a CADRL / SARL network on the GPU: the module's parameters become views of one flat CUDA tensor and their .grad views of
               another, and a minibatch runs cs_value_net_pack_device (the decision kernels' blob from the flat parameters),
               cs_value_net_loss_grad (forward, loss and the whole gradient, csrc/value_net_grad.hip) and
-              optimizer.step().  The optimiser is torch's and the caller's to replace (``self.optimizer``)."""
+              optimizer.step().  The optimiser is torch's and the caller's to replace (``self.optimizer``).
+  "device_lstm"  the same mechanics for an LSTM-RL network (lstm_rl.ValueNetwork1 / ValueNetwork2 on rows of 13 or 15 columns) on the GPU:
+              cs_value_net_pack_lstm_device and cs_value_net_loss_grad_lstm (backpropagation through time over a sample's rows as they lie,
+              csrc/value_net_lstm_grad.hip)."""
 from __future__ import annotations
 
 import logging
@@ -20,7 +23,7 @@ from torch.utils.data import DataLoader
 
 from ..policy import value_net
 
-GRADIENTS = ("autograd", "device")
+GRADIENTS = ("autograd", "device", "device_lstm")
 
 
 class _MemoryLoader:
@@ -57,10 +60,11 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ the gradient's path
     def set_gradient(self, gradient, net=None):
-        """"autograd" or "device" (the module's docstring).  `net`: the value_net.DeviceNet whose blob "device" keeps current -- a policy's
-        own (``policy.device_net()``), so that its decisions read the trained weights without a host round trip; None: one of the
-        trainer's.  "device" refuses a module that is not CADRL's or SARL's network, a model on the CPU and a memory whose stored states
-        are not [., n, 13 | 15] float32 rows."""
+        """"autograd", "device" or "device_lstm" (the module's docstring).  `net`: the value_net.DeviceNet whose blob the device modes keep
+        current -- a policy's own (``policy.device_net()``), so that its decisions read the trained weights without a host round trip;
+        None: one of the trainer's.  "device" refuses a module that is not CADRL's or SARL's network, "device_lstm" one without an LSTM or
+        with map columns (OM-LSTM-RL); both a model on the CPU, a model that is not float32, a memory whose stored states are not
+        [., n, 13 | 15] float32 rows and a `net` that is not this model's."""
         if gradient not in GRADIENTS:
             raise ValueError(f"gradient {gradient!r}: one of {', '.join(map(repr, GRADIENTS))}")
         if gradient == "autograd":
@@ -71,18 +75,27 @@ class Trainer(object):
         kind, _, layers = value_net.describe(self.model)
         params = [p for layer in layers for p in value_net.layer_params(layer)]
         first = layers[0] if layers else None
-        cols = getattr(first, "in_features", 0)
-        if kind == value_net.CS_VN_LSTM or cols not in (13, 15) or not value_net.has_gradient_kernel(value_net.family_of(kind, 0)):
-            raise ValueError(value_net.GRADIENT_REFUSAL.format('Trainer.set_gradient("device")'))
+        cols = getattr(first, "in_features", getattr(first, "input_size", 0))       # (network 1's first layer is the nn.LSTM itself)
+        who = f'Trainer.set_gradient("{gradient}")'
+        if gradient == "device_lstm":
+            has_kernel, which = value_net.has_recurrent_gradient_kernel, "recurrent"
+            if kind != value_net.CS_VN_LSTM:
+                raise ValueError(f'{who}: the module has no LSTM; CADRL and SARL train with set_gradient("device")')
+            if cols not in (13, 15):
+                raise ValueError(value_net.RECURRENT_GRADIENT_REFUSAL.format(f"{who} on rows of {cols} columns"))
+        else:
+            has_kernel, which = value_net.has_gradient_kernel, "feed-forward"
+            if kind == value_net.CS_VN_LSTM or cols not in (13, 15) or not has_kernel(value_net.family_of(kind, 0)):
+                raise ValueError(value_net.GRADIENT_REFUSAL.format(who))
         if any(not p.is_cuda for p in params):
-            raise ValueError('Trainer.set_gradient("device"): the model is on the CPU; the gradient kernel runs on the GPU (model.to("cuda"))')
+            raise ValueError(f'{who}: the model is on the CPU; the gradient kernel runs on the GPU (model.to("cuda"))')
         if any(p.dtype != torch.float32 for p in params):
-            raise ValueError('Trainer.set_gradient("device"): the gradient kernel is float32')
-        self._check_states(getattr(self.memory, "states", None), cols, kind)
+            raise ValueError(f'{who}: the gradient kernel is float32')
+        self._check_states(getattr(self.memory, "states", None), cols, kind, who)
         if net is None:
             net = value_net.DeviceNet(self.model, cols)
-        elif net.model is not self.model or not value_net.has_gradient_kernel(net.family):
-            raise ValueError('Trainer.set_gradient("device"): the DeviceNet given is not this model\'s feed-forward one')
+        elif net.model is not self.model or not has_kernel(net.family):
+            raise ValueError(f"{who}: the DeviceNet given is not this model's {which} one")
         offsets = value_net.param_offsets(net)
         flat = torch.empty(offsets[-1], dtype=torch.float32, device=params[0].device)
         grad = torch.zeros_like(flat)
@@ -95,18 +108,18 @@ class Trainer(object):
         self.gradient, self.net, self.flat, self.flat_grad = gradient, net, flat, grad
 
     @staticmethod
-    def _check_states(states, cols, kind):
-        """The stored states the gradient kernel takes: float32 [., n, cols] on the GPU ([., cols] as well for CADRL, whose n is 1)."""
+    def _check_states(states, cols, kind, who='Trainer.set_gradient("device")'):
+        """The stored states the gradient kernels take: float32 [., n, cols] on the GPU ([., cols] as well for CADRL, whose n is 1)."""
         if states is None:
             return
         dims = (2, 3) if kind == value_net.CS_VN_CADRL else (3,)
         if states.dim() not in dims or states.shape[-1] != cols or states.dtype != torch.float32:
-            raise ValueError(f'Trainer.set_gradient("device"): the memory\'s states are {tuple(states.shape[1:])} {states.dtype} rows; the gradient '
+            raise ValueError(f"{who}: the memory's states are {tuple(states.shape[1:])} {states.dtype} rows; the gradient "
                              f"kernel takes float32 [n, {cols}]")
 
     def _loader(self):
         if self.data_loader is None:
-            if self.gradient == "device" and hasattr(self.memory, "sample"):
+            if self.gradient != "autograd" and hasattr(self.memory, "sample"):
                 self.data_loader = _MemoryLoader(self.memory, self.batch_size)
             else:
                 self.data_loader = DataLoader(self.memory, self.batch_size, shuffle=True)
@@ -114,13 +127,14 @@ class Trainer(object):
 
     def _step(self, inputs, values):
         """One optimiser step on a minibatch; returns the loss as a Python float."""
-        if self.gradient == "device":
-            self._check_states(inputs, self.net.cols, self.net.kind)
+        if self.gradient != "autograd":
+            self._check_states(inputs, self.net.cols, self.net.kind, f'Trainer.set_gradient("{self.gradient}")')
             self.net.refresh("f32")
             for p in self.model.parameters():       # (an optimiser's zero_grad(set_to_none) dropped the views: the kernel writes them whole)
                 if p.grad is None:
-                    raise ValueError('Trainer: a parameter lost its gradient view; call set_gradient("device") again')
-            loss = value_net.loss_and_grad(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
+                    raise ValueError(f'Trainer: a parameter lost its gradient view; call set_gradient("{self.gradient}") again')
+            kernel = value_net.loss_and_grad_lstm if self.gradient == "device_lstm" else value_net.loss_and_grad
+            loss = kernel(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
             self.optimizer.step()
             return loss.item()
         self.optimizer.zero_grad()
