@@ -687,6 +687,31 @@ int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dims, int cols
                              size_t n_blob_floats, void* stream);
 
 /*
+ * cs_value_net_train_step  one whole optimisation step of trainer.py:50-71 for a CADRL / SARL network in two launches on `stream`:
+ *   cs_value_net_loss_grad's job kernel, unchanged, then one kernel (csrc/value_net_grad.h k_vn_sgd) that per parameter i of
+ *   the flat layout sums the workgroups' partial gradients in their fixed order -- d_grad, d_loss and d_values receive the bytes
+ *   cs_value_net_loss_grad gives for the same inputs --, takes torch.optim.SGD's step with momentum (dampening 0, no Nesterov, no weight
+ *   decay): d_momentum[i] = momentum * d_momentum[i] + d_grad[i], d_params[i] -= lr * d_momentum[i], each one float32 fused multiply-add,
+ *   and rewrites the float of d_weights that reads parameter i: afterwards d_weights is byte for byte cs_value_net_pack's blob of the
+ *   updated parameters, its zero padding untouched.  d_params and d_weights are in/out; on entry d_weights must be the blob of d_params
+ *   (cs_value_net_pack_device).  d_momentum (n_momentum_floats = n_param_floats; zeros before the first step, as torch's first step
+ *   takes buf = grad) is in/out.  d_loss_sum (may be NULL): a device double to which the step adds (double)*d_loss -- the float64 sum the
+ *   reference's loops form on the host from loss.item(), without a read-back per minibatch.  No atomics: the same call from the same
+ *   state gives the same bytes everywhere.
+ *   Errors (CS_ERR_ARG, before any device call): cs_value_net_loss_grad's, a null d_momentum, a momentum buffer of another size, an lr
+ *   that is not finite or negative, a momentum that is not finite or negative.
+ * cs_value_net_blob_index  (host only) the map the update kernel writes the blob by, evaluated by the same code: index[i] (n_param_floats
+ *   entries, cs_value_net_grad_sizes) is the float of cs_value_net_pack's blob that holds parameter i of the flat layout.  Every
+ *   parameter has a float of its own; the blob's other floats are its zero padding.
+ */
+int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                            size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                            int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                            double* d_loss_sum /* may be NULL */, float* d_values /* may be NULL */, float* d_scratch,
+                            size_t n_scratch_floats, void* stream);
+int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats);
+
+/*
  * cs_occupancy_maps OM-SARL's local occupancy maps (crowd_nav/policy/multi_human_rl.py:133-187 build_occupancy_maps) for W worlds in
  *   one kernel on `stream` (csrc/occupancy_map.hip).  d_humans [W][n][stride] holds a human's position at columns 0, 1
  *   and its velocity at vel_col, vel_col + 1: cs_lookahead's d_next [W][n][4|6] (vel_col 2 | 3) and d_current [W][n][5|7] (vel_col 2)
@@ -784,6 +809,21 @@ int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_
                                 float* d_loss, float* d_values /* may be NULL */, float* d_scratch, size_t n_scratch_floats, void* stream);
 int cs_value_net_pack_lstm_device(const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
                                   size_t n_blob_floats, void* stream);
+
+/*
+ * cs_value_net_train_step_lstm  cs_value_net_train_step for LSTM-RL: cs_value_net_loss_grad_lstm's job kernel, unchanged, then the same
+ *   update kernel on the recurrent blob's map -- the gate rows in the order 8 * gate + unit, and the gates' bias float rewritten as
+ *   bias_ih + bias_hh of the two updated values, summed in float32 as cs_value_net_pack_lstm sums it.  Arguments, results and errors are
+ *   cs_value_net_train_step's with cs_value_net_loss_grad_lstm's in the place of cs_value_net_loss_grad's.
+ * cs_value_net_blob_index_lstm  (host only) cs_value_net_blob_index for the recurrent blob: index[i] is the float of
+ *   cs_value_net_pack_lstm's blob that holds parameter i; bias_ih[row] and bias_hh[row] name the same float, which holds their sum.
+ */
+int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                 size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                                 int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                                 double* d_loss_sum /* may be NULL */, float* d_values /* may be NULL */, float* d_scratch,
+                                 size_t n_scratch_floats, void* stream);
+int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats);
 
 /*
  * cs_value_net_decide_lstm_om  cs_value_net_decide_lstm for OM-LSTM-RL (lstm_rl.with_om = true; csrc/value_net_lstm.hip

@@ -165,7 +165,9 @@ ABI = {
     "cs_value_net_grad_sizes": (I, [I, P, I, I, I, I, P, P]),
     "cs_value_net_loss_grad": (I, [I, P, I, P, Z, P, Z, I, I, I, P, P, P, P, P, P, Z, P]),
     "cs_value_net_pack_device": (I, [I, P, I, I, P, Z, P, Z, P]),
-    "cs_occupancy_maps": (I, [I, I, P, I, I, I, F, I, P, P]),
+    "cs_value_net_train_step": (I, [I, P, I, P, Z, P, Z, P, Z, F, F, I, I, I, P, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_blob_index": (I, [I, P, I, I, P, Z]),
+    "cs_occupancy_maps":(I, [I, I, P, I, I, I, F, I, P, P]),
     "cs_value_net_pack_om": (I, [I, P, I, I, I, P, P, P]),
     "cs_value_net_decide_om": (I, [I, P, I, P, Z, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_pack_lstm": (I, [P, I, I, P, P, P]),
@@ -173,7 +175,9 @@ ABI = {
     "cs_value_net_grad_sizes_lstm": (I, [P, I, I, I, I, P, P]),
     "cs_value_net_loss_grad_lstm": (I, [P, I, P, Z, P, Z, I, I, I, P, P, P, P, P, P, Z, P]),
     "cs_value_net_pack_lstm_device": (I, [P, I, I, P, Z, P, Z, P]),
-    "cs_value_net_pack_lstm_om": (I, [P, I, I, I, P, P, P]),
+    "cs_value_net_train_step_lstm": (I, [P, I, P, Z, P, Z, P, Z, F, F, I, I, I, P, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_blob_index_lstm": (I, [P, I, I, P, Z]),
+    "cs_value_net_pack_lstm_om":(I, [P, I, I, I, P, P, P]),
     "cs_value_net_decide_lstm_om": (I, [P, I, P, Z, I, I, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_step_f64": (I, [WORLDS64, D, I, P, P]),
     "cs_update_humans_parallel_f64": (I, [WORLDS64, D, P, P]),

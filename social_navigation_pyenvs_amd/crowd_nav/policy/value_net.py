@@ -40,7 +40,12 @@ tensor (crowd_nav/utils/trainer.py ``Trainer.set_gradient("device")``).  The oth
 
 The recurrent family without map columns has the same three under names of its own (csrc/value_net_lstm_grad.hip: backpropagation through
 time; ``has_recurrent_gradient_kernel``): ``grad_sizes_lstm``, ``pack_lstm_on_device`` (cs_value_net_pack_lstm_device) and
-``loss_and_grad_lstm`` (cs_value_net_loss_grad_lstm), ``param_offsets`` and ``adopt_flat`` serve both; the trainer's mode is "device_lstm"."""
+``loss_and_grad_lstm`` (cs_value_net_loss_grad_lstm), ``param_offsets`` and ``adopt_flat`` serve both; the trainer's mode is "device_lstm".
+
+``train_step`` / ``train_step_lstm`` (cs_value_net_train_step[_lstm]) are the whole optimisation step of either family: the loss and the
+gradient as above, and in the launch that sums the gradient torch's SGD step with momentum and the float32 blob rewritten from the new
+parameters, with the loss added to a device float64 sum -- nothing is read back (``Trainer.set_update("device")``).
+``DeviceNet.updated_on_device`` is their word that parameters and float32 blob changed together under the version counters."""
 from __future__ import annotations
 
 import ctypes as C
@@ -275,6 +280,16 @@ class DeviceNet:
         self.flat = flat
         self._keys["f32"] = None
 
+    def updated_on_device(self):
+        """The word of ``train_step`` / ``train_step_lstm`` that a kernel updated the flat parameters and rewrote the float32 blob from them
+        in the same launch.  A kernel's write moves no version counter: the float32 key stays valid (no repack, the blob is current), every
+        other precision's key is dropped, so its next ``refresh`` packs from the new numbers."""
+        if self.flat is None:
+            raise ValueError("updated_on_device: the network has adopted no flat parameters (adopt_flat)")
+        for precision in PRECISIONS:
+            if precision != "f32":
+                self._keys[precision] = None
+
     def head(self, caller, precision="f32"):
         """The arguments every network entry of the family opens with, for the blob of `precision`; ValueError in `caller`'s name
         without one."""
@@ -346,27 +361,68 @@ def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
     Returns the loss, a CUDA tensor of one element.  The scratch is kept on `net` and grown when a larger minibatch comes."""
     from ... import _lib
 
-    torch = _torch()
-    lead = _grad_lead(net, "loss_and_grad")
+    _grad_lead(net, "loss_and_grad")
     head = net.head("loss_and_grad")
     if rows.dim() == 2:
         rows = rows[:, None, :]
-    B, n, cols = rows.shape
-    for name, t, numel in (("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()),
-                           ("values", values, B)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel):
-            raise ValueError(f"loss_and_grad: {name} is a contiguous CUDA float32 tensor of {numel} elements")
-    if cols != net.cols:
-        raise ValueError(f"loss_and_grad: rows of {cols} columns for a network of {net.cols}")
-    _, need = grad_sizes(net, B, n)
-    scratch = getattr(net, "_grad_scratch", None)
-    if scratch is None or scratch.numel() < need or scratch.device != flat.device:
-        scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
-    loss = torch.empty(1, dtype=torch.float32, device=flat.device)
+    B, n, cols, scratch, loss = _minibatch("loss_and_grad", net, flat, rows, targets, grad, values, grad_sizes)
     _lib.check(_lib.load().cs_value_net_loss_grad(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
                                                   grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
                                                   scratch.data_ptr(), scratch.numel(), _stream(stream)))
     return loss
+
+
+def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=None, loss_sum=None):
+    """The tensor checks the loss-and-gradient and the train-step seams make alike, in `caller`'s name, and the scratch kept on `net`
+    (`sizes`: grad_sizes or grad_sizes_lstm), grown when a larger minibatch comes: (B, n, cols, scratch, a new tensor for the loss)."""
+    torch = _torch()
+    B, n, cols = rows.shape
+    tensors = [("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()), ("values", values, B)]
+    if momentum is not None:
+        tensors.append(("momentum", momentum, flat.numel()))
+    for name, t, numel in tensors:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"{caller}: {name} is a contiguous CUDA float32 tensor of {numel} elements")
+    if loss_sum is not None and (not loss_sum.is_cuda or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1):
+        raise ValueError(f"{caller}: loss_sum is a CUDA float64 tensor of one element")
+    if cols != net.cols:
+        raise ValueError(f"{caller}: rows of {cols} columns for a network of {net.cols}")
+    _, need = sizes(net, B, n)
+    scratch = getattr(net, "_grad_scratch", None)
+    if scratch is None or scratch.numel() < need or scratch.device != flat.device:
+        scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
+    return B, n, cols, scratch, torch.empty(1, dtype=torch.float32, device=flat.device)
+
+
+def _train_step(caller, entry, sizes, net, flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream):
+    """What ``train_step`` and ``train_step_lstm`` do alike behind their family's checks."""
+    from ... import _lib
+
+    if momentum is None:
+        raise ValueError(f"{caller}: momentum is a contiguous CUDA float32 tensor of {flat.numel()} elements")
+    head = net.head(caller)
+    if net.flat is not flat:
+        raise ValueError(f"{caller}: `flat` is not the tensor the network's parameters are views of (DeviceNet.adopt_flat)")
+    B, n, cols, scratch, loss = _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum, loss_sum)
+    _lib.check(getattr(_lib.load(), entry)(*head, flat.data_ptr(), flat.numel(), momentum.data_ptr(), momentum.numel(), float(lr), float(mu), B, n,
+                                           cols, rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(),
+                                           None if loss_sum is None else loss_sum.data_ptr(), None if values is None else values.data_ptr(),
+                                           scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    net.updated_on_device()
+    return loss
+
+
+def train_step(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
+    """cs_value_net_train_step: ``loss_and_grad`` (the same arguments, checks, scratch and results -- `grad`, the returned loss and `values`
+    are its bytes) and, in the launch that sums the gradient, torch's SGD step with momentum `mu` at learning rate `lr` on `flat` and
+    `momentum` (a CUDA float32 tensor like `flat`: the optimiser's momentum buffers, zeros before the first step) and `net`'s float32 blob
+    rewritten from the new parameters, byte for byte ``pack``'s.  `flat` is the tensor `net` adopted (``adopt_flat``) and its float32 blob
+    holds `flat`'s numbers on entry, as for ``loss_and_grad``.  loss_sum (a CUDA float64 tensor of one element, or None) has the loss added to
+    it on the device.  Nothing is read back.  Ends with ``net.updated_on_device()``."""
+    _grad_lead(net, "train_step")
+    if rows.dim() == 2:
+        rows = rows[:, None, :]
+    return _train_step("train_step", "cs_value_net_train_step", grad_sizes, net, flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream)
 
 
 def _grad_lead_lstm(net, caller):
@@ -405,27 +461,25 @@ def loss_and_grad_lstm(net, flat, rows, targets, grad, values=None, stream=None)
     element.  The scratch (partial gradients and tapes) is kept on `net` and grown when a larger minibatch comes."""
     from ... import _lib
 
-    torch = _torch()
     _grad_lead_lstm(net, "loss_and_grad_lstm")
     head = net.head("loss_and_grad_lstm")
     if rows.dim() != 3:
         raise ValueError(f"loss_and_grad_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
-    B, n, cols = rows.shape
-    for name, t, numel in (("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()),
-                           ("values", values, B)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel):
-            raise ValueError(f"loss_and_grad_lstm: {name} is a contiguous CUDA float32 tensor of {numel} elements")
-    if cols != net.cols:
-        raise ValueError(f"loss_and_grad_lstm: rows of {cols} columns for a network of {net.cols}")
-    _, need = grad_sizes_lstm(net, B, n)
-    scratch = getattr(net, "_grad_scratch", None)
-    if scratch is None or scratch.numel() < need or scratch.device != flat.device:
-        scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
-    loss = torch.empty(1, dtype=torch.float32, device=flat.device)
+    B, n, cols, scratch, loss = _minibatch("loss_and_grad_lstm", net, flat, rows, targets, grad, values, grad_sizes_lstm)
     _lib.check(_lib.load().cs_value_net_loss_grad_lstm(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
                                                        grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
                                                        scratch.data_ptr(), scratch.numel(), _stream(stream)))
     return loss
+
+
+def train_step_lstm(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
+    """cs_value_net_train_step_lstm: ``train_step`` for a recurrent `net` -- ``loss_and_grad_lstm``, the SGD step and the recurrent blob (the
+    gate rows, bias_ih + bias_hh) rewritten, in two launches."""
+    _grad_lead_lstm(net, "train_step_lstm")
+    if rows.dim() != 3:
+        raise ValueError(f"train_step_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
+    return _train_step("train_step_lstm", "cs_value_net_train_step_lstm", grad_sizes_lstm, net, flat, momentum, rows, targets, grad, lr, mu, values,
+                       loss_sum, stream)
 
 
 def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):

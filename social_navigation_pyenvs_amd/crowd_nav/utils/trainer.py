@@ -11,7 +11,18 @@ Three ways to the gradient, ``set_gradient``:
               optimizer.step().  The optimiser is torch's and the caller's to replace (``self.optimizer``).
   "device_lstm"  the same mechanics for an LSTM-RL network (lstm_rl.ValueNetwork1 / ValueNetwork2 on rows of 13 or 15 columns) on the GPU:
               cs_value_net_pack_lstm_device and cs_value_net_loss_grad_lstm (backpropagation through time over a sample's rows as they lie,
-              csrc/value_net_lstm_grad.hip)."""
+              csrc/value_net_lstm_grad.hip).
+
+Two ways to the update, ``set_update``:
+
+  "torch"     (the default) ``self.optimizer.step()``, whatever optimiser the caller put there, and the loss read back per minibatch.
+  "device"    for the two device gradient modes and torch.optim.SGD with momentum (one parameter group, dampening 0, no Nesterov, no weight
+              decay, not maximize -- what ``set_learning_rate`` builds): a minibatch is cs_value_net_train_step[_lstm], two launches -- the
+              gradient kernel, then one kernel that sums the gradient, takes the optimiser's step and rewrites the decision kernels' blob
+              (csrc/value_net_grad.h k_vn_sgd).  lr and momentum are read from the optimiser's group at every step; its
+              momentum buffers are views of one flat tensor the kernel updates, so ``optimizer.state_dict()`` holds them and a switch back to
+              "torch" goes on from them.  The loss is added to a float64 on the device: ``optimize_epoch`` reads it once an epoch,
+              ``optimize_batch`` once a call, nothing else crosses to the host."""
 from __future__ import annotations
 
 import logging
@@ -24,6 +35,7 @@ from torch.utils.data import DataLoader
 from ..policy import value_net
 
 GRADIENTS = ("autograd", "device", "device_lstm")
+UPDATES = ("torch", "device")
 
 
 class _MemoryLoader:
@@ -41,6 +53,24 @@ class _MemoryLoader:
             yield self.memory.states[index], self.memory.values[index]
 
 
+def fused_sgd_settings(optimizer, params=None):
+    """(lr, momentum) of `optimizer` for the fused step ("device" update mode), read from its one parameter group; ValueError, naming what
+    it is, for an optimiser the fused step does not cover: anything but torch.optim.SGD over exactly `params` (None: not compared) in one
+    group with dampening 0, no Nesterov, no weight decay and not maximize.  No device work."""
+    who = 'Trainer.set_update("device")'
+    if not isinstance(optimizer, optim.SGD):
+        raise ValueError(f'{who}: the fused step is torch.optim.SGD with momentum, not {type(optimizer).__name__}; set_update("torch") runs any optimiser')
+    if len(optimizer.param_groups) != 1:
+        raise ValueError(f"{who}: the fused step takes one parameter group, the optimiser has {len(optimizer.param_groups)}")
+    group = optimizer.param_groups[0]
+    for name in ("dampening", "nesterov", "weight_decay", "maximize"):
+        if group.get(name):
+            raise ValueError(f'{who}: the fused step has no {name} ({name} = {group[name]!r}); set_update("torch") runs this optimiser')
+    if params is not None and (len(group["params"]) != len(params) or {id(p) for p in group["params"]} != {id(p) for p in params}):
+        raise ValueError(f"{who}: the optimiser's parameters are not exactly the model's")
+    return float(group["lr"]), float(group["momentum"])
+
+
 class Trainer(object):
     def __init__(self, model, memory, device, batch_size):
         """Train the trainable model of a policy"""
@@ -53,6 +83,9 @@ class Trainer(object):
         self.optimizer = None
         self.gradient = "autograd"
         self.net = self.flat = self.flat_grad = None
+        self.update = "torch"
+        self.momentum = self.loss_sum = self.last_loss = None
+        self._momentum_views, self._sgd_bound = (), None
 
     def set_learning_rate(self, learning_rate):
         logging.info('Current learning rate: %f', learning_rate)
@@ -71,6 +104,7 @@ class Trainer(object):
             if self.net is not None:
                 self.net.adopt_flat(None)
             self.gradient, self.net, self.flat, self.flat_grad = gradient, None, None, None
+            self.update = "torch"
             return
         kind, _, layers = value_net.describe(self.model)
         params = [p for layer in layers for p in value_net.layer_params(layer)]
@@ -107,6 +141,47 @@ class Trainer(object):
         net.adopt_flat(flat)
         self.gradient, self.net, self.flat, self.flat_grad = gradient, net, flat, grad
 
+    # ------------------------------------------------------------------ the update's path
+    def set_update(self, update):
+        """"torch" or "device" (the module's docstring).  "device" needs a device gradient mode (``set_gradient`` first); the optimiser is
+        checked at every step, so it may still be replaced -- by one the fused step covers.  ``set_gradient("autograd")`` takes the mode back
+        to "torch"."""
+        if update not in UPDATES:
+            raise ValueError(f"update {update!r}: one of {', '.join(map(repr, UPDATES))}")
+        if update == "device" and self.gradient == "autograd":
+            raise ValueError('Trainer.set_update("device"): the fused step runs behind a device gradient; call set_gradient("device") '
+                             'or set_gradient("device_lstm") first')
+        self.update = update
+
+    def _sgd(self):
+        """``fused_sgd_settings`` of ``self.optimizer``, its momentum buffers bound to ``self.momentum`` as views.  The binding (and the
+        check of the optimiser's parameters against the model's) is made when the optimiser, its state or its group is another object than
+        at the step before -- a new optimiser, ``load_state_dict``, ``set_gradient`` -- or a buffer is no longer the view bound (torch's
+        first step of its own clones the gradient); a step on the same objects only reads the group's settings again."""
+        opt = self.optimizer
+        bound = self._sgd_bound
+        if (bound is not None and bound[0] is opt and bound[1] is opt.state and bound[2] is opt.param_groups[0] and bound[3] is self.flat
+                and opt.state[bound[4]].get("momentum_buffer") is self._momentum_views[0]):
+            return fused_sgd_settings(opt)
+        params = [p for layer in self.net.layers for p in value_net.layer_params(layer)]
+        settings = fused_sgd_settings(opt, params)
+        if self.momentum is None or self.momentum.numel() != self.flat.numel() or self.momentum.device != self.flat.device:
+            self.momentum = torch.zeros_like(self.flat)
+        # a fresh optimiser starts from zero momentum, buffers that torch's step or load_state_dict made are taken over
+        views = []
+        with torch.no_grad():
+            for p, at in zip(params, value_net.param_offsets(self.net)):
+                view, old = self.momentum[at:at + p.numel()].view(p.shape), opt.state[p].get("momentum_buffer")
+                if old is None:
+                    view.zero_()
+                elif old.data_ptr() != view.data_ptr():
+                    view.copy_(old)
+                opt.state[p]["momentum_buffer"] = view
+                views.append(view)
+        self._momentum_views = tuple(views)
+        self._sgd_bound = (opt, opt.state, opt.param_groups[0], self.flat, params[0])
+        return settings
+
     @staticmethod
     def _check_states(states, cols, kind, who='Trainer.set_gradient("device")'):
         """The stored states the gradient kernels take: float32 [., n, cols] on the GPU ([., cols] as well for CADRL, whose n is 1)."""
@@ -125,14 +200,31 @@ class Trainer(object):
                 self.data_loader = DataLoader(self.memory, self.batch_size, shuffle=True)
         return self.data_loader
 
+    def _device_inputs(self, inputs):
+        """What a minibatch of either device gradient mode is checked for before its launches; leaves the float32 blob current."""
+        self._check_states(inputs, self.net.cols, self.net.kind, f'Trainer.set_gradient("{self.gradient}")')
+        self.net.refresh("f32")
+        for p in self.model.parameters():       # (an optimiser's zero_grad(set_to_none) dropped the views: the kernel writes them whole)
+            if p.grad is None:
+                raise ValueError(f'Trainer: a parameter lost its gradient view; call set_gradient("{self.gradient}") again')
+
+    def _enqueue_fused_step(self, inputs, values):
+        """One optimiser step of "device" update mode on a minibatch, enqueued: nothing is read back, the loss is added to
+        ``self.loss_sum`` on the device and left in ``self.last_loss`` (a CUDA tensor of one element)."""
+        self._device_inputs(inputs)
+        lr, momentum = self._sgd()
+        kernel = value_net.train_step_lstm if self.gradient == "device_lstm" else value_net.train_step
+        self.last_loss = kernel(self.net, self.flat, self.momentum, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad,
+                                lr, momentum, loss_sum=self._device_sum())
+
     def _step(self, inputs, values):
-        """One optimiser step on a minibatch; returns the loss as a Python float."""
+        """One optimiser step on a minibatch; returns the loss as a Python float (a read-back in every mode: the loops of "device" update
+        mode enqueue their steps with ``_enqueue_fused_step`` instead)."""
+        if self.update == "device":
+            self._enqueue_fused_step(inputs, values)
+            return self.last_loss.item()
         if self.gradient != "autograd":
-            self._check_states(inputs, self.net.cols, self.net.kind, f'Trainer.set_gradient("{self.gradient}")')
-            self.net.refresh("f32")
-            for p in self.model.parameters():       # (an optimiser's zero_grad(set_to_none) dropped the views: the kernel writes them whole)
-                if p.grad is None:
-                    raise ValueError(f'Trainer: a parameter lost its gradient view; call set_gradient("{self.gradient}") again')
+            self._device_inputs(inputs)
             kernel = value_net.loss_and_grad_lstm if self.gradient == "device_lstm" else value_net.loss_and_grad
             loss = kernel(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
             self.optimizer.step()
@@ -144,6 +236,26 @@ class Trainer(object):
         self.optimizer.step()
         return loss.data.item()
 
+    def _device_sum(self):
+        """The float64 the fused steps add their losses to, on the parameters' device"""
+        if self.loss_sum is None or self.loss_sum.device != self.flat.device:
+            self.loss_sum = torch.zeros(1, dtype=torch.float64, device=self.flat.device)
+        return self.loss_sum
+
+    def _run(self, minibatches):
+        """One optimiser step per minibatch; the sum of their losses as the reference forms it (a Python float grown by loss.item()).  In
+        "device" update mode the steps are only enqueued and the same float64 sum, formed on the device in the same order, is read once."""
+        fused = self.update == "device"
+        if fused:
+            self._device_sum().zero_()
+        total = 0
+        for inputs, values in minibatches:
+            if fused:
+                self._enqueue_fused_step(inputs, values)
+            else:
+                total += self._step(inputs, values)
+        return self.loss_sum.item() if fused else total
+
     # ------------------------------------------------------------------ the reference's two loops
     def optimize_epoch(self, num_epochs):
         if self.optimizer is None:
@@ -151,9 +263,7 @@ class Trainer(object):
         loader = self._loader()
         average_epoch_loss = 0
         for epoch in range(num_epochs):
-            epoch_loss = 0
-            for inputs, values in loader:
-                epoch_loss += self._step(inputs, values)
+            epoch_loss = self._run(loader)
             average_epoch_loss = epoch_loss / len(self.memory)
             logging.debug('Average loss in epoch %d: %.2E', epoch, average_epoch_loss)
         return average_epoch_loss
@@ -162,10 +272,7 @@ class Trainer(object):
         if self.optimizer is None:
             raise ValueError('Learning rate is not set!')
         loader = self._loader()
-        losses = 0
-        for _ in range(num_batches):
-            inputs, values = next(iter(loader))
-            losses += self._step(inputs, values)
+        losses = self._run(next(iter(loader)) for _ in range(num_batches))
         average_loss = losses / num_batches
         logging.debug('Average loss : %.2E', average_loss)
         return average_loss

@@ -1,7 +1,8 @@
 // value_net_grad.h -- what the gradient kernels (value_net_grad.hip: CADRL / SARL; value_net_lstm_grad.hip: LSTM-RL) share: the flat
 // parameter offsets, the layer-indexed part of the LDS map, the forward layer of a 32-row tile, the three backward products on
-// v_mfma_f32_32x32x2_f32 (dX = dZ W, dWt = dZt X, db), the chains over them and the kernel that sums the workgroups' regions.  Unnamed
-// namespace: each translation unit gets its own copy.
+// v_mfma_f32_32x32x2_f32 (dX = dZ W, dWt = dZt X, db), the chains over them, the kernel that sums the workgroups' regions and the one that
+// sums them, takes the SGD-momentum step and rewrites the blob (k_vn_sgd, the train-step entries).  Unnamed namespace: each translation
+// unit gets its own copy.
 #pragma once
 #include "value_net_plan.h"
 
@@ -221,6 +222,90 @@ __global__ void k_vn_grad_sum(const float* __restrict__ scratch, int region, int
     for (int r = 0; r < regions; ++r) s += scratch[(long)r * region + i];
     if (i < P) grad[i] = s;
     else *loss = s / (float)B;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the fused optimiser step
+// The blob float that holds column kk (counted in the blob's k-groups: the second source's columns start at 8 * kg_split) of output `col` of
+// 32-column block cb of a layer: pack_layer_f32's map, read forwards.
+__host__ __device__ __forceinline__ int blob_weight_at(const VnLayer& L, int cb, int col, int kk)
+{
+    return L.w_off + (((cb * L.kg_total + (kk >> 3)) * 64 + col + 32 * ((kk >> 2) & 1)) << 2) + (kk & 3);
+}
+
+// the blob float of element e of a Linear layer's flat (weight [N][K1 + K2], bias [N]) pair
+__host__ __device__ __forceinline__ int blob_layer_at(const VnLayer& L, int e)
+{
+    const int K = L.K1 + L.K2;
+    if (e >= L.N * K) return L.b_off + e - L.N * K;
+    const int j = e / K, k = e - j * K;
+    return blob_weight_at(L, j >> 5, j & 31, k < L.K1 ? k : L.kg_split * 8 + k - L.K1);
+}
+
+// k_vn_grad_sum's sum for k_vn_sgd: the regions' floats i, added in region order -- the same adds, the same bytes --, with eight regions'
+// loads in flight at a time (one load a trip waits a memory latency per region: 228 of them at 4096 x 5)
+__device__ __forceinline__ float region_sum(const float* __restrict__ scratch, int region, int regions, int i)
+{
+    const float* at = scratch + i;
+    float s = 0.0f;
+    int r = 0;
+    for (; r + 8 <= regions; r += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = at[(long)(r + u) * region];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; r < regions; ++r) s += at[(long)r * region];
+    return s;
+}
+
+// k_vn_grad_sum, torch's SGD with momentum (dampening 0, no Nesterov, no weight decay) and the pack kernel in one launch, a thread per
+// parameter i of the flat layout: g = the regions' floats i in region order (d_grad's bytes as k_vn_grad_sum writes them), buf = mu buf + g,
+// p = p - lr buf, each one fmaf, and the blob float that reads p rewritten from the new value.  `Map`: map(i, twin) is that blob float; a
+// parameter that shares its blob float with another (the LSTM's bias_ih and bias_hh) is updated by its partner's thread -- the partner gets
+// twin = the other's index and writes the float32 sum of the two new values in the pack kernel's order, the other gets -1.  Every parameter
+// is read by exactly one blob float (tests/test_value_step_cpu.py), so the padding floats, zero since the blob was packed, stay zero and
+// no two threads write one float: no atomics, the same bytes twice.  The thread behind the last parameter owns the loss: the regions' terms
+// / B, and that added in float64 to *loss_sum (may be null), as the trainer's loops add loss.item() on the host.
+template <class Map>
+__global__ __launch_bounds__(256) void k_vn_sgd(Map map, const float* __restrict__ scratch, int region, int regions, int P, int B, float lr, float mu,
+                                                float* __restrict__ params, float* __restrict__ momentum, float* __restrict__ grad,
+                                                float* __restrict__ blob, float* __restrict__ loss, double* __restrict__ loss_sum)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > P) return;
+    if (i == P) {
+        const float l = region_sum(scratch, region, regions, i) / (float)B;
+        *loss = l;
+        if (loss_sum) *loss_sum += (double)l;
+        return;
+    }
+    int twin;
+    const int at = map(i, twin);
+    if (at < 0) return;
+    auto step = [&](int k) {
+        const float buf0 = momentum[k], p0 = params[k];
+        const float g = region_sum(scratch, region, regions, k);
+        const float buf = fmaf(mu, buf0, g);
+        const float p = fmaf(-lr, buf, p0);
+        grad[k] = g;
+        momentum[k] = buf;
+        params[k] = p;
+        return p;
+    };
+    float v = step(i);
+    if (twin >= 0) v = v + step(twin);
+    blob[at] = v;
+}
+
+// what the train-step entries check beyond their loss-and-gradient entry's checks
+inline int check_sgd_args(const float* d_momentum, size_t n_momentum_floats, size_t n_param_floats, float lr, float momentum)
+{
+    if (!d_momentum) return fail(CS_ERR_ARG, "null argument");
+    if (n_momentum_floats != n_param_floats) return fail(CS_ERR_ARG, "the momentum buffer does not have the size of the flat parameters");
+    if (!std::isfinite(lr) || lr < 0.0f) return fail(CS_ERR_ARG, "lr must be finite and at least 0");
+    if (!std::isfinite(momentum) || momentum < 0.0f) return fail(CS_ERR_ARG, "momentum must be finite and at least 0");
+    return CS_OK;
 }
 
 } // namespace

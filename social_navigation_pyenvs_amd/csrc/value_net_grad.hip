@@ -2,7 +2,8 @@
 // forward pass, the mean-squared-error loss against B targets and the gradient of that loss with respect to every parameter
 // (cs_value_net_loss_grad), and the packing of the flat parameters into the decision kernels' blob on the device (cs_value_net_pack_device).
 // Replaces, per optimiser step, crowd_nav/utils/trainer.py:50-71 (zero_grad, model(inputs), MSELoss, backward) for the networks of
-// crowd_nav/policy/sarl.py:28-65 and crowd_nav/policy/cadrl.py:116-123; the optimiser stays torch's.
+// crowd_nav/policy/sarl.py:28-65 and crowd_nav/policy/cadrl.py:116-123; the optimiser stays torch's -- or, for SGD with momentum, runs in
+// the launch that sums the gradient and rewrites the blob there (cs_value_net_train_step: value_net_grad.h k_vn_sgd).
 //
 // Shape of the work.  A "group" is one sample: n rows [cols], one value.  As in value_net.hip a workgroup (4 wavefronts) takes jobs of 32
 // groups and walks a job in tiles of 32 rows: whole groups while n <= 32, otherwise one group in chunks of 32 humans.  Every product of a tile --
@@ -425,25 +426,94 @@ extern "C" int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims
     return CS_OK;
 }
 
-extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                      size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
-                                      float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+namespace {
+
+// the argument checks of cs_value_net_loss_grad, which cs_value_net_train_step makes first
+inline int check_grad_args(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, const float* d_grad,
+                           const float* d_loss, const float* d_scratch, size_t n_scratch_floats, GradLaunch& q)
 {
-    GradLaunch q;
     const int rc = plan_grad(kind, dims, n_dims, cols, B, n, q);
     if (rc != CS_OK) return rc;
     if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
     if (n_weight_floats != (size_t)q.p.total_floats) return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack)");
     if (n_param_floats != (size_t)q.o.total) return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes)");
     if (n_scratch_floats < (size_t)q.grid * q.region) return fail(CS_ERR_ARG, "the scratch is too small for this minibatch (cs_value_net_grad_sizes)");
-    const int rc2 = grant_lds<k_vn_grad>(q.shmem);
-    if (rc2 != CS_OK) return rc2;
+    return CS_OK;
+}
+
+// the job kernel of both entries: every workgroup's partial gradient and loss term into its region of the scratch
+inline int launch_jobs(const GradLaunch& q, const float* d_weights, const float* d_params, int B, int n, const float* d_rows, const float* d_targets,
+                       float* d_scratch, float* d_values, void* stream)
+{
+    const int rc = grant_lds<k_vn_grad>(q.shmem);
+    if (rc != CS_OK) return rc;
     hipLaunchKernelGGL(k_vn_grad, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)stream, q.p, q.m, q.o, d_weights, d_params, B, n, q.jrows, d_rows, d_targets,
                        d_scratch, q.region, d_values);
     HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// k_vn_sgd's map of the feed-forward blob: every parameter has a blob float of its own
+struct SgdMap {
+    VnPlan p;
+    GradOffsets o;
+    __host__ __device__ int operator()(int i, int& twin) const
+    {
+        twin = -1;
+        int l = 0;
+        while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
+        return blob_layer_at(p.L[l], i - o.w[l]);
+    }
+};
+
+} // namespace
+
+extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                      size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                                      float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    GradLaunch q;
+    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
+                                   d_scratch, n_scratch_floats, q);
+    if (rc != CS_OK) return rc;
+    const int rc2 = launch_jobs(q, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
+    if (rc2 != CS_OK) return rc2;
     hipLaunchKernelGGL(k_vn_grad_sum, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_scratch, q.region, q.grid, q.o.total, B,
                        d_grad, d_loss);
     HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                       size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                                       int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum,
+                                       float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    GradLaunch q;
+    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
+                                   d_scratch, n_scratch_floats, q);
+    if (rc != CS_OK) return rc;
+    const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
+    if (rc1 != CS_OK) return rc1;
+    const int rc2 = launch_jobs(q, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
+    if (rc2 != CS_OK) return rc2;
+    hipLaunchKernelGGL(k_vn_sgd<SgdMap>, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, SgdMap{q.p, q.o}, d_scratch, q.region,
+                       q.grid, q.o.total, B, lr, momentum, d_params, d_momentum, d_grad, d_weights, d_loss, d_loss_sum);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+{
+    VnPlan p;
+    const int rc = build_plan(kind, dims, n_dims, cols, 0, p);
+    if (rc != CS_OK) return rc;
+    const GradOffsets o = param_offsets(p);
+    if (!index) return fail(CS_ERR_ARG, "null argument");
+    if (n_param_floats != (size_t)o.total) return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes)");
+    const SgdMap map{p, o};
+    for (int i = 0, twin; i < o.total; ++i) index[i] = map(i, twin);
     return CS_OK;
 }
 

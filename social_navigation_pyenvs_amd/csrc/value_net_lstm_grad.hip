@@ -2,7 +2,8 @@
 // fused: for a minibatch of B stored states the forward pass, the mean-squared-error loss against B targets and the gradient of that loss
 // with respect to every parameter by backpropagation through time (cs_value_net_loss_grad_lstm), and the packing of the flat parameters into
 // the decision kernel's blob on the device (cs_value_net_pack_lstm_device).  Replaces, per optimiser step, crowd_nav/utils/trainer.py:50-71
-// (zero_grad, model(inputs), MSELoss, backward) for the recurrent family; the optimiser stays torch's.  value_net_grad.hip is the
+// (zero_grad, model(inputs), MSELoss, backward) for the recurrent family; the optimiser stays torch's, or runs fused behind the gradient
+// (cs_value_net_train_step_lstm: value_net_grad.h k_vn_sgd on this blob's map, LstmSgdMap).  value_net_grad.hip is the
 // feed-forward family's; the two share value_net_grad.h (the forward layer of a tile, the three backward products, the chains, the sum).
 //
 // Shape of the work.  A workgroup (4 wavefronts) takes jobs of 32 sequences (samples); a sample's n rows are evaluated as they lie
@@ -384,11 +385,13 @@ extern "C" int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int
     return CS_OK;
 }
 
-extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
-                                           float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+namespace {
+
+// the argument checks of cs_value_net_loss_grad_lstm, which cs_value_net_train_step_lstm makes first
+inline int check_lstm_grad_args(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, const float* d_grad,
+                                const float* d_loss, const float* d_scratch, size_t n_scratch_floats, LstmGradLaunch& a)
 {
-    LstmGradLaunch a;
     const int rc = plan_lstm_grad(dims, n_dims, cols, B, n, a);
     if (rc != CS_OK) return rc;
     if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
@@ -398,6 +401,13 @@ extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, cons
         return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
     if (n_scratch_floats < (size_t)a.grid * a.region)
         return fail(CS_ERR_ARG, "the scratch is too small for this minibatch (cs_value_net_grad_sizes_lstm)");
+    return CS_OK;
+}
+
+// the job kernel of both entries: every workgroup's partial gradient and loss term into its region of the scratch
+inline int launch_lstm_jobs(const LstmGradLaunch& a, const float* d_weights, const float* d_params, int B, int n, const float* d_rows,
+                            const float* d_targets, float* d_scratch, float* d_values, void* stream)
+{
 #define LSTM_GRAD_LAUNCH(M1)                                                                                                         \
     {                                                                                                                                \
         const int rc2 = grant_lds<k_vn_lstm_grad<M1>>(a.shmem);                                                                      \
@@ -409,9 +419,99 @@ extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, cons
     else LSTM_GRAD_LAUNCH(false)
 #undef LSTM_GRAD_LAUNCH
     HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// k_vn_sgd's map of the recurrent blob: the Linear layers as the feed-forward blob holds them; the gates' rows in the order 8 * gate + unit
+// within a block of 8 units, weight_hh's columns before weight_ih's; bias_ih and bias_hh share one float, which bias_ih's thread writes
+struct LstmSgdMap {
+    LstmPlan q;
+    GradOffsets o;
+    LstmGradOff og;
+    __host__ __device__ int operator()(int i, int& twin) const
+    {
+        twin = -1;
+        const int H = q.H;
+        const VnLayer& G = q.g;
+        if (i >= og.wih && i < og.bhh + 4 * H) {
+            if (i >= og.bhh) return -1;
+            int row, kk = -1;
+            if (i >= og.bih) {
+                row = i - og.bih;
+                twin = og.bhh + row;
+            } else if (i >= og.whh) {
+                row = (i - og.whh) / H;
+                kk = i - og.whh - row * H;
+            } else {
+                row = (i - og.wih) / q.xin;
+                kk = G.kg_split * 8 + i - og.wih - row * q.xin;
+            }
+            const int gate = row / H, unit = row - gate * H;
+            const int cb = unit >> 3, col = 8 * gate + (unit & 7);
+            return kk < 0 ? G.b_off + cb * 32 + col : blob_weight_at(G, cb, col, kk);
+        }
+        const VnPlan& p = q.v;
+        int l = 0;
+        while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
+        return blob_layer_at(p.L[l], i - o.w[l]);
+    }
+};
+
+} // namespace
+
+extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                                           float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    LstmGradLaunch a;
+    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
+                                        d_scratch, n_scratch_floats, a);
+    if (rc != CS_OK) return rc;
+    const int rc2 = launch_lstm_jobs(a, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
+    if (rc2 != CS_OK) return rc2;
     hipLaunchKernelGGL(k_vn_grad_sum, dim3((a.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_scratch, a.region, a.grid, a.o.total, B,
                        d_grad, d_loss);
     HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                            size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B,
+                                            int n, int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                                            double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    LstmGradLaunch a;
+    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
+                                        d_scratch, n_scratch_floats, a);
+    if (rc != CS_OK) return rc;
+    const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
+    if (rc1 != CS_OK) return rc1;
+    const int rc2 = launch_lstm_jobs(a, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
+    if (rc2 != CS_OK) return rc2;
+    hipLaunchKernelGGL(k_vn_sgd<LstmSgdMap>, dim3((a.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, LstmSgdMap{a.q, a.o, a.og},
+                       d_scratch, a.region, a.grid, a.o.total, B, lr, momentum, d_params, d_momentum, d_grad, d_weights, d_loss, d_loss_sum);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+{
+    LstmPlan q;
+    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    if (rc != CS_OK) return rc;
+    GradOffsets o{};
+    LstmGradOff og{};
+    lstm_param_offsets(q, o, og);
+    if (!index) return fail(CS_ERR_ARG, "null argument");
+    if (n_param_floats != (size_t)o.total)
+        return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
+    const LstmSgdMap map{q, o, og};
+    for (int i = 0; i < o.total; ++i) {         // (bias_hh's thread writes nothing: its float is bias_ih's, which names it as its twin)
+        int twin;
+        const int at = map(i, twin);
+        if (at >= 0) index[i] = at;
+        if (twin >= 0) index[twin] = at;
+    }
     return CS_OK;
 }
 
