@@ -859,6 +859,61 @@ int cs_value_net_decide_lstm_om(const int32_t* dims, int n_dims, const float* d_
                                 float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * The optimisation step of the networks with occupancy-map columns, OM-SARL and OM-LSTM-RL (csrc/value_net_grad.hip,
+ * csrc/value_net_lstm_grad.hip): every entry below is its sibling without `_om` -- the same kernels, launches, results,
+ * determinism and errors -- with `int om_cols` behind `cols`, 1 <= om_cols and cols + om_cols <= 256.
+ *   Row layout.  d_rows is [B][n][cols + om_cols], float32 and dense: a row is the cols (13 | 15) rotated columns of a human followed by
+ *   the om_cols columns of that human's occupancy map -- what multi_human_rl.py:115-128 transform stores for a state, what
+ *   joint_state_device returns and a replay memory holds.  The maps are not a separate array here.  The self state is columns 0..5 of a
+ *   sample's first row.
+ * cs_value_net_grad_sizes_om, cs_value_net_loss_grad_om, cs_value_net_train_step_om  (kind = CS_VN_SARL alone) d_weights is
+ *   cs_value_net_pack_om's blob, d_params the flat parameters with mlp1's first weight [N][cols + om_cols]; the gradient of that weight
+ *   covers its map columns.  d_values are cs_value_net_decide_om's numbers for these rows and maps with A = 1, zero rewards and dt = 0.
+ *   Row layout: d_rows [B][n][cols + om_cols] as above.
+ * cs_value_net_pack_om_device  byte for byte cs_value_net_pack_om's blob from the flat d_params.
+ * cs_value_net_blob_index_om  (host only) index[i] is the float of cs_value_net_pack_om's blob that holds parameter i; the columns of the
+ *   first layer's k-group padding (cols + om_cols up to a multiple of 8) belong to no parameter and stay zero.
+ * cs_value_net_grad_sizes_lstm_om, cs_value_net_loss_grad_lstm_om, cs_value_net_train_step_lstm_om  d_weights is
+ *   cs_value_net_pack_lstm_om's blob; network 1: weight_ih is [4H][cols + om_cols] and the LSTM reads the row itself, network 2: mlp1's
+ *   first weight is [N][cols + om_cols].  d_values are cs_value_net_decide_lstm_om's numbers with A = 1 and sorted_by_distance = 0 (the
+ *   same descending k-group order over the wider joint row).  The tape does not depend on the row's width.  Row layout: d_rows
+ *   [B][n][cols + om_cols] as above, a sample's rows evaluated as they lie.
+ * cs_value_net_pack_lstm_om_device, cs_value_net_blob_index_lstm_om  cs_value_net_pack_lstm_device and cs_value_net_blob_index_lstm for
+ *   cs_value_net_pack_lstm_om's blob.
+ *   Further errors of all (CS_ERR_ARG, before any device call): om_cols < 1, cols + om_cols > 256, kind != CS_VN_SARL for the feed-forward
+ *   entries; the LDS-fit refusal names the widths and the bytes asked for (the input tile has rows of cols + om_cols rounded up to 8, plus 4
+ *   floats).
+ */
+int cs_value_net_grad_sizes_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
+                               size_t* n_scratch_floats);
+int cs_value_net_loss_grad_om(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                              size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows /* [B][n][cols + om_cols] */,
+                              const float* d_targets, float* d_grad, float* d_loss, float* d_values /* may be NULL */, float* d_scratch,
+                              size_t n_scratch_floats, void* stream);
+int cs_value_net_pack_om_device(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats,
+                                float* d_blob, size_t n_blob_floats, void* stream);
+int cs_value_net_train_step_om(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                               size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                               int cols, int om_cols, const float* d_rows /* [B][n][cols + om_cols] */, const float* d_targets, float* d_grad,
+                               float* d_loss, double* d_loss_sum /* may be NULL */, float* d_values /* may be NULL */, float* d_scratch,
+                               size_t n_scratch_floats, void* stream);
+int cs_value_net_blob_index_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats);
+int cs_value_net_grad_sizes_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
+                                    size_t* n_scratch_floats);
+int cs_value_net_loss_grad_lstm_om(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                   size_t n_param_floats, int B, int n, int cols, int om_cols,
+                                   const float* d_rows /* [B][n][cols + om_cols] */, const float* d_targets, float* d_grad, float* d_loss,
+                                   float* d_values /* may be NULL */, float* d_scratch, size_t n_scratch_floats, void* stream);
+int cs_value_net_pack_lstm_om_device(const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats,
+                                     float* d_blob, size_t n_blob_floats, void* stream);
+int cs_value_net_train_step_lstm_om(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                    size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B,
+                                    int n, int cols, int om_cols, const float* d_rows /* [B][n][cols + om_cols] */, const float* d_targets,
+                                    float* d_grad, float* d_loss, double* d_loss_sum /* may be NULL */, float* d_values /* may be NULL */,
+                                    float* d_scratch, size_t n_scratch_floats, void* stream);
+int cs_value_net_blob_index_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats);
+
+/*
  * Float64 worlds (csrc/sfmstep_f64.hip): the SFM / HSFM substep in the reference's own precision (PRECISION = np.float64),
  * an opt-in arithmetic beside the float32 entries above.  cs_worlds_f64 carries the fields of cs_worlds that apply, with double buffers:
  * the state is CS_LAYOUT_AOS [W][rows][13] only, a world holds up to 64 rows (one wavefront per world), the types are 0..8, the robot is

@@ -179,6 +179,16 @@ ABI = {
     "cs_value_net_blob_index_lstm": (I, [P, I, I, P, Z]),
     "cs_value_net_pack_lstm_om":(I, [P, I, I, I, P, P, P]),
     "cs_value_net_decide_lstm_om": (I, [P, I, P, Z, I, I, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_grad_sizes_om": (I, [I, P, I, I, I, I, I, P, P]),
+    "cs_value_net_loss_grad_om": (I, [I, P, I, P, Z, P, Z, I, I, I, I, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_pack_om_device": (I, [I, P, I, I, I, P, Z, P, Z, P]),
+    "cs_value_net_train_step_om": (I, [I, P, I, P, Z, P, Z, P, Z, F, F, I, I, I, I, P, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_blob_index_om": (I, [I, P, I, I, I, P, Z]),
+    "cs_value_net_grad_sizes_lstm_om": (I, [P, I, I, I, I, I, P, P]),
+    "cs_value_net_loss_grad_lstm_om": (I, [P, I, P, Z, P, Z, I, I, I, I, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_pack_lstm_om_device": (I, [P, I, I, I, P, Z, P, Z, P]),
+    "cs_value_net_train_step_lstm_om": (I, [P, I, P, Z, P, Z, P, Z, F, F, I, I, I, I, P, P, P, P, P, P, P, Z, P]),
+    "cs_value_net_blob_index_lstm_om": (I, [P, I, I, I, P, Z]),
     "cs_step_f64": (I, [WORLDS64, D, I, P, P]),
     "cs_update_humans_parallel_f64": (I, [WORLDS64, D, P, P]),
     "cs_peek_f64": (I, [WORLDS64, D, P, P]),

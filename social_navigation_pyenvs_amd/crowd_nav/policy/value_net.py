@@ -45,7 +45,13 @@ time; ``has_recurrent_gradient_kernel``): ``grad_sizes_lstm``, ``pack_lstm_on_de
 ``train_step`` / ``train_step_lstm`` (cs_value_net_train_step[_lstm]) are the whole optimisation step of either family: the loss and the
 gradient as above, and in the launch that sums the gradient torch's SGD step with momentum and the float32 blob rewritten from the new
 parameters, with the loss added to a device float64 sum -- nothing is read back (``Trainer.set_update("device")``).
-``DeviceNet.updated_on_device`` is their word that parameters and float32 blob changed together under the version counters."""
+``DeviceNet.updated_on_device`` is their word that parameters and float32 blob changed together under the version counters.
+
+The two families with map columns (OM-SARL, OM-LSTM-RL; ``has_mapped_gradient_kernel``) run the same kernels on stored rows of
+cols + om_cols columns -- the rotated columns, then the human's map, as ``transform`` stores a state -- through the `_om` entries of the
+library: ``grad_sizes_om``, ``pack_om_on_device``, ``loss_and_grad_om``, ``train_step_om`` and ``blob_index_om`` each dispatch on the net's
+family to the feed-forward or the recurrent entry; ``DeviceNet.adopt_flat(flat, mapped=True)`` is their trainer's word
+(``Trainer.set_gradient("device_om")`` / ``("device_lstm_om")``).  The names without `_om` go on refusing a mapped net."""
 from __future__ import annotations
 
 import ctypes as C
@@ -124,10 +130,13 @@ def family_of(kind, om_cols=0):
 
 GRADIENT_REFUSAL = ("{0}: the fused loss-and-gradient kernel (cs_value_net_loss_grad) covers the feed-forward networks, CADRL's and SARL's; "
                     'an LSTM without map columns has its own (cs_value_net_loss_grad_lstm: the *_lstm helpers, Trainer.set_gradient("device_lstm")); '
-                    "a network with occupancy-map columns keeps torch's autograd")
+                    'a network with occupancy-map columns has the *_om helpers (Trainer.set_gradient("device_om"), ("device_lstm_om"))')
 RECURRENT_GRADIENT_REFUSAL = ("{0}: the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm) covers LSTM-RL's two networks on rows of "
                               '13 or 15 columns; CADRL and SARL have cs_value_net_loss_grad (Trainer.set_gradient("device")), a network with '
-                              "occupancy-map columns (OM-SARL, OM-LSTM-RL) keeps torch's autograd")
+                              'occupancy-map columns (OM-SARL, OM-LSTM-RL) has the *_om helpers (Trainer.set_gradient("device_om"), '
+                              '("device_lstm_om"))')
+MAPPED_GRADIENT_REFUSAL = ("{0}: the *_om helpers cover the networks with occupancy-map columns, OM-SARL's and OM-LSTM-RL's; a network "
+                           "without map columns has {1}")
 
 
 def has_gradient_kernel(family):
@@ -138,6 +147,12 @@ def has_gradient_kernel(family):
 def has_recurrent_gradient_kernel(family):
     """Whether a family's networks have the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm): LSTM-RL without map columns."""
     return family is RECURRENT
+
+
+def has_mapped_gradient_kernel(family):
+    """Whether a family's networks have the loss-and-gradient kernels on rows with map columns (cs_value_net_loss_grad_om,
+    cs_value_net_loss_grad_lstm_om): OM-SARL's and OM-LSTM-RL's."""
+    return family is MAPPED or family is RECURRENT_MAPPED
 
 
 def check_map_order(map_order):
@@ -257,7 +272,10 @@ class DeviceNet:
         key = self._versions()
         if self.flat is not None and precision == "f32":        # the parameters are views of `flat` (adopt_flat): packed where they lie
             if key != self._keys[precision]:
-                (pack_lstm_on_device if has_recurrent_gradient_kernel(self.family) else pack_on_device)(self, self.flat)
+                if has_mapped_gradient_kernel(self.family):
+                    pack_om_on_device(self, self.flat)
+                else:
+                    (pack_lstm_on_device if has_recurrent_gradient_kernel(self.family) else pack_on_device)(self, self.flat)
                 self._keys[precision] = key
             return self.blobs[precision]
         if key != self._keys[check_precision(precision)]:
@@ -266,13 +284,16 @@ class DeviceNet:
             self._keys[precision] = key
         return self.blobs[precision]
 
-    def adopt_flat(self, flat):
+    def adopt_flat(self, flat, mapped=False):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
         ``Trainer.set_gradient("device")`` or ``("device_lstm")`` makes them): from now on ``refresh("f32")`` packs the blob on the device
         (``pack_on_device``, or ``pack_lstm_on_device`` for a recurrent net) when a parameter's version changed, with no host round trip.
-        None takes the word back."""
+        None takes the word back.  ``mapped=True`` is the word of the map modes ("device_om", "device_lstm_om") for a net with map
+        columns, which packs through ``pack_om_on_device``; without it such a net is refused as before."""
         if flat is not None:
-            if not has_gradient_kernel(self.family) and not has_recurrent_gradient_kernel(self.family):
+            if mapped:
+                _om_family(self, "adopt_flat(mapped=True)", "adopt_flat(flat)")
+            elif not has_gradient_kernel(self.family) and not has_recurrent_gradient_kernel(self.family):
                 raise ValueError(GRADIENT_REFUSAL.format("adopt_flat"))
             total = param_offsets(self)[-1]
             if not flat.is_cuda or flat.dtype != _torch().float32 or flat.dim() != 1 or flat.numel() != total or not flat.is_contiguous():
@@ -281,7 +302,7 @@ class DeviceNet:
         self._keys["f32"] = None
 
     def updated_on_device(self):
-        """The word of ``train_step`` / ``train_step_lstm`` that a kernel updated the flat parameters and rewrote the float32 blob from them
+        """The word of ``train_step`` / ``train_step_lstm`` / ``train_step_om`` that a kernel updated the flat parameters and rewrote the float32 blob from them
         in the same launch.  A kernel's write moves no version counter: the float32 key stays valid (no repack, the blob is current), every
         other precision's key is dropped, so its next ``refresh`` packs from the new numbers."""
         if self.flat is None:
@@ -372,9 +393,10 @@ def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
     return loss
 
 
-def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=None, loss_sum=None):
+def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=None, loss_sum=None, width=None):
     """The tensor checks the loss-and-gradient and the train-step seams make alike, in `caller`'s name, and the scratch kept on `net`
-    (`sizes`: grad_sizes or grad_sizes_lstm), grown when a larger minibatch comes: (B, n, cols, scratch, a new tensor for the loss)."""
+    (`sizes`: grad_sizes or grad_sizes_lstm), grown when a larger minibatch comes: (B, n, cols, scratch, a new tensor for the loss).
+    `width`: the columns of a row when they are not `net.cols` (the map modes: cols + om_cols)."""
     torch = _torch()
     B, n, cols = rows.shape
     tensors = [("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()), ("values", values, B)]
@@ -385,8 +407,8 @@ def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=N
             raise ValueError(f"{caller}: {name} is a contiguous CUDA float32 tensor of {numel} elements")
     if loss_sum is not None and (not loss_sum.is_cuda or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1):
         raise ValueError(f"{caller}: loss_sum is a CUDA float64 tensor of one element")
-    if cols != net.cols:
-        raise ValueError(f"{caller}: rows of {cols} columns for a network of {net.cols}")
+    if cols != (net.cols if width is None else width):
+        raise ValueError(f"{caller}: rows of {cols} columns for a network of {net.cols if width is None else width}")
     _, need = sizes(net, B, n)
     scratch = getattr(net, "_grad_scratch", None)
     if scratch is None or scratch.numel() < need or scratch.device != flat.device:
@@ -480,6 +502,95 @@ def train_step_lstm(net, flat, momentum, rows, targets, grad, lr, mu, values=Non
         raise ValueError(f"train_step_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
     return _train_step("train_step_lstm", "cs_value_net_train_step_lstm", grad_sizes_lstm, net, flat, momentum, rows, targets, grad, lr, mu, values,
                        loss_sum, stream)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the families with map columns
+def _om_family(net, caller, narrow):
+    """The entries' infix of a mapped `net` ("" for OM-SARL, "_lstm" for OM-LSTM-RL) and the arguments they open with; ValueError in
+    `caller`'s name for a net without map columns, naming the helper `narrow` that serves it."""
+    if not has_mapped_gradient_kernel(net.family):
+        raise ValueError(MAPPED_GRADIENT_REFUSAL.format(caller, narrow))
+    return ("_lstm" if net.lstm else ""), net.family.lead(net.kind) + (net.dims.ctypes.data, len(net.dims))
+
+
+def _om_rows(caller, net, rows):
+    if rows.dim() != 3:
+        raise ValueError(f"{caller}: rows are [B, n, cols + om_cols], not {tuple(rows.shape)}")
+    return rows
+
+
+def grad_sizes_om(net, B, n):
+    """cs_value_net_grad_sizes_om / cs_value_net_grad_sizes_lstm_om: ``grad_sizes`` / ``grad_sizes_lstm`` for a net with map columns."""
+    from ... import _lib
+
+    infix, lead = _om_family(net, "grad_sizes_om", "grad_sizes / grad_sizes_lstm")
+    n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(getattr(_lib.load(), f"cs_value_net_grad_sizes{infix}_om")(*lead, net.cols, net.om_cols, B, n, C.byref(n_params), C.byref(n_scratch)))
+    return n_params.value, n_scratch.value
+
+
+def pack_om_on_device(net, flat, stream=None):
+    """cs_value_net_pack_om_device / cs_value_net_pack_lstm_om_device: ``pack_on_device`` for a net with map columns -- byte for byte
+    ``pack``'s blob (cs_value_net_pack_om / cs_value_net_pack_lstm_om)."""
+    from ... import _lib
+
+    infix, lead = _om_family(net, "pack_om_on_device", "pack_on_device / pack_lstm_on_device")
+    blob = net.blobs["f32"]
+    if blob is None:
+        nf = C.c_size_t(0)
+        _lib.check(getattr(_lib.load(), net.family.pack["f32"][0])(*lead, net.cols, net.om_cols, None, None, C.byref(nf)))
+        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
+    _lib.check(getattr(_lib.load(), f"cs_value_net_pack{infix}_om_device")(*lead, net.cols, net.om_cols, flat.data_ptr(), flat.numel(),
+                                                                          blob.data_ptr(), blob.numel(), _stream(stream)))
+    return blob
+
+
+def loss_and_grad_om(net, flat, rows, targets, grad, values=None, stream=None):
+    """cs_value_net_loss_grad_om / cs_value_net_loss_grad_lstm_om: ``loss_and_grad`` / ``loss_and_grad_lstm`` for a net with map columns
+    on the minibatch rows [B, n, cols + om_cols] -- a row is a human's rotated columns, then its map, as ``transform`` stores them;
+    `net`'s float32 blob must hold `flat`'s numbers (``pack_om_on_device``).  Returns the loss, a CUDA tensor of one element."""
+    from ... import _lib
+
+    infix, _ = _om_family(net, "loss_and_grad_om", "loss_and_grad / loss_and_grad_lstm")
+    head = net.head("loss_and_grad_om")
+    rows = _om_rows("loss_and_grad_om", net, rows)
+    B, n, _, scratch, loss = _minibatch("loss_and_grad_om", net, flat, rows, targets, grad, values, grad_sizes_om, width=net.cols + net.om_cols)
+    _lib.check(getattr(_lib.load(), f"cs_value_net_loss_grad{infix}_om")(
+        *head, flat.data_ptr(), flat.numel(), B, n, net.cols, net.om_cols, rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(),
+        None if values is None else values.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    return loss
+
+
+def train_step_om(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
+    """cs_value_net_train_step_om / cs_value_net_train_step_lstm_om: ``train_step`` / ``train_step_lstm`` for a net with map columns --
+    ``loss_and_grad_om``, the SGD step and the blob (the wide first layer included; its k-group padding stays zero) rewritten."""
+    from ... import _lib
+
+    infix, _ = _om_family(net, "train_step_om", "train_step / train_step_lstm")
+    if momentum is None:
+        raise ValueError(f"train_step_om: momentum is a contiguous CUDA float32 tensor of {flat.numel()} elements")
+    head = net.head("train_step_om")
+    if net.flat is not flat:
+        raise ValueError("train_step_om: `flat` is not the tensor the network's parameters are views of (DeviceNet.adopt_flat)")
+    rows = _om_rows("train_step_om", net, rows)
+    B, n, _, scratch, loss = _minibatch("train_step_om", net, flat, rows, targets, grad, values, grad_sizes_om, momentum, loss_sum, net.cols + net.om_cols)
+    _lib.check(getattr(_lib.load(), f"cs_value_net_train_step{infix}_om")(
+        *head, flat.data_ptr(), flat.numel(), momentum.data_ptr(), momentum.numel(), float(lr), float(mu), B, n, net.cols, net.om_cols,
+        rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(), None if loss_sum is None else loss_sum.data_ptr(),
+        None if values is None else values.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    net.updated_on_device()
+    return loss
+
+
+def blob_index_om(net):
+    """cs_value_net_blob_index_om / cs_value_net_blob_index_lstm_om (host only): the float of ``pack``'s blob that holds every parameter
+    of ``param_offsets``' flat layout, an int32 numpy array."""
+    from ... import _lib
+
+    infix, lead = _om_family(net, "blob_index_om", "cs_value_net_blob_index / cs_value_net_blob_index_lstm")
+    index = np.full(param_offsets(net)[-1], -1, np.int32)
+    _lib.check(getattr(_lib.load(), f"cs_value_net_blob_index{infix}_om")(*lead, net.cols, net.om_cols, index.ctypes.data, index.size))
+    return index
 
 
 def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):

@@ -13,10 +13,16 @@ Three ways to the gradient, ``set_gradient``:
               cs_value_net_pack_lstm_device and cs_value_net_loss_grad_lstm (backpropagation through time over a sample's rows as they lie,
               csrc/value_net_lstm_grad.hip).
 
+  "device_om", "device_lstm_om"  (MAP_GRADIENTS) the same mechanics for the networks with occupancy-map columns, OM-SARL's and OM-LSTM-RL's, on
+              stored rows of cols + om_cols columns (the rotated columns, then the human's map, as ``transform`` stores a state):
+              cs_value_net_pack_om_device / cs_value_net_loss_grad_om and their `_lstm_om` siblings, the kernels above with a wide input
+              tile.  They need `net=`, the policy's own ``policy.device_net()``: a first layer of 61 inputs does not say how many of them
+              are map columns.
+
 Two ways to the update, ``set_update``:
 
   "torch"     (the default) ``self.optimizer.step()``, whatever optimiser the caller put there, and the loss read back per minibatch.
-  "device"    for the two device gradient modes and torch.optim.SGD with momentum (one parameter group, dampening 0, no Nesterov, no weight
+  "device"    for the device gradient modes (the map modes included) and torch.optim.SGD with momentum (one parameter group, dampening 0, no Nesterov, no weight
               decay, not maximize -- what ``set_learning_rate`` builds): a minibatch is cs_value_net_train_step[_lstm], two launches -- the
               gradient kernel, then one kernel that sums the gradient, takes the optimiser's step and rewrites the decision kernels' blob
               (csrc/value_net_grad.h k_vn_sgd).  lr and momentum are read from the optimiser's group at every step; its
@@ -35,7 +41,13 @@ from torch.utils.data import DataLoader
 from ..policy import value_net
 
 GRADIENTS = ("autograd", "device", "device_lstm")
+MAP_GRADIENTS = ("device_om", "device_lstm_om")     # the device modes of the networks with occupancy-map columns
 UPDATES = ("torch", "device")
+
+
+# a device gradient mode's (loss-and-gradient, train-step) seams
+_KERNELS = {"device": (value_net.loss_and_grad, value_net.train_step), "device_lstm": (value_net.loss_and_grad_lstm, value_net.train_step_lstm),
+            "device_om": (value_net.loss_and_grad_om, value_net.train_step_om), "device_lstm_om": (value_net.loss_and_grad_om, value_net.train_step_om)}
 
 
 class _MemoryLoader:
@@ -97,9 +109,12 @@ class Trainer(object):
         current -- a policy's own (``policy.device_net()``), so that its decisions read the trained weights without a host round trip;
         None: one of the trainer's.  "device" refuses a module that is not CADRL's or SARL's network, "device_lstm" one without an LSTM or
         with map columns (OM-LSTM-RL); both a model on the CPU, a model that is not float32, a memory whose stored states are not
-        [., n, 13 | 15] float32 rows and a `net` that is not this model's."""
-        if gradient not in GRADIENTS:
-            raise ValueError(f"gradient {gradient!r}: one of {', '.join(map(repr, GRADIENTS))}")
+        [., n, 13 | 15] float32 rows and a `net` that is not this model's.  "device_om" and "device_lstm_om" (MAP_GRADIENTS) are those two
+        for a network with map columns: `net` is required (it says how many of the first layer's inputs are map columns), the rows are
+        [., n, cols + om_cols]."""
+        if gradient not in GRADIENTS + MAP_GRADIENTS:
+            raise ValueError(f"gradient {gradient!r}: one of {', '.join(map(repr, GRADIENTS))}, or for a network with occupancy-map "
+                             f"columns {', '.join(map(repr, MAP_GRADIENTS))}")
         if gradient == "autograd":
             if self.net is not None:
                 self.net.adopt_flat(None)
@@ -111,7 +126,25 @@ class Trainer(object):
         first = layers[0] if layers else None
         cols = getattr(first, "in_features", getattr(first, "input_size", 0))       # (network 1's first layer is the nn.LSTM itself)
         who = f'Trainer.set_gradient("{gradient}")'
-        if gradient == "device_lstm":
+        if gradient in MAP_GRADIENTS:
+            narrow = "device_lstm" if gradient == "device_lstm_om" else "device"
+            has_kernel, which = value_net.has_mapped_gradient_kernel, "mapped"
+            if gradient == "device_om" and (kind != value_net.CS_VN_SARL):
+                raise ValueError(f'{who}: the module is not SARL\'s network; OM-LSTM-RL trains with set_gradient("device_lstm_om")')
+            if gradient == "device_lstm_om" and kind != value_net.CS_VN_LSTM:
+                raise ValueError(f'{who}: the module has no LSTM; OM-SARL trains with set_gradient("device_om")')
+            if net is None:
+                if cols in (13, 15):
+                    raise ValueError(f'{who}: the network has no occupancy-map columns; it trains with set_gradient("{narrow}")')
+                raise ValueError(f"{who}: a first layer of {cols} inputs does not say how many of them are map columns; pass net=, the "
+                                 "policy's own policy.device_net()")
+            if net.model is not self.model:
+                raise ValueError(f"{who}: the DeviceNet given is not this model's {which} one")
+            if not has_kernel(net.family):
+                raise ValueError(f'{who}: the network has no occupancy-map columns; it trains with set_gradient("{narrow}")')
+            if net.cols + net.om_cols != cols:
+                raise ValueError(f"{who}: the DeviceNet's {net.cols} + {net.om_cols} columns are not the first layer's {cols} inputs")
+        elif gradient == "device_lstm":
             has_kernel, which = value_net.has_recurrent_gradient_kernel, "recurrent"
             if kind != value_net.CS_VN_LSTM:
                 raise ValueError(f'{who}: the module has no LSTM; CADRL and SARL train with set_gradient("device")')
@@ -138,7 +171,7 @@ class Trainer(object):
                 flat[at:at + p.numel()].copy_(p.detach().reshape(-1))
                 p.data = flat[at:at + p.numel()].view(p.shape)
                 p.grad = grad[at:at + p.numel()].view(p.shape)
-        net.adopt_flat(flat)
+        net.adopt_flat(flat, mapped=gradient in MAP_GRADIENTS)
         self.gradient, self.net, self.flat, self.flat_grad = gradient, net, flat, grad
 
     # ------------------------------------------------------------------ the update's path
@@ -150,7 +183,7 @@ class Trainer(object):
             raise ValueError(f"update {update!r}: one of {', '.join(map(repr, UPDATES))}")
         if update == "device" and self.gradient == "autograd":
             raise ValueError('Trainer.set_update("device"): the fused step runs behind a device gradient; call set_gradient("device") '
-                             'or set_gradient("device_lstm") first')
+                             'or set_gradient("device_lstm") first (with occupancy-map columns: "device_om" or "device_lstm_om")')
         self.update = update
 
     def _sgd(self):
@@ -202,7 +235,7 @@ class Trainer(object):
 
     def _device_inputs(self, inputs):
         """What a minibatch of either device gradient mode is checked for before its launches; leaves the float32 blob current."""
-        self._check_states(inputs, self.net.cols, self.net.kind, f'Trainer.set_gradient("{self.gradient}")')
+        self._check_states(inputs, self.net.cols + self.net.om_cols, self.net.kind, f'Trainer.set_gradient("{self.gradient}")')
         self.net.refresh("f32")
         for p in self.model.parameters():       # (an optimiser's zero_grad(set_to_none) dropped the views: the kernel writes them whole)
             if p.grad is None:
@@ -213,7 +246,7 @@ class Trainer(object):
         ``self.loss_sum`` on the device and left in ``self.last_loss`` (a CUDA tensor of one element)."""
         self._device_inputs(inputs)
         lr, momentum = self._sgd()
-        kernel = value_net.train_step_lstm if self.gradient == "device_lstm" else value_net.train_step
+        kernel = _KERNELS[self.gradient][1]
         self.last_loss = kernel(self.net, self.flat, self.momentum, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad,
                                 lr, momentum, loss_sum=self._device_sum())
 
@@ -225,7 +258,7 @@ class Trainer(object):
             return self.last_loss.item()
         if self.gradient != "autograd":
             self._device_inputs(inputs)
-            kernel = value_net.loss_and_grad_lstm if self.gradient == "device_lstm" else value_net.loss_and_grad
+            kernel = _KERNELS[self.gradient][0]
             loss = kernel(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
             self.optimizer.step()
             return loss.item()

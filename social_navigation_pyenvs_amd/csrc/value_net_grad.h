@@ -13,10 +13,16 @@ constexpr int GRAD_MAX_GROUPS = 256;          // workgroups = scratch regions at
 struct GradOffsets { int w[VN_MAX_LAYERS], b[VN_MAX_LAYERS], total; };      // floats into the flat parameters: weight [N][K], bias [N] per layer
 
 // LDS map of the gradient kernel (floats).  act[l]: the output of layer l, 32 rows of up(N, 8) + 4 floats; mlp3's layers share the floats of
-// the tile's (mlp1, mlp2, attention) layers.
-struct GradLds { int X0, act[VN_MAX_LAYERS], ld[VN_MAX_LAYERS], D0, D1, dH, G, dG, J, dJ, sc, dw, den, val, grp, total; };
+// the tile's (mlp1, mlp2, attention) layers.  ldx: the input tile's row stride, the first layer's K rounded up to 8, plus 4 (value_net_om.hip's:
+// 20 for rows of 13 | 15 columns, 68 at 61 | 63, which is 4 mod 32).
+struct GradLds { int X0, ldx, act[VN_MAX_LAYERS], ld[VN_MAX_LAYERS], D0, D1, dH, G, dG, J, dJ, sc, dw, den, val, grp, total; };
 
 inline int ld8(int w) { return up(w, 8) + 4; }
+
+// The input tile's stride as the device code reads it: in a vector register (a lane's count of the set bits of an empty mask below it is 0).
+// Both gradient kernels sit at the limit of their scalar registers, which the arguments fill; one more scalar alive over the whole job makes
+// the compiler reserve a private segment (36 bytes a lane in the resource report, with this 0).
+__device__ __forceinline__ int tile_ldx(const GradLds& m) { return m.ldx + (int)__builtin_amdgcn_mbcnt_lo(0u, 0u); }
 
 // One forward layer of a 32-row tile: value_net_plan.h's layer_fwd (the same k-order per output element: the accumulator starts from the
 // bias, k-groups of 8 in order, within a group k = s, 4 + s for s = 0..3) with a destination stride of up(N, 8) + 4: columns N .. up(N, 8)

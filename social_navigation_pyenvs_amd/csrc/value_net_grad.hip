@@ -5,7 +5,8 @@
 // crowd_nav/policy/sarl.py:28-65 and crowd_nav/policy/cadrl.py:116-123; the optimiser stays torch's -- or, for SGD with momentum, runs in
 // the launch that sums the gradient and rewrites the blob there (cs_value_net_train_step: value_net_grad.h k_vn_sgd).
 //
-// Shape of the work.  A "group" is one sample: n rows [cols], one value.  As in value_net.hip a workgroup (4 wavefronts) takes jobs of 32
+// Shape of the work.  A "group" is one sample: n rows [cols], one value; for OM-SARL (the *_om entries) a row carries its human's om_cols map
+// columns behind the cols rotated ones, and the input tile's stride follows (GradLds.ldx).  As in value_net.hip a workgroup (4 wavefronts) takes jobs of 32
 // groups and walks a job in tiles of 32 rows: whole groups while n <= 32, otherwise one group in chunks of 32 humans.  Every product of a tile --
 // Z = X Wt, dX = dZ W, dWt = dZt X -- is a run of v_mfma_f32_32x32x2_f32 on 32 x 32 output blocks, one wavefront a block at a time.  The
 // forward layers read the packed blob exactly as value_net_plan.h's layer_fwd does (the same fmaf chain per output element) and the
@@ -46,7 +47,8 @@ inline GradLds grad_lds_map(const VnPlan& p, int n)
     GradLds m{};
     int o = 0, widest = 8;
     auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
-    m.X0 = take(32 * LDX);
+    m.ldx = p.L[0].kg_split * 8 + 4;
+    m.X0 = take(32 * m.ldx);
     const int tile_layers = p.kind == CS_VN_SARL ? p.c0[3] : p.n_layers;
     const int base = o;
     for (int l = 0; l < p.n_layers; ++l) {
@@ -54,7 +56,7 @@ inline GradLds grad_lds_map(const VnPlan& p, int n)
         m.ld[l] = ld8(p.L[l].N);
         m.act[l] = take(32 * m.ld[l]);
         widest = p.L[l].N > widest ? p.L[l].N : widest;
-        widest = p.L[l].K1 > widest ? p.L[l].K1 : widest;
+        if (l > 0) widest = p.L[l].K1 > widest ? p.L[l].K1 : widest;      // (the input layer's K is no buffer's width: no dX is formed for it)
     }
     int end = o;
     o = base;
@@ -64,15 +66,34 @@ inline GradLds grad_lds_map(const VnPlan& p, int n)
     m.D1 = take(32 * ld8(widest));
     if (p.kind == CS_VN_SARL) {
         const int ld_m1 = ld8(p.m1w);
-        m.dH = take(32 * ld_m1);
+        // dH and J share their floats: J lives in steps (1) and (2) -- mlp3's backward is its last reader --, dH in step (3), whose tile
+        // visits touch neither the self state nor the weighted feature; the next job zeroes J again.  (The 7.5 KiB are what lets the
+        // reference's widths with a 68-float input tile fit the 160 KiB.)
+        m.dH = take(32 * (ld_m1 > p.ld_j ? ld_m1 : p.ld_j));
+        m.J = m.dH;
         m.G = n == 1 ? m.act[p.c0[1] - 1] : take((n <= 32 ? 32 / n : 1) * ld_m1);      // one human: the mean of mlp1 over the group IS its row
         m.dG = take(ld_m1);                              // the mean's gradient of a group in chunks, summed over its chunks
-        m.J = take(32 * p.ld_j);
         m.dJ = take(32 * p.ld_j);
     }
     m.sc = take(32); m.dw = take(32); m.den = take(32); m.val = take(32); m.grp = take(32);
     m.total = o;
     return m;
+}
+
+// 32 rows of a minibatch into the input tile X0 (stride ldx): row r is the K consecutive floats at src + r * pitch -- the rotated columns and
+// behind them the map columns, as policy.transform stores a row --, zeros up to kpad (K rounded up to 8) and in the rows from `rows` on.  A
+// row's loads are consecutive floats: 16 lanes a row for the rows of 13 | 15 columns, a wavefront a row for the wide ones.
+__device__ __forceinline__ void load_rows32(float* X0, int ldx, int kpad, const float* __restrict__ src, long pitch, int rows, int K)
+{
+    const int sh = kpad <= 16 ? 4 : 6, c0 = threadIdx.x & ((1 << sh) - 1);
+#pragma unroll 1
+    for (int r = threadIdx.x >> sh; r < 32; r += NT >> sh) {
+        const bool live = r < rows;
+        const float* from = src + (long)r * pitch;
+        float* to = X0 + r * ldx;
+#pragma unroll 1
+        for (int c = c0; c < kpad; c += 1 << sh) to[c] = (live && c < K) ? from[c] : 0.0f;
+    }
 }
 
 // what a visit of a tile does beside the layers: the self state into J; the crowd mean of whole groups into G; the softmax denominator
@@ -90,8 +111,8 @@ __device__ __forceinline__ void sarl_tile_fwd(const VnPlan& p, const GradLds& m,
     const int ld_m1 = m.ld[p.c0[1] - 1], m1pad = (p.m1w + 7) & ~7;
     float* M1 = (b.lds + m.act[p.c0[1] - 1]);
     if (what & T_SELF)      // sarl.py:36: the self state is read from the first human's row
-        for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * LDX + i % SELF_DIM];
-    chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0);
+        for (int i = tid; i < tg * SELF_DIM; i += NT) b.J[(t0 + i / SELF_DIM) * p.ld_j + i % SELF_DIM] = b.X0[(i / SELF_DIM) * per * tile_ldx(m) + i % SELF_DIM];
+    chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, tile_ldx(m), nullptr, 0);
     if (what & T_MEAN) {
         for (int i = tid; i < tg * m1pad; i += NT) {
             const int k = i / m1pad, c = i - k * m1pad;
@@ -204,7 +225,7 @@ __device__ __forceinline__ void sarl_tile_bwd(const VnPlan& p, const GradLds& m,
     for (int i = tid; i < 32 * ld_m1; i += NT)      // mlp1 ends in a ReLU (last_relu)
         if (!(M1[i] > 0.0f)) b.dH[i] = 0.0f;
     __syncthreads();
-    chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.dH, b.X0, LDX, nullptr, 0, nullptr, 0, false, nullptr, 0);
+    chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.dH, b.X0, tile_ldx(m), nullptr, 0, nullptr, 0, false, nullptr, 0);
 }
 
 __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets o, const float* __restrict__ wb, const float* __restrict__ params,
@@ -216,11 +237,9 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
     b.X0 = lds + m.X0; b.D0 = lds + m.D0; b.D1 = lds + m.D1; b.dH = lds + m.dH; b.G = lds + m.G; b.dG = lds + m.dG; b.J = lds + m.J; b.dJ = lds + m.dJ;
     b.sc = lds + m.sc; b.dw = lds + m.dw; b.den = lds + m.den; b.val = lds + m.val; b.grp = reinterpret_cast<int*>(lds + m.grp);
     b.lds = lds;
-    const int tid = threadIdx.x, cols = p.cols;
+    const int tid = threadIdx.x;
     const bool sarl = p.kind == CS_VN_SARL;
     float* g = scratch + (long)blockIdx.x * region;
-    VnBufs lb{};
-    lb.X0 = b.X0; lb.grp = b.grp;
 
     for (int i = tid; i < region; i += NT) g[i] = 0.0f;
     float loss = 0.0f;                  // thread 0's: the job sums, in job order
@@ -236,7 +255,9 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
         const int ng = B - gbase < jrows ? B - gbase : jrows;
         // chunk ch of the tile whose first group is the job's t0: `per` humans of each of its tg groups
         auto load = [&](int t0, int tg, int ch, int per) {
-            load_tile(lb, rows_in + ((long)(gbase + t0) * n + ch * 32) * cols, tg * per, cols, per, 32);
+            const int K = p.L[0].K1;        // a row: the rotated columns, then the map columns
+            load_rows32(b.X0, tile_ldx(m), tile_ldx(m) - 4, rows_in + ((long)(gbase + t0) * n + ch * 32) * K, K, tg * per, K);
+            for (int r = tid; r < 32; r += NT) b.grp[r] = r < tg * per ? r / per : 0;
             __syncthreads();
         };
         auto chunk_rows = [&](int ch) { return n - ch * 32 < 32 ? n - ch * 32 : 32; };
@@ -246,7 +267,7 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
             for (int ch = 0; ch < chunks; ++ch) {
                 const int per = chunk_rows(ch);
                 load(t0, 1, ch, per);
-                chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0);
+                chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, tile_ldx(m), nullptr, 0);
                 for (int c = tid; c < m1pad; c += NT) {
                     float s = b.G[c];
                     for (int r = 0; r < per; ++r) s += M1[r * ld_m1 + c];
@@ -281,7 +302,7 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
             chain_fwd(p, m, b, wb, p.c0[3], p.c0[4], b.J, p.ld_j, nullptr, 0);
         } else {
             load(0, ng, 0, 1);
-            chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0);
+            chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, tile_ldx(m), nullptr, 0);
         }
         {   // the values, the loss terms and dV = 2 (V - target) / B as the top gradient [32][12] in D0
             const int last = p.n_layers - 1;
@@ -307,7 +328,7 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
             }
         }
         if (!sarl) {
-            chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.D0, b.X0, LDX, nullptr, 0, nullptr, 0, false, nullptr, 0);
+            chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.D0, b.X0, tile_ldx(m), nullptr, 0, nullptr, 0, false, nullptr, 0);
             continue;
         }
         chain_bwd(p, m, b, params, o, g, p.c0[3], p.c0[4], b.D0, b.J, p.ld_j, nullptr, 0, b.dJ, p.ld_j, false, nullptr, 0);
@@ -348,13 +369,13 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
                 for (int ch = 0; ch < chunks; ++ch) {
                     const int per = chunk_rows(ch);
                     load(t0, 1, ch, per);
-                    chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, LDX, nullptr, 0);
+                    chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, tile_ldx(m), nullptr, 0);
                     for (int i = tid; i < 32 * ld_m1; i += NT) {
                         const int r = i / ld_m1, c = i - r * ld_m1;
                         b.dH[i] = (r < per && c < p.m1w && M1[i] > 0.0f) ? b.dG[c] / (float)n : 0.0f;
                     }
                     __syncthreads();
-                    chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.dH, b.X0, LDX, nullptr, 0, nullptr, 0, false, nullptr, 0);
+                    chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.dH, b.X0, tile_ldx(m), nullptr, 0, nullptr, 0, false, nullptr, 0);
                 }
         }
     }
@@ -387,12 +408,13 @@ __global__ void k_vn_pack(VnPlan p, GradOffsets o, const float* __restrict__ par
     blob[i] = v;
 }
 
-// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid
+// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid.
+// om_cols: the map columns behind the rotated ones in a stored row (the *_om entries; 0: the rows of 13 | 15 columns)
 struct GradLaunch { VnPlan p; GradOffsets o; GradLds m; int grid, region, jrows; size_t shmem; };
 
-inline int plan_grad(int kind, const int32_t* dims, int n_dims, int cols, int B, int n, GradLaunch& q)
+inline int plan_grad(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, GradLaunch& q)
 {
-    const int rc = build_plan(kind, dims, n_dims, cols, 0, q.p);
+    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, q.p);
     if (rc != CS_OK) return rc;
     if (B < 1) return fail(CS_ERR_ARG, "B must be positive");
     if (n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
@@ -401,7 +423,9 @@ inline int plan_grad(int kind, const int32_t* dims, int n_dims, int cols, int B,
     q.o = param_offsets(q.p);
     q.m = grad_lds_map(q.p, n);
     q.shmem = (size_t)q.m.total * sizeof(float);
-    if (q.shmem > 160 * 1024) return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network do not fit the 160 KiB of LDS");
+    if (q.shmem > 160 * 1024)
+        return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(cols) + " + " + std::to_string(om_cols) +
+                                    " columns: " + std::to_string(q.shmem) + " bytes) do not fit the 160 KiB of LDS");
     // groups per job: whole tiles, as few as spread the minibatch over the workgroups, at most mlp3's block of 32 rows
     const int gpt = n <= 32 ? 32 / n : 1;
     const int want = up((B + GRAD_MAX_GROUPS - 1) / GRAD_MAX_GROUPS, gpt);
@@ -412,13 +436,13 @@ inline int plan_grad(int kind, const int32_t* dims, int n_dims, int cols, int B,
     return CS_OK;
 }
 
-} // namespace
+// the *_om entries' own check, made first
+inline int check_om_cols(int om_cols) { return om_cols < 1 ? fail(CS_ERR_ARG, "om_cols must be at least 1") : CS_OK; }
 
-extern "C" int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats,
-                                       size_t* n_scratch_floats)
+inline int grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
 {
     GradLaunch q;
-    const int rc = plan_grad(kind, dims, n_dims, cols, B, n, q);
+    const int rc = plan_grad(kind, dims, n_dims, cols, om_cols, B, n, q);
     if (rc != CS_OK) return rc;
     if (!n_param_floats || !n_scratch_floats) return fail(CS_ERR_ARG, "null argument");
     *n_param_floats = (size_t)q.o.total;
@@ -426,14 +450,12 @@ extern "C" int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims
     return CS_OK;
 }
 
-namespace {
-
-// the argument checks of cs_value_net_loss_grad, which cs_value_net_train_step makes first
+// the argument checks of the loss-and-gradient entries, which the train-step entries make first
 inline int check_grad_args(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, const float* d_grad,
+                           size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets, const float* d_grad,
                            const float* d_loss, const float* d_scratch, size_t n_scratch_floats, GradLaunch& q)
 {
-    const int rc = plan_grad(kind, dims, n_dims, cols, B, n, q);
+    const int rc = plan_grad(kind, dims, n_dims, cols, om_cols, B, n, q);
     if (rc != CS_OK) return rc;
     if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
     if (n_weight_floats != (size_t)q.p.total_floats) return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack)");
@@ -442,7 +464,7 @@ inline int check_grad_args(int kind, const int32_t* dims, int n_dims, const floa
     return CS_OK;
 }
 
-// the job kernel of both entries: every workgroup's partial gradient and loss term into its region of the scratch
+// the job kernel of the entries: every workgroup's partial gradient and loss term into its region of the scratch
 inline int launch_jobs(const GradLaunch& q, const float* d_weights, const float* d_params, int B, int n, const float* d_rows, const float* d_targets,
                        float* d_scratch, float* d_values, void* stream)
 {
@@ -467,15 +489,14 @@ struct SgdMap {
     }
 };
 
-} // namespace
-
-extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                      size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
-                                      float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+// cs_value_net_loss_grad[_om]
+inline int loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                     size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                     float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
     GradLaunch q;
-    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
-                                   d_scratch, n_scratch_floats, q);
+    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
+                                   d_loss, d_scratch, n_scratch_floats, q);
     if (rc != CS_OK) return rc;
     const int rc2 = launch_jobs(q, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
     if (rc2 != CS_OK) return rc2;
@@ -485,14 +506,15 @@ extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims,
     return CS_OK;
 }
 
-extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
-                                       size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
-                                       int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum,
-                                       float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+// cs_value_net_train_step[_om]
+inline int train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params, size_t n_param_floats,
+                      float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n, int cols, int om_cols, const float* d_rows,
+                      const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum, float* d_values, float* d_scratch,
+                      size_t n_scratch_floats, void* stream)
 {
     GradLaunch q;
-    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
-                                   d_scratch, n_scratch_floats, q);
+    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
+                                   d_loss, d_scratch, n_scratch_floats, q);
     if (rc != CS_OK) return rc;
     const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
     if (rc1 != CS_OK) return rc1;
@@ -504,10 +526,11 @@ extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims
     return CS_OK;
 }
 
-extern "C" int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+// cs_value_net_blob_index[_om]
+inline int blob_index(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, 0, p);
+    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, p);
     if (rc != CS_OK) return rc;
     const GradOffsets o = param_offsets(p);
     if (!index) return fail(CS_ERR_ARG, "null argument");
@@ -517,11 +540,12 @@ extern "C" int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims
     return CS_OK;
 }
 
-extern "C" int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats,
-                                        float* d_blob, size_t n_blob_floats, void* stream)
+// cs_value_net_pack[_om]_device
+inline int pack_device(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats, float* d_blob,
+                       size_t n_blob_floats, void* stream)
 {
     VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, 0, p);
+    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, p);
     if (rc != CS_OK) return rc;
     const GradOffsets o = param_offsets(p);
     if (!d_params || !d_blob) return fail(CS_ERR_ARG, "null argument");
@@ -530,4 +554,84 @@ extern "C" int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dim
     hipLaunchKernelGGL(k_vn_pack, dim3((p.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, o, d_params, d_blob);
     HIP_TRY(hipGetLastError());
     return CS_OK;
+}
+
+} // namespace
+
+// ---- the rows of 13 | 15 columns: the entries above with no map columns
+extern "C" int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats,
+                                       size_t* n_scratch_floats)
+{
+    return grad_sizes(kind, dims, n_dims, cols, 0, B, n, n_param_floats, n_scratch_floats);
+}
+
+extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                      size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                                      float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return loss_grad(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, 0, d_rows, d_targets, d_grad, d_loss, d_values,
+                     d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                       size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                                       int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum,
+                                       float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return train_step(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols, 0,
+                      d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+{
+    return blob_index(kind, dims, n_dims, cols, 0, index, n_param_floats);
+}
+
+extern "C" int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats,
+                                        float* d_blob, size_t n_blob_floats, void* stream)
+{
+    return pack_device(kind, dims, n_dims, cols, 0, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+}
+
+// ---- OM-SARL: rows of cols + om_cols columns
+extern "C" int cs_value_net_grad_sizes_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
+                                          size_t* n_scratch_floats)
+{
+    const int rc = check_om_cols(om_cols);
+    return rc != CS_OK ? rc : grad_sizes(kind, dims, n_dims, cols, om_cols, B, n, n_param_floats, n_scratch_floats);
+}
+
+extern "C" int cs_value_net_loss_grad_om(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats,
+                                         const float* d_params, size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows,
+                                         const float* d_targets, float* d_grad, float* d_loss, float* d_values, float* d_scratch,
+                                         size_t n_scratch_floats, void* stream)
+{
+    const int rc = check_om_cols(om_cols);
+    return rc != CS_OK ? rc
+                       : loss_grad(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
+                                   d_loss, d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_train_step_om(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                          size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n,
+                                          int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                                          double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    const int rc = check_om_cols(om_cols);
+    return rc != CS_OK ? rc
+                       : train_step(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B,
+                                    n, cols, om_cols, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_blob_index_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
+{
+    const int rc = check_om_cols(om_cols);
+    return rc != CS_OK ? rc : blob_index(kind, dims, n_dims, cols, om_cols, index, n_param_floats);
+}
+
+extern "C" int cs_value_net_pack_om_device(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params,
+                                           size_t n_param_floats, float* d_blob, size_t n_blob_floats, void* stream)
+{
+    const int rc = check_om_cols(om_cols);
+    return rc != CS_OK ? rc : pack_device(kind, dims, n_dims, cols, om_cols, d_params, n_param_floats, d_blob, n_blob_floats, stream);
 }

@@ -5,10 +5,13 @@
 // (zero_grad, model(inputs), MSELoss, backward) for the recurrent family; the optimiser stays torch's, or runs fused behind the gradient
 // (cs_value_net_train_step_lstm: value_net_grad.h k_vn_sgd on this blob's map, LstmSgdMap).  value_net_grad.hip is the
 // feed-forward family's; the two share value_net_grad.h (the forward layer of a tile, the three backward products, the chains, the sum).
+// OM-LSTM-RL (the *_lstm_om entries: cs_value_net_loss_grad_lstm_om, ...) is the same kernel on stored rows of cols + om_cols columns, a human's
+// map columns behind its rotated ones: network 1's LSTM or network 2's first mlp1 layer reads the wide row, nothing behind it changes.
 //
 // Shape of the work.  A workgroup (4 wavefronts) takes jobs of 32 sequences (samples); a sample's n rows are evaluated as they lie
 // (cs_value_net_decide_lstm's sorted_by_distance = 0).  A job runs in three phases.
-//   forward   t = 0 .. n-1: the 32 rows of step t, [mlp1 on them (layer_fwd32),] the gates as value_net_lstm_body.inc forms them -- the
+//   forward   t = 0 .. n-1: the 32 rows of step t (a stored row: 13 | 15 rotated columns and, for OM-LSTM-RL, its map columns behind them),
+//             [mlp1 on them (layer_fwd32),] the gates as value_net_lstm_body.inc forms them -- the
 //             transposed product, accumulators from b_ih + b_hh, the k-groups in descending order, weights streamed from the blob -- and the
 //             pointwise part in the lanes' own accumulators; h goes to the other joint-row buffer, c comes back from the lane's own tape store.  Every step's i, f,
 //             g, o, c and h go to the TAPE, the workgroup's own floats of d_scratch behind its partial gradient: [n][6][32][up(H, 8)].
@@ -40,10 +43,13 @@ enum { TP_I, TP_F, TP_G, TP_O, TP_C, TP_H };
 
 struct LstmGradOff { int wih, whh, bih, bhh; };        // floats into the flat parameters: the LSTM's four tensors between mlp1's and mlp's
 
-// LDS map (floats).  v: the input tile, the layers' outputs (mlp's over mlp1's: mlp1's are dead between the forward and the backward steps),
+// LDS map (floats).  v: the input tile (32 rows of v.ldx floats: a stored row's columns rounded up to 8, plus 4), the layers' outputs (mlp's over mlp1's: mlp1's are dead between the forward and the backward steps),
 // the two gradient buffers, J / dJ, the loss terms.  XH [2][32][ld_xh] (the forward's joint rows) shares its floats with the backward's dZ
 // [32][ldz], dh and dc [32][ldh].
 struct LstmGradLds { GradLds v; int XH, dZ, dh, dc, ldz, ldh; };
+
+// the columns of a stored row, the rotated ones and the map columns behind them: what the LSTM (network 1) or mlp1's first layer reads
+inline int row_width(const LstmPlan& q) { return q.v.c0[1] > 0 ? q.v.L[0].K1 : q.xin; }
 
 inline LstmGradLds lstm_grad_lds_map(const LstmPlan& q)
 {
@@ -51,7 +57,8 @@ inline LstmGradLds lstm_grad_lds_map(const LstmPlan& q)
     const VnPlan& p = q.v;
     int o = 0, widest = 8, end = 0;
     auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
-    m.v.X0 = take(32 * LDX);
+    m.v.ldx = up(row_width(q), 8) + 4;
+    m.v.X0 = take(32 * m.v.ldx);
     const int base = o;
     for (int l = 0; l < p.n_layers; ++l) {
         if (l == p.c0[1]) { end = o; o = base; }
@@ -100,14 +107,16 @@ __global__ __launch_bounds__(NT) void k_vn_lstm_grad(LstmPlan q, LstmGradLds m, 
     b.lds = lds; b.X0 = lds + m.v.X0; b.D0 = lds + m.v.D0; b.D1 = lds + m.v.D1; b.J = lds + m.v.J; b.dJ = lds + m.v.dJ; b.val = lds + m.v.val;
     float *XH = lds + m.XH, *dZ = lds + m.dZ, *dh = lds + m.dh, *dc = lds + m.dc;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5, li = lane & 31;
-    const int cols = p.cols, H = q.H, hpad = q.hpad, ldxh = q.ld_xh, KG = q.g.kg_total, ldz = m.ldz, ldh = m.ldh, xin = q.xin;
+    // K0: the columns of a stored row (row_width).  The input tile's stride: value_net_grad.h tile_ldx says why network 2 holds it in a vector
+    // register; network 1's build, which reads the tile in its backward products alone, reports a private segment of 0 with the scalar.
+    const int K0 = MLP1 ? p.L[0].K1 : q.xin, ldx = MLP1 ? tile_ldx(m.v) : m.v.ldx, H = q.H, hpad = q.hpad, ldxh = q.ld_xh, KG = q.g.kg_total, ldz = m.ldz, ldh = m.ldh, xin = q.xin;
     constexpr bool with_mlp1 = MLP1;
     const int nbw = (q.g.ncb - wave + 3) >> 2;              // this wavefront's blocks: wave, wave + 4, ...
     const float4* gw = reinterpret_cast<const float4*>(wb + q.g.w_off) + lane;
     // x_t as the backward products read it: mlp1's last output, or the rows themselves
     const int l_x = with_mlp1 ? p.c0[1] - 1 : 0;
     const float* xact = with_mlp1 ? lds + m.v.act[l_x] : b.X0;
-    const int ldxa = with_mlp1 ? m.v.ld[l_x] : LDX;
+    const int ldxa = with_mlp1 ? m.v.ld[l_x] : ldx;
     const int plane = 32 * hpad;                            // one array of one step of the tape
     float* g = scratch + (long)blockIdx.x * region;
     float* tape = g + gpart;
@@ -120,15 +129,14 @@ __global__ __launch_bounds__(NT) void k_vn_lstm_grad(LstmPlan q, LstmGradLds m, 
     for (int job = blockIdx.x; (long)job * JROWS < B; job += gridDim.x) {
         const int gbase = job * JROWS;
         const int ng = B - gbase < JROWS ? B - gbase : JROWS;
-        // the 32 rows of step t: 16 columns a row, zeros beyond the columns and the sequences
+        // the 32 rows of step t: a row's K0 columns, zeros up to K0 rounded up to 8 and beyond the sequences
         auto load = [&](float* dst, int ld, int t) {
+            const int kpad = ldx - 4, sh = kpad <= 16 ? 4 : 6;      // 16 lanes a row of 13 | 15 columns, a wavefront a wide one
 #pragma unroll 1
-            for (int i = tid; i < 32 * 16; i += NT) {
-                const int s = i >> 4, c = i & 15;
-                float v = 0.0f;
-                if (s < ng && c < cols) v = rows_in[((long)(gbase + s) * n + t) * cols + c];
-                dst[s * ld + c] = v;
-            }
+            for (int s = tid >> sh; s < 32; s += NT >> sh)
+#pragma unroll 1
+                for (int c = tid & ((1 << sh) - 1); c < kpad; c += 1 << sh)
+                    dst[s * ld + c] = (s < ng && c < K0) ? rows_in[((long)(gbase + s) * n + t) * K0 + c] : 0.0f;
         };
 #pragma unroll 1
         for (int i = tid; i < JROWS * p.ld_j; i += NT) b.J[i] = 0.0f;
@@ -150,19 +158,19 @@ __global__ __launch_bounds__(NT) void k_vn_lstm_grad(LstmPlan q, LstmGradLds m, 
                     const int s = i / H, u = i - s * H;
                     b.J[s * p.ld_j + SELF_DIM + u] = hn[s * ldxh + u];
                 }
-            } else if (with_mlp1 || !fwd) load(b.X0, LDX, t);
+            } else if (with_mlp1 || !fwd) load(b.X0, ldx, t);
             else load(cur + hpad, ldxh, t);
             __syncthreads();
             if (it == 0) {      // lstm_rl.py:25 / :53: the self state is read from the first row
                 const float* first = with_mlp1 ? b.X0 : cur + hpad;
-                const int ldf = with_mlp1 ? LDX : ldxh;
+                const int ldf = with_mlp1 ? ldx : ldxh;
 #pragma unroll 1
                 for (int i = tid; i < ng * SELF_DIM; i += NT) b.J[(i / SELF_DIM) * p.ld_j + i % SELF_DIM] = first[(i / SELF_DIM) * ldf + i % SELF_DIM];
             }
             const bool chain = head || with_mlp1;
             const int c_first = head ? p.c0[1] : p.c0[0], c_last = head ? p.c0[2] : p.c0[1];
             const float* c_src = head ? b.J : b.X0;
-            const int c_ld = head ? p.ld_j : LDX;
+            const int c_ld = head ? p.ld_j : ldx;
             if (chain) chain_fwd(p, m.v, b, wb, c_first, c_last, c_src, c_ld, nullptr, 0);
             if (fwd) {
                 if (with_mlp1) {
@@ -348,12 +356,13 @@ inline void lstm_param_offsets(const LstmPlan& q, GradOffsets& o, LstmGradOff& o
     o.total = at;
 }
 
-// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid
+// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid.
+// om, om_cols: build_lstm_plan's -- the map columns behind the rotated ones in a stored row (the *_lstm_om entries)
 struct LstmGradLaunch { LstmPlan q; GradOffsets o; LstmGradOff og; LstmGradLds m; int grid, region, gpart; size_t shmem; };
 
-inline int plan_lstm_grad(const int32_t* dims, int n_dims, int cols, int B, int n, LstmGradLaunch& a)
+inline int plan_lstm_grad(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int B, int n, LstmGradLaunch& a)
 {
-    const int rc = build_lstm_plan(dims, n_dims, cols, a.q);
+    const int rc = build_lstm_plan(dims, n_dims, cols, a.q, om, om_cols);
     if (rc != CS_OK) return rc;
     if (B < 1) return fail(CS_ERR_ARG, "B must be positive");
     if (n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
@@ -364,7 +373,9 @@ inline int plan_lstm_grad(const int32_t* dims, int n_dims, int cols, int B, int 
     lstm_param_offsets(a.q, a.o, a.og);
     a.m = lstm_grad_lds_map(a.q);
     a.shmem = (size_t)a.m.v.total * sizeof(float);
-    if (a.shmem > 160 * 1024) return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network do not fit the 160 KiB of LDS");
+    if (a.shmem > 160 * 1024)
+        return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(cols) + " + " + std::to_string(om_cols) +
+                                    " columns, H = " + std::to_string(a.q.H) + ": " + std::to_string(a.shmem) + " bytes) do not fit the 160 KiB of LDS");
     const int jobs = (B + JROWS - 1) / JROWS;
     a.grid = jobs < GRAD_MAX_GROUPS ? jobs : GRAD_MAX_GROUPS;
     a.gpart = up(a.o.total + 1, 4);
@@ -372,12 +383,10 @@ inline int plan_lstm_grad(const int32_t* dims, int n_dims, int cols, int B, int 
     return CS_OK;
 }
 
-} // namespace
-
-extern "C" int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
+inline int grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
 {
     LstmGradLaunch a;
-    const int rc = plan_lstm_grad(dims, n_dims, cols, B, n, a);
+    const int rc = plan_lstm_grad(dims, n_dims, cols, om, om_cols, B, n, a);
     if (rc != CS_OK) return rc;
     if (!n_param_floats || !n_scratch_floats) return fail(CS_ERR_ARG, "null argument");
     *n_param_floats = (size_t)a.o.total;
@@ -385,14 +394,12 @@ extern "C" int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int
     return CS_OK;
 }
 
-namespace {
-
-// the argument checks of cs_value_net_loss_grad_lstm, which cs_value_net_train_step_lstm makes first
+// the argument checks of the loss-and-gradient entries, which the train-step entries make first
 inline int check_lstm_grad_args(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, const float* d_grad,
-                                const float* d_loss, const float* d_scratch, size_t n_scratch_floats, LstmGradLaunch& a)
+                                size_t n_param_floats, int B, int n, int cols, bool om, int om_cols, const float* d_rows, const float* d_targets,
+                                const float* d_grad, const float* d_loss, const float* d_scratch, size_t n_scratch_floats, LstmGradLaunch& a)
 {
-    const int rc = plan_lstm_grad(dims, n_dims, cols, B, n, a);
+    const int rc = plan_lstm_grad(dims, n_dims, cols, om, om_cols, B, n, a);
     if (rc != CS_OK) return rc;
     if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
     if (n_weight_floats != (size_t)a.q.v.total_floats)
@@ -404,7 +411,7 @@ inline int check_lstm_grad_args(const int32_t* dims, int n_dims, const float* d_
     return CS_OK;
 }
 
-// the job kernel of both entries: every workgroup's partial gradient and loss term into its region of the scratch
+// the job kernel of the entries: every workgroup's partial gradient and loss term into its region of the scratch
 inline int launch_lstm_jobs(const LstmGradLaunch& a, const float* d_weights, const float* d_params, int B, int n, const float* d_rows,
                             const float* d_targets, float* d_scratch, float* d_values, void* stream)
 {
@@ -457,15 +464,14 @@ struct LstmSgdMap {
     }
 };
 
-} // namespace
-
-extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
-                                           float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+// cs_value_net_loss_grad_lstm[_om]
+inline int loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params, size_t n_param_floats,
+                          int B, int n, int cols, bool om, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                          float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
     LstmGradLaunch a;
-    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
-                                        d_scratch, n_scratch_floats, a);
+    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om, om_cols, d_rows, d_targets, d_grad,
+                                        d_loss, d_scratch, n_scratch_floats, a);
     if (rc != CS_OK) return rc;
     const int rc2 = launch_lstm_jobs(a, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
     if (rc2 != CS_OK) return rc2;
@@ -475,14 +481,15 @@ extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, cons
     return CS_OK;
 }
 
-extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
-                                            size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B,
-                                            int n, int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
-                                            double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+// cs_value_net_train_step_lstm[_om]
+inline int train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params, size_t n_param_floats,
+                           float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n, int cols, bool om, int om_cols,
+                           const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum, float* d_values,
+                           float* d_scratch, size_t n_scratch_floats, void* stream)
 {
     LstmGradLaunch a;
-    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, d_rows, d_targets, d_grad, d_loss,
-                                        d_scratch, n_scratch_floats, a);
+    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om, om_cols, d_rows, d_targets, d_grad,
+                                        d_loss, d_scratch, n_scratch_floats, a);
     if (rc != CS_OK) return rc;
     const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
     if (rc1 != CS_OK) return rc1;
@@ -494,17 +501,29 @@ extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, flo
     return CS_OK;
 }
 
-extern "C" int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+// what the blob-index and the device-pack entries do alike before their own part: the plan, the offsets, the size of the flat parameters
+inline int plan_lstm_flat(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, const void* a1, const void* a2, size_t n_param_floats,
+                          LstmPlan& q, GradOffsets& o, LstmGradOff& og)
 {
-    LstmPlan q;
-    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    const int rc = build_lstm_plan(dims, n_dims, cols, q, om, om_cols);
     if (rc != CS_OK) return rc;
-    GradOffsets o{};
-    LstmGradOff og{};
+    o = GradOffsets{};
+    og = LstmGradOff{};
     lstm_param_offsets(q, o, og);
-    if (!index) return fail(CS_ERR_ARG, "null argument");
+    if (!a1 || !a2) return fail(CS_ERR_ARG, "null argument");
     if (n_param_floats != (size_t)o.total)
         return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
+    return CS_OK;
+}
+
+// cs_value_net_blob_index_lstm[_om]
+inline int blob_index_lstm(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int32_t* index, size_t n_param_floats)
+{
+    LstmPlan q;
+    GradOffsets o;
+    LstmGradOff og;
+    const int rc = plan_lstm_flat(dims, n_dims, cols, om, om_cols, index, index, n_param_floats, q, o, og);
+    if (rc != CS_OK) return rc;
     const LstmSgdMap map{q, o, og};
     for (int i = 0; i < o.total; ++i) {         // (bias_hh's thread writes nothing: its float is bias_ih's, which names it as its twin)
         int twin;
@@ -515,21 +534,89 @@ extern "C" int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int
     return CS_OK;
 }
 
-extern "C" int cs_value_net_pack_lstm_device(const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
-                                             size_t n_blob_floats, void* stream)
+// cs_value_net_pack_lstm[_om]_device
+inline int pack_lstm_device(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, const float* d_params, size_t n_param_floats, float* d_blob,
+                            size_t n_blob_floats, void* stream)
 {
     LstmPlan q;
-    const int rc = build_lstm_plan(dims, n_dims, cols, q);
+    GradOffsets o;
+    LstmGradOff og;
+    const int rc = plan_lstm_flat(dims, n_dims, cols, om, om_cols, d_params, d_blob, n_param_floats, q, o, og);
     if (rc != CS_OK) return rc;
-    GradOffsets o{};
-    LstmGradOff og{};
-    lstm_param_offsets(q, o, og);
-    if (!d_params || !d_blob) return fail(CS_ERR_ARG, "null argument");
-    if (n_param_floats != (size_t)o.total)
-        return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
     if (n_blob_floats != (size_t)q.v.total_floats)
         return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack_lstm)");
     hipLaunchKernelGGL(k_vn_pack_lstm, dim3((q.v.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, q, o, og, d_params, d_blob);
     HIP_TRY(hipGetLastError());
     return CS_OK;
+}
+
+} // namespace
+
+// ---- LSTM-RL on rows of 13 | 15 columns: the entries above with no map columns
+extern "C" int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
+{
+    return grad_sizes_lstm(dims, n_dims, cols, false, 0, B, n, n_param_floats, n_scratch_floats);
+}
+
+extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                           size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
+                                           float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return loss_grad_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, false, 0, d_rows, d_targets, d_grad, d_loss,
+                          d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                            size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B,
+                                            int n, int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                                            double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return train_step_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols,
+                           false, 0, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
+{
+    return blob_index_lstm(dims, n_dims, cols, false, 0, index, n_param_floats);
+}
+
+extern "C" int cs_value_net_pack_lstm_device(const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
+                                             size_t n_blob_floats, void* stream)
+{
+    return pack_lstm_device(dims, n_dims, cols, false, 0, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+}
+
+// ---- OM-LSTM-RL: rows of cols + om_cols columns (build_lstm_plan refuses om_cols < 1)
+extern "C" int cs_value_net_grad_sizes_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
+                                               size_t* n_scratch_floats)
+{
+    return grad_sizes_lstm(dims, n_dims, cols, true, om_cols, B, n, n_param_floats, n_scratch_floats);
+}
+
+extern "C" int cs_value_net_loss_grad_lstm_om(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
+                                              size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets,
+                                              float* d_grad, float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return loss_grad_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, true, om_cols, d_rows, d_targets, d_grad, d_loss,
+                          d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_train_step_lstm_om(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
+                                               size_t n_param_floats, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B,
+                                               int n, int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
+                                               double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
+{
+    return train_step_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols,
+                           true, om_cols, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+}
+
+extern "C" int cs_value_net_blob_index_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
+{
+    return blob_index_lstm(dims, n_dims, cols, true, om_cols, index, n_param_floats);
+}
+
+extern "C" int cs_value_net_pack_lstm_om_device(const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats,
+                                                float* d_blob, size_t n_blob_floats, void* stream)
+{
+    return pack_lstm_device(dims, n_dims, cols, true, om_cols, d_params, n_param_floats, d_blob, n_blob_floats, stream);
 }
