@@ -952,6 +952,40 @@ int cs_step_f64(const cs_worlds_f64* w, double dt, int n_substeps, const double*
 int cs_update_humans_parallel_f64(const cs_worlds_f64* w, double dt, double* d_out, void* stream);
 int cs_peek_f64(const cs_worlds_f64* w, double dt, double* d_next /* [W][n][8] */, void* stream);
 
+/*
+ * Device episode buffer (csrc/episodes.hip): the per-world trajectory store behind crowd_nav/utils/explorer.py's
+ * update_memory / run_k_episodes, and the flush that turns finished episodes into replay-memory samples.  The store is the caller's:
+ * states [W][T][F], rewards [W][T], targets [W][T] float32, cursor [W] and overflow [W] int32 (all zero at the start).
+ *   cs_episode_append   every world w with t = cursor[w] < T stores d_state[w] (F floats), d_reward[w] and, when given, d_target[w] at
+ *                       [w][t] and advances its cursor; a world already at T stores nothing and sets overflow[w] = 1.  Two launches: the
+ *                       copy reads the cursors, the advance follows it on the stream.  d_target / d_targets may both be NULL.
+ *   cs_episode_flush    L_w = cursor[w]; kept_w = L_w where d_done[w], (keep_mask >> d_code[w]) & 1 and overflow[w] == 0, else 0.  Sample
+ *                       (w, i), i < kept_w, has the index g = sum_{u<w} kept_u + i of K = sum_w kept_w and goes to ring slot
+ *                       (position + g) mod capacity of d_mem_states [capacity + 1][F] / d_mem_values [capacity + 1] when g >= K - capacity:
+ *                       what K single pushes in the order world-ascending, step-ascending leave behind.  Row `capacity` is never written.
+ *                       Then position = (position + K) mod capacity, count = min(count + K, capacity) (int64 device scalars), and
+ *                       cursor[w] = overflow[w] = 0 for every done world.  The value of a sample: CS_EPISODE_RETURNS -- the discounted
+ *                       return-to-go sum_{t>=i} gamma^((t-i) * dt * v_w) * r_t, float64 products and sums in ascending t (explorer.py:132)
+ *                       rounded once to float32, v_w = d_v_pref[w] or v_pref when d_v_pref is NULL; CS_EPISODE_STORED -- the target given
+ *                       at append.  d_figures [6] float64 accumulates over the done worlds: episodes, those of code 2 / 3 / 4 (ReachGoal,
+ *                       Collision, Timeout), sum of L_w * dt over code 2, sum of sum_t gamma^(t * dt * v_w) * r_t (explorer.py:99); an
+ *                       overflowed episode counts with the T steps it stored.  d_scratch: 16 * (W + 1) bytes, 8-byte aligned.  Three
+ *                       launches on `stream`, integer prefix sum and fixed-shape float64 sums: no atomics on floats, nothing read back.
+ * Errors (CS_ERR_ARG with a message, before any device call): a null pointer (d_target / d_targets / d_v_pref excepted; CS_EPISODE_STORED
+ * needs d_targets; a d_target needs d_targets), W, T, F or capacity < 1, T above 2048 (the discount table and the rewards of a world live
+ * in LDS), W * T beyond 2^31 - 1, an unknown target mode, gamma outside (0, 1], dt <= 0, a d_scratch that is not 8-byte aligned.
+ */
+#define CS_EPISODE_RETURNS 0
+#define CS_EPISODE_STORED 1
+int cs_episode_append(int W, int T, int F, const float* d_state /* [W][F] */, const float* d_reward /* [W] */,
+                      const float* d_target /* [W] or NULL */, float* d_states, float* d_rewards, float* d_targets /* may be NULL */,
+                      int32_t* d_cursor, int32_t* d_overflow, void* stream);
+int cs_episode_flush(int W, int T, int F, const float* d_states, const float* d_rewards, const float* d_targets /* may be NULL */,
+                     int32_t* d_cursor, int32_t* d_overflow, const uint8_t* d_done /* [W] */, const int32_t* d_code /* [W] */,
+                     unsigned keep_mask, int target_mode, double gamma, double dt, double v_pref, const double* d_v_pref /* [W] or NULL */,
+                     int capacity, float* d_mem_states, float* d_mem_values, void* d_position /* int64 */, void* d_count /* int64 */,
+                     double* d_figures /* [6] */, void* d_scratch, void* stream);
+
 /* layout conversion of a state array between the reference's AoS rows and SoA planes */
 int cs_state_aos_to_soa(const float* d_aos, float* d_soa, int W, int rows, void* stream);
 int cs_state_soa_to_aos(const float* d_soa, float* d_aos, int W, int rows, void* stream);

@@ -192,6 +192,8 @@ ABI = {
     "cs_step_f64": (I, [WORLDS64, D, I, P, P]),
     "cs_update_humans_parallel_f64": (I, [WORLDS64, D, P, P]),
     "cs_peek_f64": (I, [WORLDS64, D, P, P]),
+    "cs_episode_append": (I, [I, I, I, P, P, P, P, P, P, P, P, P]),
+    "cs_episode_flush": (I, [I, I, I, P, P, P, P, P, P, P, U, I, D, D, D, P, I, P, P, P, P, P, P, P]),
     "cs_state_aos_to_soa": (I, [P, P, I, I, P]),
     "cs_state_soa_to_aos": (I, [P, P, I, I, P]),
     "cs_launch_geometry": (I, [WORLDS, P, P, P]),

@@ -28,6 +28,17 @@ class ReplayMemory(Dataset):
         self._position = torch.zeros((), dtype=torch.int64, device=state.device)
         self._count = torch.zeros((), dtype=torch.int64, device=state.device)
 
+    def _attach(self, state_shape, dtype, device):
+        """What a writer that fills the ring itself (crowd_nav.utils.episodes.EpisodeBuffer.flush) needs first: the tensors of an empty
+        memory allocated for states of `state_shape`, as push_batch does on first use, and a memory of another state shape, dtype or device
+        refused."""
+        if self.states is None:
+            self._allocate(torch.empty(tuple(state_shape), dtype=dtype, device=device), torch.float32)
+        have = (tuple(self.states.shape[1:]), self.states.dtype, self.values.dtype, self.states.device)
+        if have != (tuple(state_shape), dtype, torch.float32, torch.device(device)):
+            raise ValueError(f"ReplayMemory: states {tuple(state_shape)} {dtype} on {device} in a memory of {have[0]} {have[1]} (values {have[2]}) "
+                             f"on {have[3]}")
+
     @property
     def device(self):
         return None if self.states is None else self.states.device
