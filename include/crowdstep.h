@@ -778,6 +778,35 @@ int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const float* d_wei
                              int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_lstm_bf16  cs_value_net_decide_lstm with the opt-in bf16 arithmetic (csrc/value_net_lstm_bf16.hip): the
+ *   same arguments, results, errors and messages, with the blob of cs_value_net_pack_lstm_bf16 and its length in bytes.  float32 layers
+ *   (full weights, unrounded inputs): network 1's weight_ih on the raw row, network 2's mlp1 layer 0, mlp's layer 0.  bf16 layers (weights
+ *   rounded to bf16, nearest even, by the pack; float32 biases and accumulation): weight_hh, network 2's weight_ih, every mlp1 / mlp layer
+ *   behind the first.  Rounded once, nearest even, when stored as a bf16 operand: h_t after o * tanh(c) (the next step's operand and what
+ *   mlp reads as h_n), an mlp1 / mlp activation behind bias and ReLU that a bf16 layer reads, mlp1's last output.  Never rounded: c, the
+ *   gate pre-activations, sigmoid, tanh, mlp's last output, the value.  A gate pre-activation is one chain: the bias, the input's part,
+ *   then weight_hh's.  Position independence, the order rule, the pick and d_override are cs_value_net_decide_lstm's.
+ * cs_value_net_pack_lstm_bf16  (host only) params as cs_value_net_pack_lstm takes them.  blob == NULL: only *n_bytes is set.  Layout, one
+ *   piece after the other, each a whole number of floats, weights and biases beyond a width zero:
+ *     mlp1's layer 0, mlp's layer 0   float32 layers as cs_value_net_pack lays them out: float [ncb][kg][64 lanes][4], float bias[32 ncb];
+ *     every other mlp1 / mlp layer    as cs_value_net_pack_bf16 lays a bf16 layer out: bf16 [ncb][ks][64 lanes][8] with ncb = ceil(N / 32),
+ *                       ks = ceil(K / 16): lane l, element e of k-step s of block b holds weight[32 b + (l & 31)][16 s + 8 (l >> 5) + e];
+ *                       then float bias[32 ncb];
+ *     the gates (between mlp1's layers and mlp's)   [nb][ksh + ksx][64 lanes] slots of 16 bytes, nb = ceil(H / 8) blocks of 8 hidden units;
+ *                       lane l of block b stands for row = (j >> 3) * H + 8 b + (j & 7), j = l & 31.  Slot s < ksh = ceil(H / 16): 8 bf16,
+ *                       element e = weight_hh[row][16 s + 8 (l >> 5) + e].  The ksx slots behind them hold weight_ih: network 2, ksx =
+ *                       ceil(in / 16), 8 bf16, element e = weight_ih[row][16 (s - ksh) + 8 (l >> 5) + e]; network 1, ksx = ceil(cols / 8),
+ *                       4 floats, element e = weight_ih[row][8 (s - ksh) + 4 (l >> 5) + e].  Then float bias[32 nb], bias[32 b + j] =
+ *                       bias_ih[row] + bias_hh[row] summed in float32.
+ *   A NaN weight becomes the quiet NaN 0x7fc0.
+ */
+int cs_value_net_pack_lstm_bf16(const int32_t* dims, int n_dims, int cols, const float* const* params, void* blob, size_t* n_bytes);
+int cs_value_net_decide_lstm_bf16(const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n, int cols,
+                                  int sorted_by_distance, const float* d_rotated, const float* d_rewards, const float* d_actions,
+                                  const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values,
+                                  int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * cs_value_net_loss_grad_lstm  cs_value_net_loss_grad for LSTM-RL (crowd_nav/policy/lstm_rl.py:9-65, ValueNetwork1 and ValueNetwork2;
  *   csrc/value_net_lstm_grad.hip): what crowd_nav/utils/trainer.py:50-71 does per minibatch before optimizer.step() -- zero_grad,
  *   outputs = model(inputs), loss = MSELoss(outputs, values), loss.backward() -- by backpropagation through time, in two launches on `stream`.

@@ -16,7 +16,11 @@ cs_value_net_pack_om, ``occupancy_maps`` is cs_occupancy_maps, ``decide_om`` cs_
 LSTM-RL (crowd_nav/policy/lstm_rl.py) has a kernel of its own (cs_value_net_decide_lstm, csrc/value_net_lstm.hip) and its own description:
 ``describe`` answers CS_VN_LSTM -- a tag of this module, not a `kind` of the C entries --, such a ``DeviceNet`` packs through
 cs_value_net_pack_lstm, ``decide_lstm`` is the library call and ``decide_for_worlds`` runs lookahead -> decide_lstm(sorted_by_distance=1);
-``state_values_for_worlds`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor only.
+``state_values_for_worlds`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor, or -- under
+names of its own, so that what ``set_decision_precision``, ``check_decision_input`` and ``pack`` refuse stays refused -- the opt-in recurrent
+bf16 arithmetic (csrc/value_net_lstm_bf16.hip): RECURRENT_PRECISIONS, ``pack_lstm_bf16`` (cs_value_net_pack_lstm_bf16),
+``decide_lstm_bf16`` (cs_value_net_decide_lstm_bf16), ``DeviceNet.refresh_recurrent`` (a blob under a key of its own) and
+``decide_for_worlds(..., recurrent_precision="bf16")``; a policy chooses with ``LstmRL.set_recurrent_precision``.
 
 OM-LSTM-RL (crowd_nav/policy/om_lstm_rl.py: lstm_rl.with_om = true) is the recurrent network on rows widened by the maps: a CS_VN_LSTM
 ``DeviceNet`` with ``om_cols`` > 0 packs through cs_value_net_pack_lstm_om and decides through cs_value_net_decide_lstm_om
@@ -65,6 +69,8 @@ CS_VN_LSTM = "lstm"                # this module's tag of an LSTM-RL network: th
 MAP_ORDERS = frozen({"own": 0, "reference": 1})      # include/crowdstep.h CS_VN_MAPS_OWN, CS_VN_MAPS_FIRST_ACTION
 PRECISIONS = ("f32", "bf16")
 DECISION_INPUTS = ("tensor", "fused")
+RECURRENT_PRECISIONS = ("f32", "bf16")      # of the recurrent family without map columns: "bf16" is cs_value_net_decide_lstm_bf16
+RECURRENT_BF16 = "recurrent_bf16"           # DeviceNet's key of that arithmetic's blob
 
 
 def check_precision(precision):
@@ -155,6 +161,19 @@ def has_mapped_gradient_kernel(family):
     return family is MAPPED or family is RECURRENT_MAPPED
 
 
+def check_recurrent_precision(precision, family=None):
+    """The arithmetic of the recurrent decision kernel a policy may hold: one of RECURRENT_PRECISIONS; "bf16" for the recurrent family
+    without map columns alone (`family`: the policy's or the net's row, None asks only the name)."""
+    if precision not in RECURRENT_PRECISIONS:
+        raise ValueError(f"recurrent precision {precision!r}: one of {', '.join(map(repr, RECURRENT_PRECISIONS))}")
+    if precision == "bf16" and family is not None and family is not RECURRENT:
+        if family is RECURRENT_MAPPED:
+            raise ValueError('recurrent precision "bf16" for a recurrent network with occupancy-map columns: OM-LSTM-RL has the one kernel, '
+                             'cs_value_net_decide_lstm_om, float32 on the look-ahead tensor and the maps')
+        raise ValueError('recurrent precision "bf16": the network is not an LSTM-RL one (CADRL and SARL choose with set_decision_precision)')
+    return precision
+
+
 def check_map_order(map_order):
     if map_order not in MAP_ORDERS:
         raise ValueError(f"map order {map_order!r}: one of {', '.join(map(repr, sorted(MAP_ORDERS, reverse=True)))}")
@@ -226,6 +245,15 @@ def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     return _pack_with(getattr(_lib.load(), entry), unit, lead, arrays)
 
 
+def pack_lstm_bf16(dims, cols, arrays):
+    """cs_value_net_pack_lstm_bf16's blob (uint8 numpy: include/crowdstep.h states the bytes) of an LSTM-RL network without map columns from
+    the float32 arrays ``pack(CS_VN_LSTM, ...)`` takes.  Host only: no GPU needed."""
+    from ... import _lib
+
+    dims = np.ascontiguousarray(dims, np.int32)
+    return _pack_with(_lib.load().cs_value_net_pack_lstm_bf16, np.uint8, (dims.ctypes.data, len(dims), cols), arrays)
+
+
 def _pack_with(entry, unit, lead, arrays):
     """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `lead`: the arguments
     it takes before the arrays."""
@@ -255,8 +283,8 @@ class DeviceNet:
         self.kind, self.dims, self.layers = describe(model)
         self.family = family_of(self.kind, self.om_cols)
         self.lstm = self.kind == CS_VN_LSTM
-        self._keys = dict.fromkeys(PRECISIONS)
-        self.blobs = dict.fromkeys(PRECISIONS)
+        self._keys = dict.fromkeys(PRECISIONS + (RECURRENT_BF16,))       # (the recurrent bf16 blob under a key of its own: "bf16" stays
+        self.blobs = dict.fromkeys(PRECISIONS + (RECURRENT_BF16,))      # the feed-forward arithmetic's, which a recurrent net refuses)
         self.flat = None
 
     @property
@@ -284,6 +312,21 @@ class DeviceNet:
             self._keys[precision] = key
         return self.blobs[precision]
 
+    def refresh_recurrent(self, precision="f32"):
+        """``refresh`` for the recurrent family's own arithmetics (RECURRENT_PRECISIONS): "f32" is ``refresh("f32")``; "bf16" keeps
+        cs_value_net_pack_lstm_bf16's blob under the key RECURRENT_BF16, rebuilt on the same version-counter rule and dropped by
+        ``updated_on_device``; it never aliases the float32 blob."""
+        import torch
+
+        if check_recurrent_precision(precision, self.family) == "f32":
+            return self.refresh("f32")
+        key = self._versions()
+        if key != self._keys[RECURRENT_BF16]:
+            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
+            self.blobs[RECURRENT_BF16] = torch.from_numpy(pack_lstm_bf16(self.dims, self.cols, arrays)).to("cuda")
+            self._keys[RECURRENT_BF16] = key
+        return self.blobs[RECURRENT_BF16]
+
     def adopt_flat(self, flat, mapped=False):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
         ``Trainer.set_gradient("device")`` or ``("device_lstm")`` makes them): from now on ``refresh("f32")`` packs the blob on the device
@@ -307,7 +350,7 @@ class DeviceNet:
         other precision's key is dropped, so its next ``refresh`` packs from the new numbers."""
         if self.flat is None:
             raise ValueError("updated_on_device: the network has adopted no flat parameters (adopt_flat)")
-        for precision in PRECISIONS:
+        for precision in self._keys:
             if precision != "f32":
                 self._keys[precision] = None
 
@@ -657,6 +700,21 @@ def decide_lstm(net, W, A, n, sorted_by_distance, rotated, rewards, actions, rob
                 action_out, stream)
 
 
+def decide_lstm_bf16(net, W, A, n, sorted_by_distance, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                     action_out, stream=None):
+    """cs_value_net_decide_lstm_bf16 on device pointers (ints): ``decide_lstm`` in the opt-in bf16 arithmetic, for a DeviceNet of an LSTM-RL
+    network without map columns whose recurrent bf16 blob is current (``refresh_recurrent("bf16")``)."""
+    from ... import _lib
+
+    if net.family is not RECURRENT:
+        raise ValueError("decide_lstm_bf16: the network is not an LSTM-RL one without map columns (lstm_rl.ValueNetwork1 / ValueNetwork2)")
+    blob = net.blobs[RECURRENT_BF16]
+    if blob is None:
+        raise ValueError('decide_lstm_bf16: the network has no recurrent bf16 blob yet (DeviceNet.refresh_recurrent("bf16"))')
+    _lib.check(_lib.load().cs_value_net_decide_lstm_bf16(*_head((), net.dims, blob), W, A, n, net.cols, int(bool(sorted_by_distance)), rotated, rewards,
+                                                         actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream))
+
+
 def decide_lstm_om(net, W, A, n, sorted_by_distance, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
                    action_out, stream=None):
     """cs_value_net_decide_lstm_om on device pointers (ints): ``decide_lstm`` for a DeviceNet of an OM-LSTM-RL network, maps
@@ -770,15 +828,23 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
     return rot, rew
 
 
-def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None):
+def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None,
+                      recurrent_precision="f32"):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
     decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order (with map columns: lookahead,
     occupancy_maps on the NEXT humans, decide_lstm_om in that order with the net's ``map_order``); a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
     branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
-    "fused"."""
+    "fused".  ``recurrent_precision`` "bf16" (an LSTM-RL net without map columns alone, whose ``refresh_recurrent("bf16")`` blob is current):
+    lookahead, then decide_lstm_bf16 in the decision's order."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
+    if check_recurrent_precision(recurrent_precision, net.family) == "bf16":
+        check_mode(net.family, decision_input, precision)
+        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
+        decide_lstm_bf16(net, W, A, n, 1, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
+                         values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return rot, rew
     if check_mode(net.family, decision_input, precision) == "fused":      # one library call on the worlds' own rows
         decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
                       None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)

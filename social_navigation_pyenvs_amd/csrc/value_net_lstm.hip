@@ -90,25 +90,7 @@ inline void pack_gates(const LstmPlan& q, const float* wih, const float* whh, co
     }
 }
 
-// an integer that orders like the distance: NaN above everything (numpy's argsort leaves it last, the flip first), -0 = +0
-__device__ __forceinline__ unsigned lstm_key(float x)
-{
-    if (x != x) return 0xFFFFFFFFu;
-    unsigned u = __float_as_uint(x);
-    if (x == 0.0f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// rows perm[s][t] of the tile's sequences into rows of stride ld: 16 columns a row, zeros beyond the columns and the sequences
-__device__ __forceinline__ void lstm_gather(float* X, int ld, const float* __restrict__ rotated, const int* perm, long gbase, int ng, int n, int cols, int t)
-{
-    for (int i = threadIdx.x; i < TILE_M * 16; i += NT) {
-        const int s = i >> 4, c = i & 15;
-        float v = 0.0f;
-        if (s < ng && c < cols) v = rotated[((gbase + s) * n + perm[s * n + t]) * cols + c];
-        X[s * ld + c] = v;
-    }
-}
+// (lstm_key and lstm_gather, the order's key and a step's gather, are value_net_lstm_plan.h's: value_net_lstm_bf16.hip uses them too)
 
 // What the rows with map columns add to a launch (cs_value_net_decide_lstm_om): the maps [W][n][om_cols], which map a step pairs with its
 // row, xw = cols + om_cols rounded up to 8 (the columns a gathered row holds) and where the keys and the order of a world's action 0 lie in LDS.

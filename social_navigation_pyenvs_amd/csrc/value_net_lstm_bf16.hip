@@ -1,0 +1,482 @@
+// value_net_lstm_bf16.hip -- LSTM-RL's decision (value_net_lstm.hip: cs_value_net_decide_lstm) with the opt-in bf16 arithmetic
+// (cs_value_net_decide_lstm_bf16; Python: LstmRL.set_recurrent_precision("bf16")).  The recurrent family without map columns only: networks 1
+// and 2 on rows of 13 or 15 columns.  The tiling is k_value_net_lstm's -- a workgroup of 4 wavefronts owns 32 sequences, the order of a
+// sequence's rows is ranked in LDS, the gates are the TRANSPOSED product (A = the gate weights, rows 8 * gate + unit of a block of 8 hidden
+// units; B = the sequences' operand rows from LDS), wavefront w owns the blocks w, w + 4, ..., a lane holds i, f, g, o of four units of one
+// sequence, c stays in registers for all n steps -- and so are the sort, sorted_by_distance, the value and the pick (value_net_pick.h).
+//
+// The arithmetic:
+//   float32 layers   network 1's W_ih on the raw row x_t, network 2's mlp1 layer 0, layer 0 of mlp (it reads the raw self state): full
+//                    weights, unrounded inputs, v_mfma_f32_32x32x2_f32.  Columns reach 10 m, where one bf16 step is 3 cm.
+//   bf16 layers      W_hh in both networks, network 2's W_ih (it reads mlp1's output), every mlp1 / mlp layer behind the first: weights
+//                    rounded to bf16 (nearest even) at pack time, float32 biases, float32 accumulation, v_mfma_f32_32x32x16_bf16.
+//   rounding points  each value once, nearest even, when it is stored as a bf16 operand: h_t after o * tanh(c) -- that one rounded value is
+//                    the next step's operand and what mlp reads as h_n --; an mlp1 / mlp activation after the bias and the ReLU when a bf16
+//                    layer reads it; mlp1's last output (no ReLU) as the gates' operand of network 2.
+//   never rounded    c, the gate pre-activations, sigmoid and tanh (lstm_sigmoid, lstm_tanh), mlp's last output, rewards + gamma^(dt v_pref) V.
+//   order            a gate pre-activation is one fixed chain: b_ih + b_hh (summed in float32 by the pack), the x part (network 1: the
+//                    float32 k-groups ascending; network 2: W_ih's k-steps of 16 ascending), then W_hh's k-steps of 16 ascending.
+// The x part does not depend on h: the register-resident build issues it before the barrier that publishes h_{t-1}, so that only W_hh's
+// k-steps and the pointwise part lie between two barriers.  Hidden units beyond H are stored as exact 0.  A sequence's result depends on
+// its own rows alone: the same bits for W = 1 as inside any batch, at any position of a tile.  No atomics.  gfx950 only.
+//
+// LDS image of a bf16 operand (value_net_bf16.hip's): row-major bfloat16, a row of 16 * odd bytes (a stride of 4 * odd floats); lane l reads
+// the 8 k at 16 s + 8 (l >> 5) of row l & 31 with one ds_read_b128, conflict-free.  h: [2][32] rows of ceil(H / 16) * 16 bf16 (+ 8 bytes
+// of pitch), double-buffered; network 2's gate input: [32] rows of mlp1's last width rounded up to 32.
+#include <hip/hip_runtime.h>
+
+#include "value_net_lstm_plan.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int RB = 2, RKH = 4, RKX = 4;    // register-resident gate weights: blocks a wavefront; 16-byte lane slots of W_hh and of the x part a block
+constexpr int GB = 8;                      // blocks a wavefront at the widest H (256 / 8 / 4)
+
+// the float32 plan and what this arithmetic changes: ksh k-steps of 16 of W_hh; ksx slots of the x part (network 1: float32 k-groups of 8 of
+// W_ih, network 2: k-steps of 16); the strides (floats) of the h rows and of network 2's gate input rows
+struct LstmHPlan { LstmPlan q; int ksh, ksx, ld_h, ld_xb; };
+
+__host__ __device__ inline bool lh_f32_layer(const VnPlan& p, int l) { return l == p.c0[0] || l == p.c0[1]; }
+// a layer whose output is the operand of a bf16 layer: all of mlp1 (its last output is the gates' operand), mlp but its last layer
+inline bool lh_out_bf16(const VnPlan& p, int l) { return l < p.c0[1] || l != p.c0[2] - 1; }
+
+// build_lstm_plan's table with the bf16 layers and the gates counted in 16-byte lane slots, the blob offsets that follow (in floats: a
+// lane's 8 bf16 are 4 floats wide, so a piece keeps the size formula ncb * slots * 64 * 4 + ncb * 32) and the strides of bf16 rows
+inline int build_lstm_bf16_plan(const int32_t* dims, int n_dims, int cols, LstmHPlan& s)
+{
+    const int rc = build_lstm_plan(dims, n_dims, cols, s.q);
+    if (rc != CS_OK) return rc;
+    VnPlan& p = s.q.v;
+    VnLayer& g = s.q.g;
+    int off = 0, widest = 36;
+    const auto place = [&](VnLayer& L) {
+        L.w_off = off;
+        off += L.ncb * L.kg_total * 64 * 4;
+        L.b_off = off;
+        off += L.ncb * 32;
+    };
+    for (int l = 0; l < p.n_layers; ++l) {
+        if (l == p.c0[1]) {             // the gates lie between the two chains in the blob
+            s.ksh = up(s.q.H, 16) / 16;
+            s.ksx = p.c0[1] > 0 ? up(s.q.xin, 16) / 16 : up(cols, 8) / 8;
+            g.kg_split = s.ksh;
+            g.kg_total = s.ksh + s.ksx;
+            place(g);
+        }
+        VnLayer& L = p.L[l];
+        if (!lh_f32_layer(p, l)) L.kg_split = L.kg_total = up(L.K1, 16) / 16;
+        place(L);
+        const int ld = lh_out_bf16(p, l) ? L.ncb * 16 + 4 : L.ncb * 32 + 4;
+        widest = ld > widest ? ld : widest;
+    }
+    p.ld_pq = widest;
+    p.total_floats = off;
+    s.ld_h = up(s.q.H, 16) / 2 + 4;
+    s.ld_xb = up(s.q.xin, 32) / 2 + 4;
+    return CS_OK;
+}
+
+struct LstmHLds { int key, perm, G, HB, XB, P, Q, J, LT, total; };
+
+inline LstmHLds lstm_bf16_lds_map(const LstmHPlan& s, int n)
+{
+    const VnPlan& p = s.q.v;
+    LstmHLds m{};
+    int o = 0;
+    auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
+    m.key = take(TILE_M * n);
+    m.perm = take(TILE_M * n);
+    m.G = take(2 * TILE_M * LDX);
+    m.HB = take(2 * TILE_M * s.ld_h);
+    m.XB = p.c0[1] > 0 ? take(TILE_M * s.ld_xb) : m.HB;
+    m.P = take(TILE_M * p.ld_pq);
+    m.Q = take(TILE_M * p.ld_pq);
+    m.J = take(JROWS * p.ld_j);
+    m.LT = take(VN_MAX_LAYERS * 8);
+    m.total = o;
+    return m;
+}
+
+inline uint16_t bf16_bits(float f)       // round to nearest even; a NaN becomes the quiet NaN 0x7fc0 (what torch's .bfloat16() gives)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+// one bf16 layer's weights where the lanes of lh_layer read them (cs_value_net_pack_bf16's layout of a bf16 layer); blob zeroed before
+inline void pack_layer_bf16(const VnLayer& L, const float* wgt, const float* bias, float* fb)
+{
+    uint16_t* hb = reinterpret_cast<uint16_t*>(fb + L.w_off);
+    for (int cb = 0; cb < L.ncb; ++cb)
+        for (int ks = 0; ks < L.kg_total; ++ks)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 8; ++e) {
+                    const int j = cb * 32 + (lane & 31), k = ks * 16 + 8 * (lane >> 5) + e;
+                    if (j < L.N && k < L.K1) hb[((size_t)(cb * L.kg_total + ks) * 64 + lane) * 8 + e] = bf16_bits(wgt[(size_t)j * L.K1 + k]);
+                }
+    for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
+}
+
+// the gate rows where the lanes of the transposed product read them: slot s of block b, lane l, gate row j = l & 31 = 8 * gate + u, torch's
+// row gate * H + 8 b + u.  Slots below ksh: 8 bf16 of weight_hh at k = 16 s + 8 (l >> 5) + e.  Behind them the x part: network 2, 8 bf16 of
+// weight_ih at k = 16 (s - ksh) + 8 (l >> 5) + e; network 1, 4 floats of weight_ih at k = 8 (s - ksh) + 4 (l >> 5) + e.  bias = b_ih + b_hh
+// in float32.  blob zeroed before
+inline void pack_gates_bf16(const LstmHPlan& s, const float* wih, const float* whh, const float* bih, const float* bhh, float* fb)
+{
+    const VnLayer& g = s.q.g;
+    const int H = s.q.H, xin = s.q.xin;
+    const bool net2 = s.q.v.c0[1] > 0;
+    for (int cb = 0; cb < g.ncb; ++cb)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int j = lane & 31, hh = lane >> 5, unit = cb * 8 + (j & 7), row = (j >> 3) * H + unit;
+            if (unit >= H) continue;
+            if (hh == 0) fb[g.b_off + cb * 32 + j] = bih[row] + bhh[row];
+            for (int sl = 0; sl < g.kg_total; ++sl) {
+                float* slot = fb + g.w_off + ((size_t)(cb * g.kg_total + sl) * 64 + lane) * 4;
+                uint16_t* hs = reinterpret_cast<uint16_t*>(slot);
+                if (sl < s.ksh) {
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 16 * sl + 8 * hh + e;
+                        if (k < H) hs[e] = bf16_bits(whh[(size_t)row * H + k]);
+                    }
+                } else if (net2) {
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 16 * (sl - s.ksh) + 8 * hh + e;
+                        if (k < xin) hs[e] = bf16_bits(wih[(size_t)row * xin + k]);
+                    }
+                } else {
+                    for (int e = 0; e < 4; ++e) {
+                        const int k = 8 * (sl - s.ksh) + 4 * hh + e;
+                        if (k < xin) slot[e] = wih[(size_t)row * xin + k];
+                    }
+                }
+            }
+        }
+}
+
+// One layer of the tile's 32 rows, one row block, the waves over the 32-column output blocks: value_net_lstm.hip's lstm_layer (the fields
+// from the table in LDS, a one-deep weight prefetch) in this file's two arithmetics.  in_bf16: src holds bfloat16 rows (stride lds_ floats)
+// and the weights are k-steps of 16 (value_net_bf16.hip's layer_fwd_h); else the float32 layer.  out_bf16: the output is the operand of a
+// bf16 layer -- dst holds bfloat16 rows of 2 * ldd elements, each value rounded to nearest even after the bias and the ReLU.  The two are
+// arguments, uniform over the workgroup, not template arguments: one copy of the layer per call site keeps the kernel at two workgroups a CU.
+enum { LT_N, LT_KG, LT_NCB, LT_RELU, LT_W, LT_B, LT_STRIDE = 8 };
+
+__device__ __forceinline__ void lh_layer(const int* lt, const float* __restrict__ wb, const float* src, int lds_, float* dst, int ldd, bool in_bf16, bool out_bf16)
+{
+    const auto field = [&](int k) { return __builtin_amdgcn_readfirstlane(lt[k]); };
+    const struct { int N, kg_total, ncb, relu, w_off, b_off; } L{field(LT_N), field(LT_KG), field(LT_NCB), field(LT_RELU), field(LT_W), field(LT_B)};
+    const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31, KG = L.kg_total;
+    const float* a1 = src + li * lds_ + 4 * h;
+    for (int cb = threadIdx.x >> 6; cb < L.ncb; cb += 4) {
+        const float4* bw = reinterpret_cast<const float4*>(wb + L.w_off) + cb * KG * 64 + lane;
+        const float bias = wb[L.b_off + cb * 32 + li];
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bias;
+        float4 nw = bw[0];
+        for (int kg = 0; kg < KG; ++kg) {
+            const float4 w = nw;
+            nw = bw[(kg + 1 < KG ? kg + 1 : kg) * 64];
+            const float4 a = *reinterpret_cast<const float4*>(a1 + kg * 8);
+            if (in_bf16) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, w), acc, 0, 0, 0);
+            } else {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
+            }
+        }
+        // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+        const bool pad = cb * 32 + li >= L.N;              // (the zero weights give 0 * inf = NaN there when an input is infinite)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = acc[r];
+            if (L.relu) v = v < 0.0f ? 0.0f : v;          // (a NaN stays a NaN, as torch's ReLU leaves it)
+            acc[r] = pad ? 0.0f : v;
+        }
+        const int ocol = cb * 32 + li;
+        if (out_bf16) {
+            __bf16* d = reinterpret_cast<__bf16*>(dst) + 4 * h * 2 * ldd + ocol;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d[((r & 3) + 8 * (r >> 2)) * 2 * ldd] = static_cast<__bf16>(acc[r]);
+        } else {
+            float* d = dst + 4 * h * ldd + ocol;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d[((r & 3) + 8 * (r >> 2)) * ldd] = acc[r];
+        }
+    }
+}
+
+// layers [first, last) from `src` (float32 rows: the first layer of either chain is a float32 layer), a barrier behind each; outputs
+// alternate P, Q, the last one goes to final_dst when given.  HEAD: the chain is mlp, whose last output stays float32; else mlp1, whose
+// every output is a bf16 operand.  Returns where the result is, out_ld its row stride.
+template <bool HEAD>
+__device__ __forceinline__ const float* lh_chain(const int* ltab, int ld_pq, const float* __restrict__ wb, float* P, float* Q, int first, int last,
+                                                 const float* src, int lds_, float* final_dst, int final_ld, int& out_ld)
+{
+    const float* cur = src;
+    int cur_ld = lds_;
+    for (int l = first; l < last; ++l) {
+        const bool fin = l == last - 1, given = fin && final_dst;
+        float* dst = given ? final_dst : (((l - first) & 1) ? Q : P);
+        const int ldd = given ? final_ld : ld_pq;
+        const int* lt = ltab + l * LT_STRIDE;
+        lh_layer(lt, wb, cur, cur_ld, dst, ldd, l != first, HEAD ? !fin : true);
+        __syncthreads();
+        cur = dst;
+        cur_ld = ldd;
+    }
+    out_ld = cur_ld;
+    return cur;
+}
+
+// one 16-byte slot of the x part (network 1: a float32 k-group of W_ih on the raw row; network 2: a bf16 k-step of W_ih on mlp1's rounded
+// output) and one of W_hh on the rounded h; `row`: the lane's operand row in LDS at the slot (its sequence, its half of the k range)
+template <bool MLP1>
+__device__ __forceinline__ void lh_x_slot(f32x16& acc, const float4 w, const float* row)
+{
+    if constexpr (MLP1) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), *reinterpret_cast<const bf16x8*>(row), acc, 0, 0, 0);
+    } else {
+        const float4 xv = *reinterpret_cast<const float4*>(row);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, xv.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, xv.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, xv.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, xv.w, acc, 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ void lh_h_slot(f32x16& acc, const float4 w, const float* row)
+{
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), *reinterpret_cast<const bf16x8*>(row), acc, 0, 0, 0);
+}
+
+// the pointwise part of a block: the lane's i, f, g, o of four hidden units of its sequence -> c (float32, in place) and h, rounded once and
+// stored as 4 bf16 (units beyond H as 0: the zero weights give 0 for finite inputs only)
+__device__ __forceinline__ void lh_pointwise(const f32x16& acc, float (&c)[4], int unit0, int H, __bf16* hdst)
+{
+    bf16x4 hv;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float ig = lstm_sigmoid(acc[u]), fg = lstm_sigmoid(acc[4 + u]), gg = lstm_tanh(acc[8 + u]), og = lstm_sigmoid(acc[12 + u]);
+        const float cn = fg * c[u] + ig * gg;
+        c[u] = cn;
+        hv[u] = static_cast<__bf16>(unit0 + u < H ? og * lstm_tanh(cn) : 0.0f);
+    }
+    *reinterpret_cast<bf16x4*>(hdst + unit0) = hv;
+}
+
+template <bool WREG, bool MLP1>
+__global__ __launch_bounds__(NT, 2) void k_value_net_lstm_bf16(LstmHPlan s, LstmHLds m, const float* __restrict__ wb, int NG, int A, int n, int sorted,
+                                                            const float* __restrict__ rotated, const float* __restrict__ rewards,
+                                                            const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values)
+{
+    extern __shared__ float lds[];
+    constexpr int NB = WREG ? RB : GB;
+    const LstmPlan& q = s.q;
+    const VnPlan& p = q.v;
+    float *P = lds + m.P, *Q = lds + m.Q, *J = lds + m.J, *G = lds + m.G, *HB = lds + m.HB, *XB = lds + m.XB;
+    unsigned* key = reinterpret_cast<unsigned*>(lds + m.key);
+    int* perm = reinterpret_cast<int*>(lds + m.perm);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5, li = lane & 31;
+    const int row8 = tid >> 3;
+    const int cols = p.cols, H = q.H, ldh = s.ld_h, ksh = s.ksh, ksx = s.ksx, KT = q.g.kg_total;
+    const int nbw = (q.g.ncb - wave + 3) >> 2;              // this wavefront's blocks: wave, wave + 4, ...
+    constexpr int gbuf = TILE_M * LDX;
+    const float4* gw = reinterpret_cast<const float4*>(wb + q.g.w_off) + lane;
+    int out_ld;
+
+    int* ltab = reinterpret_cast<int*>(lds + m.LT);
+    if (tid == 0)
+        for (int l = 0; l < p.n_layers; ++l) {
+            int* e = ltab + l * LT_STRIDE;
+            e[LT_N] = p.L[l].N; e[LT_KG] = p.L[l].kg_total; e[LT_NCB] = p.L[l].ncb; e[LT_RELU] = p.L[l].relu; e[LT_W] = p.L[l].w_off; e[LT_B] = p.L[l].b_off;
+        }
+    // (the first barrier of the first job publishes the table)
+
+    float4 wh[RB][RKH], wx[RB][RKX];
+    if constexpr (WREG) {
+        const int slots = q.g.ncb * KT;
+#pragma unroll
+        for (int bi = 0; bi < RB; ++bi) {
+            const int at = ((tid >> 6) + 4 * bi) * KT;             // (clamped: what lies beyond the wavefront's blocks and slots is never used)
+#pragma unroll
+            for (int k = 0; k < RKH; ++k) wh[bi][k] = gw[(at + k < slots ? at + k : 0) * 64];
+#pragma unroll
+            for (int j = 0; j < RKX; ++j) wx[bi][j] = gw[(at + ksh + j < slots ? at + ksh + j : 0) * 64];
+        }
+    }
+
+    for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
+        const long gbase = (long)job * JROWS;
+        const int ng = NG - gbase < JROWS ? (int)(NG - gbase) : JROWS;
+        for (int i = tid; i < ng * n; i += NT) key[i] = lstm_key(rotated[(gbase * n + i) * cols + 11]);
+        for (int i = tid; i < JROWS * p.ld_j; i += NT) J[i] = 0.0f;
+        for (int i = tid; i < 2 * TILE_M * ldh; i += NT) HB[i] = 0.0f;           // h0 = 0, and the columns between H and the last k-step's end
+        __syncthreads();
+        for (int j = tid & 7; j < n && row8 < ng; j += 8) {          // eight lanes a sequence
+            int rank = j;
+            if (sorted) {
+                const unsigned kj = key[row8 * n + j];
+                rank = 0;
+#pragma unroll 1
+                for (int k = 0; k < n; ++k) {
+                    const unsigned kk = key[row8 * n + k];
+                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
+                }
+            }
+            perm[row8 * n + rank] = j;
+        }
+        __syncthreads();
+        lstm_gather(G, LDX, rotated, perm, gbase, ng, n, cols, 0);
+        float c[NB][4];
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) c[bi][u] = 0.0f;
+        __syncthreads();
+        // lstm_rl.py:25 / :53: the self state is read from the first row in evaluation order
+        if (row8 < ng && (tid & 7) < SELF_DIM) J[row8 * p.ld_j + (tid & 7)] = G[row8 * LDX + (tid & 7)];
+
+        for (int t = 0; t < n; ++t) {
+            const float* hrow = HB + (t & 1) * TILE_M * ldh + li * ldh + 4 * hh;
+            __bf16* hdst = reinterpret_cast<__bf16*>(HB + ((t + 1) & 1) * TILE_M * ldh + li * ldh);
+            if (t + 1 < n) lstm_gather(G + ((t + 1) & 1) * gbuf, LDX, rotated, perm, gbase, ng, n, cols, t + 1);
+            if constexpr (MLP1) lh_chain<false>(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, LDX, XB, s.ld_xb, out_ld);
+            const float* xrow = (MLP1 ? XB + li * s.ld_xb : G + (t & 1) * gbuf + li * LDX) + 4 * hh;
+            if constexpr (WREG) {
+                // the x part of every block of the wavefront, then the barrier that publishes h_{t-1}, then W_hh and the pointwise part
+                f32x16 acc[RB];
+#pragma unroll
+                for (int bi = 0; bi < RB; ++bi) {
+                    if (bi >= nbw) break;
+                    const float* bias = wb + q.g.b_off + (wave + 4 * bi) * 32 + 4 * hh;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[bi][r] = bias[(r & 3) + 8 * (r >> 2)];
+#pragma unroll
+                    for (int j = 0; j < RKX; ++j)
+                        if (j < ksx) lh_x_slot<MLP1>(acc[bi], wx[bi][j], xrow + 8 * j);
+                }
+                __syncthreads();
+#pragma unroll
+                for (int bi = 0; bi < RB; ++bi) {
+                    if (bi >= nbw) break;
+#pragma unroll
+                    for (int k = 0; k < RKH; ++k)
+                        if (k < ksh) lh_h_slot(acc[bi], wh[bi][k], hrow + 8 * k);
+                    lh_pointwise(acc[bi], c[bi], (wave + 4 * bi) * 8 + 4 * hh, H, hdst);
+                }
+            } else {
+                // the same chain per block, its weights from the blob; the second barrier keeps the next step's gather and mlp1 off this step's rows
+                __syncthreads();
+#pragma unroll
+                for (int bi = 0; bi < NB; ++bi) {
+                    if (bi >= nbw) break;
+                    const int blk = wave + 4 * bi;
+                    const float* bias = wb + q.g.b_off + blk * 32 + 4 * hh;
+                    f32x16 acc;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = bias[(r & 3) + 8 * (r >> 2)];
+                    const float4* w = gw + (long)blk * KT * 64;
+                    float4 nw = w[(long)ksh * 64];
+                    for (int j = 0; j < ksx; ++j) {
+                        const float4 wv = nw;
+                        nw = w[(long)(j + 1 < ksx ? ksh + j + 1 : 0) * 64];
+                        lh_x_slot<MLP1>(acc, wv, xrow + 8 * j);
+                    }
+                    for (int k = 0; k < ksh; ++k) {
+                        const float4 wv = nw;
+                        nw = w[(long)(k + 1 < ksh ? k + 1 : k) * 64];
+                        lh_h_slot(acc, wv, hrow + 8 * k);
+                    }
+                    lh_pointwise(acc, c[bi], blk * 8 + 4 * hh, H, hdst);
+                }
+                __syncthreads();
+            }
+        }
+        if constexpr (WREG) __syncthreads();          // (publishes h_n)
+
+        const __bf16* hn = reinterpret_cast<const __bf16*>(HB + (n & 1) * TILE_M * ldh);
+        for (int u = tid & 7; u < H; u += 8) J[row8 * p.ld_j + SELF_DIM + u] = static_cast<float>(hn[row8 * 2 * ldh + u]);
+        __syncthreads();
+        const float* out = lh_chain<true>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
+        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
+            const long g = gbase + tid;
+            const float vpref = robot[(g / A) * rstride + 7];
+            values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace
+
+#include "value_net_pick.h"
+
+extern "C" int cs_value_net_pack_lstm_bf16(const int32_t* dims, int n_dims, int cols, const float* const* params, void* blob, size_t* n_bytes)
+{
+    LstmHPlan s;
+    const int rc = build_lstm_bf16_plan(dims, n_dims, cols, s);
+    if (rc != CS_OK) return rc;
+    const VnPlan& p = s.q.v;
+    if (!n_bytes) return fail(CS_ERR_ARG, "null argument");
+    *n_bytes = (size_t)p.total_floats * sizeof(float);
+    if (!blob) return CS_OK;
+    if (!params) return fail(CS_ERR_ARG, "null argument");
+    const int n1 = p.c0[1], n_params = 2 * p.n_layers + 4;
+    for (int i = 0; i < n_params; ++i)
+        if (!params[i]) return fail(CS_ERR_ARG, "null weight or bias array");
+    float* fb = static_cast<float*>(blob);
+    memset(fb, 0, (size_t)p.total_floats * sizeof(float));
+    for (int l = 0; l < p.n_layers; ++l) {
+        const int at = l < n1 ? 2 * l : 2 * l + 4;          // (the LSTM's four arrays lie between mlp1's and mlp's)
+        if (lh_f32_layer(p, l)) pack_layer_f32(p.L[l], params[at], params[at + 1], fb);
+        else pack_layer_bf16(p.L[l], params[at], params[at + 1], fb);
+    }
+    pack_gates_bf16(s, params[2 * n1], params[2 * n1 + 1], params[2 * n1 + 2], params[2 * n1 + 3], fb);
+    return CS_OK;
+}
+
+extern "C" int cs_value_net_decide_lstm_bf16(const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n, int cols,
+                                             int sorted_by_distance, const float* d_rotated, const float* d_rewards, const float* d_actions,
+                                             const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override, float* d_values,
+                                             int32_t* d_choice, float* d_action_out, void* stream)
+{
+    LstmHPlan s;
+    const int rc = build_lstm_bf16_plan(dims, n_dims, cols, s);
+    if (rc != CS_OK) return rc;
+    const LstmPlan& q = s.q;
+    // (a length that is no whole number of floats is no blob of any network: it fails the size check as SIZE_MAX floats)
+    const size_t n_floats = n_weight_bytes % sizeof(float) ? (size_t)-1 : n_weight_bytes / sizeof(float);
+    const int rc2 = check_decide_args(q.v, d_weights, n_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    if (rc2 != CS_OK) return rc2;
+    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
+    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm_bf16 takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
+    const LstmHLds m = lstm_bf16_lds_map(s, n);
+    const size_t shmem = (size_t)m.total * sizeof(float);
+    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
+    int NG, grid;
+    job_grid(W, A, NG, grid);
+    const bool wreg = q.g.ncb <= 4 * RB && s.ksh <= RKH && s.ksx <= RKX, mlp1 = q.v.c0[1] > 0;
+    const float* wb = static_cast<const float*>(d_weights);
+#define LSTM_LAUNCH(WR, M1)                                                                                                          \
+    {                                                                                                                                \
+        const int rc3 = grant_lds<k_value_net_lstm_bf16<WR, M1>>(shmem);                                                             \
+        if (rc3 != CS_OK) return rc3;                                                                                                \
+        hipLaunchKernelGGL((k_value_net_lstm_bf16<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, s, m, wb, NG, A, n,    \
+                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);                    \
+    }
+    if (wreg && mlp1) LSTM_LAUNCH(true, true)
+    else if (wreg) LSTM_LAUNCH(true, false)
+    else if (mlp1) LSTM_LAUNCH(false, true)
+    else LSTM_LAUNCH(false, false)
+#undef LSTM_LAUNCH
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
+}

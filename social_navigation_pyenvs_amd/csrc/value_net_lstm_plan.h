@@ -1,5 +1,6 @@
 // value_net_lstm_plan.h -- what LSTM-RL's decision kernels (value_net_lstm.hip) and its gradient kernel (value_net_lstm_grad.hip) share: the
-// plan of a network description (the Linear layers and the gates as a layer of the blob) and the activations on v_exp_f32 / v_rcp_f32.
+// plan of a network description (the Linear layers and the gates as a layer of the blob), the activations on v_exp_f32 / v_rcp_f32 and, for the
+// decision kernels of value_net_lstm.hip and value_net_lstm_bf16.hip, the sort key of a row and the gather of a step's rows.
 // Unnamed namespace: each translation unit gets its own copy.
 #pragma once
 #include "value_net_plan.h"
@@ -62,6 +63,26 @@ inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& 
     p.ld_j = up(SELF_DIM + q.H, 8) + 4;
     p.total_floats = off;
     return CS_OK;
+}
+
+// an integer that orders like the distance: NaN above everything (numpy's argsort leaves it last, the flip first), -0 = +0
+__device__ __forceinline__ unsigned lstm_key(float x)
+{
+    if (x != x) return 0xFFFFFFFFu;
+    unsigned u = __float_as_uint(x);
+    if (x == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// rows perm[s][t] of the tile's sequences into rows of stride ld: 16 columns a row, zeros beyond the columns and the sequences
+__device__ __forceinline__ void lstm_gather(float* X, int ld, const float* __restrict__ rotated, const int* perm, long gbase, int ng, int n, int cols, int t)
+{
+    for (int i = threadIdx.x; i < TILE_M * 16; i += NT) {
+        const int s = i >> 4, c = i & 15;
+        float v = 0.0f;
+        if (s < ng && c < cols) v = rotated[((gbase + s) * n + perm[s * n + t]) * cols + c];
+        X[s * ld + c] = v;
+    }
 }
 
 __device__ __forceinline__ float lstm_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }

@@ -723,7 +723,8 @@ class BatchedSocialNavGym:
         values and choices of that decision stay readable through ``last_values_device()``.  An OM-SARL instance
         (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om, an
         LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
-        (world, action)'s humans by decreasing distance inside the kernel; an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
+        (world, action)'s humans by decreasing distance inside the kernel (cs_value_net_decide_lstm_bf16 after the policy's
+        ``set_recurrent_precision("bf16")``); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
         the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order."""
         import torch
 
@@ -817,7 +818,8 @@ class BatchedSocialNavGym:
                        if self.headed_obs else torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 2], o[..., 3]], -1)).contiguous()
             nxt, cur_, rob = self._worlds_on_side_stream(dl, nxt)
             rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
-                                                   explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream)
+                                                   explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream,
+                                                   recurrent_precision=pol.recurrent_precision)
             for t in (nxt, cur_, rob, rot, rew, explore):
                 if t is not None:
                     t.record_stream(side)

@@ -11,8 +11,12 @@ With --om the rows are OM-LSTM-RL's (lstm_rl.with_om = true: 48 map columns behi
   (v)   cs_occupancy_maps on the next humans of all worlds, on its own
   (vi)  the wide torch module on the GPU: the sort as in (iii), the maps gathered in action 0's order and concatenated by torch ops
 
+With --precision f32 bf16 only the recurrent kernel's arithmetics are timed: cs_value_net_decide_lstm and cs_value_net_decide_lstm_bf16
+(LstmRL.set_recurrent_precision) on the same tensors, ALTERNATED repetition by repetition in this one process, so that clocks and
+neighbours are the same for both; the line ends with the ratio of the medians and the share of worlds in which the two pick the same action.
+
 Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5]
-        [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--out profiles/lstm_rl_decision.txt]
+        [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--precision f32 bf16] [--out profiles/lstm_rl_decision.txt]
 With --only one variant runs alone, for a `rocprofv3 --kernel-trace --stats -- python tools/time_value_lstm.py --only lstm` run of its own.
 Times are per decision of all worlds: median, minimum and maximum over --reps repetitions, each between two device events.  The work per
 decision is counted from the shapes.  Without a GPU the script fails."""
@@ -86,6 +90,26 @@ def timed(fn, reps, warmup):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def timed_alternated(fns, reps, warmup):
+    """`timed` for several callables taking turns: {key: (median, min, max)}; repetition r runs every callable once, in order"""
+    import torch
+
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {key: [] for key in fns}
+    for _ in range(reps):
+        for key, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[key].append(a.elapsed_time(b))
+    return {key: (statistics.median(v), min(v), max(v)) for key, v in ms.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worlds", type=int, default=4096)
@@ -95,6 +119,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=("lstm", "sarl", "torch", "om", "maps", "omtorch"))
     ap.add_argument("--om", action="store_true")
+    ap.add_argument("--precision", nargs="+", choices=("f32", "bf16"), help="time the recurrent kernel in these arithmetics, alternated")
     ap.add_argument("--out")
     args = ap.parse_args()
 
@@ -117,6 +142,8 @@ def main():
             nets["om " + order] = value_net.DeviceNet(wide.model, cols, C, grid, order)
     for net in nets.values():
         net.refresh()
+    if args.precision and "bf16" in args.precision:
+        nets["lstm"].refresh_recurrent("bf16")
     stream = torch.cuda.current_stream().cuda_stream
     lines = [f"LSTM-RL decision, network {args.network}: {W} worlds x {A} actions, {args.reps} repetitions after {args.warmup} warm-up, ms per decision "
              f"of all worlds (median, min .. max); device {torch.cuda.get_device_name(0)}"]
@@ -175,6 +202,21 @@ def main():
             })
         macs, nbytes = work_per_decision(lstm.model, W, A, n, cols)
         lines.append(f"n = {n}: {macs / 1e9:.2f} G multiply-adds, {nbytes / 1e6:.0f} MB of look-ahead rows per decision")
+        if args.precision:
+            entries = {"f32": ("cs_value_net_decide_lstm", value_net.decide_lstm), "bf16": ("cs_value_net_decide_lstm_bf16", value_net.decide_lstm_bf16)}
+            run = lambda entry: (lambda: entry(nets["lstm"], W, A, n, 1, rot.data_ptr(), *tail))
+            got = timed_alternated({p: run(entries[p][1]) for p in args.precision}, args.reps, args.warmup)
+            picks = {}
+            for p in args.precision:
+                med, lo, hi = got[p]
+                lines.append(f"  {p:5s} {entries[p][0]:32s} {med:9.3f}  ({lo:.3f} .. {hi:.3f})  {2 * macs / med / 1e9:.1f} TFLOP/s")
+                run(entries[p][1])()
+                torch.cuda.synchronize()
+                picks[p] = pick.clone()
+            if len(got) == 2:
+                agree = float((picks["f32"] == picks["bf16"]).float().mean())
+                lines.append(f"  f32 / bf16 = {got['f32'][0] / got['bf16'][0]:.2f} in the medians; the two pick the same action in {100 * agree:.2f} % of the worlds")
+            continue
         results = {}
         for key, (label, fn) in variants.items():
             if args.only and key.split()[0] != args.only:
