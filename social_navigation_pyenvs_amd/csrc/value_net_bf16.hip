@@ -2,6 +2,8 @@
 // policy.set_decision_precision("bf16")).  The kernel is value_net.hip's: the same body (value_net_body.inc: groups, tiles, workgroups, phases,
 // reductions) with the same copying loader; this file states the arithmetic the body runs on -- the bf16 layer, the chain of layers and the
 // handful of functions the body asks an arithmetic for -- the pack entry of its blob and the decide entry.  The pick kernel follows.
+// The host's rounding (bf16_bits), the pack of one bf16 layer and the operand vector bf16x8 are value_net_bf16.h's, which
+// value_net_lstm_bf16.hip shares.
 //
 // The arithmetic:
 //   float32 layers   a layer whose input holds raw rotated-state columns: CADRL value_network layer 0, SARL mlp1 layer 0, all of mlp3.
@@ -26,11 +28,9 @@
 // conflict-free (the float32 file's width + 4 floats does the same for 8 rows of its 32-byte k-groups).
 #include <hip/hip_runtime.h>
 
-#include "value_net_plan.h"
+#include "value_net_bf16.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __host__ __device__ inline bool vn_mlp3(const VnPlan& p, int l) { return p.kind == CS_VN_SARL && l >= p.c0[3]; }
 // a float32 layer: its input holds raw rotated-state columns
@@ -56,25 +56,13 @@ void replan_bf16(VnPlan& p)
             L.kg_split = up(L.K1, 16) / 16;
             L.kg_total = L.kg_split + up(L.K2, 16) / 16;
         }
-        L.w_off = off;
-        off += L.ncb * L.kg_total * 64 * 4;
-        L.b_off = off;
-        off += L.ncb * 32;
+        place_layer(L, off);
         const int ld = vn_out_bf16(p, l) ? L.ncb * 16 + 4 : L.ncb * 32 + 4;
         widest = ld > widest ? ld : widest;
     }
     p.ld_pq = widest;
     p.ld_m1 = up(p.m1w > 0 ? p.m1w : 1, 32) / 2 + 4;
     p.total_floats = off;
-}
-
-inline uint16_t bf16_bits(float f)       // round to nearest even; a NaN becomes the quiet NaN 0x7fc0 (what torch's .bfloat16() gives)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
 }
 
 __device__ __forceinline__ void f2h(float* buf, int ld, int r, int c, float v) { reinterpret_cast<__bf16*>(buf)[r * 2 * ld + c] = static_cast<__bf16>(v); }
@@ -207,25 +195,9 @@ extern "C" int cs_value_net_pack_bf16(int kind, const int32_t* dims, int n_dims,
     const int rc = begin_pack(kind, dims, n_dims, cols, 0, replan_bf16, sizeof(float), params, blob, n_bytes, p, fill);
     if (rc != CS_OK || !fill) return rc;
     float* fb = static_cast<float*>(blob);
-    for (int l = 0; l < p.n_layers; ++l) {
-        const VnLayer& L = p.L[l];
-        const float* wgt = params[2 * l];       // torch.nn.Linear.weight: [N][K1 + K2]
-        const float* bias = params[2 * l + 1];
-        if (vn_f32_layer(p, l)) { pack_layer_f32(L, wgt, bias, fb); continue; }
-        uint16_t* hb = reinterpret_cast<uint16_t*>(fb + L.w_off);
-        const int K = L.K1 + L.K2;
-        for (int cb = 0; cb < L.ncb; ++cb)
-            for (int ks = 0; ks < L.kg_total; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int j = cb * 32 + (lane & 31);
-                        const int kk = ks * 16 + 8 * (lane >> 5) + e;
-                        int k = -1;
-                        if (ks < L.kg_split) { if (kk < L.K1) k = kk; }
-                        else if (kk - L.kg_split * 16 < L.K2) k = L.K1 + kk - L.kg_split * 16;
-                        if (j < L.N && k >= 0) hb[((size_t)(cb * L.kg_total + ks) * 64 + lane) * 8 + e] = bf16_bits(wgt[(size_t)j * K + k]);
-                    }
-        for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
+    for (int l = 0; l < p.n_layers; ++l) {       // params: torch.nn.Linear.weight [N][K1 + K2] and bias of every layer
+        if (vn_f32_layer(p, l)) pack_layer_f32(p.L[l], params[2 * l], params[2 * l + 1], fb);
+        else pack_layer_bf16(p.L[l], params[2 * l], params[2 * l + 1], fb);
     }
     return CS_OK;
 }

@@ -30,6 +30,10 @@
 //               network 2's gather tile and mlp1's first layer do; the register-resident build holds 15 k-groups (16 would leave one wave per
 //               SIMD: DESIGN.md 4.5), and network 1's P buffer lies over the joint rows, dead by then, to keep two workgroups a CU.  The four
 //               builds of k_value_net_lstm are the preprocessor's LSTM_OM 0 text: the instructions they had before.
+//   shared      with k_value_net_lstm_bf16 (value_net_lstm_bf16.hip), in value_net_lstm_kernel.h: the layer table, a job's start, the rank pass,
+//               the self state, h_n into J, the value store, lstm_layer (both arithmetics; here false, false) and lstm_chain, and the host's
+//               checks and (wreg, mlp1) choice of a decide entry.  This file keeps what is its own: the LDS maps, the pack of the gates, the
+//               gather with map columns, the two kernels around the body and its step loop, the entries.
 //
 // Numerics: float32.  Every gate pre-activation is one fixed fmaf chain from b_ih + b_hh (summed in float32 by the pack) over the k-groups in
 // descending order (x_t's, then h's); sigmoid(x) = rcp(1 + exp2(-x * log2 e)), tanh(x) = sign(x) * (1 - e) * rcp(1 + e) with e = exp2(-2 |x| * log2 e) on
@@ -38,13 +42,12 @@
 // inside any batch, at any position of a tile.  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include "value_net_lstm_plan.h"
+#include "value_net_lstm_kernel.h"
 
 namespace {
 
-constexpr int RB = 2, RKG = 14;    // register-resident gate weights: blocks a wavefront, k-groups a block
+constexpr int RKG = 14;            // register-resident gate weights: k-groups a block (RB blocks a wavefront)
 constexpr int RKG_OM = 15;         // ... of the kernel with map columns: the reference's [om] defaults are 7 blocks x (7 + 8) k-groups
-constexpr int GB = 8;              // blocks a wavefront at the widest H (256 / 8 / 4)
 
 struct LstmLds { int key, perm, X, XH, P, Q, J, LT, total; };
 
@@ -115,75 +118,6 @@ __device__ __forceinline__ void lstm_gather_om(float* X, int ld, const float* __
     }
 }
 
-// One float32 layer of the tile's 32 rows, dst[32][ncb * 32] = act(src[32][K] x Wt + b): value_net_plan.h's layer_fwd for one row block and
-// one source -- the same blob layout, the same k order, zeros beyond N -- with a one-deep weight prefetch.
-// The layer's fields come from the table the kernel keeps in LDS (LT_*), one register each.  Fetched from the kernel's arguments (p.L[l], as
-// layer_fwd does) beside the gates, the build reported a private segment of 20 - 36 bytes that no instruction used: a dead 16-byte spill slot
-// of the scalar allocator and its scavenging slot.  With the table it reports 0.
-enum { LT_N, LT_KG, LT_NCB, LT_RELU, LT_W, LT_B, LT_STRIDE = 8 };
-
-__device__ __forceinline__ void lstm_layer(const int* lt, const float* __restrict__ wb, const float* src, int lds_, float* dst, int ldd)
-{
-    const auto field = [&](int k) { return __builtin_amdgcn_readfirstlane(lt[k]); };
-    const struct { int N, kg_total, ncb, relu, w_off, b_off; } L{field(LT_N), field(LT_KG), field(LT_NCB), field(LT_RELU), field(LT_W), field(LT_B)};
-    const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31, KG = L.kg_total;
-    const float* a1 = src + li * lds_ + 4 * h;
-    for (int cb = threadIdx.x >> 6; cb < L.ncb; cb += 4) {
-        const float4* bw = reinterpret_cast<const float4*>(wb + L.w_off) + cb * KG * 64 + lane;
-        const float bias = wb[L.b_off + cb * 32 + li];
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = bias;
-        float4 nw = bw[0];
-        for (int kg = 0; kg < KG; ++kg) {
-            const float4 w = nw;
-            nw = bw[(kg + 1 < KG ? kg + 1 : kg) * 64];
-            const float4 a = *reinterpret_cast<const float4*>(a1 + kg * 8);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
-        }
-        float* d = dst + 4 * h * ldd + cb * 32 + li;
-        const bool pad = cb * 32 + li >= L.N;              // (the zero weights give 0 * inf = NaN there when an input is infinite)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = acc[r];
-            if (L.relu) v = v < 0.0f ? 0.0f : v;          // (a NaN stays a NaN, as torch's ReLU leaves it)
-            d[((r & 3) + 8 * (r >> 2)) * ldd] = pad ? 0.0f : v;
-        }
-    }
-}
-
-// layers [first, last) from `src`, a barrier behind each; outputs alternate P, Q, the last one goes to final_dst when given.  Returns where
-// the result is, out_ld its row stride.
-__device__ __forceinline__ const float* lstm_chain(const int* ltab, int ld_pq, const float* __restrict__ wb, float* P, float* Q, int first, int last, const float* src,
-                                                   int lds_, float* final_dst, int final_ld, int& out_ld)
-{
-    const float* cur = src;
-    int cur_ld = lds_;
-    for (int l = first; l < last; ++l) {
-        const bool fin = l == last - 1 && final_dst;
-        float* dst = fin ? final_dst : (((l - first) & 1) ? Q : P);
-        const int ldd = fin ? final_ld : ld_pq;
-        lstm_layer(ltab + l * LT_STRIDE, wb, cur, cur_ld, dst, ldd);
-        __syncthreads();
-        cur = dst;
-        cur_ld = ldd;
-    }
-    out_ld = cur_ld;
-    return cur;
-}
-
-#define LSTM_KSTEP(WV, KGI)                                                                                                  \
-    {                                                                                                                        \
-        const float4 xv = *reinterpret_cast<const float4*>(brow + (KGI) * 8);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.x, xv.x, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.y, xv.y, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.z, xv.z, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.w, xv.w, acc, 0, 0, 0);                                                \
-    }
-
 template <bool WREG, bool MLP1>
 __global__ __launch_bounds__(NT) void k_value_net_lstm(LstmPlan q, LstmLds m, const float* __restrict__ wb, int NG, int A, int n, int sorted,
                                                        const float* __restrict__ rotated, const float* __restrict__ rewards,
@@ -205,7 +139,6 @@ __global__ __launch_bounds__(NT) void k_value_net_lstm_om(LstmPlan q, LstmLds m,
 #include "value_net_lstm_body.inc"
 #undef LSTM_OM
 }
-#undef LSTM_KSTEP
 
 // the pack entries' common part
 inline int pack_lstm(const LstmPlan& q, const float* const* params, float* blob, size_t* n_floats)
@@ -253,28 +186,20 @@ extern "C" int cs_value_net_decide_lstm(const int32_t* dims, int n_dims, const f
     LstmPlan q;
     const int rc = build_lstm_plan(dims, n_dims, cols, q);
     if (rc != CS_OK) return rc;
-    const int rc2 = check_decide_args(q.v, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    const int rc2 = lstm_check_decide("cs_value_net_decide_lstm", q.v, d_weights, n_weight_floats, W, A, n, sorted_by_distance, d_rotated, d_rewards, d_actions,
+                                      d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;
-    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
-    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
     const LstmLds m = lstm_lds_map(q, n);
-    const size_t shmem = (size_t)m.total * sizeof(float);
-    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    int NG, grid;
-    job_grid(W, A, NG, grid);
     const bool wreg = q.g.ncb <= 4 * RB && q.g.kg_total <= RKG, mlp1 = q.v.c0[1] > 0;
-#define LSTM_LAUNCH(WR, M1)                                                                                                          \
-    {                                                                                                                                \
-        const int rc3 = grant_lds<k_value_net_lstm<WR, M1>>(shmem);                                                                  \
-        if (rc3 != CS_OK) return rc3;                                                                                                \
-        hipLaunchKernelGGL((k_value_net_lstm<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n,  \
-                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);                    \
-    }
-    if (wreg && mlp1) LSTM_LAUNCH(true, true)
-    else if (wreg) LSTM_LAUNCH(true, false)
-    else if (mlp1) LSTM_LAUNCH(false, true)
-    else LSTM_LAUNCH(false, false)
-#undef LSTM_LAUNCH
+    const int rc3 = lstm_launch(m.total, W, A, wreg, mlp1, [&](auto WR, auto M1, size_t shmem, int NG, int grid) {
+        constexpr auto kernel = k_value_net_lstm<decltype(WR)::value, decltype(M1)::value>;
+        const int rc4 = grant_lds<kernel>(shmem);
+        if (rc4 != CS_OK) return rc4;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n, sorted_by_distance, d_rotated, d_rewards,
+                           d_robot, robot_stride, gamma, dt, d_values);
+        return (int)CS_OK;
+    });
+    if (rc3 != CS_OK) return rc3;
     return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }
 
@@ -286,33 +211,23 @@ extern "C" int cs_value_net_decide_lstm_om(const int32_t* dims, int n_dims, cons
     LstmPlan q;
     const int rc = build_lstm_plan(dims, n_dims, cols, q, true, om_cols);
     if (rc != CS_OK) return rc;
-    const int rc2 = check_decide_args(q.v, d_weights, n_weight_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    const int rc2 = lstm_check_decide("cs_value_net_decide_lstm_om", q.v, d_weights, n_weight_floats, W, A, n, sorted_by_distance, d_rotated, d_rewards,
+                                      d_actions, d_robot, robot_stride, d_values, d_action_out, true, d_maps, map_order);
     if (rc2 != CS_OK) return rc2;
-    if (!d_maps) return fail(CS_ERR_ARG, "null argument");
-    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
-    if (map_order != CS_VN_MAPS_OWN && map_order != CS_VN_MAPS_FIRST_ACTION) return fail(CS_ERR_ARG, "map_order is CS_VN_MAPS_OWN or CS_VN_MAPS_FIRST_ACTION");
-    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm_om takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
     LstmOm om{d_maps, om_cols, map_order, up(cols + om_cols, 8), 0, 0};
     LstmLds m = lstm_lds_map(q, n, om.xw + 4, true);
     om.key0 = m.total;                          // the keys and the order of action 0, behind the narrow kernel's map
     om.perm0 = om.key0 + up(TILE_M * n, 4);
     m.total = om.perm0 + up(TILE_M * n, 4);
-    const size_t shmem = (size_t)m.total * sizeof(float);
-    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    int NG, grid;
-    job_grid(W, A, NG, grid);
     const bool wreg = q.g.ncb <= 4 * RB && q.g.kg_total <= RKG_OM, mlp1 = q.v.c0[1] > 0;
-#define LSTM_LAUNCH(WR, M1)                                                                                                             \
-    {                                                                                                                                   \
-        const int rc3 = grant_lds<k_value_net_lstm_om<WR, M1>>(shmem);                                                                  \
-        if (rc3 != CS_OK) return rc3;                                                                                                   \
-        hipLaunchKernelGGL((k_value_net_lstm_om<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n,  \
-                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values, om);                   \
-    }
-    if (wreg && mlp1) LSTM_LAUNCH(true, true)
-    else if (wreg) LSTM_LAUNCH(true, false)
-    else if (mlp1) LSTM_LAUNCH(false, true)
-    else LSTM_LAUNCH(false, false)
-#undef LSTM_LAUNCH
+    const int rc3 = lstm_launch(m.total, W, A, wreg, mlp1, [&](auto WR, auto M1, size_t shmem, int NG, int grid) {
+        constexpr auto kernel = k_value_net_lstm_om<decltype(WR)::value, decltype(M1)::value>;
+        const int rc4 = grant_lds<kernel>(shmem);
+        if (rc4 != CS_OK) return rc4;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, q, m, d_weights, NG, A, n, sorted_by_distance, d_rotated, d_rewards,
+                           d_robot, robot_stride, gamma, dt, d_values, om);
+        return (int)CS_OK;
+    });
+    if (rc3 != CS_OK) return rc3;
     return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }

@@ -4,6 +4,10 @@
 // sequence's rows is ranked in LDS, the gates are the TRANSPOSED product (A = the gate weights, rows 8 * gate + unit of a block of 8 hidden
 // units; B = the sequences' operand rows from LDS), wavefront w owns the blocks w, w + 4, ..., a lane holds i, f, g, o of four units of one
 // sequence, c stays in registers for all n steps -- and so are the sort, sorted_by_distance, the value and the pick (value_net_pick.h).
+// What the two kernels do alike is value_net_lstm_kernel.h's, stated once: the layer table, a job's start, the rank pass, the self state, h_n
+// into J, the value store, the layer (lstm_layer, here with its in_bf16 / out_bf16 flags set per layer by lstm_chain<LC_BF16_*>) and the
+// host's checks and (wreg, mlp1) choice; the bf16 pack of a Linear layer is value_net_bf16.h's.  This file keeps the plan's changes, the LDS
+// map, the pack of the gates, the slots of the gate product, the pointwise part, the step loop and the entries.
 //
 // The arithmetic:
 //   float32 layers   network 1's W_ih on the raw row x_t, network 2's mlp1 layer 0, layer 0 of mlp (it reads the raw self state): full
@@ -25,15 +29,13 @@
 // of pitch), double-buffered; network 2's gate input: [32] rows of mlp1's last width rounded up to 32.
 #include <hip/hip_runtime.h>
 
-#include "value_net_lstm_plan.h"
+#include "value_net_lstm_kernel.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int RB = 2, RKH = 4, RKX = 4;    // register-resident gate weights: blocks a wavefront; 16-byte lane slots of W_hh and of the x part a block
-constexpr int GB = 8;                      // blocks a wavefront at the widest H (256 / 8 / 4)
+constexpr int RKH = 4, RKX = 4;            // register-resident gate weights: 16-byte lane slots of W_hh and of the x part a block (RB blocks a wavefront)
 
 // the float32 plan and what this arithmetic changes: ksh k-steps of 16 of W_hh; ksx slots of the x part (network 1: float32 k-groups of 8 of
 // W_ih, network 2: k-steps of 16); the strides (floats) of the h rows and of network 2's gate input rows
@@ -52,23 +54,17 @@ inline int build_lstm_bf16_plan(const int32_t* dims, int n_dims, int cols, LstmH
     VnPlan& p = s.q.v;
     VnLayer& g = s.q.g;
     int off = 0, widest = 36;
-    const auto place = [&](VnLayer& L) {
-        L.w_off = off;
-        off += L.ncb * L.kg_total * 64 * 4;
-        L.b_off = off;
-        off += L.ncb * 32;
-    };
     for (int l = 0; l < p.n_layers; ++l) {
         if (l == p.c0[1]) {             // the gates lie between the two chains in the blob
             s.ksh = up(s.q.H, 16) / 16;
             s.ksx = p.c0[1] > 0 ? up(s.q.xin, 16) / 16 : up(cols, 8) / 8;
             g.kg_split = s.ksh;
             g.kg_total = s.ksh + s.ksx;
-            place(g);
+            place_layer(g, off);
         }
         VnLayer& L = p.L[l];
         if (!lh_f32_layer(p, l)) L.kg_split = L.kg_total = up(L.K1, 16) / 16;
-        place(L);
+        place_layer(L, off);
         const int ld = lh_out_bf16(p, l) ? L.ncb * 16 + 4 : L.ncb * 32 + 4;
         widest = ld > widest ? ld : widest;
     }
@@ -100,28 +96,8 @@ inline LstmHLds lstm_bf16_lds_map(const LstmHPlan& s, int n)
     return m;
 }
 
-inline uint16_t bf16_bits(float f)       // round to nearest even; a NaN becomes the quiet NaN 0x7fc0 (what torch's .bfloat16() gives)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// one bf16 layer's weights where the lanes of lh_layer read them (cs_value_net_pack_bf16's layout of a bf16 layer); blob zeroed before
-inline void pack_layer_bf16(const VnLayer& L, const float* wgt, const float* bias, float* fb)
-{
-    uint16_t* hb = reinterpret_cast<uint16_t*>(fb + L.w_off);
-    for (int cb = 0; cb < L.ncb; ++cb)
-        for (int ks = 0; ks < L.kg_total; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int j = cb * 32 + (lane & 31), k = ks * 16 + 8 * (lane >> 5) + e;
-                    if (j < L.N && k < L.K1) hb[((size_t)(cb * L.kg_total + ks) * 64 + lane) * 8 + e] = bf16_bits(wgt[(size_t)j * L.K1 + k]);
-                }
-    for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
-}
+// (bf16_bits and pack_layer_bf16 -- a bf16 layer's weights where the lanes of lstm_layer read them, cs_value_net_pack_bf16's layout -- are
+// value_net_bf16.h's)
 
 // the gate rows where the lanes of the transposed product read them: slot s of block b, lane l, gate row j = l & 31 = 8 * gate + u, torch's
 // row gate * H + 8 b + u.  Slots below ksh: 8 bf16 of weight_hh at k = 16 s + 8 (l >> 5) + e.  Behind them the x part: network 2, 8 bf16 of
@@ -160,83 +136,6 @@ inline void pack_gates_bf16(const LstmHPlan& s, const float* wih, const float* w
         }
 }
 
-// One layer of the tile's 32 rows, one row block, the waves over the 32-column output blocks: value_net_lstm.hip's lstm_layer (the fields
-// from the table in LDS, a one-deep weight prefetch) in this file's two arithmetics.  in_bf16: src holds bfloat16 rows (stride lds_ floats)
-// and the weights are k-steps of 16 (value_net_bf16.hip's layer_fwd_h); else the float32 layer.  out_bf16: the output is the operand of a
-// bf16 layer -- dst holds bfloat16 rows of 2 * ldd elements, each value rounded to nearest even after the bias and the ReLU.  The two are
-// arguments, uniform over the workgroup, not template arguments: one copy of the layer per call site keeps the kernel at two workgroups a CU.
-enum { LT_N, LT_KG, LT_NCB, LT_RELU, LT_W, LT_B, LT_STRIDE = 8 };
-
-__device__ __forceinline__ void lh_layer(const int* lt, const float* __restrict__ wb, const float* src, int lds_, float* dst, int ldd, bool in_bf16, bool out_bf16)
-{
-    const auto field = [&](int k) { return __builtin_amdgcn_readfirstlane(lt[k]); };
-    const struct { int N, kg_total, ncb, relu, w_off, b_off; } L{field(LT_N), field(LT_KG), field(LT_NCB), field(LT_RELU), field(LT_W), field(LT_B)};
-    const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31, KG = L.kg_total;
-    const float* a1 = src + li * lds_ + 4 * h;
-    for (int cb = threadIdx.x >> 6; cb < L.ncb; cb += 4) {
-        const float4* bw = reinterpret_cast<const float4*>(wb + L.w_off) + cb * KG * 64 + lane;
-        const float bias = wb[L.b_off + cb * 32 + li];
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = bias;
-        float4 nw = bw[0];
-        for (int kg = 0; kg < KG; ++kg) {
-            const float4 w = nw;
-            nw = bw[(kg + 1 < KG ? kg + 1 : kg) * 64];
-            const float4 a = *reinterpret_cast<const float4*>(a1 + kg * 8);
-            if (in_bf16) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, w), acc, 0, 0, 0);
-            } else {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
-            }
-        }
-        // C/D map of the 32x32 forms: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-        const bool pad = cb * 32 + li >= L.N;              // (the zero weights give 0 * inf = NaN there when an input is infinite)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = acc[r];
-            if (L.relu) v = v < 0.0f ? 0.0f : v;          // (a NaN stays a NaN, as torch's ReLU leaves it)
-            acc[r] = pad ? 0.0f : v;
-        }
-        const int ocol = cb * 32 + li;
-        if (out_bf16) {
-            __bf16* d = reinterpret_cast<__bf16*>(dst) + 4 * h * 2 * ldd + ocol;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d[((r & 3) + 8 * (r >> 2)) * 2 * ldd] = static_cast<__bf16>(acc[r]);
-        } else {
-            float* d = dst + 4 * h * ldd + ocol;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d[((r & 3) + 8 * (r >> 2)) * ldd] = acc[r];
-        }
-    }
-}
-
-// layers [first, last) from `src` (float32 rows: the first layer of either chain is a float32 layer), a barrier behind each; outputs
-// alternate P, Q, the last one goes to final_dst when given.  HEAD: the chain is mlp, whose last output stays float32; else mlp1, whose
-// every output is a bf16 operand.  Returns where the result is, out_ld its row stride.
-template <bool HEAD>
-__device__ __forceinline__ const float* lh_chain(const int* ltab, int ld_pq, const float* __restrict__ wb, float* P, float* Q, int first, int last,
-                                                 const float* src, int lds_, float* final_dst, int final_ld, int& out_ld)
-{
-    const float* cur = src;
-    int cur_ld = lds_;
-    for (int l = first; l < last; ++l) {
-        const bool fin = l == last - 1, given = fin && final_dst;
-        float* dst = given ? final_dst : (((l - first) & 1) ? Q : P);
-        const int ldd = given ? final_ld : ld_pq;
-        const int* lt = ltab + l * LT_STRIDE;
-        lh_layer(lt, wb, cur, cur_ld, dst, ldd, l != first, HEAD ? !fin : true);
-        __syncthreads();
-        cur = dst;
-        cur_ld = ldd;
-    }
-    out_ld = cur_ld;
-    return cur;
-}
-
 // one 16-byte slot of the x part (network 1: a float32 k-group of W_ih on the raw row; network 2: a bf16 k-step of W_ih on mlp1's rounded
 // output) and one of W_hh on the rounded h; `row`: the lane's operand row in LDS at the slot (its sequence, its half of the k range)
 template <bool MLP1>
@@ -246,10 +145,7 @@ __device__ __forceinline__ void lh_x_slot(f32x16& acc, const float4 w, const flo
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), *reinterpret_cast<const bf16x8*>(row), acc, 0, 0, 0);
     } else {
         const float4 xv = *reinterpret_cast<const float4*>(row);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, xv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, xv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, xv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, xv.w, acc, 0, 0, 0);
+        LSTM_MFMA4(acc, w, xv)
     }
 }
 
@@ -294,12 +190,7 @@ __global__ __launch_bounds__(NT, 2) void k_value_net_lstm_bf16(LstmHPlan s, Lstm
     int out_ld;
 
     int* ltab = reinterpret_cast<int*>(lds + m.LT);
-    if (tid == 0)
-        for (int l = 0; l < p.n_layers; ++l) {
-            int* e = ltab + l * LT_STRIDE;
-            e[LT_N] = p.L[l].N; e[LT_KG] = p.L[l].kg_total; e[LT_NCB] = p.L[l].ncb; e[LT_RELU] = p.L[l].relu; e[LT_W] = p.L[l].w_off; e[LT_B] = p.L[l].b_off;
-        }
-    // (the first barrier of the first job publishes the table)
+    LSTM_FILL_TABLE(ltab, p)
 
     float4 wh[RB][RKH], wx[RB][RKX];
     if constexpr (WREG) {
@@ -317,23 +208,10 @@ __global__ __launch_bounds__(NT, 2) void k_value_net_lstm_bf16(LstmHPlan s, Lstm
     for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
         const long gbase = (long)job * JROWS;
         const int ng = NG - gbase < JROWS ? (int)(NG - gbase) : JROWS;
-        for (int i = tid; i < ng * n; i += NT) key[i] = lstm_key(rotated[(gbase * n + i) * cols + 11]);
-        for (int i = tid; i < JROWS * p.ld_j; i += NT) J[i] = 0.0f;
+        LSTM_BEGIN_JOB(key, J, p.ld_j, rotated, gbase, ng, n, cols)
         for (int i = tid; i < 2 * TILE_M * ldh; i += NT) HB[i] = 0.0f;           // h0 = 0, and the columns between H and the last k-step's end
         __syncthreads();
-        for (int j = tid & 7; j < n && row8 < ng; j += 8) {          // eight lanes a sequence
-            int rank = j;
-            if (sorted) {
-                const unsigned kj = key[row8 * n + j];
-                rank = 0;
-#pragma unroll 1
-                for (int k = 0; k < n; ++k) {
-                    const unsigned kk = key[row8 * n + k];
-                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
-                }
-            }
-            perm[row8 * n + rank] = j;
-        }
+        LSTM_RANK(key, perm, n, ng, sorted)
         __syncthreads();
         lstm_gather(G, LDX, rotated, perm, gbase, ng, n, cols, 0);
         float c[NB][4];
@@ -342,14 +220,13 @@ __global__ __launch_bounds__(NT, 2) void k_value_net_lstm_bf16(LstmHPlan s, Lstm
 #pragma unroll
             for (int u = 0; u < 4; ++u) c[bi][u] = 0.0f;
         __syncthreads();
-        // lstm_rl.py:25 / :53: the self state is read from the first row in evaluation order
-        if (row8 < ng && (tid & 7) < SELF_DIM) J[row8 * p.ld_j + (tid & 7)] = G[row8 * LDX + (tid & 7)];
+        lstm_self_state(J, p.ld_j, G, LDX, ng, tid);
 
         for (int t = 0; t < n; ++t) {
             const float* hrow = HB + (t & 1) * TILE_M * ldh + li * ldh + 4 * hh;
             __bf16* hdst = reinterpret_cast<__bf16*>(HB + ((t + 1) & 1) * TILE_M * ldh + li * ldh);
             if (t + 1 < n) lstm_gather(G + ((t + 1) & 1) * gbuf, LDX, rotated, perm, gbase, ng, n, cols, t + 1);
-            if constexpr (MLP1) lh_chain<false>(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, LDX, XB, s.ld_xb, out_ld);
+            if constexpr (MLP1) lstm_chain<LC_BF16_MLP1>(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, LDX, XB, s.ld_xb, out_ld);
             const float* xrow = (MLP1 ? XB + li * s.ld_xb : G + (t & 1) * gbuf + li * LDX) + 4 * hh;
             if constexpr (WREG) {
                 // the x part of every block of the wavefront, then the barrier that publishes h_{t-1}, then W_hh and the pointwise part
@@ -403,15 +280,10 @@ __global__ __launch_bounds__(NT, 2) void k_value_net_lstm_bf16(LstmHPlan s, Lstm
         }
         if constexpr (WREG) __syncthreads();          // (publishes h_n)
 
-        const __bf16* hn = reinterpret_cast<const __bf16*>(HB + (n & 1) * TILE_M * ldh);
-        for (int u = tid & 7; u < H; u += 8) J[row8 * p.ld_j + SELF_DIM + u] = static_cast<float>(hn[row8 * 2 * ldh + u]);
+        lstm_hn_to_j(J, p.ld_j, reinterpret_cast<const __bf16*>(HB + (n & 1) * TILE_M * ldh), 2 * ldh, H, tid);
         __syncthreads();
-        const float* out = lh_chain<true>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
-        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
-            const long g = gbase + tid;
-            const float vpref = robot[(g / A) * rstride + 7];
-            values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
-        }
+        const float* out = lstm_chain<LC_BF16_MLP>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
+        lstm_store_values(out, out_ld, gbase, ng, A, rewards, robot, rstride, gamma, dt, values, tid);
         __syncthreads();
     }
 }
@@ -455,28 +327,20 @@ extern "C" int cs_value_net_decide_lstm_bf16(const int32_t* dims, int n_dims, co
     const LstmPlan& q = s.q;
     // (a length that is no whole number of floats is no blob of any network: it fails the size check as SIZE_MAX floats)
     const size_t n_floats = n_weight_bytes % sizeof(float) ? (size_t)-1 : n_weight_bytes / sizeof(float);
-    const int rc2 = check_decide_args(q.v, d_weights, n_floats, W, A, n, d_rotated, d_rewards, d_actions, d_robot, robot_stride, d_values, d_action_out);
+    const int rc2 = lstm_check_decide("cs_value_net_decide_lstm_bf16", q.v, d_weights, n_floats, W, A, n, sorted_by_distance, d_rotated, d_rewards, d_actions,
+                                      d_robot, robot_stride, d_values, d_action_out);
     if (rc2 != CS_OK) return rc2;
-    if (sorted_by_distance != 0 && sorted_by_distance != 1) return fail(CS_ERR_ARG, "sorted_by_distance is 0 or 1");
-    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_decide_lstm_bf16 takes at most 128 humans a world (CS_VN_LSTM_MAX_N)");
     const LstmHLds m = lstm_bf16_lds_map(s, n);
-    const size_t shmem = (size_t)m.total * sizeof(float);
-    if (shmem > 160 * 1024) return fail(CS_ERR_ARG, "the tile buffers of this network do not fit the 160 KiB of LDS");
-    int NG, grid;
-    job_grid(W, A, NG, grid);
     const bool wreg = q.g.ncb <= 4 * RB && s.ksh <= RKH && s.ksx <= RKX, mlp1 = q.v.c0[1] > 0;
     const float* wb = static_cast<const float*>(d_weights);
-#define LSTM_LAUNCH(WR, M1)                                                                                                          \
-    {                                                                                                                                \
-        const int rc3 = grant_lds<k_value_net_lstm_bf16<WR, M1>>(shmem);                                                             \
-        if (rc3 != CS_OK) return rc3;                                                                                                \
-        hipLaunchKernelGGL((k_value_net_lstm_bf16<WR, M1>), dim3(grid), dim3(NT), shmem, (hipStream_t)stream, s, m, wb, NG, A, n,    \
-                           sorted_by_distance, d_rotated, d_rewards, d_robot, robot_stride, gamma, dt, d_values);                    \
-    }
-    if (wreg && mlp1) LSTM_LAUNCH(true, true)
-    else if (wreg) LSTM_LAUNCH(true, false)
-    else if (mlp1) LSTM_LAUNCH(false, true)
-    else LSTM_LAUNCH(false, false)
-#undef LSTM_LAUNCH
+    const int rc3 = lstm_launch(m.total, W, A, wreg, mlp1, [&](auto WR, auto M1, size_t shmem, int NG, int grid) {
+        constexpr auto kernel = k_value_net_lstm_bf16<decltype(WR)::value, decltype(M1)::value>;
+        const int rc4 = grant_lds<kernel>(shmem);
+        if (rc4 != CS_OK) return rc4;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, s, m, wb, NG, A, n, sorted_by_distance, d_rotated, d_rewards, d_robot,
+                           robot_stride, gamma, dt, d_values);
+        return (int)CS_OK;
+    });
+    if (rc3 != CS_OK) return rc3;
     return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }

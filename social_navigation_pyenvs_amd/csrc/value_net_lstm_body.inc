@@ -1,7 +1,9 @@
 // value_net_lstm_body.inc -- the body of k_value_net_lstm<WREG, MLP1> and of k_value_net_lstm_om<WREG, MLP1> (value_net_lstm.hip), which
 // includes it once with LSTM_OM 0 and once with LSTM_OM 1.  LSTM_OM 1: a row carries `om.om_cols` occupancy-map columns behind the rotated
 // ones (cs_value_net_decide_lstm_om), the register-resident weights hold RKG_OM k-groups.  With LSTM_OM 0 the preprocessor leaves the text
-// k_value_net_lstm had before there were map columns: its four builds keep their device code.
+// k_value_net_lstm had before there were map columns: its four builds keep their device code.  The fixed ends of a job (LSTM_FILL_TABLE,
+// LSTM_BEGIN_JOB, LSTM_RANK, lstm_self_state, lstm_hn_to_j, lstm_store_values) and the layers (lstm_chain<LC_F32>) are value_net_lstm_kernel.h's,
+// shared with k_value_net_lstm_bf16; the step loop between them is this kernel's own.
     extern __shared__ float lds[];
     constexpr int NB = WREG ? RB : GB;
 #if LSTM_OM
@@ -31,12 +33,7 @@
     int out_ld;
 
     int* ltab = reinterpret_cast<int*>(lds + m.LT);
-    if (tid == 0)
-        for (int l = 0; l < p.n_layers; ++l) {
-            int* e = ltab + l * LT_STRIDE;
-            e[LT_N] = p.L[l].N; e[LT_KG] = p.L[l].kg_total; e[LT_NCB] = p.L[l].ncb; e[LT_RELU] = p.L[l].relu; e[LT_W] = p.L[l].w_off; e[LT_B] = p.L[l].b_off;
-        }
-    // (the first barrier of the first job publishes the table)
+    LSTM_FILL_TABLE(ltab, p)
 
     float4 wreg[RB][RK];
     if constexpr (WREG) {
@@ -52,8 +49,7 @@
     for (int job = blockIdx.x; job * JROWS < NG; job += gridDim.x) {
         const long gbase = (long)job * JROWS;
         const int ng = NG - gbase < JROWS ? (int)(NG - gbase) : JROWS;
-        for (int i = tid; i < ng * n; i += NT) key[i] = lstm_key(rotated[(gbase * n + i) * cols + 11]);
-        for (int i = tid; i < JROWS * p.ld_j; i += NT) J[i] = 0.0f;
+        LSTM_BEGIN_JOB(key, J, p.ld_j, rotated, gbase, ng, n, cols)
         for (int i = tid; i < TILE_M * ldxh; i += NT) XH[i] = 0.0f;                                  // h0 = 0
 #if LSTM_OM
         // which map a step takes: its row's own (mperm = perm), or the one at that place in the order of the world's action 0, which is worked
@@ -69,31 +65,9 @@
 #endif
         __syncthreads();
 #if LSTM_OM
-        if (first_order)
-            for (int j = tid & 7; j < n && row8 < ng; j += 8) {
-                const unsigned kj = key0[row8 * n + j];
-                int rank = 0;
-#pragma unroll 1
-                for (int k = 0; k < n; ++k) {
-                    const unsigned kk = key0[row8 * n + k];
-                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
-                }
-                perm0[row8 * n + rank] = j;
-            }
+        if (first_order) LSTM_RANK(key0, perm0, n, ng, true)
 #endif
-        for (int j = tid & 7; j < n && row8 < ng; j += 8) {          // eight lanes a sequence
-            int rank = j;
-            if (sorted) {
-                const unsigned kj = key[row8 * n + j];
-                rank = 0;
-#pragma unroll 1
-                for (int k = 0; k < n; ++k) {
-                    const unsigned kk = key[row8 * n + k];
-                    rank += (kk > kj || (kk == kj && k > j)) ? 1 : 0;
-                }
-            }
-            perm[row8 * n + rank] = j;
-        }
+        LSTM_RANK(key, perm, n, ng, sorted)
         __syncthreads();
 #if LSTM_OM
 #define LSTM_GATHER(X, T) lstm_gather_om(X, ldg, rotated, om, perm, mperm, gbase, ng, A, n, cols, T)
@@ -107,14 +81,13 @@
 #pragma unroll
             for (int u = 0; u < 4; ++u) c[bi][u] = 0.0f;
         __syncthreads();
-        // lstm_rl.py:25 / :53: the self state is read from the first row in evaluation order
-        if (row8 < ng && (tid & 7) < SELF_DIM) J[row8 * p.ld_j + (tid & 7)] = G[row8 * ldg + (tid & 7)];
+        lstm_self_state(J, p.ld_j, G, ldg, ng, tid);
 
         for (int t = 0; t < n; ++t) {
             float* cur = XH + (t & 1) * TILE_M * ldxh;
             float* nxt = XH + ((t + 1) & 1) * TILE_M * ldxh;
             if (t + 1 < n) LSTM_GATHER(G + ((t + 1) & 1) * (with_mlp1 ? gbuf : TILE_M * ldxh), t + 1);
-            if constexpr (with_mlp1) lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, ldx, cur + hpad, ldxh, out_ld);
+            if constexpr (with_mlp1) lstm_chain<LC_F32>(ltab, p.ld_pq, wb, P, Q, p.c0[0], p.c0[1], G + (t & 1) * gbuf, ldx, cur + hpad, ldxh, out_ld);
             const float* brow = cur + li * ldxh + 4 * hh;
 #pragma unroll
             for (int bi = 0; bi < NB; ++bi) {
@@ -170,14 +143,9 @@
         }
 #undef LSTM_GATHER
 
-        const float* hn = XH + (n & 1) * TILE_M * ldxh;
-        for (int u = tid & 7; u < H; u += 8) J[row8 * p.ld_j + SELF_DIM + u] = hn[row8 * ldxh + u];
+        lstm_hn_to_j(J, p.ld_j, XH + (n & 1) * TILE_M * ldxh, ldxh, H, tid);
         __syncthreads();
-        const float* out = lstm_chain(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
-        if (tid < ng) {                     // cadrl.py:85-90 compute_action_value
-            const long g = gbase + tid;
-            const float vpref = robot[(g / A) * rstride + 7];
-            values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
-        }
+        const float* out = lstm_chain<LC_F32>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
+        lstm_store_values(out, out_ld, gbase, ng, A, rewards, robot, rstride, gamma, dt, values, tid);
         __syncthreads();
     }

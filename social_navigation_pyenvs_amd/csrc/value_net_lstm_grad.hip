@@ -85,14 +85,7 @@ inline LstmGradLds lstm_grad_lds_map(const LstmPlan& q)
     return m;
 }
 
-#define LSTM_KSTEP(WV, KGI)                                                                                                  \
-    {                                                                                                                        \
-        const float4 xv = *reinterpret_cast<const float4*>(brow + (KGI) * 8);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.x, xv.x, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.y, xv.y, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.z, xv.z, acc, 0, 0, 0);                                                \
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(WV.w, xv.w, acc, 0, 0, 0);                                                \
-    }
+// (LSTM_KSTEP, a k-group of the gates in the forward step, is value_net_lstm_plan.h's: the decision kernels' step)
 
 // gpart: the floats of a region before its tape (P + 1, rounded up to 4).  MLP1: network 2's mlp1 in the step loops.
 template <bool MLP1>
@@ -294,7 +287,6 @@ __global__ __launch_bounds__(NT) void k_vn_lstm_grad(LstmPlan q, LstmGradLds m, 
     for (int c = tid; c < 4 * H; c += NT) g[og.bhh + c] = g[og.bih + c];       // (the thread that summed the column: bwd_db)
     if (tid == 0) g[o.total] = loss;
 }
-#undef LSTM_KSTEP
 
 // blob float i from the flat parameters: pack_layer_f32's and pack_gates' maps, read backwards
 __global__ void k_vn_pack_lstm(LstmPlan q, GradOffsets o, LstmGradOff og, const float* __restrict__ params, float* __restrict__ blob)

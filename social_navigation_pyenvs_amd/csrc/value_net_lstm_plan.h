@@ -1,6 +1,7 @@
 // value_net_lstm_plan.h -- what LSTM-RL's decision kernels (value_net_lstm.hip) and its gradient kernel (value_net_lstm_grad.hip) share: the
-// plan of a network description (the Linear layers and the gates as a layer of the blob), the activations on v_exp_f32 / v_rcp_f32 and, for the
-// decision kernels of value_net_lstm.hip and value_net_lstm_bf16.hip, the sort key of a row and the gather of a step's rows.
+// plan of a network description (the Linear layers and the gates as a layer of the blob), the activations on v_exp_f32 / v_rcp_f32, the
+// quad of float32 MFMAs and the gates' k-step on it (LSTM_MFMA4, LSTM_KSTEP) and, for the decision kernels of value_net_lstm.hip and
+// value_net_lstm_bf16.hip, the sort key of a row and the gather of a step's rows (what else those share is value_net_lstm_kernel.h).
 // Unnamed namespace: each translation unit gets its own copy.
 #pragma once
 #include "value_net_plan.h"
@@ -42,10 +43,7 @@ inline int build_lstm_plan(const int32_t* dims, int n_dims, int cols, LstmPlan& 
             g.kg_split = q.hpad / 8;
             g.kg_total = g.kg_split + up(k1, 8) / 8;
             g.ncb = q.hpad / 8;
-            g.w_off = off;
-            off += g.ncb * g.kg_total * 64 * 4;
-            g.b_off = off;
-            off += g.ncb * 32;
+            place_layer(g, off);
             k1 = SELF_DIM + q.H;
         }
         for (int i = 0; i < nl; ++i) {
@@ -93,5 +91,20 @@ __device__ __forceinline__ float lstm_tanh(float x)
     const float t = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
     return x != x ? x : copysignf(t, x);
 }
+
+// four v_mfma_f32_32x32x2_f32 on a float4 pair (two float4 variables): the lane's four k of one k-group of 8, in order.  A macro: as an
+// inline function it moved the schedule of every kernel that uses it, the gradient kernel at 256 VGPRs among them
+#define LSTM_MFMA4(ACC, A, B)                                                                                                \
+    ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A.x, B.x, ACC, 0, 0, 0);                                                      \
+    ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A.y, B.y, ACC, 0, 0, 0);                                                      \
+    ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A.z, B.z, ACC, 0, 0, 0);                                                      \
+    ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A.w, B.w, ACC, 0, 0, 0);
+
+// k-group KGI of the gates' transposed product in a step loop: the lane's weights WV against its joint row `brow`, into `acc`
+#define LSTM_KSTEP(WV, KGI)                                                                                                  \
+    {                                                                                                                        \
+        const float4 xv = *reinterpret_cast<const float4*>(brow + (KGI) * 8);                                                \
+        LSTM_MFMA4(acc, WV, xv)                                                                                              \
+    }
 
 } // namespace

@@ -1,5 +1,5 @@
 // value_net_plan.h -- what the three kernels of the value-network decision share beside their body (value_net_body.inc) and their
-// arithmetic (value_net_f32.h: float32, for value_net.hip and value_net_worlds.hip; value_net_bf16.hip: the opt-in bf16 layers).  Host: the
+// arithmetic (value_net_f32.h: float32, for value_net.hip and value_net_worlds.hip; value_net_bf16.hip: the opt-in bf16 layers, whose host pieces are value_net_bf16.h).  Host: the
 // layer table of a network description, the argument checks, the LDS map, what the decide entries do before their launch and the pack
 // entries before they fill.  Device: the LDS buffers, the chain tags, the tile loader that copies rows and the float32 layer of a tile.
 // Everything sits in an unnamed namespace: each translation unit gets its own copy, the kernels keep their names.  The per-world pick and
@@ -48,6 +48,16 @@ struct VnPlan {
 
 inline int up(int x, int m) { return (x + m - 1) / m * m; }
 
+// a layer's place in the blob, from its ncb and kg_total: the weights [ncb][kg_total][64 lanes][4 floats] at float `off` (a lane's 8 bf16 of
+// a k-step of 16 are as wide), then [ncb * 32] biases; `off` moves behind them
+inline void place_layer(VnLayer& l, int& off)
+{
+    l.w_off = off;
+    off += l.ncb * l.kg_total * 64 * 4;
+    l.b_off = off;
+    off += l.ncb * 32;
+}
+
 // one Linear layer of `wdt` outputs behind the table's last: k1 (+ k2) inputs, its weights and biases at float `off` of the blob, which
 // moves behind them; CS_OK or the fail() status
 inline int add_layer(VnPlan& p, int k1, int k2, int wdt, int relu, int& off)
@@ -59,10 +69,7 @@ inline int add_layer(VnPlan& p, int k1, int k2, int wdt, int relu, int& off)
     l.kg_total = l.kg_split + up(k2, 8) / 8;
     l.ncb = up(wdt, 32) / 32;
     l.relu = relu;
-    l.w_off = off;
-    off += l.ncb * l.kg_total * 64 * 4;
-    l.b_off = off;
-    off += l.ncb * 32;
+    place_layer(l, off);
     return CS_OK;
 }
 
