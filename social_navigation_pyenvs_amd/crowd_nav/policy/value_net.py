@@ -36,26 +36,20 @@ Which entries a network uses, with which arguments, and which modes it may run i
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes;
 ``state_values_for_worlds`` is that for every family.
 
-The optimisation step of the feed-forward family has kernels too (csrc/value_net_grad.hip; ``has_gradient_kernel``):
-``param_offsets`` is the flat parameter layout, ``pack_on_device`` (cs_value_net_pack_device) writes the float32 blob from the flat
-parameters without leaving the device, ``loss_and_grad`` (cs_value_net_loss_grad) is the forward, the mean-squared-error loss and the whole
-gradient of a minibatch of stored rows; ``DeviceNet.adopt_flat`` is a trainer's word that the module's parameters are views of such a flat
-tensor (crowd_nav/utils/trainer.py ``Trainer.set_gradient("device")``).  The other families are refused with GRADIENT_REFUSAL.
-
-The recurrent family without map columns has the same three under names of its own (csrc/value_net_lstm_grad.hip: backpropagation through
-time; ``has_recurrent_gradient_kernel``): ``grad_sizes_lstm``, ``pack_lstm_on_device`` (cs_value_net_pack_lstm_device) and
-``loss_and_grad_lstm`` (cs_value_net_loss_grad_lstm), ``param_offsets`` and ``adopt_flat`` serve both; the trainer's mode is "device_lstm".
-
-``train_step`` / ``train_step_lstm`` (cs_value_net_train_step[_lstm]) are the whole optimisation step of either family: the loss and the
-gradient as above, and in the launch that sums the gradient torch's SGD step with momentum and the float32 blob rewritten from the new
-parameters, with the loss added to a device float64 sum -- nothing is read back (``Trainer.set_update("device")``).
-``DeviceNet.updated_on_device`` is their word that parameters and float32 blob changed together under the version counters.
-
-The two families with map columns (OM-SARL, OM-LSTM-RL; ``has_mapped_gradient_kernel``) run the same kernels on stored rows of
-cols + om_cols columns -- the rotated columns, then the human's map, as ``transform`` stores a state -- through the `_om` entries of the
-library: ``grad_sizes_om``, ``pack_om_on_device``, ``loss_and_grad_om``, ``train_step_om`` and ``blob_index_om`` each dispatch on the net's
-family to the feed-forward or the recurrent entry; ``DeviceNet.adopt_flat(flat, mapped=True)`` is their trainer's word
-(``Trainer.set_gradient("device_om")`` / ``("device_lstm_om")``).  The names without `_om` go on refusing a mapped net."""
+The optimisation step has kernels too, for all four families (csrc/value_net_grad.hip: CADRL, SARL and OM-SARL; csrc/value_net_lstm_grad.hip:
+LSTM-RL and OM-LSTM-RL by backpropagation through time).  ``param_offsets`` is the flat parameter layout.  Each seam exists
+once and takes its entry from the net's row of ``Family`` (``Family.train_entry``: cs_value_net_{grad_sizes|loss_grad|train_step|blob_index}
+[_lstm][_om], cs_value_net_pack[_lstm][_om]_device): the sizes of the flat parameters and the scratch; the float32 blob written from the flat
+parameters without leaving the device; the forward, the mean-squared-error loss and the whole gradient of a minibatch of stored rows
+[B, n, cols (+ om_cols)] -- a human's rotated columns, then its map, as ``transform`` stores them --; that and, in the launch that sums the
+gradient, torch's SGD step with momentum and the blob rewritten from the new parameters, the loss added to a device float64 sum, nothing
+read back (``Trainer.set_update("device")``; ``DeviceNet.updated_on_device`` is its word that parameters and blob changed together under the
+version counters); and, on the host, the blob float of every parameter.  The public names are those seams for one family each, refusing
+every other net with their own sentence: ``grad_sizes``, ``pack_on_device``, ``loss_and_grad``, ``train_step`` (the feed-forward family,
+``has_gradient_kernel``, GRADIENT_REFUSAL), the same with `_lstm` (the recurrent one without map columns, ``has_recurrent_gradient_kernel``,
+RECURRENT_GRADIENT_REFUSAL) and with `_om` and ``blob_index_om`` (both families with map columns, ``has_mapped_gradient_kernel``,
+MAPPED_GRADIENT_REFUSAL).  ``DeviceNet.adopt_flat`` is a trainer's word that the module's parameters are views of such a flat tensor
+(crowd_nav/utils/trainer.py ``Trainer.set_gradient``; ``mapped=True`` from its map modes)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -79,6 +73,17 @@ def check_precision(precision):
     return precision
 
 
+GRADIENT_REFUSAL = ("{0}: the fused loss-and-gradient kernel (cs_value_net_loss_grad) covers the feed-forward networks, CADRL's and SARL's; "
+                    'an LSTM without map columns has its own (cs_value_net_loss_grad_lstm: the *_lstm helpers, Trainer.set_gradient("device_lstm")); '
+                    'a network with occupancy-map columns has the *_om helpers (Trainer.set_gradient("device_om"), ("device_lstm_om"))')
+RECURRENT_GRADIENT_REFUSAL = ("{0}: the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm) covers LSTM-RL's two networks on rows of "
+                              '13 or 15 columns; CADRL and SARL have cs_value_net_loss_grad (Trainer.set_gradient("device")), a network with '
+                              'occupancy-map columns (OM-SARL, OM-LSTM-RL) has the *_om helpers (Trainer.set_gradient("device_om"), '
+                              '("device_lstm_om"))')
+MAPPED_GRADIENT_REFUSAL = ("{0}: the *_om helpers cover the networks with occupancy-map columns, OM-SARL's and OM-LSTM-RL's; a network "
+                           "without map columns has {1}")
+
+
 class Family(NamedTuple):
     """What one family of value networks states about itself; everything else in this module, the policies and the Gym ask a row of this
     table."""
@@ -92,9 +97,17 @@ class Family(NamedTuple):
     refusal: str            # the sentence every other pair is refused with ({0!r}: the input, {1!r}: the precision)
     min_humans: int         # humans a world needs
     state_launch: bool      # V(s) is one cs_value_net_state launch; else rows, [maps,] the decide entry with A = 1
+    train_infix: str        # the training entries' infix: "" or "_lstm" (`_om`, and om_cols behind cols, follow from takes_maps)
+    flat_rows: bool         # the training seams take rows [B, cols] as n = 1 (CADRL's stored states)
+    train_refusal: str      # the sentence the family's training seams refuse every other net with ({0}: the caller, {1}: the helper to use)
 
     def lead(self, kind):
         return (kind,) if self.takes_kind else ()
+
+    def train_entry(self, stem):
+        """The name of the family's training entry `stem`: grad_sizes, loss_grad, train_step, blob_index or pack_device."""
+        tail = "_om" if self.takes_maps else ""
+        return f"cs_value_net_pack{self.train_infix}{tail}_device" if stem == "pack_device" else f"cs_value_net_{stem}{self.train_infix}{tail}"
 
 
 FEED_FORWARD = Family(
@@ -103,28 +116,28 @@ FEED_FORWARD = Family(
     modes=(("tensor", "f32"), ("tensor", "bf16"), ("fused", "f32")),
     refusal='decision input "fused" with decision precision "bf16": the bf16 kernel has its own tile loader and reads the look-ahead tensor; '
             'choose "tensor" or "f32"',
-    min_humans=1, state_launch=True)
+    min_humans=1, state_launch=True, train_infix="", flat_rows=True, train_refusal=GRADIENT_REFUSAL)
 MAPPED = Family(
     pack=frozen({"f32": ("cs_value_net_pack_om", np.float32)}), takes_kind=True,
     decide=frozen({"f32": "cs_value_net_decide_om"}), decide_int="om_cols", takes_maps=True,
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a network with occupancy-map columns: no kernel pairs the map columns '
             'with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"',
-    min_humans=2, state_launch=False)
+    min_humans=2, state_launch=False, train_infix="", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL)
 RECURRENT = Family(
     pack=frozen({"f32": ("cs_value_net_pack_lstm", np.float32)}), takes_kind=False,
     decide=frozen({"f32": "cs_value_net_decide_lstm"}), decide_int="sorted_by_distance", takes_maps=False,
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a recurrent network: LSTM-RL has the one kernel, float32 on the '
             'look-ahead tensor; it decides with "tensor" and "f32"',
-    min_humans=1, state_launch=False)
+    min_humans=1, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=RECURRENT_GRADIENT_REFUSAL)
 RECURRENT_MAPPED = Family(
     pack=frozen({"f32": ("cs_value_net_pack_lstm_om", np.float32)}), takes_kind=False,
     decide=frozen({"f32": "cs_value_net_decide_lstm_om"}), decide_int="om_cols sorted_by_distance map_order", takes_maps=True,
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a recurrent network with occupancy-map columns: OM-LSTM-RL has the one '
             'kernel, float32 on the look-ahead tensor and the maps; it decides with "tensor" and "f32"',
-    min_humans=2, state_launch=False)
+    min_humans=2, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL)
 
 
 def family_of(kind, om_cols=0):
@@ -132,17 +145,6 @@ def family_of(kind, om_cols=0):
     if kind == CS_VN_LSTM:
         return RECURRENT_MAPPED if om_cols else RECURRENT
     return MAPPED if om_cols else FEED_FORWARD
-
-
-GRADIENT_REFUSAL = ("{0}: the fused loss-and-gradient kernel (cs_value_net_loss_grad) covers the feed-forward networks, CADRL's and SARL's; "
-                    'an LSTM without map columns has its own (cs_value_net_loss_grad_lstm: the *_lstm helpers, Trainer.set_gradient("device_lstm")); '
-                    'a network with occupancy-map columns has the *_om helpers (Trainer.set_gradient("device_om"), ("device_lstm_om"))')
-RECURRENT_GRADIENT_REFUSAL = ("{0}: the recurrent loss-and-gradient kernel (cs_value_net_loss_grad_lstm) covers LSTM-RL's two networks on rows of "
-                              '13 or 15 columns; CADRL and SARL have cs_value_net_loss_grad (Trainer.set_gradient("device")), a network with '
-                              'occupancy-map columns (OM-SARL, OM-LSTM-RL) has the *_om helpers (Trainer.set_gradient("device_om"), '
-                              '("device_lstm_om"))')
-MAPPED_GRADIENT_REFUSAL = ("{0}: the *_om helpers cover the networks with occupancy-map columns, OM-SARL's and OM-LSTM-RL's; a network "
-                           "without map columns has {1}")
 
 
 def has_gradient_kernel(family):
@@ -300,10 +302,7 @@ class DeviceNet:
         key = self._versions()
         if self.flat is not None and precision == "f32":        # the parameters are views of `flat` (adopt_flat): packed where they lie
             if key != self._keys[precision]:
-                if has_mapped_gradient_kernel(self.family):
-                    pack_om_on_device(self, self.flat)
-                else:
-                    (pack_lstm_on_device if has_recurrent_gradient_kernel(self.family) else pack_on_device)(self, self.flat)
+                _pack_on_device(self, self.flat)
                 self._keys[precision] = key
             return self.blobs[precision]
         if key != self._keys[check_precision(precision)]:
@@ -335,9 +334,9 @@ class DeviceNet:
         columns, which packs through ``pack_om_on_device``; without it such a net is refused as before."""
         if flat is not None:
             if mapped:
-                _om_family(self, "adopt_flat(mapped=True)", "adopt_flat(flat)")
-            elif not has_gradient_kernel(self.family) and not has_recurrent_gradient_kernel(self.family):
-                raise ValueError(GRADIENT_REFUSAL.format("adopt_flat"))
+                _served(self, "adopt_flat(mapped=True)", MAPPED, RECURRENT_MAPPED, narrow="adopt_flat(flat)")
+            else:
+                _served(self, "adopt_flat", FEED_FORWARD, RECURRENT)
             total = param_offsets(self)[-1]
             if not flat.is_cuda or flat.dtype != _torch().float32 or flat.dim() != 1 or flat.numel() != total or not flat.is_contiguous():
                 raise ValueError(f"adopt_flat: the flat parameters are one contiguous CUDA float32 tensor of {total} elements")
@@ -384,63 +383,71 @@ def param_offsets(net):
     return tuple(offsets)
 
 
-def _grad_lead(net, caller):
-    if not has_gradient_kernel(net.family):
-        raise ValueError(GRADIENT_REFUSAL.format(caller))
-    return (net.kind, net.dims.ctypes.data, len(net.dims))
-
-
 def _stream(stream):
     return _torch().cuda.current_stream().cuda_stream if stream is None else stream
 
 
-def pack_on_device(net, flat, stream=None):
-    """cs_value_net_pack_device: `net`'s float32 blob from the flat parameters `flat` (``param_offsets``' layout, a CUDA tensor), one
-    launch on `stream` (None: torch's current one); byte for byte ``pack``'s blob.  The blob is allocated once and rewritten in place."""
+# ---------------------------------------------------------------------------------------------------------------- the training seams, once
+def _served(net, caller, *families, narrow=None):
+    """`net`, when its family is one of `families`; ValueError in `caller`'s name with their refusal sentence otherwise (`narrow`: the
+    helper that sentence names for a net without map columns)."""
+    if not any(net.family is family for family in families):
+        raise ValueError(families[0].train_refusal.format(caller, narrow))
+    return net
+
+
+def _entry(net, stem):
     from ... import _lib
 
-    lead = _grad_lead(net, "pack_on_device")
-    blob = net.blobs["f32"]
-    if blob is None:
-        nf = C.c_size_t(0)
-        _lib.check(_lib.load().cs_value_net_pack(*lead, net.cols, None, None, C.byref(nf)))
-        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
-    _lib.check(_lib.load().cs_value_net_pack_device(*lead, net.cols, flat.data_ptr(), flat.numel(), blob.data_ptr(), blob.numel(), _stream(stream)))
-    return blob
+    return getattr(_lib.load(), net.family.train_entry(stem))
 
 
-def grad_sizes(net, B, n):
-    """cs_value_net_grad_sizes: (the length of the flat parameters, the scratch floats a minibatch of B samples of n humans needs)."""
+def _described(net):
+    """What a training entry without a blob opens with: [kind,] dims, its length, cols[, om_cols]"""
+    return net.family.lead(net.kind) + (net.dims.ctypes.data, len(net.dims)) + _width(net)
+
+
+def _width(net):
+    return (net.cols, net.om_cols) if net.family.takes_maps else (net.cols,)
+
+
+def _grad_sizes(net, B, n):
     from ... import _lib
 
     n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(_lib.load().cs_value_net_grad_sizes(*_grad_lead(net, "grad_sizes"), net.cols, B, n, C.byref(n_params), C.byref(n_scratch)))
+    _lib.check(_entry(net, "grad_sizes")(*_described(net), B, n, C.byref(n_params), C.byref(n_scratch)))
     return n_params.value, n_scratch.value
 
 
-def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
-    """cs_value_net_loss_grad: the mean-squared-error loss of `net` on the minibatch rows [B, n, cols] (CADRL: n = 1, or [B, cols])
-    against targets [B] or [B, 1], and its gradient into `grad` (the layout of `flat`; written, not accumulated); values [B] or None
-    receives the network's outputs.  CUDA float32 tensors; `net`'s float32 blob must hold `flat`'s numbers (``pack_on_device``).
-    Returns the loss, a CUDA tensor of one element.  The scratch is kept on `net` and grown when a larger minibatch comes."""
+def _pack_on_device(net, flat, stream=None):
+    """The float32 blob is allocated once and rewritten in place."""
     from ... import _lib
 
-    _grad_lead(net, "loss_and_grad")
-    head = net.head("loss_and_grad")
-    if rows.dim() == 2:
-        rows = rows[:, None, :]
-    B, n, cols, scratch, loss = _minibatch("loss_and_grad", net, flat, rows, targets, grad, values, grad_sizes)
-    _lib.check(_lib.load().cs_value_net_loss_grad(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
-                                                  grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
-                                                  scratch.data_ptr(), scratch.numel(), _stream(stream)))
-    return loss
+    blob = net.blobs["f32"]
+    if blob is None:
+        nf = C.c_size_t(0)
+        _lib.check(getattr(_lib.load(), net.family.pack["f32"][0])(*_described(net), None, None, C.byref(nf)))
+        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
+    _lib.check(_entry(net, "pack_device")(*_described(net), flat.data_ptr(), flat.numel(), blob.data_ptr(), blob.numel(), _stream(stream)))
+    return blob
 
 
-def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=None, loss_sum=None, width=None):
-    """The tensor checks the loss-and-gradient and the train-step seams make alike, in `caller`'s name, and the scratch kept on `net`
-    (`sizes`: grad_sizes or grad_sizes_lstm), grown when a larger minibatch comes: (B, n, cols, scratch, a new tensor for the loss).
-    `width`: the columns of a row when they are not `net.cols` (the map modes: cols + om_cols)."""
+def _blob_index(net):
+    from ... import _lib
+
+    index = np.full(param_offsets(net)[-1], -1, np.int32)
+    _lib.check(_entry(net, "blob_index")(*_described(net), index.ctypes.data, index.size))
+    return index
+
+
+def _minibatch(caller, net, flat, rows, targets, grad, values, stream, momentum=None, loss_sum=None):
+    """The tensor checks the loss-and-gradient and the train-step seams make alike, in `caller`'s name, and the scratch kept on `net`,
+    grown when a larger minibatch comes: (a new tensor for the loss, the entry's arguments from B to the loss, its last four)."""
     torch = _torch()
+    if rows.dim() == 2 and net.family.flat_rows:
+        rows = rows[:, None, :]
+    if rows.dim() != 3:
+        raise ValueError(f"{caller}: rows are [B, n, {'cols + om_cols' if net.family.takes_maps else 'cols'}], not {tuple(rows.shape)}")
     B, n, cols = rows.shape
     tensors = [("flat", flat, flat.numel()), ("rows", rows, B * n * cols), ("targets", targets, B), ("grad", grad, flat.numel()), ("values", values, B)]
     if momentum is not None:
@@ -450,17 +457,27 @@ def _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum=N
             raise ValueError(f"{caller}: {name} is a contiguous CUDA float32 tensor of {numel} elements")
     if loss_sum is not None and (not loss_sum.is_cuda or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1):
         raise ValueError(f"{caller}: loss_sum is a CUDA float64 tensor of one element")
-    if cols != (net.cols if width is None else width):
-        raise ValueError(f"{caller}: rows of {cols} columns for a network of {net.cols if width is None else width}")
-    _, need = sizes(net, B, n)
+    if cols != net.cols + net.om_cols:
+        raise ValueError(f"{caller}: rows of {cols} columns for a network of {net.cols + net.om_cols}")
+    _, need = _grad_sizes(net, B, n)
     scratch = getattr(net, "_grad_scratch", None)
     if scratch is None or scratch.numel() < need or scratch.device != flat.device:
         scratch = net._grad_scratch = torch.empty(need, dtype=torch.float32, device=flat.device)
-    return B, n, cols, scratch, torch.empty(1, dtype=torch.float32, device=flat.device)
+    loss = torch.empty(1, dtype=torch.float32, device=flat.device)
+    return (loss, (B, n, *_width(net), rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr()),
+            (None if values is None else values.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(stream)))
 
 
-def _train_step(caller, entry, sizes, net, flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream):
-    """What ``train_step`` and ``train_step_lstm`` do alike behind their family's checks."""
+def _loss_and_grad(caller, net, flat, rows, targets, grad, values, stream):
+    from ... import _lib
+
+    head = net.head(caller)
+    loss, batch, tail = _minibatch(caller, net, flat, rows, targets, grad, values, stream)
+    _lib.check(_entry(net, "loss_grad")(*head, flat.data_ptr(), flat.numel(), *batch, *tail))
+    return loss
+
+
+def _train_step(caller, net, flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream):
     from ... import _lib
 
     if momentum is None:
@@ -468,13 +485,31 @@ def _train_step(caller, entry, sizes, net, flat, momentum, rows, targets, grad, 
     head = net.head(caller)
     if net.flat is not flat:
         raise ValueError(f"{caller}: `flat` is not the tensor the network's parameters are views of (DeviceNet.adopt_flat)")
-    B, n, cols, scratch, loss = _minibatch(caller, net, flat, rows, targets, grad, values, sizes, momentum, loss_sum)
-    _lib.check(getattr(_lib.load(), entry)(*head, flat.data_ptr(), flat.numel(), momentum.data_ptr(), momentum.numel(), float(lr), float(mu), B, n,
-                                           cols, rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(),
-                                           None if loss_sum is None else loss_sum.data_ptr(), None if values is None else values.data_ptr(),
-                                           scratch.data_ptr(), scratch.numel(), _stream(stream)))
+    loss, batch, tail = _minibatch(caller, net, flat, rows, targets, grad, values, stream, momentum, loss_sum)
+    _lib.check(_entry(net, "train_step")(*head, flat.data_ptr(), flat.numel(), momentum.data_ptr(), momentum.numel(), float(lr), float(mu), *batch,
+                                         None if loss_sum is None else loss_sum.data_ptr(), *tail))
     net.updated_on_device()
     return loss
+
+
+# ---------------------------------------------------------------------------------------------------------------- their public names
+def pack_on_device(net, flat, stream=None):
+    """cs_value_net_pack_device: `net`'s float32 blob from the flat parameters `flat` (``param_offsets``' layout, a CUDA tensor), one
+    launch on `stream` (None: torch's current one); byte for byte ``pack``'s blob.  The blob is allocated once and rewritten in place."""
+    return _pack_on_device(_served(net, "pack_on_device", FEED_FORWARD), flat, stream)
+
+
+def grad_sizes(net, B, n):
+    """cs_value_net_grad_sizes: (the length of the flat parameters, the scratch floats a minibatch of B samples of n humans needs)."""
+    return _grad_sizes(_served(net, "grad_sizes", FEED_FORWARD), B, n)
+
+
+def loss_and_grad(net, flat, rows, targets, grad, values=None, stream=None):
+    """cs_value_net_loss_grad: the mean-squared-error loss of `net` on the minibatch rows [B, n, cols] (CADRL: n = 1, or [B, cols])
+    against targets [B] or [B, 1], and its gradient into `grad` (the layout of `flat`; written, not accumulated); values [B] or None
+    receives the network's outputs.  CUDA float32 tensors; `net`'s float32 blob must hold `flat`'s numbers (``pack_on_device``).
+    Returns the loss, a CUDA tensor of one element.  The scratch is kept on `net` and grown when a larger minibatch comes."""
+    return _loss_and_grad("loss_and_grad", _served(net, "loss_and_grad", FEED_FORWARD), flat, rows, targets, grad, values, stream)
 
 
 def train_step(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
@@ -484,156 +519,68 @@ def train_step(net, flat, momentum, rows, targets, grad, lr, mu, values=None, lo
     rewritten from the new parameters, byte for byte ``pack``'s.  `flat` is the tensor `net` adopted (``adopt_flat``) and its float32 blob
     holds `flat`'s numbers on entry, as for ``loss_and_grad``.  loss_sum (a CUDA float64 tensor of one element, or None) has the loss added to
     it on the device.  Nothing is read back.  Ends with ``net.updated_on_device()``."""
-    _grad_lead(net, "train_step")
-    if rows.dim() == 2:
-        rows = rows[:, None, :]
-    return _train_step("train_step", "cs_value_net_train_step", grad_sizes, net, flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream)
-
-
-def _grad_lead_lstm(net, caller):
-    if not has_recurrent_gradient_kernel(net.family):
-        raise ValueError(RECURRENT_GRADIENT_REFUSAL.format(caller))
-    return (net.dims.ctypes.data, len(net.dims))
+    return _train_step("train_step", _served(net, "train_step", FEED_FORWARD), flat, momentum, rows, targets, grad, lr, mu, values, loss_sum, stream)
 
 
 def pack_lstm_on_device(net, flat, stream=None):
     """cs_value_net_pack_lstm_device: ``pack_on_device`` for a recurrent `net` -- byte for byte ``pack``'s blob (cs_value_net_pack_lstm)."""
-    from ... import _lib
-
-    lead = _grad_lead_lstm(net, "pack_lstm_on_device")
-    blob = net.blobs["f32"]
-    if blob is None:
-        nf = C.c_size_t(0)
-        _lib.check(_lib.load().cs_value_net_pack_lstm(*lead, net.cols, None, None, C.byref(nf)))
-        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
-    _lib.check(_lib.load().cs_value_net_pack_lstm_device(*lead, net.cols, flat.data_ptr(), flat.numel(), blob.data_ptr(), blob.numel(), _stream(stream)))
-    return blob
+    return _pack_on_device(_served(net, "pack_lstm_on_device", RECURRENT), flat, stream)
 
 
 def grad_sizes_lstm(net, B, n):
     """cs_value_net_grad_sizes_lstm: (the length of the flat parameters, the scratch floats a minibatch of B samples of n humans needs: a
     partial gradient and the tape of n steps per workgroup)."""
-    from ... import _lib
-
-    n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(_lib.load().cs_value_net_grad_sizes_lstm(*_grad_lead_lstm(net, "grad_sizes_lstm"), net.cols, B, n, C.byref(n_params), C.byref(n_scratch)))
-    return n_params.value, n_scratch.value
+    return _grad_sizes(_served(net, "grad_sizes_lstm", RECURRENT), B, n)
 
 
 def loss_and_grad_lstm(net, flat, rows, targets, grad, values=None, stream=None):
     """cs_value_net_loss_grad_lstm: ``loss_and_grad`` for a recurrent `net` on the minibatch rows [B, n, cols], every sample's rows in the
     order they lie in; `net`'s float32 blob must hold `flat`'s numbers (``pack_lstm_on_device``).  Returns the loss, a CUDA tensor of one
     element.  The scratch (partial gradients and tapes) is kept on `net` and grown when a larger minibatch comes."""
-    from ... import _lib
-
-    _grad_lead_lstm(net, "loss_and_grad_lstm")
-    head = net.head("loss_and_grad_lstm")
-    if rows.dim() != 3:
-        raise ValueError(f"loss_and_grad_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
-    B, n, cols, scratch, loss = _minibatch("loss_and_grad_lstm", net, flat, rows, targets, grad, values, grad_sizes_lstm)
-    _lib.check(_lib.load().cs_value_net_loss_grad_lstm(*head, flat.data_ptr(), flat.numel(), B, n, cols, rows.data_ptr(), targets.data_ptr(),
-                                                       grad.data_ptr(), loss.data_ptr(), None if values is None else values.data_ptr(),
-                                                       scratch.data_ptr(), scratch.numel(), _stream(stream)))
-    return loss
+    return _loss_and_grad("loss_and_grad_lstm", _served(net, "loss_and_grad_lstm", RECURRENT), flat, rows, targets, grad, values, stream)
 
 
 def train_step_lstm(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
     """cs_value_net_train_step_lstm: ``train_step`` for a recurrent `net` -- ``loss_and_grad_lstm``, the SGD step and the recurrent blob (the
     gate rows, bias_ih + bias_hh) rewritten, in two launches."""
-    _grad_lead_lstm(net, "train_step_lstm")
-    if rows.dim() != 3:
-        raise ValueError(f"train_step_lstm: rows are [B, n, cols], not {tuple(rows.shape)}")
-    return _train_step("train_step_lstm", "cs_value_net_train_step_lstm", grad_sizes_lstm, net, flat, momentum, rows, targets, grad, lr, mu, values,
-                       loss_sum, stream)
+    return _train_step("train_step_lstm", _served(net, "train_step_lstm", RECURRENT), flat, momentum, rows, targets, grad, lr, mu, values, loss_sum,
+                       stream)
 
 
-# ---------------------------------------------------------------------------------------------------------------- the families with map columns
-def _om_family(net, caller, narrow):
-    """The entries' infix of a mapped `net` ("" for OM-SARL, "_lstm" for OM-LSTM-RL) and the arguments they open with; ValueError in
-    `caller`'s name for a net without map columns, naming the helper `narrow` that serves it."""
-    if not has_mapped_gradient_kernel(net.family):
-        raise ValueError(MAPPED_GRADIENT_REFUSAL.format(caller, narrow))
-    return ("_lstm" if net.lstm else ""), net.family.lead(net.kind) + (net.dims.ctypes.data, len(net.dims))
-
-
-def _om_rows(caller, net, rows):
-    if rows.dim() != 3:
-        raise ValueError(f"{caller}: rows are [B, n, cols + om_cols], not {tuple(rows.shape)}")
-    return rows
+def _mapped(net, caller, narrow):
+    return _served(net, caller, MAPPED, RECURRENT_MAPPED, narrow=narrow)
 
 
 def grad_sizes_om(net, B, n):
     """cs_value_net_grad_sizes_om / cs_value_net_grad_sizes_lstm_om: ``grad_sizes`` / ``grad_sizes_lstm`` for a net with map columns."""
-    from ... import _lib
-
-    infix, lead = _om_family(net, "grad_sizes_om", "grad_sizes / grad_sizes_lstm")
-    n_params, n_scratch = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(getattr(_lib.load(), f"cs_value_net_grad_sizes{infix}_om")(*lead, net.cols, net.om_cols, B, n, C.byref(n_params), C.byref(n_scratch)))
-    return n_params.value, n_scratch.value
+    return _grad_sizes(_mapped(net, "grad_sizes_om", "grad_sizes / grad_sizes_lstm"), B, n)
 
 
 def pack_om_on_device(net, flat, stream=None):
     """cs_value_net_pack_om_device / cs_value_net_pack_lstm_om_device: ``pack_on_device`` for a net with map columns -- byte for byte
     ``pack``'s blob (cs_value_net_pack_om / cs_value_net_pack_lstm_om)."""
-    from ... import _lib
-
-    infix, lead = _om_family(net, "pack_om_on_device", "pack_on_device / pack_lstm_on_device")
-    blob = net.blobs["f32"]
-    if blob is None:
-        nf = C.c_size_t(0)
-        _lib.check(getattr(_lib.load(), net.family.pack["f32"][0])(*lead, net.cols, net.om_cols, None, None, C.byref(nf)))
-        blob = net.blobs["f32"] = _torch().empty(nf.value, dtype=_torch().float32, device=flat.device)
-    _lib.check(getattr(_lib.load(), f"cs_value_net_pack{infix}_om_device")(*lead, net.cols, net.om_cols, flat.data_ptr(), flat.numel(),
-                                                                          blob.data_ptr(), blob.numel(), _stream(stream)))
-    return blob
+    return _pack_on_device(_mapped(net, "pack_om_on_device", "pack_on_device / pack_lstm_on_device"), flat, stream)
 
 
 def loss_and_grad_om(net, flat, rows, targets, grad, values=None, stream=None):
     """cs_value_net_loss_grad_om / cs_value_net_loss_grad_lstm_om: ``loss_and_grad`` / ``loss_and_grad_lstm`` for a net with map columns
     on the minibatch rows [B, n, cols + om_cols] -- a row is a human's rotated columns, then its map, as ``transform`` stores them;
     `net`'s float32 blob must hold `flat`'s numbers (``pack_om_on_device``).  Returns the loss, a CUDA tensor of one element."""
-    from ... import _lib
-
-    infix, _ = _om_family(net, "loss_and_grad_om", "loss_and_grad / loss_and_grad_lstm")
-    head = net.head("loss_and_grad_om")
-    rows = _om_rows("loss_and_grad_om", net, rows)
-    B, n, _, scratch, loss = _minibatch("loss_and_grad_om", net, flat, rows, targets, grad, values, grad_sizes_om, width=net.cols + net.om_cols)
-    _lib.check(getattr(_lib.load(), f"cs_value_net_loss_grad{infix}_om")(
-        *head, flat.data_ptr(), flat.numel(), B, n, net.cols, net.om_cols, rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(),
-        None if values is None else values.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(stream)))
-    return loss
+    return _loss_and_grad("loss_and_grad_om", _mapped(net, "loss_and_grad_om", "loss_and_grad / loss_and_grad_lstm"), flat, rows, targets, grad, values,
+                          stream)
 
 
 def train_step_om(net, flat, momentum, rows, targets, grad, lr, mu, values=None, loss_sum=None, stream=None):
     """cs_value_net_train_step_om / cs_value_net_train_step_lstm_om: ``train_step`` / ``train_step_lstm`` for a net with map columns --
     ``loss_and_grad_om``, the SGD step and the blob (the wide first layer included; its k-group padding stays zero) rewritten."""
-    from ... import _lib
-
-    infix, _ = _om_family(net, "train_step_om", "train_step / train_step_lstm")
-    if momentum is None:
-        raise ValueError(f"train_step_om: momentum is a contiguous CUDA float32 tensor of {flat.numel()} elements")
-    head = net.head("train_step_om")
-    if net.flat is not flat:
-        raise ValueError("train_step_om: `flat` is not the tensor the network's parameters are views of (DeviceNet.adopt_flat)")
-    rows = _om_rows("train_step_om", net, rows)
-    B, n, _, scratch, loss = _minibatch("train_step_om", net, flat, rows, targets, grad, values, grad_sizes_om, momentum, loss_sum, net.cols + net.om_cols)
-    _lib.check(getattr(_lib.load(), f"cs_value_net_train_step{infix}_om")(
-        *head, flat.data_ptr(), flat.numel(), momentum.data_ptr(), momentum.numel(), float(lr), float(mu), B, n, net.cols, net.om_cols,
-        rows.data_ptr(), targets.data_ptr(), grad.data_ptr(), loss.data_ptr(), None if loss_sum is None else loss_sum.data_ptr(),
-        None if values is None else values.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(stream)))
-    net.updated_on_device()
-    return loss
+    return _train_step("train_step_om", _mapped(net, "train_step_om", "train_step / train_step_lstm"), flat, momentum, rows, targets, grad, lr, mu,
+                       values, loss_sum, stream)
 
 
 def blob_index_om(net):
     """cs_value_net_blob_index_om / cs_value_net_blob_index_lstm_om (host only): the float of ``pack``'s blob that holds every parameter
     of ``param_offsets``' flat layout, an int32 numpy array."""
-    from ... import _lib
-
-    infix, lead = _om_family(net, "blob_index_om", "cs_value_net_blob_index / cs_value_net_blob_index_lstm")
-    index = np.full(param_offsets(net)[-1], -1, np.int32)
-    _lib.check(getattr(_lib.load(), f"cs_value_net_blob_index{infix}_om")(*lead, net.cols, net.om_cols, index.ctypes.data, index.size))
-    return index
+    return _blob_index(_mapped(net, "blob_index_om", "cs_value_net_blob_index / cs_value_net_blob_index_lstm"))
 
 
 def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):

@@ -32,6 +32,7 @@ Two ways to the update, ``set_update``:
 from __future__ import annotations
 
 import logging
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -45,9 +46,30 @@ MAP_GRADIENTS = ("device_om", "device_lstm_om")     # the device modes of the ne
 UPDATES = ("torch", "device")
 
 
-# a device gradient mode's (loss-and-gradient, train-step) seams
-_KERNELS = {"device": (value_net.loss_and_grad, value_net.train_step), "device_lstm": (value_net.loss_and_grad_lstm, value_net.train_step_lstm),
-            "device_om": (value_net.loss_and_grad_om, value_net.train_step_om), "device_lstm_om": (value_net.loss_and_grad_om, value_net.train_step_om)}
+class _Mode(NamedTuple):
+    """What a device gradient mode states about itself; ``set_gradient`` and the steps ask its row of _MODES."""
+    kinds: tuple                # ``describe``'s kinds of the modules it trains
+    other_kind: str             # the refusal of any other module ({who}: the caller)
+    wide_rows: str              # the refusal of a first layer that reads more than 13 | 15 columns ({who}, {cols}); a map mode has none
+    has_kernel: object          # value_net's predicate of the families it trains
+    which: str                  # what the messages call a DeviceNet of those families
+    narrow: str                 # a map mode's sibling for the same network without map columns
+    needs_net: bool             # `net=` is required: the first layer does not say how many of its inputs are map columns
+    loss_and_grad: object       # value_net's two seams
+    train_step: object
+
+
+_MODES = {
+    "device": _Mode((value_net.CS_VN_CADRL, value_net.CS_VN_SARL), value_net.GRADIENT_REFUSAL.format("{who}"), value_net.GRADIENT_REFUSAL.format("{who}"),
+                    value_net.has_gradient_kernel, "feed-forward", "", False, value_net.loss_and_grad, value_net.train_step),
+    "device_lstm": _Mode((value_net.CS_VN_LSTM,), '{who}: the module has no LSTM; CADRL and SARL train with set_gradient("device")',
+                         value_net.RECURRENT_GRADIENT_REFUSAL.format("{who} on rows of {cols} columns"), value_net.has_recurrent_gradient_kernel,
+                         "recurrent", "", False, value_net.loss_and_grad_lstm, value_net.train_step_lstm),
+    "device_om": _Mode((value_net.CS_VN_SARL,), '{who}: the module is not SARL\'s network; OM-LSTM-RL trains with set_gradient("device_lstm_om")', "",
+                       value_net.has_mapped_gradient_kernel, "mapped", "device", True, value_net.loss_and_grad_om, value_net.train_step_om),
+    "device_lstm_om": _Mode((value_net.CS_VN_LSTM,), '{who}: the module has no LSTM; OM-SARL trains with set_gradient("device_om")', "",
+                            value_net.has_mapped_gradient_kernel, "mapped", "device_lstm", True, value_net.loss_and_grad_om, value_net.train_step_om),
+}
 
 
 class _MemoryLoader:
@@ -126,34 +148,25 @@ class Trainer(object):
         first = layers[0] if layers else None
         cols = getattr(first, "in_features", getattr(first, "input_size", 0))       # (network 1's first layer is the nn.LSTM itself)
         who = f'Trainer.set_gradient("{gradient}")'
-        if gradient in MAP_GRADIENTS:
-            narrow = "device_lstm" if gradient == "device_lstm_om" else "device"
-            has_kernel, which = value_net.has_mapped_gradient_kernel, "mapped"
-            if gradient == "device_om" and (kind != value_net.CS_VN_SARL):
-                raise ValueError(f'{who}: the module is not SARL\'s network; OM-LSTM-RL trains with set_gradient("device_lstm_om")')
-            if gradient == "device_lstm_om" and kind != value_net.CS_VN_LSTM:
-                raise ValueError(f'{who}: the module has no LSTM; OM-SARL trains with set_gradient("device_om")')
+        mode = _MODES[gradient]
+        has_kernel, which = mode.has_kernel, mode.which
+        if kind not in mode.kinds:
+            raise ValueError(mode.other_kind.format(who=who))
+        if mode.needs_net:
+            no_maps = f'{who}: the network has no occupancy-map columns; it trains with set_gradient("{mode.narrow}")'
             if net is None:
                 if cols in (13, 15):
-                    raise ValueError(f'{who}: the network has no occupancy-map columns; it trains with set_gradient("{narrow}")')
+                    raise ValueError(no_maps)
                 raise ValueError(f"{who}: a first layer of {cols} inputs does not say how many of them are map columns; pass net=, the "
                                  "policy's own policy.device_net()")
             if net.model is not self.model:
                 raise ValueError(f"{who}: the DeviceNet given is not this model's {which} one")
             if not has_kernel(net.family):
-                raise ValueError(f'{who}: the network has no occupancy-map columns; it trains with set_gradient("{narrow}")')
+                raise ValueError(no_maps)
             if net.cols + net.om_cols != cols:
                 raise ValueError(f"{who}: the DeviceNet's {net.cols} + {net.om_cols} columns are not the first layer's {cols} inputs")
-        elif gradient == "device_lstm":
-            has_kernel, which = value_net.has_recurrent_gradient_kernel, "recurrent"
-            if kind != value_net.CS_VN_LSTM:
-                raise ValueError(f'{who}: the module has no LSTM; CADRL and SARL train with set_gradient("device")')
-            if cols not in (13, 15):
-                raise ValueError(value_net.RECURRENT_GRADIENT_REFUSAL.format(f"{who} on rows of {cols} columns"))
-        else:
-            has_kernel, which = value_net.has_gradient_kernel, "feed-forward"
-            if kind == value_net.CS_VN_LSTM or cols not in (13, 15) or not has_kernel(value_net.family_of(kind, 0)):
-                raise ValueError(value_net.GRADIENT_REFUSAL.format(who))
+        elif cols not in (13, 15):
+            raise ValueError(mode.wide_rows.format(who=who, cols=cols))
         if any(not p.is_cuda for p in params):
             raise ValueError(f'{who}: the model is on the CPU; the gradient kernel runs on the GPU (model.to("cuda"))')
         if any(p.dtype != torch.float32 for p in params):
@@ -171,7 +184,7 @@ class Trainer(object):
                 flat[at:at + p.numel()].copy_(p.detach().reshape(-1))
                 p.data = flat[at:at + p.numel()].view(p.shape)
                 p.grad = grad[at:at + p.numel()].view(p.shape)
-        net.adopt_flat(flat, mapped=gradient in MAP_GRADIENTS)
+        net.adopt_flat(flat, mapped=mode.needs_net)
         self.gradient, self.net, self.flat, self.flat_grad = gradient, net, flat, grad
 
     # ------------------------------------------------------------------ the update's path
@@ -246,9 +259,8 @@ class Trainer(object):
         ``self.loss_sum`` on the device and left in ``self.last_loss`` (a CUDA tensor of one element)."""
         self._device_inputs(inputs)
         lr, momentum = self._sgd()
-        kernel = _KERNELS[self.gradient][1]
-        self.last_loss = kernel(self.net, self.flat, self.momentum, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad,
-                                lr, momentum, loss_sum=self._device_sum())
+        self.last_loss = _MODES[self.gradient].train_step(self.net, self.flat, self.momentum, inputs.contiguous(), values.reshape(-1).contiguous(),
+                                                          self.flat_grad, lr, momentum, loss_sum=self._device_sum())
 
     def _step(self, inputs, values):
         """One optimiser step on a minibatch; returns the loss as a Python float (a read-back in every mode: the loops of "device" update
@@ -258,8 +270,7 @@ class Trainer(object):
             return self.last_loss.item()
         if self.gradient != "autograd":
             self._device_inputs(inputs)
-            kernel = _KERNELS[self.gradient][0]
-            loss = kernel(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
+            loss = _MODES[self.gradient].loss_and_grad(self.net, self.flat, inputs.contiguous(), values.reshape(-1).contiguous(), self.flat_grad)
             self.optimizer.step()
             return loss.item()
         self.optimizer.zero_grad()

@@ -1,8 +1,11 @@
-// value_net_grad.h -- what the gradient kernels (value_net_grad.hip: CADRL / SARL; value_net_lstm_grad.hip: LSTM-RL) share: the flat
-// parameter offsets, the layer-indexed part of the LDS map, the forward layer of a 32-row tile, the three backward products on
-// v_mfma_f32_32x32x2_f32 (dX = dZ W, dWt = dZt X, db), the chains over them, the kernel that sums the workgroups' regions and the one that
-// sums them, takes the SGD-momentum step and rewrites the blob (k_vn_sgd, the train-step entries).  Unnamed namespace: each translation
-// unit gets its own copy.
+// value_net_grad.h -- what the training entries of the four value-network families (value_net_grad.hip: CADRL / SARL / OM-SARL;
+// value_net_lstm_grad.hip: LSTM-RL / OM-LSTM-RL) share.  Device: the flat parameter offsets, the layer-indexed part of the LDS map, the forward
+// layer of a 32-row tile, the three backward products on v_mfma_f32_32x32x2_f32 (dX = dZ W, dWt = dZt X, db), the chains over them, the value
+// head of a job (VG_LOSS_HEAD), the kernel that sums the workgroups' regions, the one that sums them, takes the SGD-momentum step and rewrites
+// the blob (k_vn_sgd, the train-step entries), and pack_layer_f32's map read forwards (blob_layer_at) and backwards (unpack_layer_at, the
+// device-pack kernels).  Host: one call of an entry as a struct (GradCall) and the host functions behind the entries -- plan_grad, check_grad_args
+// and one per kind of entry: grad_sizes, loss_grad, train_step, blob_index, pack_device --, templates over the family type each .hip file defines.  Unnamed
+// namespace: each translation unit gets its own copy.
 #pragma once
 #include "value_net_plan.h"
 
@@ -181,6 +184,36 @@ __device__ __forceinline__ void bwd_db(float* gb, int N, const float* dZ, int ld
 // (a layer's output is lds + m.act[l]: an array of pointers indexed by a run-time layer would live in scratch memory)
 struct GradBufs { float *lds, *X0, *D0, *D1, *dH, *G, *dG, *J, *dJ, *sc, *dw, *den, *val; int* grp; };
 
+// The value head of a job behind its last layer: the values of its ng groups from gbase, the loss terms and dV = 2 (V - target) / B as the
+// top gradient [32][12] in D0; thread 0 adds the job's loss terms, in group order, to its `loss`.  Reads the kernel's p, b, tid, gbase, ng,
+// B, targets, values and loss; M: its GradLds; UNROLL: what stands before the loop (the recurrent kernels' `unroll 1`, or nothing).  A
+// macro: as an inline function it left both recurrent builds at their registers but moved their schedule (DESIGN.md 4.5 "where the training side's pieces live").
+#define VG_LOSS_HEAD(M, UNROLL)                                                                                              \
+    {                                                                                                                        \
+        const int last = p.n_layers - 1;                                                                                     \
+        const float* out = b.lds + M.act[last];                                                                              \
+        const int ldo = M.ld[last];                                                                                          \
+        UNROLL                                                                                                               \
+        for (int i = tid; i < 32 * ldo; i += NT) {                                                                           \
+            const int k = i / ldo, c = i - k * ldo;                                                                          \
+            float d = 0.0f;                                                                                                  \
+            if (c == 0 && k < ng) {                                                                                          \
+                const float v = out[k * ldo];                                                                                \
+                if (values) values[gbase + k] = 0.0f + v;                                                                    \
+                d = v - targets[gbase + k];                                                                                  \
+                b.val[k] = d * d;                                                                                            \
+                d = 2.0f * d / (float)B;                                                                                     \
+            }                                                                                                                \
+            b.D0[i] = d;                                                                                                     \
+        }                                                                                                                    \
+        __syncthreads();                                                                                                     \
+        if (tid == 0) {                                                                                                      \
+            float s = 0.0f;                                                                                                  \
+            for (int k = 0; k < ng; ++k) s += b.val[k];                                                                      \
+            loss += s;                                                                                                       \
+        }                                                                                                                    \
+    }
+
 // layers [first, last) forward from src (and src2 per group behind it), every output kept in its act buffer
 __device__ __forceinline__ void chain_fwd(const VnPlan& p, const GradLds& m, const GradBufs& b, const float* __restrict__ wb, int first, int last,
                                           const float* src, int lds_, const float* src2, int lds2)
@@ -247,6 +280,31 @@ __host__ __device__ __forceinline__ int blob_layer_at(const VnLayer& L, int e)
     return blob_weight_at(L, j >> 5, j & 31, k < L.K1 ? k : L.kg_split * 8 + k - L.K1);
 }
 
+// pack_layer_f32's loop variables of float e of a layer's weights in the blob: the 32-column block, the column in it, the k-group and the
+// column kk counted in the blob's k-groups
+__device__ __forceinline__ void blob_weight_of(const VnLayer& L, int e, int& cb, int& col, int& kg, int& kk)
+{
+    const int s = e & 3, lane = (e >> 2) & 63, q = e >> 8;
+    kg = q % L.kg_total;
+    cb = q / L.kg_total;
+    col = lane & 31;
+    kk = kg * 8 + 4 * (lane >> 5) + s;
+}
+
+// blob float i of a Linear layer from its flat (weight [N][K1 + K2], bias [N]) pair: pack_layer_f32's map, read backwards (blob_layer_at
+// reads it forwards); the padding is 0
+__device__ __forceinline__ float unpack_layer_at(const VnLayer& L, int i, const float* __restrict__ weight, const float* __restrict__ bias)
+{
+    if (i >= L.b_off) return i - L.b_off < L.N ? bias[i - L.b_off] : 0.0f;
+    int cb, col, kg, kk;
+    blob_weight_of(L, i - L.w_off, cb, col, kg, kk);
+    const int j = cb * 32 + col;
+    int k = -1;
+    if (kg < L.kg_split) { if (kk < L.K1) k = kk; }
+    else if (kk - L.kg_split * 8 < L.K2) k = L.K1 + kk - L.kg_split * 8;
+    return j < L.N && k >= 0 ? weight[(long)j * (L.K1 + L.K2) + k] : 0.0f;
+}
+
 // k_vn_grad_sum's sum for k_vn_sgd: the regions' floats i, added in region order -- the same adds, the same bytes --, with eight regions'
 // loads in flight at a time (one load a trip waits a memory latency per region: 228 of them at 4096 x 5)
 __device__ __forceinline__ float region_sum(const float* __restrict__ scratch, int region, int regions, int i)
@@ -304,13 +362,165 @@ __global__ __launch_bounds__(256) void k_vn_sgd(Map map, const float* __restrict
     blob[at] = v;
 }
 
-// what the train-step entries check beyond their loss-and-gradient entry's checks
-inline int check_sgd_args(const float* d_momentum, size_t n_momentum_floats, size_t n_param_floats, float lr, float momentum)
+// ---------------------------------------------------------------------------------------------------------------- the entries' host side
+// One call of a training entry, whichever of the twenty: an extern "C" function fills the fields its arguments name (the rest stay null / 0)
+// and hands it to one of the templates below.  `kind` is the feed-forward entries' alone; `om`: an *_om entry, whose rows carry om_cols
+// map columns behind the cols rotated ones.  d_weights is the float32 blob: read by the job kernel, rewritten by the train-step and the
+// device-pack entries.
+struct GradCall {
+    int kind; const int32_t* dims; int n_dims, cols; bool om; int om_cols;                      // the description
+    int B, n; const float *d_rows, *d_targets;                                                  // the minibatch
+    float* d_weights; size_t n_weight_floats; float* d_params; size_t n_param_floats; float* d_momentum; size_t n_momentum_floats;
+    float *d_grad, *d_loss; double* d_loss_sum; float *d_values, *d_scratch; size_t n_scratch_floats;
+    float lr, momentum;
+    void* stream;
+};
+
+inline GradCall describe_call(int kind, const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int B = 0, int n = 0)
 {
-    if (!d_momentum) return fail(CS_ERR_ARG, "null argument");
-    if (n_momentum_floats != n_param_floats) return fail(CS_ERR_ARG, "the momentum buffer does not have the size of the flat parameters");
-    if (!std::isfinite(lr) || lr < 0.0f) return fail(CS_ERR_ARG, "lr must be finite and at least 0");
-    if (!std::isfinite(momentum) || momentum < 0.0f) return fail(CS_ERR_ARG, "momentum must be finite and at least 0");
+    GradCall c{};
+    c.kind = kind; c.dims = dims; c.n_dims = n_dims; c.cols = cols; c.om = om; c.om_cols = om_cols; c.B = B; c.n = n;
+    return c;
+}
+
+// the arguments of a loss-and-gradient entry behind the description
+inline void set_minibatch(GradCall& c, const float* d_weights, size_t n_weight_floats, const float* d_params, size_t n_param_floats,
+                          const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, float* d_values, float* d_scratch,
+                          size_t n_scratch_floats, void* stream)
+{
+    c.d_weights = const_cast<float*>(d_weights); c.n_weight_floats = n_weight_floats; c.d_params = const_cast<float*>(d_params); c.n_param_floats = n_param_floats;
+    c.d_rows = d_rows; c.d_targets = d_targets; c.d_grad = d_grad; c.d_loss = d_loss; c.d_values = d_values;
+    c.d_scratch = d_scratch; c.n_scratch_floats = n_scratch_floats; c.stream = stream;
+}
+
+// what a train-step entry takes beyond them
+inline void set_sgd(GradCall& c, float* d_momentum, size_t n_momentum_floats, float lr, float momentum, double* d_loss_sum)
+{
+    c.d_momentum = d_momentum; c.n_momentum_floats = n_momentum_floats; c.lr = lr; c.momentum = momentum; c.d_loss_sum = d_loss_sum;
+}
+
+// the arguments of a device-pack entry behind the description
+inline void set_pack(GradCall& c, const float* d_params, size_t n_param_floats, float* d_blob, size_t n_blob_floats, void* stream)
+{
+    c.d_params = const_cast<float*>(d_params); c.n_param_floats = n_param_floats; c.d_weights = d_blob; c.n_weight_floats = n_blob_floats; c.stream = stream;
+}
+
+// The host functions below exist once, over a family type F (FeedForwardGrad in value_net_grad.hip, LstmGrad in value_net_lstm_grad.hip):
+//   F::Launch          the launch record: the plan, the offsets `o`, the LDS map, grid, region, shmem; blob_floats()
+//   F::describe(c, q)  the plan of the description and the flat offsets
+//   F::check_n(c)      the family's own check of n, made between "n < 1" and "B * n"
+//   F::plan(c, q)      the LDS map -- refused in the family's words when it does not fit --, the grid and the region (P + 1 rounded up to 4,
+//                      plus the tape for the recurrent family)
+//   F::launch_jobs(q, c), F::sgd_map(q), F::launch_pack(q, c)
+//   F::pack_entry, F::sizes_entry   the entry names the messages quote
+template <class F>
+inline int plan_grad(const GradCall& c, typename F::Launch& q)
+{
+    const int rc = F::describe(c, q);
+    if (rc != CS_OK) return rc;
+    if (c.B < 1) return fail(CS_ERR_ARG, "B must be positive");
+    if (c.n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
+    const int rc1 = F::check_n(c);
+    if (rc1 != CS_OK) return rc1;
+    if ((long)c.B * c.n > INT_MAX / 16) return fail(CS_ERR_ARG, "B * n is too large");
+    return F::plan(c, q);
+}
+
+// a size that is not this network's: `what`, and in brackets the entry that tells the right one
+inline int size_refusal(const char* what, const char* entry) { return fail(CS_ERR_ARG, std::string(what) + " (" + entry + ")"); }
+
+// cs_value_net_grad_sizes[_lstm][_om]
+template <class F>
+inline int grad_sizes(const GradCall& c, size_t* n_param_floats, size_t* n_scratch_floats)
+{
+    typename F::Launch q;
+    const int rc = plan_grad<F>(c, q);
+    if (rc != CS_OK) return rc;
+    if (!n_param_floats || !n_scratch_floats) return fail(CS_ERR_ARG, "null argument");
+    *n_param_floats = (size_t)q.o.total;
+    *n_scratch_floats = (size_t)q.grid * q.region;
+    return CS_OK;
+}
+
+// the argument checks of the loss-and-gradient entries, which the train-step entries make first
+template <class F>
+inline int check_grad_args(const GradCall& c, typename F::Launch& q)
+{
+    const int rc = plan_grad<F>(c, q);
+    if (rc != CS_OK) return rc;
+    if (!c.d_weights || !c.d_params || !c.d_rows || !c.d_targets || !c.d_grad || !c.d_loss || !c.d_scratch) return fail(CS_ERR_ARG, "null argument");
+    if (c.n_weight_floats != q.blob_floats()) return size_refusal("the weight blob does not have the size of this network", F::pack_entry);
+    if (c.n_param_floats != (size_t)q.o.total) return size_refusal("the flat parameters do not have the size of this network", F::sizes_entry);
+    if (c.n_scratch_floats < (size_t)q.grid * q.region) return size_refusal("the scratch is too small for this minibatch", F::sizes_entry);
+    return CS_OK;
+}
+
+// cs_value_net_loss_grad[_lstm][_om]: the job kernel, then the regions summed
+template <class F>
+inline int loss_grad(const GradCall& c)
+{
+    typename F::Launch q;
+    const int rc = check_grad_args<F>(c, q);
+    if (rc != CS_OK) return rc;
+    const int rc2 = F::launch_jobs(q, c);
+    if (rc2 != CS_OK) return rc2;
+    hipLaunchKernelGGL(k_vn_grad_sum, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)c.stream, c.d_scratch, q.region, q.grid, q.o.total, c.B,
+                       c.d_grad, c.d_loss);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// cs_value_net_train_step[_lstm][_om]: the job kernel, then k_vn_sgd on the family's map of its blob
+template <class F>
+inline int train_step(const GradCall& c)
+{
+    typename F::Launch q;
+    const int rc = check_grad_args<F>(c, q);
+    if (rc != CS_OK) return rc;
+    if (!c.d_momentum) return fail(CS_ERR_ARG, "null argument");
+    if (c.n_momentum_floats != c.n_param_floats) return fail(CS_ERR_ARG, "the momentum buffer does not have the size of the flat parameters");
+    if (!std::isfinite(c.lr) || c.lr < 0.0f) return fail(CS_ERR_ARG, "lr must be finite and at least 0");
+    if (!std::isfinite(c.momentum) || c.momentum < 0.0f) return fail(CS_ERR_ARG, "momentum must be finite and at least 0");
+    const int rc2 = F::launch_jobs(q, c);
+    if (rc2 != CS_OK) return rc2;
+    hipLaunchKernelGGL(k_vn_sgd<decltype(F::sgd_map(q))>, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)c.stream, F::sgd_map(q), c.d_scratch,
+                       q.region, q.grid, q.o.total, c.B, c.lr, c.momentum, c.d_params, c.d_momentum, c.d_grad, c.d_weights, c.d_loss, c.d_loss_sum);
+    HIP_TRY(hipGetLastError());
+    return CS_OK;
+}
+
+// cs_value_net_blob_index[_lstm][_om]: a parameter whose map answers no float of its own (the LSTM's bias_hh) is written by its partner,
+// which names it as its twin; the feed-forward map has no twins
+template <class F>
+inline int blob_index(const GradCall& c, int32_t* index, size_t n_param_floats)
+{
+    typename F::Launch q;
+    const int rc = F::describe(c, q);
+    if (rc != CS_OK) return rc;
+    if (!index) return fail(CS_ERR_ARG, "null argument");
+    if (n_param_floats != (size_t)q.o.total) return size_refusal("the flat parameters do not have the size of this network", F::sizes_entry);
+    const auto map = F::sgd_map(q);
+    for (int i = 0; i < q.o.total; ++i) {
+        int twin;
+        const int at = map(i, twin);
+        if (at >= 0) index[i] = at;
+        if (twin >= 0) index[twin] = at;
+    }
+    return CS_OK;
+}
+
+// cs_value_net_pack[_lstm][_om]_device: the blob (c.d_weights) from the flat parameters
+template <class F>
+inline int pack_device(const GradCall& c)
+{
+    typename F::Launch q;
+    const int rc = F::describe(c, q);
+    if (rc != CS_OK) return rc;
+    if (!c.d_params || !c.d_weights) return fail(CS_ERR_ARG, "null argument");
+    if (c.n_param_floats != (size_t)q.o.total) return size_refusal("the flat parameters do not have the size of this network", F::sizes_entry);
+    if (c.n_weight_floats != q.blob_floats()) return size_refusal("the weight blob does not have the size of this network", F::pack_entry);
+    F::launch_pack(q, c);
+    HIP_TRY(hipGetLastError());
     return CS_OK;
 }
 

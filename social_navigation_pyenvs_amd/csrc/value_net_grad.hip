@@ -1,6 +1,7 @@
 // value_net_grad.hip -- the training side of the feed-forward value networks (CADRL, SARL), fused: for a minibatch of B stored states the
 // forward pass, the mean-squared-error loss against B targets and the gradient of that loss with respect to every parameter
 // (cs_value_net_loss_grad), and the packing of the flat parameters into the decision kernels' blob on the device (cs_value_net_pack_device).
+// The entries' host side is value_net_grad.h's templates over this file's FeedForwardGrad.
 // Replaces, per optimiser step, crowd_nav/utils/trainer.py:50-71 (zero_grad, model(inputs), MSELoss, backward) for the networks of
 // crowd_nav/policy/sarl.py:28-65 and crowd_nav/policy/cadrl.py:116-123; the optimiser stays torch's -- or, for SGD with momentum, runs in
 // the launch that sums the gradient and rewrites the blob there (cs_value_net_train_step: value_net_grad.h k_vn_sgd).
@@ -304,29 +305,7 @@ __global__ __launch_bounds__(NT) void k_vn_grad(VnPlan p, GradLds m, GradOffsets
             load(0, ng, 0, 1);
             chain_fwd(p, m, b, wb, p.c0[0], p.c0[1], b.X0, tile_ldx(m), nullptr, 0);
         }
-        {   // the values, the loss terms and dV = 2 (V - target) / B as the top gradient [32][12] in D0
-            const int last = p.n_layers - 1;
-            const float* out = (b.lds + m.act[last]);
-            const int ldo = m.ld[last];
-            for (int i = tid; i < 32 * ldo; i += NT) {
-                const int k = i / ldo, c = i - k * ldo;
-                float d = 0.0f;
-                if (c == 0 && k < ng) {
-                    const float v = out[k * ldo];
-                    if (values) values[gbase + k] = 0.0f + v;
-                    d = v - targets[gbase + k];
-                    b.val[k] = d * d;
-                    d = 2.0f * d / (float)B;
-                }
-                b.D0[i] = d;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                float s = 0.0f;
-                for (int k = 0; k < ng; ++k) s += b.val[k];
-                loss += s;
-            }
-        }
+        VG_LOSS_HEAD(m, )
         if (!sarl) {
             chain_bwd(p, m, b, params, o, g, p.c0[0], p.c0[1], b.D0, b.X0, tile_ldx(m), nullptr, 0, nullptr, 0, false, nullptr, 0);
             continue;
@@ -389,188 +368,96 @@ __global__ void k_vn_pack(VnPlan p, GradOffsets o, const float* __restrict__ par
     if (i >= p.total_floats) return;
     int l = 0;
     while (l + 1 < p.n_layers && i >= p.L[l + 1].w_off) ++l;
-    const VnLayer& L = p.L[l];
-    float v = 0.0f;
-    if (i >= L.b_off) {
-        const int j = i - L.b_off;
-        if (j < L.N) v = params[o.b[l] + j];
-    } else {
-        const int e = i - L.w_off;
-        const int s = e & 3, lane = (e >> 2) & 63, q = e >> 8;
-        const int kg = q % L.kg_total, cb = q / L.kg_total;
-        const int j = cb * 32 + (lane & 31);
-        const int kk = kg * 8 + 4 * (lane >> 5) + s;
-        int k = -1;
-        if (kg < L.kg_split) { if (kk < L.K1) k = kk; }
-        else if (kk - L.kg_split * 8 < L.K2) k = L.K1 + kk - L.kg_split * 8;
-        if (j < L.N && k >= 0) v = params[o.w[l] + (long)j * (L.K1 + L.K2) + k];
-    }
-    blob[i] = v;
+    blob[i] = unpack_layer_at(p.L[l], i, params + o.w[l], params + o.b[l]);
 }
 
-// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid.
-// om_cols: the map columns behind the rotated ones in a stored row (the *_om entries; 0: the rows of 13 | 15 columns)
-struct GradLaunch { VnPlan p; GradOffsets o; GradLds m; int grid, region, jrows; size_t shmem; };
+// The feed-forward family as value_net_grad.h's host templates ask it (GradCall: the call; om_cols: the map columns behind the rotated ones in
+// a stored row, 0 for the rows of 13 | 15 columns)
+struct FeedForwardGrad {
+    struct Launch {
+        VnPlan p; GradOffsets o; GradLds m; int grid, region, jrows; size_t shmem;
+        size_t blob_floats() const { return (size_t)p.total_floats; }
+    };
+    static constexpr const char *pack_entry = "cs_value_net_pack", *sizes_entry = "cs_value_net_grad_sizes";
 
-inline int plan_grad(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, GradLaunch& q)
-{
-    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, q.p);
-    if (rc != CS_OK) return rc;
-    if (B < 1) return fail(CS_ERR_ARG, "B must be positive");
-    if (n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
-    if (kind == CS_VN_CADRL && n != 1) return fail(CS_ERR_ARG, "CADRL's trainer stores one human's row per sample: n must be 1");
-    if ((long)B * n > INT_MAX / 16) return fail(CS_ERR_ARG, "B * n is too large");
-    q.o = param_offsets(q.p);
-    q.m = grad_lds_map(q.p, n);
-    q.shmem = (size_t)q.m.total * sizeof(float);
-    if (q.shmem > 160 * 1024)
-        return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(cols) + " + " + std::to_string(om_cols) +
-                                    " columns: " + std::to_string(q.shmem) + " bytes) do not fit the 160 KiB of LDS");
-    // groups per job: whole tiles, as few as spread the minibatch over the workgroups, at most mlp3's block of 32 rows
-    const int gpt = n <= 32 ? 32 / n : 1;
-    const int want = up((B + GRAD_MAX_GROUPS - 1) / GRAD_MAX_GROUPS, gpt);
-    q.jrows = want < JROWS ? want : JROWS;
-    const int jobs = (B + q.jrows - 1) / q.jrows;
-    q.grid = jobs < GRAD_MAX_GROUPS ? jobs : GRAD_MAX_GROUPS;
-    q.region = up(q.o.total + 1, 4);
-    return CS_OK;
-}
-
-// the *_om entries' own check, made first
-inline int check_om_cols(int om_cols) { return om_cols < 1 ? fail(CS_ERR_ARG, "om_cols must be at least 1") : CS_OK; }
-
-inline int grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
-{
-    GradLaunch q;
-    const int rc = plan_grad(kind, dims, n_dims, cols, om_cols, B, n, q);
-    if (rc != CS_OK) return rc;
-    if (!n_param_floats || !n_scratch_floats) return fail(CS_ERR_ARG, "null argument");
-    *n_param_floats = (size_t)q.o.total;
-    *n_scratch_floats = (size_t)q.grid * q.region;
-    return CS_OK;
-}
-
-// the argument checks of the loss-and-gradient entries, which the train-step entries make first
-inline int check_grad_args(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                           size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets, const float* d_grad,
-                           const float* d_loss, const float* d_scratch, size_t n_scratch_floats, GradLaunch& q)
-{
-    const int rc = plan_grad(kind, dims, n_dims, cols, om_cols, B, n, q);
-    if (rc != CS_OK) return rc;
-    if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
-    if (n_weight_floats != (size_t)q.p.total_floats) return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack)");
-    if (n_param_floats != (size_t)q.o.total) return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes)");
-    if (n_scratch_floats < (size_t)q.grid * q.region) return fail(CS_ERR_ARG, "the scratch is too small for this minibatch (cs_value_net_grad_sizes)");
-    return CS_OK;
-}
-
-// the job kernel of the entries: every workgroup's partial gradient and loss term into its region of the scratch
-inline int launch_jobs(const GradLaunch& q, const float* d_weights, const float* d_params, int B, int n, const float* d_rows, const float* d_targets,
-                       float* d_scratch, float* d_values, void* stream)
-{
-    const int rc = grant_lds<k_vn_grad>(q.shmem);
-    if (rc != CS_OK) return rc;
-    hipLaunchKernelGGL(k_vn_grad, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)stream, q.p, q.m, q.o, d_weights, d_params, B, n, q.jrows, d_rows, d_targets,
-                       d_scratch, q.region, d_values);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// k_vn_sgd's map of the feed-forward blob: every parameter has a blob float of its own
-struct SgdMap {
-    VnPlan p;
-    GradOffsets o;
-    __host__ __device__ int operator()(int i, int& twin) const
+    static int describe(const GradCall& c, Launch& q)
     {
-        twin = -1;
-        int l = 0;
-        while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
-        return blob_layer_at(p.L[l], i - o.w[l]);
+        if (c.om && c.om_cols < 1) return fail(CS_ERR_ARG, "om_cols must be at least 1");      // the *_om entries' own check, made first
+        const int rc = build_plan(c.kind, c.dims, c.n_dims, c.cols, c.om_cols, q.p);
+        if (rc == CS_OK) q.o = param_offsets(q.p);
+        return rc;
+    }
+
+    static int check_n(const GradCall& c)
+    {
+        return c.kind == CS_VN_CADRL && c.n != 1 ? fail(CS_ERR_ARG, "CADRL's trainer stores one human's row per sample: n must be 1") : CS_OK;
+    }
+
+    static int plan(const GradCall& c, Launch& q)
+    {
+        q.m = grad_lds_map(q.p, c.n);
+        q.shmem = (size_t)q.m.total * sizeof(float);
+        if (q.shmem > 160 * 1024)
+            return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(c.cols) + " + " +
+                                        std::to_string(c.om_cols) + " columns: " + std::to_string(q.shmem) + " bytes) do not fit the 160 KiB of LDS");
+        // groups per job: whole tiles, as few as spread the minibatch over the workgroups, at most mlp3's block of 32 rows
+        const int gpt = c.n <= 32 ? 32 / c.n : 1;
+        const int want = up((c.B + GRAD_MAX_GROUPS - 1) / GRAD_MAX_GROUPS, gpt);
+        q.jrows = want < JROWS ? want : JROWS;
+        const int jobs = (c.B + q.jrows - 1) / q.jrows;
+        q.grid = jobs < GRAD_MAX_GROUPS ? jobs : GRAD_MAX_GROUPS;
+        q.region = up(q.o.total + 1, 4);
+        return CS_OK;
+    }
+
+    // the job kernel: every workgroup's partial gradient and loss term into its region of the scratch
+    static int launch_jobs(const Launch& q, const GradCall& c)
+    {
+        const int rc = grant_lds<k_vn_grad>(q.shmem);
+        if (rc != CS_OK) return rc;
+        hipLaunchKernelGGL(k_vn_grad, dim3(q.grid), dim3(NT), q.shmem, (hipStream_t)c.stream, q.p, q.m, q.o, c.d_weights, c.d_params, c.B, c.n, q.jrows,
+                           c.d_rows, c.d_targets, c.d_scratch, q.region, c.d_values);
+        HIP_TRY(hipGetLastError());
+        return CS_OK;
+    }
+
+    // k_vn_sgd's map of the feed-forward blob: every parameter has a blob float of its own
+    struct SgdMap {
+        VnPlan p;
+        GradOffsets o;
+        __host__ __device__ int operator()(int i, int& twin) const
+        {
+            twin = -1;
+            int l = 0;
+            while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
+            return blob_layer_at(p.L[l], i - o.w[l]);
+        }
+    };
+    static SgdMap sgd_map(const Launch& q) { return SgdMap{q.p, q.o}; }
+
+    static void launch_pack(const Launch& q, const GradCall& c)
+    {
+        hipLaunchKernelGGL(k_vn_pack, dim3((q.p.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)c.stream, q.p, q.o, c.d_params, c.d_weights);
     }
 };
 
-// cs_value_net_loss_grad[_om]
-inline int loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                     size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
-                     float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
-{
-    GradLaunch q;
-    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
-                                   d_loss, d_scratch, n_scratch_floats, q);
-    if (rc != CS_OK) return rc;
-    const int rc2 = launch_jobs(q, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
-    if (rc2 != CS_OK) return rc2;
-    hipLaunchKernelGGL(k_vn_grad_sum, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_scratch, q.region, q.grid, q.o.total, B,
-                       d_grad, d_loss);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// cs_value_net_train_step[_om]
-inline int train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params, size_t n_param_floats,
-                      float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n, int cols, int om_cols, const float* d_rows,
-                      const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum, float* d_values, float* d_scratch,
-                      size_t n_scratch_floats, void* stream)
-{
-    GradLaunch q;
-    const int rc = check_grad_args(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
-                                   d_loss, d_scratch, n_scratch_floats, q);
-    if (rc != CS_OK) return rc;
-    const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
-    if (rc1 != CS_OK) return rc1;
-    const int rc2 = launch_jobs(q, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
-    if (rc2 != CS_OK) return rc2;
-    hipLaunchKernelGGL(k_vn_sgd<SgdMap>, dim3((q.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, SgdMap{q.p, q.o}, d_scratch, q.region,
-                       q.grid, q.o.total, B, lr, momentum, d_params, d_momentum, d_grad, d_weights, d_loss, d_loss_sum);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// cs_value_net_blob_index[_om]
-inline int blob_index(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
-{
-    VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, p);
-    if (rc != CS_OK) return rc;
-    const GradOffsets o = param_offsets(p);
-    if (!index) return fail(CS_ERR_ARG, "null argument");
-    if (n_param_floats != (size_t)o.total) return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes)");
-    const SgdMap map{p, o};
-    for (int i = 0, twin; i < o.total; ++i) index[i] = map(i, twin);
-    return CS_OK;
-}
-
-// cs_value_net_pack[_om]_device
-inline int pack_device(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats, float* d_blob,
-                       size_t n_blob_floats, void* stream)
-{
-    VnPlan p;
-    const int rc = build_plan(kind, dims, n_dims, cols, om_cols, p);
-    if (rc != CS_OK) return rc;
-    const GradOffsets o = param_offsets(p);
-    if (!d_params || !d_blob) return fail(CS_ERR_ARG, "null argument");
-    if (n_param_floats != (size_t)o.total) return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes)");
-    if (n_blob_floats != (size_t)p.total_floats) return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack)");
-    hipLaunchKernelGGL(k_vn_pack, dim3((p.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, o, d_params, d_blob);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
 } // namespace
 
-// ---- the rows of 13 | 15 columns: the entries above with no map columns
+// ---- the rows of 13 | 15 columns: no map columns
 extern "C" int cs_value_net_grad_sizes(int kind, const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats,
                                        size_t* n_scratch_floats)
 {
-    return grad_sizes(kind, dims, n_dims, cols, 0, B, n, n_param_floats, n_scratch_floats);
+    const GradCall c = describe_call(kind, dims, n_dims, cols, false, 0, B, n);
+    return grad_sizes<FeedForwardGrad>(c, n_param_floats, n_scratch_floats);
 }
 
 extern "C" int cs_value_net_loss_grad(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
                                       size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
                                       float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return loss_grad(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, 0, d_rows, d_targets, d_grad, d_loss, d_values,
-                     d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, false, 0, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    return loss_grad<FeedForwardGrad>(c);
 }
 
 extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
@@ -578,27 +465,31 @@ extern "C" int cs_value_net_train_step(int kind, const int32_t* dims, int n_dims
                                        int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum,
                                        float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return train_step(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols, 0,
-                      d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, false, 0, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    set_sgd(c, d_momentum, n_momentum_floats, lr, momentum, d_loss_sum);
+    return train_step<FeedForwardGrad>(c);
 }
 
 extern "C" int cs_value_net_blob_index(int kind, const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
 {
-    return blob_index(kind, dims, n_dims, cols, 0, index, n_param_floats);
+    return blob_index<FeedForwardGrad>(describe_call(kind, dims, n_dims, cols, false, 0), index, n_param_floats);
 }
 
 extern "C" int cs_value_net_pack_device(int kind, const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats,
                                         float* d_blob, size_t n_blob_floats, void* stream)
 {
-    return pack_device(kind, dims, n_dims, cols, 0, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, false, 0);
+    set_pack(c, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    return pack_device<FeedForwardGrad>(c);
 }
 
-// ---- OM-SARL: rows of cols + om_cols columns
+// ---- OM-SARL: rows of cols + om_cols columns (FeedForwardGrad::describe refuses om_cols < 1 before anything else)
 extern "C" int cs_value_net_grad_sizes_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
                                           size_t* n_scratch_floats)
 {
-    const int rc = check_om_cols(om_cols);
-    return rc != CS_OK ? rc : grad_sizes(kind, dims, n_dims, cols, om_cols, B, n, n_param_floats, n_scratch_floats);
+    const GradCall c = describe_call(kind, dims, n_dims, cols, true, om_cols, B, n);
+    return grad_sizes<FeedForwardGrad>(c, n_param_floats, n_scratch_floats);
 }
 
 extern "C" int cs_value_net_loss_grad_om(int kind, const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats,
@@ -606,10 +497,9 @@ extern "C" int cs_value_net_loss_grad_om(int kind, const int32_t* dims, int n_di
                                          const float* d_targets, float* d_grad, float* d_loss, float* d_values, float* d_scratch,
                                          size_t n_scratch_floats, void* stream)
 {
-    const int rc = check_om_cols(om_cols);
-    return rc != CS_OK ? rc
-                       : loss_grad(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om_cols, d_rows, d_targets, d_grad,
-                                   d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, true, om_cols, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    return loss_grad<FeedForwardGrad>(c);
 }
 
 extern "C" int cs_value_net_train_step_om(int kind, const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
@@ -617,21 +507,21 @@ extern "C" int cs_value_net_train_step_om(int kind, const int32_t* dims, int n_d
                                           int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
                                           double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    const int rc = check_om_cols(om_cols);
-    return rc != CS_OK ? rc
-                       : train_step(kind, dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B,
-                                    n, cols, om_cols, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, true, om_cols, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    set_sgd(c, d_momentum, n_momentum_floats, lr, momentum, d_loss_sum);
+    return train_step<FeedForwardGrad>(c);
 }
 
 extern "C" int cs_value_net_blob_index_om(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
 {
-    const int rc = check_om_cols(om_cols);
-    return rc != CS_OK ? rc : blob_index(kind, dims, n_dims, cols, om_cols, index, n_param_floats);
+    return blob_index<FeedForwardGrad>(describe_call(kind, dims, n_dims, cols, true, om_cols), index, n_param_floats);
 }
 
 extern "C" int cs_value_net_pack_om_device(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params,
                                            size_t n_param_floats, float* d_blob, size_t n_blob_floats, void* stream)
 {
-    const int rc = check_om_cols(om_cols);
-    return rc != CS_OK ? rc : pack_device(kind, dims, n_dims, cols, om_cols, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    GradCall c = describe_call(kind, dims, n_dims, cols, true, om_cols);
+    set_pack(c, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    return pack_device<FeedForwardGrad>(c);
 }

@@ -3,8 +3,9 @@
 // with respect to every parameter by backpropagation through time (cs_value_net_loss_grad_lstm), and the packing of the flat parameters into
 // the decision kernel's blob on the device (cs_value_net_pack_lstm_device).  Replaces, per optimiser step, crowd_nav/utils/trainer.py:50-71
 // (zero_grad, model(inputs), MSELoss, backward) for the recurrent family; the optimiser stays torch's, or runs fused behind the gradient
-// (cs_value_net_train_step_lstm: value_net_grad.h k_vn_sgd on this blob's map, LstmSgdMap).  value_net_grad.hip is the
-// feed-forward family's; the two share value_net_grad.h (the forward layer of a tile, the three backward products, the chains, the sum).
+// (cs_value_net_train_step_lstm: value_net_grad.h k_vn_sgd on this blob's map, LstmGrad::SgdMap).  value_net_grad.hip is the
+// feed-forward family's; the two share value_net_grad.h (the forward layer of a tile, the three backward products, the chains, the value
+// head, the sum, and the entries' host side: its templates over this file's LstmGrad).
 // OM-LSTM-RL (the *_lstm_om entries: cs_value_net_loss_grad_lstm_om, ...) is the same kernel on stored rows of cols + om_cols columns, a human's
 // map columns behind its rotated ones: network 1's LSTM or network 2's first mlp1 layer reads the wide row, nothing behind it changes.
 //
@@ -218,30 +219,7 @@ __global__ __launch_bounds__(NT) void k_vn_lstm_grad(LstmPlan q, LstmGradLds m, 
                 continue;
             }
             if (head) {
-                {   // the values, the loss terms and dV = 2 (V - target) / B as the top gradient [32][12] in D0
-                    const int last = p.n_layers - 1;
-                    const float* out = b.lds + m.v.act[last];
-                    const int ldo = m.v.ld[last];
-#pragma unroll 1
-                    for (int i = tid; i < 32 * ldo; i += NT) {
-                        const int k = i / ldo, cc = i - k * ldo;
-                        float d = 0.0f;
-                        if (cc == 0 && k < ng) {
-                            const float v = out[k * ldo];
-                            if (values) values[gbase + k] = 0.0f + v;
-                            d = v - targets[gbase + k];
-                            b.val[k] = d * d;
-                            d = 2.0f * d / (float)B;
-                        }
-                        b.D0[i] = d;
-                    }
-                    __syncthreads();
-                    if (tid == 0) {
-                        float s = 0.0f;
-                        for (int k = 0; k < ng; ++k) s += b.val[k];
-                        loss += s;
-                    }
-                }
+                VG_LOSS_HEAD(m.v, _Pragma("unroll 1"))
             } else {
                 const float* tp = tape + (long)t * TAPE * plane;
                 const float* tb = tape + (long)(t > 0 ? t - 1 : 0) * TAPE * plane;      // the step before (unused at t = 0)
@@ -301,11 +279,9 @@ __global__ void k_vn_pack_lstm(LstmPlan q, GradOffsets o, LstmGradOff og, const 
             const int j = i - G.b_off, cb = j >> 5, unit = cb * 8 + (j & 7), row = ((j & 31) >> 3) * q.H + unit;
             if (unit < q.H) v = params[og.bih + row] + params[og.bhh + row];
         } else {
-            const int e = i - G.w_off;
-            const int s = e & 3, lane = (e >> 2) & 63, qq = e >> 8;
-            const int kg = qq % G.kg_total, cb = qq / G.kg_total, j = lane & 31;
+            int cb, j, kg, kk;
+            blob_weight_of(G, i - G.w_off, cb, j, kg, kk);
             const int unit = cb * 8 + (j & 7), row = (j >> 3) * q.H + unit;
-            const int kk = kg * 8 + 4 * (lane >> 5) + s;
             if (unit < q.H) {
                 if (kg < G.kg_split) { if (kk < G.K1) v = params[og.whh + (long)row * G.K1 + kk]; }
                 else if (kk - G.kg_split * 8 < G.K2) v = params[og.wih + (long)row * G.K2 + kk - G.kg_split * 8];
@@ -314,18 +290,7 @@ __global__ void k_vn_pack_lstm(LstmPlan q, GradOffsets o, LstmGradOff og, const 
     } else {
         int l = 0;
         while (l + 1 < p.n_layers && i >= p.L[l + 1].w_off) ++l;
-        const VnLayer& L = p.L[l];
-        if (i >= L.b_off) {
-            const int j = i - L.b_off;
-            if (j < L.N) v = params[o.b[l] + j];
-        } else {
-            const int e = i - L.w_off;
-            const int s = e & 3, lane = (e >> 2) & 63, qq = e >> 8;
-            const int kg = qq % L.kg_total, cb = qq / L.kg_total;
-            const int j = cb * 32 + (lane & 31);
-            const int kk = kg * 8 + 4 * (lane >> 5) + s;
-            if (j < L.N && kk < L.K1) v = params[o.w[l] + (long)j * L.K1 + kk];
-        }
+        v = unpack_layer_at(p.L[l], i, params + o.w[l], params + o.b[l]);
     }
     blob[i] = v;
 }
@@ -348,214 +313,121 @@ inline void lstm_param_offsets(const LstmPlan& q, GradOffsets& o, LstmGradOff& o
     o.total = at;
 }
 
-// what the entries of this file check alike: the description, the shape of the minibatch; leaves the plan, the offsets, the map, the grid.
-// om, om_cols: build_lstm_plan's -- the map columns behind the rotated ones in a stored row (the *_lstm_om entries)
-struct LstmGradLaunch { LstmPlan q; GradOffsets o; LstmGradOff og; LstmGradLds m; int grid, region, gpart; size_t shmem; };
+// The recurrent family as value_net_grad.h's host templates ask it (GradCall: the call; om, om_cols: build_lstm_plan's -- the map columns
+// behind the rotated ones in a stored row, the *_lstm_om entries)
+struct LstmGrad {
+    struct Launch {
+        LstmPlan q; GradOffsets o; LstmGradOff og; LstmGradLds m; int grid, region, gpart; size_t shmem;
+        size_t blob_floats() const { return (size_t)q.v.total_floats; }
+    };
+    static constexpr const char *pack_entry = "cs_value_net_pack_lstm", *sizes_entry = "cs_value_net_grad_sizes_lstm",
+                                *loss_grad_entry = "cs_value_net_loss_grad_lstm";
 
-inline int plan_lstm_grad(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int B, int n, LstmGradLaunch& a)
-{
-    const int rc = build_lstm_plan(dims, n_dims, cols, a.q, om, om_cols);
-    if (rc != CS_OK) return rc;
-    if (B < 1) return fail(CS_ERR_ARG, "B must be positive");
-    if (n < 1) return fail(CS_ERR_ARG, "n must be at least 1: a value network needs a human to look at");
-    if (n > LSTM_MAX_N) return fail(CS_ERR_ARG, "cs_value_net_loss_grad_lstm takes at most 128 humans a sample (CS_VN_LSTM_MAX_N)");
-    if ((long)B * n > INT_MAX / 16) return fail(CS_ERR_ARG, "B * n is too large");
-    a.o = GradOffsets{};
-    a.og = LstmGradOff{};
-    lstm_param_offsets(a.q, a.o, a.og);
-    a.m = lstm_grad_lds_map(a.q);
-    a.shmem = (size_t)a.m.v.total * sizeof(float);
-    if (a.shmem > 160 * 1024)
-        return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(cols) + " + " + std::to_string(om_cols) +
-                                    " columns, H = " + std::to_string(a.q.H) + ": " + std::to_string(a.shmem) + " bytes) do not fit the 160 KiB of LDS");
-    const int jobs = (B + JROWS - 1) / JROWS;
-    a.grid = jobs < GRAD_MAX_GROUPS ? jobs : GRAD_MAX_GROUPS;
-    a.gpart = up(a.o.total + 1, 4);
-    a.region = a.gpart + n * TAPE * 32 * a.q.hpad;
-    return CS_OK;
-}
-
-inline int grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
-{
-    LstmGradLaunch a;
-    const int rc = plan_lstm_grad(dims, n_dims, cols, om, om_cols, B, n, a);
-    if (rc != CS_OK) return rc;
-    if (!n_param_floats || !n_scratch_floats) return fail(CS_ERR_ARG, "null argument");
-    *n_param_floats = (size_t)a.o.total;
-    *n_scratch_floats = (size_t)a.grid * a.region;
-    return CS_OK;
-}
-
-// the argument checks of the loss-and-gradient entries, which the train-step entries make first
-inline int check_lstm_grad_args(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
-                                size_t n_param_floats, int B, int n, int cols, bool om, int om_cols, const float* d_rows, const float* d_targets,
-                                const float* d_grad, const float* d_loss, const float* d_scratch, size_t n_scratch_floats, LstmGradLaunch& a)
-{
-    const int rc = plan_lstm_grad(dims, n_dims, cols, om, om_cols, B, n, a);
-    if (rc != CS_OK) return rc;
-    if (!d_weights || !d_params || !d_rows || !d_targets || !d_grad || !d_loss || !d_scratch) return fail(CS_ERR_ARG, "null argument");
-    if (n_weight_floats != (size_t)a.q.v.total_floats)
-        return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack_lstm)");
-    if (n_param_floats != (size_t)a.o.total)
-        return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
-    if (n_scratch_floats < (size_t)a.grid * a.region)
-        return fail(CS_ERR_ARG, "the scratch is too small for this minibatch (cs_value_net_grad_sizes_lstm)");
-    return CS_OK;
-}
-
-// the job kernel of the entries: every workgroup's partial gradient and loss term into its region of the scratch
-inline int launch_lstm_jobs(const LstmGradLaunch& a, const float* d_weights, const float* d_params, int B, int n, const float* d_rows,
-                            const float* d_targets, float* d_scratch, float* d_values, void* stream)
-{
-#define LSTM_GRAD_LAUNCH(M1)                                                                                                         \
-    {                                                                                                                                \
-        const int rc2 = grant_lds<k_vn_lstm_grad<M1>>(a.shmem);                                                                      \
-        if (rc2 != CS_OK) return rc2;                                                                                                \
-        hipLaunchKernelGGL((k_vn_lstm_grad<M1>), dim3(a.grid), dim3(NT), a.shmem, (hipStream_t)stream, a.q, a.m, a.o, a.og, d_weights, \
-                           d_params, B, n, d_rows, d_targets, d_scratch, a.region, a.gpart, d_values);                               \
-    }
-    if (a.q.v.c0[1] > 0) LSTM_GRAD_LAUNCH(true)
-    else LSTM_GRAD_LAUNCH(false)
-#undef LSTM_GRAD_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// k_vn_sgd's map of the recurrent blob: the Linear layers as the feed-forward blob holds them; the gates' rows in the order 8 * gate + unit
-// within a block of 8 units, weight_hh's columns before weight_ih's; bias_ih and bias_hh share one float, which bias_ih's thread writes
-struct LstmSgdMap {
-    LstmPlan q;
-    GradOffsets o;
-    LstmGradOff og;
-    __host__ __device__ int operator()(int i, int& twin) const
+    static int describe(const GradCall& c, Launch& a)
     {
-        twin = -1;
-        const int H = q.H;
-        const VnLayer& G = q.g;
-        if (i >= og.wih && i < og.bhh + 4 * H) {
-            if (i >= og.bhh) return -1;
-            int row, kk = -1;
-            if (i >= og.bih) {
-                row = i - og.bih;
-                twin = og.bhh + row;
-            } else if (i >= og.whh) {
-                row = (i - og.whh) / H;
-                kk = i - og.whh - row * H;
-            } else {
-                row = (i - og.wih) / q.xin;
-                kk = G.kg_split * 8 + i - og.wih - row * q.xin;
+        const int rc = build_lstm_plan(c.dims, c.n_dims, c.cols, a.q, c.om, c.om_cols);
+        if (rc != CS_OK) return rc;
+        a.o = GradOffsets{};
+        a.og = LstmGradOff{};
+        lstm_param_offsets(a.q, a.o, a.og);
+        return CS_OK;
+    }
+
+    static int check_n(const GradCall& c)
+    {
+        return c.n > LSTM_MAX_N ? fail(CS_ERR_ARG, std::string(loss_grad_entry) + " takes at most 128 humans a sample (CS_VN_LSTM_MAX_N)") : CS_OK;
+    }
+
+    static int plan(const GradCall& c, Launch& a)
+    {
+        a.m = lstm_grad_lds_map(a.q);
+        a.shmem = (size_t)a.m.v.total * sizeof(float);
+        if (a.shmem > 160 * 1024)
+            return fail(CS_ERR_ARG, "the activations and gradients of a tile of this network (rows of " + std::to_string(c.cols) + " + " +
+                                        std::to_string(c.om_cols) + " columns, H = " + std::to_string(a.q.H) + ": " + std::to_string(a.shmem) +
+                                        " bytes) do not fit the 160 KiB of LDS");
+        const int jobs = (c.B + JROWS - 1) / JROWS;
+        a.grid = jobs < GRAD_MAX_GROUPS ? jobs : GRAD_MAX_GROUPS;
+        a.gpart = up(a.o.total + 1, 4);
+        a.region = a.gpart + c.n * TAPE * 32 * a.q.hpad;
+        return CS_OK;
+    }
+
+    // the job kernel: every workgroup's partial gradient and loss term into its region of the scratch; network 2's build has mlp1 in its step loops
+    static int launch_jobs(const Launch& a, const GradCall& c)
+    {
+#define LSTM_GRAD_LAUNCH(M1)                                                                                                           \
+    {                                                                                                                                  \
+        const int rc2 = grant_lds<k_vn_lstm_grad<M1>>(a.shmem);                                                                        \
+        if (rc2 != CS_OK) return rc2;                                                                                                  \
+        hipLaunchKernelGGL((k_vn_lstm_grad<M1>), dim3(a.grid), dim3(NT), a.shmem, (hipStream_t)c.stream, a.q, a.m, a.o, a.og, c.d_weights, \
+                           c.d_params, c.B, c.n, c.d_rows, c.d_targets, c.d_scratch, a.region, a.gpart, c.d_values);                   \
+    }
+        if (a.q.v.c0[1] > 0) LSTM_GRAD_LAUNCH(true)
+        else LSTM_GRAD_LAUNCH(false)
+#undef LSTM_GRAD_LAUNCH
+        HIP_TRY(hipGetLastError());
+        return CS_OK;
+    }
+
+    // k_vn_sgd's map of the recurrent blob: the Linear layers as the feed-forward blob holds them; the gates' rows in the order 8 * gate + unit
+    // within a block of 8 units, weight_hh's columns before weight_ih's; bias_ih and bias_hh share one float, which bias_ih's thread writes
+    struct SgdMap {
+        LstmPlan q;
+        GradOffsets o;
+        LstmGradOff og;
+        __host__ __device__ int operator()(int i, int& twin) const
+        {
+            twin = -1;
+            const int H = q.H;
+            const VnLayer& G = q.g;
+            if (i >= og.wih && i < og.bhh + 4 * H) {
+                if (i >= og.bhh) return -1;
+                int row, kk = -1;
+                if (i >= og.bih) {
+                    row = i - og.bih;
+                    twin = og.bhh + row;
+                } else if (i >= og.whh) {
+                    row = (i - og.whh) / H;
+                    kk = i - og.whh - row * H;
+                } else {
+                    row = (i - og.wih) / q.xin;
+                    kk = G.kg_split * 8 + i - og.wih - row * q.xin;
+                }
+                const int gate = row / H, unit = row - gate * H;
+                const int cb = unit >> 3, col = 8 * gate + (unit & 7);
+                return kk < 0 ? G.b_off + cb * 32 + col : blob_weight_at(G, cb, col, kk);
             }
-            const int gate = row / H, unit = row - gate * H;
-            const int cb = unit >> 3, col = 8 * gate + (unit & 7);
-            return kk < 0 ? G.b_off + cb * 32 + col : blob_weight_at(G, cb, col, kk);
+            const VnPlan& p = q.v;
+            int l = 0;
+            while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
+            return blob_layer_at(p.L[l], i - o.w[l]);
         }
-        const VnPlan& p = q.v;
-        int l = 0;
-        while (l + 1 < p.n_layers && i >= o.w[l + 1]) ++l;
-        return blob_layer_at(p.L[l], i - o.w[l]);
+    };
+    static SgdMap sgd_map(const Launch& a) { return SgdMap{a.q, a.o, a.og}; }
+
+    static void launch_pack(const Launch& a, const GradCall& c)
+    {
+        hipLaunchKernelGGL(k_vn_pack_lstm, dim3((a.q.v.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)c.stream, a.q, a.o, a.og, c.d_params, c.d_weights);
     }
 };
 
-// cs_value_net_loss_grad_lstm[_om]
-inline int loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params, size_t n_param_floats,
-                          int B, int n, int cols, bool om, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
-                          float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
-{
-    LstmGradLaunch a;
-    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om, om_cols, d_rows, d_targets, d_grad,
-                                        d_loss, d_scratch, n_scratch_floats, a);
-    if (rc != CS_OK) return rc;
-    const int rc2 = launch_lstm_jobs(a, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
-    if (rc2 != CS_OK) return rc2;
-    hipLaunchKernelGGL(k_vn_grad_sum, dim3((a.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_scratch, a.region, a.grid, a.o.total, B,
-                       d_grad, d_loss);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// cs_value_net_train_step_lstm[_om]
-inline int train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params, size_t n_param_floats,
-                           float* d_momentum, size_t n_momentum_floats, float lr, float momentum, int B, int n, int cols, bool om, int om_cols,
-                           const float* d_rows, const float* d_targets, float* d_grad, float* d_loss, double* d_loss_sum, float* d_values,
-                           float* d_scratch, size_t n_scratch_floats, void* stream)
-{
-    LstmGradLaunch a;
-    const int rc = check_lstm_grad_args(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, om, om_cols, d_rows, d_targets, d_grad,
-                                        d_loss, d_scratch, n_scratch_floats, a);
-    if (rc != CS_OK) return rc;
-    const int rc1 = check_sgd_args(d_momentum, n_momentum_floats, n_param_floats, lr, momentum);
-    if (rc1 != CS_OK) return rc1;
-    const int rc2 = launch_lstm_jobs(a, d_weights, d_params, B, n, d_rows, d_targets, d_scratch, d_values, stream);
-    if (rc2 != CS_OK) return rc2;
-    hipLaunchKernelGGL(k_vn_sgd<LstmSgdMap>, dim3((a.o.total + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, LstmSgdMap{a.q, a.o, a.og},
-                       d_scratch, a.region, a.grid, a.o.total, B, lr, momentum, d_params, d_momentum, d_grad, d_weights, d_loss, d_loss_sum);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
-// what the blob-index and the device-pack entries do alike before their own part: the plan, the offsets, the size of the flat parameters
-inline int plan_lstm_flat(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, const void* a1, const void* a2, size_t n_param_floats,
-                          LstmPlan& q, GradOffsets& o, LstmGradOff& og)
-{
-    const int rc = build_lstm_plan(dims, n_dims, cols, q, om, om_cols);
-    if (rc != CS_OK) return rc;
-    o = GradOffsets{};
-    og = LstmGradOff{};
-    lstm_param_offsets(q, o, og);
-    if (!a1 || !a2) return fail(CS_ERR_ARG, "null argument");
-    if (n_param_floats != (size_t)o.total)
-        return fail(CS_ERR_ARG, "the flat parameters do not have the size of this network (cs_value_net_grad_sizes_lstm)");
-    return CS_OK;
-}
-
-// cs_value_net_blob_index_lstm[_om]
-inline int blob_index_lstm(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, int32_t* index, size_t n_param_floats)
-{
-    LstmPlan q;
-    GradOffsets o;
-    LstmGradOff og;
-    const int rc = plan_lstm_flat(dims, n_dims, cols, om, om_cols, index, index, n_param_floats, q, o, og);
-    if (rc != CS_OK) return rc;
-    const LstmSgdMap map{q, o, og};
-    for (int i = 0; i < o.total; ++i) {         // (bias_hh's thread writes nothing: its float is bias_ih's, which names it as its twin)
-        int twin;
-        const int at = map(i, twin);
-        if (at >= 0) index[i] = at;
-        if (twin >= 0) index[twin] = at;
-    }
-    return CS_OK;
-}
-
-// cs_value_net_pack_lstm[_om]_device
-inline int pack_lstm_device(const int32_t* dims, int n_dims, int cols, bool om, int om_cols, const float* d_params, size_t n_param_floats, float* d_blob,
-                            size_t n_blob_floats, void* stream)
-{
-    LstmPlan q;
-    GradOffsets o;
-    LstmGradOff og;
-    const int rc = plan_lstm_flat(dims, n_dims, cols, om, om_cols, d_params, d_blob, n_param_floats, q, o, og);
-    if (rc != CS_OK) return rc;
-    if (n_blob_floats != (size_t)q.v.total_floats)
-        return fail(CS_ERR_ARG, "the weight blob does not have the size of this network (cs_value_net_pack_lstm)");
-    hipLaunchKernelGGL(k_vn_pack_lstm, dim3((q.v.total_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, q, o, og, d_params, d_blob);
-    HIP_TRY(hipGetLastError());
-    return CS_OK;
-}
-
 } // namespace
 
-// ---- LSTM-RL on rows of 13 | 15 columns: the entries above with no map columns
+// ---- LSTM-RL on rows of 13 | 15 columns: no map columns (the entries of this file take no `kind`: 0)
 extern "C" int cs_value_net_grad_sizes_lstm(const int32_t* dims, int n_dims, int cols, int B, int n, size_t* n_param_floats, size_t* n_scratch_floats)
 {
-    return grad_sizes_lstm(dims, n_dims, cols, false, 0, B, n, n_param_floats, n_scratch_floats);
+    const GradCall c = describe_call(0, dims, n_dims, cols, false, 0, B, n);
+    return grad_sizes<LstmGrad>(c, n_param_floats, n_scratch_floats);
 }
 
 extern "C" int cs_value_net_loss_grad_lstm(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
                                            size_t n_param_floats, int B, int n, int cols, const float* d_rows, const float* d_targets, float* d_grad,
                                            float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return loss_grad_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, false, 0, d_rows, d_targets, d_grad, d_loss,
-                          d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, false, 0, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    return loss_grad<LstmGrad>(c);
 }
 
 extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
@@ -563,34 +435,40 @@ extern "C" int cs_value_net_train_step_lstm(const int32_t* dims, int n_dims, flo
                                             int n, int cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
                                             double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return train_step_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols,
-                           false, 0, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, false, 0, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    set_sgd(c, d_momentum, n_momentum_floats, lr, momentum, d_loss_sum);
+    return train_step<LstmGrad>(c);
 }
 
 extern "C" int cs_value_net_blob_index_lstm(const int32_t* dims, int n_dims, int cols, int32_t* index, size_t n_param_floats)
 {
-    return blob_index_lstm(dims, n_dims, cols, false, 0, index, n_param_floats);
+    return blob_index<LstmGrad>(describe_call(0, dims, n_dims, cols, false, 0), index, n_param_floats);
 }
 
 extern "C" int cs_value_net_pack_lstm_device(const int32_t* dims, int n_dims, int cols, const float* d_params, size_t n_param_floats, float* d_blob,
                                              size_t n_blob_floats, void* stream)
 {
-    return pack_lstm_device(dims, n_dims, cols, false, 0, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, false, 0);
+    set_pack(c, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    return pack_device<LstmGrad>(c);
 }
 
 // ---- OM-LSTM-RL: rows of cols + om_cols columns (build_lstm_plan refuses om_cols < 1)
 extern "C" int cs_value_net_grad_sizes_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int B, int n, size_t* n_param_floats,
                                                size_t* n_scratch_floats)
 {
-    return grad_sizes_lstm(dims, n_dims, cols, true, om_cols, B, n, n_param_floats, n_scratch_floats);
+    const GradCall c = describe_call(0, dims, n_dims, cols, true, om_cols, B, n);
+    return grad_sizes<LstmGrad>(c, n_param_floats, n_scratch_floats);
 }
 
 extern "C" int cs_value_net_loss_grad_lstm_om(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, const float* d_params,
                                               size_t n_param_floats, int B, int n, int cols, int om_cols, const float* d_rows, const float* d_targets,
                                               float* d_grad, float* d_loss, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return loss_grad_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, B, n, cols, true, om_cols, d_rows, d_targets, d_grad, d_loss,
-                          d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, true, om_cols, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    return loss_grad<LstmGrad>(c);
 }
 
 extern "C" int cs_value_net_train_step_lstm_om(const int32_t* dims, int n_dims, float* d_weights, size_t n_weight_floats, float* d_params,
@@ -598,17 +476,21 @@ extern "C" int cs_value_net_train_step_lstm_om(const int32_t* dims, int n_dims, 
                                                int n, int cols, int om_cols, const float* d_rows, const float* d_targets, float* d_grad, float* d_loss,
                                                double* d_loss_sum, float* d_values, float* d_scratch, size_t n_scratch_floats, void* stream)
 {
-    return train_step_lstm(dims, n_dims, d_weights, n_weight_floats, d_params, n_param_floats, d_momentum, n_momentum_floats, lr, momentum, B, n, cols,
-                           true, om_cols, d_rows, d_targets, d_grad, d_loss, d_loss_sum, d_values, d_scratch, n_scratch_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, true, om_cols, B, n);
+    set_minibatch(c, d_weights, n_weight_floats, d_params, n_param_floats, d_rows, d_targets, d_grad, d_loss, d_values, d_scratch, n_scratch_floats, stream);
+    set_sgd(c, d_momentum, n_momentum_floats, lr, momentum, d_loss_sum);
+    return train_step<LstmGrad>(c);
 }
 
 extern "C" int cs_value_net_blob_index_lstm_om(const int32_t* dims, int n_dims, int cols, int om_cols, int32_t* index, size_t n_param_floats)
 {
-    return blob_index_lstm(dims, n_dims, cols, true, om_cols, index, n_param_floats);
+    return blob_index<LstmGrad>(describe_call(0, dims, n_dims, cols, true, om_cols), index, n_param_floats);
 }
 
 extern "C" int cs_value_net_pack_lstm_om_device(const int32_t* dims, int n_dims, int cols, int om_cols, const float* d_params, size_t n_param_floats,
                                                 float* d_blob, size_t n_blob_floats, void* stream)
 {
-    return pack_lstm_device(dims, n_dims, cols, true, om_cols, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    GradCall c = describe_call(0, dims, n_dims, cols, true, om_cols);
+    set_pack(c, d_params, n_param_floats, d_blob, n_blob_floats, stream);
+    return pack_device<LstmGrad>(c);
 }
