@@ -888,6 +888,38 @@ int cs_value_net_decide_lstm_om(const int32_t* dims, int n_dims, const float* d_
                                 float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_lstm_om_bf16  cs_value_net_decide_lstm_om with the opt-in bf16 arithmetic (csrc/value_net_lstm_om_bf16.hip):
+ *   the same arguments, results, errors and messages -- om_cols < 1, cols + om_cols > 256, a null d_maps, map_order outside 0..1, the LDS-fit
+ *   refusal for this kernel's own LDS --, with the blob of cs_value_net_pack_lstm_om_bf16 and its length in bytes.  The first layer that
+ *   reads a row (network 1: weight_ih; network 2: mlp1's layer 0) is split by column: its cols rotated columns stay float32 (full weights,
+ *   unrounded inputs); its om_cols map columns are bf16 operands with float32 accumulation -- the weights [:, cols:] rounded to bf16, nearest
+ *   even, by the pack, a map value rounded once, nearest even, when it is staged, zeros up to a multiple of 16 columns.  mlp's layer 0 is
+ *   float32; weight_hh, network 2's weight_ih and every mlp1 / mlp layer behind the first are bf16 layers; the rounding points (h_t once a
+ *   step) and what is never rounded (c, the pre-activations, sigmoid, tanh, mlp's last output, the value) are
+ *   cs_value_net_decide_lstm_bf16's.  A first-layer pre-activation is one chain: the bias, the float32 k-groups of the rotated columns
+ *   ascending, the map k-steps of 16 ascending, for network 1's gates then weight_hh's k-steps ascending.  The order of a sequence's rows,
+ *   the map pairing, ties, NaN distances, d_override and the pick are cs_value_net_decide_lstm_om's: the arithmetic never touches the order.
+ *   A (world, action)'s value depends on its own rows and the map rows it reads: W = 1 gives the bits of any batch.  With all-zero map
+ *   weights and finite maps the values equal cs_value_net_decide_lstm_bf16's on the narrow network bit for bit.  No atomics.
+ * cs_value_net_pack_lstm_om_bf16  (host only) params as cs_value_net_pack_lstm_om takes them.  blob == NULL: only *n_bytes is set.  The
+ *   blob is zeroed, then written.  Layout: cs_value_net_pack_lstm_bf16's, piece for piece, with the one wider layer:
+ *     network 2's mlp1 layer 0   [ncb][2 + ksm][64 lanes] slots of 16 bytes, ksm = ceil(om_cols / 16): slot s < 2 holds 4 floats, element
+ *                       e = weight[32 b + (l & 31)][8 s + 4 (l >> 5) + e] for k < cols; slot s >= 2 holds 8 bf16, element e =
+ *                       weight[32 b + (l & 31)][cols + 16 (s - 2) + 8 (l >> 5) + e] for k < cols + om_cols; then float bias[32 ncb];
+ *     network 1's gates   [nb][ksh + 2 + ksm][64 lanes] slots: the ksh slots of weight_hh as in cs_value_net_pack_lstm_bf16; then 2 slots of
+ *                       4 floats, element e = weight_ih[row][8 (s - ksh) + 4 (l >> 5) + e] for k < cols; then ksm slots of 8 bf16, element e
+ *                       = weight_ih[row][cols + 16 (s - ksh - 2) + 8 (l >> 5) + e]; then float bias[32 nb] = bias_ih + bias_hh.
+ *   Network 2's gates and every other layer are cs_value_net_pack_lstm_bf16's.  A NaN weight becomes the quiet NaN 0x7fc0.
+ */
+int cs_value_net_pack_lstm_om_bf16(const int32_t* dims, int n_dims, int cols, int om_cols, const float* const* params, void* blob,
+                                   size_t* n_bytes);
+int cs_value_net_decide_lstm_om_bf16(const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n,
+                                     int cols, int om_cols, int sorted_by_distance, int map_order, const float* d_rotated,
+                                     const float* d_maps /* [W][n][om_cols] */, const float* d_rewards, const float* d_actions,
+                                     const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
+                                     float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * The optimisation step of the networks with occupancy-map columns, OM-SARL and OM-LSTM-RL (csrc/value_net_grad.hip,
  * csrc/value_net_lstm_grad.hip): every entry below is its sibling without `_om` -- the same kernels, launches, results,
  * determinism and errors -- with `int om_cols` behind `cols`, 1 <= om_cols and cols + om_cols <= 256.

@@ -157,6 +157,7 @@ class CADRL(Policy):
         self.decision_precision = "f32"
         self.decision_input = "tensor"
         self.recurrent_precision = "f32"         # (LSTM-RL's own choice, lstm_rl.py set_recurrent_precision; "f32" for every other policy)
+        self.mapped_precision = "f32"            # (OM-LSTM-RL's own choice, om_lstm_rl.py set_mapped_precision; "f32" for every other policy)
 
     # ------------------------------------------------------------------ configuration
     def configure(self, config):
@@ -216,6 +217,8 @@ class CADRL(Policy):
         self._net.refresh(self.decision_precision)
         if self.recurrent_precision != "f32":
             self._net.refresh_recurrent(self.recurrent_precision)
+        if self.mapped_precision != "f32":
+            self._net.refresh_mapped(self.mapped_precision)
         return self._net
 
     _STATE_NETS_KEPT = 4
@@ -293,7 +296,7 @@ class CADRL(Policy):
         stream = lambda: torch.cuda.current_stream().cuda_stream
         rot, _ = value_net.decide_for_worlds(net, self.decision_input, self.decision_precision, d_a, d_n, d_c, d_r, self.gamma, self.time_step,
                                              up(np.array([override]), torch.int32), vals, pick, act, stream(),
-                                             recurrent_precision=self.recurrent_precision)
+                                             recurrent_precision=self.recurrent_precision, mapped_precision=self.mapped_precision)
         # (SARL's attention weights read the last action's rows; without the look-ahead tensor they are made when asked for)
         self._last_rotated = rot if rot is not None else (lambda: value_net.lookahead(d_a[-1:].contiguous(), d_n, d_c, d_r, self.time_step, stream()))
         return vals[0].cpu().numpy(), int(pick.item()), act[0].cpu().numpy()

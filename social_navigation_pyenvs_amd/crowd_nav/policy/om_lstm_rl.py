@@ -14,8 +14,13 @@ map a step's row is paired with has two answers in the reference, and ``set_map_
   "own"        every human beside its own map: what ``transform`` (multi_human_rl.py:115-128) stores and a trainer evaluates, so what the
                network was trained on.
 
-``transform``, ``state_value`` and the Gym's ``value_device`` evaluate the rows in the humans' own order beside their own maps, whatever
-the map order.  It is a key of its own in policy_factory, "om_lstm_rl": ``policy_factory["lstm_rl_device"]`` with with_om = true keeps
+``set_mapped_precision("bf16")`` moves ``predict`` and the batched Gym's ``act_device`` to the opt-in bf16 arithmetic
+(cs_value_net_decide_lstm_om_bf16, csrc/value_net_lstm_om_bf16.hip): the map columns and what LSTM-RL's bf16 kernel runs in
+bf16, the rotated columns float32, the same order and pairing.  ``set_recurrent_precision("bf16")`` keeps refusing: that is the kernel
+without map columns.
+
+``transform``, ``state_value``, ``joint_state_device``, the Gym's ``value_device`` and the trainers stay float32 and evaluate the rows in
+the humans' own order beside their own maps, whatever the map order and the precision.  It is a key of its own in policy_factory, "om_lstm_rl": ``policy_factory["lstm_rl_device"]`` with with_om = true keeps
 raising."""
 from __future__ import annotations
 
@@ -65,6 +70,12 @@ class OMLstmRL(LstmRL):
         for net in [self._net] + list(self._state_nets):
             if net is not None:
                 net.map_order = map_order
+
+    def set_mapped_precision(self, precision):
+        """The arithmetic of the decision kernel on rows with map columns, for ``predict`` and ``act_device`` alike: "f32" (the default) or
+        the opt-in "bf16" (DESIGN.md 4.5).  ``decision_precision``, ``decision_input`` and ``recurrent_precision`` stay ("f32", "tensor",
+        "f32"); ``set_map_order`` keeps its meaning."""
+        self.mapped_precision = value_net.check_mapped_precision(precision, self.family)
 
     map_columns = OMSARL.map_columns
     input_dim = OMSARL.input_dim

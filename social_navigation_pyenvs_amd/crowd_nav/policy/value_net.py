@@ -26,7 +26,12 @@ OM-LSTM-RL (crowd_nav/policy/om_lstm_rl.py: lstm_rl.with_om = true) is the recur
 ``DeviceNet`` with ``om_cols`` > 0 packs through cs_value_net_pack_lstm_om and decides through cs_value_net_decide_lstm_om
 (``decide_lstm_om``), which takes the maps, sorted_by_distance and ``map_order`` -- which map a step's row is paired with: MAP_ORDERS'
 "reference" (the map at that place of action 0's order, what the reference's serial decision does) or "own" (every human beside its own map,
-what ``transform`` stores).
+what ``transform`` stores).  Its opt-in bf16 arithmetic (csrc/value_net_lstm_om_bf16.hip: the map columns and everything
+the narrow bf16 kernel runs in bf16, the rotated columns float32) again has names of its own, so that what ``set_recurrent_precision``,
+``set_decision_precision`` and ``pack`` refuse for such a net stays refused: MAPPED_PRECISIONS, ``pack_lstm_om_bf16``
+(cs_value_net_pack_lstm_om_bf16), ``decide_lstm_om_bf16`` (cs_value_net_decide_lstm_om_bf16), ``DeviceNet.refresh_mapped`` (a blob under the
+key MAPPED_RECURRENT_BF16, which only such a net has) and ``decide_for_worlds(..., mapped_precision="bf16")``; a policy chooses with
+``OMLstmRL.set_mapped_precision``.
 
 Which entries a network uses, with which arguments, and which modes it may run in is stated once, in the four rows of ``Family``
 (FEED_FORWARD, MAPPED, RECURRENT, RECURRENT_MAPPED); a ``DeviceNet`` holds its row, a policy class names its own, and ``pack``, ``decide_rows``,
@@ -65,6 +70,8 @@ PRECISIONS = ("f32", "bf16")
 DECISION_INPUTS = ("tensor", "fused")
 RECURRENT_PRECISIONS = ("f32", "bf16")      # of the recurrent family without map columns: "bf16" is cs_value_net_decide_lstm_bf16
 RECURRENT_BF16 = "recurrent_bf16"           # DeviceNet's key of that arithmetic's blob
+MAPPED_PRECISIONS = ("f32", "bf16")         # of the recurrent family with map columns: "bf16" is cs_value_net_decide_lstm_om_bf16
+MAPPED_RECURRENT_BF16 = "mapped_recurrent_bf16"     # the key of that arithmetic's blob, on a DeviceNet of family RECURRENT_MAPPED alone
 
 
 def check_precision(precision):
@@ -176,6 +183,18 @@ def check_recurrent_precision(precision, family=None):
     return precision
 
 
+def check_mapped_precision(precision, family=None):
+    """The arithmetic of the recurrent decision kernel on rows with map columns a policy may hold: one of MAPPED_PRECISIONS; "bf16" for
+    the recurrent family with map columns alone (`family`: the policy's or the net's row, None asks only the name)."""
+    if precision not in MAPPED_PRECISIONS:
+        raise ValueError(f"mapped precision {precision!r}: one of {', '.join(map(repr, MAPPED_PRECISIONS))}")
+    if precision == "bf16" and family is not None and family is not RECURRENT_MAPPED:
+        raise ValueError('mapped precision "bf16": cs_value_net_decide_lstm_om_bf16 is the kernel of OM-LSTM-RL, the recurrent network on rows '
+                         "with occupancy-map columns; LSTM-RL without map columns chooses with set_recurrent_precision, CADRL and SARL with "
+                         "set_decision_precision, OM-SARL decides in float32")
+    return precision
+
+
 def check_map_order(map_order):
     if map_order not in MAP_ORDERS:
         raise ValueError(f"map order {map_order!r}: one of {', '.join(map(repr, sorted(MAP_ORDERS, reverse=True)))}")
@@ -256,6 +275,15 @@ def pack_lstm_bf16(dims, cols, arrays):
     return _pack_with(_lib.load().cs_value_net_pack_lstm_bf16, np.uint8, (dims.ctypes.data, len(dims), cols), arrays)
 
 
+def pack_lstm_om_bf16(dims, cols, om_cols, arrays):
+    """cs_value_net_pack_lstm_om_bf16's blob (uint8 numpy: include/crowdstep.h states the bytes) of an OM-LSTM-RL network from the float32
+    arrays ``pack(CS_VN_LSTM, ..., om_cols=om_cols)`` takes.  Host only: no GPU needed."""
+    from ... import _lib
+
+    dims = np.ascontiguousarray(dims, np.int32)
+    return _pack_with(_lib.load().cs_value_net_pack_lstm_om_bf16, np.uint8, (dims.ctypes.data, len(dims), cols, om_cols), arrays)
+
+
 def _pack_with(entry, unit, lead, arrays):
     """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `lead`: the arguments
     it takes before the arrays."""
@@ -285,8 +313,11 @@ class DeviceNet:
         self.kind, self.dims, self.layers = describe(model)
         self.family = family_of(self.kind, self.om_cols)
         self.lstm = self.kind == CS_VN_LSTM
-        self._keys = dict.fromkeys(PRECISIONS + (RECURRENT_BF16,))       # (the recurrent bf16 blob under a key of its own: "bf16" stays
-        self.blobs = dict.fromkeys(PRECISIONS + (RECURRENT_BF16,))      # the feed-forward arithmetic's, which a recurrent net refuses)
+        # (the recurrent bf16 blob under a key of its own: "bf16" stays the feed-forward arithmetic's, which a recurrent net refuses; so has
+        # the one of the rows with map columns, a key that only a net of that family carries)
+        keys = PRECISIONS + (RECURRENT_BF16,) + ((MAPPED_RECURRENT_BF16,) if self.family is RECURRENT_MAPPED else ())
+        self._keys = dict.fromkeys(keys)
+        self.blobs = dict.fromkeys(keys)
         self.flat = None
 
     @property
@@ -325,6 +356,21 @@ class DeviceNet:
             self.blobs[RECURRENT_BF16] = torch.from_numpy(pack_lstm_bf16(self.dims, self.cols, arrays)).to("cuda")
             self._keys[RECURRENT_BF16] = key
         return self.blobs[RECURRENT_BF16]
+
+    def refresh_mapped(self, precision="f32"):
+        """``refresh`` for the arithmetics of the recurrent family with map columns (MAPPED_PRECISIONS): "f32" is ``refresh("f32")``; "bf16"
+        keeps cs_value_net_pack_lstm_om_bf16's blob under the key MAPPED_RECURRENT_BF16, rebuilt on the same version-counter rule and
+        dropped by ``updated_on_device``; it never aliases the float32 blob.  Every other family is refused with the reason."""
+        import torch
+
+        if check_mapped_precision(precision, self.family) == "f32":
+            return self.refresh("f32")
+        key = self._versions()
+        if key != self._keys[MAPPED_RECURRENT_BF16]:
+            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
+            self.blobs[MAPPED_RECURRENT_BF16] = torch.from_numpy(pack_lstm_om_bf16(self.dims, self.cols, self.om_cols, arrays)).to("cuda")
+            self._keys[MAPPED_RECURRENT_BF16] = key
+        return self.blobs[MAPPED_RECURRENT_BF16]
 
     def adopt_flat(self, flat, mapped=False):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
@@ -672,6 +718,22 @@ def decide_lstm_om(net, W, A, n, sorted_by_distance, rotated, maps, rewards, act
                 action_out, stream)
 
 
+def decide_lstm_om_bf16(net, W, A, n, sorted_by_distance, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values,
+                        choice, action_out, stream=None):
+    """cs_value_net_decide_lstm_om_bf16 on device pointers (ints): ``decide_lstm_om`` in the opt-in bf16 arithmetic, for a DeviceNet of an
+    OM-LSTM-RL network whose bf16 blob is current (``refresh_mapped("bf16")``); the pairing is ``net.map_order``."""
+    from ... import _lib
+
+    if net.family is not RECURRENT_MAPPED:
+        raise ValueError("decide_lstm_om_bf16: the network is not an LSTM-RL one with occupancy-map columns (DeviceNet(model, cols, om_cols))")
+    blob = net.blobs[MAPPED_RECURRENT_BF16]
+    if blob is None:
+        raise ValueError('decide_lstm_om_bf16: the network has no bf16 blob yet (DeviceNet.refresh_mapped("bf16"))')
+    _lib.check(_lib.load().cs_value_net_decide_lstm_om_bf16(*_head((), net.dims, blob), W, A, n, net.cols, net.om_cols, int(bool(sorted_by_distance)),
+                                                            MAP_ORDERS[net.map_order], rotated, maps, rewards, actions, robot, robot_stride, gamma, dt,
+                                                            override, values, choice, action_out, stream))
+
+
 def _extra_input(net, humans, vel_col, in_order, stream):
     """What ``decide_rows`` takes as `extra` for `net`: (the argument, the tensor behind it or None) -- the maps of `humans` [W, n, stride]
     for a family with maps (a launch), `in_order` as sorted_by_distance for a recurrent one, the pair for a family with both, nothing
@@ -776,16 +838,26 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 
 
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None,
-                      recurrent_precision="f32"):
+                      recurrent_precision="f32", mapped_precision="f32"):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
     decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order (with map columns: lookahead,
     occupancy_maps on the NEXT humans, decide_lstm_om in that order with the net's ``map_order``); a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
     branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
     "fused".  ``recurrent_precision`` "bf16" (an LSTM-RL net without map columns alone, whose ``refresh_recurrent("bf16")`` blob is current):
-    lookahead, then decide_lstm_bf16 in the decision's order."""
+    lookahead, then decide_lstm_bf16 in the decision's order.  ``mapped_precision`` "bf16" (an OM-LSTM-RL net alone, whose
+    ``refresh_mapped("bf16")`` blob is current): lookahead, occupancy_maps on the NEXT humans, decide_lstm_om_bf16 in that order with the
+    net's ``map_order``."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
+    if check_mapped_precision(mapped_precision, net.family) == "bf16":
+        check_mode(net.family, decision_input, precision)
+        check_recurrent_precision(recurrent_precision, net.family)
+        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
+        net.last_maps = maps = maps_of(nxt, 3 if cc == 7 else 2, net.om_grid, stream)
+        decide_lstm_om_bf16(net, W, A, n, 1, rot.data_ptr(), maps.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma,
+                            dt, ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return rot, rew
     if check_recurrent_precision(recurrent_precision, net.family) == "bf16":
         check_mode(net.family, decision_input, precision)
         rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)

@@ -1,5 +1,6 @@
 // value_net_lstm_kernel.h -- what LSTM-RL's decision kernels share beside their plan (value_net_lstm_plan.h): k_value_net_lstm and
-// k_value_net_lstm_om (value_net_lstm.hip, value_net_lstm_body.inc) and k_value_net_lstm_bf16 (value_net_lstm_bf16.hip).  Device: the layer
+// k_value_net_lstm_om (value_net_lstm.hip, value_net_lstm_body.inc), k_value_net_lstm_bf16 (value_net_lstm_bf16.hip) and
+// k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip).  Device: the layer
 // table in LDS, the order of a tile's rows, the ends of a job around its step loop (the step loops themselves differ by design and stay with
 // their kernels), the layer of 32 rows in its two arithmetics and the chain of layers.  Host: what a decide entry does between its plan and
 // its launch.  The gradient kernel (value_net_lstm_grad.hip) needs none of it: the one piece it shares with the step loop here, LSTM_KSTEP, is
@@ -139,8 +140,9 @@ __device__ __forceinline__ void lstm_layer(const int* lt, const float* __restric
 }
 
 // the arithmetic of a chain: float32 throughout; or the bf16 kernel's, whose first layer reads float32 rows and every later one bf16 rows --
-// mlp1, whose every output is a bf16 operand (the last one the gates'), and mlp, whose last output stays float32
-enum { LC_F32, LC_BF16_MLP1, LC_BF16_MLP };
+// mlp1, whose every output is a bf16 operand (the last one the gates'), and mlp, whose last output stays float32; or what lies behind an
+// mlp1 layer 0 that its kernel ran itself (the rows with map columns, value_net_lstm_om_bf16.hip): bf16 rows in, bf16 rows out
+enum { LC_F32, LC_BF16_MLP1, LC_BF16_MLP, LC_BF16_MLP1_REST };
 
 // layers [first, last) from `src`, a barrier behind each; outputs alternate P, Q, the last one goes to final_dst when given.  Returns where
 // the result is, out_ld its row stride.
@@ -154,7 +156,8 @@ __device__ __forceinline__ const float* lstm_chain(const int* ltab, int ld_pq, c
         const bool fin = l == last - 1, given = fin && final_dst;
         float* dst = given ? final_dst : (((l - first) & 1) ? Q : P);
         const int ldd = given ? final_ld : ld_pq;
-        lstm_layer(ltab + l * LT_STRIDE, wb, cur, cur_ld, dst, ldd, ARITH != LC_F32 && l != first, ARITH == LC_BF16_MLP1 || (ARITH == LC_BF16_MLP && !fin));
+        lstm_layer(ltab + l * LT_STRIDE, wb, cur, cur_ld, dst, ldd, ARITH != LC_F32 && (l != first || ARITH == LC_BF16_MLP1_REST),
+                   ARITH == LC_BF16_MLP1 || ARITH == LC_BF16_MLP1_REST || (ARITH == LC_BF16_MLP && !fin));
         __syncthreads();
         cur = dst;
         cur_ld = ldd;

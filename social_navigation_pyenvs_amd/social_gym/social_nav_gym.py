@@ -725,7 +725,8 @@ class BatchedSocialNavGym:
         LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
         (world, action)'s humans by decreasing distance inside the kernel (cs_value_net_decide_lstm_bf16 after the policy's
         ``set_recurrent_precision("bf16")``); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
-        the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order."""
+        the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order (cs_value_net_decide_lstm_om_bf16 after the
+        policy's ``set_mapped_precision("bf16")``)."""
         import torch
 
         dl = self._device_loop_state()
@@ -819,7 +820,7 @@ class BatchedSocialNavGym:
             nxt, cur_, rob = self._worlds_on_side_stream(dl, nxt)
             rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
                                                    explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream,
-                                                   recurrent_precision=pol.recurrent_precision)
+                                                   recurrent_precision=pol.recurrent_precision, mapped_precision=pol.mapped_precision)
             for t in (nxt, cur_, rob, rot, rew, explore):
                 if t is not None:
                     t.record_stream(side)

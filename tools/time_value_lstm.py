@@ -14,9 +14,13 @@ With --om the rows are OM-LSTM-RL's (lstm_rl.with_om = true: 48 map columns behi
 With --precision f32 bf16 only the recurrent kernel's arithmetics are timed: cs_value_net_decide_lstm and cs_value_net_decide_lstm_bf16
 (LstmRL.set_recurrent_precision) on the same tensors, ALTERNATED repetition by repetition in this one process, so that clocks and
 neighbours are the same for both; the line ends with the ratio of the medians and the share of worlds in which the two pick the same action.
+With --om --precision f32 bf16 it is OM-LSTM-RL's kernel instead: cs_value_net_decide_lstm_om and cs_value_net_decide_lstm_om_bf16
+(OMLstmRL.set_mapped_precision) alternated in the same way, once per pairing of rows and maps, the maps already in HBM; the line also says
+whether the bf16 median lies below the float32 median by more than the float32 runs' own min .. max spread.
 
 Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5]
         [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--precision f32 bf16] [--out profiles/lstm_rl_decision.txt]
+        python tools/time_value_lstm.py --om --precision f32 bf16 --network 1 --out profiles/om_lstm_rl_bf16_decision.txt   (then --network 2)
 With --only one variant runs alone, for a `rocprofv3 --kernel-trace --stats -- python tools/time_value_lstm.py --only lstm` run of its own.
 Times are per decision of all worlds: median, minimum and maximum over --reps repetitions, each between two device events.  The work per
 decision is counted from the shapes.  Without a GPU the script fails."""
@@ -144,6 +148,9 @@ def main():
         net.refresh()
     if args.precision and "bf16" in args.precision:
         nets["lstm"].refresh_recurrent("bf16")
+        for key, net in nets.items():
+            if key.startswith("om "):
+                net.refresh_mapped("bf16")
     stream = torch.cuda.current_stream().cuda_stream
     lines = [f"LSTM-RL decision, network {args.network}: {W} worlds x {A} actions, {args.reps} repetitions after {args.warmup} warm-up, ms per decision "
              f"of all worlds (median, min .. max); device {torch.cuda.get_device_name(0)}"]
@@ -202,6 +209,27 @@ def main():
             })
         macs, nbytes = work_per_decision(lstm.model, W, A, n, cols)
         lines.append(f"n = {n}: {macs / 1e9:.2f} G multiply-adds, {nbytes / 1e6:.0f} MB of look-ahead rows per decision")
+        if args.precision and args.om:
+            wmacs, _ = work_per_decision(wide.model, W, A, n, cols + C)
+            entries = {"f32": ("cs_value_net_decide_lstm_om", value_net.decide_lstm_om), "bf16": ("cs_value_net_decide_lstm_om_bf16", value_net.decide_lstm_om_bf16)}
+            for order in ("reference", "own"):
+                run = lambda entry: (lambda: entry(nets["om " + order], W, A, n, 1, *om_tail))
+                got = timed_alternated({p: run(entries[p][1]) for p in args.precision}, args.reps, args.warmup)
+                lines.append(f"  {cols} + {C} columns, the {order} pairing, {wmacs / 1e9:.2f} G multiply-adds")
+                picks = {}
+                for p in args.precision:
+                    med, lo, hi = got[p]
+                    lines.append(f"  {p:5s} {entries[p][0]:34s} {med:9.3f}  ({lo:.3f} .. {hi:.3f})  {2 * wmacs / med / 1e9:.1f} TFLOP/s")
+                    run(entries[p][1])()
+                    torch.cuda.synchronize()
+                    picks[p] = pick.clone()
+                if len(got) == 2:
+                    agree = float((picks["f32"] == picks["bf16"]).float().mean())
+                    (f_med, f_lo, f_hi), b_med = got["f32"], got["bf16"][0]
+                    lines.append(f"  f32 / bf16 = {f_med / b_med:.2f} in the medians; the bf16 median is {f_med - b_med:.3f} ms below the float32 one, whose runs "
+                                 f"spread over {f_hi - f_lo:.3f} ms: {'beyond' if f_med - b_med > f_hi - f_lo else 'WITHIN'} the spread; the two pick the same "
+                                 f"action in {100 * agree:.2f} % of the worlds")
+            continue
         if args.precision:
             entries = {"f32": ("cs_value_net_decide_lstm", value_net.decide_lstm), "bf16": ("cs_value_net_decide_lstm_bf16", value_net.decide_lstm_bf16)}
             run = lambda entry: (lambda: entry(nets["lstm"], W, A, n, 1, rot.data_ptr(), *tail))
