@@ -214,11 +214,7 @@ class CADRL(Policy):
         """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
         if self._net is None or self._net.model is not self.model:
             self._net = self._new_device_net(self.model)
-        self._net.refresh(self.decision_precision)
-        if self.recurrent_precision != "f32":
-            self._net.refresh_recurrent(self.recurrent_precision)
-        if self.mapped_precision != "f32":
-            self._net.refresh_mapped(self.mapped_precision)
+        self._net.refresh_selected(self.decision_precision, self.recurrent_precision, self.mapped_precision)
         return self._net
 
     _STATE_NETS_KEPT = 4

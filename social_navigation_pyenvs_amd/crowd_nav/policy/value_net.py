@@ -9,33 +9,21 @@ Two arithmetics: "f32", the default, and the opt-in "bf16" (cs_v
 own blob; a policy chooses with ``set_decision_precision``.  Two inputs: "tensor", the default (cs_lookahead's rows in HBM), and the opt-in
 "fused" (``decide_worlds``: cs_value_net_decide_worlds generates the rows in the kernel, float32 only); ``set_decision_input``.
 
-OM-SARL (crowd_nav/policy/om_sarl.py) widens every human's row by its occupancy map: a ``DeviceNet`` with ``om_cols`` > 0 packs through
-cs_value_net_pack_om, ``occupancy_maps`` is cs_occupancy_maps, ``decide_om`` cs_value_net_decide_om (csrc/value_net_om.hip), and
-``decide_for_worlds`` runs lookahead -> occupancy_maps(next humans) -> decide_om for such a net; float32 on the look-ahead tensor only.
-
-LSTM-RL (crowd_nav/policy/lstm_rl.py) has a kernel of its own (cs_value_net_decide_lstm, csrc/value_net_lstm.hip) and its own description:
-``describe`` answers CS_VN_LSTM -- a tag of this module, not a `kind` of the C entries --, such a ``DeviceNet`` packs through
-cs_value_net_pack_lstm, ``decide_lstm`` is the library call and ``decide_for_worlds`` runs lookahead -> decide_lstm(sorted_by_distance=1);
-``state_values_for_worlds`` evaluates the current state's rows in the humans' own order.  float32 on the look-ahead tensor, or -- under
-names of its own, so that what ``set_decision_precision``, ``check_decision_input`` and ``pack`` refuse stays refused -- the opt-in recurrent
-bf16 arithmetic (csrc/value_net_lstm_bf16.hip): RECURRENT_PRECISIONS, ``pack_lstm_bf16`` (cs_value_net_pack_lstm_bf16),
-``decide_lstm_bf16`` (cs_value_net_decide_lstm_bf16), ``DeviceNet.refresh_recurrent`` (a blob under a key of its own) and
-``decide_for_worlds(..., recurrent_precision="bf16")``; a policy chooses with ``LstmRL.set_recurrent_precision``.
-
-OM-LSTM-RL (crowd_nav/policy/om_lstm_rl.py: lstm_rl.with_om = true) is the recurrent network on rows widened by the maps: a CS_VN_LSTM
-``DeviceNet`` with ``om_cols`` > 0 packs through cs_value_net_pack_lstm_om and decides through cs_value_net_decide_lstm_om
-(``decide_lstm_om``), which takes the maps, sorted_by_distance and ``map_order`` -- which map a step's row is paired with: MAP_ORDERS'
-"reference" (the map at that place of action 0's order, what the reference's serial decision does) or "own" (every human beside its own map,
-what ``transform`` stores).  Its opt-in bf16 arithmetic (csrc/value_net_lstm_om_bf16.hip: the map columns and everything
-the narrow bf16 kernel runs in bf16, the rotated columns float32) again has names of its own, so that what ``set_recurrent_precision``,
-``set_decision_precision`` and ``pack`` refuse for such a net stays refused: MAPPED_PRECISIONS, ``pack_lstm_om_bf16``
-(cs_value_net_pack_lstm_om_bf16), ``decide_lstm_om_bf16`` (cs_value_net_decide_lstm_om_bf16), ``DeviceNet.refresh_mapped`` (a blob under the
-key MAPPED_RECURRENT_BF16, which only such a net has) and ``decide_for_worlds(..., mapped_precision="bf16")``; a policy chooses with
-``OMLstmRL.set_mapped_precision``.
-
 Which entries a network uses, with which arguments, and which modes it may run in is stated once, in the four rows of ``Family``
-(FEED_FORWARD, MAPPED, RECURRENT, RECURRENT_MAPPED); a ``DeviceNet`` holds its row, a policy class names its own, and ``pack``, ``decide_rows``,
-``decide_for_worlds``, ``state_values_for_worlds`` and ``check_mode`` ask it.
+(DESIGN.md 4.5): FEED_FORWARD (CADRL, SARL), MAPPED (OM-SARL: every human's row widened by its occupancy map, ``om_cols`` > 0), RECURRENT
+(LSTM-RL; ``describe`` answers CS_VN_LSTM -- a tag of this module, not a `kind` of the C entries) and RECURRENT_MAPPED (OM-LSTM-RL, whose
+entries also take ``map_order``, MAP_ORDERS: "reference" pairs a step's row with the map at that place of action 0's order, as the
+reference's serial decision does, "own" with its own map, as ``transform`` stores them).  A ``DeviceNet`` holds its row, a policy class
+names its own, and ``pack``, ``decide_rows``, ``decide_for_worlds``, ``state_values_for_worlds`` and ``check_mode`` ask it; ``decide_om``,
+``decide_lstm`` and ``decide_lstm_om`` are ``decide_rows`` for one family each.  A family with maps runs lookahead -> ``occupancy_maps``
+(cs_occupancy_maps, the next humans) -> its decide entry.
+
+The two recurrent rows also state an arithmetic of their own (``Family.own``, an ``OwnArithmetic``): the opt-in bf16 decision of
+csrc/value_net_lstm_bf16.hip and csrc/value_net_lstm_om_bf16.hip, under names apart from ``precision`` so that what ``set_decision_precision``,
+``check_decision_input`` and ``pack`` refuse for a recurrent net stays refused.  The row names the blob's key on a ``DeviceNet``
+(RECURRENT_BF16, MAPPED_RECURRENT_BF16), the pack and decide entries and the word of its names: ``check_<word>_precision``,
+``DeviceNet.refresh_<word>``, ``decide_for_worlds(..., <word>_precision="bf16")`` and a policy's ``set_<word>_precision`` (``LstmRL``: recurrent,
+``OMLstmRL``: mapped).  ``pack_lstm_bf16`` / ``pack_lstm_om_bf16`` and ``decide_lstm_bf16`` / ``decide_lstm_om_bf16`` are the public names.
 
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes;
@@ -91,6 +79,15 @@ MAPPED_GRADIENT_REFUSAL = ("{0}: the *_om helpers cover the networks with occupa
                            "without map columns has {1}")
 
 
+class OwnArithmetic(NamedTuple):
+    """A family's own opt-in arithmetic beside its ``modes`` (the recurrent families' bf16 decision)."""
+    key: str                # DeviceNet's key of its blob
+    pack: tuple             # (pack entry, what it counts its blob in)
+    decide: str             # the decide entry on the look-ahead tensor: the family's decide_int and takes_maps hold for it too
+    word: str               # what its names say: check_<word>_precision, DeviceNet.refresh_<word>, <word>_precision
+    no_blob: str            # the sentence a decision without a packed blob is refused with, behind the caller's name
+
+
 class Family(NamedTuple):
     """What one family of value networks states about itself; everything else in this module, the policies and the Gym ask a row of this
     table."""
@@ -107,6 +104,7 @@ class Family(NamedTuple):
     train_infix: str        # the training entries' infix: "" or "_lstm" (`_om`, and om_cols behind cols, follow from takes_maps)
     flat_rows: bool         # the training seams take rows [B, cols] as n = 1 (CADRL's stored states)
     train_refusal: str      # the sentence the family's training seams refuse every other net with ({0}: the caller, {1}: the helper to use)
+    own: OwnArithmetic = None       # the family's own opt-in arithmetic, where it has one
 
     def lead(self, kind):
         return (kind,) if self.takes_kind else ()
@@ -137,14 +135,18 @@ RECURRENT = Family(
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a recurrent network: LSTM-RL has the one kernel, float32 on the '
             'look-ahead tensor; it decides with "tensor" and "f32"',
-    min_humans=1, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=RECURRENT_GRADIENT_REFUSAL)
+    min_humans=1, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=RECURRENT_GRADIENT_REFUSAL,
+    own=OwnArithmetic(key=RECURRENT_BF16, pack=("cs_value_net_pack_lstm_bf16", np.uint8), decide="cs_value_net_decide_lstm_bf16", word="recurrent",
+                      no_blob='the network has no recurrent bf16 blob yet (DeviceNet.refresh_recurrent("bf16"))'))
 RECURRENT_MAPPED = Family(
     pack=frozen({"f32": ("cs_value_net_pack_lstm_om", np.float32)}), takes_kind=False,
     decide=frozen({"f32": "cs_value_net_decide_lstm_om"}), decide_int="om_cols sorted_by_distance map_order", takes_maps=True,
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a recurrent network with occupancy-map columns: OM-LSTM-RL has the one '
             'kernel, float32 on the look-ahead tensor and the maps; it decides with "tensor" and "f32"',
-    min_humans=2, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL)
+    min_humans=2, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL,
+    own=OwnArithmetic(key=MAPPED_RECURRENT_BF16, pack=("cs_value_net_pack_lstm_om_bf16", np.uint8), decide="cs_value_net_decide_lstm_om_bf16",
+                      word="mapped", no_blob='the network has no bf16 blob yet (DeviceNet.refresh_mapped("bf16"))'))
 
 
 def family_of(kind, om_cols=0):
@@ -256,39 +258,31 @@ def pack(kind, dims, cols, arrays, precision="f32", om_cols=0):
     of cs_value_net_pack_bf16's layout for "bf16"; with ``om_cols`` > 0 cs_value_net_pack_om's (float32 only: mlp1 reads cols + om_cols
     columns); for CS_VN_LSTM cs_value_net_pack_lstm's (float32 only; the LSTM's four arrays between mlp1's and mlp's), with ``om_cols`` > 0
     cs_value_net_pack_lstm_om's.  Host only: no GPU needed."""
-    from ... import _lib
-
     family = family_of(kind, om_cols)
     check_mode(family, "tensor", precision)
-    entry, unit = family.pack[check_precision(precision)]
-    dims = np.ascontiguousarray(dims, np.int32)
-    lead = family.lead(kind) + (dims.ctypes.data, len(dims), cols) + ((om_cols,) if family.takes_maps else ())
-    return _pack_with(getattr(_lib.load(), entry), unit, lead, arrays)
+    return _pack_with(family, kind, family.pack[check_precision(precision)], dims, cols, om_cols, arrays)
 
 
 def pack_lstm_bf16(dims, cols, arrays):
     """cs_value_net_pack_lstm_bf16's blob (uint8 numpy: include/crowdstep.h states the bytes) of an LSTM-RL network without map columns from
     the float32 arrays ``pack(CS_VN_LSTM, ...)`` takes.  Host only: no GPU needed."""
-    from ... import _lib
-
-    dims = np.ascontiguousarray(dims, np.int32)
-    return _pack_with(_lib.load().cs_value_net_pack_lstm_bf16, np.uint8, (dims.ctypes.data, len(dims), cols), arrays)
+    return _pack_with(RECURRENT, CS_VN_LSTM, RECURRENT.own.pack, dims, cols, 0, arrays)
 
 
 def pack_lstm_om_bf16(dims, cols, om_cols, arrays):
     """cs_value_net_pack_lstm_om_bf16's blob (uint8 numpy: include/crowdstep.h states the bytes) of an OM-LSTM-RL network from the float32
     arrays ``pack(CS_VN_LSTM, ..., om_cols=om_cols)`` takes.  Host only: no GPU needed."""
+    return _pack_with(RECURRENT_MAPPED, CS_VN_LSTM, RECURRENT_MAPPED.own.pack, dims, cols, om_cols, arrays)
+
+
+def _pack_with(family, kind, entry_and_unit, dims, cols, om_cols, arrays):
+    """The size query and the packing call of one of `family`'s pack entries: (its name, what it counts its blob in), from the row's
+    ``pack`` or its ``own``."""
     from ... import _lib
 
+    entry, unit = getattr(_lib.load(), entry_and_unit[0]), entry_and_unit[1]
     dims = np.ascontiguousarray(dims, np.int32)
-    return _pack_with(_lib.load().cs_value_net_pack_lstm_om_bf16, np.uint8, (dims.ctypes.data, len(dims), cols, om_cols), arrays)
-
-
-def _pack_with(entry, unit, lead, arrays):
-    """The size query and the packing call of one of the pack entries; `unit`: what the entry counts its blob in; `lead`: the arguments
-    it takes before the arrays."""
-    from ... import _lib
-
+    lead = family.lead(kind) + (dims.ctypes.data, len(dims), cols) + ((om_cols,) if family.takes_maps else ())
     arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
     ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
     nf = C.c_size_t(0)
@@ -313,9 +307,9 @@ class DeviceNet:
         self.kind, self.dims, self.layers = describe(model)
         self.family = family_of(self.kind, self.om_cols)
         self.lstm = self.kind == CS_VN_LSTM
-        # (the recurrent bf16 blob under a key of its own: "bf16" stays the feed-forward arithmetic's, which a recurrent net refuses; so has
-        # the one of the rows with map columns, a key that only a net of that family carries)
-        keys = PRECISIONS + (RECURRENT_BF16,) + ((MAPPED_RECURRENT_BF16,) if self.family is RECURRENT_MAPPED else ())
+        # (an own arithmetic's blob lies under the key its row states: "bf16" stays the feed-forward arithmetic's, which a recurrent net
+        # refuses.  RECURRENT's key is on every net, as it was before the table stated it; any other row's on a net of that family alone)
+        keys = PRECISIONS + (RECURRENT.own.key,) + ((self.family.own.key,) if self.family.own else ())
         self._keys = dict.fromkeys(keys)
         self.blobs = dict.fromkeys(keys)
         self.flat = None
@@ -327,50 +321,51 @@ class DeviceNet:
     def _versions(self):
         return tuple((p.data_ptr(), p._version) for l in self.layers for p in layer_params(l))
 
-    def refresh(self, precision="f32"):
+    def _repacked(self, key, entry_and_unit):
+        """The blob under `key`, packed again through that entry of the family when a parameter's version changed."""
         import torch
 
-        key = self._versions()
+        versions = self._versions()
+        if versions != self._keys[key]:
+            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
+            blob = _pack_with(self.family, self.kind, entry_and_unit, self.dims, self.cols, self.om_cols, arrays)
+            self.blobs[key] = torch.from_numpy(blob).to("cuda")
+            self._keys[key] = versions
+        return self.blobs[key]
+
+    def refresh(self, precision="f32"):
         if self.flat is not None and precision == "f32":        # the parameters are views of `flat` (adopt_flat): packed where they lie
+            key = self._versions()
             if key != self._keys[precision]:
                 _pack_on_device(self, self.flat)
                 self._keys[precision] = key
             return self.blobs[precision]
-        if key != self._keys[check_precision(precision)]:
-            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
-            self.blobs[precision] = torch.from_numpy(pack(self.kind, self.dims, self.cols, arrays, precision, self.om_cols)).to("cuda")
-            self._keys[precision] = key
-        return self.blobs[precision]
+        check_mode(self.family, "tensor", check_precision(precision))
+        return self._repacked(precision, self.family.pack[precision])
 
     def refresh_recurrent(self, precision="f32"):
         """``refresh`` for the recurrent family's own arithmetics (RECURRENT_PRECISIONS): "f32" is ``refresh("f32")``; "bf16" keeps
         cs_value_net_pack_lstm_bf16's blob under the key RECURRENT_BF16, rebuilt on the same version-counter rule and dropped by
         ``updated_on_device``; it never aliases the float32 blob."""
-        import torch
-
         if check_recurrent_precision(precision, self.family) == "f32":
             return self.refresh("f32")
-        key = self._versions()
-        if key != self._keys[RECURRENT_BF16]:
-            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
-            self.blobs[RECURRENT_BF16] = torch.from_numpy(pack_lstm_bf16(self.dims, self.cols, arrays)).to("cuda")
-            self._keys[RECURRENT_BF16] = key
-        return self.blobs[RECURRENT_BF16]
+        return self._repacked(self.family.own.key, self.family.own.pack)
 
     def refresh_mapped(self, precision="f32"):
         """``refresh`` for the arithmetics of the recurrent family with map columns (MAPPED_PRECISIONS): "f32" is ``refresh("f32")``; "bf16"
         keeps cs_value_net_pack_lstm_om_bf16's blob under the key MAPPED_RECURRENT_BF16, rebuilt on the same version-counter rule and
         dropped by ``updated_on_device``; it never aliases the float32 blob.  Every other family is refused with the reason."""
-        import torch
-
         if check_mapped_precision(precision, self.family) == "f32":
             return self.refresh("f32")
-        key = self._versions()
-        if key != self._keys[MAPPED_RECURRENT_BF16]:
-            arrays = [p.detach().to("cpu", torch.float32).numpy() for l in self.layers for p in layer_params(l)]
-            self.blobs[MAPPED_RECURRENT_BF16] = torch.from_numpy(pack_lstm_om_bf16(self.dims, self.cols, self.om_cols, arrays)).to("cuda")
-            self._keys[MAPPED_RECURRENT_BF16] = key
-        return self.blobs[MAPPED_RECURRENT_BF16]
+        return self._repacked(self.family.own.key, self.family.own.pack)
+
+    def refresh_selected(self, decision_precision, recurrent_precision, mapped_precision):
+        """What a policy's three attributes select: the blob of ``decision_precision`` and, where the others are not "f32", the family's own."""
+        self.refresh(decision_precision)
+        if recurrent_precision != "f32":
+            self.refresh_recurrent(recurrent_precision)
+        if mapped_precision != "f32":
+            self.refresh_mapped(mapped_precision)
 
     def adopt_flat(self, flat, mapped=False):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
@@ -629,21 +624,27 @@ def blob_index_om(net):
     return _blob_index(_mapped(net, "blob_index_om", "cs_value_net_blob_index / cs_value_net_blob_index_lstm"))
 
 
-def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32"):
+def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32", own=False):
     """The tensor decide entry of `net`'s family on device pointers (ints).  `extra`: what that entry takes beyond
     cs_value_net_decide's arguments -- the maps [W][n][net.om_cols], or sorted_by_distance, or the pair (maps, sorted_by_distance) for a
     family that takes both (``net.map_order`` goes with them); `tail`: rewards, actions, robot, robot_stride, gamma, dt, override, values,
-    choice, action_out, stream."""
+    choice, action_out, stream.  `own`: the family's own arithmetic (``Family.own``) -- its entry on its blob, the same arguments."""
     from ... import _lib
 
     family = net.family
-    head = net.head(family.decide["f32"].removeprefix("cs_value_net_"), precision)
+    if own:
+        entry, blob = family.own.decide, net.blobs[family.own.key]
+        if blob is None:
+            raise ValueError(f"{entry.removeprefix('cs_value_net_')}: {family.own.no_blob}")
+        head = _head((), net.dims, blob)
+    else:
+        entry, head = family.decide[precision], net.head(family.decide["f32"].removeprefix("cs_value_net_"), precision)
     both = "sorted_by_distance" in family.decide_int and family.takes_maps
     maps, in_order = extra if both else (extra, extra)
     given = {"om_cols": lambda: net.om_cols, "sorted_by_distance": lambda: int(bool(in_order)), "map_order": lambda: MAP_ORDERS[net.map_order]}
     behind_cols = tuple(given[name]() for name in family.decide_int.split())
     behind_rotated = (maps,) if family.takes_maps else ()
-    _lib.check(getattr(_lib.load(), family.decide[precision])(*head, W, A, n, net.cols, *behind_cols, rotated, *behind_rotated, *tail))
+    _lib.check(getattr(_lib.load(), entry)(*head, W, A, n, net.cols, *behind_cols, rotated, *behind_rotated, *tail))
 
 
 def decide(net, W, A, n, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None,
@@ -697,15 +698,10 @@ def decide_lstm_bf16(net, W, A, n, sorted_by_distance, rotated, rewards, actions
                      action_out, stream=None):
     """cs_value_net_decide_lstm_bf16 on device pointers (ints): ``decide_lstm`` in the opt-in bf16 arithmetic, for a DeviceNet of an LSTM-RL
     network without map columns whose recurrent bf16 blob is current (``refresh_recurrent("bf16")``)."""
-    from ... import _lib
-
     if net.family is not RECURRENT:
         raise ValueError("decide_lstm_bf16: the network is not an LSTM-RL one without map columns (lstm_rl.ValueNetwork1 / ValueNetwork2)")
-    blob = net.blobs[RECURRENT_BF16]
-    if blob is None:
-        raise ValueError('decide_lstm_bf16: the network has no recurrent bf16 blob yet (DeviceNet.refresh_recurrent("bf16"))')
-    _lib.check(_lib.load().cs_value_net_decide_lstm_bf16(*_head((), net.dims, blob), W, A, n, net.cols, int(bool(sorted_by_distance)), rotated, rewards,
-                                                         actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream))
+    decide_rows(net, W, A, n, rotated, sorted_by_distance, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                action_out, stream, own=True)
 
 
 def decide_lstm_om(net, W, A, n, sorted_by_distance, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
@@ -722,16 +718,10 @@ def decide_lstm_om_bf16(net, W, A, n, sorted_by_distance, rotated, maps, rewards
                         choice, action_out, stream=None):
     """cs_value_net_decide_lstm_om_bf16 on device pointers (ints): ``decide_lstm_om`` in the opt-in bf16 arithmetic, for a DeviceNet of an
     OM-LSTM-RL network whose bf16 blob is current (``refresh_mapped("bf16")``); the pairing is ``net.map_order``."""
-    from ... import _lib
-
     if net.family is not RECURRENT_MAPPED:
         raise ValueError("decide_lstm_om_bf16: the network is not an LSTM-RL one with occupancy-map columns (DeviceNet(model, cols, om_cols))")
-    blob = net.blobs[MAPPED_RECURRENT_BF16]
-    if blob is None:
-        raise ValueError('decide_lstm_om_bf16: the network has no bf16 blob yet (DeviceNet.refresh_mapped("bf16"))')
-    _lib.check(_lib.load().cs_value_net_decide_lstm_om_bf16(*_head((), net.dims, blob), W, A, n, net.cols, net.om_cols, int(bool(sorted_by_distance)),
-                                                            MAP_ORDERS[net.map_order], rotated, maps, rewards, actions, robot, robot_stride, gamma, dt,
-                                                            override, values, choice, action_out, stream))
+    decide_rows(net, W, A, n, rotated, (maps, sorted_by_distance), rewards, actions, robot, robot_stride, gamma, dt, override, values, choice,
+                action_out, stream, own=True)
 
 
 def _extra_input(net, humans, vel_col, in_order, stream):
@@ -841,29 +831,19 @@ def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gam
                       recurrent_precision="f32", mapped_precision="f32"):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
-    decide with `precision`; an LSTM-RL net runs lookahead and decide_lstm in the decision's order (with map columns: lookahead,
-    occupancy_maps on the NEXT humans, decide_lstm_om in that order with the net's ``map_order``); a net with map columns runs lookahead, occupancy_maps on the NEXT humans -- the maps the reference's serial
-    branch builds, once per decision -- and decide_om, and keeps the maps in ``net.last_maps``.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for
-    "fused".  ``recurrent_precision`` "bf16" (an LSTM-RL net without map columns alone, whose ``refresh_recurrent("bf16")`` blob is current):
-    lookahead, then decide_lstm_bf16 in the decision's order.  ``mapped_precision`` "bf16" (an OM-LSTM-RL net alone, whose
-    ``refresh_mapped("bf16")`` blob is current): lookahead, occupancy_maps on the NEXT humans, decide_lstm_om_bf16 in that order with the
-    net's ``map_order``."""
+    the family's decide entry with `precision` -- a recurrent net in the decision's order; a net with map columns on occupancy_maps of the
+    NEXT humans (the maps the reference's serial branch builds, once per decision; with the net's ``map_order``), which it keeps in
+    ``net.last_maps``.  ``recurrent_precision`` / ``mapped_precision`` "bf16" (the net of that family alone, whose ``refresh_recurrent`` /
+    ``refresh_mapped("bf16")`` blob is current): the same sequence with the family's own arithmetic.  Returns (rotated, rewards), the
+    look-ahead tensors it allocated and the launches read -- (None, None) for "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
-    if check_mapped_precision(mapped_precision, net.family) == "bf16":
+    # (the order of these checks is which refusal a caller with several bad arguments sees: the mapped precision; with it "bf16" the mode in
+    # front of the recurrent precision, else behind it)
+    own = check_mapped_precision(mapped_precision, net.family) == "bf16"
+    if own:
         check_mode(net.family, decision_input, precision)
-        check_recurrent_precision(recurrent_precision, net.family)
-        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
-        net.last_maps = maps = maps_of(nxt, 3 if cc == 7 else 2, net.om_grid, stream)
-        decide_lstm_om_bf16(net, W, A, n, 1, rot.data_ptr(), maps.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma,
-                            dt, ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
-        return rot, rew
-    if check_recurrent_precision(recurrent_precision, net.family) == "bf16":
-        check_mode(net.family, decision_input, precision)
-        rot, rew = lookahead(acts, nxt, cur, robot, dt, stream)
-        decide_lstm_bf16(net, W, A, n, 1, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
-                         values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
-        return rot, rew
+    own = check_recurrent_precision(recurrent_precision, net.family) == "bf16" or own
     if check_mode(net.family, decision_input, precision) == "fused":      # one library call on the worlds' own rows
         decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
                       None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
@@ -873,5 +853,5 @@ def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gam
     if maps is not None:
         net.last_maps = maps
     decide_rows(net, W, A, n, rot.data_ptr(), extra, rew.data_ptr(), acts.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt,
-                ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream, precision=precision)
+                ovr, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream, precision=precision, own=own)
     return rot, rew

@@ -1,9 +1,50 @@
-// value_net_lstm_bf16.h -- what the two recurrent decision kernels with the opt-in bf16 arithmetic share beside value_net_lstm_kernel.h:
-// k_value_net_lstm_bf16 (value_net_lstm_bf16.hip, rows of 13 | 15 columns) and k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip, the
-// rows widened by occupancy-map columns).  Host: the plan's changes, the pack of the gates and of a whole blob.  Device: one slot of W_hh
-// on the rounded h, one of the narrow x part, the pointwise part.  Each kernel keeps its LDS map, its step loop and its entries.
-// om_cols = 0 everywhere below is the narrow network, whose plan and blob are what they were before there were map columns here.
-// Unnamed namespace: each translation unit gets its own copy.
+// value_net_lstm_bf16.h -- the opt-in bf16 arithmetic of the recurrent decision, beside value_net_lstm_kernel.h: what k_value_net_lstm_bf16
+// (value_net_lstm_bf16.hip, rows of 13 | 15 columns; LstmRL.set_recurrent_precision("bf16")) and k_value_net_lstm_om_bf16
+// (value_net_lstm_om_bf16.hip, the rows widened by om_cols occupancy-map columns; OMLstmRL.set_mapped_precision("bf16")) have in common.  The
+// kernel text is value_net_lstm_bf16_body.inc, included by each file; here are the host's side -- the plan's changes, the pack of the gates
+// and of a whole blob, the LDS map, a decide entry behind its name -- and the device's small pieces: one slot of W_hh on the rounded h, one
+// of the narrow x part, the pointwise part.  om_cols = 0 everywhere below is the narrow network, whose plan and blob are what they were before
+// there were map columns here.  Unnamed namespace: each translation unit gets its own copy.
+//
+// The tiling is k_value_net_lstm's (value_net_lstm.hip) -- a workgroup of 4 wavefronts owns 32 sequences, the order of a sequence's rows is
+// ranked in LDS on the float32 distances before any rounding, the gates are the TRANSPOSED product (A = the gate weights, rows 8 * gate + unit
+// of a block of 8 hidden units; B = the sequences' operand rows from LDS), wavefront w owns the blocks w, w + 4, ..., a lane holds i, f, g, o
+// of four units of one sequence, c stays in registers for all n steps -- and so are the sort, sorted_by_distance, the map pairing, the value
+// and the pick (value_net_pick.h).
+//
+// The arithmetic, said here for both kernels:
+//   float32 layers   the 13 | 15 rotated columns of the first layer that reads a row -- network 1's W_ih, network 2's mlp1 layer 0 -- and layer 0
+//                    of mlp (it reads the raw self state): full weights, unrounded inputs, v_mfma_f32_32x32x2_f32.  Columns reach 10 m, where
+//                    one bf16 step is 3 cm.
+//   bf16 layers      W_hh in both networks, network 2's W_ih (it reads mlp1's output), every mlp1 / mlp layer behind the first, and the map
+//                    columns [:, cols:] of the first layer that reads a row: weights rounded to bf16 (nearest even) at pack time, float32
+//                    biases, float32 accumulation, v_mfma_f32_32x32x16_bf16.
+//   rounding points  each value once, nearest even, when it is stored as a bf16 operand: h_t after o * tanh(c) -- that one rounded value is
+//                    the next step's operand and what mlp reads as h_n --; an mlp1 / mlp activation after the bias and the ReLU when a bf16
+//                    layer reads it; mlp1's last output (no ReLU) as the gates' operand of network 2; a map value when the gather stages it
+//                    (an occupancy is 0 or 1, a mean velocity a few m/s), zeros up to a multiple of 16 columns.
+//   never rounded    c, the gate pre-activations, sigmoid and tanh (lstm_sigmoid, lstm_tanh), mlp's last output, rewards + gamma^(dt v_pref) V.
+//   order            a gate pre-activation is one fixed chain: b_ih + b_hh (summed in float32 by the pack), the x part (network 1: the
+//                    float32 k-groups of the rotated columns ascending, then the map k-steps of 16 ascending; network 2: W_ih's k-steps of
+//                    16 ascending), then W_hh's k-steps of 16 ascending.  Network 2's mlp1 layer 0 on rows with maps: the bias, the float32
+//                    k-groups, the map k-steps.  With all-zero map weights and finite maps the map k-steps add exact zeros: the values are
+//                    the narrow kernel's on the narrow network, bit for bit.
+// The x part does not depend on h: the register-resident build issues it before the barrier that publishes h_{t-1}, so that only W_hh's
+// k-steps and the pointwise part lie between two barriers.  Hidden units beyond H are stored as exact 0.  A sequence's value depends on its
+// own rows and the map rows it reads: the same bits for W = 1 as inside any batch, at any position of a tile.  No atomics, no inline
+// assembly.  gfx950 only.
+//
+// Register-resident weights (<true, .>): a block holds RKH slots of W_hh and RKX of the x part; network 1 with map columns holds the x part's
+// KGF float32 slots and RKM = 3 map k-steps (om_cols <= 48, the reference's 4 x 4 x 3 maps), 9 slots x 2 blocks = 72 VGPRs -- they stay
+// resident because the x part is what this arithmetic shortens, and reading the slots from the blob would put a global load in front of
+// every map k-step of every step.  A fourth resident k-step fills the 256 VGPRs of two workgroups a CU and spills (8 bytes of scratch):
+// wider maps read the gates from the blob.  Network 2's map weights belong to mlp1's first layer, which reads its weights from the blob as
+// every layer does (lstm_layer's one-deep prefetch); its gates are the narrow kernel's.  DESIGN.md 4.5 has the compiler's figures.
+//
+// LDS image of a bf16 operand (value_net_bf16.hip's): row-major bfloat16, a row of 16 * odd bytes (a stride of 4 * odd floats); lane l reads
+// the 8 k at 16 s + 8 (l >> 5) of row l & 31 with one ds_read_b128, conflict-free.  h: [2][32] rows of ceil(H / 16) * 16 bf16 (+ 8 bytes
+// of pitch), double-buffered; network 2's gate input: [32] rows of mlp1's last width rounded up to 32; the map columns: MB [2][32] rows of
+// ceil(om_cols / 16) * 16 bf16 (+ 8 bytes of pitch), double-buffered beside the gather tile G of the rotated columns.
 #pragma once
 #include "value_net_lstm_kernel.h"
 
@@ -13,6 +54,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RKH = 4, RKX = 4;            // register-resident gate weights: 16-byte lane slots of W_hh and of the x part a block (RB blocks a wavefront)
 constexpr int KGF = 2;                     // float32 k-groups of 8 of a rotated row: 13 | 15 columns
+constexpr int RKM = 3;                     // register-resident map k-steps of 16 a block (network 1): the reference's 48 map columns
 
 // the float32 plan and what this arithmetic changes: ksh k-steps of 16 of W_hh; ksx slots of the x part (network 1: float32 k-groups of 8 of
 // W_ih's rotated columns, then k-steps of 16 of its map columns; network 2: k-steps of 16); the strides (floats) of the h rows and of
@@ -190,6 +232,82 @@ __device__ __forceinline__ void lh_pointwise(const f32x16& acc, float (&c)[4], i
         hv[u] = static_cast<__bf16>(unit0 + u < H ? og * lstm_tanh(cn) : 0.0f);
     }
     *reinterpret_cast<bf16x4*>(hdst + unit0) = hv;
+}
+
+// The kernels' LDS maps (offsets in floats).  The narrow kernel's is its kernel argument and keeps its fields; the one of the rows with map
+// columns adds the staged map rows MB and, behind everything else, the keys and the order of action 0.
+struct LstmHLds { int key, perm, G, HB, XB, P, Q, J, LT, total; };
+struct LstmOmHLds { int key, perm, G, MB, HB, XB, P, Q, J, LT, key0, perm0, total; };
+
+// what the map columns add to a launch: the maps [W][n][om_cols], which map a step pairs with its row, ksm k-steps of 16 and the stride
+// (floats) of a bf16 map row in LDS
+struct LstmOmH { const float* maps; int om_cols, map_order, ksm, ld_m; };
+
+template <class Lds>
+inline Lds lstm_bf16_lds_map(const LstmHPlan& s, int n, int ld_m)
+{
+    constexpr bool om = std::is_same<Lds, LstmOmHLds>::value;
+    const VnPlan& p = s.q.v;
+    Lds m{};
+    int o = 0;
+    auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
+    m.key = take(TILE_M * n);
+    m.perm = take(TILE_M * n);
+    m.G = take(2 * TILE_M * LDX);
+    if constexpr (om) m.MB = take(2 * TILE_M * ld_m);
+    m.HB = take(2 * TILE_M * s.ld_h);
+    m.XB = p.c0[1] > 0 ? take(TILE_M * s.ld_xb) : m.HB;
+    m.P = take(TILE_M * p.ld_pq);
+    m.Q = take(TILE_M * p.ld_pq);
+    m.J = take(JROWS * p.ld_j);
+    m.LT = take(VN_MAX_LAYERS * 8);
+    if constexpr (om) {
+        m.key0 = take(TILE_M * n);
+        m.perm0 = take(TILE_M * n);
+    }
+    m.total = o;
+    return m;
+}
+
+inline int launch_pick(int W, int A, const float* d_values, const float* d_actions, const float* d_robot, int robot_stride, const int32_t* d_override,
+                       int32_t* d_choice, float* d_action_out, void* stream);         // (value_net_pick.h, included behind the unit's kernel)
+
+// A decide entry behind its name.  K is the entry's kernel: K::om, whether its rows carry map columns (the entry without passes om_cols = 0,
+// d_maps = nullptr, map_order = CS_VN_MAPS_OWN), K::Lds, its LDS map, and K::kernel<WREG, MLP1>, its four builds.
+template <class K>
+inline int lstm_bf16_decide(const char* entry, const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n, int cols,
+                            int om_cols, int sorted_by_distance, int map_order, const float* d_rotated, const float* d_maps, const float* d_rewards,
+                            const float* d_actions, const float* d_robot, int robot_stride, float gamma, float dt, const int32_t* d_override,
+                            float* d_values, int32_t* d_choice, float* d_action_out, void* stream)
+{
+    LstmHPlan s;
+    const int rc = build_lstm_bf16_plan(dims, n_dims, cols, s, K::om, om_cols);
+    if (rc != CS_OK) return rc;
+    const LstmPlan& q = s.q;
+    // (a length that is no whole number of floats is no blob of any network: it fails the size check as SIZE_MAX floats)
+    const size_t n_floats = n_weight_bytes % sizeof(float) ? (size_t)-1 : n_weight_bytes / sizeof(float);
+    const int rc2 = lstm_check_decide(entry, q.v, d_weights, n_floats, W, A, n, sorted_by_distance, d_rotated, d_rewards, d_actions, d_robot, robot_stride,
+                                      d_values, d_action_out, K::om, d_maps, map_order);
+    if (rc2 != CS_OK) return rc2;
+    const LstmOmH om{d_maps, om_cols, map_order, up(om_cols, 16) / 16, up(om_cols, 16) / 2 + 4};
+    const auto m = lstm_bf16_lds_map<typename K::Lds>(s, n, om.ld_m);
+    const bool mlp1 = q.v.c0[1] > 0;
+    const bool wreg = q.g.ncb <= 4 * RB && s.ksh <= RKH && s.ksx <= (K::om && !mlp1 ? KGF + RKM : RKX);
+    const float* wb = static_cast<const float*>(d_weights);
+    const int rc3 = lstm_launch(m.total, W, A, wreg, mlp1, [&](auto WR, auto M1, size_t shmem, int NG, int grid) {
+        constexpr auto kernel = K::template kernel<decltype(WR)::value, decltype(M1)::value>;
+        const int rc4 = grant_lds<kernel>(shmem);
+        if (rc4 != CS_OK) return rc4;
+        const auto launch = [&](auto... behind) {       // (the kernel with map columns takes `om` behind the narrow kernel's arguments)
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), shmem, (hipStream_t)stream, s, m, wb, NG, A, n, sorted_by_distance, d_rotated, d_rewards, d_robot,
+                               robot_stride, gamma, dt, d_values, behind...);
+        };
+        if constexpr (K::om) launch(om);
+        else launch();
+        return (int)CS_OK;
+    });
+    if (rc3 != CS_OK) return rc3;
+    return launch_pick(W, A, d_values, d_actions, d_robot, robot_stride, d_override, d_choice, d_action_out, stream);
 }
 
 } // namespace

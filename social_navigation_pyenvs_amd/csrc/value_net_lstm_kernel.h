@@ -1,6 +1,6 @@
 // value_net_lstm_kernel.h -- what LSTM-RL's decision kernels share beside their plan (value_net_lstm_plan.h): k_value_net_lstm and
 // k_value_net_lstm_om (value_net_lstm.hip, value_net_lstm_body.inc), k_value_net_lstm_bf16 (value_net_lstm_bf16.hip) and
-// k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip).  Device: the layer
+// k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip; both value_net_lstm_bf16_body.inc).  Device: the layer
 // table in LDS, the order of a tile's rows, the ends of a job around its step loop (the step loops themselves differ by design and stay with
 // their kernels), the layer of 32 rows in its two arithmetics and the chain of layers.  Host: what a decide entry does between its plan and
 // its launch.  The gradient kernel (value_net_lstm_grad.hip) needs none of it: the one piece it shares with the step loop here, LSTM_KSTEP, is
