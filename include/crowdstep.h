@@ -920,6 +920,33 @@ int cs_value_net_decide_lstm_om_bf16(const int32_t* dims, int n_dims, const void
                                      float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_om_bf16  cs_value_net_decide_om with the opt-in bf16 arithmetic (csrc/value_net_om_bf16.hip): the same
+ *   arguments, results, errors and messages -- kind != CS_VN_SARL, om_cols < 1, cols + om_cols > 256, a null d_maps, the LDS-fit refusal for
+ *   this kernel's own LDS --, with the blob of cs_value_net_pack_om_bf16 and its length in bytes.  mlp1's layer 0 is split by column: its
+ *   cols rotated columns stay float32 (full weights, unrounded inputs, v_mfma_f32_32x32x2_f32); its om_cols map columns are bf16 operands
+ *   with float32 accumulation -- the weights [:, cols:] rounded to bf16, nearest even, by the pack, a map value rounded once, nearest even,
+ *   when it is staged, zeros up to a multiple of 16 columns.  A pre-activation of that layer is one chain: the bias, the two float32
+ *   k-groups of the rotated columns ascending, the ksm = ceil(om_cols / 16) map k-steps ascending; then the ReLU; then it is rounded once
+ *   as the next layer's operand.  Everything else is cs_value_net_decide_bf16's contract: every later layer outside mlp3 a bf16 layer, mlp3
+ *   float32 on the unrounded self state (the first six columns of the first human's row), what a reduction consumes not rounded, the
+ *   crowd mean summed in human order from the rounded mlp1 outputs and rounded once, the softmax, the weighted sum, the action value and
+ *   the pick float32.  One map row serves the A actions of its world.  A (world, action) gives the same bits for W = 1 as inside any
+ *   batch.  With all-zero map weights and finite maps the values equal cs_value_net_decide_bf16's on the narrow network.  No atomics.
+ * cs_value_net_pack_om_bf16  (host only) params as cs_value_net_pack_om takes them.  blob == NULL: only *n_bytes is set.  The blob is
+ *   zeroed, then written.  Layout: cs_value_net_pack_bf16's, layer after layer, with the one wider layer:
+ *     mlp1 layer 0      [ncb][2 + ksm][64 lanes] slots of 16 bytes, ncb = ceil(N / 32): slot s < 2 holds 4 floats, element e =
+ *                       weight[32 b + (l & 31)][8 s + 4 (l >> 5) + e] for k < cols; slot s >= 2 holds 8 bf16, element e =
+ *                       weight[32 b + (l & 31)][cols + 16 (s - 2) + 8 (l >> 5) + e] for k < cols + om_cols; then float bias[32 ncb].
+ *   Weights and biases beyond N or K are zero.  A NaN weight becomes the quiet NaN 0x7fc0.
+ */
+int cs_value_net_pack_om_bf16(int kind, const int32_t* dims, int n_dims, int cols, int om_cols, const float* const* params, void* blob,
+                              size_t* n_bytes);
+int cs_value_net_decide_om_bf16(int kind, const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n,
+                                int cols, int om_cols, const float* d_rotated, const float* d_maps /* [W][n][om_cols] */,
+                                const float* d_rewards, const float* d_actions, const float* d_robot, int robot_stride, float gamma, float dt,
+                                const int32_t* d_override, float* d_values, int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * The optimisation step of the networks with occupancy-map columns, OM-SARL and OM-LSTM-RL (csrc/value_net_grad.hip,
  * csrc/value_net_lstm_grad.hip): every entry below is its sibling without `_om` -- the same kernels, launches, results,
  * determinism and errors -- with `int om_cols` behind `cols`, 1 <= om_cols and cols + om_cols <= 256.

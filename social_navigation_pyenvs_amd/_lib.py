@@ -183,6 +183,8 @@ ABI = {
     "cs_value_net_decide_lstm_om": (I, [P, I, P, Z, I, I, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_pack_lstm_om_bf16": (I, [P, I, I, I, P, P, P]),
     "cs_value_net_decide_lstm_om_bf16": (I, [P, I, P, Z, I, I, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_pack_om_bf16": (I, [I, P, I, I, I, P, P, P]),
+    "cs_value_net_decide_om_bf16": (I, [I, P, I, P, Z, I, I, I, I, I, P, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_grad_sizes_om": (I, [I, P, I, I, I, I, I, P, P]),
     "cs_value_net_loss_grad_om": (I, [I, P, I, P, Z, P, Z, I, I, I, I, P, P, P, P, P, P, Z, P]),
     "cs_value_net_pack_om_device": (I, [I, P, I, I, I, P, Z, P, Z, P]),

@@ -158,6 +158,7 @@ class CADRL(Policy):
         self.decision_input = "tensor"
         self.recurrent_precision = "f32"         # (LSTM-RL's own choice, lstm_rl.py set_recurrent_precision; "f32" for every other policy)
         self.mapped_precision = "f32"            # (OM-LSTM-RL's own choice, om_lstm_rl.py set_mapped_precision; "f32" for every other policy)
+        self.wide_precision = "f32"              # (OM-SARL's own choice, om_sarl.py set_wide_precision; "f32" for every other policy)
 
     # ------------------------------------------------------------------ configuration
     def configure(self, config):
@@ -214,7 +215,7 @@ class CADRL(Policy):
         """The network as the kernel reads it (value_net.DeviceNet), the blob of ``decision_precision`` repacked only after a parameter changed."""
         if self._net is None or self._net.model is not self.model:
             self._net = self._new_device_net(self.model)
-        self._net.refresh_selected(self.decision_precision, self.recurrent_precision, self.mapped_precision)
+        self._net.refresh_selected(self.decision_precision, self.recurrent_precision, self.mapped_precision, self.wide_precision)
         return self._net
 
     _STATE_NETS_KEPT = 4
@@ -292,7 +293,8 @@ class CADRL(Policy):
         stream = lambda: torch.cuda.current_stream().cuda_stream
         rot, _ = value_net.decide_for_worlds(net, self.decision_input, self.decision_precision, d_a, d_n, d_c, d_r, self.gamma, self.time_step,
                                              up(np.array([override]), torch.int32), vals, pick, act, stream(),
-                                             recurrent_precision=self.recurrent_precision, mapped_precision=self.mapped_precision)
+                                             recurrent_precision=self.recurrent_precision, mapped_precision=self.mapped_precision,
+                                             wide_precision=self.wide_precision)
         # (SARL's attention weights read the last action's rows; without the look-ahead tensor they are made when asked for)
         self._last_rotated = rot if rot is not None else (lambda: value_net.lookahead(d_a[-1:].contiguous(), d_n, d_c, d_r, self.time_step, stream()))
         return vals[0].cpu().numpy(), int(pick.item()), act[0].cpu().numpy()

@@ -6,8 +6,15 @@ joint_state_dim + cell_num^2 * om_channel_size wide), so a reference OM-SARL che
 
 The maps are cs_occupancy_maps (csrc/occupancy_map.hip), the decision cs_lookahead -> cs_occupancy_maps on the NEXT human states ->
 cs_value_net_decide_om (csrc/value_net_om.hip): SARL's decision from the same rows and rewards with the maps the reference's serial branch
-builds (multi_human_rl.py:75-78; its parallel branch reads a name it never binds).  It is a key of its own in policy_factory,
-"om_sarl": ``policy_factory["sarl"]`` with with_om = true keeps raising."""
+builds (multi_human_rl.py:75-78; its parallel branch reads a name it never binds).
+
+``set_wide_precision("bf16")`` moves ``predict`` and the batched Gym's ``act_device`` to the opt-in bf16 arithmetic
+(cs_value_net_decide_om_bf16, csrc/value_net_om_bf16.hip): mlp1's layer 0 keeps the rotated columns float32 and takes the
+map columns in bf16, everything behind it is SARL's bf16 decision.  ``set_decision_precision("bf16")`` and ``set_decision_input("fused")``
+keep refusing: those are the kernels without map columns.  ``transform``, ``state_value``, ``joint_state_device``, the Gym's
+``value_device`` and the trainers stay float32.
+
+It is a key of its own in policy_factory, "om_sarl": ``policy_factory["sarl"]`` with with_om = true keeps raising."""
 from __future__ import annotations
 
 import logging
@@ -40,6 +47,11 @@ class OMSARL(SARL):
                                   widths["attention_dims"], config.getboolean(section, "with_global_state"))
         self.multiagent_training = config.getboolean(section, "multiagent_training")
         logging.debug("%s: %d map columns, widths %s", self.name, self.map_columns(), widths)
+
+    def set_wide_precision(self, precision):
+        """The arithmetic of the decision kernel on the rows with map columns, for ``predict`` and ``act_device`` alike: "f32" (the
+        default) or the opt-in "bf16" (DESIGN.md 4.5).  ``decision_precision`` and ``decision_input`` stay ("f32", "tensor")."""
+        self.wide_precision = value_net.check_wide_precision(precision, self.family)
 
     def map_columns(self):
         return int(self.cell_num) ** 2 * int(self.om_channel_size) if self.with_om else 0

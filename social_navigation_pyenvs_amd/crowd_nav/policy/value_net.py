@@ -25,6 +25,14 @@ csrc/value_net_lstm_bf16.hip and csrc/value_net_lstm_om_bf16.hip, under names ap
 ``DeviceNet.refresh_<word>``, ``decide_for_worlds(..., <word>_precision="bf16")`` and a policy's ``set_<word>_precision`` (``LstmRL``: recurrent,
 ``OMLstmRL``: mapped).  ``pack_lstm_bf16`` / ``pack_lstm_om_bf16`` and ``decide_lstm_bf16`` / ``decide_lstm_om_bf16`` are the public names.
 
+MAPPED states OM-SARL's opt-in bf16 decision (csrc/value_net_om_bf16.hip: mlp1's layer 0 split between float32 rotated columns and bf16 map
+columns, everything behind it the feed-forward bf16 arithmetic) the same way, as an ``OwnArithmetic`` with the word "wide" -- in the row's
+``wide`` field, not in ``own``: ``MAPPED.own`` is None and ``MAPPED.modes`` holds ("tensor", "f32") alone, so that ``set_decision_precision("bf16")``,
+``set_decision_input("fused")`` and ``check_mapped_precision("bf16", MAPPED)`` keep refusing an OM-SARL network with the sentences they have.
+``own_arithmetic(family)`` is the one place that answers which of the two a row states.  Its names: WIDE_PRECISIONS, the key WIDE_BF16,
+``check_wide_precision``, ``DeviceNet.refresh_wide``, ``decide_for_worlds(..., wide_precision="bf16")``, ``OMSARL.set_wide_precision``,
+``pack_om_bf16`` and ``decide_om_bf16``.
+
 ``state_values`` is the training side (cs_value_net_state, csrc/value_net_state.hip): the network on the worlds' current state -- the
 rotated joint states a trainer stores and V(s) or the target reward + gamma^(dt * v_pref) * V(s) --, float32 whatever the policy's modes;
 ``state_values_for_worlds`` is that for every family.
@@ -60,6 +68,8 @@ RECURRENT_PRECISIONS = ("f32", "bf16")      # of the recurrent family without ma
 RECURRENT_BF16 = "recurrent_bf16"           # DeviceNet's key of that arithmetic's blob
 MAPPED_PRECISIONS = ("f32", "bf16")         # of the recurrent family with map columns: "bf16" is cs_value_net_decide_lstm_om_bf16
 MAPPED_RECURRENT_BF16 = "mapped_recurrent_bf16"     # the key of that arithmetic's blob, on a DeviceNet of family RECURRENT_MAPPED alone
+WIDE_PRECISIONS = ("f32", "bf16")           # of the feed-forward family with map columns (OM-SARL): "bf16" is cs_value_net_decide_om_bf16
+WIDE_BF16 = "wide_bf16"                     # the key of that arithmetic's blob, on a DeviceNet of family MAPPED alone
 
 
 def check_precision(precision):
@@ -80,7 +90,7 @@ MAPPED_GRADIENT_REFUSAL = ("{0}: the *_om helpers cover the networks with occupa
 
 
 class OwnArithmetic(NamedTuple):
-    """A family's own opt-in arithmetic beside its ``modes`` (the recurrent families' bf16 decision)."""
+    """A family's own opt-in arithmetic beside its ``modes`` (the recurrent families' and OM-SARL's bf16 decision)."""
     key: str                # DeviceNet's key of its blob
     pack: tuple             # (pack entry, what it counts its blob in)
     decide: str             # the decide entry on the look-ahead tensor: the family's decide_int and takes_maps hold for it too
@@ -105,6 +115,7 @@ class Family(NamedTuple):
     flat_rows: bool         # the training seams take rows [B, cols] as n = 1 (CADRL's stored states)
     train_refusal: str      # the sentence the family's training seams refuse every other net with ({0}: the caller, {1}: the helper to use)
     own: OwnArithmetic = None       # the family's own opt-in arithmetic, where it has one
+    wide: OwnArithmetic = None      # MAPPED's: the same statement under the word "wide", apart from `own` (the module's docstring)
 
     def lead(self, kind):
         return (kind,) if self.takes_kind else ()
@@ -128,7 +139,9 @@ MAPPED = Family(
     modes=(("tensor", "f32"),),
     refusal='decision input {0!r} with decision precision {1!r} for a network with occupancy-map columns: no kernel pairs the map columns '
             'with the "fused" or the "bf16" tile loader; OM-SARL decides with "tensor" and "f32"',
-    min_humans=2, state_launch=False, train_infix="", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL)
+    min_humans=2, state_launch=False, train_infix="", flat_rows=False, train_refusal=MAPPED_GRADIENT_REFUSAL,
+    wide=OwnArithmetic(key=WIDE_BF16, pack=("cs_value_net_pack_om_bf16", np.uint8), decide="cs_value_net_decide_om_bf16", word="wide",
+                       no_blob='the network has no wide bf16 blob yet (DeviceNet.refresh_wide("bf16"))'))
 RECURRENT = Family(
     pack=frozen({"f32": ("cs_value_net_pack_lstm", np.float32)}), takes_kind=False,
     decide=frozen({"f32": "cs_value_net_decide_lstm"}), decide_int="sorted_by_distance", takes_maps=False,
@@ -154,6 +167,11 @@ def family_of(kind, om_cols=0):
     if kind == CS_VN_LSTM:
         return RECURRENT_MAPPED if om_cols else RECURRENT
     return MAPPED if om_cols else FEED_FORWARD
+
+
+def own_arithmetic(family):
+    """The opt-in arithmetic a family states beside its ``modes``, in ``own`` or in ``wide``; None where it states none."""
+    return family.own or family.wide
 
 
 def has_gradient_kernel(family):
@@ -194,6 +212,18 @@ def check_mapped_precision(precision, family=None):
         raise ValueError('mapped precision "bf16": cs_value_net_decide_lstm_om_bf16 is the kernel of OM-LSTM-RL, the recurrent network on rows '
                          "with occupancy-map columns; LSTM-RL without map columns chooses with set_recurrent_precision, CADRL and SARL with "
                          "set_decision_precision, OM-SARL decides in float32")
+    return precision
+
+
+def check_wide_precision(precision, family=None):
+    """The arithmetic of the decision kernel on SARL's rows with map columns a policy may hold: one of WIDE_PRECISIONS; "bf16" for the
+    feed-forward family with map columns alone (`family`: the policy's or the net's row, None asks only the name)."""
+    if precision not in WIDE_PRECISIONS:
+        raise ValueError(f"wide precision {precision!r}: one of {', '.join(map(repr, WIDE_PRECISIONS))}")
+    if precision == "bf16" and family is not None and family is not MAPPED:
+        raise ValueError('wide precision "bf16": cs_value_net_decide_om_bf16 is the kernel of OM-SARL, SARL\'s network on rows with '
+                         "occupancy-map columns; CADRL and SARL choose with set_decision_precision, LSTM-RL with set_recurrent_precision, "
+                         "OM-LSTM-RL with set_mapped_precision")
     return precision
 
 
@@ -275,9 +305,15 @@ def pack_lstm_om_bf16(dims, cols, om_cols, arrays):
     return _pack_with(RECURRENT_MAPPED, CS_VN_LSTM, RECURRENT_MAPPED.own.pack, dims, cols, om_cols, arrays)
 
 
+def pack_om_bf16(dims, cols, om_cols, arrays):
+    """cs_value_net_pack_om_bf16's blob (uint8 numpy: include/crowdstep.h states the bytes) of an OM-SARL network from the float32 arrays
+    ``pack(CS_VN_SARL, ..., om_cols=om_cols)`` takes.  Host only: no GPU needed."""
+    return _pack_with(MAPPED, CS_VN_SARL, MAPPED.wide.pack, dims, cols, om_cols, arrays)
+
+
 def _pack_with(family, kind, entry_and_unit, dims, cols, om_cols, arrays):
     """The size query and the packing call of one of `family`'s pack entries: (its name, what it counts its blob in), from the row's
-    ``pack`` or its ``own``."""
+    ``pack``, its ``own`` or its ``wide``."""
     from ... import _lib
 
     entry, unit = getattr(_lib.load(), entry_and_unit[0]), entry_and_unit[1]
@@ -309,7 +345,8 @@ class DeviceNet:
         self.lstm = self.kind == CS_VN_LSTM
         # (an own arithmetic's blob lies under the key its row states: "bf16" stays the feed-forward arithmetic's, which a recurrent net
         # refuses.  RECURRENT's key is on every net, as it was before the table stated it; any other row's on a net of that family alone)
-        keys = PRECISIONS + (RECURRENT.own.key,) + ((self.family.own.key,) if self.family.own else ())
+        stated = own_arithmetic(self.family)
+        keys = PRECISIONS + (RECURRENT.own.key,) + ((stated.key,) if stated else ())
         self._keys = dict.fromkeys(keys)
         self.blobs = dict.fromkeys(keys)
         self.flat = None
@@ -359,13 +396,23 @@ class DeviceNet:
             return self.refresh("f32")
         return self._repacked(self.family.own.key, self.family.own.pack)
 
-    def refresh_selected(self, decision_precision, recurrent_precision, mapped_precision):
-        """What a policy's three attributes select: the blob of ``decision_precision`` and, where the others are not "f32", the family's own."""
+    def refresh_wide(self, precision="f32"):
+        """``refresh`` for the arithmetics of the feed-forward family with map columns (WIDE_PRECISIONS): "f32" is ``refresh("f32")``; "bf16"
+        keeps cs_value_net_pack_om_bf16's blob under the key WIDE_BF16, rebuilt on the same version-counter rule and dropped by
+        ``updated_on_device``; it never aliases the float32 blob.  Every other family is refused with the reason."""
+        if check_wide_precision(precision, self.family) == "f32":
+            return self.refresh("f32")
+        return self._repacked(self.family.wide.key, self.family.wide.pack)
+
+    def refresh_selected(self, decision_precision, recurrent_precision, mapped_precision, wide_precision="f32"):
+        """What a policy's four attributes select: the blob of ``decision_precision`` and, where the others are not "f32", the family's own."""
         self.refresh(decision_precision)
         if recurrent_precision != "f32":
             self.refresh_recurrent(recurrent_precision)
         if mapped_precision != "f32":
             self.refresh_mapped(mapped_precision)
+        if wide_precision != "f32":
+            self.refresh_wide(wide_precision)
 
     def adopt_flat(self, flat, mapped=False):
         """A trainer's word that the module's parameters are views of `flat` (a CUDA float32 tensor in ``param_offsets``' layout, as
@@ -628,15 +675,16 @@ def decide_rows(net, W, A, n, rotated, extra, *tail, precision="f32", own=False)
     """The tensor decide entry of `net`'s family on device pointers (ints).  `extra`: what that entry takes beyond
     cs_value_net_decide's arguments -- the maps [W][n][net.om_cols], or sorted_by_distance, or the pair (maps, sorted_by_distance) for a
     family that takes both (``net.map_order`` goes with them); `tail`: rewards, actions, robot, robot_stride, gamma, dt, override, values,
-    choice, action_out, stream.  `own`: the family's own arithmetic (``Family.own``) -- its entry on its blob, the same arguments."""
+    choice, action_out, stream.  `own`: the family's own arithmetic (``own_arithmetic``) -- its entry on its blob, the same arguments."""
     from ... import _lib
 
     family = net.family
     if own:
-        entry, blob = family.own.decide, net.blobs[family.own.key]
+        stated = own_arithmetic(family)
+        entry, blob = stated.decide, net.blobs[stated.key]
         if blob is None:
-            raise ValueError(f"{entry.removeprefix('cs_value_net_')}: {family.own.no_blob}")
-        head = _head((), net.dims, blob)
+            raise ValueError(f"{entry.removeprefix('cs_value_net_')}: {stated.no_blob}")
+        head = _head(family.lead(net.kind), net.dims, blob)
     else:
         entry, head = family.decide[precision], net.head(family.decide["f32"].removeprefix("cs_value_net_"), precision)
     both = "sorted_by_distance" in family.decide_int and family.takes_maps
@@ -682,6 +730,15 @@ def decide_om(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride
     if net.family is not MAPPED:
         raise ValueError("decide_om: the network has no occupancy-map columns (DeviceNet(model, cols, om_cols))")
     decide_rows(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream)
+
+
+def decide_om_bf16(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream=None):
+    """cs_value_net_decide_om_bf16 on device pointers (ints): ``decide_om`` in the opt-in bf16 arithmetic, for a DeviceNet of an OM-SARL
+    network whose wide bf16 blob is current (``refresh_wide("bf16")``)."""
+    if net.family is not MAPPED:
+        raise ValueError("decide_om_bf16: the network is not SARL's with occupancy-map columns (DeviceNet(model, cols, om_cols))")
+    decide_rows(net, W, A, n, rotated, maps, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out, stream,
+                own=True)
 
 
 def decide_lstm(net, W, A, n, sorted_by_distance, rotated, rewards, actions, robot, robot_stride, gamma, dt, override, values, choice, action_out,
@@ -828,14 +885,14 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 
 
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None,
-                      recurrent_precision="f32", mapped_precision="f32"):
+                      recurrent_precision="f32", mapped_precision="f32", wide_precision="f32"):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
     the family's decide entry with `precision` -- a recurrent net in the decision's order; a net with map columns on occupancy_maps of the
     NEXT humans (the maps the reference's serial branch builds, once per decision; with the net's ``map_order``), which it keeps in
-    ``net.last_maps``.  ``recurrent_precision`` / ``mapped_precision`` "bf16" (the net of that family alone, whose ``refresh_recurrent`` /
-    ``refresh_mapped("bf16")`` blob is current): the same sequence with the family's own arithmetic.  Returns (rotated, rewards), the
-    look-ahead tensors it allocated and the launches read -- (None, None) for "fused"."""
+    ``net.last_maps``.  ``recurrent_precision`` / ``mapped_precision`` / ``wide_precision`` "bf16" (the net of that family alone, whose
+    ``refresh_recurrent`` / ``refresh_mapped`` / ``refresh_wide("bf16")`` blob is current): the same sequence with the family's own
+    arithmetic.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
     # (the order of these checks is which refusal a caller with several bad arguments sees: the mapped precision; with it "bf16" the mode in
@@ -844,6 +901,7 @@ def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gam
     if own:
         check_mode(net.family, decision_input, precision)
     own = check_recurrent_precision(recurrent_precision, net.family) == "bf16" or own
+    own = check_wide_precision(wide_precision, net.family) == "bf16" or own
     if check_mode(net.family, decision_input, precision) == "fused":      # one library call on the worlds' own rows
         decide_worlds(net, W, A, n, cc == 7, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr,
                       None, values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)

@@ -1,5 +1,6 @@
-// value_net_bf16.h -- bf16 as the two opt-in arithmetics (value_net_bf16.hip, value_net_lstm_bf16.hip) share it: the operand vector of
-// v_mfma_f32_32x32x16_bf16, the host's rounding and the pack of a bf16 layer.  Unnamed namespace, as value_net_plan.h.
+// value_net_bf16.h -- bf16 as the opt-in arithmetics (value_net_bf16_layers.h, value_net_lstm_bf16.h) share it: the operand vector of
+// v_mfma_f32_32x32x16_bf16, the host's rounding, the pack of a bf16 layer and of a first layer split between float32 rotated columns and
+// bf16 map columns.  Unnamed namespace, as value_net_plan.h.
 #pragma once
 #include "value_net_plan.h"
 
@@ -34,6 +35,34 @@ inline void pack_layer_bf16(const VnLayer& L, const float* wgt, const float* bia
                     else if (kk - L.kg_split * 16 < L.K2) k = L.K1 + kk - L.kg_split * 16;
                     if (j < L.N && k >= 0) hb[((size_t)(cb * L.kg_total + ks) * 64 + lane) * 8 + e] = bf16_bits(wgt[(size_t)j * K + k]);
                 }
+    for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
+}
+
+// a first layer on rows with map columns (OM-SARL's mlp1 layer 0, OM-LSTM-RL network 2's), where the lanes of its layer read it:
+// [ncb][k-groups + k-steps][64 lanes] slots of 16 bytes -- the float32 layer's k-groups of the rotated columns (pack_layer_f32's), then
+// the bf16 layer's k-steps of the map columns (pack_layer_bf16's, k counted from `cols`); float32 biases.  blob zeroed before
+inline void pack_layer_mixed(const VnLayer& L, int cols, const float* wgt, const float* bias, float* fb)
+{
+    const int K = L.K1;
+    for (int cb = 0; cb < L.ncb; ++cb)
+        for (int sl = 0; sl < L.kg_total; ++sl)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int j = cb * 32 + (lane & 31), hh = lane >> 5;
+                if (j >= L.N) continue;
+                float* slot = fb + L.w_off + ((size_t)(cb * L.kg_total + sl) * 64 + lane) * 4;
+                if (sl < L.kg_split) {
+                    for (int e = 0; e < 4; ++e) {
+                        const int k = 8 * sl + 4 * hh + e;
+                        if (k < cols) slot[e] = wgt[(size_t)j * K + k];
+                    }
+                } else {
+                    uint16_t* hs = reinterpret_cast<uint16_t*>(slot);
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = cols + 16 * (sl - L.kg_split) + 8 * hh + e;
+                        if (k < K) hs[e] = bf16_bits(wgt[(size_t)j * K + k]);
+                    }
+                }
+            }
     for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
 }
 

@@ -7,7 +7,7 @@
 //   VN_TILE_SOURCE(g0)             a declaration, once per tile whose first group is g0
 //   VN_LOAD_TILE(ch, rows, per)    chunk ch of the tile into b.X0 and b.grp as load_tile leaves them: `rows` rows, `per` humans a group
 //   VN_REWARD(g, k)                the reward of group g, the job's k-th
-// From value_net_plan.h it takes VnBufs, the CH_* tags and the constants; from its arithmetic (value_net_f32.h or value_net_bf16.hip):
+// From value_net_plan.h it takes VnBufs, the CH_* tags and the constants; from its arithmetic (value_net_f32.h or value_net_bf16_layers.h):
 //   run_chain<CH>(...)             the layers of one chain; the tag says which chain, for an arithmetic that treats them differently
 //   vn_m1(buf, ld, r, c)           element (r, c) of mlp1's output or of the crowd mean, as float
 //   vn_mean_store(buf, ld, k, c, v)  element c of group k's crowd mean into G

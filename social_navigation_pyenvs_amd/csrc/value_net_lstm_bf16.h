@@ -104,8 +104,8 @@ inline int build_lstm_bf16_plan(const int32_t* dims, int n_dims, int cols, LstmH
     return CS_OK;
 }
 
-// (bf16_bits and pack_layer_bf16 -- a bf16 layer's weights where the lanes of lstm_layer read them, cs_value_net_pack_bf16's layout -- are
-// value_net_bf16.h's)
+// (bf16_bits, pack_layer_bf16 -- a bf16 layer's weights where the lanes of lstm_layer read them, cs_value_net_pack_bf16's layout -- and
+// pack_layer_mixed -- network 2's first layer on rows with map columns -- are value_net_bf16.h's)
 
 // the gate rows where the lanes of the transposed product read them: slot s of block b, lane l, gate row j = l & 31 = 8 * gate + u, torch's
 // row gate * H + 8 b + u.  Slots below ksh: 8 bf16 of weight_hh at k = 16 s + 8 (l >> 5) + e.  Behind them the x part: network 2, 8 bf16 of
@@ -148,34 +148,6 @@ inline void pack_gates_bf16(const LstmHPlan& s, const float* wih, const float* w
                 }
             }
         }
-}
-
-// network 2's first layer on rows with map columns, where the lanes of its layer read it: [ncb][k-groups + k-steps][64 lanes] slots of 16
-// bytes -- the float32 layer's k-groups of the rotated columns (pack_layer_f32's), then the bf16 layer's k-steps of the map columns
-// (pack_layer_bf16's, k counted from `cols`); float32 biases.  blob zeroed before
-inline void pack_layer_mixed(const VnLayer& L, int cols, const float* wgt, const float* bias, float* fb)
-{
-    const int K = L.K1;
-    for (int cb = 0; cb < L.ncb; ++cb)
-        for (int sl = 0; sl < L.kg_total; ++sl)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int j = cb * 32 + (lane & 31), hh = lane >> 5;
-                if (j >= L.N) continue;
-                float* slot = fb + L.w_off + ((size_t)(cb * L.kg_total + sl) * 64 + lane) * 4;
-                if (sl < L.kg_split) {
-                    for (int e = 0; e < 4; ++e) {
-                        const int k = 8 * sl + 4 * hh + e;
-                        if (k < cols) slot[e] = wgt[(size_t)j * K + k];
-                    }
-                } else {
-                    uint16_t* hs = reinterpret_cast<uint16_t*>(slot);
-                    for (int e = 0; e < 8; ++e) {
-                        const int k = cols + 16 * (sl - L.kg_split) + 8 * hh + e;
-                        if (k < K) hs[e] = bf16_bits(wgt[(size_t)j * K + k]);
-                    }
-                }
-            }
-    for (int j = 0; j < L.N; ++j) fb[L.b_off + j] = bias[j];
 }
 
 // what the two pack entries do behind their plan: the size in bytes, the null checks, the zeroed blob, every layer in its arithmetic, the gates

@@ -1,5 +1,5 @@
 // value_net_plan.h -- what the three kernels of the value-network decision share beside their body (value_net_body.inc) and their
-// arithmetic (value_net_f32.h: float32, for value_net.hip and value_net_worlds.hip; value_net_bf16.hip: the opt-in bf16 layers, whose host pieces are value_net_bf16.h).  Host: the
+// arithmetic (value_net_f32.h: float32, for value_net.hip and value_net_worlds.hip; value_net_bf16_layers.h: the opt-in bf16 layers, whose host pieces are value_net_bf16.h).  Host: the
 // layer table of a network description, the argument checks, the LDS map, what the decide entries do before their launch and the pack
 // entries before they fill.  Device: the LDS buffers, the chain tags, the tile loader that copies rows and the float32 layer of a tile.
 // Everything sits in an unnamed namespace: each translation unit gets its own copy, the kernels keep their names.  The per-world pick and

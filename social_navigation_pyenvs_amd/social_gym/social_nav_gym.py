@@ -721,7 +721,8 @@ class BatchedSocialNavGym:
         cs_value_net_decide_worlds, which generates the look-ahead rows in the kernel and allocates no look-ahead tensor.  ``explore``: an
         int32 CUDA tensor [W] of action indices forced on their worlds, -1 = greedy (the caller's epsilon-greedy draw).  The action
         values and choices of that decision stay readable through ``last_values_device()``.  An OM-SARL instance
-        (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om, an
+        (``policy_factory["om_sarl"]``) runs cs_peek -> cs_lookahead -> cs_occupancy_maps on the next humans -> cs_value_net_decide_om
+        (cs_value_net_decide_om_bf16 after the policy's ``set_wide_precision("bf16")``), an
         LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
         (world, action)'s humans by decreasing distance inside the kernel (cs_value_net_decide_lstm_bf16 after the policy's
         ``set_recurrent_precision("bf16")``); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
@@ -820,7 +821,8 @@ class BatchedSocialNavGym:
             nxt, cur_, rob = self._worlds_on_side_stream(dl, nxt)
             rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
                                                    explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream,
-                                                   recurrent_precision=pol.recurrent_precision, mapped_precision=pol.mapped_precision)
+                                                   recurrent_precision=pol.recurrent_precision, mapped_precision=pol.mapped_precision,
+                                                   wide_precision=pol.wide_precision)
             for t in (nxt, cur_, rob, rot, rew, explore):
                 if t is not None:
                     t.record_stream(side)

@@ -13,6 +13,9 @@ tile is not counted), the fraction is against the 157 TFLOP/s float32 matrix pea
     python tools/value_policy_timing.py [--worlds 4096] [--humans 5 25] [--policies cadrl sarl] [--repeats 20] [--out FILE]
     python tools/value_policy_timing.py --precision f32 bf16   # both arithmetics, alternated inside every repeat; one record each
     python tools/value_policy_timing.py --trace-only        # a few act_device decisions, for a kernel trace of `decide`
+    python tools/value_policy_timing.py --om [--precision f32 bf16]   # the OM-SARL row: cs_value_net_decide_om against
+                                                            # cs_value_net_decide_om_bf16 on the look-ahead rows and the 48-column
+                                                            # maps of the next humans, both in HBM, alternated inside every repeat; text lines
 """
 import argparse
 import json
@@ -76,6 +79,78 @@ def torch_decide(pol, rot, rew, disc, chunk):
         return values, torch.argmax(values, dim=1)
 
 
+def om_rows(a):
+    """The OM-SARL row: the float32 and the bf16 decision kernel (each with the per-world pick) on the same look-ahead rows, rewards and
+    maps [W, n, 48] of the next humans, all in HBM, the default network with seeded weights; the arithmetics of --precision alternated
+    inside every repeat.  Prints, per crowd size, the median (min .. max) of each and how often the two pick the same action."""
+    import numpy as np
+    import om_cases
+    import torch
+    from test_value_om_cpu import om_policy
+
+    from social_navigation_pyenvs_amd import _lib
+    from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
+
+    entries = {"f32": ("cs_value_net_decide_om", value_net.decide_om), "bf16": ("cs_value_net_decide_om_bf16", getattr(value_net, "decide_om_bf16", None))}
+    warm = 5
+    print(f"OM-SARL decision, 48 map columns: {a.worlds} worlds x 81 actions, {a.repeats} repetitions after {warm} warm-up, ms per decision of all "
+          f"worlds (median, min .. max); device {_lib.device_name(0)}; library {os.environ.get('CROWDSTEP_LIB', 'product build')}")
+    for n in a.humans:
+        env = _env(n, a.worlds)
+        W = env.W
+        pol = om_policy()
+        om_cases.draw_weights(pol.model, 1700)
+        pol.set_phase("test")
+        pol.set_device(torch.device("cuda"))
+        pol.time_step = env.robot_time_step
+        with torch.cuda.stream(env.device_stream()):
+            for _ in range(3):
+                env.act_device(pol)                 # (builds the action table for the batch's robot speed)
+            acts = pol.device_action_space()
+            rot, rew = env.lookahead_device(acts)
+            maps = env.occupancy_maps_device(*pol.om_grid(), which="next").contiguous()
+            rob = env.cw.d_robot.torch().view(W, 13)[:, [0, 1, 3, 4, 8, 10, 11, 12, 2]].contiguous()
+            net = pol.device_net()
+            if "bf16" in a.precision:
+                net.refresh_wide("bf16")
+            stream = env.device_stream().cuda_stream
+            out = {p: (torch.zeros((W, 81), device="cuda"), torch.zeros(W, dtype=torch.int32, device="cuda"), torch.zeros((W, 2), device="cuda")) for p in a.precision}
+
+            def kernel(prec):
+                vals, pick, act = out[prec]
+                entries[prec][1](net, W, 81, n, rot.data_ptr(), maps.data_ptr(), rew.data_ptr(), acts.data_ptr(), rob.data_ptr(), 9, pol.gamma,
+                                 env.robot_time_step, None, vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+
+            def timed(fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1)
+
+            for _ in range(warm):
+                for prec in a.precision:
+                    kernel(prec)
+            t = {p: [] for p in a.precision}
+            for _ in range(a.repeats):
+                for prec in a.precision:
+                    t[prec].append(timed(lambda: kernel(prec)))
+            torch.cuda.synchronize()
+            flop = useful_flop(pol, W * 81 * n, W * 81)
+            print(f"n = {n}: {flop / 2e9:.2f} G multiply-adds, {rot.numel() * 4 / 1e6:.0f} MB of look-ahead rows and {maps.numel() * 4 / 1e6:.1f} MB of maps per decision")
+            for prec in a.precision:
+                med = float(np.median(t[prec]))
+                print(f"  {prec:<5} {entries[prec][0]:<32} {med:8.3f}  ({min(t[prec]):.3f} .. {max(t[prec]):.3f})  {flop / (med * 1e-3) / 1e12:.1f} TFLOP/s")
+            if len(a.precision) == 2:
+                f, h = t["f32"], t["bf16"]
+                same = float((out["f32"][1] == out["bf16"][1]).float().mean())
+                finite = bool(torch.isfinite(out["f32"][0]).all() and torch.isfinite(out["bf16"][0]).all())
+                print(f"  f32 / bf16 = {np.median(f) / np.median(h):.2f} in the medians; bf16's slowest repeat {'beats' if max(h) < min(f) else 'DOES NOT beat'} "
+                      f"f32's fastest; the two pick the same action in {100 * same:.2f} % of the worlds (all values finite: {finite})")
+        env.close()
+
+
 def main():
     import numpy as np
     import torch
@@ -90,12 +165,15 @@ def main():
     ap.add_argument("--precision", nargs="+", default=["f32"], choices=["f32", "bf16"], help="decision arithmetics to time, alternated inside every repeat")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch baseline (an A/B of two libraries needs only the kernels)")
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--om", action="store_true", help="the OM-SARL row instead: the float32 and the bf16 wide-row kernel on rows and maps in HBM")
     a = ap.parse_args()
 
     from social_navigation_pyenvs_amd import _lib
     from social_navigation_pyenvs_amd.crowd_nav.policy import value_net
 
     _lib.require_gpu()
+    if a.om:
+        return om_rows(a)
     results = []
     for n in a.humans:
         env = _env(n, a.worlds)
