@@ -498,7 +498,7 @@ def laser_scan(pos, yaw, rng, samples, max_distance, human_pos, human_radius, ob
 
 
 def social_momentum_step(pos, vel, radius, safety, vd, goals, dt, robot=None, n_actions=20, lam=0.11, dtype=np.float64,
-                         amb_eps=None):
+                         amb_eps=None, filter_margins=False):
     """numpy restatement of one update_humans(t, dt) of the social-momentum crowd model
     (/root/reference/social_gym/src/motion_model_manager.py:395-404 with :66-70 update_goals and :247-251 action set;
     /root/reference/social_gym/src/social_momentum.py:10-27 filter, :29-44 reactive agents, :46-75 optimize_momentum).
@@ -509,7 +509,9 @@ def social_momentum_step(pos, vel, radius, safety, vd, goals, dt, robot=None, n_
     arithmetic whenever two agents move with the same velocity, or a candidate action equals the partner's velocity --
     both common with 20 discrete headings and equal speeds -- and the reference then follows float64 rounding noise.
     With `amb_eps` the function also returns, as a 6th value, (lo, hi) [n, A]: the smallest / largest reward each action
-    can get when every pair with |product| < amb_eps may fall either way (a zeroed momentum term or the full sum)."""
+    can get when every pair with |product| < amb_eps may fall either way (a zeroed momentum term or the full sum).
+    With `filter_margins` as well, a 7th value (gap, margin): gap [n, A] = the smallest |next_j - next_i| - thr over the partners (an
+    action is free when it is >= 0), margin [n] = the smallest | |next_j - next_i| - thr | over actions and partners (inf without partners)."""
     pos = np.array(pos, dtype); vel = np.array(vel, dtype); goals = np.array(goals, dtype)
     radius = np.asarray(radius, dtype); safety = np.asarray(safety, dtype); vd = np.asarray(vd, dtype)
     n = len(pos)
@@ -526,6 +528,8 @@ def social_momentum_step(pos, vel, radius, safety, vd, goals, dt, robot=None, n_
     r_lo = np.full((n, n_actions), -np.inf, dtype)
     r_hi = np.full((n, n_actions), -np.inf, dtype)
     chosen = np.full(n, -1)
+    gap = np.full((n, n_actions), np.inf, dtype)        # min over partners of |next_j - next_i| - thr: free <=> gap >= 0
+    margin = np.full(n, np.inf, dtype)                  # min over actions and partners of | |next_j - next_i| - thr |
     new_vel = np.zeros_like(vel)
     for i in range(n):
         gi = goals[i]
@@ -550,54 +554,107 @@ def social_momentum_step(pos, vel, radius, safety, vd, goals, dt, robot=None, n_
             react = others[angle <= np.pi]                                                               # :36-43 (NaN -> not reactive)
             w = 1 / np.linalg.norm(ep[react] - pos[i], axis=-1)
             w = w / np.sum(w)                                                                            # :49-52
-        best, best_a = -100000, -1
-        for a in range(n_actions):
-            if not free[a]:
-                continue
-            nd = np.linalg.norm(goals[i, 0] - (pos[i] + acts[a] * dt))
-            rew = 1 / nd
-            mom = 0
-            mom_full, amb, hard_break = 0, False, False
-            for t, j in enumerate(react):
-                c = (pos[i] + ep[j]) / 2
-                pr, ph = pos[i] - c, ep[j] - c
-                other = ph[0] * ev[j][1] - ph[1] * ev[j][0]
-                cur = pr[0] * vel[i][1] - pr[1] * vel[i][0] + other
-                exp = pr[0] * acts[a][1] - pr[1] * acts[a][0] + other
-                if amb_eps is not None and not hard_break:
-                    if abs(cur * exp) < amb_eps:
-                        amb = True                      # either way: contributes ~0 if kept
-                    elif cur * exp > 0:
-                        mom_full += w[t] * exp
-                    else:
-                        hard_break = True
-            for t, j in enumerate(react):
-                c = (pos[i] + ep[j]) / 2
-                pr, ph = pos[i] - c, ep[j] - c
-                other = ph[0] * ev[j][1] - ph[1] * ev[j][0]
-                cur = pr[0] * vel[i][1] - pr[1] * vel[i][0] + other
-                exp = pr[0] * acts[a][1] - pr[1] * acts[a][0] + other
-                if cur * exp > 0:
-                    mom += w[t] * exp
-                else:
-                    mom = 0
-                    break
-            base_rew = rew
-            rew = rew + lam * mom
-            rewards[i, a] = rew
-            if amb_eps is not None:
-                full = base_rew if hard_break else base_rew + lam * mom_full
-                cands = [full, base_rew] if amb else [full]
-                r_lo[i, a], r_hi[i, a] = min(cands), max(cands)
-            if rew > best:
-                best, best_a = rew, a
+        if len(others):
+            gap[i] = np.min(dist - thr[None], axis=1)
+            margin[i] = np.min(np.abs(dist - thr[None]))
+        # optimize_momentum (:54-75) for all actions at once, term by term as the reference's loops form them: the sums run over the
+        # reactive agents in index order (np.cumsum adds sequentially), and a zero added for a skipped term changes nothing
+        J = len(react)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            base_rew = 1 / np.array([np.linalg.norm(goals[i, 0] - (pos[i] + acts[a] * dt)) for a in range(n_actions)])   # [A]
+            c = (pos[i][None] + ep[react]) / 2
+            pr, ph = pos[i][None] - c, ep[react] - c
+            other = ph[:, 0] * ev[react, 1] - ph[:, 1] * ev[react, 0]                                    # [J]
+            cur = pr[:, 0] * vel[i][1] - pr[:, 1] * vel[i][0] + other
+            exp = pr[None, :, 0] * acts[:, None, 1] - pr[None, :, 1] * acts[:, None, 0] + other[None]   # [A, J]
+            prod = cur[None] * exp
+            keep = prod > 0
+            terms = w[None] * exp
+        if J:
+            mom = np.where(np.all(keep, axis=1), np.cumsum(terms, axis=1)[:, -1], 0)                     # a break zeroes the sum (:70)
+        else:
+            mom = np.zeros(n_actions, dtype)
+        rew_all = base_rew + lam * mom
+        rewards[i] = np.where(free, rew_all, -np.inf)
+        if amb_eps is not None:
+            small = np.abs(prod) < amb_eps                  # either way: contributes ~0 if kept
+            hard = ~small & ~keep
+            before = np.cumsum(hard, axis=1) == 0           # partners the loop reaches before the first sure sign change
+            hard_break = hard.any(axis=1)
+            amb = (small & before).any(axis=1)
+            mom_full = np.cumsum(np.where(before & ~small, terms, 0), axis=1)[:, -1] if J else np.zeros(n_actions, dtype)
+            full = np.where(hard_break, base_rew, base_rew + lam * mom_full)
+            r_lo[i] = np.where(free, np.where(amb, np.minimum(full, base_rew), full), -np.inf)
+            r_hi[i] = np.where(free, np.where(amb, np.maximum(full, base_rew), full), -np.inf)
+        best_a = -1
+        if free.any():
+            a_ = int(np.argmax(np.where(free, rew_all, -np.inf)))                                        # the first maximum (:72)
+            if rew_all[a_] > -100000:
+                best_a = a_
         chosen[i] = best_a
         if best_a >= 0:
             new_vel[i] = acts[best_a]
     new_pos = pos + vel * dt                                                                             # :401-403
+    if amb_eps is not None and filter_margins:
+        return new_pos, new_vel, goals, rewards, chosen, (r_lo, r_hi), (gap, margin)
     if amb_eps is not None:
         return new_pos, new_vel, goals, rewards, chosen, (r_lo, r_hi)
     return new_pos, new_vel, goals, rewards, chosen
+
+
+def social_momentum_block(pos, vel, radius, safety, vd, goals, dt, n_substeps, robot=None, robot_visible=False, robot_safety=0.0,
+                          action=None, kinematics=0, respawn=None, respawn_bounds=(0.0, 0.0), n_actions=20, amb_eps=1e-5):
+    """K = n_substeps of the Gym loop around the social-momentum crowd for W worlds, float64: robot.step(action, dt)
+    (/root/reference/social_gym/src/robot_agent.py:114-136, holonomic ActionXY or unicycle ActionRot; social_nav_gym.py:240-245 calls it
+    before every update), `social_momentum_step`, and -- in the worlds whose `respawn` flag is set -- the parallel-traffic rule of
+    update_humans' post_update branch (motion_model_manager.py:407-422, `respawn`).  respawn=None is post_update=False (the peek path).
+    pos, vel [W, n, 2]; radius, safety, vd [W, n]; goals [W, n, G, 2] NaN-padded; robot None or [W, 13] rows (px, py, yaw, vx, vy, ...,
+    radius at 8), an entity of the crowd only when `robot_visible`; robot_safety, action [W, 2] broadcast.
+    Returns a dict of per-substep records [K, W, ...]: pos, vel, goals, robot (the robot as that substep saw it), respawned [K, W, n] bool,
+    and social_momentum_step's diagnostics rewards, lo, hi, gap [K, W, n, A], chosen, margin [K, W, n]."""
+    pos = np.array(pos, np.float64); vel = np.array(vel, np.float64); goals = np.array(goals, np.float64)
+    W, n = pos.shape[0], pos.shape[1]
+    G = goals.shape[2]
+    bc = lambda a, shape: np.array(np.broadcast_to(np.asarray(a, np.float64), shape))
+    radius, safety, vd = bc(radius, (W, n)), bc(safety, (W, n)), bc(vd, (W, n))
+    rb = None if robot is None else bc(robot, (W, 13))
+    rsafe = bc(robot_safety, (W,))
+    act = None if action is None else bc(action, (W, 2))
+    flags = np.zeros(W, bool) if respawn is None else np.broadcast_to(np.asarray(respawn).astype(bool), (W,))
+    K, A = int(n_substeps), int(n_actions)
+    out = dict(pos=np.empty((K, W, n, 2)), vel=np.empty((K, W, n, 2)), goals=np.empty((K, W, n, G, 2)),
+               robot=None if rb is None else np.empty((K, W, 13)), respawned=np.zeros((K, W, n), bool),
+               rewards=np.empty((K, W, n, A)), lo=np.empty((K, W, n, A)), hi=np.empty((K, W, n, A)), gap=np.empty((K, W, n, A)),
+               chosen=np.empty((K, W, n), int), margin=np.empty((K, W, n)))
+    for k in range(K):
+        if rb is not None and act is not None:
+            if kinematics == 0:                                                                          # robot_agent.py:114-118
+                rb[:, 0:2] += act * dt; rb[:, 3:5] = act
+            else:                                                                                        # robot_agent.py:119-136
+                h = rb[:, 2] + act[:, 1]
+                rb[:, 0] += np.cos(h) * act[:, 0] * dt; rb[:, 1] += np.sin(h) * act[:, 0] * dt
+                rb[:, 2] = np.mod(h, 2 * np.pi)
+                rb[:, 3] = np.cos(rb[:, 2]) * act[:, 0]; rb[:, 4] = np.sin(rb[:, 2]) * act[:, 0]
+        for w in range(W):
+            ent = np.array([*rb[w, 0:2], *rb[w, 3:5], rb[w, 8], rsafe[w]]) if (robot_visible and rb is not None) else None
+            p, v, g, rew, ch, (lo, hi), (gap, margin) = social_momentum_step(pos[w], vel[w], radius[w], safety[w], vd[w], goals[w], dt,
+                                                                              ent, n_actions=A, amb_eps=amb_eps, filter_margins=True)
+            if flags[w]:
+                S = np.zeros((n, 13)); S[:, 0:2] = p; S[:, 8] = radius[w]
+                S, g2 = respawn_rule(S, g, safety[w], None if ent is None else np.array([ent[0], ent[4] + ent[5]]),
+                                     respawn_bounds[0], respawn_bounds[1])
+                out["respawned"][k, w] = np.any(S[:, 0:2] != p, axis=1) | np.any(np.nan_to_num(g2) != np.nan_to_num(g), axis=(1, 2))
+                p, g = S[:, 0:2], g2
+            pos[w], vel[w], goals[w] = p, v, g
+            for name, val in (("rewards", rew), ("lo", lo), ("hi", hi), ("gap", gap), ("chosen", ch), ("margin", margin)):
+                out[name][k, w] = val
+        out["pos"][k], out["vel"][k], out["goals"][k] = pos, vel, goals
+        if rb is not None:
+            out["robot"][k] = rb
+    return out
+
+
+respawn_rule = respawn   # (social_momentum_block's `respawn` argument, named like step_block's, hides the function inside it)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
