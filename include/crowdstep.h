@@ -807,6 +807,39 @@ int cs_value_net_decide_lstm_bf16(const int32_t* dims, int n_dims, const void* d
                                   int32_t* d_choice, float* d_action_out, void* stream);
 
 /*
+ * cs_value_net_decide_lstm_worlds  cs_lookahead followed by cs_value_net_decide_lstm as ONE entry point, without the look-ahead tensor
+ *   (csrc/value_net_lstm_worlds.hip), as cs_value_net_decide_worlds is for CADRL and SARL: the recurrent kernel computes a
+ *   job's frames, rewards and sort keys and generates every step's rows in LDS from the worlds' own rows, so rotated [W][A][n][13|15] --
+ *   431 MB at 4096 worlds x 81 actions x 25 humans -- is neither allocated, written nor gathered back; nothing of size W * A * n is read
+ *   or written.  d_actions [A][2], d_next [W][n][4|6], d_current [W][n][5|7], d_robot [W][robot_stride], robot_stride and dt are exactly
+ *   what cs_lookahead takes; dims, d_weights (cs_value_net_pack_lstm's blob for cols = 13, or 15 with theta_and_omega_visible),
+ *   sorted_by_distance, gamma, d_override, d_values, d_choice and d_action_out exactly what cs_value_net_decide_lstm takes.
+ *   d_rewards_out (may be NULL) receives [W][A], the rewards the kernel computed.  d_values, d_choice, d_action_out and d_rewards_out
+ *   are, bit for bit, those of cs_lookahead followed by cs_value_net_decide_lstm on the same inputs -- the order of tied distances
+ *   included: the sort key is the tensor's column 11, computed by the same function --; a (world, action) gives the same bits for W = 1
+ *   as inside any batch.  Two kernels on `stream`: the network, then the per-world pick.  Errors (CS_ERR_ARG, before any device call):
+ *   those of cs_value_net_decide_lstm and of cs_lookahead with their messages (d_next and d_current are required; robot_stride >= 8;
+ *   sorted_by_distance outside 0..1; n > CS_VN_LSTM_MAX_N, in this entry's name); the LDS-fit check is made for this kernel's own LDS
+ *   (cs_value_net_decide_lstm's buffers and a table of 32 x 8 floats).  The entry takes no `cols`: the column count follows from
+ *   theta_and_omega_visible, and a blob packed for the other count cannot be detected here -- the blobs of 13 and of 15 columns have the
+ *   same size (both round up to two k-groups of 8), the two columns' weights are then zero or unread.  The caller pairs the flag with
+ *   the `cols` it packed for (the Python binding does: decide_lstm_worlds refuses a DeviceNet of the other count).
+ * cs_value_net_decide_lstm_worlds_bf16  the same for cs_value_net_decide_lstm_bf16 (csrc/value_net_lstm_worlds_bf16.hip): that entry's
+ *   arithmetic on the blob of cs_value_net_pack_lstm_bf16 and its length in bytes, bit for bit cs_lookahead followed by
+ *   cs_value_net_decide_lstm_bf16.  No pack entry of their own: the blobs are the tensor entries'.
+ */
+int cs_value_net_decide_lstm_worlds(const int32_t* dims, int n_dims, const float* d_weights, size_t n_weight_floats, int W, int A, int n,
+                                    int theta_and_omega_visible, int sorted_by_distance, const float* d_actions, const float* d_next,
+                                    const float* d_current, const float* d_robot, int robot_stride, float gamma, float dt,
+                                    const int32_t* d_override, float* d_rewards_out /* may be NULL */, float* d_values, int32_t* d_choice,
+                                    float* d_action_out, void* stream);
+int cs_value_net_decide_lstm_worlds_bf16(const int32_t* dims, int n_dims, const void* d_weights, size_t n_weight_bytes, int W, int A, int n,
+                                         int theta_and_omega_visible, int sorted_by_distance, const float* d_actions, const float* d_next,
+                                         const float* d_current, const float* d_robot, int robot_stride, float gamma, float dt,
+                                         const int32_t* d_override, float* d_rewards_out /* may be NULL */, float* d_values,
+                                         int32_t* d_choice, float* d_action_out, void* stream);
+
+/*
  * cs_value_net_loss_grad_lstm  cs_value_net_loss_grad for LSTM-RL (crowd_nav/policy/lstm_rl.py:9-65, ValueNetwork1 and ValueNetwork2;
  *   csrc/value_net_lstm_grad.hip): what crowd_nav/utils/trainer.py:50-71 does per minibatch before optimizer.step() -- zero_grad,
  *   outputs = model(inputs), loss = MSELoss(outputs, values), loss.backward() -- by backpropagation through time, in two launches on `stream`.

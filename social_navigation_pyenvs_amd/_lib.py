@@ -174,6 +174,8 @@ ABI = {
     "cs_value_net_decide_lstm": (I, [P, I, P, Z, I, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
     "cs_value_net_pack_lstm_bf16": (I, [P, I, I, P, P, P]),
     "cs_value_net_decide_lstm_bf16": (I, [P, I, P, Z, I, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P]),
+    "cs_value_net_decide_lstm_worlds": (I, [P, I, P, Z, I, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P, P]),
+    "cs_value_net_decide_lstm_worlds_bf16": (I, [P, I, P, Z, I, I, I, I, I, P, P, P, P, I, F, F, P, P, P, P, P, P]),
     "cs_value_net_grad_sizes_lstm": (I, [P, I, I, I, I, P, P]),
     "cs_value_net_loss_grad_lstm": (I, [P, I, P, Z, P, Z, I, I, I, P, P, P, P, P, P, Z, P]),
     "cs_value_net_pack_lstm_device": (I, [P, I, I, P, Z, P, Z, P]),

@@ -157,6 +157,7 @@ class CADRL(Policy):
         self.decision_precision = "f32"
         self.decision_input = "tensor"
         self.recurrent_precision = "f32"         # (LSTM-RL's own choice, lstm_rl.py set_recurrent_precision; "f32" for every other policy)
+        self.recurrent_input = "tensor"          # (LSTM-RL's own choice, set_recurrent_input below; "tensor" for every other policy)
         self.mapped_precision = "f32"            # (OM-LSTM-RL's own choice, om_lstm_rl.py set_mapped_precision; "f32" for every other policy)
         self.wide_precision = "f32"              # (OM-SARL's own choice, om_sarl.py set_wide_precision; "f32" for every other policy)
 
@@ -194,6 +195,14 @@ class CADRL(Policy):
         rotated [W][A][n][13|15] to HBM, cs_value_net_decide reads it back) or the opt-in "fused" (cs_value_net_decide_worlds generates
         the rows in LDS from the worlds' own rows, bit for bit the same decision).  "fused" is float32 only."""
         self.decision_input = value_net.check_mode(self.family, decision_input, self.decision_precision)
+
+    def set_recurrent_input(self, recurrent_input):
+        """Where the recurrent decision kernel's rows come from, for ``predict`` and ``act_device`` alike: "tensor" (the default: cs_lookahead
+        writes rotated [W][A][n][13|15], the kernel gathers it back one sorted row at a time) or the opt-in "fused"
+        (cs_value_net_decide_lstm_worlds[_bf16] generates every step's rows in LDS from the worlds' own rows, bit for bit the same decision
+        in either ``recurrent_precision``).  "fused" is LSTM-RL's alone: every other policy is refused with the reason (CADRL
+        and SARL have ``set_decision_input``), before anything touches the device."""
+        self.recurrent_input = value_net.check_recurrent_input(recurrent_input, self.family)
 
     def build_action_space(self, v_pref):
         """(0, 0) plus rotation_samples headings x speed_samples exponentially spaced speeds up to v_pref."""
@@ -294,7 +303,7 @@ class CADRL(Policy):
         rot, _ = value_net.decide_for_worlds(net, self.decision_input, self.decision_precision, d_a, d_n, d_c, d_r, self.gamma, self.time_step,
                                              up(np.array([override]), torch.int32), vals, pick, act, stream(),
                                              recurrent_precision=self.recurrent_precision, mapped_precision=self.mapped_precision,
-                                             wide_precision=self.wide_precision)
+                                             wide_precision=self.wide_precision, recurrent_input=self.recurrent_input)
         # (SARL's attention weights read the last action's rows; without the look-ahead tensor they are made when asked for)
         self._last_rotated = rot if rot is not None else (lambda: value_net.lookahead(d_a[-1:].contiguous(), d_n, d_c, d_r, self.time_step, stream()))
         return vals[0].cpu().numpy(), int(pick.item()), act[0].cpu().numpy()

@@ -8,7 +8,9 @@ The decision is cs_lookahead -> cs_value_net_decide_lstm (csrc/value_net_lstm.hi
 dependent LSTM steps and the value MLP of all (world, action) pairs in one kernel, float32 on the look-ahead tensor; ``predict`` is its
 W = 1 launch.  ``set_recurrent_precision("bf16")`` moves ``predict`` and the batched Gym's ``act_device`` to the opt-in bf16 arithmetic
 (cs_value_net_decide_lstm_bf16, csrc/value_net_lstm_bf16.hip); ``state_value``, ``value_device``, ``joint_state_device`` and
-the trainers stay float32.  The reference sorts inside ``predict`` only: ``transform`` keeps the humans' own order, and its trainer evaluates the target
+the trainers stay float32.  ``set_recurrent_input("fused")`` moves both, in either precision, to cs_value_net_decide_lstm_worlds[_bf16]
+(csrc/value_net_lstm_worlds.hip): the kernel generates its rows from the worlds' own, no look-ahead tensor, bit for bit the same decision.
+The reference sorts inside ``predict`` only: ``transform`` keeps the humans' own order, and its trainer evaluates the target
 network on those rows as stored, so ``state_value`` and ``value_device`` evaluate the rows in the order given.  It is a key of its own in
 policy_factory, "lstm_rl_device": ``policy_factory["lstm_rl"]`` keeps raising."""
 from __future__ import annotations
@@ -67,7 +69,8 @@ class LstmRL(MultiHumanRL):
     def set_recurrent_precision(self, precision):
         """The arithmetic of the recurrent decision kernel, for ``predict`` and ``act_device`` alike: "f32" (the default) or the opt-in
         "bf16" (W_hh, network 2's W_ih and the layers behind each chain's first on bf16 matrix instructions, h rounded once a
-        step, c and the accumulation float32).  ``decision_precision`` and ``decision_input`` stay ("f32", "tensor")."""
+        step, c and the accumulation float32).  ``decision_precision`` and ``decision_input`` stay ("f32", "tensor"); combines freely with
+        ``set_recurrent_input`` (cadrl.py: the setter lies beside the attribute, and refuses every policy but this one)."""
         self.recurrent_precision = value_net.check_recurrent_precision(precision, self.family)
 
     def configure(self, config):

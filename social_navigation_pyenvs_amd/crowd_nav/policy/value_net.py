@@ -25,6 +25,12 @@ csrc/value_net_lstm_bf16.hip and csrc/value_net_lstm_om_bf16.hip, under names ap
 ``DeviceNet.refresh_<word>``, ``decide_for_worlds(..., <word>_precision="bf16")`` and a policy's ``set_<word>_precision`` (``LstmRL``: recurrent,
 ``OMLstmRL``: mapped).  ``pack_lstm_bf16`` / ``pack_lstm_om_bf16`` and ``decide_lstm_bf16`` / ``decide_lstm_om_bf16`` are the public names.
 
+RECURRENT also states an input of its own (``Family.worlds``; RECURRENT_INPUTS, ``check_recurrent_input``): "fused" decides from the worlds' own
+rows in either recurrent precision (cs_value_net_decide_lstm_worlds[_bf16], csrc/value_net_lstm_worlds.hip: the recurrent kernels generate
+their rows, no look-ahead tensor), bit for bit the tensor path -- ``decide_lstm_worlds`` / ``decide_lstm_worlds_bf16``,
+``decide_for_worlds(..., recurrent_input="fused")``, a policy's ``set_recurrent_input``.  A name apart from ``set_decision_input``, whose
+"fused" keeps refusing a recurrent net with the sentence it has.
+
 MAPPED states OM-SARL's opt-in bf16 decision (csrc/value_net_om_bf16.hip: mlp1's layer 0 split between float32 rotated columns and bf16 map
 columns, everything behind it the feed-forward bf16 arithmetic) the same way, as an ``OwnArithmetic`` with the word "wide" -- in the row's
 ``wide`` field, not in ``own``: ``MAPPED.own`` is None and ``MAPPED.modes`` holds ("tensor", "f32") alone, so that ``set_decision_precision("bf16")``,
@@ -66,6 +72,7 @@ PRECISIONS = ("f32", "bf16")
 DECISION_INPUTS = ("tensor", "fused")
 RECURRENT_PRECISIONS = ("f32", "bf16")      # of the recurrent family without map columns: "bf16" is cs_value_net_decide_lstm_bf16
 RECURRENT_BF16 = "recurrent_bf16"           # DeviceNet's key of that arithmetic's blob
+RECURRENT_INPUTS = ("tensor", "fused")      # of the same family: "fused" is cs_value_net_decide_lstm_worlds[_bf16], no look-ahead tensor
 MAPPED_PRECISIONS = ("f32", "bf16")         # of the recurrent family with map columns: "bf16" is cs_value_net_decide_lstm_om_bf16
 MAPPED_RECURRENT_BF16 = "mapped_recurrent_bf16"     # the key of that arithmetic's blob, on a DeviceNet of family RECURRENT_MAPPED alone
 WIDE_PRECISIONS = ("f32", "bf16")           # of the feed-forward family with map columns (OM-SARL): "bf16" is cs_value_net_decide_om_bf16
@@ -116,6 +123,7 @@ class Family(NamedTuple):
     train_refusal: str      # the sentence the family's training seams refuse every other net with ({0}: the caller, {1}: the helper to use)
     own: OwnArithmetic = None       # the family's own opt-in arithmetic, where it has one
     wide: OwnArithmetic = None      # MAPPED's: the same statement under the word "wide", apart from `own` (the module's docstring)
+    worlds: frozen = None           # RECURRENT's: recurrent precision -> the decide entry on the worlds' own rows (RECURRENT_INPUTS "fused")
 
     def lead(self, kind):
         return (kind,) if self.takes_kind else ()
@@ -150,7 +158,8 @@ RECURRENT = Family(
             'look-ahead tensor; it decides with "tensor" and "f32"',
     min_humans=1, state_launch=False, train_infix="_lstm", flat_rows=False, train_refusal=RECURRENT_GRADIENT_REFUSAL,
     own=OwnArithmetic(key=RECURRENT_BF16, pack=("cs_value_net_pack_lstm_bf16", np.uint8), decide="cs_value_net_decide_lstm_bf16", word="recurrent",
-                      no_blob='the network has no recurrent bf16 blob yet (DeviceNet.refresh_recurrent("bf16"))'))
+                      no_blob='the network has no recurrent bf16 blob yet (DeviceNet.refresh_recurrent("bf16"))'),
+    worlds=frozen({"f32": "cs_value_net_decide_lstm_worlds", "bf16": "cs_value_net_decide_lstm_worlds_bf16"}))
 RECURRENT_MAPPED = Family(
     pack=frozen({"f32": ("cs_value_net_pack_lstm_om", np.float32)}), takes_kind=False,
     decide=frozen({"f32": "cs_value_net_decide_lstm_om"}), decide_int="om_cols sorted_by_distance map_order", takes_maps=True,
@@ -201,6 +210,20 @@ def check_recurrent_precision(precision, family=None):
                              'cs_value_net_decide_lstm_om, float32 on the look-ahead tensor and the maps')
         raise ValueError('recurrent precision "bf16": the network is not an LSTM-RL one (CADRL and SARL choose with set_decision_precision)')
     return precision
+
+
+def check_recurrent_input(recurrent_input, family=None):
+    """Where the recurrent decision kernel's rows come from, as a policy may hold it: one of RECURRENT_INPUTS; "fused" for the recurrent
+    family without map columns alone (`family`: the policy's or the net's row, None asks only the name)."""
+    if recurrent_input not in RECURRENT_INPUTS:
+        raise ValueError(f"recurrent input {recurrent_input!r}: one of {', '.join(map(repr, RECURRENT_INPUTS))}")
+    if recurrent_input == "fused" and family is not None and family is not RECURRENT:
+        if family is RECURRENT_MAPPED:
+            raise ValueError('recurrent input "fused" for a recurrent network with occupancy-map columns: its kernel pairs every row with a '
+                             "map and has no loader that generates the rows; OM-LSTM-RL decides from the look-ahead tensor")
+        raise ValueError('recurrent input "fused": the network is not an LSTM-RL one (CADRL and SARL choose with set_decision_input; OM-SARL '
+                         "decides from the look-ahead tensor)")
+    return recurrent_input
 
 
 def check_mapped_precision(precision, family=None):
@@ -855,6 +878,44 @@ def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, 
                                                       rewards_out, values, choice, action_out, stream))
 
 
+def _decide_lstm_worlds(caller, precision, net, W, A, n, headed, sorted_by_distance, actions, nxt, cur, robot, robot_stride, gamma, dt, override,
+                        rewards_out, values, choice, action_out, stream):
+    """The RECURRENT row's worlds entry of recurrent precision `precision`, on that arithmetic's blob."""
+    from ... import _lib
+
+    if net.family is not RECURRENT:
+        raise ValueError(f"{caller}: the network is not an LSTM-RL one without map columns (lstm_rl.ValueNetwork1 / ValueNetwork2)")
+    if net.cols != (15 if headed else 13):
+        raise ValueError(f"{caller}: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    if precision == "f32":
+        head = net.head(caller)
+    else:
+        blob = net.blobs[net.family.own.key]
+        if blob is None:
+            raise ValueError(f"{caller}: {net.family.own.no_blob}")
+        head = _head((), net.dims, blob)
+    _lib.check(getattr(_lib.load(), net.family.worlds[precision])(*head, W, A, n, bool(headed), int(bool(sorted_by_distance)), actions, nxt, cur, robot,
+                                                                  robot_stride, gamma, dt, override, rewards_out, values, choice, action_out, stream))
+
+
+def decide_lstm_worlds(net, W, A, n, headed, sorted_by_distance, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out, values,
+                       choice, action_out, stream=None):
+    """cs_value_net_decide_lstm_worlds on device pointers (ints): the decision of ``decide_lstm`` from the worlds' own rows -- what
+    cs_lookahead takes (actions [A][2], nxt [W][n][4|6], cur [W][n][5|7], robot [W][robot_stride]) -- without the look-ahead tensor, bit
+    for bit.  `net` a DeviceNet of an LSTM-RL network whose float32 blob is current and whose cols match `headed`; rewards_out [W][A] or
+    None."""
+    _decide_lstm_worlds("decide_lstm_worlds", "f32", net, W, A, n, headed, sorted_by_distance, actions, nxt, cur, robot, robot_stride, gamma, dt,
+                        override, rewards_out, values, choice, action_out, stream)
+
+
+def decide_lstm_worlds_bf16(net, W, A, n, headed, sorted_by_distance, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out,
+                            values, choice, action_out, stream=None):
+    """cs_value_net_decide_lstm_worlds_bf16 on device pointers (ints): ``decide_lstm_worlds`` in the opt-in bf16 arithmetic -- the decision
+    of ``decide_lstm_bf16``, bit for bit --, for a DeviceNet whose recurrent bf16 blob is current (``refresh_recurrent("bf16")``)."""
+    _decide_lstm_worlds("decide_lstm_worlds_bf16", "bf16", net, W, A, n, headed, sorted_by_distance, actions, nxt, cur, robot, robot_stride, gamma,
+                        dt, override, rewards_out, values, choice, action_out, stream)
+
+
 def state_values(net, W, n, headed, cur, robot, robot_stride, rewards, gamma, dt, rotated_out, values, stream=None):
     """cs_value_net_state on device pointers (ints): the network on the worlds' CURRENT state, for a trainer -- cur [W][n][5|7], robot
     [W][robot_stride] as cs_lookahead takes them; rotated_out [W][n][13|15] or None receives the rotated joint states (``transform``),
@@ -885,16 +946,27 @@ def lookahead(acts, nxt, cur, robot, dt, stream=None):
 
 
 def decide_for_worlds(net, decision_input, precision, acts, nxt, cur, robot, gamma, dt, override, values, choice, action_out, stream=None,
-                      recurrent_precision="f32", mapped_precision="f32", wide_precision="f32"):
+                      recurrent_precision="f32", mapped_precision="f32", wide_precision="f32", recurrent_input="tensor"):
     """The decision of W robots from their worlds' rows (CUDA tensors as ``lookahead`` takes them; override int32 [W] or None; the outputs
     values [W, A], choice [W], action_out [W, 2]), on `stream` (an int): "fused" is decide_worlds alone; "tensor" is lookahead, then
     the family's decide entry with `precision` -- a recurrent net in the decision's order; a net with map columns on occupancy_maps of the
     NEXT humans (the maps the reference's serial branch builds, once per decision; with the net's ``map_order``), which it keeps in
     ``net.last_maps``.  ``recurrent_precision`` / ``mapped_precision`` / ``wide_precision`` "bf16" (the net of that family alone, whose
     ``refresh_recurrent`` / ``refresh_mapped`` / ``refresh_wide("bf16")`` blob is current): the same sequence with the family's own
-    arithmetic.  Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for "fused"."""
+    arithmetic.  ``recurrent_input`` "fused" (RECURRENT_INPUTS; a recurrent net without map columns alone): one library call on the
+    worlds' own rows in either recurrent precision, ``decide_lstm_worlds`` or ``decide_lstm_worlds_bf16``, and no look-ahead tensor.
+    Returns (rotated, rewards), the look-ahead tensors it allocated and the launches read -- (None, None) for either "fused"."""
     (W, n, cc), A = cur.shape, acts.shape[0]
     ovr = None if override is None else override.data_ptr()
+    if check_recurrent_input(recurrent_input, net.family) == "fused":
+        # (a recurrent net without map columns: what the tensor path refuses of the other families' arguments is refused here too)
+        check_mapped_precision(mapped_precision, net.family)
+        check_wide_precision(wide_precision, net.family)
+        check_mode(net.family, decision_input, precision)
+        fused = decide_lstm_worlds if check_recurrent_precision(recurrent_precision, net.family) == "f32" else decide_lstm_worlds_bf16
+        fused(net, W, A, n, cc == 7, 1, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), robot.data_ptr(), robot.shape[1], gamma, dt, ovr, None,
+              values.data_ptr(), choice.data_ptr(), action_out.data_ptr(), stream)
+        return None, None
     # (the order of these checks is which refusal a caller with several bad arguments sees: the mapped precision; with it "bf16" the mode in
     # front of the recurrent precision, else behind it)
     own = check_mapped_precision(mapped_precision, net.family) == "bf16"

@@ -32,8 +32,10 @@
 //               builds of k_value_net_lstm are the preprocessor's LSTM_OM 0 text: the instructions they had before.
 //   shared      with k_value_net_lstm_bf16 (value_net_lstm_bf16.hip), in value_net_lstm_kernel.h: the layer table, a job's start, the rank pass,
 //               the self state, h_n into J, the value store, lstm_layer (both arithmetics; here false, false) and lstm_chain, and the host's
-//               checks and (wreg, mlp1) choice of a decide entry.  This file keeps what is its own: the LDS maps, the pack of the gates, the
-//               gather with map columns, the two kernels around the body and its step loop, the entries.
+//               checks and (wreg, mlp1) choice of a decide entry.  This file keeps what is its own: the pack of the gates, the gather with
+//               map columns, the two kernels around the body and its step loop, the entries (the LDS map is value_net_lstm_f32.h's).
+//   worlds      k_value_net_lstm_worlds (value_net_lstm_worlds.hip, cs_value_net_decide_lstm_worlds) is the body a third time, LSTM_OM 0, with
+//               the three seams of a job's input (value_net_lstm_kernel.h) redefined: its rows are generated from the worlds, not gathered.
 //
 // Numerics: float32.  Every gate pre-activation is one fixed fmaf chain from b_ih + b_hh (summed in float32 by the pack) over the k-groups in
 // descending order (x_t's, then h's); sigmoid(x) = rcp(1 + exp2(-x * log2 e)), tanh(x) = sign(x) * (1 - e) * rcp(1 + e) with e = exp2(-2 |x| * log2 e) on
@@ -42,33 +44,12 @@
 // inside any batch, at any position of a tile.  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include "value_net_lstm_kernel.h"
+#include "value_net_lstm_f32.h"
 
 namespace {
 
-constexpr int RKG = 14;            // register-resident gate weights: k-groups a block (RB blocks a wavefront)
-constexpr int RKG_OM = 15;         // ... of the kernel with map columns: the reference's [om] defaults are 7 blocks x (7 + 8) k-groups
-
-struct LstmLds { int key, perm, X, XH, P, Q, J, LT, total; };
-
-// ldg: the row stride of network 2's gather tile.  share_p: network 1's P lies over the joint rows, which are dead when mlp starts (h_n has
-// gone to J, a barrier behind it) -- the kernel with map columns asks for it where P fits, to stay at two workgroups a CU with its wider rows
-inline LstmLds lstm_lds_map(const LstmPlan& q, int n, int ldg = LDX, bool share_p = false)
-{
-    LstmLds m{};
-    int o = 0;
-    auto take = [&](int floats) { const int at = o; o += up(floats, 4); return at; };
-    m.key = take(TILE_M * n);
-    m.perm = take(TILE_M * n);
-    m.XH = take(2 * TILE_M * q.ld_xh);
-    m.X = q.v.c0[1] > 0 ? take(2 * TILE_M * ldg) : m.XH;
-    m.P = share_p && q.v.c0[1] == 0 && q.v.ld_pq <= 2 * q.ld_xh ? m.XH : take(TILE_M * q.v.ld_pq);
-    m.Q = take(TILE_M * q.v.ld_pq);
-    m.J = take(JROWS * q.v.ld_j);
-    m.LT = take(VN_MAX_LAYERS * 8);
-    m.total = o;
-    return m;
-}
+// (RKG, RKG_OM, the register-resident k-groups, and LstmLds / lstm_lds_map, the LDS map, are value_net_lstm_f32.h's: value_net_lstm_worlds.hip
+// uses them too)
 
 // the gate rows where the lanes of the transposed product read them: row 8 * gate + u of block b is torch's row gate * H + 8 b + u of
 // weight_hh (k-groups below kg_split: h comes first in a joint row) and weight_ih (behind them); bias = b_ih + b_hh in float32; blob zeroed before

@@ -5,7 +5,9 @@
 // (lom_first_layer, lom_x_slot), NX resident slots of the x part.  With LSTM_OM 0 the preprocessor leaves the text k_value_net_lstm_bf16
 // had before the two were one: its four builds keep their device code.  The arithmetic is stated in value_net_lstm_bf16.h; the fixed ends
 // of a job and the layers are value_net_lstm_kernel.h's.  The LSTM_OM 1 declarations stand where k_value_net_lstm_om_bf16 had them, not in
-// one block: moved together in front of `tid` they reordered scalar instructions of its <true, false> build.
+// one block: moved together in front of `tid` they reordered scalar instructions of its <true, false> build.  The input is named through
+// the three seams of value_net_lstm_kernel.h alone: k_value_net_lstm_worlds_bf16 (value_net_lstm_worlds_bf16.hip) is this text under LSTM_OM 0
+// with the seams of value_net_lstm_worlds.h.
     extern __shared__ float lds[];
     constexpr int NB = WREG ? RB : GB;
 #if LSTM_OM
@@ -82,7 +84,7 @@
     }
 #define LH_X_SLOT(ACC, W, J_) lom_x_slot<MLP1>(ACC, W, J_, xrow, mrow)
 #else
-#define LH_GATHER(B, T) lstm_gather(G + (B) * gbuf, LDX, rotated, perm, gbase, ng, n, cols, T);
+#define LH_GATHER(B, T) LSTM_STEP_ROWS(G + (B) * gbuf, LDX, T);
 #define LH_X_SLOT(ACC, W, J_) lh_x_slot<MLP1>(ACC, W, xrow + 8 * (J_))
 #endif
         LH_GATHER(0, 0)
@@ -170,6 +172,6 @@
         lstm_hn_to_j(J, p.ld_j, reinterpret_cast<const __bf16*>(HB + (n & 1) * TILE_M * ldh), 2 * ldh, H, tid);
         __syncthreads();
         const float* out = lstm_chain<LC_BF16_MLP>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
-        lstm_store_values(out, out_ld, gbase, ng, A, rewards, robot, rstride, gamma, dt, values, tid);
+        LSTM_STORE_VALUES(out, out_ld);
         __syncthreads();
     }

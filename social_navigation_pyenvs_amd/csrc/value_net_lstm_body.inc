@@ -3,7 +3,9 @@
 // ones (cs_value_net_decide_lstm_om), the register-resident weights hold RKG_OM k-groups.  With LSTM_OM 0 the preprocessor leaves the text
 // k_value_net_lstm had before there were map columns: its four builds keep their device code.  The fixed ends of a job (LSTM_FILL_TABLE,
 // LSTM_BEGIN_JOB, LSTM_RANK, lstm_self_state, lstm_hn_to_j, lstm_store_values) and the layers (lstm_chain<LC_F32>) are value_net_lstm_kernel.h's,
-// shared with k_value_net_lstm_bf16; the step loop between them is this kernel's own.
+// shared with k_value_net_lstm_bf16; the step loop between them is this kernel's own.  The input is named through the three seams of
+// value_net_lstm_kernel.h alone (LSTM_BEGIN_JOB, LSTM_STEP_ROWS, LSTM_STORE_VALUES): k_value_net_lstm_worlds (value_net_lstm_worlds.hip) is
+// this text under LSTM_OM 0 with the seams of value_net_lstm_worlds.h, which generate the rows from the worlds.
     extern __shared__ float lds[];
     constexpr int NB = WREG ? RB : GB;
 #if LSTM_OM
@@ -72,7 +74,7 @@
 #if LSTM_OM
 #define LSTM_GATHER(X, T) lstm_gather_om(X, ldg, rotated, om, perm, mperm, gbase, ng, A, n, cols, T)
 #else
-#define LSTM_GATHER(X, T) lstm_gather(X, ldg, rotated, perm, gbase, ng, n, cols, T)
+#define LSTM_GATHER(X, T) LSTM_STEP_ROWS(X, ldg, T)
 #endif
         LSTM_GATHER(G, 0);
         float c[NB][4];
@@ -146,6 +148,6 @@
         lstm_hn_to_j(J, p.ld_j, XH + (n & 1) * TILE_M * ldxh, ldxh, H, tid);
         __syncthreads();
         const float* out = lstm_chain<LC_F32>(ltab, p.ld_pq, wb, P, Q, p.c0[1], p.c0[2], J, p.ld_j, nullptr, 0, out_ld);
-        lstm_store_values(out, out_ld, gbase, ng, A, rewards, robot, rstride, gamma, dt, values, tid);
+        LSTM_STORE_VALUES(out, out_ld);
         __syncthreads();
     }

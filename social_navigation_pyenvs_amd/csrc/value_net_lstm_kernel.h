@@ -1,6 +1,7 @@
 // value_net_lstm_kernel.h -- what LSTM-RL's decision kernels share beside their plan (value_net_lstm_plan.h): k_value_net_lstm and
 // k_value_net_lstm_om (value_net_lstm.hip, value_net_lstm_body.inc), k_value_net_lstm_bf16 (value_net_lstm_bf16.hip) and
-// k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip; both value_net_lstm_bf16_body.inc).  Device: the layer
+// k_value_net_lstm_om_bf16 (value_net_lstm_om_bf16.hip; both value_net_lstm_bf16_body.inc), and the two that generate their rows from the
+// worlds, k_value_net_lstm_worlds and k_value_net_lstm_worlds_bf16 (value_net_lstm_worlds[_bf16].hip: the same two texts).  Device: the layer
 // table in LDS, the order of a tile's rows, the ends of a job around its step loop (the step loops themselves differ by design and stay with
 // their kernels), the layer of 32 rows in its two arithmetics and the chain of layers.  Host: what a decide entry does between its plan and
 // its launch.  The gradient kernel (value_net_lstm_grad.hip) needs none of it: the one piece it shares with the step loop here, LSTM_KSTEP, is
@@ -75,16 +76,25 @@ __device__ __forceinline__ void lstm_hn_to_j(float* J, int ld_j, const T* hn, in
     for (int u = tid & 7; u < H; u += 8) J[row8 * ld_j + SELF_DIM + u] = static_cast<float>(hn[row8 * ldh + u]);
 }
 
-// cadrl.py:85-90 compute_action_value of the job's ng sequences; out: the rows of mlp's output, stride out_ld
+// cadrl.py:85-90 compute_action_value of the job's ng sequences; out: the rows of mlp's output, stride out_ld.  rewards: the look-ahead's
+// [W][A] (PITCH 0), or a table of the job's own sequences, PITCH floats apart (the kernels that generate their rows: their frame table)
+template <int PITCH = 0>
 __device__ __forceinline__ void lstm_store_values(const float* out, int out_ld, long gbase, int ng, int A, const float* __restrict__ rewards,
                                                   const float* __restrict__ robot, int rstride, float gamma, float dt, float* __restrict__ values, int tid)
 {
     if (tid < ng) {
         const long g = gbase + tid;
         const float vpref = robot[(g / A) * rstride + 7];
-        values[g] = rewards[g] + powf(gamma, dt * vpref) * out[tid * out_ld];
+        values[g] = rewards[PITCH ? (long)PITCH * tid : g] + powf(gamma, dt * vpref) * out[tid * out_ld];
     }
 }
+
+// The input of a job sits behind three seams, and the two kernel texts (value_net_lstm_body.inc, value_net_lstm_bf16_body.inc) name their
+// input through them alone: LSTM_BEGIN_JOB above (the sort keys), LSTM_STEP_ROWS (the rows perm[s][T] of the tile's sequences into X, rows
+// of stride LD) and LSTM_STORE_VALUES (where a sequence's reward comes from).  Here: the look-ahead tensor `rotated` and `rewards` of the
+// kernel's arguments.  A unit whose kernels generate their rows redefines the three (value_net_lstm_worlds.h).
+#define LSTM_STEP_ROWS(X, LD, T) lstm_gather(X, LD, rotated, perm, gbase, ng, n, cols, T)
+#define LSTM_STORE_VALUES(OUT, OUT_LD) lstm_store_values(OUT, OUT_LD, gbase, ng, A, rewards, robot, rstride, gamma, dt, values, tid)
 
 // One layer of the tile's 32 rows, dst[32][ncb * 32] = act(src[32][K] x Wt + b), the waves over the 32-column output blocks: value_net_plan.h's
 // layer_fwd for one row block and one source -- the same blob layout, the same k order, zeros beyond N -- with the fields from the table in

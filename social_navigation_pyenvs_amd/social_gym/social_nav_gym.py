@@ -725,7 +725,8 @@ class BatchedSocialNavGym:
         (cs_value_net_decide_om_bf16 after the policy's ``set_wide_precision("bf16")``), an
         LSTM-RL instance (``policy_factory["lstm_rl_device"]``) cs_peek -> cs_lookahead -> cs_value_net_decide_lstm, which sorts every
         (world, action)'s humans by decreasing distance inside the kernel (cs_value_net_decide_lstm_bf16 after the policy's
-        ``set_recurrent_precision("bf16")``); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
+        ``set_recurrent_precision("bf16")``; after its ``set_recurrent_input("fused")``, cs_peek -> cs_value_net_decide_lstm_worlds[_bf16] alone,
+        which allocates no look-ahead tensor); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
         the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order (cs_value_net_decide_lstm_om_bf16 after the
         policy's ``set_mapped_precision("bf16")``)."""
         import torch
@@ -822,7 +823,7 @@ class BatchedSocialNavGym:
             rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
                                                    explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream,
                                                    recurrent_precision=pol.recurrent_precision, mapped_precision=pol.mapped_precision,
-                                                   wide_precision=pol.wide_precision)
+                                                   wide_precision=pol.wide_precision, recurrent_input=pol.recurrent_input)
             for t in (nxt, cur_, rob, rot, rew, explore):
                 if t is not None:
                     t.record_stream(side)

@@ -18,8 +18,15 @@ With --om --precision f32 bf16 it is OM-LSTM-RL's kernel instead: cs_value_net_d
 (OMLstmRL.set_mapped_precision) alternated in the same way, once per pairing of rows and maps, the maps already in HBM; the line also says
 whether the bf16 median lies below the float32 median by more than the float32 runs' own min .. max spread.
 
+With --input tensor fused the decision starts from the worlds' own rows (LstmRL.set_recurrent_input): "tensor" is cs_lookahead into a tensor
+allocated once plus cs_value_net_decide_lstm[_bf16] -- the two calls the fused entry replaces --, "fused" is cs_value_net_decide_lstm_worlds[_bf16];
+ALTERNATED repetition by repetition, once per arithmetic of --precision (float32 without it).  The line says whether the fused median lies
+beyond the tensor sequence's own min .. max spread, on which side, and whether the action values are bit-equal.  --input does not combine
+with --om or --only (refused).
+
 Usage:  python tools/time_value_lstm.py [--worlds 4096] [--humans 5 25] [--network 1] [--reps 20] [--warmup 5]
-        [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--precision f32 bf16] [--out profiles/lstm_rl_decision.txt]
+        [--only lstm|sarl|torch|om|maps|omtorch] [--om] [--precision f32 bf16] [--input tensor fused] [--out profiles/lstm_rl_decision.txt]
+        python tools/time_value_lstm.py --input tensor fused --precision f32 bf16 --network 1 --out profiles/lstm_rl_fused_decision.txt   (then --network 2)
         python tools/time_value_lstm.py --om --precision f32 bf16 --network 1 --out profiles/om_lstm_rl_bf16_decision.txt   (then --network 2)
 With --only one variant runs alone, for a `rocprofv3 --kernel-trace --stats -- python tools/time_value_lstm.py --only lstm` run of its own.
 Times are per decision of all worlds: median, minimum and maximum over --reps repetitions, each between two device events.  The work per
@@ -124,8 +131,11 @@ def main():
     ap.add_argument("--only", choices=("lstm", "sarl", "torch", "om", "maps", "omtorch"))
     ap.add_argument("--om", action="store_true")
     ap.add_argument("--precision", nargs="+", choices=("f32", "bf16"), help="time the recurrent kernel in these arithmetics, alternated")
+    ap.add_argument("--input", nargs="+", choices=("tensor", "fused"), help="time LSTM-RL's decision from the worlds' rows with these inputs, alternated")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.input and (args.om or args.only):
+        ap.error("--input times LSTM-RL's decision from the worlds' rows alone: it does not combine with --om or --only")
 
     import torch
 
@@ -209,6 +219,49 @@ def main():
             })
         macs, nbytes = work_per_decision(lstm.model, W, A, n, cols)
         lines.append(f"n = {n}: {macs / 1e9:.2f} G multiply-adds, {nbytes / 1e6:.0f} MB of look-ahead rows per decision")
+        if args.input:
+            # synthetic worlds as cs_lookahead takes them: the humans 2 - 5 m from their robot, the goal 5 m away
+            ang, dist = torch.rand((W, n), generator=g, device="cuda") * 6.2831853, torch.rand((W, n), generator=g, device="cuda") * 3 + 2
+            rob_w = rob.clone()
+            rob_w[:, 0:2] = torch.rand((W, 2), generator=g, device="cuda") * 4 - 2
+            rob_w[:, 5:7] = rob_w[:, 0:2] + torch.tensor([4.0, 3.0], device="cuda")
+            cur = torch.empty((W, n, 5), device="cuda")
+            cur[..., 0], cur[..., 1] = rob_w[:, None, 0] + dist * torch.cos(ang), rob_w[:, None, 1] + dist * torch.sin(ang)
+            cur[..., 2:4], cur[..., 4] = torch.rand((W, n, 2), generator=g, device="cuda") * 2 - 1, 0.3
+            nxt = torch.cat([cur[..., 0:2] + cur[..., 2:4] * dt, cur[..., 2:4]], dim=2).contiguous()
+            lib = _lib.load()
+            world_tail = (rob_w.data_ptr(), rob_w.shape[1], gamma, dt, None)
+            outputs = (vals.data_ptr(), pick.data_ptr(), act.data_ptr(), stream)
+            by_rows = {"f32": ("cs_value_net_decide_lstm", value_net.decide_lstm), "bf16": ("cs_value_net_decide_lstm_bf16", value_net.decide_lstm_bf16)}
+            by_worlds = {"f32": ("cs_value_net_decide_lstm_worlds", value_net.decide_lstm_worlds),
+                         "bf16": ("cs_value_net_decide_lstm_worlds_bf16", value_net.decide_lstm_worlds_bf16)}
+            for p in args.precision or ["f32"]:
+                def tensor_path(p=p):       # (the tensor and the rewards are allocated once: only the two library calls are timed)
+                    _lib.check(lib.cs_lookahead(W, n, A, 0, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), rob_w.data_ptr(), rob_w.shape[1], dt,
+                                                rot.data_ptr(), rew.data_ptr(), stream))
+                    by_rows[p][1](nets["lstm"], W, A, n, 1, rot.data_ptr(), rew.data_ptr(), acts.data_ptr(), *world_tail, *outputs)
+
+                def fused_path(p=p):
+                    by_worlds[p][1](nets["lstm"], W, A, n, False, 1, acts.data_ptr(), nxt.data_ptr(), cur.data_ptr(), *world_tail, None, *outputs)
+
+                paths = {"tensor": ("cs_lookahead + " + by_rows[p][0], tensor_path), "fused": (by_worlds[p][0], fused_path)}
+                got = timed_alternated({k: paths[k][1] for k in args.input}, args.reps, args.warmup)
+                seen = {}
+                for k in args.input:
+                    med, lo, hi = got[k]
+                    lines.append(f"  {p:5s} {k:7s} {paths[k][0]:46s} {med:9.3f}  ({lo:.3f} .. {hi:.3f})")
+                    paths[k][1]()
+                    torch.cuda.synchronize()
+                    seen[k] = vals.clone()
+                if len(got) == 2:
+                    (t_med, t_lo, t_hi), f_med = got["tensor"], got["fused"][0]
+                    gap, spread = t_med - f_med, t_hi - t_lo
+                    word = "WITHIN the spread" if abs(gap) <= spread else ("faster beyond the spread" if gap > 0 else "SLOWER beyond the spread")
+                    lines.append(f"  {p:5s} tensor / fused = {t_med / f_med:.2f} in the medians; the tensor sequence's median minus the fused one is {gap:+.3f} ms, and its "
+                                 f"runs spread over {spread:.3f} ms: fused is {word}; the action values are "
+                                 f"{'bit-equal' if torch.equal(seen['tensor'].view(torch.int32), seen['fused'].view(torch.int32)) else 'DIFFERENT'}; "
+                                 f"{nbytes / 1e6:.0f} MB of rows neither written nor read")
+            continue
         if args.precision and args.om:
             wmacs, _ = work_per_decision(wide.model, W, A, n, cols + C)
             entries = {"f32": ("cs_value_net_decide_lstm_om", value_net.decide_lstm_om), "bf16": ("cs_value_net_decide_lstm_om_bf16", value_net.decide_lstm_om_bf16)}
