@@ -864,6 +864,12 @@ def state_values_for_worlds(net, cur, robot, rewards, gamma, dt, want_rows, stre
     return values, rows if maps is None else torch.cat([rows, maps], dim=2)
 
 
+def _check_cols_headed(caller, net, headed):
+    """The entries that generate their rows take `headed` beside the network: its 13 or 15 input columns must say the same."""
+    if net.cols != (15 if headed else 13):
+        raise ValueError(f"{caller}: a network of {net.cols} input columns and headed={bool(headed)} differ")
+
+
 def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, gamma, dt, override, rewards_out, values, choice, action_out,
                   stream=None):
     """cs_value_net_decide_worlds on device pointers (ints): the decision of ``decide`` from the worlds' own rows -- what cs_lookahead takes
@@ -872,8 +878,7 @@ def decide_worlds(net, W, A, n, headed, actions, nxt, cur, robot, robot_stride, 
     from ... import _lib
 
     head = net.head("decide_worlds")
-    if net.cols != (15 if headed else 13):
-        raise ValueError(f"decide_worlds: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    _check_cols_headed("decide_worlds", net, headed)
     _lib.check(_lib.load().cs_value_net_decide_worlds(*head, W, A, n, bool(headed), actions, nxt, cur, robot, robot_stride, gamma, dt, override,
                                                       rewards_out, values, choice, action_out, stream))
 
@@ -885,8 +890,7 @@ def _decide_lstm_worlds(caller, precision, net, W, A, n, headed, sorted_by_dista
 
     if net.family is not RECURRENT:
         raise ValueError(f"{caller}: the network is not an LSTM-RL one without map columns (lstm_rl.ValueNetwork1 / ValueNetwork2)")
-    if net.cols != (15 if headed else 13):
-        raise ValueError(f"{caller}: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    _check_cols_headed(caller, net, headed)
     if precision == "f32":
         head = net.head(caller)
     else:
@@ -924,8 +928,7 @@ def state_values(net, W, n, headed, cur, robot, robot_stride, rewards, gamma, dt
     from ... import _lib
 
     head = net.head("state_values")
-    if net.cols != (15 if headed else 13):
-        raise ValueError(f"state_values: a network of {net.cols} input columns and headed={bool(headed)} differ")
+    _check_cols_headed("state_values", net, headed)
     _lib.check(_lib.load().cs_value_net_state(*head, W, n, bool(headed), cur, robot, robot_stride, rewards, gamma, dt, rotated_out, values,
                                               stream))
 

@@ -7,8 +7,9 @@
 // One block per world.  Phase 1: one lane per action runs the swept collision test over the humans (sequential, with
 // the reference's early break) and the agent-centric frame of that action into LDS.  Phase 2: one lane per
 // (action, human) element writes a 13- or 15-float row.  The arithmetic of both phases is lookahead_math.h's, shared with the
-// value-network kernel that generates the same rows in LDS (value_net.hip, cs_value_net_decide_worlds).  The output is the HBM cost: 4 * 13 * A * n bytes per world
-// (81 actions x 25 humans: 105 KB), written once; inputs are ~1 KB per world.
+// value-network kernels that generate the same rows in LDS (cs_value_net_decide_worlds, cs_value_net_decide_lstm_worlds[_bf16],
+// cs_value_net_state).  The output is the HBM cost: 4 * 13 * A * n bytes per world (81 actions x 25 humans: 105 KB), written once;
+// inputs are ~1 KB per world.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void k_lookahead(int W, int n, int A, int head
                                                    const float* cur, const float* robot, int rstride, float dt,
                                                    float* rotated, float* rewards)
 {
-    extern __shared__ float lds[]; // [A][8]: ax, ay, nrx, nry, cos, sin, dg, -
+    extern __shared__ float lds[]; // [A][LA_FRAME_FLOATS]: the actions' frames (LA_REWARD unused)
     const int w = blockIdx.x;
     const int nc = headed ? 6 : 4, cc = headed ? 7 : 5, oc = headed ? 15 : 13;
     const float* rb = robot + (long)w * rstride;
@@ -35,9 +36,7 @@ __global__ __launch_bounds__(256) void k_lookahead(int W, int n, int A, int head
         const float ax = actions[2 * a], ay = actions[2 * a + 1];
         const LaStep st = la_step(rb, ax, ay, dt);
         rewards[(long)w * A + a] = la_reward(curw, n, cc, rb, ax, ay, dt, st.dg);
-        float* s = lds + LA_FRAME_FLOATS * a;
-        s[0] = ax; s[1] = ay; s[2] = st.nrx; s[3] = st.nry; s[6] = st.dg;
-        la_frame(st, s[4], s[5]);
+        la_store_frame(lds + LA_FRAME_FLOATS * a, st, ax, ay);
     }
     __syncthreads();
     float* outw = rotated + (long)w * A * n * oc;
@@ -66,7 +65,7 @@ extern "C" int cs_lookahead(int W, int n, int A, int theta_and_omega_visible, co
     if (W <= 0 || n <= 0 || A <= 0) return fail(CS_ERR_ARG, "W, n, A must be positive");
     if (!d_actions || !d_next || !d_current || !d_robot || !d_rotated || !d_rewards) return fail(CS_ERR_ARG, "null argument");
     if (robot_stride < 8) return fail(CS_ERR_ARG, "robot rows need at least 8 columns: px,py,vx,vy,r,gx,gy,v_pref");
-    const size_t shmem = (size_t)A * 8 * sizeof(float);
+    const size_t shmem = (size_t)A * LA_FRAME_FLOATS * sizeof(float);
     if (shmem > 60 * 1024) return fail(CS_ERR_ARG, "action set too large");
     hipLaunchKernelGGL(k_lookahead, dim3(W), dim3(256), shmem, (hipStream_t)stream, W, n, A, theta_and_omega_visible ? 1 : 0,
                        d_actions, d_next, d_current, d_robot, robot_stride, dt, d_rotated, d_rewards);

@@ -4,13 +4,13 @@
 // (world, action) look-ahead groups; here a group is a world as it stands.
 //
 // The kernel is value_net.hip's (value_net_body.inc with A = 1: the same tiles, workgroups, layers and reductions, value_net_f32.h's
-// arithmetic, cs_value_net_pack's blob) with a fourth tile loader, modelled on value_net_worlds.hip's.  Once per job, lane k of wavefront 0
-// computes the frame of world gbase + k from its robot row (lookahead_math.h la_state_frame: the look-ahead frame for action = the robot's
-// velocity and a step of 0) into a table of 32 x 8 floats behind the LDS map; the job's first barrier publishes it.  A tile is written by
-// one lane per (row, four columns) with one ds_write_b128, zero beyond the rows and the columns as load_tile pads; la_row_quad reads the
-// human's current row where the look-ahead has its next row -- the headed layout (px, py, vx, vy, radius, theta, omega) is mapped onto
-// (x, y, yaw, Vx, Vy, Omega) here.  A world in chunks (n > 32) regenerates a chunk at each of SARL's passes.  With d_rotated_out the
-// tile's rows -- one dense run of rows * cols floats of [W][n][cols] -- are also stored from LDS, 16 bytes a lane between the run's first
+// arithmetic, cs_value_net_pack's blob) with a fourth tile loader, value_net_worlds.hip's on other rows (the frame, la_row_quad and
+// la_wave_quad are lookahead_math.h's).  Once per job, lane k of wavefront 0 computes the frame of world gbase + k from its robot row
+// (la_state_frame: the look-ahead frame for action = the robot's velocity and a step of 0) into a table of 32 x LA_FRAME_FLOATS floats
+// behind the LDS map; the job's first barrier publishes it.  A tile is written as there, but la_row_quad reads the human's current row
+// where the look-ahead has its next row -- the headed layout (px, py, vx, vy, radius, theta, omega) is mapped onto (x, y, yaw, Vx, Vy,
+// Omega) here, which is why this loader stays its own.  A world in chunks (n > 32) regenerates a chunk at each of SARL's passes.  With
+// d_rotated_out the tile's rows -- one dense run of rows * cols floats of [W][n][cols] -- are also stored from LDS, 16 bytes a lane between the run's first
 // and last 16-byte boundary (a run starts at any float: cols is odd), the first time the tile holds them.  The rows are cs_lookahead's
 // for (action = robot velocity, dt = 0, next = current) to the last bit.  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
@@ -26,7 +26,7 @@ struct StateRows {
     const float* __restrict__ cur;         // [W][n][5 | 7]
     const float* __restrict__ robot;
     float* __restrict__ rotated_out;       // [W][n][13 | 15] or null
-    float* frames;                         // LDS [JROWS][LA_FRAME_FLOATS]: vx, vy, px, py, cos, sin, dg of the job's worlds (the eighth float is unused)
+    float* frames;                         // LDS [JROWS][LA_FRAME_FLOATS]: the frames of the job's worlds (LA_REWARD unused)
     int rstride, headed, n;
 };
 
@@ -62,12 +62,7 @@ __device__ __forceinline__ void generate_quad(const StateRows& s, const VnBufs& 
 
 __device__ __forceinline__ void generate_tile(const StateRows& s, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
 {
-    switch (threadIdx.x >> 6) {
-    case 0: generate_quad<0>(s, b, t0, g0, ch, rows, per, M); break;
-    case 1: generate_quad<1>(s, b, t0, g0, ch, rows, per, M); break;
-    case 2: generate_quad<2>(s, b, t0, g0, ch, rows, per, M); break;
-    default: generate_quad<3>(s, b, t0, g0, ch, rows, per, M); break;
-    }
+    la_wave_quad([&](auto Q) { generate_quad<Q()>(s, b, t0, g0, ch, rows, per, M); });
 }
 
 // The tile's rows to rotated_out: they are the `rows * cols` floats from float `first` of the dense output on.  Float4 stores between the

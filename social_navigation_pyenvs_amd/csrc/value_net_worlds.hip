@@ -3,15 +3,14 @@
 // look-ahead reads: 431 MB at 4096 worlds x 81 actions x 25 humans) is never written.  Replaces cs_lookahead + cs_value_net_decide, whose
 // results it reproduces bit for bit.
 //
-// The kernel is value_net.hip's (value_net_body.inc: the same groups, tiles, workgroups, layers and reductions) with another tile loader.
-// Once per job, lane k of wavefront 0 computes the frame of the job's group k -- world g / A, action g % A: a job of 32 groups crosses
-// worlds, so world and action are per group -- and lane k of wavefront 1 its reward (the swept collision loop over the humans), into a
-// table of 32 x 8 floats behind the LDS map; the job's first barrier publishes both.  A tile is then written by one lane per (row, four
-// columns): wavefront Q writes columns [4 Q, 4 Q + 4) of row r = lane with one ds_write_b128 (rows are 80 bytes apart), zero beyond the
-// rows and the columns as load_tile pads.  A group in chunks (n > 32) regenerates the rows of a chunk at each of SARL's three passes
-// (human ch * 32 + r); its frame is computed once.  The arithmetic of frame, row and reward is lookahead_math.h's, shared with
-// k_lookahead, so the rows are cs_lookahead's to the last bit.  HBM traffic: the worlds' rows, the weight blob, one float per group (two
-// with d_rewards_out).  No atomics.  gfx950 only.
+// The kernel is value_net.hip's (value_net_body.inc: the same groups, tiles, workgroups, layers and reductions) with another tile loader,
+// built from lookahead_math.h's pieces.  Once per job, la_job_table computes the frames and rewards of the job's groups into a table of
+// 32 x LA_FRAME_FLOATS floats behind the LDS map; the job's first barrier publishes it.  A tile is then written by one lane per (row, four
+// columns): wavefront Q (la_wave_quad) writes columns [4 Q, 4 Q + 4) of row r = lane, la_world_quad<Q> of the row's world and human, with
+// one ds_write_b128 (rows are 80 bytes apart), zero beyond the rows and the columns as load_tile pads.  A group in chunks (n > 32)
+// regenerates the rows of a chunk at each of SARL's three passes (human ch * 32 + r); its frame is computed once.  The arithmetic is the
+// one k_lookahead runs, so the rows are cs_lookahead's to the last bit.  HBM traffic: the worlds' rows, the weight blob, one float per
+// group (two with d_rewards_out).  No atomics.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "lookahead_math.h"
@@ -19,64 +18,25 @@
 
 namespace {
 
-struct WorldRows {
-    const float* __restrict__ actions;
-    const float* __restrict__ next;        // [W][n][4 | 6]
-    const float* __restrict__ cur;         // [W][n][5 | 7]
-    const float* __restrict__ robot;
-    float* __restrict__ rewards_out;       // [W][A] or null
-    float* frames;                         // LDS [JROWS][LA_FRAME_FLOATS]: ax, ay, nrx, nry, cos, sin, dg, reward of the job's groups
-    int rstride, headed, A, n;
-};
-
-__device__ __forceinline__ void begin_job(const WorldRows& s, int gbase, int ng, float dt)
-{
-    const int wave = threadIdx.x >> 6, k = threadIdx.x & 63;
-    if (wave > 1 || k >= ng) return;
-    const int g = gbase + k, w = g / s.A, a = g - w * s.A;
-    const float* rb = s.robot + (long)w * s.rstride;
-    const float ax = s.actions[2 * a], ay = s.actions[2 * a + 1];
-    const LaStep st = la_step(rb, ax, ay, dt);
-    float* f = s.frames + LA_FRAME_FLOATS * k;
-    if (wave == 0) {
-        f[0] = ax; f[1] = ay; f[2] = st.nrx; f[3] = st.nry; f[6] = st.dg;
-        la_frame(st, f[4], f[5]);
-    } else {
-        const int cc = s.headed ? 7 : 5;
-        const float rew = la_reward(s.cur + (long)w * s.n * cc, s.n, cc, rb, ax, ay, dt, st.dg);
-        f[7] = rew;
-        if (s.rewards_out) s.rewards_out[g] = rew;
-    }
-}
-
 // columns [4 Q, 4 Q + 4) of the tile's rows: row r belongs to the tile's group r / per (the job's group t0 + r / per, the launch's g0 + r / per)
 // and is its human ch * M + r % per
 template <int Q>
-__device__ __forceinline__ void generate_quad(const WorldRows& s, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
+__device__ __forceinline__ void generate_quad(const LaWorlds& s, const float* frames, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
 {
     const int r = threadIdx.x & 63;
     if (r >= M) return;
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (r < rows) {
         const int k = r / per, j = ch * M + r - k * per;
-        const int w = (g0 + k) / s.A;
-        const float* rb = s.robot + (long)w * s.rstride;
-        const float* q = s.next + ((long)w * s.n + j) * (s.headed ? 6 : 4);
-        const float hr = s.cur[((long)w * s.n + j) * (s.headed ? 7 : 5) + 4];
-        v = la_row_quad<Q>(s.frames + LA_FRAME_FLOATS * (t0 + k), q, hr, rb[7], rb[4], s.headed != 0);
+        v = la_world_quad<Q>(s, frames + LA_FRAME_FLOATS * (t0 + k), (g0 + k) / s.A, j);
     }
     *reinterpret_cast<float4*>(b.X0 + r * LDX + 4 * Q) = v;
     if (Q == 0) b.grp[r] = r < rows ? r / per : 0;
 }
 
-__device__ __forceinline__ void generate_tile(const WorldRows& s, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
+__device__ __forceinline__ void generate_tile(const LaWorlds& s, const float* frames, const VnBufs& b, int t0, int g0, int ch, int rows, int per, int M)
 {
-    switch (threadIdx.x >> 6) {
-    case 0: generate_quad<0>(s, b, t0, g0, ch, rows, per, M); break;
-    case 1: generate_quad<1>(s, b, t0, g0, ch, rows, per, M); break;
-    case 2: generate_quad<2>(s, b, t0, g0, ch, rows, per, M); break;
-    default: generate_quad<3>(s, b, t0, g0, ch, rows, per, M); break;
-    }
+    la_wave_quad([&](auto Q) { generate_quad<Q()>(s, frames, b, t0, g0, ch, rows, per, M); });
 }
 
 // `frames`: floats from the start of the dynamic block to the frame table, behind the map m that the other two kernels share
@@ -87,11 +47,12 @@ __global__ __launch_bounds__(NT) void k_value_net_worlds(VnPlan p, VnLds m, int 
 {
     extern __shared__ float lds[];
     const int gsum = m.G;
-    const WorldRows world{actions, next, cur, robot, rewards_out, lds + frames, rstride, headed, A, n};
-#define VN_BEGIN_JOB(gbase, ng) begin_job(world, gbase, ng, dt)
+    const LaWorlds world{actions, next, cur, robot, rewards_out, rstride, headed, A, n};
+    float* const table = lds + frames;
+#define VN_BEGIN_JOB(gbase, ng) la_job_table(world, table, gbase, ng, dt)
 #define VN_TILE_SOURCE(g0) const int tile_g0 = (g0)
-#define VN_LOAD_TILE(ch, rows, per) generate_tile(world, b, t0, tile_g0, ch, rows, per, M)
-#define VN_REWARD(g, k) world.frames[LA_FRAME_FLOATS * (k) + 7]
+#define VN_LOAD_TILE(ch, rows, per) generate_tile(world, table, b, t0, tile_g0, ch, rows, per, M)
+#define VN_REWARD(g, k) table[LA_FRAME_FLOATS * (k) + LA_REWARD]
 #include "value_net_body.inc"
 #undef VN_BEGIN_JOB
 #undef VN_TILE_SOURCE
