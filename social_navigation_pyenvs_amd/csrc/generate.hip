@@ -37,63 +37,39 @@ using csimpl::fail;
 using namespace csimpl;
 
 constexpr int GEN_MAXN = 128; // humans per world the per-lane placement arrays hold
+constexpr double PI = 3.141592653589793;
+
+// where a generated world goes (the batch being reset, a staging batch, or the live batch of cs_consume_staged_worlds)
+struct GenOut {
+    float* S; long as, fs; float* goals; float* robot; int* world_flags; int rows, G, robot_row;
+    int orca;     // the batch is an ORCA crowd: columns 5:7 carry RVO2's preferred velocity (orca_pref below)
+};
 
 struct GArgs {
     cs_generator g;
-    int W, rows, G, robot_row;
-    int orca;     // the batch is an ORCA crowd: columns 5:7 carry RVO2's preferred velocity (orca_pref below)
-    float* S;
-    long as, fs;
-    float* goals;
-    float* robot;
-    int* world_flags;
+    int W;        // (in front of `out`: behind it the wavefront kernel spilled 3x the scalar registers and lost 2-5 us a world, HISTORY.md)
+    GenOut out;
     const uint32_t* seeds;
     const int32_t* mask;
     int32_t* status;
     int32_t* scenario_out;
-    uint32_t* mt; // [624][W]
+    uint32_t* mt; // [624][W]: the states of the lane-per-world kernel
 };
 
-struct MT {
-    uint32_t* s;
-    long stride;
-    int pos;
-    __device__ uint32_t& at(int k) { return s[(long)k * stride]; }
-};
+// ---- MT19937 as numpy's legacy stream runs it (numpy/random/src/mt19937/mt19937.c): the pieces both storages below are made of ----
+// one step of mt19937_seed (init_genrand): word i from word i - 1
+__device__ __forceinline__ uint32_t mt_seed_step(uint32_t prev, int i) { return 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i; }
 
-// numpy/random/src/mt19937/mt19937.c: mt19937_seed (init_genrand)
-__device__ void mt_seed(MT& m, uint32_t seed)
-{
-    uint32_t prev = seed;
-    m.at(0) = prev;
-    for (int i = 1; i < 624; ++i) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        m.at(i) = prev;
-    }
-    m.pos = 624;
-}
-
-__device__ void mt_twist(MT& m)
+// word k of the next block (genrand's block update) from old[k], old[k + 1] and the far word: old[k + 397], or new[k - 227] from k = 227 on
+__device__ __forceinline__ uint32_t mt_twist_word(uint32_t w0, uint32_t w1, uint32_t far)
 {
     constexpr uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, MATRIX_A = 0x9908b0dfu;
-    int kk = 0;
-    for (; kk < 624 - 397; ++kk) {
-        const uint32_t y = (m.at(kk) & UPPER) | (m.at(kk + 1) & LOWER);
-        m.at(kk) = m.at(kk + 397) ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
-    }
-    for (; kk < 623; ++kk) {
-        const uint32_t y = (m.at(kk) & UPPER) | (m.at(kk + 1) & LOWER);
-        m.at(kk) = m.at(kk - 227) ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
-    }
-    const uint32_t y = (m.at(623) & UPPER) | (m.at(0) & LOWER);
-    m.at(623) = m.at(396) ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
-    m.pos = 0;
+    const uint32_t y = (w0 & UPPER) | (w1 & LOWER);
+    return far ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
 }
 
-__device__ uint32_t mt_next(MT& m)
+__device__ __forceinline__ uint32_t mt_temper(uint32_t y)
 {
-    if (m.pos >= 624) mt_twist(m);
-    uint32_t y = m.at(m.pos++);
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680u;
     y ^= (y << 15) & 0xefc60000u;
@@ -101,241 +77,66 @@ __device__ uint32_t mt_next(MT& m)
     return y;
 }
 
-// legacy random_sample(): 53-bit double in [0, 1)
-__device__ double rnd(MT& m)
+// legacy random_sample(): the 53-bit double in [0, 1) of two consecutive tempered words
+__device__ __forceinline__ double mt_double(uint32_t ta, uint32_t tb)
 {
-    const uint32_t a = mt_next(m) >> 5, b = mt_next(m) >> 6;
+    const uint32_t a = ta >> 5, b = tb >> 6;
     return (a * 67108864.0 + b) / 9007199254740992.0;
 }
 
-__device__ double uniform(MT& m, double lo, double hi) { return lo + (hi - lo) * rnd(m); }
+// storage 1, one LANE per world: 624 words in a strided global array, twisted in place
+struct MT {
+    uint32_t* s;
+    long stride;
+    int pos;
+    __device__ uint32_t& at(int k) { return s[(long)k * stride]; }
+};
 
-// social_gym/src/utils.py:7-13 (Python's sign-of-divisor modulo == fmod for the operand signs of each branch)
-__device__ double bound_angle_d(double a)
+__device__ void mt_seed(MT& m, uint32_t seed)
 {
-    const double two_pi = 2.0 * 3.141592653589793, pi = 3.141592653589793;
-    if (a >= two_pi) a = fmod(a, two_pi);
-    if (a <= -two_pi) a = fmod(a, two_pi);
-    if (a > pi) a -= two_pi;
-    if (a < -pi) a += two_pi;
-    return a;
+    uint32_t prev = seed;
+    m.at(0) = prev;
+    for (int i = 1; i < 624; ++i) m.at(i) = prev = mt_seed_step(prev, i);
+    m.pos = 624;
 }
 
-__device__ double norm2d(double x, double y) { return sqrt(x * x + y * y); } // np.linalg.norm of a 2-vector
-
-// An ORCA crowd keeps RVO2's preferred velocity in columns 5:7 of its rows (set_state_orca / update_goals_orca,
-// motion_model_manager.py:105-133: (g - p) / |g - p| if |g - p| > desired_speed else (g - p)), set when the simulator is built -- so
-// a world generated on the device must carry it from its first substep on.  float32 on the stored (rounded) columns, as the host
-// form of the same reset computes it (BatchedSocialNavGym._reset_on_device).
-__device__ __forceinline__ void orca_pref(float* s, long fs, float px, float py, float gx, float gy, float vd)
+__device__ void mt_twist(MT& m)
 {
-    const float dx = gx - px, dy = gy - py;
-    const float dn = sqrtf(dx * dx + dy * dy);
-    const float dd = dn > 1e-30f ? dn : 1e-30f;
-    s[5 * fs] = dn > vd ? dx / dd : dx;
-    s[6 * fs] = dn > vd ? dy / dd : dy;
+    for (int kk = 0; kk < 624 - 397; ++kk) m.at(kk) = mt_twist_word(m.at(kk), m.at(kk + 1), m.at(kk + 397));
+    for (int kk = 624 - 397; kk < 623; ++kk) m.at(kk) = mt_twist_word(m.at(kk), m.at(kk + 1), m.at(kk - 227));
+    m.at(623) = mt_twist_word(m.at(623), m.at(0), m.at(396));
+    m.pos = 0;
 }
 
-__global__ __launch_bounds__(64) void k_generate(const GArgs a)
+__device__ uint32_t mt_next(MT& m)
 {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= a.W) return;
-    if (a.mask != nullptr && a.mask[w] == 0) return;
-    const cs_generator& g = a.g;
-    const int n = g.n;
-    const double pi = 3.141592653589793;
-    MT m{a.mt + w, (long)a.W, 624};
-    const uint32_t seed = a.seeds[w];
-    mt_seed(m, seed);
-    int scenario = g.scenario;
-    if (scenario == CS_SCN_HYBRID) { // np.random.choice(['circle_crossing', 'parallel_traffic']); np.random.seed(seed)
-        scenario = (mt_next(m) & 1u) ? CS_SCN_PARALLEL_TRAFFIC : CS_SCN_CIRCULAR_CROSSING;
-        mt_seed(m, seed);
-    }
-    double px[GEN_MAXN], py[GEN_MAXN], yaw[GEN_MAXN], rad[GEN_MAXN], spd[GEN_MAXN];
-    int status = 0;
-    const double R = g.circle_radius, L = g.traffic_length, H = g.traffic_height, rr = g.robot_radius;
-    double rpx = 0, rpy = 0, ryaw = 0, rgx = 0, rgy = 0;
-    const bool insert_robot = g.insert_robot != 0;
-
-    if (scenario == CS_SCN_CIRCULAR_CROSSING || scenario == CS_SCN_PARALLEL_TRAFFIC) {
-        for (int i = 0; i < n; ++i) { // one speed draw then one radius draw per human (:217-220)
-            if (g.randomize_attributes) { spd[i] = uniform(m, 0.5, 1.5); rad[i] = uniform(m, 0.3, 0.5); }
-            else { spd[i] = 1.0; rad[i] = 0.3; }
-        }
-    }
-    if (scenario == CS_SCN_CIRCULAR_CROSSING) {
-        rpx = 0.0; rpy = 0.0 - R; ryaw = pi / 2.0; rgx = 0.0; rgy = 0.0 + R;
-        if (!g.randomize_positions) { // evenly spaced (:231-251)
-            const int slots = n + (insert_robot ? 1 : 0);
-            const double step = (2.0 * pi) / slots;
-            for (int i = 0; i < n; ++i) {
-                const int k = insert_robot ? i + 1 : i;
-                const double off = insert_robot ? -(pi / 2.0) : 0.0;
-                px[i] = 0.0 + R * cos(off + step * k); py[i] = 0.0 + R * sin(off + step * k);
-                yaw[i] = insert_robot ? bound_angle_d((pi / 2.0) + step * k) : bound_angle_d(-pi + step * k);
-            }
-        } else {
-            for (int i = 0; i < n && status == 0; ++i) {
-                bool placed = false;
-                for (int t = 0; t < g.max_tries; ++t) {
-                    const double angle = rnd(m) * pi * 2.0;
-                    const double nx = (rnd(m) - 0.5) * spd[i];
-                    const double ny = (rnd(m) - 0.5) * spd[i];
-                    const double x = 0.0 + R * cos(angle) + nx, y = 0.0 + R * sin(angle) + ny;
-                    bool collide = false;
-                    for (int j = 0; j < i; ++j) {
-                        const double md = rad[i] + rad[j] + 0.2;
-                        // goal of a placed human: (-x + 2 cx, -y + 2 cx)  (:280 uses the centre's x twice; cx = cy = 0)
-                        if (norm2d(x - px[j], y - py[j]) < md || norm2d(x - (-px[j] + 0.0), y - (-py[j] + 0.0)) < md) {
-                            collide = true;
-                            break;
-                        }
-                    }
-                    if (insert_robot && (norm2d(x - rpx, y - rpy) < rad[i] + rr + 0.2 || norm2d(x - rgx, y - rgy) < rad[i] + rr + 0.2))
-                        collide = true;
-                    if (!collide) {
-                        px[i] = x; py[i] = y; yaw[i] = bound_angle_d(pi + angle);
-                        placed = true;
-                        break;
-                    }
-                }
-                if (!placed) status = 1;
-            }
-        }
-    } else if (scenario == CS_SCN_PARALLEL_TRAFFIC) {
-        rpx = -(L / 2.0) + 1.0; rpy = 0.0; ryaw = 0.0; rgx = (L / 2.0) - 1.0; rgy = 0.0;
-        double area = 0.0;
-        for (int i = 0; i < n; ++i) area += pi * (rad[i] * rad[i]);
-        if (area > L * H * 0.4) status = 2; // ValueError in the reference (:318-319)
-        for (int i = 0; i < n && status == 0; ++i) {
-            bool placed = false;
-            for (int t = 0; t < g.max_tries; ++t) {
-                const double lo = -(L / 2.0) + rad[i], hi = L / 2.0 - rad[i];
-                const double x = (hi - lo) * rnd(m) + lo;
-                const double y = (rnd(m) - 0.5) * H;
-                bool collide = false;
-                for (int j = 0; j < i; ++j)
-                    if (norm2d(x - px[j], y - py[j]) - rad[i] - rad[j] - 0.1 < 0.0) { collide = true; break; }
-                if (insert_robot && norm2d(x - rpx, y - rpy) - rad[i] - rr - 0.1 < 0.0) collide = true;
-                if (!collide) {
-                    px[i] = x; py[i] = y; yaw[i] = bound_angle_d(-pi);
-                    placed = true;
-                    break;
-                }
-            }
-            if (!placed) status = 1;
-        }
-    } else { // circular crossing with static obstacles
-        rpx = 0.0; rpy = 0.0 - R; ryaw = pi / 2.0; rgx = 0.0; rgy = 0.0 + R;
-        const double inner = R - 3.0;
-        for (int i = 0; i < n; ++i) { // the three "obstacles" are immobile humans with a drawn radius (:381-387)
-            if (i < 3) { spd[i] = 0.0; rad[i] = 1.0 + (rnd(m) - 1.0) * 0.4; }
-            else { spd[i] = 1.0; rad[i] = 0.3; }
-        }
-        const double sector = pi / (double)(n / 2);
-        for (int i = 0; i < n && status == 0; ++i) {
-            bool placed = false;
-            for (int t = 0; t < g.max_tries; ++t) {
-                double angle, nx, ny, ring;
-                if (i < 3) {
-                    angle = sector * (-0.5 + 2.0 * i + (rnd(m) - 0.5) * 0.5);
-                    nx = (rnd(m) - 0.5) * 0.1; ny = (rnd(m) - 0.5) * 0.1;
-                    ring = inner;
-                } else {
-                    angle = sector * (0.5 + 2.0 * i + (rnd(m) - 0.5) * 0.5);
-                    nx = (rnd(m) - 0.5) * 0.7; ny = (rnd(m) - 0.5) * 0.7;
-                    ring = R;
-                }
-                const double x = 0.0 + ring * cos(angle) + nx, y = 0.0 + ring * sin(angle) + ny;
-                bool collide = false;
-                for (int j = 0; j < i; ++j) {
-                    const double md = rad[i] + rad[j] + 0.2;
-                    const double gxj = (j < 3) ? px[j] : (-px[j] + 0.0), gyj = (j < 3) ? py[j] : (-py[j] + 0.0);
-                    if (norm2d(x - px[j], y - py[j]) < md || norm2d(x - gxj, y - gyj) < md) { collide = true; break; }
-                }
-                if (norm2d(x - rpx, y - rpy) < rad[i] + rr + 0.2 || norm2d(x - rgx, y - rgy) < rad[i] + rr + 0.2) collide = true;
-                if (!collide) {
-                    px[i] = x; py[i] = y; yaw[i] = bound_angle_d(pi + angle);
-                    placed = true;
-                    break;
-                }
-            }
-            if (!placed) status = 1;
-        }
-    }
-    if (a.status != nullptr) a.status[w] = status;
-    if (a.scenario_out != nullptr) a.scenario_out[w] = scenario;
-    if (status != 0) return; // the rows of a world that could not be generated are left untouched
-
-    // ---- rows: [px,py,theta,vx,vy,bvx,bvy,omega,r,m,gx,gy,vd]  (agent.py:256-258), goals [n][G][2] NaN-padded
-    const float nanf_ = __builtin_nanf("");
-    for (int i = 0; i < n; ++i) {
-        double g0x, g0y, g1x, g1y;
-        int ng;
-        if (scenario == CS_SCN_PARALLEL_TRAFFIC) { g0x = -(L / 2.0) - 3.0; g0y = py[i]; g1x = g1y = 0; ng = 1; }
-        else if (scenario == CS_SCN_CIRCULAR_CROSSING_STATIC_OBSTACLES && i < 3) { g0x = px[i]; g0y = py[i]; g1x = px[i]; g1y = py[i]; ng = 2; }
-        else { g0x = 0.0 * 2.0 - px[i]; g0y = 0.0 * 2.0 - py[i]; g1x = px[i]; g1y = py[i]; ng = 2; }
-        float* s = a.S + ((long)w * a.rows + i) * a.as;
-        const long fs = a.fs;
-        s[0] = (float)px[i]; s[fs] = (float)py[i]; s[2 * fs] = (float)yaw[i];
-        for (int c = 3; c < 8; ++c) s[c * fs] = 0.0f;
-        s[8 * fs] = (float)rad[i]; s[9 * fs] = (float)g.human_mass; s[10 * fs] = (float)g0x; s[11 * fs] = (float)g0y;
-        s[12 * fs] = (float)spd[i];
-        if (a.orca) orca_pref(s, fs, (float)px[i], (float)py[i], (float)g0x, (float)g0y, (float)spd[i]);
-        float* gl = a.goals + ((long)w * n + i) * a.G * 2;
-        for (int k = 0; k < a.G; ++k) {
-            float gx = nanf_, gy = nanf_;
-            if (k == 0) { gx = (float)g0x; gy = (float)g0y; }
-            else if (k == 1 && ng == 2) { gx = (float)g1x; gy = (float)g1y; }
-            gl[2 * k] = gx; gl[2 * k + 1] = gy;
-        }
-    }
-    // robot safe-state row (social_nav_gym.py:211-213: robot.set(px, py, gx, gy, 0, 0, yaw, w=0))
-    auto robot_row = [&](float* o, long fs) {
-        o[0] = (float)rpx; o[fs] = (float)rpy; o[2 * fs] = (float)ryaw;
-        for (int c = 3; c < 8; ++c) o[c * fs] = 0.0f;
-        o[8 * fs] = (float)rr; o[9 * fs] = (float)g.robot_mass; o[10 * fs] = (float)rgx; o[11 * fs] = (float)rgy;
-        o[12 * fs] = (float)g.robot_desired_speed;
-    };
-    if (a.robot != nullptr) robot_row(a.robot + (long)w * 13, 1);
-    if (a.robot_row) robot_row(a.S + ((long)w * a.rows + n) * a.as, a.fs);
-    if (a.world_flags != nullptr) a.world_flags[w] = (scenario == CS_SCN_PARALLEL_TRAFFIC) ? 1 : 0; // respawn rule on (:359-360)
+    if (m.pos >= 624) mt_twist(m);
+    return mt_temper(m.at(m.pos++));
 }
 
-// ------------------------------------------------------------------------------------------
-// One WAVEFRONT per world (n <= 64): the latency form, used for the masked auto-reset inside a device-resident loop.
-// MT19937 state in LDS (the current block and its successor, twisted cooperatively); attribute draws are read as wave-wide
-// broadcasts.  The rejection loops of the circular crossing and of the parallel traffic are SPECULATIVE: eight attempts of
-// the human being placed are evaluated at once, each from its own words of the stream by eight lanes that share the test
-// against the placed humans (kept in LDS); the first accepted attempt wins and the stream position moves to just behind
-// it, so a human mostly costs one round whatever its rejection count -- the slowest world of a batch no longer sets the
-// latency of a masked reset.
-// Same draws, same f64 expressions, same accept / reject decisions as k_generate above.
-// ------------------------------------------------------------------------------------------
+__device__ double rnd(MT& m)
+{
+    const uint32_t a = mt_next(m), b = mt_next(m);
+    return mt_double(a, b);
+}
+
+// storage 2, one WAVEFRONT per world: the block the stream is in and its successor in LDS, twisted cooperatively and out of place
 struct WMT {
     uint32_t* cur; // [624] in LDS: the block the stream is in
     uint32_t* nxt; // [624] in LDS: twist(cur), kept ready so that speculative attempts can read across the block boundary
     int pos;       // wave-uniform index into cur; 624 <= pos < 1248 means "in nxt" until the next advance
 };
 
-// nw = twist(old) (genrand's block update, out of place), cooperatively: chunks of 64 in increasing order -- element kk reads
-// old[kk], old[kk + 1] and either old[kk + 397] (kk < 227) or nw[kk - 227], written at least three chunks earlier
+// nw = twist(old), cooperatively: chunks of 64 in increasing order -- element kk reads old[kk], old[kk + 1] and either old[kk + 397]
+// (kk < 227) or nw[kk - 227], written at least three chunks earlier
 __device__ void wmt_twist_from(const uint32_t* old, uint32_t* nw, int lane)
 {
-    constexpr uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, MATRIX_A = 0x9908b0dfu;
     for (int k0 = 0; k0 < 623; k0 += 64) {
         const int kk = k0 + lane;
-        if (kk < 623) {
-            const uint32_t y = (old[kk] & UPPER) | (old[kk + 1] & LOWER);
-            nw[kk] = (kk < 227 ? old[kk + 397] : nw[kk - 227]) ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
-        }
+        if (kk < 623) nw[kk] = mt_twist_word(old[kk], old[kk + 1], kk < 227 ? old[kk + 397] : nw[kk - 227]);
         __syncthreads();
     }
-    if (lane == 0) {
-        const uint32_t y = (old[623] & UPPER) | (nw[0] & LOWER);
-        nw[623] = nw[396] ^ (y >> 1) ^ ((y & 1u) ? MATRIX_A : 0u);
-    }
+    if (lane == 0) nw[623] = mt_twist_word(old[623], nw[0], nw[396]);
     __syncthreads();
 }
 
@@ -345,10 +146,7 @@ __device__ void wmt_seed(WMT& m, uint32_t seed, int lane)
     if (lane == 0) { // the init_genrand recurrence is serial
         uint32_t prev = seed;
         m.cur[0] = prev;
-        for (int i = 1; i < 624; ++i) {
-            prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-            m.cur[i] = prev;
-        }
+        for (int i = 1; i < 624; ++i) m.cur[i] = prev = mt_seed_step(prev, i);
     }
     __syncthreads();
     wmt_twist_from(m.cur, m.nxt, lane);
@@ -363,15 +161,6 @@ __device__ void wmt_advance(WMT& m, int lane)   // the stream has left `cur`: ma
     wmt_twist_from(m.cur, m.nxt, lane);
 }
 
-__device__ __forceinline__ uint32_t mt_temper(uint32_t y)
-{
-    y ^= (y >> 11);
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= (y >> 18);
-    return y;
-}
-
 __device__ uint32_t wmt_next(WMT& m, int lane)
 {
     if (m.pos >= 624) wmt_advance(m, lane);
@@ -380,8 +169,8 @@ __device__ uint32_t wmt_next(WMT& m, int lane)
 
 __device__ double wrnd(WMT& m, int lane)
 {
-    const uint32_t a = wmt_next(m, lane) >> 5, b = wmt_next(m, lane) >> 6;
-    return (a * 67108864.0 + b) / 9007199254740992.0;
+    const uint32_t a = wmt_next(m, lane), b = wmt_next(m, lane);
+    return mt_double(a, b);
 }
 
 // random_sample() number q of the stream counted from word index k0 (k0 < 624, read-ahead below 1248), without consuming it
@@ -390,10 +179,258 @@ __device__ __forceinline__ double wmt_peek_double(const WMT& m, int k0, int q)
     const int k = k0 + 2 * q;
     const uint32_t wa = (k < 624) ? m.cur[k] : m.nxt[k - 624];
     const uint32_t wb = (k + 1 < 624) ? m.cur[k + 1] : m.nxt[k + 1 - 624];
-    const uint32_t a = mt_temper(wa) >> 5, b = mt_temper(wb) >> 6;
-    return (a * 67108864.0 + b) / 9007199254740992.0;
+    return mt_double(mt_temper(wa), mt_temper(wb));
 }
 
+// ---- the reference's rules as functions of values: they read no stream and do not know which kernel calls them ----------------------
+// social_gym/src/utils.py:7-13 (Python's sign-of-divisor modulo == fmod for the operand signs of each branch)
+__device__ double bound_angle_d(double a)
+{
+    const double two_pi = 2.0 * PI;
+    if (a >= two_pi) a = fmod(a, two_pi);
+    if (a <= -two_pi) a = fmod(a, two_pi);
+    if (a > PI) a -= two_pi;
+    if (a < -PI) a += two_pi;
+    return a;
+}
+
+__device__ double norm2d(double x, double y) { return sqrt(x * x + y * y); } // np.linalg.norm of a 2-vector
+
+struct P2 { double x, y; };
+
+// the scenario frame: where the robot starts, where it looks and where it goes (centre (0, 0): the reference's cx, cy)
+struct Frame { double px, py, yaw, gx, gy; };
+
+__device__ __forceinline__ Frame scenario_frame(int scenario, double R, double L)
+{
+    if (scenario == CS_SCN_PARALLEL_TRAFFIC) return Frame{-(L / 2.0) + 1.0, 0.0, 0.0, (L / 2.0) - 1.0, 0.0};
+    return Frame{0.0, 0.0 - R, PI / 2.0, 0.0, 0.0 + R}; // the circular crossing, with and without static obstacles
+}
+
+// attributes of human i: the random_sample() draws they take, in order, and what the draws give
+__device__ __forceinline__ int attribute_draws(const cs_generator& g, bool obstacles, int i)
+{
+    if (obstacles) return i < 3 ? 1 : 0;
+    return g.randomize_attributes ? 2 : 0;
+}
+
+__device__ __forceinline__ void attributes(const cs_generator& g, bool obstacles, int i, double d0, double d1, double& spd, double& rad)
+{
+    spd = 1.0; rad = 0.3;
+    if (obstacles) {                                              // the three "obstacles" are immobile humans with a drawn radius (:381-387)
+        if (i < 3) { spd = 0.0; rad = 1.0 + (d0 - 1.0) * 0.4; }
+    } else if (g.randomize_attributes) {                          // uniform(0.5, 1.5) speed then uniform(0.3, 0.5) radius (:217-220)
+        spd = 0.5 + (1.5 - 0.5) * d0; rad = 0.3 + (0.5 - 0.3) * d1;
+    }
+}
+
+// parallel traffic: ValueError in the reference when the humans cover more than 40 % of the box (:318-319)
+__device__ __forceinline__ bool traffic_too_dense(const double* rad, int n, double L, double H)
+{
+    double area = 0.0;
+    for (int i = 0; i < n; ++i) area += PI * (rad[i] * rad[i]);
+    return area > L * H * 0.4;
+}
+
+// the candidate position of one attempt, from its draws in stream order (d0, d1, d2) and the caller's (cos, sin) of the attempt's angle
+__device__ __forceinline__ double circle_angle(double d0) { return d0 * PI * 2.0; }
+
+__device__ __forceinline__ P2 circle_candidate(double R, double spd, double d1, double d2, double ca, double sa)
+{
+    const double nx = (d1 - 0.5) * spd, ny = (d2 - 0.5) * spd;
+    return P2{0.0 + R * ca + nx, 0.0 + R * sa + ny};
+}
+
+__device__ __forceinline__ P2 traffic_candidate(double L, double H, double rad, double d0, double d1)
+{
+    const double lo = -(L / 2.0) + rad, hi = L / 2.0 - rad;
+    return P2{(hi - lo) * d0 + lo, (d1 - 0.5) * H};
+}
+
+__device__ __forceinline__ double static_angle(int n, int i, double d0) // obstacles in the even sectors, humans in the odd ones
+{
+    const double sector = PI / (double)(n / 2);
+    return sector * ((i < 3 ? -0.5 : 0.5) + 2.0 * i + (d0 - 0.5) * 0.5);
+}
+
+__device__ __forceinline__ P2 static_candidate(double R, int i, double d1, double d2, double ca, double sa)
+{
+    const double noise = i < 3 ? 0.1 : 0.7, ring = i < 3 ? R - 3.0 : R; // obstacles stand on the inner circle
+    const double nx = (d1 - 0.5) * noise, ny = (d2 - 0.5) * noise;
+    return P2{0.0 + ring * ca + nx, 0.0 + ring * sa + ny};
+}
+
+// the spot a placed human keeps free besides its own: its goal as the rejection test states it -- (-x + 2 cx, -y + 2 cx), :280 uses
+// the centre's x twice, cx = cy = 0 --, or, for a static obstacle, where it stands
+__device__ __forceinline__ P2 kept_free(bool obstacle, double x, double y) { return obstacle ? P2{x, y} : P2{-x + 0.0, -y + 0.0}; }
+
+// slot i of the evenly spaced circle (:231-251); the robot, when inserted, takes slot 0 at the bottom
+__device__ __forceinline__ void fixed_circle_slot(double R, int n, bool insert_robot, int i, double& x, double& y, double& yaw)
+{
+    const int slots = n + (insert_robot ? 1 : 0);
+    const double step = (2.0 * PI) / slots;
+    const int k = insert_robot ? i + 1 : i;
+    const double off = insert_robot ? -(PI / 2.0) : 0.0;
+    x = 0.0 + R * cos(off + step * k); y = 0.0 + R * sin(off + step * k);
+    yaw = insert_robot ? bound_angle_d((PI / 2.0) + step * k) : bound_angle_d(-PI + step * k);
+}
+
+// the goals of human i placed at (x, y): the far end of the corridor, its own spot twice (a static obstacle), or the opposite point and back
+struct Goals { double x0, y0, x1, y1; int count; };
+
+__device__ __forceinline__ Goals human_goals(int scenario, double L, int i, double x, double y)
+{
+    if (scenario == CS_SCN_PARALLEL_TRAFFIC) return Goals{-(L / 2.0) - 3.0, y, 0.0, 0.0, 1};
+    if (scenario == CS_SCN_CIRCULAR_CROSSING_STATIC_OBSTACLES && i < 3) return Goals{x, y, x, y, 2};
+    return Goals{0.0 * 2.0 - x, 0.0 * 2.0 - y, x, y, 2};
+}
+
+// ---- the row store -------------------------------------------------------------------------------------------------------------------
+// An ORCA crowd keeps RVO2's preferred velocity in columns 5:7 of its rows (set_state_orca / update_goals_orca,
+// motion_model_manager.py:105-133: (g - p) / |g - p| if |g - p| > desired_speed else (g - p)), set when the simulator is built -- so
+// a world generated on the device must carry it from its first substep on.  float32 on the stored (rounded) columns, as the host
+// form of the same reset computes it (BatchedSocialNavGym._reset_on_device).
+__device__ __forceinline__ void orca_pref(float* s, long fs, float px, float py, float gx, float gy, float vd)
+{
+    const float dx = gx - px, dy = gy - py;
+    const float dn = sqrtf(dx * dx + dy * dy);
+    const float dd = dn > 1e-30f ? dn : 1e-30f;
+    s[5 * fs] = dn > vd ? dx / dd : dx;
+    s[6 * fs] = dn > vd ? dy / dd : dy;
+}
+
+// one agent at rest: [px,py,theta,vx,vy,bvx,bvy,omega,r,m,gx,gy,vd]  (agent.py:256-258), rounded to f32 here and nowhere earlier
+__device__ __forceinline__ void store_row(float* o, long fs, double x, double y, double yaw, double rad, double mass, double gx, double gy, double vd)
+{
+    o[0] = (float)x; o[fs] = (float)y; o[2 * fs] = (float)yaw;
+    for (int c = 3; c < 8; ++c) o[c * fs] = 0.0f;
+    o[8 * fs] = (float)rad; o[9 * fs] = (float)mass; o[10 * fs] = (float)gx; o[11 * fs] = (float)gy;
+    o[12 * fs] = (float)vd;
+}
+
+// human i of world w: its row, an ORCA crowd's preferred velocity, and its goal list [G][2], NaN-padded
+__device__ __forceinline__ void store_human(const cs_generator& g, const GenOut& a, int scenario, int w, int i, double x, double y, double yaw,
+                                            double rad, double spd)
+{
+    const Goals gl = human_goals(scenario, g.traffic_length, i, x, y);
+    float* s = a.S + ((long)w * a.rows + i) * a.as;
+    store_row(s, a.fs, x, y, yaw, rad, g.human_mass, gl.x0, gl.y0, spd);
+    if (a.orca) orca_pref(s, a.fs, (float)x, (float)y, (float)gl.x0, (float)gl.y0, (float)spd);
+    const float nanf_ = __builtin_nanf("");
+    float* o = a.goals + ((long)w * g.n + i) * a.G * 2;
+    for (int k = 0; k < a.G; ++k) {
+        float gx = nanf_, gy = nanf_;
+        if (k == 0) { gx = (float)gl.x0; gy = (float)gl.y0; }
+        else if (k == 1 && gl.count == 2) { gx = (float)gl.x1; gy = (float)gl.y1; }
+        o[2 * k] = gx; o[2 * k + 1] = gy;
+    }
+}
+
+// the robot's safe-state row (social_nav_gym.py:211-213: robot.set(px, py, gx, gy, 0, 0, yaw, w=0)) in the robot buffer and, where the
+// batch has one, in the state row behind the humans; the flag of the traffic's respawn rule (:359-360)
+__device__ __forceinline__ void store_robot_and_flag(const cs_generator& g, const GenOut& a, int scenario, int w, const Frame& f)
+{
+    if (a.robot != nullptr) store_row(a.robot + (long)w * 13, 1, f.px, f.py, f.yaw, g.robot_radius, g.robot_mass, f.gx, f.gy, g.robot_desired_speed);
+    if (a.robot_row)
+        store_row(a.S + ((long)w * a.rows + g.n) * a.as, a.fs, f.px, f.py, f.yaw, g.robot_radius, g.robot_mass, f.gx, f.gy, g.robot_desired_speed);
+    if (a.world_flags != nullptr) a.world_flags[w] = (scenario == CS_SCN_PARALLEL_TRAFFIC) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// One LANE per world (n <= 128): the plain sequential loops of the reference, its np.linalg.norm tests written as they stand.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_generate(const GArgs a)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.W) return;
+    if (a.mask != nullptr && a.mask[w] == 0) return;
+    const cs_generator& g = a.g;
+    const int n = g.n;
+    MT m{a.mt + w, (long)a.W, 624};
+    const uint32_t seed = a.seeds[w];
+    mt_seed(m, seed);
+    int scenario = g.scenario;
+    if (scenario == CS_SCN_HYBRID) { // np.random.choice(['circle_crossing', 'parallel_traffic']); np.random.seed(seed)
+        scenario = (mt_next(m) & 1u) ? CS_SCN_PARALLEL_TRAFFIC : CS_SCN_CIRCULAR_CROSSING;
+        mt_seed(m, seed);
+    }
+    double px[GEN_MAXN], py[GEN_MAXN], yaw[GEN_MAXN], rad[GEN_MAXN], spd[GEN_MAXN];
+    int status = 0;
+    const double R = g.circle_radius, L = g.traffic_length, H = g.traffic_height, rr = g.robot_radius;
+    const bool insert_robot = g.insert_robot != 0;
+    const Frame f = scenario_frame(scenario, R, L);
+    const bool obstacles = scenario == CS_SCN_CIRCULAR_CROSSING_STATIC_OBSTACLES;
+
+    for (int i = 0; i < n; ++i) {
+        const int k = attribute_draws(g, obstacles, i);
+        const double d0 = k > 0 ? rnd(m) : 0.0, d1 = k > 1 ? rnd(m) : 0.0;
+        attributes(g, obstacles, i, d0, d1, spd[i], rad[i]);
+    }
+    if (scenario == CS_SCN_CIRCULAR_CROSSING && !g.randomize_positions) {
+        for (int i = 0; i < n; ++i) fixed_circle_slot(R, n, insert_robot, i, px[i], py[i], yaw[i]);
+    } else if (scenario == CS_SCN_PARALLEL_TRAFFIC) {
+        if (traffic_too_dense(rad, n, L, H)) status = 2;
+        for (int i = 0; i < n && status == 0; ++i) {
+            bool placed = false;
+            for (int t = 0; t < g.max_tries; ++t) {
+                const double d0 = rnd(m), d1 = rnd(m);
+                const P2 c = traffic_candidate(L, H, rad[i], d0, d1);
+                bool collide = false;
+                for (int j = 0; j < i; ++j)
+                    if (norm2d(c.x - px[j], c.y - py[j]) - rad[i] - rad[j] - 0.1 < 0.0) { collide = true; break; }
+                if (insert_robot && norm2d(c.x - f.px, c.y - f.py) - rad[i] - rr - 0.1 < 0.0) collide = true;
+                if (!collide) {
+                    px[i] = c.x; py[i] = c.y; yaw[i] = bound_angle_d(-PI);
+                    placed = true;
+                    break;
+                }
+            }
+            if (!placed) status = 1;
+        }
+    } else { // the circular crossing and its form with static obstacles: one loop, each with its own candidate; the latter always keeps off the robot
+        for (int i = 0; i < n && status == 0; ++i) {
+            bool placed = false;
+            for (int t = 0; t < g.max_tries; ++t) {
+                const double d0 = rnd(m), d1 = rnd(m), d2 = rnd(m);
+                const double angle = obstacles ? static_angle(n, i, d0) : circle_angle(d0);
+                const double ca = cos(angle), sa = sin(angle);
+                const P2 c = obstacles ? static_candidate(R, i, d1, d2, ca, sa) : circle_candidate(R, spd[i], d1, d2, ca, sa);
+                bool collide = false;
+                for (int j = 0; j < i; ++j) {
+                    const double md = rad[i] + rad[j] + 0.2;
+                    const P2 q = kept_free(obstacles && j < 3, px[j], py[j]);
+                    if (norm2d(c.x - px[j], c.y - py[j]) < md || norm2d(c.x - q.x, c.y - q.y) < md) { collide = true; break; }
+                }
+                if ((obstacles || insert_robot) &&
+                    (norm2d(c.x - f.px, c.y - f.py) < rad[i] + rr + 0.2 || norm2d(c.x - f.gx, c.y - f.gy) < rad[i] + rr + 0.2))
+                    collide = true;
+                if (!collide) {
+                    px[i] = c.x; py[i] = c.y; yaw[i] = bound_angle_d(PI + angle);
+                    placed = true;
+                    break;
+                }
+            }
+            if (!placed) status = 1;
+        }
+    }
+    if (a.status != nullptr) a.status[w] = status;
+    if (a.scenario_out != nullptr) a.scenario_out[w] = scenario;
+    if (status != 0) return; // the rows of a world that could not be generated are left untouched
+
+    for (int i = 0; i < n; ++i) store_human(g, a.out, scenario, w, i, px[i], py[i], yaw[i], rad[i], spd[i]);
+    store_robot_and_flag(g, a.out, scenario, w, f);
+}
+
+// ------------------------------------------------------------------------------------------
+// One WAVEFRONT per world (n <= 64): the latency form, used for the masked auto-reset inside a device-resident loop.
+// MT19937 state in LDS (the current block and its successor, twisted cooperatively); attribute draws are read as wave-wide
+// broadcasts.  The rejection loops of the circular crossing and of the parallel traffic are SPECULATIVE: eight attempts of
+// the human being placed are evaluated at once, each from its own words of the stream by eight lanes that share the test
+// against the placed humans (kept in LDS); the first accepted attempt wins and the stream position moves to just behind
+// it, so a human mostly costs one round whatever its rejection count -- the slowest world of a batch no longer sets the
+// latency of a masked reset.
+// Same draws, same f64 expressions, same accept / reject decisions as k_generate above.
+// ------------------------------------------------------------------------------------------
 // np.linalg.norm((dx, dy)) < md, decided on the squares; the square root only inside the rounding band of the comparison
 __device__ __forceinline__ bool closer_than(double dx, double dy, double md)
 {
@@ -403,14 +440,44 @@ __device__ __forceinline__ bool closer_than(double dx, double dy, double md)
     return c;
 }
 
-// where a generated world goes (the batch being reset, a staging batch, or the live batch of cs_consume_staged_worlds)
-struct GenOut {
-    float* S; long as, fs; float* goals; float* robot; int* world_flags; int rows, G, robot_row, orca;
-};
-
-__device__ __forceinline__ GenOut gen_out(const GArgs& a)
+// the traffic's norm((dx, dy)) - ri - rj - 0.1 < 0, decided on the squares outside the rounding band of that expression
+__device__ __forceinline__ bool traffic_closer(double dx, double dy, double ri, double rj)
 {
-    return GenOut{a.S, a.as, a.fs, a.goals, a.robot, a.world_flags, a.rows, a.G, a.robot_row, a.orca};
+    const double d2 = dx * dx + dy * dy, T = ri + rj + 0.1, T2 = T * T;
+    bool c = d2 < T2;
+    if (fabs(d2 - T2) <= 1e-12 * T2) c = norm2d(dx, dy) - ri - rj - 0.1 < 0.0;
+    return c;
+}
+
+struct Attempt { double x, y, yaw; bool collide; }; // a candidate, its heading before bound_angle, and what THIS lane's share of the test found
+
+// Speculative rejection sampling of one human: the wavefront evaluates 8 attempts at once, attempt lane / 8 from its own WORDS words of
+// the stream (read ahead without consuming them) -- `attempt(k0)` is that evaluation for the attempt whose words start at k0 --, its 8
+// lanes sharing the test against the placed humans (lane % 8 takes every eighth one).  The first attempt none of whose lanes found a
+// collision wins, is stored to (px, py, yaw) and the stream moves to just behind it: the same draws and decisions as the sequential loop.
+// Returns whether the human was placed within max_tries attempts.
+template <int WORDS, class F>
+__device__ __forceinline__ bool place_speculatively(WMT& m, int lane, int max_tries, double& px, double& py, double& yaw, F attempt)
+{
+    const int att = lane >> 3;
+    bool placed = false;
+    for (int t0 = 0; t0 < max_tries && !placed; t0 += 8) {
+        if (m.pos >= 624) wmt_advance(m, lane);
+        const int base = m.pos;
+        const Attempt c = attempt(base + WORDS * att);
+        const unsigned long long bad = __builtin_amdgcn_ballot_w64(c.collide || t0 + att >= max_tries);
+        int win = -1;
+        for (int q = 7; q >= 0; --q) if (((bad >> (8 * q)) & 0xFFull) == 0) win = q;
+        if (win >= 0) {
+            if (lane == 8 * win) { px = c.x; py = c.y; yaw = bound_angle_d(c.yaw); }
+            m.pos = base + WORDS * (win + 1);
+            placed = true;
+        } else {
+            m.pos = base + WORDS * 8;
+        }
+        __syncthreads();
+    }
+    return placed;
 }
 
 // One world by one wavefront (the block): the reference's generator for `seed`, rows written to `a` when it succeeds.  Returns the
@@ -420,7 +487,6 @@ __device__ int generate_world_wave(const cs_generator& g, const GenOut& a, int w
     __shared__ uint32_t s_mt[2][624];
     __shared__ double s_rad[64], s_spd[64], s_px[64], s_py[64], s_yaw[64];
     const int n = g.n;
-    const double pi = 3.141592653589793;
     WMT m;
     m.cur = s_mt[0];
     m.nxt = s_mt[1];
@@ -435,21 +501,25 @@ __device__ int generate_world_wave(const cs_generator& g, const GenOut& a, int w
     }
     const double R = g.circle_radius, L = g.traffic_length, H = g.traffic_height, rr = g.robot_radius;
     const bool insert_robot = g.insert_robot != 0;
+    // The robot's frame, the attribute draws and the static obstacles' candidate are restated in this function, not taken from
+    // scenario_frame(), attribute_draws() and static_angle() / static_candidate(): each of the three moved a line of
+    // tools/gen_latency.py out of the parent's spread (HISTORY.md, "Scenario generators"); k_generate uses the functions.
     double rpx = 0, rpy = 0, ryaw = 0, rgx = 0, rgy = 0;
     double mx = 0, my = 0, myaw = 0; // placed human `lane`
     int status = 0;
 
     // attributes: every lane sees every draw; slot i keeps its own in LDS for the uniform reads below
-    if (scenario == CS_SCN_CIRCULAR_CROSSING || scenario == CS_SCN_PARALLEL_TRAFFIC) {
+    if (scenario == CS_SCN_CIRCULAR_CROSSING_STATIC_OBSTACLES) {
         for (int i = 0; i < n; ++i) {
-            double sp = 1.0, ra = 0.3;
-            if (g.randomize_attributes) { sp = 0.5 + (1.5 - 0.5) * wrnd(m, lane); ra = 0.3 + (0.5 - 0.3) * wrnd(m, lane); }
+            double sp, ra;
+            attributes(g, true, i, i < 3 ? wrnd(m, lane) : 0.0, 0.0, sp, ra);
             if (lane == i) { s_spd[i] = sp; s_rad[i] = ra; }
         }
     } else {
         for (int i = 0; i < n; ++i) {
-            double sp = 1.0, ra = 0.3;
-            if (i < 3) { sp = 0.0; ra = 1.0 + (wrnd(m, lane) - 1.0) * 0.4; }
+            double d0 = 0.0, d1 = 0.0, sp, ra;
+            if (g.randomize_attributes) { d0 = wrnd(m, lane); d1 = wrnd(m, lane); }
+            attributes(g, false, i, d0, d1, sp, ra);
             if (lane == i) { s_spd[i] = sp; s_rad[i] = ra; }
         }
     }
@@ -457,105 +527,54 @@ __device__ int generate_world_wave(const cs_generator& g, const GenOut& a, int w
     const double myrad = lane < n ? s_rad[lane] : 0.0;
 
     if (scenario == CS_SCN_CIRCULAR_CROSSING) {
-        rpx = 0.0; rpy = 0.0 - R; ryaw = pi / 2.0; rgx = 0.0; rgy = 0.0 + R;
+        rpx = 0.0; rpy = 0.0 - R; ryaw = PI / 2.0; rgx = 0.0; rgy = 0.0 + R;
         if (!g.randomize_positions) {
-            const int slots = n + (insert_robot ? 1 : 0);
-            const double step = (2.0 * pi) / slots;
-            const int k = insert_robot ? lane + 1 : lane;
-            const double off = insert_robot ? -(pi / 2.0) : 0.0;
-            mx = 0.0 + R * cos(off + step * k); my = 0.0 + R * sin(off + step * k);
-            myaw = insert_robot ? bound_angle_d((pi / 2.0) + step * k) : bound_angle_d(-pi + step * k);
+            fixed_circle_slot(R, n, insert_robot, lane, mx, my, myaw);
         } else {
-            // speculative rejection sampling: the wavefront evaluates 8 attempts of human i at once, attempt a = lane / 8 from
-            // its own six words of the stream (read ahead without consuming them), its 8 lanes sharing the test against the
-            // placed humans (lane % 8 takes every eighth one).  The first attempt none of whose lanes found a collision wins
-            // and the stream moves to just behind it: the same draws and decisions as the sequential loop.
-            const int att = lane >> 3, sub = lane & 7;
+            const int sub = lane & 7;                      // speculative, six words per attempt: this lane's share of an attempt's test
             for (int i = 0; i < n && status == 0; ++i) {
                 const double ri = s_rad[i], si = s_spd[i];
-                bool placed = false;
-                for (int t0 = 0; t0 < g.max_tries && !placed; t0 += 8) {
-                    if (m.pos >= 624) wmt_advance(m, lane);
-                    const int base = m.pos, k0 = base + 6 * att;
-                    const double angle = wmt_peek_double(m, k0, 0) * pi * 2.0;
-                    const double nx = (wmt_peek_double(m, k0, 1) - 0.5) * si;
-                    const double ny = (wmt_peek_double(m, k0, 2) - 0.5) * si;
+                const bool placed = place_speculatively<6>(m, lane, g.max_tries, s_px[i], s_py[i], s_yaw[i], [&](int k0) {
+                    const double angle = circle_angle(wmt_peek_double(m, k0, 0));
                     double sa, ca;
                     sincos(angle, &sa, &ca); // one range reduction for both (same values as cos() and sin(): G6 parity)
-                    const double x = 0.0 + R * ca + nx, y = 0.0 + R * sa + ny;
-                    bool collide = t0 + att >= g.max_tries;
+                    const P2 c = circle_candidate(R, si, wmt_peek_double(m, k0, 1), wmt_peek_double(m, k0, 2), ca, sa);
+                    const double x = c.x, y = c.y;
+                    bool collide = false;
                     for (int j = sub; j < i; j += 8) {
                         const double qx = s_px[j], qy = s_py[j], md = ri + s_rad[j] + 0.2;
-                        collide |= closer_than(x - qx, y - qy, md) || closer_than(x - (-qx + 0.0), y - (-qy + 0.0), md);
+                        const P2 q = kept_free(false, qx, qy);
+                        collide |= closer_than(x - qx, y - qy, md) || closer_than(x - q.x, y - q.y, md);
                     }
                     if (insert_robot && sub == 0)
                         collide |= closer_than(x - rpx, y - rpy, ri + rr + 0.2) || closer_than(x - rgx, y - rgy, ri + rr + 0.2);
-                    const unsigned long long bad = __builtin_amdgcn_ballot_w64(collide);
-                    int win = -1;
-                    for (int q = 7; q >= 0; --q) if (((bad >> (8 * q)) & 0xFFull) == 0) win = q;
-                    if (win >= 0) {
-                        if (lane == 8 * win) { s_px[i] = x; s_py[i] = y; s_yaw[i] = bound_angle_d(pi + angle); }
-                        m.pos = base + 6 * (win + 1);
-                        placed = true;
-                    } else {
-                        m.pos = base + 6 * 8;
-                    }
-                    __syncthreads();
-                }
+                    return Attempt{x, y, PI + angle, collide};
+                });
                 if (!placed) status = 1;
             }
             if (lane < n) { mx = s_px[lane]; my = s_py[lane]; myaw = s_yaw[lane]; }
         }
     } else if (scenario == CS_SCN_PARALLEL_TRAFFIC) {
         rpx = -(L / 2.0) + 1.0; rpy = 0.0; ryaw = 0.0; rgx = (L / 2.0) - 1.0; rgy = 0.0;
-        double area = 0.0;
-        for (int i = 0; i < n; ++i) area += pi * (s_rad[i] * s_rad[i]);
-        if (area > L * H * 0.4) status = 2;
-        const int att = lane >> 3, sub = lane & 7;
-        for (int i = 0; i < n && status == 0; ++i) {   // speculative, four words per attempt (see the circular crossing)
+        if (traffic_too_dense(s_rad, n, L, H)) status = 2;
+        const int sub = lane & 7;                          // speculative, four words per attempt
+        for (int i = 0; i < n && status == 0; ++i) {
             const double ri = s_rad[i];
-            const double lo = -(L / 2.0) + ri, hi = L / 2.0 - ri;
-            bool placed = false;
-            for (int t0 = 0; t0 < g.max_tries && !placed; t0 += 8) {
-                if (m.pos >= 624) wmt_advance(m, lane);
-                const int base = m.pos, k0 = base + 4 * att;
-                const double x = (hi - lo) * wmt_peek_double(m, k0, 0) + lo;
-                const double y = (wmt_peek_double(m, k0, 1) - 0.5) * H;
-                bool collide = t0 + att >= g.max_tries;
-                for (int j = sub; j < i; j += 8) {
-                    // norm(...) - ri - radius_j - 0.1 < 0, decided on the squares outside the rounding band of that expression
-                    const double dx = x - s_px[j], dy = y - s_py[j], rj = s_rad[j];
-                    const double d2 = dx * dx + dy * dy, T = ri + rj + 0.1, T2 = T * T;
-                    bool c = d2 < T2;
-                    if (fabs(d2 - T2) <= 1e-12 * T2) c = norm2d(dx, dy) - ri - rj - 0.1 < 0.0;
-                    collide |= c;
-                }
-                if (insert_robot && sub == 0) {
-                    const double dx = x - rpx, dy = y - rpy;
-                    const double d2 = dx * dx + dy * dy, T = ri + rr + 0.1, T2 = T * T;
-                    bool c = d2 < T2;
-                    if (fabs(d2 - T2) <= 1e-12 * T2) c = norm2d(dx, dy) - ri - rr - 0.1 < 0.0;
-                    collide |= c;
-                }
-                const unsigned long long bad = __builtin_amdgcn_ballot_w64(collide);
-                int win = -1;
-                for (int q = 7; q >= 0; --q) if (((bad >> (8 * q)) & 0xFFull) == 0) win = q;
-                if (win >= 0) {
-                    if (lane == 8 * win) { s_px[i] = x; s_py[i] = y; s_yaw[i] = bound_angle_d(-pi); }
-                    m.pos = base + 4 * (win + 1);
-                    placed = true;
-                } else {
-                    m.pos = base + 4 * 8;
-                }
-                __syncthreads();
-            }
+            const bool placed = place_speculatively<4>(m, lane, g.max_tries, s_px[i], s_py[i], s_yaw[i], [&](int k0) {
+                const P2 c = traffic_candidate(L, H, ri, wmt_peek_double(m, k0, 0), wmt_peek_double(m, k0, 1));
+                const double x = c.x, y = c.y;
+                bool collide = false;
+                for (int j = sub; j < i; j += 8) collide |= traffic_closer(x - s_px[j], y - s_py[j], ri, s_rad[j]);
+                if (insert_robot && sub == 0) collide |= traffic_closer(x - rpx, y - rpy, ri, rr);
+                return Attempt{x, y, -PI, collide};
+            });
             if (!placed) status = 1;
         }
         if (lane < n) { mx = s_px[lane]; my = s_py[lane]; myaw = s_yaw[lane]; }
-    } else {
-        rpx = 0.0; rpy = 0.0 - R; ryaw = pi / 2.0; rgx = 0.0; rgy = 0.0 + R;
+    } else { // static obstacles: sequential attempts, lane j holding placed human j in registers and testing the candidate against it
+        rpx = 0.0; rpy = 0.0 - R; ryaw = PI / 2.0; rgx = 0.0; rgy = 0.0 + R;
         const double inner = R - 3.0;
-        const double sector = pi / (double)(n / 2);
+        const double sector = PI / (double)(n / 2);
         for (int i = 0; i < n && status == 0; ++i) {
             const double ri = s_rad[i];
             bool placed = false;
@@ -579,7 +598,7 @@ __device__ int generate_world_wave(const cs_generator& g, const GenOut& a, int w
                 bool collide = __builtin_amdgcn_ballot_w64(hit) != 0;
                 if (norm2d(x - rpx, y - rpy) < ri + rr + 0.2 || norm2d(x - rgx, y - rgy) < ri + rr + 0.2) collide = true;
                 if (!collide) {
-                    if (lane == i) { mx = x; my = y; myaw = bound_angle_d(pi + angle); }
+                    if (lane == i) { mx = x; my = y; myaw = bound_angle_d(PI + angle); }
                     placed = true;
                     break;
                 }
@@ -590,40 +609,8 @@ __device__ int generate_world_wave(const cs_generator& g, const GenOut& a, int w
     scenario_out = scenario;
     if (status != 0) return status;
 
-    const float nanf_ = __builtin_nanf("");
-    if (lane < n) {
-        const int i = lane;
-        double g0x, g0y, g1x, g1y;
-        int ng;
-        if (scenario == CS_SCN_PARALLEL_TRAFFIC) { g0x = -(L / 2.0) - 3.0; g0y = my; g1x = g1y = 0; ng = 1; }
-        else if (scenario == CS_SCN_CIRCULAR_CROSSING_STATIC_OBSTACLES && i < 3) { g0x = mx; g0y = my; g1x = mx; g1y = my; ng = 2; }
-        else { g0x = 0.0 * 2.0 - mx; g0y = 0.0 * 2.0 - my; g1x = mx; g1y = my; ng = 2; }
-        float* s = a.S + ((long)w * a.rows + i) * a.as;
-        const long fs = a.fs;
-        s[0] = (float)mx; s[fs] = (float)my; s[2 * fs] = (float)myaw;
-        for (int c = 3; c < 8; ++c) s[c * fs] = 0.0f;
-        s[8 * fs] = (float)myrad; s[9 * fs] = (float)g.human_mass; s[10 * fs] = (float)g0x; s[11 * fs] = (float)g0y;
-        s[12 * fs] = (float)s_spd[i];
-        if (a.orca) orca_pref(s, fs, (float)mx, (float)my, (float)g0x, (float)g0y, (float)s_spd[i]);
-        float* gl = a.goals + ((long)w * n + i) * a.G * 2;
-        for (int k = 0; k < a.G; ++k) {
-            float gx = nanf_, gy = nanf_;
-            if (k == 0) { gx = (float)g0x; gy = (float)g0y; }
-            else if (k == 1 && ng == 2) { gx = (float)g1x; gy = (float)g1y; }
-            gl[2 * k] = gx; gl[2 * k + 1] = gy;
-        }
-    }
-    if (lane == 0) {
-        auto robot_row = [&](float* o, long fs) {
-            o[0] = (float)rpx; o[fs] = (float)rpy; o[2 * fs] = (float)ryaw;
-            for (int c = 3; c < 8; ++c) o[c * fs] = 0.0f;
-            o[8 * fs] = (float)rr; o[9 * fs] = (float)g.robot_mass; o[10 * fs] = (float)rgx; o[11 * fs] = (float)rgy;
-            o[12 * fs] = (float)g.robot_desired_speed;
-        };
-        if (a.robot != nullptr) robot_row(a.robot + (long)w * 13, 1);
-        if (a.robot_row) robot_row(a.S + ((long)w * a.rows + n) * a.as, a.fs);
-        if (a.world_flags != nullptr) a.world_flags[w] = (scenario == CS_SCN_PARALLEL_TRAFFIC) ? 1 : 0;
-    }
+    if (lane < n) store_human(g, a, scenario, w, lane, mx, my, myaw, myrad, s_spd[lane]);
+    if (lane == 0) store_robot_and_flag(g, a, scenario, w, Frame{rpx, rpy, ryaw, rgx, rgy});
     return 0;
 }
 
@@ -632,7 +619,7 @@ __global__ __launch_bounds__(64) void k_generate_wave(const GArgs a)
     const int w = blockIdx.x, lane = threadIdx.x;
     if (a.mask != nullptr && a.mask[w] == 0) return; // block-uniform
     int scenario = 0;
-    const int status = generate_world_wave(a.g, gen_out(a), w, lane, a.seeds[w], scenario);
+    const int status = generate_world_wave(a.g, a.out, w, lane, a.seeds[w], scenario);
     if (lane == 0) {
         if (a.status != nullptr) a.status[w] = status;
         if (a.scenario_out != nullptr) a.scenario_out[w] = scenario;
@@ -846,17 +833,8 @@ int cs_generate_worlds(const cs_generator* gen, const cs_worlds* w, const uint32
     }
     GArgs a;
     a.g = *gen;
+    if (const int rc = fill_gen_out(w, a.out)) return rc;
     a.W = w->W;
-    a.rows = rows_of(w);
-    a.robot_row = a.rows - w->n;
-    a.orca = w->type == CS_ORCA ? 1 : 0;
-    a.G = w->G;
-    a.S = w->d_state;
-    if (const int rc = check_layout(w)) return rc;
-    state_strides(w, a.as, a.fs);
-    a.goals = w->d_goals;
-    a.robot = w->d_robot;
-    a.world_flags = const_cast<int*>(w->d_world_flags);
     a.seeds = d_seeds;
     a.mask = d_mask;
     a.status = d_status;

@@ -383,6 +383,154 @@ def test_more_than_64_humans_use_the_lane_per_world_kernel():
             np.testing.assert_array_equal(S[w, :, 8], hr.astype(np.float32))
 
 
+_BIG_BOX = dict(circle_radius=30, traffic_length=60, traffic_height=20)
+_LANE_SEEDS = (11, 12, 13, 14)
+
+
+def _host_world(scenario, seed, n, *, insert_robot=True, randomize_attributes=False, randomize_positions=True, circle_radius=7,
+                traffic_length=14, traffic_height=3, max_tries=None):
+    """One world of the host generators (social_nav_sim.py) under np.random.seed(seed), as the rows cs_generate_worlds writes: the status,
+    the scenario drawn, the float64 columns, both goal slots (NaN where the reference has one goal), the robot row, the respawn flag --
+    and the number of random_sample() draws the generator took from the re-seeded stream."""
+    from social_navigation_pyenvs_amd.social_gym import social_nav_sim as sns
+
+    host = types.SimpleNamespace(_attributes=sns.SocialNavSim._attributes)
+    R, L = float(circle_radius), float(traffic_length)
+    np.random.seed(seed)
+    if scenario == "hybrid_scenario":                     # social_nav_gym.py:156-157: the choice, then the same seed again
+        scenario = str(np.random.choice(["circle_crossing", "parallel_traffic"]))
+        np.random.seed(seed)
+    kw = dict(insert_robot=insert_robot, human_policy="hsfm_farina", robot_radius=0.3, n_actors=n)
+    minimum = {"circle_crossing": (2 * n if randomize_attributes else 0) + (3 * n if randomize_positions else 0),
+               "parallel_traffic": (2 * n if randomize_attributes else 0) + 2 * n,
+               "circular_crossing_with_static_obstacles": 3 + 3 * n}[scenario]
+    saved = sns.MAX_PLACEMENT_TRIES
+    status = 0
+    try:
+        if max_tries is not None:
+            sns.MAX_PLACEMENT_TRIES = max_tries
+        if scenario == "circle_crossing":
+            data = sns.SocialNavSim.generate_circular_crossing_setting(host, circle_radius=R, randomize_human_positions=randomize_positions,
+                                                                       randomize_human_attributes=randomize_attributes, **kw)
+        elif scenario == "parallel_traffic":
+            data = sns.SocialNavSim.generate_parallel_traffic_scenario(host, traffic_length=L, traffic_height=float(traffic_height),
+                                                                       randomize_human_attributes=randomize_attributes, **kw)
+        else:
+            data = sns.SocialNavSim.generate_circular_crossing_with_static_obstacles(host, circle_radius=R, **kw)
+    except RuntimeError:
+        status, data = 1, None
+    finally:
+        sns.MAX_PLACEMENT_TRIES = saved
+    out = types.SimpleNamespace(status=status, scenario={"circle_crossing": 0, "parallel_traffic": 1}.get(scenario, 2), minimum=minimum)
+    if data is None:
+        return out
+    end, rs, out.draws = np.random.get_state(), np.random.RandomState(seed), 0
+    while True:                                            # every draw of the generators is one random_sample()
+        st = rs.get_state()
+        if st[2] == end[2] and np.array_equal(st[1], end[1]):
+            break
+        rs.random_sample()
+        out.draws += 1
+        assert out.draws < 10 ** 5
+    hum = [data["humans"][i] for i in range(n)]
+    out.pos = np.array([h["pos"] for h in hum], np.float64)
+    out.yaw = np.array([h["yaw"] for h in hum], np.float64)
+    out.radius = np.array([h["radius"] for h in hum], np.float64)
+    out.speed = np.array([h["des_speed"] for h in hum], np.float64)
+    out.goals = np.full((n, 2, 2), np.nan)
+    for i, h in enumerate(hum):
+        out.goals[i, :len(h["goals"])] = h["goals"]
+    # the robot's safe-state row (social_nav_gym.py:211-213), written whether or not the robot stands among the humans
+    if scenario == "parallel_traffic":
+        rp, ryaw, rg = [-(L / 2) + 1, 0.0], 0.0, [(L / 2) - 1, 0.0]
+    else:
+        rp, ryaw, rg = [0.0, -R], np.pi / 2, [0.0, R]
+    if insert_robot:
+        assert data["robot"]["pos"] == rp and data["robot"]["yaw"] == ryaw and data["robot"]["goals"][0] == rg
+    out.robot = np.array([rp[0], rp[1], ryaw, 0, 0, 0, 0, 0, 0.3, 80, rg[0], rg[1], 1], np.float64)
+    out.flag = 1 if scenario == "parallel_traffic" else 0
+    return out
+
+
+def _assert_world_is_the_hosts(S, goals, robot, flag, h, n, *, robot_row=False, orca=False):
+    np.testing.assert_allclose(S[:n, 0:2], h.pos.astype(np.float32), **F32_TOL)
+    np.testing.assert_allclose(S[:n, 2], h.yaw.astype(np.float32), **F32_TOL)
+    np.testing.assert_array_equal(S[:n, 8], h.radius.astype(np.float32))                 # draws only: bit-exact
+    np.testing.assert_array_equal(S[:n, 12], h.speed.astype(np.float32))
+    assert np.all(S[:n, 9] == 75)
+    assert np.all(S[:n, 3:5] == 0) and np.all(S[:n, 7] == 0)
+    if orca:    # the host form of test_orca_worlds_generated_on_the_device_carry_the_preferred_velocity, on the stored float32 columns
+        d = S[:n, 10:12] - S[:n, 0:2]
+        dn = np.linalg.norm(d, axis=-1, keepdims=True)
+        np.testing.assert_array_equal(S[:n, 5:7], np.where(dn > S[:n, 12:13], d / np.maximum(dn, np.float32(1e-30)), d).astype(np.float32))
+        assert np.abs(S[3:n, 5:7]).max() > 0.5
+    else:
+        assert np.all(S[:n, 5:7] == 0)
+    np.testing.assert_allclose(goals, h.goals.astype(np.float32), **F32_TOL)             # both slots; NaN padding compares equal
+    np.testing.assert_array_equal(np.isnan(goals), np.isnan(h.goals))
+    np.testing.assert_allclose(S[:n, 10:12], h.goals[:, 0].astype(np.float32), **F32_TOL)
+    np.testing.assert_allclose(robot, h.robot.astype(np.float32), **F32_TOL)
+    if robot_row:
+        np.testing.assert_array_equal(S[n], robot)
+    assert flag == h.flag
+
+
+_LANE_CASES = {
+    "static_66": ("circular_crossing_with_static_obstacles", 66, {}),
+    "static_70": ("circular_crossing_with_static_obstacles", 70, {}),
+    "traffic_70": ("parallel_traffic", 70, dict(randomize_attributes=True)),
+    "fixed_circle_65_robot": ("circle_crossing", 65, dict(randomize_positions=False)),
+    "fixed_circle_65_no_robot": ("circle_crossing", 65, dict(randomize_positions=False, insert_robot=False)),
+    "hybrid_65": ("hybrid_scenario", 65, {}),
+    "hybrid_65_orca_soa_robot_row": ("hybrid_scenario", 65, dict(robot_row=True, layout="soa", type="orca")),
+    "failure_traffic_70": ("parallel_traffic", 70, dict(randomize_attributes=True, max_tries=2)),
+    "failure_circle_70": ("circle_crossing", 70, dict(randomize_attributes=True, max_tries=48)),
+}
+
+
+@pytest.mark.parametrize("case", list(_LANE_CASES))
+def test_lane_per_world_kernel_writes_the_hosts_worlds(case):
+    """Worlds of more than 64 humans (one lane per world, k_generate) against the host generators under the same seed, every column:
+    the static obstacles (390-978 draws a world: every world has rejections and crosses an MT19937 block), the traffic with drawn
+    attributes, the evenly spaced circle with and without the robot's slot, the hybrid choice (both scenarios among the seeds), the ORCA
+    columns through the SoA layout with the robot's row -- and worlds whose bounded rejection sampling gives up: status 1, rows untouched."""
+    from social_navigation_pyenvs_amd.batched import CrowdWorlds
+    from social_navigation_pyenvs_amd.generators import generate_worlds
+
+    scenario, n, opts = _LANE_CASES[case]
+    opts = dict(opts)
+    robot_row, layout, model = opts.pop("robot_row", False), opts.pop("layout", "aos"), opts.pop("type", "sfm_helbing")
+    max_tries = opts.get("max_tries")
+    W, seeds = len(_LANE_SEEDS), np.array(_LANE_SEEDS)
+    assert n > 64
+    hosts = [_host_world(scenario, int(s), n, **_BIG_BOX, **opts) for s in seeds]
+    if max_tries is None:
+        assert not any(h.status for h in hosts)
+        if opts.get("randomize_positions", True):
+            assert all(h.draws > h.minimum for h in hosts), [(h.draws, h.minimum) for h in hosts]   # every world had a rejection
+        if scenario == "circular_crossing_with_static_obstacles":
+            assert all(h.draws > 312 for h in hosts)                                               # ... and left its first MT19937 block
+        if scenario == "hybrid_scenario":
+            assert {h.scenario for h in hosts} == {0, 1}
+    else:
+        assert {h.status for h in hosts} == {0, 1}
+    rows = n + int(robot_row)
+    fill = (np.float32(7), np.float32(5), np.float32(3))    # what a world that could not be generated must still hold afterwards
+    cw = CrowdWorlds(np.full((W, rows, 13), fill[0]), np.full((W, n, 2, 2), fill[1]), np.zeros((n, 20)), None, None, type=model,
+                     all_params_equal=True, robot_row=robot_row, robot=np.full((W, 13), fill[2]), respawn_worlds=np.ones(W, np.int32),
+                     layout=layout)
+    assert cw.orca == (model == "orca")
+    status, scn = generate_worlds(cw, scenario, seeds, raise_on_failure=False, **_BIG_BOX, **opts)
+    S, goals, robot, flags = cw.get_states(), cw.get_goals(), cw.get_robot(), cw.d_world_flags.download()
+    np.testing.assert_array_equal(status, [h.status for h in hosts])
+    np.testing.assert_array_equal(scn, [h.scenario for h in hosts])
+    for w, h in enumerate(hosts):
+        if h.status:
+            assert np.all(S[w] == fill[0]) and np.all(goals[w] == fill[1]) and np.all(robot[w] == fill[2]) and flags[w] == 1
+        else:
+            _assert_world_is_the_hosts(S[w], goals[w], robot[w], flags[w], h, n, robot_row=robot_row, orca=cw.orca)
+
+
 def test_failed_regeneration_never_replaces_a_live_world():
     """The masked auto-reset of step_device: cs_generate_worlds into a staging batch with a status array, then
     cs_copy_worlds_masked_status -- a world whose bounded rejection sampling gives up (status != 0; forced here with max_tries = 2) keeps its live rows, the others are replaced by the regenerated ones."""
