@@ -23,6 +23,7 @@
 #include "common.h"
 #include "goals.h"
 #include "crowdstep.h"
+#include "forces_ref.h"
 #include "robot_model.h"
 
 namespace {
@@ -47,43 +48,9 @@ struct KArgsRk {
     float* dense;
 };
 
-using rmodel::PI_F;
-using rmodel::bound_angle;
+using fref::bound_angle;
 using rmodel::wave_sum;
-
-// compute_pairwise_social_force(kind, agent1, agent2) (forces.py:63-128): force on agent 1; r1 / r2 = radius + safety_space
-__device__ __forceinline__ void pair_force(int kind, const float* P, float p1x, float p1y, float v1x, float v1y, float r1, float p2x,
-                                           float p2y, float v2x, float v2y, float r2, float& fx, float& fy)
-{
-    const float dx = p1x - p2x, dy = p1y - p2y;
-    const float dn = sqrtf(dx * dx + dy * dy);
-    const float nx = dx / dn, ny = dy / dn;
-    const float rd = r1 + r2 - dn;
-    const float comp = fmaxf(0.0f, rd);
-    if (kind == 2) {
-        const float ivx = P[12] * (v1x - v2x) - nx, ivy = P[12] * (v1y - v2y) - ny;
-        const float inorm = sqrtf(ivx * ivx + ivy * ivy);
-        const float ix = ivx / inorm, iy = ivy / inorm;
-        const float th = bound_angle(atan2f(ny, nx) - atan2f(iy, ix) + PI_F);
-        const float k = (th > 0.0f) ? 1.0f : ((th < 0.0f) ? -1.0f : 0.0f);
-        const float hx = -iy, hy = ix;
-        const float F = P[13] * inorm;
-        const float dvh = (v2x - v1x) * hx + (v2y - v1y) * hy;
-        const float e0 = P[9] * expf(-dn / F);
-        const float t1 = P[15] * F * th, t2 = P[14] * F * th;
-        const float e1 = expf(-(t1 * t1)), e2 = k * expf(-(t2 * t2));
-        fx = -(e0 * (e1 * ix + e2 * hx) + P[10] * comp * ix + P[11] * comp * dvh * hx);
-        fy = -(e0 * (e1 * iy + e2 * hy) + P[10] * comp * iy + P[11] * comp * dvh * hy);
-    } else {
-        const float tx = -ny, ty = nx;
-        const float dv = (v2x - v1x) * tx + (v2y - v1y) * ty;
-        const float fn = P[1] * expf(rd / P[3]) + P[10] * comp;
-        float ft = P[11] * comp * dv;
-        if (kind == 1) ft += P[5] * expf(rd / P[7]);
-        fx = fn * nx + ft * tx;
-        fy = fn * ny + ft * ty;
-    }
-}
+using CrowdMath = fref::fused::Libm<float>;   // the crowd's laws: libm throughout, contraction as the compiler likes (forces_ref.h)
 
 // ---- scipy's explicit Dormand-Prince pair with its step-size control, shared by the crowd's and the robot's solve --------------
 // (scipy/integrate/_ivp/rk.py RK45 + common.py select_initial_step, version 1.15.3: rtol 1e-3, atol 1e-6, SAFETY 0.9, factors
@@ -247,7 +214,7 @@ __global__ __launch_bounds__(64) void k_rk45_step(const KArgsRk a)
     // f_rk45_*(t, yt): set the trial state, compute_forces, ydot
     auto rhs = [&](const float (&yt)[NS], float (&out)[NS]) {
         ++nfev;
-        float sn = 0.0f, cs = 1.0f;
+        float cs = 1.0f, sn = 0.0f;   // (declared in this order on purpose, like `foy, fox` below)
         if (human) {
             px = yt[0]; py = yt[1];
             if (HEADED) {
@@ -281,61 +248,24 @@ __global__ __launch_bounds__(64) void k_rk45_step(const KArgsRk a)
                 const float rj = s_rs[j];
                 float fx, fy;
                 if (all_equal && j < lane) {   // mirrored: minus the force the lower index feels from me
-                    pair_force(kind, P, q.x, q.y, q.z, q.w, rj, px, py, vx, vy, rs, fx, fy);
+                    fref::fused::pair_force<CrowdMath>(kind, P, q.x, q.y, q.z, q.w, px, py, vx, vy, rj + rs, fx, fy);
                     fsx -= fx; fsy -= fy;
                 } else {
-                    pair_force(kind, P, px, py, vx, vy, rs, q.x, q.y, q.z, q.w, rj, fx, fy);
+                    fref::fused::pair_force<CrowdMath>(kind, P, px, py, vx, vy, q.x, q.y, q.z, q.w, rs + rj, fx, fy);
                     fsx += fx; fsy += fy;
                 }
             }
-            // desired force, kept within one radius of the goal
-            {
-                const float ddx = g0x - px, ddy = g0y - py;
-                const float dist = sqrtf(ddx * ddx + ddy * ddy);
-                if (dist > radius) {
-                    fdx = mass * (ddx / dist * vd - vx) / P[0];
-                    fdy = mass * (ddy / dist * vd - vy) / P[0];
-                }
-            }
-            // obstacle force: the LAST nearest point of every polygon (obstacle.py:53-66)
-            float fox = 0.0f, foy = 0.0f;
-            for (int o = 0; o < a.O; ++o) {
-                float bx = 0.0f, by = 0.0f, bd = 10000.0f;
-                for (int sg = 0; sg < a.Smax; ++sg) {
-                    const float* q = ob + ((long)o * a.Smax + sg) * 4;
-                    const float ax = q[0], ay = q[1], ex = q[2], ey = q[3];
-                    if (isnan(ax) || isnan(ay) || isnan(ex) || isnan(ey)) continue;
-                    const float sx = ex - ax, sy = ey - ay;
-                    const float len = sqrtf(sx * sx + sy * sy);
-                    float t = ((px - ax) * sx + (py - ay) * sy) / (len * len);
-                    t = fminf(fmaxf(0.0f, t), 1.0f);
-                    const float hx = ax + t * sx, hy = ay + t * sy;
-                    const float d = sqrtf((hx - px) * (hx - px) + (hy - py) * (hy - py));
-                    if (d <= bd) { bx = hx; by = hy; bd = d; }
-                }
-                const float dx = px - bx, dy = py - by;
-                const float dn = sqrtf(dx * dx + dy * dy);
-                const float nx = dx / dn, ny = dy / dn, tx = -ny, ty = nx;
-                const float dv = -(vx * tx + vy * ty);
-                const float rd = rs - dn;
-                const float comp = fmaxf(0.0f, rd);
-                const float fn = P[2] * expf(rd / P[4]) + P[10] * comp;
-                const float ft = (kind == 1) ? (-P[6] * expf(rd / P[8]) - P[11] * comp) * dv : -P[11] * comp * dv;
-                fox += fn * nx + ft * tx;
-                foy += fn * ny + ft * ty;
-            }
-            if (a.O > 0 && kind != 1) { fox /= (float)a.O; foy /= (float)a.O; }
+            // desired force, kept within one radius of the goal; obstacle force; both of the single-agent functions
+            fref::fused::desired_force(g0x, g0y, px, py, vx, vy, radius, mass, vd, P[0], fdx, fdy);
+            float foy, fox;   // (y first on purpose: under contraction the order of these two decides WHICH product of tx * tx + ty * ty and
+                              //  of the body-frame sums is fused; this order gives the bits the step has always had)
+            fref::fused::obstacle_force(ob, a.O, a.Smax, kind, P, px, py, vx, vy, rs, fox, foy);
             if (!HEADED) {
                 out[0] = vx; out[1] = vy;
                 out[2] = (fdx + fox + fsx) / mass; out[3] = (fdy + foy + fsy) / mass;
             } else {
-                const float tx = torque_new ? fdx + fox + fsx : fdx, ty = torque_new ? fdy + foy + fsy : fdy;
-                const float tn = sqrtf(tx * tx + ty * ty);
-                const float k_theta = inertia * P[19] * tn;
-                const float k_omega = inertia * (1.0f + P[18]) * sqrtf(P[19] * tn / P[18]);
-                const float torque = -k_theta * bound_angle(th - atan2f(ty, tx)) - k_omega * om;
-                const float g0 = (fdx + fox + fsx) * cs + (fdy + foy + fsy) * sn;
-                const float g1 = P[16] * ((fox + fsx) * -sn + (foy + fsy) * cs) - P[17] * bvy;
+                float g0, g1, torque;
+                fref::fused::headed_force(torque_new, P, inertia, fdx, fdy, fdx + fox + fsx, fdy + foy + fsy, fox + fsx, foy + fsy, th, om, bvy, sn, cs, g0, g1, torque);
                 out[0] = cs * bvx - sn * bvy; out[1] = sn * bvx + cs * bvy; out[2] = om;
                 out[3] = g0 / mass; out[4] = g1 / mass; out[5] = torque / inertia;
             }
@@ -466,7 +396,7 @@ __global__ __launch_bounds__(64) void k_robot_rk45(const KArgsRobotRk a)
         float fsx = 0.0f, fsy = 0.0f;
         for (int j = 0; j < a.n; ++j) { const float2 t = s_term[j]; fsx += t.x; fsy += t.y; }
         float fox, foy;
-        rmodel::obstacle_force(ob, a.O, a.Smax, soc, a.P, r.px, r.py, r.vx, r.vy, rme, fox, foy);
+        fref::strict::obstacle_force(ob, a.O, a.Smax, soc, a.P, r.px, r.py, r.vx, r.vy, rme, fox, foy);
         rmodel::derivative(r, a.type, a.P, fsx, fsy, fox, foy, sn, cs, out);
     };
     const float invN = 1.0f / (float)NS;

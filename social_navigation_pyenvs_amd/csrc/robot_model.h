@@ -13,20 +13,9 @@
 
 #include <cmath>
 
+#include "forces_ref.h"
+
 namespace rmodel {
-
-constexpr float PI_F = 3.14159265358979323846f;
-constexpr float TWO_PI_F = 6.28318530717958647692f;
-
-// utils.py:7-13
-__device__ __forceinline__ float bound_angle(float a)
-{
-    if (a >= TWO_PI_F) a = fmodf(a, TWO_PI_F);
-    if (a <= -TWO_PI_F) a = fmodf(a, TWO_PI_F);
-    if (a > PI_F) a -= TWO_PI_F;
-    if (a < -PI_F) a += TWO_PI_F;
-    return a;
-}
 
 // sum over the 64 lanes of a wavefront, xor butterfly (every lane gets the total; robot_model.hip's DPP / readlane sum adds in another order)
 __device__ __forceinline__ float wave_sum(float v)
@@ -48,39 +37,7 @@ struct RState {
 __device__ __forceinline__ void pair_term(int soc, const float* P, float px, float py, float vx, float vy, float hx, float hy, float hvx,
                                           float hvy, float rij, float& tx_out, float& ty_out)
 {
-#pragma clang fp contract(off)
-    // (single-instruction rsq / exp as in the crowd kernel: <= 1 ulp each, two orders of magnitude inside the parity bar)
-    const float dx = px - hx, dy = py - hy;
-    const float d2h = fmaxf(dx * dx + dy * dy, 1e-30f);    // (coincident robot and human: finite, as in the crowd kernel)
-    const float dinv = __builtin_amdgcn_rsqf(d2h);
-    const float dn = d2h * dinv;
-    const float nx = dx * dinv, ny = dy * dinv;
-    const float rd = rij - dn;
-    // body-contact overlap from a Newton-refined distance: one ulp of dist is 1.4e-5 of the k1 / k2 force (stepcommon.h dist_refined)
-    const float comp = fmaxf(0.0f, rij - fmaf(fmaf(-dn, dn, d2h), 0.5f * dinv, dn));
-    if (soc == 2) {
-        const float ivx = P[12] * (vx - hvx) - nx, ivy = P[12] * (vy - hvy) - ny;
-        const float inorm = sqrtf(ivx * ivx + ivy * ivy);
-        const float ix = ivx / inorm, iy = ivy / inorm;
-        const float th = bound_angle(atan2f(ny, nx) - atan2f(iy, ix) + PI_F);
-        const float k = (th > 0.0f) ? 1.0f : ((th < 0.0f) ? -1.0f : 0.0f);
-        const float hxv = -iy, hyv = ix;
-        const float F = P[13] * inorm;
-        const float dvh = (hvx - vx) * hxv + (hvy - vy) * hyv;
-        const float e0 = P[9] * expf(-dn / F);
-        const float t1 = P[15] * F * th, t2 = P[14] * F * th;
-        const float e1 = expf(-(t1 * t1)), e2 = k * expf(-(t2 * t2));
-        tx_out = -(e0 * (e1 * ix + e2 * hxv) + P[10] * comp * ix + P[11] * comp * dvh * hxv);
-        ty_out = -(e0 * (e1 * iy + e2 * hyv) + P[10] * comp * iy + P[11] * comp * dvh * hyv);
-    } else {
-        const float tx = -ny, ty = nx;
-        const float dv = (hvx - vx) * tx + (hvy - vy) * ty;
-        const float fn = P[1] * __expf(rd / P[3]) + P[10] * comp;
-        float ft = P[11] * comp * dv;
-        if (soc == 1) ft += P[5] * __expf(rd / P[7]);
-        tx_out = fn * nx + ft * tx;
-        ty_out = fn * ny + ft * ty;
-    }
+    fref::strict::pair_force<fref::strict::FastF>(soc, P, px, py, vx, vy, hx, hy, hvx, hvy, rij, tx_out, ty_out);
 }
 
 // headed_agent_update_linear_velocity (motion_model_manager.py:143-145) at the head of compute_robot_forces: the heading's sine /
@@ -92,44 +49,6 @@ __device__ __forceinline__ void refresh_velocity(RState& r, bool headed, float& 
     if (headed) { r.vx = cs * r.bvx - sn * r.bvy; r.vy = sn * r.bvx + cs * r.bvy; }
 }
 
-// obstacle force of the single-agent functions (forces.py:27-53): one closest point per polygon (the LAST nearest segment point,
-// `<=`, obstacle.py:53-66), Helbing averaged over the polygons, Guo a plain sum.  ob: [O][Smax][2][2] NaN-padded, or null.
-__device__ __forceinline__ void obstacle_force(const float* ob, int O, int Smax, int soc, const float* P, float px, float py, float vx, float vy,
-                                               float rme, float& fox, float& foy)
-{
-#pragma clang fp contract(off)
-    fox = 0.0f; foy = 0.0f;
-    if (ob == nullptr || O <= 0) return;
-    for (int o = 0; o < O; ++o) {
-        float bx = 0.0f, by = 0.0f, bd = 10000.0f;
-        for (int sg = 0; sg < Smax; ++sg) {
-            const float* q = ob + ((long)o * Smax + sg) * 4;
-            const float ax = q[0], ay = q[1], ex = q[2], ey = q[3];
-            if (isnan(ax) || isnan(ay) || isnan(ex) || isnan(ey)) continue;
-            const float sx = ex - ax, sy = ey - ay;
-            const float len = sqrtf(sx * sx + sy * sy);
-            float t = ((px - ax) * sx + (py - ay) * sy) / (len * len);
-            t = fminf(fmaxf(0.0f, t), 1.0f);
-            const float hx = ax + t * sx, hy = ay + t * sy;
-            const float d = sqrtf((hx - px) * (hx - px) + (hy - py) * (hy - py));
-            if (d <= bd) { bx = hx; by = hy; bd = d; }
-        }
-        const float dx = px - bx, dy = py - by;
-        const float dn = sqrtf(dx * dx + dy * dy);
-        const float nx = dx / dn, ny = dy / dn, tx = -ny, ty = nx;
-        const float dv = -(vx * tx + vy * ty);
-        const float rd = rme - dn;
-        const float comp = fmaxf(0.0f, rd);
-        const float fn = P[2] * expf(rd / P[4]) + P[10] * comp;
-        float ft;
-        if (soc == 1) ft = (-P[6] * expf(rd / P[8]) - P[11] * comp) * dv;
-        else ft = -P[11] * comp * dv;
-        fox += fn * nx + ft * tx;
-        foy += fn * ny + ft * ty;
-    }
-    if (soc != 1) { fox /= (float)O; foy /= (float)O; }   // Guo's single-agent obstacle force is not averaged
-}
-
 // the right-hand side of the robot's RK45 solve (motion_model_manager.py:661-687) from the forces of compute_robot_forces: the
 // desired force (kept within one radius of the goal), then ydot = [v, F / m] or [R bv, omega, F_body / m, torque / I]
 template <int NS>
@@ -138,27 +57,15 @@ __device__ __forceinline__ void derivative(RState& r, int type, const float* P, 
 {
 #pragma clang fp contract(off)
     const bool torque_new = type >= 6;
-    {
-        const float ddx = r.gx - r.px, ddy = r.gy - r.py;
-        const float dist = sqrtf(ddx * ddx + ddy * ddy);
-        if (dist > r.radius) {
-            r.fdx = r.mass * (ddx / dist * r.vd - r.vx) / P[0];
-            r.fdy = r.mass * (ddy / dist * r.vd - r.vy) / P[0];
-        }
-    }
+    fref::strict::desired_force(r.gx, r.gy, r.px, r.py, r.vx, r.vy, r.radius, r.mass, r.vd, P[0], r.fdx, r.fdy);
     const float fdx = r.fdx, fdy = r.fdy;
     if constexpr (NS == 4) {
         out[0] = r.vx; out[1] = r.vy;
         out[2] = (fdx + fox + fsx) / r.mass; out[3] = (fdy + foy + fsy) / r.mass;
     } else {
         const float inertia = 0.5f * r.mass * r.radius * r.radius;
-        const float tx = torque_new ? fdx + fox + fsx : fdx, ty = torque_new ? fdy + foy + fsy : fdy;
-        const float tn = sqrtf(tx * tx + ty * ty);
-        const float k_theta = inertia * P[19] * tn;
-        const float k_omega = inertia * (1.0f + P[18]) * sqrtf(P[19] * tn / P[18]);
-        const float torque = -k_theta * bound_angle(r.yaw - atan2f(ty, tx)) - k_omega * r.om;
-        const float g0 = (fdx + fox + fsx) * cs + (fdy + foy + fsy) * sn;
-        const float g1 = P[16] * ((fox + fsx) * -sn + (foy + fsy) * cs) - P[17] * r.bvy;
+        float g0, g1, torque;
+        fref::strict::headed_force(torque_new, P, inertia, fdx, fdy, fdx + fox + fsx, fdy + foy + fsy, fox + fsx, foy + fsy, r.yaw, r.om, r.bvy, sn, cs, g0, g1, torque);
         out[0] = cs * r.bvx - sn * r.bvy; out[1] = sn * r.bvx + cs * r.bvy; out[2] = r.om;
         out[3] = g0 / r.mass; out[4] = g1 / r.mass; out[5] = torque / inertia;
     }
@@ -172,14 +79,7 @@ __device__ __forceinline__ void integrate(RState& r, int type, const float* P, f
 {
 #pragma clang fp contract(off)
     const bool headed = type >= 3, torque_new = type >= 6;
-    {
-        const float ddx = r.gx - r.px, ddy = r.gy - r.py;
-        const float dist = sqrtf(ddx * ddx + ddy * ddy);
-        if (dist > r.radius) {
-            r.fdx = r.mass * (ddx / dist * r.vd - r.vx) / P[0];
-            r.fdy = r.mass * (ddy / dist * r.vd - r.vy) / P[0];
-        }
-    }
+    fref::strict::desired_force(r.gx, r.gy, r.px, r.py, r.vx, r.vy, r.radius, r.mass, r.vd, P[0], r.fdx, r.fdy);
     const float fdx = r.fdx, fdy = r.fdy;
     float npx, npy, nyaw = r.yaw, nvx, nvy, nbx = r.bvx, nby = r.bvy, nom = r.om;
     if (!headed) {
@@ -190,16 +90,10 @@ __device__ __forceinline__ void integrate(RState& r, int type, const float* P, f
         if (sp > r.vd) { nvx = nvx / sp * r.vd; nvy = nvy / sp * r.vd; }
     } else {
         const float inertia = 0.5f * r.mass * r.radius * r.radius;
-        const float tx = torque_new ? fdx + fox + fsx : fdx, ty = torque_new ? fdy + foy + fsy : fdy;
-        const float tn = sqrtf(tx * tx + ty * ty);
-        const float k_theta = inertia * P[19] * tn;
-        const float k_omega = inertia * (1.0f + P[18]) * sqrtf(P[19] * tn / P[18]);
-        const float torque = -k_theta * bound_angle(r.yaw - atan2f(ty, tx)) - k_omega * r.om;
-        // global_force = [ (fd + fo + fs) . R[:,0] ,  ko * (fo + fs) . R[:,1] - kd * body_velocity[1] ]
-        const float g0 = (fdx + fox + fsx) * cs + (fdy + foy + fsy) * sn;
-        const float g1 = P[16] * ((fox + fsx) * -sn + (foy + fsy) * cs) - P[17] * r.bvy;
+        float g0, g1, torque;
+        fref::strict::headed_force(torque_new, P, inertia, fdx, fdy, fdx + fox + fsx, fdy + foy + fsy, fox + fsx, foy + fsy, r.yaw, r.om, r.bvy, sn, cs, g0, g1, torque);
         npx = just_velocities ? r.px : r.px + r.vx * dt; npy = just_velocities ? r.py : r.py + r.vy * dt;
-        nyaw = just_velocities ? r.yaw : bound_angle(r.yaw + r.om * dt);
+        nyaw = just_velocities ? r.yaw : fref::bound_angle(r.yaw + r.om * dt);
         nbx = r.bvx + g0 / r.mass * dt; nby = r.bvy + g1 / r.mass * dt;
         nom = r.om + torque / inertia * dt;
         const float sp = sqrtf(nbx * nbx + nby * nby);

@@ -49,10 +49,6 @@ struct RArgs {
     int nsub;
 };
 
-using rmodel::PI_F;
-using rmodel::TWO_PI_F;
-using rmodel::bound_angle;
-
 // sum over the 64 lanes, left in every lane: four DPP rotate-and-add steps inside each 16-lane row, then the four row sums through
 // scalar registers (v_readlane) -- a few dozen cycles instead of six dependent LDS-crossbar shuffles (~120 cycles each)
 template <int N> __device__ __forceinline__ float row_ror_add(float x)
@@ -129,40 +125,10 @@ __global__ __launch_bounds__(256) void k_robot_model_step(const RArgs a)
         fsy = wave_sum(fsy);
     }
 
-    // ---- obstacle force: one closest point per polygon (the LAST nearest segment point, `<=`)
-    float fox = 0.0f, foy = 0.0f;
-    if (a.O > 0) {
-        const float px = r.px, py = r.py, vx = r.vx, vy = r.vy;
-        const float* ob = a.obstacles + (a.obstacles_shared ? 0 : (long)w * a.O * a.Smax * 4);
-        for (int o = 0; o < a.O; ++o) {
-            float bx = 0.0f, by = 0.0f, bd = 10000.0f;
-            for (int sg = 0; sg < a.Smax; ++sg) {
-                const float* q = ob + ((long)o * a.Smax + sg) * 4;
-                const float ax = q[0], ay = q[1], ex = q[2], ey = q[3];
-                if (isnan(ax) || isnan(ay) || isnan(ex) || isnan(ey)) continue;
-                const float sx = ex - ax, sy = ey - ay;
-                const float len = sqrtf(sx * sx + sy * sy);
-                float t = ((px - ax) * sx + (py - ay) * sy) / (len * len);
-                t = fminf(fmaxf(0.0f, t), 1.0f);
-                const float hx = ax + t * sx, hy = ay + t * sy;
-                const float d = sqrtf((hx - px) * (hx - px) + (hy - py) * (hy - py));
-                if (d <= bd) { bx = hx; by = hy; bd = d; }
-            }
-            const float dx = px - bx, dy = py - by;
-            const float dn = sqrtf(dx * dx + dy * dy);
-            const float nx = dx / dn, ny = dy / dn, tx = -ny, ty = nx;
-            const float dv = -(vx * tx + vy * ty);
-            const float rd = rme - dn;
-            const float comp = fmaxf(0.0f, rd);
-            const float fn = P[2] * expf(rd / P[4]) + P[10] * comp;
-            float ft;
-            if (soc == 1) ft = (-P[6] * expf(rd / P[8]) - P[11] * comp) * dv;
-            else ft = -P[11] * comp * dv;
-            fox += fn * nx + ft * tx;
-            foy += fn * ny + ft * ty;
-        }
-        if (soc != 1) { fox /= (float)a.O; foy /= (float)a.O; }   // Guo's single-agent obstacle force is not averaged
-    }
+    // ---- obstacle force of the single-agent functions (contraction as this kernel has always had it there: forces_ref.h `fused`)
+    float fox, foy;
+    fref::fused::obstacle_force(a.O > 0 ? a.obstacles + (a.obstacles_shared ? 0 : (long)w * a.O * a.Smax * 4) : nullptr, a.O, a.Smax, soc, P, r.px, r.py,
+                                r.vx, r.vy, rme, fox, foy);
     rmodel::integrate(r, a.type, P, fsx, fsy, fox, foy, sn, cs, a.dt, a.just_velocities);
     qpre = qnext;
     }   // substeps

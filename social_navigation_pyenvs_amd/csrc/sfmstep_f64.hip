@@ -23,9 +23,9 @@
 #include <cmath>
 #include <string>
 
-#include "atan2_cr.h"
 #include "common.h"
 #include "crowdstep.h"
+#include "forces_ref.h"
 
 namespace {
 
@@ -53,16 +53,8 @@ struct Args64 {
 
 __device__ inline double norm2(double x, double y) { return sqrt(x * x + y * y); }
 
-// utils.py:7-13
-__device__ inline double bound_angle(double a)
-{
-    const double two_pi = 2.0 * M_PI, pi = M_PI;
-    if (a >= two_pi) a = fmod(a, two_pi);
-    if (a <= -two_pi) a = fmod(a, two_pi);
-    if (a > pi) a -= two_pi;
-    if (a < -pi) a += two_pi;
-    return a;
-}
+using fref::bound_angle;
+namespace laws = fref::strict;   // the four laws with Libm<double> + correctly rounded theta_ij (forces_ref.h), no contraction
 
 struct Body { double px, py, vx, vy, r, s; };
 
@@ -70,39 +62,7 @@ struct Body { double px, py, vx, vy, r, s; };
 template <int SOC>
 __device__ inline void pair_force(const Body& A, const Body& B, const double (&P)[20], double& fx, double& fy)
 {
-    const double rij = A.r + B.r + A.s + B.s;
-    const double dx = A.px - B.px, dy = A.py - B.py;
-    const double dist = norm2(dx, dy);
-    const double nx = dx / dist, ny = dy / dist;
-    const double rd = rij - dist;
-    const double m0 = rd > 0 ? rd : 0.0;
-    if constexpr (SOC < 2) {
-        const double tx = -ny, ty = nx;
-        const double dv = (B.vx - A.vx) * tx + (B.vy - A.vy) * ty;
-        const double fn = P[1] * exp(rd / P[3]) + P[10] * m0;
-        double ft;
-        if constexpr (SOC == 0) ft = P[11] * m0 * dv;
-        else ft = P[5] * exp(rd / P[7]) + P[11] * m0 * dv;
-        fx = fn * nx + ft * tx;
-        fy = fn * ny + ft * ty;
-    } else {
-        const double vdx = A.vx - B.vx, vdy = A.vy - B.vy;
-        const double ivx = P[12] * vdx - nx, ivy = P[12] * vdy - ny;
-        const double inorm = norm2(ivx, ivy);
-        const double ix = ivx / inorm, iy = ivy / inorm;
-        // (the correctly rounded atan2, atan2_cr.h: with nobody moving theta_ij is the rounding of these two values and the law takes its
-        //  sign -- the reference's C library rounds them correctly, the device library's atan2 is an ulp off now and then)
-        const double th = bound_angle(crmath::atan2_cr(ny, nx) - crmath::atan2_cr(iy, ix) + M_PI);
-        const double k = (th > 0) ? 1.0 : ((th < 0) ? -1.0 : 0.0);
-        const double hx = -iy, hy = ix;
-        const double F = P[13] * inorm;
-        const double dv = (-vdx) * hx + (-vdy) * hy;
-        const double e0 = P[9] * exp(-dist / F);
-        const double a1 = P[15] * F * th, a2 = P[14] * F * th;
-        const double e1 = exp(-(a1 * a1)), e2 = exp(-(a2 * a2));
-        fx = -(e0 * (e1 * ix + k * e2 * hx) + P[10] * m0 * ix + P[11] * m0 * dv * hx);
-        fy = -(e0 * (e1 * iy + k * e2 * hy) + P[10] * m0 * iy + P[11] * m0 * dv * hy);
-    }
+    laws::pair_force<laws::CrD>(SOC, P, A.px, A.py, A.vx, A.vy, B.px, B.py, B.vx, B.vy, A.r + B.r + A.s + B.s, fx, fy);
 }
 
 template <int SOC, bool PEQ>
@@ -214,15 +174,7 @@ __global__ __launch_bounds__(64 * F64_WPB) void k_sfm_step_f64(const Args64 a)
         if (human) {
             // -- desired force :23-40
             double fdx = 0, fdy = 0;
-            {
-                const double dx = gx - px, dy = gy - py;
-                const double dist = norm2(dx, dy);
-                if (dist > r) {
-                    const double ex = dx / dist, ey = dy / dist;
-                    fdx = m * (ex * vd - svx) / Pi[0];
-                    fdy = m * (ey * vd - svy) / Pi[0];
-                }
-            }
+            laws::desired_force(gx, gy, px, py, svx, svy, r, m, vd, Pi[0], fdx, fdy);
             // -- closest point per polygon :236-252 (first argmin, a NaN segment = huge distance) and the obstacle force :136-162
             double fox = 0, foy = 0;
             if (ob != nullptr) {
@@ -248,21 +200,7 @@ __global__ __launch_bounds__(64 * F64_WPB) void k_sfm_step_f64(const Args64 a)
                     }
                     const double dx = px - cx, dy = py - cy;
                     const double dist = norm2(dx, dy);
-                    const double nx = dx / dist, ny = dy / dist;
-                    const double tx = -ny, ty = nx;
-                    const double dv = -(svx * tx + svy * ty);
-                    const double rd = r - dist + sf;
-                    const double m0 = rd > 0 ? rd : 0.0;
-                    const double fn = Pi[2] * exp(rd / Pi[4]) + Pi[10] * m0;
-                    if constexpr (SOC != 1) {
-                        const double ft = Pi[11] * m0 * dv;
-                        fox += fn * nx - ft * tx;
-                        foy += fn * ny - ft * ty;
-                    } else {
-                        const double ft = (-Pi[6] * exp(rd / Pi[8]) - Pi[11] * m0) * dv;
-                        fox += fn * nx + ft * tx;
-                        foy += fn * ny + ft * ty;
-                    }
+                    laws::wall_term(SOC, Pi, dx / dist, dy / dist, r - dist + sf, svx, svy, fox, foy);
                 }
                 fox /= (double)a.O; foy /= (double)a.O;
             }
@@ -271,13 +209,7 @@ __global__ __launch_bounds__(64 * F64_WPB) void k_sfm_step_f64(const Args64 a)
             if (headed == 0) { gfx = fix; gfy = fiy; }
             else {
                 inertia = 0.5 * m * r * r;
-                const double drx = headed == 1 ? fdx : fix, dry = headed == 1 ? fdy : fiy;
-                const double fnorm = norm2(drx, dry);
-                const double k_theta = inertia * Pi[19] * fnorm;
-                const double k_omega = inertia * (1 + Pi[18]) * sqrt((Pi[19] * fnorm) / Pi[18]);
-                torque = -k_theta * bound_angle(th - atan2(dry, drx)) - k_omega * om;
-                gfx = fix * c + fiy * s;
-                gfy = Pi[16] * ((fox + fsx) * (-s) + (foy + fsy) * c) - Pi[17] * bvy;
+                laws::headed_force(headed == 2, Pi, inertia, fdx, fdy, fix, fiy, fox + fsx, foy + fsy, th, om, bvy, s, c, gfx, gfy, torque);
             }
             // -- update_humans_parallel(...) out of place: the input array keeps the reference's in-place mutations
             if (a.mode & M64_MUTATE_INPUT) {
