@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import _lib
 from ..batched import CrowdWorlds, HUMAN_MODELS as _MODELS
+from .device_loop import DeviceLoop, SideStream, StepPieces, clock_table, stage_depth
 from .social_nav_sim import SocialNavSim
 from .src.info import INFO_BY_CODE, Collision, Danger, Nothing, ReachGoal, Timeout  # noqa: F401
 from .src.utils import is_multiple
@@ -386,106 +387,38 @@ class BatchedSocialNavGym:
     STAGE_BYTES = 1 << 30
     REFILL_PRIORITY = 0      # stream priority of the refill passes (1 = the device's lowest: no measurable difference)
     FOLD_RESET = True        # the take-over of the staged episodes inside the step's launch (cs_gym_step_staged) where the step kernel allows it
-
-    def _stage_depth(self):
-        rows = self.cw.rows
-        level = self.W * (rows * 13 + self.n * self.cw.G * 2 + 13 + 1) * 4
-        d = max(1, int(self.STAGE_DEPTH))
-        while d > 2 and d * level > self.STAGE_BYTES:
-            d //= 2
-        return 1 << (d.bit_length() - 1)
+    _dl = None               # the batch's DeviceLoop once a device method has run
 
     def _device_loop_state(self):
-        """Per-world step counters, seeds, the float32 clock table and the pre-staged next episodes, resident on the GPU."""
-        import ctypes as C
-
-        import torch
-
+        """The batch's ``DeviceLoop`` (device_loop.py), built with the first call after ``reset(..., device=True)``."""
         from .. import generators as gen
 
-        if getattr(self, "_dl", None) is not None and self._dl["cw"] is self.cw:
-            return self._dl
+        dl = self._dl
+        if dl is not None and dl.cw is self.cw:
+            return dl
         if getattr(self, "_gen_scenario", None) is None:
             raise RuntimeError("step_device needs a world batch generated on the device: reset(..., device=True)")
-        if getattr(self, "_dl", None) is not None:       # a new batch: the old one's refill pass may still be writing its staging worlds
-            self._release_device_loop()
+        self._release_device_loop()      # a new batch: the old one's refill pass may still be writing its staging worlds
         try:
+            import torch
+
             torch.zeros(1, device="cuda")
         except RuntimeError as e:  # _lib.load() maps torch's bundled HIP runtime for both, whatever the import order
             raise _lib.CrowdstepError("torch cannot see the GPU in this process (HIP runtime in use: "
                                       f"{_lib.hip_runtime_path or 'system'}; CROWDSTEP_HIP_RUNTIME=system forces two runtimes): {e}") from e
-        W = self.W
-        # global_time is accumulated in float32, time_step_factor additions of time_step per step (social_nav_gym.py:244):
-        # the same sequence as a table indexed by the per-world step counter
-        max_steps = int(self.time_limit / (self.time_step * self.time_step_factor)) + 8
-        clock = np.zeros(max_steps, np.float32)
-        t = np.float32(0)
-        for k in range(1, max_steps):
-            for _ in range(self.time_step_factor):
-                t = t + np.float32(self.time_step)
-            clock[k] = t
-        seeds = torch.as_tensor(self._seeds_host.astype(np.int64), device="cuda").to(torch.int32)
-        depth = self._stage_depth()
-        dl = dict(depth=depth, cw=self.cw, clock=torch.as_tensor(clock, device="cuda"),
-                  counter=torch.zeros(W, dtype=torch.int32, device="cuda"),
-                  parity=0,
-                  results=[(torch.zeros(W, dtype=torch.float32, device="cuda"), torch.zeros(W, dtype=torch.bool, device="cuda"),
-                            torch.zeros(W, dtype=torch.bool, device="cuda"), torch.zeros(W, dtype=torch.int32, device="cuda"))
-                           for _ in range(2)],
-                  gtime=torch.zeros(W, dtype=torch.float32, device="cuda"),
-                  seeds=seeds,
-                  # a world's seed moves on by the worlds of the WHOLE job when its episode ends: world w walks s + w + k * stride on
-                  # any rank count (ShardedBatchedSocialNavGym sets seed_stride = total_worlds; a single process: W)
-                  stride=int(getattr(self, "seed_stride", None) or W),
-                  mask=torch.zeros(W, dtype=torch.int32, device="cuda"),
-                  # pre-staged episodes (include/crowdstep.h cs_stage_book): episode e of world w draws base_seed[w] + e * stride; no slot's
-                  # tag is the seed of the episode that belongs in it, so the first refill pass generates every slot
-                  base_seed=seeds.clone(), epoch=torch.zeros(W, dtype=torch.int32, device="cuda"),
-                  staged_seed=seeds.repeat(depth).contiguous(),
-                  staged_status=torch.zeros(W * depth, dtype=torch.int32, device="cuda"),
-                  failed=torch.zeros(W, dtype=torch.int32, device="cuda"),
-                  pending=torch.zeros(W, dtype=torch.int32, device="cuda"),     # cs_gym_step_staged: take-overs deferred to a later step
-                  out=self.cw._buffer("reward_out", (W, 7)).torch(),
-                  state=self.cw.d_state.torch().view(W, self.cw.rows, 13),
-                  gen=gen.make_generator(self.cw, self._gen_scenario, **self._gen_kw),
-                  cols=torch.as_tensor([0, 1, 3, 4, 8] + ([2, 7] if self.headed_obs else []), device="cuda"))
-        # the step runs on a torch side stream (ordered against the caller's stream with wait_stream); a library stream carries the
-        # refill passes of the staging batch; persistent action / observation tensors
-        dl["stream"] = torch.cuda.Stream()
-        dl["stream_b"] = _lib.stream_create(priority=self.REFILL_PRIORITY)
-        dl["act"] = torch.zeros((W, 2), dtype=torch.float32, device="cuda")
-        dl["obs"] = torch.zeros((W, self.n, 7 if self.headed_obs else 5), dtype=torch.float32, device="cuda")
-        dl["staging"] = self.cw.staging_copy(depth)
-        dl["staging"].stream = dl["stream_b"]
-        P = lambda t: t.data_ptr()
-        dl["stage_book"] = _lib.cs_stage_book(d_seeds=P(dl["seeds"]), d_base_seed=P(dl["base_seed"]), d_epoch=P(dl["epoch"]),
-                                              d_staged_seed=P(dl["staged_seed"]), d_staged_status=P(dl["staged_status"]), d_failed=P(dl["failed"]),
-                                              seed_stride=dl["stride"], depth=depth, d_pending=P(dl["pending"]))
-        dl["staging_desc"] = dl["staging"].descriptor()
-        dl["refill_args"] = (C.byref(dl["gen"]), C.byref(dl["staging_desc"]), C.byref(dl["stage_book"]), C.c_void_p(dl["stream_b"]))
-        dl["refill_ev"] = _lib.Event()
-        dl["since_refill"] = 0
-        self.cw.stream = dl["stream"].cuda_stream
-        torch.cuda.synchronize()
-        # every world's next STAGE_DEPTH episodes, generated once up front; from here on a pass only regenerates the consumed slots
-        _lib.check(_lib.load().cs_refill_staged_worlds(*dl["refill_args"]))
-        dl["refill_ev"].record(dl["stream_b"])
-        _lib.stream_sync(dl["stream_b"])
-        self._dl = dl
-        return dl
+        cw = self.cw
+        level = self.W * (cw.rows * 13 + self.n * cw.G * 2 + 13 + 1) * 4
+        self._dl = DeviceLoop(cw, n=self.n, headed_obs=self.headed_obs, clock=clock_table(self.time_limit, self.time_step, self.time_step_factor),
+                              seeds_host=self._seeds_host, stride=getattr(self, "seed_stride", None) or self.W,
+                              depth=stage_depth(level, self.STAGE_DEPTH, self.STAGE_BYTES),
+                              gen=gen.make_generator(cw, self._gen_scenario, **self._gen_kw), refill_priority=self.REFILL_PRIORITY)
+        return self._dl
 
     def _release_device_loop(self):
-        """The refill passes run on a library stream torch's allocator knows nothing about, on tensors torch owns (epoch, base_seed, the
-        staging tags): before those tensors can go back to the allocator the stream must have drained -- and it is destroyed, not leaked."""
-        dl = getattr(self, "_dl", None)
-        if dl is None:
-            return
-        self._dl = None
-        try:
-            _lib.stream_sync(dl["stream_b"])
-            _lib.stream_destroy(dl["stream_b"])
-        except Exception:
-            pass
+        """Drains and destroys the loop's refill stream (``DeviceLoop.release``) and lets the loop go."""
+        dl, self._dl = self._dl, None
+        if dl is not None:
+            dl.release()
 
     def close(self):
         """End of the environment's device-resident loop (also run when the object is collected): drains and destroys the refill stream."""
@@ -497,28 +430,10 @@ class BatchedSocialNavGym:
         except Exception:
             pass
 
-    def _maybe_refill(self, dl):
-        """Every REFILL_EVERY steps: one pass of cs_refill_staged_worlds on the side stream (at most one in flight).  Nothing orders it
-        against the step's stream -- the staging slots carry tags (cs_stage_book) -- so it costs the step no wait and no event."""
-        dl["since_refill"] += 1
-        if dl["since_refill"] < self.REFILL_EVERY or not dl["refill_ev"].done():
-            return
-        _lib.check(_lib.load().cs_refill_staged_worlds(*dl["refill_args"]))
-        dl["refill_ev"].record(dl["stream_b"])
-        dl["since_refill"] = 0
-
     def observe_device(self):
         """Observations [W, N, 5|7] as a torch CUDA tensor gathered from the resident state (no host copy)."""
         dl = self._device_loop_state()
-        return dl["state"][:, :self.n].index_select(2, dl["cols"])
-
-    def _gym_book(self, dl, parity, mask, prev_mask, auto_reset):
-        reward, terminated, truncated, info = dl["results"][parity]
-        return _lib.cs_gym_book(d_counter=dl["counter"].data_ptr(), d_seeds=dl["seeds"].data_ptr(), d_mask=mask.data_ptr(),
-                                d_prev_mask=None if prev_mask is None else prev_mask.data_ptr(), d_clock=dl["clock"].data_ptr(),
-                                clock_len=dl["clock"].numel(), auto_reset=int(bool(auto_reset)), d_reward=reward.data_ptr(),
-                                d_terminated=terminated.data_ptr(), d_truncated=truncated.data_ptr(), d_info=info.data_ptr(),
-                                seed_stride=dl["stride"])
+        return dl.state[:, :self.n].index_select(2, dl.cols)
 
     def _step_pieces(self, dl, parity, mode):
         r"""One vectorised Gym step = ONE library launch (cs_gym_step_staged; SFM / HSFM crowds on the one-wavefront kernels) or two on one
@@ -529,7 +444,7 @@ class BatchedSocialNavGym:
         Which worlds end is known from the reward of the state BEFORE the substeps (social_nav_gym.py:229-233); their next episode
         was generated ahead (its seed is the live one + stride), so the reset is a masked copy.  The regeneration of the consumed
         staging slots (one latency-bound wavefront per world, ~0.15 ms) runs on a side stream with a whole episode to finish
-        (_maybe_refill) -- round 3 had it on the critical path (144 us per step) or beside the next step (NEXT_STEP mode, 88 us).
+        (DeviceLoop.maybe_refill) -- round 3 had it on the critical path (144 us per step) or beside the next step (NEXT_STEP mode, 88 us).
 
         mode "same_step": the worlds whose episode ends NOW take over their staged episode before the observation is returned;
         mode "next_step" (Gymnasium's default since 1.0): the bookkeeping of this parity writes mask_p and reads prev = mask_{1-p};
@@ -541,38 +456,38 @@ class BatchedSocialNavGym:
         saves the host nothing it needs (28 us of host time per step against 44 us on the GPU)."""
         import ctypes as C
 
-        key = ("pieces", parity, mode)
-        if key in dl:
-            return dl[key]
+        c = dl.pieces.get((parity, mode))
+        if c is not None:
+            return c
         cw = self.cw
-        A = C.c_void_p(dl["stream"].cuda_stream)
+        A = C.c_void_p(dl.stream.cuda_stream)
         d = cw.descriptor()
         dref = C.byref(d)
         cfg = (C.c_float * 5)(*[float(x) for x in self.reward_cfg])
         P = lambda t: C.c_void_p(t.data_ptr())
         if mode == "next_step":
-            masks = dl["ns_masks"]
-            book = self._gym_book(dl, parity, masks[parity], masks[parity ^ 1], True)
+            masks = dl.ns_masks
+            book = dl.gym_book(parity, masks[parity], masks[parity ^ 1], True)
             tail_mask = masks[parity ^ 1]
         else:
-            book = self._gym_book(dl, parity, dl["mask"], None, mode == "same_step")
-            tail_mask = dl["mask"] if mode == "same_step" else None
+            book = dl.gym_book(parity, dl.mask, None, mode == "same_step")
+            tail_mask = dl.mask if mode == "same_step" else None
         # cs_gym_step: reward of the state before the substeps + typed results, step counter, float32 clock, reset mask and next seeds
         # (the head: the step kernel's prologue), the substeps, and the observation of the stepped crowd from the kernel's registers
-        a_step = (dref, C.c_float(self.time_step), C.c_int(self.time_step_factor), P(dl["act"]), C.c_float(self.robot_time_step), P(dl["gtime"]), cfg,
-                  P(dl["out"]), C.byref(book), C.c_int(int(self.headed_obs)), P(dl["obs"]), A)
+        a_step = (dref, C.c_float(self.time_step), C.c_int(self.time_step_factor), P(dl.act), C.c_float(self.robot_time_step), P(dl.gtime), cfg,
+                  P(dl.out), C.byref(book), C.c_int(int(self.headed_obs)), P(dl.obs), A)
         # ... rewritten for the worlds that take over their staged episode (a world whose generation failed keeps its rows and is
         # flagged in reset_failed_mask())
-        a_tail = None if tail_mask is None else (C.byref(dl["gen"]), C.byref(dl["staging_desc"]), dref, P(tail_mask), C.byref(dl["stage_book"]),
-                                                 C.c_int(int(self.headed_obs)), P(dl["obs"]), A)
+        a_tail = None if tail_mask is None else (C.byref(dl.gen), C.byref(dl.staging_desc), dref, P(tail_mask), C.byref(dl.stage_book),
+                                                 C.c_int(int(self.headed_obs)), P(dl.obs), A)
         # ... or both in ONE launch (cs_gym_step_staged: the take-over in the step kernel's epilogue) where the step is the one-wavefront
         # SFM / HSFM kernel; FOLD_RESET = False keeps the two launches (the bit-equality reference of the tests)
         a_fold = None
         if tail_mask is not None and self.FOLD_RESET and _lib.load().cs_gym_step_is_one_launch(dref) == 2:
-            a_fold = a_step[:-1] + (C.byref(dl["gen"]), C.byref(dl["staging_desc"]), C.byref(dl["stage_book"]), A)
+            a_fold = a_step[:-1] + (C.byref(dl.gen), C.byref(dl.staging_desc), C.byref(dl.stage_book), A)
         keep = (d, cfg, book)              # the structs the byref arguments point into
-        dl[key] = dict(step=a_step, tail=a_tail, fold=a_fold, keep=keep, results=(dl["obs"],) + dl["results"][parity])
-        return dl[key]
+        c = dl.pieces[parity, mode] = StepPieces(a_step, a_tail, a_fold, keep, (dl.obs,) + dl.results[parity])
+        return c
 
     def _open_step(self, dl, auto_reset):
         """The head of a step: the auto-reset mode (no change while a NEXT_STEP reset is pending), the parity flip, its _step_pieces."""
@@ -580,41 +495,33 @@ class BatchedSocialNavGym:
 
         mode = "next_step" if auto_reset == "next_step" else ("same_step" if auto_reset else "none")
         if mode == "next_step":
-            if "ns_masks" not in dl:
-                dl["ns_masks"] = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
+            if dl.ns_masks is None:
+                dl.ns_masks = [torch.zeros(self.W, dtype=torch.int32, device="cuda") for _ in range(2)]
                 torch.cuda.synchronize()
-        elif dl.get("mode") == "next_step" and "ns_masks" in dl and any(bool(m.any().item()) for m in dl["ns_masks"]):
+        elif dl.mode == "next_step" and dl.ns_masks is not None and any(bool(m.any().item()) for m in dl.ns_masks):
             raise RuntimeError("a NEXT_STEP auto-reset is pending for some world: keep auto_reset=\"next_step\" (or reset()) before changing the mode")
-        dl["mode"] = mode
-        parity = dl["parity"]
-        dl["parity"] ^= 1
+        dl.mode = mode
+        parity = dl.parity
+        dl.parity = parity ^ 1
         return self._step_pieces(dl, parity, mode)
-
-    @staticmethod
-    def _stream_handshake(dl, cur, before):
-        """Device-side ordering of a call on the library's stream with the caller's ``cur``: before it with whatever produced the actions,
-        after it with whoever reads the results.  Nothing where the caller already works on the library's stream (``device_stream()``)."""
-        side = dl["stream"]
-        if cur.cuda_stream != side.cuda_stream:
-            side.wait_stream(cur) if before else cur.wait_stream(side)
 
     def _issue_step(self, dl, c, pargs=None):
         """One step's library calls: the one-launch fold, or the step + tail; with ``pargs`` the entries that decide the action first."""
         lib, chk = _lib.load(), _lib.check
-        if c["fold"] is not None:
+        if c.fold is not None:
             if pargs is None:
-                chk(lib.cs_gym_step_staged(*c["fold"]))
+                chk(lib.cs_gym_step_staged(*c.fold))
             else:
-                chk(lib.cs_gym_step_staged_policy(*c["fold"][:-1], *pargs, c["fold"][-1]))
-            self._maybe_refill(dl)
+                chk(lib.cs_gym_step_staged_policy(*c.fold[:-1], *pargs, c.fold[-1]))
+            dl.maybe_refill(self.REFILL_EVERY)
             return
         if pargs is None:
-            chk(lib.cs_gym_step(*c["step"]))
+            chk(lib.cs_gym_step(*c.step))
         else:
-            chk(lib.cs_gym_step_policy(*c["step"][:-1], *pargs, c["step"][-1]))
-        if c["tail"] is not None:
-            chk(lib.cs_consume_staged_worlds(*c["tail"]))
-            self._maybe_refill(dl)
+            chk(lib.cs_gym_step_policy(*c.step[:-1], *pargs, c.step[-1]))
+        if c.tail is not None:
+            chk(lib.cs_consume_staged_worlds(*c.tail))
+            dl.maybe_refill(self.REFILL_EVERY)
 
     def _no_train_policy(self, dl, policy, who):
         """The no-train policy behind a policy_factory name or an instance, refused where this batch cannot take it (``who`` asks)."""
@@ -623,7 +530,7 @@ class BatchedSocialNavGym:
         if isinstance(policy, str):
             from ..crowd_nav.policy_no_train.policy_factory import policy_factory
 
-            pol = dl.setdefault("pnt_named", {}).get(policy) or dl["pnt_named"].setdefault(policy, policy_factory[policy]())
+            pol = dl.pnt_named.get(policy) or dl.pnt_named.setdefault(policy, policy_factory[policy]())
         else:
             pol = policy
         if not isinstance(pol, NoTrainPolicy):
@@ -641,23 +548,23 @@ class BatchedSocialNavGym:
         ts = self.robot_time_step if pol.time_step is None else pol.time_step
         prm = pol.packed_params()
         key = (pol.pnt_id, ts, None if prm is None else prm.ctypes.data)
-        bound = dl.setdefault("pnt_args", {})
+        bound = dl.pnt_args
         b = bound.get(key)
         if b is None:
             P = lambda t: C.c_void_p(t.data_ptr())
             step = (C.c_int(pol.pnt_id), C.c_float(ts), None if prm is None else prm.ctypes.data_as(C.c_void_p))
-            act = (step[0], C.c_int(self.W), C.c_int(self.n), C.c_void_p(self.cw.d_robot.ptr), P(dl["obs"]), C.c_int(dl["obs"].shape[2]), step[1], step[2],
-                   P(dl["act"]), C.c_void_p(dl["stream"].cuda_stream))
+            act = (step[0], C.c_int(self.W), C.c_int(self.n), C.c_void_p(self.cw.d_robot.ptr), P(dl.obs), C.c_int(dl.obs.shape[2]), step[1], step[2],
+                   P(dl.act), C.c_void_p(dl.stream.cuda_stream))
             b = bound[key] = dict(step=step, act=act, keep=prm)
         return b
 
     def _observe_if_stale(self, dl):
         """No step since the batch was generated: the observation of the resident rows (what a decision in a launch of its own reads)."""
-        if dl.get("obs_fresh"):
+        if dl.obs_fresh:
             return
         d = self.cw.descriptor(respawn=False)
-        _lib.check(_lib.load().cs_gym_observe(d, self.headed_obs, dl["obs"].data_ptr(), dl["stream"].cuda_stream))
-        dl["obs_fresh"] = True
+        _lib.check(_lib.load().cs_gym_observe(d, self.headed_obs, dl.obs.data_ptr(), dl.stream.cuda_stream))
+        dl.obs_fresh = True
 
     def step_device(self, actions, auto_reset=True):
         """``step`` without leaving the GPU: ``actions`` is a float32 torch CUDA tensor [W, 2] (holonomic vx, vy) -- or
@@ -669,19 +576,16 @@ class BatchedSocialNavGym:
         NEXT_STEP mode: a world that ended at step t returns its terminal observation at t and the first observation of its next
         episode -- with reward 0 and no termination -- at t + 1, taken over from the staging batch at the end of step t + 1.
         ``auto_reset=False``: no resets (a finished world keeps stepping)."""
-        import torch
-
         dl = self._device_loop_state()
         c = self._open_step(dl, auto_reset)
-        cur = torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        if actions is not dl["act"]:
-            with torch.cuda.stream(dl["stream"]):
-                dl["act"].copy_(actions.to(device="cuda", dtype=torch.float32), non_blocking=True)
-        self._issue_step(dl, c)
-        self._stream_handshake(dl, cur, False)
-        dl["obs_fresh"] = True                     # the step wrote the observation buffer act_device reads
-        return c["results"]
+        with SideStream(dl):
+            if actions is not dl.act:
+                import torch
+
+                dl.act.copy_(actions.to(device="cuda", dtype=torch.float32), non_blocking=True)
+            self._issue_step(dl, c)
+        dl.obs_fresh = True                        # the step wrote the observation buffer act_device reads
+        return c.results
 
     def reset_failed_mask(self):
         """int32 CUDA tensor [W], no synchronisation: 1 where the world's LAST device-side auto-reset could not be generated
@@ -692,20 +596,20 @@ class BatchedSocialNavGym:
         reset that succeeds.  2: the take-over was DEFERRED (one-launch step, cs_gym_step_staged: the staged episode was not ready; the
         world is between two episodes -- reward 0, no flags -- until a later step finds it; with the refill cadence of this class that does
         not happen)."""
-        return self._device_loop_state()["failed"]
+        return self._device_loop_state().failed
 
     def failed_resets(self) -> int:
         """Number of worlds flagged in ``reset_failed_mask()``.  Synchronises."""
-        return int((self._device_loop_state()["failed"] != 0).sum().item())
+        return int((self._device_loop_state().failed != 0).sum().item())
 
     def device_stream(self):
         """The torch stream the device-resident step runs on.  A loop that does its own GPU work inside ``with torch.cuda.stream(env.device_stream())``
         is ordered with the step by the stream itself: step_device then skips its two cross-stream waits (four HIP calls per step)."""
-        return self._device_loop_state()["stream"]
+        return self._device_loop_state().stream
 
     def action_buffer(self):
         """The persistent [W, 2] action tensor the step kernel reads: write actions into it and pass it to ``step_device``."""
-        return self._device_loop_state()["act"]
+        return self._device_loop_state().act
 
     def act_device(self, policy, explore=None):
         """Every world's robot decides with a no-train CrowdNav policy (``policy``: a name of crowd_nav.policy_no_train.policy_factory or
@@ -729,23 +633,19 @@ class BatchedSocialNavGym:
         which allocates no look-ahead tensor); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
         the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order (cs_value_net_decide_lstm_om_bf16 after the
         policy's ``set_mapped_precision("bf16")``)."""
-        import torch
-
-        dl = self._device_loop_state()
         if not isinstance(policy, str):
             from ..crowd_nav.policy.cadrl import CADRL
 
             if isinstance(policy, CADRL):
-                return self._act_device_value(dl, policy, explore)
+                return self._act_device_value(policy, explore)
+        dl = self._device_loop_state()
         if explore is not None:
             raise ValueError("act_device: explore= belongs to the value-based policies (CADRL, SARL)")
         pol = self._no_train_policy(dl, policy, "act_device")
-        cur = torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        self._observe_if_stale(dl)
-        _lib.check(_lib.load().cs_policy_no_train(*self._policy_args(dl, pol)["act"]))     # a decision is one library call
-        self._stream_handshake(dl, cur, False)
-        return dl["act"]
+        with SideStream(dl):
+            self._observe_if_stale(dl)
+            _lib.check(_lib.load().cs_policy_no_train(*self._policy_args(dl, pol)["act"]))     # a decision is one library call
+        return dl.act
 
     def act_step_device(self, policy, auto_reset=True):
         """``act_device(policy)`` and ``step_device(action_buffer(), auto_reset)`` as ONE library call -- and, for the SFM / HSFM crowds of
@@ -755,8 +655,6 @@ class BatchedSocialNavGym:
         actions in ``action_buffer()``; runs on ``device_stream()``, nothing crosses to the host.  Bit for bit the results of the two
         calls.  The other crowds (ORCA, social momentum, walls, the smallest worlds) run the decision kernel and the step's launches
         inside the same call.  A CADRL / SARL instance decides in milliseconds and gains nothing here: ``act_device``, then ``step_device``."""
-        import torch
-
         from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
 
         if not isinstance(policy, (str, NoTrainPolicy)):   # (refused before anything touches the device)
@@ -766,12 +664,10 @@ class BatchedSocialNavGym:
         pol = self._no_train_policy(dl, policy, "act_step_device")
         c = self._open_step(dl, auto_reset)
         pargs = self._policy_args(dl, pol)["step"]
-        cur = torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        self._observe_if_stale(dl)
-        self._issue_step(dl, c, pargs)
-        self._stream_handshake(dl, cur, False)
-        return c["results"]
+        with SideStream(dl):
+            self._observe_if_stale(dl)
+            self._issue_step(dl, c, pargs)
+        return c.results
 
     def act_step_variant(self) -> str:
         """Which kernels ``act_step_device`` runs for this batch (cs_gym_step_policy_variant): the step build that decides in its head, or
@@ -783,21 +679,34 @@ class BatchedSocialNavGym:
         _lib.check(_lib.load().cs_gym_step_policy_variant(d, buf, 320))
         return buf.value.decode()
 
-    def _act_device_value(self, dl, pol, explore):
+    def _refuse_value_policy(self, who, pol, before, kinematics_first=False):
+        """What ``who`` cannot take as a value-based policy of this batch, refused before anything touches the device.  ``before``: what the
+        policy was about to do unconfigured; ``kinematics_first``: act_device's order, the robot's kinematics ahead of the missing model."""
+        from ..crowd_nav.policy.cadrl import CADRL
+
+        if not isinstance(pol, CADRL):
+            raise TypeError(f"{who} takes a value-based policy (CADRL, SARL), not {pol!r}")
+        refusals = [(pol.model is None, AttributeError(f"{pol.name}: configure() the policy before it {before}")),
+                    (pol.kinematics != "holonomic" or (self.cw is not None and self.cw.unicycle),
+                     ValueError(f"{who}: the value-based policies act in ActionXY and need a holonomic robot"))]
+        for refused, error in reversed(refusals) if kinematics_first else refusals:
+            if refused:
+                raise error
+        if bool(pol.with_theta_and_omega_visible) != self.headed_obs:
+            raise ValueError(f"{who}: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
+        if self.cw is not None and self.cw.d_robot is None:
+            raise ValueError(f"{who} needs the robot rows")
+        if 1 < pol.family.min_humans and self._human_count() < pol.family.min_humans:      # (only a family with maps asks for more than one)
+            raise ValueError(f"{who}: {pol.name}'s occupancy maps need at least two humans a world")
+
+    def _act_device_value(self, pol, explore):
         """act_device for a CADRL / SARL instance: W decisions of its value network, nothing crosses to the host."""
         import torch
 
         from ..crowd_nav.policy import value_net
 
-        if pol.kinematics != "holonomic" or self.cw.unicycle:
-            raise ValueError("act_device: the value-based policies act in ActionXY and need a holonomic robot")
-        if pol.model is None:
-            raise AttributeError(f"{pol.name}: configure() the policy before it decides")
-        if bool(pol.with_theta_and_omega_visible) != self.headed_obs:
-            raise ValueError("act_device: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
-        if self.cw.d_robot is None:
-            raise ValueError("act_device needs the robot rows")
-        self._require_humans("act_device", pol)
+        self._refuse_value_policy("act_device", pol, "decides", kinematics_first=True)
+        dl = self._device_loop_state()
         if pol.action_space_ndarray is None:
             pol.build_action_space(float(self._gen_kw["robot_desired_speed"]))
         W = self.W
@@ -808,12 +717,10 @@ class BatchedSocialNavGym:
                 raise ValueError("act_device: explore is an int32 CUDA tensor [W] of action indices (-1 = greedy)")
             explore = explore.contiguous()
         net = pol.device_net()                       # (repacked here, on the caller's stream, only when a parameter changed)
-        if dl.get("vn_values") is None or dl["vn_values"].shape[1] != A:
-            dl["vn_values"] = torch.zeros((W, A), dtype=torch.float32, device="cuda")
-            dl["vn_choice"] = torch.zeros(W, dtype=torch.int32, device="cuda")
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        with torch.cuda.stream(side):
+        if dl.vn_values is None or dl.vn_values.shape[1] != A:
+            dl.vn_values = torch.zeros((W, A), dtype=torch.float32, device="cuda")
+            dl.vn_choice = torch.zeros(W, dtype=torch.int32, device="cuda")
+        with SideStream(dl) as s:
             nxt = None
             if not pol.query_env:                    # cadrl.py:92-105: the humans keep their velocity over the robot's step
                 o, T = self.observe_device(), self.robot_time_step
@@ -821,22 +728,19 @@ class BatchedSocialNavGym:
                        if self.headed_obs else torch.stack([o[..., 0] + o[..., 2] * T, o[..., 1] + o[..., 3] * T, o[..., 2], o[..., 3]], -1)).contiguous()
             nxt, cur_, rob = self._worlds_on_side_stream(dl, nxt)
             rot, rew = value_net.decide_for_worlds(net, pol.decision_input, pol.decision_precision, acts, nxt, cur_, rob, pol.gamma, self.robot_time_step,
-                                                   explore, dl["vn_values"], dl["vn_choice"], dl["act"], side.cuda_stream,
+                                                   explore, dl.vn_values, dl.vn_choice, dl.act, dl.stream.cuda_stream,
                                                    recurrent_precision=pol.recurrent_precision, mapped_precision=pol.mapped_precision,
                                                    wide_precision=pol.wide_precision, recurrent_input=pol.recurrent_input)
-            for t in (nxt, cur_, rob, rot, rew, explore):
-                if t is not None:
-                    t.record_stream(side)
-        self._stream_handshake(dl, cur, False)
-        return dl["act"]
+            s.inputs = (nxt, cur_, rob, rot, rew, explore)
+        return dl.act
 
     def last_values_device(self):
         """(action values [W, A] float32, chosen action index [W] int32) of the last value-based ``act_device`` decision, as CUDA tensors
         rewritten by the next one; None before the first."""
         dl = self._device_loop_state()
-        if dl.get("vn_values") is None:
+        if dl.vn_values is None:
             return None
-        return dl["vn_values"], dl["vn_choice"]
+        return dl.vn_values, dl.vn_choice
 
     def joint_state_device(self, policy):
         """What a trainer stores for the decision every robot is about to take: ``policy.transform`` of every world's resident state -- the
@@ -866,21 +770,8 @@ class BatchedSocialNavGym:
         return (values, rows) if with_state else values
 
     def _state_values_device(self, who, pol, model, rewards, dt, with_rows):
-        """cs_value_net_state on the resident worlds, with act_device's refusals (made before anything touches the device), stream handshake
-        and record_stream discipline: (values [W], rows [W, n, cols] or None)."""
-        from ..crowd_nav.policy.cadrl import CADRL
-
-        if not isinstance(pol, CADRL):
-            raise TypeError(f"{who} takes a value-based policy (CADRL, SARL), not {pol!r}")
-        if pol.model is None:
-            raise AttributeError(f"{pol.name}: configure() the policy before it evaluates a state")
-        if pol.kinematics != "holonomic" or (self.cw is not None and self.cw.unicycle):
-            raise ValueError(f"{who}: the value-based policies act in ActionXY and need a holonomic robot")
-        if bool(pol.with_theta_and_omega_visible) != self.headed_obs:
-            raise ValueError(f"{who}: the policy's with_theta_and_omega_visible and the batch's headed_obs differ")
-        if self.cw is not None and self.cw.d_robot is None:
-            raise ValueError(f"{who} needs the robot rows")
-        self._require_humans(who, pol)
+        """cs_value_net_state on the resident worlds, with act_device's refusals and stream scope: (values [W], rows [W, n, cols] or None)."""
+        self._refuse_value_policy(who, pol, "evaluates a state")
         import torch
 
         from ..crowd_nav.policy import value_net
@@ -891,26 +782,16 @@ class BatchedSocialNavGym:
                 raise ValueError(f"{who}: rewards is a float32 CUDA tensor [W]")
             rewards = rewards.contiguous()
         net = pol.state_net(model)                   # (repacked here, on the caller's stream, only when a parameter changed)
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        with torch.cuda.stream(side):
+        with SideStream(dl) as s:
             _, cur_, rob = self._worlds_on_side_stream(dl, peek=False)
-            values, rows = value_net.state_values_for_worlds(net, cur_, rob, rewards, pol.gamma, dt, with_rows, side.cuda_stream)
-            for t in (cur_, rob, rewards, values, rows):
-                if t is not None:
-                    t.record_stream(cur if t is values or t is rows else side)
-        self._stream_handshake(dl, cur, False)
+            values, rows = value_net.state_values_for_worlds(net, cur_, rob, rewards, pol.gamma, dt, with_rows, dl.stream.cuda_stream)
+            s.inputs, s.outputs = (cur_, rob, rewards), (values, rows)
         return values, rows
 
     def _human_count(self):
         """Humans a world: of the generated batch, or what the configuration will generate"""
         n = getattr(self, "n", None)
         return int(n) if n is not None else self.config.getint("sim", "human_num")
-
-    def _require_humans(self, who, pol):
-        """The refusal of a batch whose worlds have fewer humans than the policy's network family needs (value_net.Family.min_humans)"""
-        if 1 < pol.family.min_humans and self._human_count() < pol.family.min_humans:      # (only a family with maps asks for more than one)
-            raise ValueError(f"{who}: {pol.name}'s occupancy maps need at least two humans a world")
 
     def occupancy_maps_device(self, cell_num, cell_size, channels, which="current"):
         """OM-SARL's local occupancy maps of every world's humans (cs_occupancy_maps; ``build_occupancy_maps`` for W worlds), for a network
@@ -927,15 +808,10 @@ class BatchedSocialNavGym:
             raise ValueError("occupancy_maps_device: occupancy maps need at least two humans a world")
         grid = (int(cell_num), float(cell_size), int(channels))
         dl = self._device_loop_state()
-        side, cur = dl["stream"], torch.cuda.current_stream()
-        self._stream_handshake(dl, cur, True)
-        with torch.cuda.stream(side):
+        with SideStream(dl) as s:
             nxt, cur_, _ = self._worlds_on_side_stream(dl, peek=which == "next")
-            maps = value_net.maps_of(*((nxt, 3 if self.headed_obs else 2) if which == "next" else (cur_, 2)), grid, side.cuda_stream)
-            for t in (nxt, cur_, maps):
-                if t is not None:
-                    t.record_stream(cur if t is maps else side)
-        self._stream_handshake(dl, cur, False)
+            maps = value_net.maps_of(*((nxt, 3 if self.headed_obs else 2) if which == "next" else (cur_, 2)), grid, dl.stream.cuda_stream)
+            s.inputs, s.outputs = (nxt, cur_), (maps,)
         return maps
 
     def lookahead_device(self, action_space):
@@ -952,13 +828,10 @@ class BatchedSocialNavGym:
         dl = self._device_loop_state()
         if self.cw.d_robot is None:
             raise ValueError("lookahead_device needs the robot rows")
-        side, cur_stream = dl["stream"], torch.cuda.current_stream()
-        side.wait_stream(cur_stream)
-        with torch.cuda.stream(side):               # the library launches on this stream (cw.stream); the torch ops between them follow
+        with SideStream(dl) as s:                   # the library launches on this stream (cw.stream); the torch ops between them follow
             acts = torch.as_tensor(np.asarray(action_space, dtype=np.float32) if not torch.is_tensor(action_space) else action_space,
                                    dtype=torch.float32, device="cuda").contiguous()
-            out = value_net.lookahead(acts, *self._worlds_on_side_stream(dl), self.robot_time_step, side.cuda_stream)
-        cur_stream.wait_stream(side)
+            out = s.outputs = value_net.lookahead(acts, *self._worlds_on_side_stream(dl), self.robot_time_step, dl.stream.cuda_stream)
         return out
 
     def _worlds_on_side_stream(self, dl, next_humans=None, peek=True):
@@ -972,14 +845,14 @@ class BatchedSocialNavGym:
         peek_buf = cw._buffer("peek", (W, n, 8))
         if next_humans is None and peek:
             _lib.check(lib.cs_peek(d, self.robot_time_step, peek_buf.ptr, cw.stream))
-        if "la_cols" not in dl:
+        if dl.la_cols is None:
             # next humans: (px, py, vx, vy), or (x, y, yaw, Vx, Vy, Omega) with theta / omega visible (cadrl.py:42-83) = cs_peek's first six
-            dl["la_cols"] = torch.as_tensor([0, 1, 2, 3, 4, 5] if self.headed_obs else [0, 1, 3, 4], device="cuda")
-            dl["la_robot_cols"] = torch.as_tensor([0, 1, 3, 4, 8, 10, 11, 12, 2], device="cuda")   # FullState order
-            dl["la_robot"] = cw.d_robot.torch().view(W, 13)
-        nxt = peek_buf.torch().view(W, n, 8).index_select(2, dl["la_cols"]).contiguous() if next_humans is None and peek else next_humans
-        cur = dl["state"][:, :n].index_select(2, dl["cols"]).contiguous()
-        rob = dl["la_robot"].index_select(1, dl["la_robot_cols"]).contiguous()
+            dl.la_cols = torch.as_tensor([0, 1, 2, 3, 4, 5] if self.headed_obs else [0, 1, 3, 4], device="cuda")
+            dl.la_robot_cols = torch.as_tensor([0, 1, 3, 4, 8, 10, 11, 12, 2], device="cuda")   # FullState order
+            dl.la_robot = cw.d_robot.torch().view(W, 13)
+        nxt = peek_buf.torch().view(W, n, 8).index_select(2, dl.la_cols).contiguous() if next_humans is None and peek else next_humans
+        cur = dl.state[:, :n].index_select(2, dl.cols).contiguous()
+        rob = dl.la_robot.index_select(1, dl.la_robot_cols).contiguous()
         return nxt, cur, rob
 
     # ------------------------------------------------------------------ imitation learning, W worlds at once

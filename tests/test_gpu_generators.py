@@ -225,9 +225,9 @@ def test_device_resident_step_equals_host_step_and_auto_resets():
         np.testing.assert_array_equal(rd.cpu().numpy(), rh)
         np.testing.assert_array_equal(td.cpu().numpy(), th)
         np.testing.assert_array_equal(idv.cpu().numpy(), ih)
-    np.testing.assert_array_equal(dev._dl["gtime"].cpu().numpy(), host.global_time)
+    np.testing.assert_array_equal(dev._dl.gtime.cpu().numpy(), host.global_time)
     # drive every robot straight to its goal (0, R): ReachGoal ends the episode and the world is regenerated
-    seeds0 = dev._dl["seeds"].cpu().numpy().copy()
+    seeds0 = dev._dl.seeds.cpu().numpy().copy()
     ended = np.zeros(W, bool)
     for k in range(80):
         rb = dev.cw.d_robot.torch()
@@ -238,9 +238,9 @@ def test_device_resident_step_equals_host_step_and_auto_resets():
         if ended.all():
             break
     assert ended.all()
-    seeds1 = dev._dl["seeds"].cpu().numpy()
+    seeds1 = dev._dl.seeds.cpu().numpy()
     assert np.all((seeds1 - seeds0) % W == 0) and np.all(seeds1 > seeds0)
-    fresh = (dev._dl["counter"] == 0).cpu().numpy()          # worlds regenerated in the very last step
+    fresh = (dev._dl.counter == 0).cpu().numpy()          # worlds regenerated in the very last step
     assert fresh.any()
     check = BatchedSocialNavGym(cfg, W)
     check.reset(phase="test", first_case=3, device=True)
@@ -248,7 +248,7 @@ def test_device_resident_step_equals_host_step_and_auto_resets():
     generate_worlds(check.cw, "circle_crossing", seeds1.astype(np.uint32), insert_robot=True)
     np.testing.assert_array_equal(dev.cw.get_states()[fresh], check.cw.get_states()[fresh])
     np.testing.assert_array_equal(dev.cw.get_robot()[fresh], check.cw.get_robot()[fresh])
-    assert np.all(dev._dl["gtime"].cpu().numpy()[fresh] == 0)
+    assert np.all(dev._dl.gtime.cpu().numpy()[fresh] == 0)
 
 
 def test_device_step_next_step_autoreset_mode():
@@ -265,7 +265,7 @@ def test_device_step_next_step_autoreset_mode():
     nxt = BatchedSocialNavGym(cfg, W); nxt.reset(phase="test", first_case=3, device=True)
     alive = np.ones(W, bool)                      # worlds that have not terminated yet (in either environment: same inputs)
     prev_done = np.zeros(W, bool)
-    seeds_prev = nxt._device_loop_state()["seeds"].cpu().numpy().copy()
+    seeds_prev = nxt._device_loop_state().seeds.cpu().numpy().copy()
     checked = 0
     for k in range(60):
         rb = nxt.cw.d_robot.torch()
@@ -286,15 +286,15 @@ def test_device_step_next_step_autoreset_mode():
         # (b) the step after a termination is the reset step
         if prev_done.any():
             assert np.all(r2.cpu().numpy()[prev_done] == 0) and not done2[prev_done].any() and np.all(i2.cpu().numpy()[prev_done] == 0)
-            assert np.all(nxt._dl["gtime"].cpu().numpy()[prev_done] == 0)
-            seeds_now = nxt._dl["seeds"].cpu().numpy()
+            assert np.all(nxt._dl.gtime.cpu().numpy()[prev_done] == 0)
+            seeds_now = nxt._dl.seeds.cpu().numpy()
             assert np.all(seeds_now[prev_done] == seeds_prev[prev_done] + W)     # (advanced when the episode ended)
             check = BatchedSocialNavGym(cfg, W); check.reset(phase="test", first_case=3, device=True)
             generate_worlds(check.cw, "circle_crossing", seeds_now.astype(np.uint32), insert_robot=True)
             np.testing.assert_array_equal(nxt.cw.get_states()[prev_done], check.cw.get_states()[prev_done])
             np.testing.assert_array_equal(o2[prev_done], check.observe()[prev_done])
             checked += int(prev_done.sum())
-        seeds_prev = np.where(prev_done, nxt._dl["seeds"].cpu().numpy(), seeds_prev)
+        seeds_prev = np.where(prev_done, nxt._dl.seeds.cpu().numpy(), seeds_prev)
         alive &= ~done2
         prev_done = done2
     assert checked >= W // 2, checked
@@ -826,9 +826,9 @@ def test_step_device_is_the_same_whatever_the_refill_cadence():
     for e in envs[1:]:
         np.testing.assert_array_equal(e.cw.get_states(), envs[0].cw.get_states())
         assert e.failed_resets() == 0
-    assert envs[1]._dl["depth"] == 2 and int(envs[1]._dl["epoch"].max()) > 2                   # (its staging batch really ran dry)
-    assert envs[0]._dl[("pieces", 0, "same_step")]["fold"] is not None and envs[1]._dl[("pieces", 0, "same_step")]["fold"] is None
-    assert int(envs[0]._dl["pending"].sum()) == 0                                                # nothing was ever deferred at the default cadence
+    assert envs[1]._dl.depth == 2 and int(envs[1]._dl.epoch.max()) > 2                   # (its staging batch really ran dry)
+    assert envs[0]._dl.pieces[0, "same_step"].fold is not None and envs[1]._dl.pieces[0, "same_step"].fold is None
+    assert int(envs[0]._dl.pending.sum()) == 0                                                # nothing was ever deferred at the default cadence
 
 
 @pytest.mark.parametrize("mode", [True, "next_step"])
@@ -871,18 +871,18 @@ def test_one_launch_gym_step_equals_the_two_launches(mode, W, n, steps, max_trie
             f1, f2 = one.reset_failed_mask(), two.reset_failed_mask()
             assert torch.equal(f1, f2), k
             failed_seen += int((f1 == 1).sum())
-    assert one._dl[("pieces", 0, "next_step" if mode == "next_step" else "same_step")]["fold"] is not None
+    assert one._dl.pieces[0, "next_step" if mode == "next_step" else "same_step"].fold is not None
     assert (ended >= 1).sum() >= W // 8, ended.sum()
     np.testing.assert_array_equal(one.cw.get_states(), two.cw.get_states())
     np.testing.assert_array_equal(one.cw.get_goals(), two.cw.get_goals())
     np.testing.assert_array_equal(one.cw.get_robot(), two.cw.get_robot())
     for key in ("seeds", "epoch", "counter", "gtime", "failed"):
-        assert torch.equal(one._dl[key], two._dl[key]), key
-    assert int(one._dl["pending"].sum()) == 0
+        assert torch.equal(getattr(one._dl, key), getattr(two._dl, key)), key
+    assert int(one._dl.pending.sum()) == 0
     if max_tries is None:
         assert one.failed_resets() == 0
     else:
-        fine = int(((one._dl["epoch"] > 0) & (one.reset_failed_mask() == 0)).sum())
+        fine = int(((one._dl.epoch > 0) & (one.reset_failed_mask() == 0)).sum())
         assert failed_seen > 0 and fine > 0, (failed_seen, fine)   # some staged episodes could not be generated, others could
 
 
@@ -910,7 +910,7 @@ def test_one_launch_gym_step_defers_a_take_over_whose_episode_is_not_staged_yet(
         a = (near / near.norm(dim=1, keepdim=True).clamp(min=1e-6)).contiguous()
         obs, rew, term, trunc, info = [t.clone() for t in env.step_device(a)]
         torch.cuda.synchronize()
-        pend = env._dl["pending"].cpu().numpy().astype(bool)
+        pend = env._dl.pending.cpu().numpy().astype(bool)
         failed = env.reset_failed_mask().cpu().numpy()
         done = (term | trunc).cpu().numpy()
         # a world that entered this step pending was between two episodes: nothing is reported for it
@@ -922,14 +922,14 @@ def test_one_launch_gym_step_defers_a_take_over_whose_episode_is_not_staged_yet(
         took = (done | was_pending) & ~pend
         if took.any():
             check = BatchedSocialNavGym(cfg, W); check.reset(phase="train", first_case=3, device=True)
-            generate_worlds(check.cw, "circle_crossing", env._dl["seeds"].cpu().numpy().astype(np.uint32), insert_robot=True)
+            generate_worlds(check.cw, "circle_crossing", env._dl.seeds.cpu().numpy().astype(np.uint32), insert_robot=True)
             np.testing.assert_array_equal(env.cw.get_states()[took], check.cw.get_states()[took])
             np.testing.assert_array_equal(obs.cpu().numpy()[took], check.observe()[took])
         was_pending = pend
     assert deferred_seen > 0, "the staging batch never ran dry: the test did not exercise a deferral"
-    epoch = env._dl["epoch"].cpu().numpy()
+    epoch = env._dl.epoch.cpu().numpy()
     assert np.array_equal(epoch + was_pending.astype(int), ends), (epoch, ends)          # every ended episode was followed by exactly one take-over
-    assert np.array_equal(env._dl["seeds"].cpu().numpy().astype(np.int64) - env._dl["base_seed"].cpu().numpy().astype(np.int64), ends * W)
+    assert np.array_equal(env._dl.seeds.cpu().numpy().astype(np.int64) - env._dl.base_seed.cpu().numpy().astype(np.int64), ends * W)
 
 
 @pytest.mark.parametrize("n,model,robot_row,next_step,unicycle", [(25, "hsfm_farina", False, False, False), (25, "hsfm_farina", True, True, False), (17, "sfm_guo", False, True, False),
@@ -1094,7 +1094,7 @@ def test_device_resident_step_with_a_visible_robot_equals_the_host_step(headed_o
         od, rd, td, ud, idv = dev.step_device(a)
         fresh = (td | ud).cpu().numpy()
         if fresh.any():
-            seeds = dev._dl["seeds"].cpu().numpy().astype(np.uint32)
+            seeds = dev._dl.seeds.cpu().numpy().astype(np.uint32)
             check = BatchedSocialNavGym(cfg, W, robot_visible=True, headed_obs=headed_obs)
             check.reset(phase="test", first_case=3, device=True)
             generate_worlds(check.cw, "hybrid_scenario", seeds, **check._gen_kw)

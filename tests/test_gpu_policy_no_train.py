@@ -97,7 +97,7 @@ def test_act_device_equals_w1_predict_bit_for_bit(n):
         act = env.act_device(name).cpu().numpy().copy()
         assert np.all(np.isfinite(act))
         robot = env.cw.d_robot.download()
-        obs = env._dl["obs"].cpu().numpy()
+        obs = env._dl.obs.cpu().numpy()
         pol = policy_factory[name]()
         pol.time_step = env.robot_time_step
         for w in rows:
@@ -128,7 +128,7 @@ def test_act_step_loop_reads_the_current_observation(policy, visible):
     for k in range(200):
         act = env.act_device(pol)
         assert act is env.action_buffer()
-        obs = env._dl["obs"].clone()
+        obs = env._dl.obs.clone()
         rob = env.cw.d_robot.torch().view(env.W, 13).clone()
         np.testing.assert_array_equal(obs.cpu().numpy(), env.observe_device().cpu().numpy())     # the observation of the resident rows
         check = torch.empty_like(act)
@@ -136,7 +136,7 @@ def test_act_step_loop_reads_the_current_observation(policy, visible):
                    check.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
         np.testing.assert_array_equal(act.cpu().numpy(), check.cpu().numpy())
         if act_prev is not None:
-            kept = (env._dl["counter"] != 0).cpu().numpy()       # worlds that were not reset by the previous step
+            kept = (env._dl.counter != 0).cpu().numpy()       # worlds that were not reset by the previous step
             np.testing.assert_array_equal(rob.cpu().numpy()[kept][:, 3:5], act_prev[kept])
         act_prev = act.cpu().numpy().copy()
         _, _, term, trunc, _ = env.step_device(env.action_buffer())

@@ -41,9 +41,9 @@ def _buffers(env, ret):
     dl = env._dl
     obs, reward, term, trunc, info = ret
     return dict(crowd_rows=env.cw.d_state.torch(), goals=env.cw.d_goals.torch(), robot_rows=env.cw.d_robot.torch(), observation=obs,
-                reward=reward, terminated=term, truncated=trunc, info=info, reward_row=dl["out"], reset_failed_mask=env.reset_failed_mask(),
-                action_buffer=env.action_buffer(), counter=dl["counter"], seeds=dl["seeds"], global_time=dl["gtime"], epoch=dl["epoch"],
-                pending=dl["pending"])
+                reward=reward, terminated=term, truncated=trunc, info=info, reward_row=dl.out, reset_failed_mask=env.reset_failed_mask(),
+                action_buffer=env.action_buffer(), counter=dl.counter, seeds=dl.seeds, global_time=dl.gtime, epoch=dl.epoch,
+                pending=dl.pending)
 
 
 def _words(t):
@@ -124,7 +124,7 @@ def test_one_call_equals_act_then_step_bit_for_bit_96_worlds(policy, n, crowd, v
     _STEPS_RUN[(n, crowd, visible, mode)] = _STEPS_RUN.get((n, crowd, visible, mode), 0) + STEPS
     if _STEPS_RUN[(n, crowd, visible, mode)] == STEPS * len(POLICIES):
         # the pair has been through the five policies: episodes ended on the way and staged episodes were taken over -- part of what was compared
-        assert int(one._dl["epoch"].sum().item()) > 0 and torch.equal(one._dl["epoch"], two._dl["epoch"])
+        assert int(one._dl.epoch.sum().item()) > 0 and torch.equal(one._dl.epoch, two._dl.epoch)
         two.close()
         one.close()
         del _PAIRS[(n, crowd, visible, mode)]
@@ -140,7 +140,7 @@ def test_one_call_equals_act_then_step_bit_for_bit_4096_worlds(policy, n, crowd,
         if n == 25:
             assert "OCC=1" in one.act_step_variant(), one.act_step_variant()     # two wavefronts per SIMD: the one-wave register budget
         ended = _run_pair(two, one, policy, policy, mode, f"4096 worlds {policy} n={n} {crowd} visible={visible} {mode}")
-        assert ended > 0 and int(one._dl["epoch"].sum().item()) > 0
+        assert ended > 0 and int(one._dl.epoch.sum().item()) > 0
         print(f"4096 worlds {policy} n={n} {crowd} visible={visible} {mode}: {ended} episodes ended, variant {one.act_step_variant()}")
     finally:
         two.close()

@@ -95,7 +95,7 @@ def test_shards_stay_the_single_process_batch_across_auto_resets():
     for s in shards:
         s.reset(phase="val", first_case=5, device=True)
     assert [(s.first, s.W) for s in shards] == [(0, 19), (19, 18)] and all(s.env.seed_stride == TOTAL for s in shards)
-    seeds0 = full._device_loop_state()["seeds"].cpu().numpy().copy()
+    seeds0 = full._device_loop_state().seeds.cpu().numpy().copy()
     ended = np.zeros(TOTAL, int)
     for k in range(90):
         rb = full.cw.d_robot.torch().view(TOTAL, 13)
@@ -107,7 +107,7 @@ def test_shards_stay_the_single_process_batch_across_auto_resets():
             assert torch.equal(torch.cat([g[j] for g in got], 0), r), (k, j)
         ended += (ref[2] | ref[3]).cpu().numpy().astype(int)
     assert (ended >= 2).all(), ended
-    seeds = np.concatenate([s._dl["seeds"].cpu().numpy() for s in shards])
-    np.testing.assert_array_equal(seeds, full._dl["seeds"].cpu().numpy())
+    seeds = np.concatenate([s._dl.seeds.cpu().numpy() for s in shards])
+    np.testing.assert_array_equal(seeds, full._dl.seeds.cpu().numpy())
     np.testing.assert_array_equal(seeds, seeds0 + TOTAL * ended)                       # world w walks s + w + k * total_worlds
     np.testing.assert_array_equal(np.concatenate([s.cw.get_states() for s in shards]), full.cw.get_states())

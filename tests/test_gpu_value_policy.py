@@ -368,7 +368,7 @@ def test_act_step_loop_reads_the_current_observation(name, query_env):
             np.testing.assert_array_equal(v.cpu().numpy(), values.cpu().numpy())
             np.testing.assert_array_equal(a.cpu().numpy(), act.cpu().numpy())
         if act_prev is not None:
-            kept = (env._dl["counter"] != 0).cpu().numpy()
+            kept = (env._dl.counter != 0).cpu().numpy()
             np.testing.assert_array_equal(rob.cpu().numpy()[kept][:, 3:5], act_prev[kept])
         act_prev = act.cpu().numpy().copy()
         distinct.update(int(c) for c in choice.cpu().numpy())

@@ -31,13 +31,13 @@ if sys.argv[1] == "run":
     with torch.cuda.stream(env.device_stream()):
         for rep in range(REPS):
             for k in COUNTS:
-                dl["mask"].zero_()
+                dl.mask.zero_()
                 if k:
                     idx = torch.randperm(4096, device="cuda", generator=g)[:k]
-                    dl["mask"][idx] = 1
-                    dl["seeds"][idx] += dl["stride"]          # what the bookkeeping of the step does for a finished world
+                    dl.mask[idx] = 1
+                    dl.seeds[idx] += dl.stride          # what the bookkeeping of the step does for a finished world
                 torch.cuda.synchronize()
-                _lib.check(lib.cs_consume_staged_worlds(*c["tail"]))
+                _lib.check(lib.cs_consume_staged_worlds(*c.tail))
                 torch.cuda.synchronize()
     assert env.failed_resets() == 0
     sys.exit(0)

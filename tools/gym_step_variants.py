@@ -34,6 +34,6 @@ for every, depth, mode, prio in VARIANTS:
         torch.cuda.synchronize()
         el = (time.perf_counter() - t0) / 400 * 1e6
     dl = env._dl
-    stale = int((dl["epoch"] > 0).sum())
-    print(f"prio {prio} refill every {every:>10d} depth {depth:3d} mode {str(mode):9s}: {el:6.1f} us per step; worlds that ended {stale}, max epoch {int(dl['epoch'].max())}, failed {env.failed_resets()}")
+    stale = int((dl.epoch > 0).sum())
+    print(f"prio {prio} refill every {every:>10d} depth {depth:3d} mode {str(mode):9s}: {el:6.1f} us per step; worlds that ended {stale}, max epoch {int(dl.epoch.max())}, failed {env.failed_resets()}")
     del env

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-side cost of the pieces of BatchedSocialNavGym._maybe_refill inside a running device loop (us per call)."""
+"""Host-side cost of the pieces of DeviceLoop.maybe_refill inside a running device loop (us per call)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -35,11 +35,11 @@ with torch.cuda.stream(env.device_stream()):
         t0 = time.perf_counter(); env.step_device(buf); t1 = time.perf_counter()
         T["graph"].append(t1 - t0)
         if k % 4 == 3:
-            t0 = time.perf_counter(); d = dl["refill_ev"].done(); t1 = time.perf_counter()
+            t0 = time.perf_counter(); d = dl.refill_ev.done(); t1 = time.perf_counter()
             T["query"].append(t1 - t0)
             if d:
-                t0 = time.perf_counter(); _lib.check(lib.cs_refill_staged_worlds(*dl["refill_args"])); t1 = time.perf_counter()
-                dl["refill_ev"].record(dl["stream_b"]); t2 = time.perf_counter()
+                t0 = time.perf_counter(); _lib.check(lib.cs_refill_staged_worlds(*dl.refill_args)); t1 = time.perf_counter()
+                dl.refill_ev.record(dl.stream_b); t2 = time.perf_counter()
                 T["launch"].append(t1 - t0); T["record"].append(t2 - t1)
     torch.cuda.synchronize()
     print("per step %.1f us" % ((time.perf_counter() - t_all) / 400 * 1e6))
