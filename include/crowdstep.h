@@ -535,7 +535,26 @@ int cs_policy_no_train(int policy, int W, int n, const float* d_robot13, const f
                        const float* params /* host, CS_PNT_N_PARAMS floats */, float* d_action, void* stream);
 
 /*
- * cs_gym_step_policy  cs_policy_no_train followed by cs_gym_step -- `action = robot.act(ob); ob, reward, done, info = env.step(action)`, the
+ * cs_policy_orca  the CrowdNav ORCA robot policy (crowd_nav/policy_no_train/orca.py:82-132, ORCA.predict) for the robots of W worlds in
+ *   one launch: one doStep of a fresh RVO2 simulator in which the robot is agent 0 and human j agent j + 1, of which only agent 0's new
+ *   velocity is read.  d_robot13 / d_obs / obs_cols / d_action as cs_policy_no_train's.  Agent 0 has radius `radius + margin` and
+ *   maxSpeed v_pref; human j has radius `radius_j + margin` (margin = float32(0.01 + safety_space), added in float32).  Preferred
+ *   velocity: d = goal - position, s = sqrt(d.x * d.x + d.y * d.y), d / s where s > 1 (strict; an IEEE division), d otherwise.
+ *   Neighbours: the humans with distSq < neighbor_dist^2 (strict), the first max_neighbors of them in ascending (distSq, index) order --
+ *   the list RVO2's insertion leaves after a walk in index order; one half-plane each in that order (a colliding pair uses
+ *   1 / time_step instead of 1 / time_horizon), linearProgram2, linearProgram3 where that is infeasible.  Exact arithmetic only (IEEE
+ *   divide and square root, no contraction): bit for bit what oracle/orca_oracle.c computes for agent 0, for a world alone (W = 1) and
+ *   in any batch.  Parity with the rvo2 library itself is unpinned, as for every ORCA path here.  One launch of
+ *   k_policy_orca on `stream` (a wavefront per world, lanes over humans); only d_action is written.
+ *   Errors (CS_ERR_ARG with a message, before any device call): W < 1, n < 0, obs_cols not 5 or 7, a null d_robot13 or d_action, a null
+ *   d_obs with n > 0, time_step <= 0, time_horizon <= 0, neighbor_dist < 0, max_neighbors outside 0..10 (the kernel keeps at most ten
+ *   neighbours; the reference's value is 10).
+ */
+int cs_policy_orca(int W, int n, const float* d_robot13, const float* d_obs, int obs_cols, float time_step, float neighbor_dist,
+                   int max_neighbors, float time_horizon, float margin, float* d_action, void* stream);
+
+/*
+ * cs_gym_step_policycs_policy_no_train followed by cs_gym_step -- `action = robot.act(ob); ob, reward, done, info = env.step(action)`, the
  *   seam of Explorer.run_k_episodes (crowd_nav/utils/explorer.py:57-58) with a robot of crowd_nav/policy_no_train/ (*.py) -- in ONE launch: the
  *   step kernel's prologue decides every world's ActionXY from the rows it has loaded (the robot row of cs_worlds.d_robot and the humans'
  *   state rows: the values cs_policy_no_train reads from d_robot13 and from the observation rows), BEFORE the Gym head, the swept collision

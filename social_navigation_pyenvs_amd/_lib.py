@@ -153,6 +153,7 @@ ABI = {
     "cs_gym_step_is_one_launch": (I, [WORLDS]),
     "cs_gym_step_staged": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, GEN, WORLDS, STAGE_BOOK, P]),
     "cs_policy_no_train": (I, [I, I, I, P, P, I, F, P, P, P]),
+    "cs_policy_orca": (I, [I, I, P, P, I, F, F, I, F, F, P, P]),
     "cs_gym_step_policy": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, I, F, P, P]),
     "cs_gym_step_staged_policy": (I, [WORLDS, F, I, P, F, P, P, P, GYM_BOOK, I, P, GEN, WORLDS, STAGE_BOOK, I, F, P, P]),
     "cs_gym_step_policy_variant": (I, [WORLDS, P, Z]),

@@ -1,7 +1,9 @@
 """policy_factory with the reference's keys (crowd_nav/policy_no_train/policy_factory.py).
 
-'orca' and 'socialforce' need rvo2 / socialforce, which this project does not ship and nothing here can pin them against; the 'hsfm_*'
-policies fail inside the reference itself (FullState has no 'w': hsfm_farina.py:61; their ActionXYW would then fail
+'socialforce' needs the socialforce library, which this project does not ship and nothing here can pin it against.  'orca' needs rvo2 in
+the reference; its decision runs here as crowd_nav.policy.policy_factory["orca_device"] (orca.py, csrc/policy_orca.hip), pinned bit for bit on
+the project's float32 restatement of RVO2 -- parity with the third-party library itself stays unpinned, as for every ORCA
+path here -- and this factory's 'orca' key keeps raising, with a pointer there.  The 'hsfm_*' policies fail inside the reference itself (FullState has no 'w': hsfm_farina.py:61; their ActionXYW would then fail
 RobotAgent.check_validity) -- tests/golden/g18_policy_no_train.npz records that exception.  Those keys raise NotImplementedError."""
 from .blind_planner import BlindPlanner
 from .sfm_guo import SFMGuo
@@ -30,7 +32,8 @@ policy_factory = dict()
 policy_factory["none"] = none_policy
 policy_factory["bp"] = BlindPlanner
 policy_factory["ssp"] = SimpleSocialPlanner
-policy_factory["orca"] = _unsupported("orca", _NO_LIBRARY.format("rvo2"))
+policy_factory["orca"] = _unsupported("orca", "under this key it needs the rvo2 library, which is not part of this project; the same decision on the "
+                                               "project's float32 restatement of RVO2 is crowd_nav.policy.policy_factory[\"orca_device\"]")
 policy_factory["socialforce"] = _unsupported("socialforce", _NO_LIBRARY.format("socialforce"))
 policy_factory["sfm_helbing"] = SFMHelbing
 policy_factory["sfm_guo"] = SFMGuo

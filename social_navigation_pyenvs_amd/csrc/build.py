@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(PKG, "libcrowdstep.so")
 MANIFEST_PATH = LIB_PATH + ".manifest.json"
 OBJ_DIR = os.path.join(CSRC, ".build")
 SOURCES = ["crowdstep.hip", "sfmstep_generic.hip", "sfmstep_leanrt.hip", "sfmstep_lean25.hip", "sfmstep_lean30.hip", "sfmstep_small.hip", "sfmstep_lean50.hip", "sfmstep_robot26.hip", "sfmstep_robotx.hip", "sfmstep_imit.hip", "sfmstep_peragent.hip", "sfmstep_policy.hip", "sfmstep_policy_robot.hip", "orca.hip", "lookahead.hip", "generate.hip", "laser.hip", "social_momentum.hip", "robot_model.hip",
-           "rk45.hip", "rowstep.hip", "gymstep.hip", "bigworld.hip", "policy_no_train.hip", "value_net.hip", "value_net_bf16.hip", "value_net_worlds.hip", "value_net_state.hip", "value_net_grad.hip", "value_net_lstm_grad.hip", "value_net_om.hip", "value_net_lstm.hip", "value_net_lstm_bf16.hip", "value_net_lstm_om_bf16.hip", "occupancy_map.hip", "sfmstep_f64.hip", "episodes.hip", "value_net_om_bf16.hip", "value_net_lstm_worlds.hip", "value_net_lstm_worlds_bf16.hip"]
+           "rk45.hip", "rowstep.hip", "gymstep.hip", "bigworld.hip", "policy_no_train.hip", "policy_orca.hip", "value_net.hip", "value_net_bf16.hip", "value_net_worlds.hip", "value_net_state.hip", "value_net_grad.hip", "value_net_lstm_grad.hip", "value_net_om.hip", "value_net_lstm.hip", "value_net_lstm_bf16.hip", "value_net_lstm_om_bf16.hip", "occupancy_map.hip", "sfmstep_f64.hip", "episodes.hip", "value_net_om_bf16.hip", "value_net_lstm_worlds.hip", "value_net_lstm_worlds_bf16.hip"]
 ARCH = "gfx950"
 # -fno-slp-vectorize: v_pk_*_f32 has no throughput advantage over two scalar ops on gfx950 (measured,
 # tools/valu_microbench.hip) and packing costs ~2 v_mov per partner in the pair loop

@@ -558,6 +558,35 @@ class BatchedSocialNavGym:
             b = bound[key] = dict(step=step, act=act, keep=prm)
         return b
 
+    @staticmethod
+    def _is_orca_policy(policy):
+        """``policy`` asks for the ORCA robot of crowd_nav/policy_no_train/orca.py: an instance, or its key in the combined factory."""
+        from ..crowd_nav.policy_no_train.orca import ORCA
+
+        return isinstance(policy, ORCA) or (isinstance(policy, str) and policy == "orca_device")
+
+    def _orca_policy(self, policy, who, explore=None):
+        """The ORCA policy behind ``"orca_device"`` or an instance, with the no-train policies' refusals -- made before anything touches the
+        device (``who`` asks)."""
+        if explore is not None:
+            raise ValueError(f"{who}: explore= belongs to the value-based policies (CADRL, SARL)")
+        if isinstance(policy, str):
+            from ..crowd_nav.policy_no_train.orca import ORCA
+
+            policy = ORCA()                      # (the class's constants: no state, no device)
+        if policy.kinematics != "holonomic" or (self.cw is not None and self.cw.unicycle):
+            raise ValueError(f"{who}: the ORCA policy acts in ActionXY and needs a holonomic robot")
+        if self.cw is not None and self.cw.d_robot is None:
+            raise ValueError(f"{who} needs the robot rows")
+        return policy
+
+    def _orca_launch(self, dl, pol):
+        """One launch of cs_policy_orca for the W resident worlds on the device stream (called inside its scope): the decision is one library call."""
+        from ..crowd_nav.policy_no_train.orca import launch
+
+        launch(self.W, self.n, self.cw.d_robot.ptr, dl.obs.data_ptr(), dl.obs.shape[2], self.robot_time_step if pol.time_step is None else pol.time_step,
+               pol.neighbor_dist, pol.max_neighbors, pol.time_horizon, pol.safety_space, dl.act.data_ptr(), dl.stream.cuda_stream)
+
     def _observe_if_stale(self, dl):
         """No step since the batch was generated: the observation of the resident rows (what a decision in a launch of its own reads)."""
         if dl.obs_fresh:
@@ -632,7 +661,19 @@ class BatchedSocialNavGym:
         ``set_recurrent_precision("bf16")``; after its ``set_recurrent_input("fused")``, cs_peek -> cs_value_net_decide_lstm_worlds[_bf16] alone,
         which allocates no look-ahead tensor); an OM-LSTM-RL instance (``policy_factory["om_lstm_rl"]``) both:
         the maps of the next humans, then cs_value_net_decide_lstm_om with the policy's map order (cs_value_net_decide_lstm_om_bf16 after the
-        policy's ``set_mapped_precision("bf16")``)."""
+        policy's ``set_mapped_precision("bf16")``).
+
+        An ``ORCA`` instance (crowd_nav/policy_no_train/orca.py) or the name ``"orca_device"`` -- its key in crowd_nav.policy.policy_factory --
+        decides with one launch of cs_policy_orca instead (csrc/policy_orca.hip: one RVO2 doStep for agent 0, a wavefront per world), with the
+        same inputs, the same output buffer and the same refusals as the no-train policies; the policy's ``time_step`` (None: the robot time
+        step) is the simulator's.  The no-train factory's ``"orca"`` keeps raising NotImplementedError."""
+        if self._is_orca_policy(policy):
+            pol = self._orca_policy(policy, "act_device", explore)      # (refused before anything touches the device)
+            dl = self._device_loop_state()
+            with SideStream(dl):
+                self._observe_if_stale(dl)
+                self._orca_launch(dl, pol)
+            return dl.act
         if not isinstance(policy, str):
             from ..crowd_nav.policy.cadrl import CADRL
 
@@ -654,8 +695,21 @@ class BatchedSocialNavGym:
         takes it (a name of policy_factory or an instance of its classes).  Returns what ``step_device`` returns and leaves the decided
         actions in ``action_buffer()``; runs on ``device_stream()``, nothing crosses to the host.  Bit for bit the results of the two
         calls.  The other crowds (ORCA, social momentum, walls, the smallest worlds) run the decision kernel and the step's launches
-        inside the same call.  A CADRL / SARL instance decides in milliseconds and gains nothing here: ``act_device``, then ``step_device``."""
+        inside the same call.  A CADRL / SARL instance decides in milliseconds and gains nothing here: ``act_device``, then ``step_device``.
+        An ``ORCA`` instance or ``"orca_device"`` (see ``act_device``) takes the second form for every crowd: no step build decides ORCA in
+        its head, so the decision launch (cs_policy_orca) and the plain step run behind each other inside one stream scope and one call."""
         from ..crowd_nav.policy_no_train.policy import NoTrainPolicy
+
+        if self._is_orca_policy(policy):
+            pol = self._orca_policy(policy, "act_step_device")          # (refused before anything touches the device)
+            dl = self._device_loop_state()
+            c = self._open_step(dl, auto_reset)
+            with SideStream(dl):
+                self._observe_if_stale(dl)
+                self._orca_launch(dl, pol)
+                self._issue_step(dl, c)
+            dl.obs_fresh = True
+            return c.results
 
         if not isinstance(policy, (str, NoTrainPolicy)):   # (refused before anything touches the device)
             raise TypeError(f"act_step_device takes a no-train policy (bp, ssp, sfm_helbing, sfm_guo, sfm_moussaid), not {policy!r}: "
